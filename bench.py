@@ -20,6 +20,11 @@ RANK / LOCAL_RANK / WORLD_SIZE from the environment.  ``--dry`` runs the same
 launcher / shard / gather / timing / JSON code on CPU tensors over gloo with a
 stub step (no kernel runs; covered by tests/test_dist_cpu.py).
 
+``--dump-outputs DIR`` writes what the last timed step of the headline leg
+returned (det / link / new / end scores of its pairs, float32 .npy, at most
+64 MB) to DIR.  The inputs and weights are seeded, so two builds run with the
+same arguments can be compared output for output.
+
 Arithmetic legs.  The headline (``value``, ``dtype``, ``roofline``) is the
 ``--trunk`` mode, by default ``f16x3`` - the fp32-class arithmetic (3-term fp16
 hi/lo split, 22 significand bits, score error ~3e-5 against the fp32 reference).
@@ -395,9 +400,15 @@ def parse_args(argv=None):
     ap.add_argument('--detail', default='stderr', choices=['stderr', 'stdout', 'none'],
                     help='where the full record goes as ONE line prefixed "BENCH_DETAIL " (always also written to '
                          'gpurun_out/bench_detail_n<N>.json); stdout carries the compact line last either way')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the results of the last timed step of the headline leg to DIR/<name>.npy (float32, at most '
+                         '64 MB: a fixed sample of the pairs above that); the inputs are seeded, the same on every run')
     ap.add_argument('--dry', action='store_true',
                     help='CPU / gloo dry run of the launcher, sharding, gather, timing and JSON with a stub step')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1 (the timed steps of every leg)')
+    return args
 
 
 def relaunch_under_torchrun(args):
@@ -540,6 +551,31 @@ def time_steps(step, steps, barrier):
         res = step()
     barrier()
     return time.perf_counter() - t0, res
+
+
+DUMP_LIMIT = 64 * 2 ** 20  # bytes --dump-outputs may write
+
+
+def dump_outputs(res, out_dir, limit=DUMP_LIMIT):
+    """--dump-outputs: the per-pair results of one step, as a caller of forward_batch receives them, stacked over the
+    pairs into float32 arrays DIR/det.npy, new.npy, end.npy [pairs, rows, L] and link<f>.npy [pairs, rows, N, M], with
+    DIR/pair_index.npy (float64) naming the pairs of the step they hold.  A step above ``limit`` bytes is cut to a fixed
+    sample of its pairs (seeded: the same pairs on every run)."""
+    n = len(res)
+    det, links, new, end = res[0]
+    per_pair = 4 * (det.numel() + sum(l.numel() for l in links) + new.numel() + end.numel()) + 8
+    budget = limit - 128 * (4 + len(links))  # the .npy headers
+    keep = np.arange(n)
+    if n * per_pair > budget:
+        keep = np.sort(np.random.default_rng(0).choice(n, budget // per_pair, replace=False))
+    pick = lambda f: np.stack([f(res[i]).detach().float().cpu().numpy() for i in keep])
+    arrays = {'pair_index': keep.astype(np.float64), 'det': pick(lambda r: r[0]), 'new': pick(lambda r: r[2]),
+              'end': pick(lambda r: r[3])}
+    for j in range(len(links)):
+        arrays['link%d' % j] = pick(lambda r: r[1][j])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def max_over_ranks(dt, world, dev):
@@ -965,6 +1001,8 @@ def main():
         for _ in range(args.warmup):
             step()
         dt_own, res = time_steps(step, args.steps, barrier)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(res, args.dump_outputs)
         dt = max_over_ranks(dt_own, world, dev)
         mine = dict(ms_per_step=round(dt_own / args.steps * 1e3, 3), pairs=hi - lo, first_pair=lo, gather_us_per_step=None,
                     sclk_mhz=None, sclk_vs_solo=None, power_w=None, **place)
@@ -1043,8 +1081,9 @@ def main():
                     G=total if total is not None else Bw * world,
                     shape=(N_, M_, S_, pts_, fusion_), input_mb=round(len(sets) * set_bytes / 2 ** 20, 1))
 
-    def run_leg(wl, trunk, steps, warmup, graph=False, profile=False):
-        """W warm-up steps, then exactly K timed steps between barrier + synchronize brackets, max over ranks."""
+    def run_leg(wl, trunk, steps, warmup, graph=False, profile=False, dump=None):
+        """W warm-up steps, then exactly K timed steps between barrier + synchronize brackets, max over ranks.  ``dump``:
+        directory the results of the last timed step go to (rank 0), before any later step can overwrite them."""
         mdl, plan_, sets = wl['model'], wl['plan'], wl['sets']
         mdl.set_trunk(trunk)
         eng = mdl.engine()
@@ -1095,6 +1134,8 @@ def main():
         with telemetry:
             dt, res = time_steps(step, steps, barrier)
         tele = telemetry.result()
+        if dump and rank == 0:
+            dump_outputs(res, dump)
         events, eng.conv_events = eng.conv_events, None
         dt_own = dt
         dt = max_over_ranks(dt, world, dev)
@@ -1178,7 +1219,8 @@ def main():
     model, ins = head_wl['model'], head_wl['ins']
     do_prof = not args.no_profile
     kernels = {}
-    head, res, layers = run_leg(head_wl, args.trunk, args.steps, args.warmup, graph=args.graph, profile=do_prof)
+    head, res, layers = run_leg(head_wl, args.trunk, args.steps, args.warmup, graph=args.graph, profile=do_prof,
+                                dump=args.dump_outputs)
     if 'kernels' in head:
         kernels['headline_%s_%s' % (args.workload, args.trunk)] = head.pop('kernels')
     value = head['value']

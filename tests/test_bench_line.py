@@ -95,3 +95,36 @@ def test_dry_run_prints_one_bounded_line_and_the_detail_record(tmp_path):
     lines = p.stdout.splitlines()
     assert len(lines) == 2 and lines[0].startswith('BENCH_DETAIL ')
     _check(b, lines[1])
+
+
+def test_dump_outputs_writes_the_last_timed_step_the_same_on_every_run(tmp_path):
+    """--dump-outputs: the gathered results of the last timed step as float32 .npy files, identical over two runs with
+    the same arguments; a step above the size limit is cut to a seeded sample of its pairs that fits."""
+    import numpy as np
+    b = _bench()
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    dirs = [tmp_path / 'a', tmp_path / 'b']
+    for d in dirs:
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry', '--workload', 'tiny', '--steps', '3',
+                            '--warmup', '1', '--pairs', '4', '--detail', 'none', '--dump-outputs', str(d)],
+                           capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert json.loads(p.stdout.splitlines()[-1])['steps'] == 3
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ['det.npy', 'end.npy', 'link0.npy', 'new.npy', 'pair_index.npy']
+    for n in names:
+        x, y = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    stub = b.stub_results(4, 6, 5, 1000)  # what the dry run's step returns for pairs 0..3 of the tiny workload
+    assert np.array_equal(np.load(dirs[0] / 'pair_index.npy'), np.arange(4.0))
+    assert np.array_equal(np.load(dirs[0] / 'link0.npy'), np.stack([r[1][0].numpy() for r in stub]))
+    assert np.array_equal(np.load(dirs[0] / 'end.npy'), np.stack([r[3].numpy() for r in stub]))
+
+    res = b.stub_results(40, 6, 5, 1000)
+    limit = 8000
+    for d in ('s1', 's2'):
+        b.dump_outputs(res, str(tmp_path / d), limit=limit)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= limit
+    idx = np.load(tmp_path / 's1' / 'pair_index.npy')
+    assert np.array_equal(idx, np.load(tmp_path / 's2' / 'pair_index.npy')) and 1 < len(idx) < 40
+    assert np.array_equal(np.load(tmp_path / 's1' / 'det.npy'), np.stack([res[int(i)][0].numpy() for i in idx]))
