@@ -25,6 +25,31 @@ from .ops import (ACT_NONE, ACT_RELU, ACT_SIGMOID, A_NORM_RELU, A_PAIR, A_PLAIN,
 EPS = 1e-5  # nn.GroupNorm / nn.BatchNorm default used everywhere in the reference
 
 
+def check_crop_side(S):
+    if S < 32 or S % 2 != 0:
+        # five 2x2 poolings: a 32-pixel crop ends in a 1 x 1 map.  Sides that are not a multiple of 32 give odd maps
+        # on the way down, floored by every pooling like nn.MaxPool2d(2, 2) (reference modules/vgg.py:72) - e.g.
+        # 100 -> 50 -> 25 -> 12 -> 6 -> 3.  The first layer (NCHW crops, fused conv1_1 + conv1_2 + pool) wants an
+        # even side; the reference's dataset resizes every crop to 224 (dataset/test_seq_dataset.py:218).
+        raise ValueError('crop side %d is not supported: the HIP VGG trunk needs an even side >= 32; resize the crops '
+                         '(mmmot_amd.crops.crop_resize_normalize)' % S)
+
+
+def check_crop_layout(dets):
+    """Host check of the crops of a reference-shaped call, before anything is queued: the normalised fp32 [L,3,S,S]
+    tensor or the uint8 [L,S,S,3] crops of the resize (mmmot_amd.crops.crop_resize_u8) with an even side >= 32.
+    Returns the side S."""
+    if dets.dtype == torch.uint8:
+        if dets.dim() != 4 or dets.shape[3] != 3 or dets.shape[1] != dets.shape[2]:
+            raise ValueError('uint8 crops must be [L,S,S,3] (HWC, the output of mmmot_amd.crops.crop_resize_u8), got %s'
+                             % (tuple(dets.shape),))
+        S = int(dets.shape[1])
+    else:
+        S = int(dets.shape[-1])
+    check_crop_side(S)
+    return S
+
+
 class Engine:
     def __init__(self, packed, ops, fusion='A', affinity_op='multiply', softmax_mode='none',
                  neg_threshold=0.0, score_arch='branch_cls', end_mode='avg', trunk=None):
@@ -166,13 +191,7 @@ class Engine:
     def appearance(self, plan, crops, cat):
         """crops [Lt,3,S,S] NCHW (reference contract) -> cat[:, 0:512]."""
         ops, Lt, S = self.ops, plan.Lt, plan.S
-        if S < 32 or S % 2 != 0:
-            # five 2x2 poolings: a 32-pixel crop ends in a 1 x 1 map.  Sides that are not a multiple of 32 give odd maps
-            # on the way down, floored by every pooling like nn.MaxPool2d(2, 2) (reference modules/vgg.py:72) - e.g.
-            # 100 -> 50 -> 25 -> 12 -> 6 -> 3.  The first layer (NCHW crops, fused conv1_1 + conv1_2 + pool) wants an
-            # even side; the reference's dataset resizes every crop to 224 (dataset/test_seq_dataset.py:218).
-            raise ValueError('crop side %d is not supported: the HIP VGG trunk needs an even side >= 32; resize the crops '
-                             '(mmmot_amd.crops.crop_resize_normalize)' % S)
+        check_crop_side(S)
         if Lt * S * S * 16 >= 2 ** 31 - 64:
             # the trunk kernels address activations with 32-bit offsets in 16-byte pieces (largest tensor: L x S x S x 64)
             raise ValueError('%d crops of %dx%d in one launch sequence exceed the 32-bit piece offsets of the trunk kernels '
@@ -669,6 +688,7 @@ class Engine:
         if not (ok_f32 or ok_u8) or not crops.is_contiguous():
             raise ValueError('crops must be a contiguous fp32 [%d,3,%d,%d] tensor (the reference\'s normalised `dets`) or '
                              'the uint8 [%d,%d,%d,3] crops of the resize' % (Lt, plan.S, plan.S, Lt, plan.S, plan.S))
+        check_crop_side(plan.S)  # here, before any launch (appearance() repeats it for its direct callers)
 
     def image_first(self, plan, crops):
         """Issue the image branch (trunk + SkipPool heads -> the appearance half of `cat`) of the NEXT ``forward`` now.

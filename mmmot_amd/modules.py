@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import torch_ops
-from .engine import Engine
+from .engine import Engine, check_crop_layout
 from .pack import VGG_STAGES, pack_weights
 from .plan import BatchPlan
 
@@ -680,7 +680,12 @@ class TrackingNet(nn.Module):
         need_img = (0 in rows) or (2 in rows)
         # dets: the reference's normalised fp32 [L,3,S,S] crops, or the uint8 [L,S,S,3] crops of the resize
         # (mmmot_amd.crops.crop_resize_u8): ToTensor / Normalize then happen inside the first trunk launch
-        S = (int(dets.shape[1]) if dets.dtype == torch.uint8 else int(dets.shape[-1])) if dets is not None else 0
+        # (checked on the host before anything is queued: a wrong layout or side must not reach the D2H copy of the point
+        # split or the trunk of Engine.image_first)
+        if need_img and dets is not None:
+            S = check_crop_layout(dets)
+        else:
+            S = (int(dets.shape[1]) if dets.dtype == torch.uint8 else int(dets.shape[-1])) if dets is not None else 0
         ps = None
         points = None
         crops = dets.contiguous() if need_img else None

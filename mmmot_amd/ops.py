@@ -266,7 +266,9 @@ class HipOps:
         _lib.check(st, 'mmmot_pn_mlp64')
 
     def gram_rows(self, X, K, sc, sh, tiles, Gout, Sout):
-        """Per super-tile Gram matrix / column sums (float64) of relu(X*sc+sh); see mmmot_gram_rows."""
+        """Per super-tile Gram matrix / column sums (float64) of relu(X*sc+sh); see mmmot_gram_rows.  K = 128: only the
+        32 x 32 blocks on and above the block diagonal of Gout are written (the lower ones keep what the buffer held);
+        gn_finalize_gram(_dbias) reads those blocks only."""
         st = self.lib.mmmot_gram_rows(_ptr(X), _ld(X), K, _ptr(sc), _ptr(sh), _ld(sc), _iptr(tiles.row0),
                                       _iptr(tiles.nrows), _iptr(tiles.group), tiles.T,
                                       _ptr(Gout, torch.float64), _ptr(Sout, torch.float64), self._stream())

@@ -327,6 +327,11 @@ def forward_train(model, dets, det_info, dets_split):
     """``TrackingNet.forward`` in training mode (reference modules/tracking_net.py:165-193 with ``self.training``):
     returns (det_scores 3 x L raw, [link_scores 3 x N x M ...], new_scores 3 x (L - N_first), end_scores 3 x (L - N_last),
     trans) on the autograd graph of every parameter (``model.freeze_appearance = True`` keeps the image encoder out)."""
+    if dets.dtype == torch.uint8:
+        # the training trunk (train_vgg.py) reads the normalised fp32 [L,3,S,S] crops only; checked before anything is
+        # queued (an 8-bit [L,S,S,3] tensor would otherwise be taken for crops of side 3)
+        raise ValueError('the training-mode forward takes the normalised fp32 [L,3,S,S] crops, not uint8 crops: apply '
+                         'ToTensor + Normalize first (mmmot_amd.crops.crop_resize_normalize)')
     from . import torch_ops
     from .plan import BatchPlan
     fc = [int(d.item()) if torch.is_tensor(d) else int(d) for d in dets_split]

@@ -160,3 +160,98 @@ def compare_train_step(g, outs, loss, grad_of, buffers, out_tol, loss_tol, grad_
     worst['bn_buffers'] = bn
     assert bn < bn_tol, (what, worst)
     return worst
+
+
+# ---- 8-bit crops and poisoned workspaces (tests/test_u8_crops_*.py, tests/test_workspace_poison_*.py) ----
+U8_LO = (0, 96, 192)  # R in [0, 64), G in [96, 160), B in [192, 256): a swapped channel or a wrong mean cannot pass
+
+
+def u8_crops(dets):
+    """uint8 [L,S,S,3] crops (HWC, what mmmot_amd.crops.crop_resize_u8 returns) made from the fp32 [L,3,S,S] crops of
+    make_pair (every detection keeps its own appearance): each colour channel in its own 64-value byte range, bytes 0
+    and 255 both present."""
+    q = ((dets.float() + 2.2) * (64.0 / 4.9)).floor().clamp(0, 63)
+    q = q + torch.tensor(U8_LO, dtype=torch.float32).view(1, 3, 1, 1)
+    u8 = q.to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+    u8[0, 0, 0, 0] = 0
+    u8[-1, -1, -1, 2] = 255
+    return u8
+
+
+def u8_image(L, H, W, seed):
+    """i.i.d. uint8 [L,H,W,3] pixels with the channel ranges of u8_crops, bytes 0 and 255 present"""
+    g = torch.Generator().manual_seed(seed)
+    u8 = torch.randint(0, 64, (L, H, W, 3), generator=g, dtype=torch.int32) + torch.tensor(U8_LO, dtype=torch.int32)
+    u8 = u8.to(torch.uint8)
+    u8[0, 0, 0, 0] = 0
+    u8[-1, -1, -1, 2] = 255
+    return u8
+
+
+def normalise_u8(u8):
+    """host ToTensor + Normalize of uint8 [L,H,W,3] crops -> fp32 [L,3,H,W]: oracle.crops_ref.to_tensor_normalize per crop"""
+    from oracle.crops_ref import to_tensor_normalize
+    return torch.from_numpy(np.ascontiguousarray(np.stack([to_tensor_normalize(c) for c in u8.cpu().numpy()])))
+
+
+class CallLog:
+    """Operator backend proxy that records every operator an engine calls (stream pinning is not a launch)."""
+    _quiet = ('name', 'on_current_stream', 'on_stream')
+
+    def __init__(self, ops):
+        self.ops = ops
+        self.calls = []
+
+    def __getattr__(self, k):
+        v = getattr(self.ops, k)
+        if k in self._quiet or k.startswith('_') or not callable(v):
+            return v
+
+        def call(*a, **kw):
+            self.calls.append(k)
+            return v(*a, **kw)
+        return call
+
+
+POISON = (0xFF, 0x7B)  # NaN as f64 / f32 / f16 / e4m3;  finite but huge: 1.3e36 (f32), 61280 (f16), 352 (e4m3)
+
+
+def poison_workspace(eng, byte):
+    """Fill every scratch entry of the engine's workspace arena (string keys) byte-wise.  Tuple keys hold constants
+    (('mean_std', dev), the backward's ('unit', C, dev)) and are left alone."""
+    n = 0
+    for k, t in eng.ws.items():
+        if isinstance(k, str):
+            t.view(torch.uint8).fill_(byte)
+            n += 1
+    assert n > 0, 'empty workspace: nothing was poisoned'
+
+
+def scores(out):
+    """(det, [links], new, end) of a forward, detached copies on the host"""
+    det, links, new, end = out[:4]
+    c = lambda t: t.detach().cpu().clone()
+    return c(det), [c(l) for l in links], c(new), c(end)
+
+
+def assert_same_scores(got, want, what):
+    names = ('det', 'link', 'new', 'end')
+    for name, a, b in zip(names, got, want):
+        for i, (x, y) in enumerate(zip(a, b) if name == 'link' else [(a, b)]):
+            assert x.shape == y.shape, (what, name, i, x.shape, y.shape)
+            if not torch.equal(x, y):
+                d = (x.double() - y.double()).abs()
+                raise AssertionError('%s: %s%s differs: max |diff| %.3e, %d of %d elements differ, %d non-finite' % (
+                    what, name, '[%d]' % i if name == 'link' else '', d.nan_to_num(float('inf')).max().item(),
+                    int((x != y).sum()), x.numel(), int((~torch.isfinite(x)).sum())))
+    assert len(got[1]) == len(want[1]), what
+
+
+def check_over_poison(m, call, what):
+    """warm-up forward, then for each poison pattern: fill the workspace, repeat the forward, compare bit for bit"""
+    with torch.no_grad():
+        want = scores(call())
+        for byte in POISON:
+            poison_workspace(m.engine(), byte)
+            assert_same_scores(scores(call()), want, '%s, workspace filled with 0x%02X' % (what, byte))
+    return want

@@ -701,6 +701,13 @@ def test_gemm_ares_register_kernel_random_tilings_bitwise(hip, seed):
         assert torch.equal(outs[1], outs[0]), 'register-resident and streaming kernels differ'
 
 
+def _poisoned(t):
+    """a buffer like t filled with 0xFF bytes (NaN in float64 / float32)"""
+    q = torch.empty_like(t)
+    q.view(torch.uint8).fill_(0xFF)
+    return q
+
+
 @pytest.mark.parametrize('K,N', [(128, 1024), (64, 192)])
 def test_gram_statistics_match_direct_statistics(hip, K, N):
     """GroupNorm(N, N) scale/shift of v = W relu(X*sc+sh) + b from the Gram matrix of the input (gram_rows +
@@ -753,6 +760,13 @@ def test_gram_statistics_match_direct_statistics(hip, K, N):
     hip.gn_finalize_gram(Gp, Sp, gpu, K, W.cuda(), bias.cuda(), N, gamma.cuda(), beta.cuda(), 1e-5, work, scg, shg)
     close(scg, sc_ref.float(), 5e-6, 'scale from the Gram route')
     close(shg, sh_ref.float(), 5e-6, 'shift from the Gram route')
+    # over poison (what the engine's workspace may hold): Gp (the lower blocks at K = 128 included), Sp and work filled
+    # with 0xFF bytes (NaN) - scale / shift bit for bit those of the zero-filled run
+    Gq, Sq, wq = [_poisoned(t) for t in (Gp, Sp, work)]
+    hip.gram_rows(X.cuda(), K, sc.cuda(), sh.cuda(), gpu, Gq, Sq)
+    scq, shq = torch.full((2, N), float('nan')).cuda(), torch.full((2, N), float('nan')).cuda()
+    hip.gn_finalize_gram(Gq, Sq, gpu, K, W.cuda(), bias.cuda(), N, gamma.cuda(), beta.cuda(), 1e-5, wq, scq, shq)
+    assert torch.equal(scq, scg) and torch.equal(shq, shg), 'Gram route over poisoned partials differs'
 
 
 @pytest.mark.parametrize('dets,tile', [([[700, 1, 130, 2048], [90, 300]], 512), ([[3, 5, 1]], 128), ([[2048] * 6, [1024] * 5], 2048)])
@@ -801,6 +815,12 @@ def test_gram_statistics_with_a_gathered_per_detection_bias(hip, dets, tile):
                                work, scg, shg)
     close(scg, sc_ref.float(), 5e-6, 'scale from the Gram route with a per-detection bias')
     close(shg, sh_ref.float(), 5e-6, 'shift from the Gram route with a per-detection bias')
+    Gq, Sq, wq = [_poisoned(t) for t in (Gp, Sp, work)]
+    hip.gram_rows(X.cuda(), K, sc.cuda(), sh.cuda(), gpu, Gq, Sq)
+    scq, shq = torch.full((G, N), float('nan')).cuda(), torch.full((G, N), float('nan')).cuda()
+    hip.gn_finalize_gram_dbias(Gq, Sq, gpu, tile_det.cuda(), K, W.cuda(), dbias.cuda(), N, gamma.cuda(), beta.cuda(), 1e-5,
+                               wq, scq, shq)
+    assert torch.equal(scq, scg) and torch.equal(shq, shg), 'Gram route (per-detection bias) over poisoned partials differs'
 
 
 @pytest.mark.parametrize('N', [64, 128])
