@@ -5,8 +5,16 @@
 #include <stdint.h>
 #include "../../include/mmmot_hip.h"
 
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 #define MM_BM 128          // rows (positions) per workgroup tile
 #define MM_BK 32           // reduction depth per LDS stage
@@ -36,6 +44,56 @@ __device__ __forceinline__ int mm_xcd_remap(int bid, int nwg) {
   const int xcd = bid & 7, slot = bid >> 3;
   const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
   return base + slot;
+}
+
+// ---- hand-written memory primitives: LDS-DMA, counted waits, LDS reads and scalar loads the compiler does not track.
+// Kernels that keep LDS-DMA in flight across their loops write these out because the compiler answers any load it can
+// see - and any LDS read it cannot tell from a DMA destination - with s_waitcnt vmcnt(0).  A counted wait does not name
+// the registers it guards: the consumers stay behind it only by the sched_barrier / asm ordering of the call site.
+
+// 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4: no VGPR staging, counted by vmcnt)
+__device__ __forceinline__ void mm_dma16(const void* src, unsigned char* dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+}
+
+// at most N of this wave's vector-memory requests (loads, LDS-DMA, stores) still in flight
+template <int N>
+__device__ __forceinline__ void mm_wait_vm() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// this wave's LDS reads (and scalar loads) landed
+__device__ __forceinline__ void mm_lds_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// workgroup barrier that orders LDS accesses only (no vmcnt drain)
+__device__ __forceinline__ void mm_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// LDS reads, written out: invisible to the compiler's wait insertion (pair with mm_lds_wait).  For a buffer that really is
+// disjoint from every LDS-DMA destination in flight but lives in the same array (runtime offsets): a plain read of it is
+// answered with vmcnt(0), which also waits for the wave's own global stores.
+__device__ __forceinline__ unsigned mm_lds_addr(const void* p) {
+  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+}
+__device__ __forceinline__ void mm_lds_read32(unsigned addr, f32x4& a, f32x4& b) {  // 32 bytes at addr
+  asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16" : "=&v"(a), "=&v"(b) : "v"(addr));
+}
+
+// Four wave-uniform words (the tile-table entries of a work item) by s_load_dword, and their wait, as ONE asm block with
+// early-clobber outputs: with the wait in a separate statement the compiler does not know the destination registers are
+// pending and may schedule a scalar move / select on them in between.  A compiler-visible load would be
+// answered with a wait that also drains the LDS-DMA in flight.
+__device__ __forceinline__ void mm_sload4(const int* p0, const int* p1, const int* p2, const int* p3, int& v0, int& v1,
+                                          int& v2, int& v3) {
+  asm volatile(
+      "s_load_dword %0, %4, 0x0\n\t"
+      "s_load_dword %1, %5, 0x0\n\t"
+      "s_load_dword %2, %6, 0x0\n\t"
+      "s_load_dword %3, %7, 0x0\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&s"(v0), "=&s"(v1), "=&s"(v2), "=&s"(v3)
+      : "s"(p0), "s"(p1), "s"(p2), "s"(p3)
+      : "memory");
 }
 
 // One BK=32 stage of the wave-level MMA: the wave owns TM x TN 32x32 output
@@ -78,15 +136,19 @@ __device__ __forceinline__ int mm_acc_row(int e, int lane) { return (e & 3) + 8 
 // the ds_bpermute behind __shfl_xor(.., 32) (an LDS round trip twice per channel block).  Measured and not adopted for
 // the 32-value sums: packed fp32 (v_pk_add_f32 / v_pk_fma_f32) tree reductions - fewer instructions, no faster
 // (tools/bench_ares.py A/B on one box: 0.44 ms sequential vs 0.47 ms packed, statistics pass of conv1).
-__device__ __forceinline__ float mm_xor32_sum(float x) {  // x + (x of lane ^ 32)
-  // v_permlane32_swap_b32 a, b: the upper 32 lanes of a <-> the lower 32 lanes of b.  Inline assembly: with this
-  // toolchain (ROCm 7.2 clang) the second result of __builtin_amdgcn_permlane32_swap comes back equal to the first
-  // (probed on an MI355X), and the hazard recogniser does not see into inline assembly - the instruction needs wait
-  // states after the VALU write of its operands and before a VALU read of its results (without the s_nops the upper
-  // lanes read stale values).
-  float a = x, b = x;
+// v_permlane32_swap_b32 a, b: the upper 32 lanes of a <-> the lower 32 lanes of b; returns the new {a, b}.  Inline
+// assembly: with this toolchain (ROCm 7.2 clang) the second result of __builtin_amdgcn_permlane32_swap comes back equal
+// to the first (probed on an MI355X), and the hazard recogniser does not see into inline assembly - the instruction needs
+// wait states after the VALU write of its operands and before a VALU read of its results (without the s_nops the upper
+// lanes read stale values).
+__device__ __forceinline__ f32x2 mm_permlane32_swap(float a, float b) {
   asm volatile("s_nop 3\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 3" : "+v"(a), "+v"(b));
-  return a + b;
+  return f32x2{a, b};
+}
+
+__device__ __forceinline__ float mm_xor32_sum(float x) {  // x + (x of lane ^ 32)
+  const f32x2 s = mm_permlane32_swap(x, x);
+  return s[0] + s[1];
 }
 
 __device__ __forceinline__ float mm_sum32(const f32x16& a, const f32x16& b) {  // sum of the lane's 32 values
@@ -122,6 +184,13 @@ __device__ __forceinline__ float mm_relu_sum32(const f32x16& a, const f32x16& b,
   return s;
 }
 
+// lo half of the hl16 split of one value, given its hi half (f16)y: (f16)(y - (float)hi) - convert back, subtract, convert
+// (mm_split_lo2 below: the same halves of two values with v_fma_mix).  Clamps and ReLU are the caller's.
+__device__ __forceinline__ _Float16 mm_hl_lo(float y, _Float16 hi) { return (_Float16)(y - (float)hi); }
+
+// hl16 join: the fp32 value of a (hi, lo) pair
+__device__ __forceinline__ float mm_hl_join(_Float16 hi, _Float16 lo) { return (float)hi + (float)lo; }
+
 // The lo halves of the two-term fp16 split of (y0, y1), given their rounded hi halves packed in one register:
 // (f16)(y - (float)hi) per element.  v_fma_mix{lo,hi}_f16 computes an fp32 fma of mixed fp16 / fp32 sources and rounds the
 // result to f16 into one half of the destination: ONE instruction per element where convert-back + subtract + convert take
@@ -138,8 +207,7 @@ __device__ __forceinline__ unsigned mm_split_lo2(unsigned hi2, float y0, float y
 
 // two values -> their packed fp16 hi halves and lo halves (RNE both; three instructions: v_cvt_pk_f16_f32 + the two above)
 __device__ __forceinline__ void mm_split2(float y0, float y1, unsigned& hi2, unsigned& lo2) {
-  typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-  const h2_t h = {(_Float16)y0, (_Float16)y1};
+  const f16x2 h = {(_Float16)y0, (_Float16)y1};
   hi2 = __builtin_bit_cast(unsigned, h);
   lo2 = mm_split_lo2(hi2, y0, y1);
 }

@@ -135,8 +135,6 @@ __global__ __launch_bounds__(MM_THREADS, 2) void conv3x3_kernel(
   if constexpr (OUT16 && !POOL) {
     // hl16 output: accumulators -> LDS -> bias + ReLU -> hi/lo split -> two 16-byte stores per 8 channels
     // (per-lane 2-byte stores made this layer store-issue bound: 0.67 ms per 2 frame pairs at cfg3)
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
     constexpr int CLD = BN + 4;
     float* Cs = smem;
 #pragma unroll
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(MM_THREADS, 2) void conv3x3_kernel(
         for (int e = 0; e < 8; ++e) {
           const float val = fminf(fmaxf(Cs[r * CLD + u * 8 + e] + bv[e], 0.f), 65000.f);
           hh[e] = (_Float16)val;
-          ll[e] = (_Float16)(val - (float)hh[e]);
+          ll[e] = mm_hl_lo(val, hh[e]);
         }
         u32x4* o = out16 + (pix * (Cout >> 3) + (n0 >> 3) + u) * 2;
         o[0] = __builtin_bit_cast(u32x4, hh);
@@ -218,7 +216,7 @@ __global__ __launch_bounds__(MM_THREADS, 2) void conv3x3_kernel(
               _Float16* o16 = reinterpret_cast<_Float16*>(out) + pix * Cout * 2 + (n >> 3) * 16 + (n & 7);
               const _Float16 h = (_Float16)val;
               o16[0] = h;
-              o16[8] = (_Float16)(val - (float)h);
+              o16[8] = mm_hl_lo(val, h);
             } else {
               out[pix * Cout + n] = val;
             }

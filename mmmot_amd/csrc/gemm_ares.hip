@@ -26,9 +26,6 @@
 
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 #define AR_BM 128
 #define AR_BN 256   // channels per channel tile: a wave owns 64 rows x 64 channels (2 x 2 MFMA blocks)
 #define AR_BK 32    // k per weight stage

@@ -17,9 +17,6 @@
 //                 A operand is produced by the prologue and split while it is staged to LDS.
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 #define G16_BK 64
 #define G16_LDT 72  // halves per LDS row (144 B): conflict-free ds_read_b128
 

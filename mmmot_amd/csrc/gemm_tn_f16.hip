@@ -11,9 +11,6 @@
 // Deterministic: rows are split into gridDim.z contiguous shares with their own partial dW / db (the caller adds them).
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 #define TF_ROWS 128
 #define TF_LD 136  // halves per transposed LDS row: [channel][row], 272 B (conflict-free 16-byte fragment reads)
 
@@ -106,7 +103,7 @@ __global__ __launch_bounds__(256) void gemm_tn_f16_kernel(mmmot_gemm_tn_args a, 
         for (int rr = 0; rr < 4; ++rr) {
           const float y = x[rr][e] * sd;
           hi[rr] = (_Float16)y;
-          lo[rr] = (_Float16)(y - (float)hi[rr]);
+          lo[rr] = mm_hl_lo(y, hi[rr]);
         }
         const int c = sq * CPN + c4 + e;
         *reinterpret_cast<f16x4*>(&Dh[c * TF_LD + sr4]) = hi;
@@ -163,7 +160,7 @@ __global__ __launch_bounds__(256) void gemm_tn_f16_kernel(mmmot_gemm_tn_args a, 
         for (int rr = 0; rr < 4; ++rr) {
           const float y = fminf(fmaxf(x[rr][e], -65000.f), 65000.f);
           hi[rr] = (_Float16)y;
-          lo[rr] = (_Float16)(y - (float)hi[rr]);
+          lo[rr] = mm_hl_lo(y, hi[rr]);
         }
         const int c = sq * CPK + c4 + e;
         *reinterpret_cast<f16x4*>(&Ah[c * TF_LD + sr4]) = hi;
@@ -179,7 +176,7 @@ __global__ __launch_bounds__(256) void gemm_tn_f16_kernel(mmmot_gemm_tn_args a, 
         const f16x8 h = *reinterpret_cast<const f16x8*>(&Dh[tid * TF_LD + r8]);
         const f16x8 l = *reinterpret_cast<const f16x8*>(&Dl[tid * TF_LD + r8]);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) acc += (float)h[e] + (float)l[e];
+        for (int e = 0; e < 8; ++e) acc += mm_hl_join(h[e], l[e]);
       }
       bsum += acc;
     }

@@ -40,21 +40,6 @@
 
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void gw_dma16(const u32x4* src, unsigned char* dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-
-__device__ __forceinline__ void gw_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <int N>
-__device__ __forceinline__ void gw_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 struct GwRaw {  // source values of one 16-k step of this lane's row: 8 consecutive k of b_j (PAIR) / X (NORM_RELU)
   f32x4 x[2];
 };
@@ -130,8 +115,8 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
     // written-out loads: the compiler's waitcnt pass answers a register that waits for a load with vmcnt(0) once
     // LDS-DMA requests are in flight beside it - here that would drain the source rows requested a few instructions
     // earlier (a full HBM round trip every second step).  The loads are invisible to it; the counted waits in front of
-    // the arithmetic that consumes them (gw_wait_vm in step / the prologue) are written out too.  The kernel has no
-    // scratch: no register of R is copied or parked between the request and that wait (checked in the ISA).
+    // the arithmetic that consumes them (mm_wait_vm of common.h, in step / the prologue) are written out too.  The kernel
+    // has no scratch: no register of R is copied or parked between the request and that wait (checked in the ISA).
     const float* p = p0 + 16 * n;
     asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %2, off offset:16"
                  : "=&v"(R.x[0]), "=&v"(R.x[1]) : "v"(p) : "memory");
@@ -139,14 +124,14 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
   auto dma_uniform = [&](const Src& S, int ub) {
     if constexpr (AMODE == MMMOT_A_PAIR) {
       unsigned char* dst = smem + UNI_OFF + ub * UNI_BUF + wave * 2048;
-      gw_dma16(reinterpret_cast<const u32x4*>(S.u0) + lane, dst);
-      if (a.K > 256) gw_dma16(reinterpret_cast<const u32x4*>(S.u0) + 64 + lane, dst + 1024);
+      mm_dma16(reinterpret_cast<const u32x4*>(S.u0) + lane, dst);
+      if (a.K > 256) mm_dma16(reinterpret_cast<const u32x4*>(S.u0) + 64 + lane, dst + 1024);
     } else {
       const int v = wq & 1;  // waves 1, 3: the shift row; 0, 2: the scale row (same NUMBER of requests per wave)
       unsigned char* dst = smem + UNI_OFF + ub * UNI_BUF + (half * 2 + v) * 2048;
       const float* src = v ? S.u1 : S.u0;
-      gw_dma16(reinterpret_cast<const u32x4*>(src) + lane, dst);
-      if (a.K > 256) gw_dma16(reinterpret_cast<const u32x4*>(src) + 64 + lane, dst + 1024);
+      mm_dma16(reinterpret_cast<const u32x4*>(src) + lane, dst);
+      if (a.K > 256) mm_dma16(reinterpret_cast<const u32x4*>(src) + 64 + lane, dst + 1024);
     }
   };
   auto dma_stage = [&](const u32x4* wbase, int n, int slot) {  // this wave's share of the weights of 16-k step n
@@ -157,7 +142,7 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
       const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(ubl >> 32));
       const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ubl);
       const u32x4* ub = (const u32x4*)(((unsigned long)hi << 32) | (unsigned long)lo);
-      gw_dma16(ub + dma_off, smem + slot * SLOT + q * 1024);
+      mm_dma16(ub + dma_off, smem + slot * SLOT + q * 1024);
     }
   };
 
@@ -191,7 +176,6 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
   // two elements of the A fragment of the next step: op / normalise, clamp, hi/lo split (the arithmetic of generate())
   auto gen_pair = [&](auto JTC, auto PC, float top) {
     constexpr int jt = decltype(JTC)::value, p = decltype(PC)::value;
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
     float y2[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -225,7 +209,7 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
       const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(ubl >> 32));
       const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ubl);
       const u32x4* ub = (const u32x4*)(((unsigned long)hi << 32) | (unsigned long)lo);
-      gw_dma16(ub + dma_off, smem + slot * SLOT + q * 1024);
+      mm_dma16(ub + dma_off, smem + slot * SLOT + q * 1024);
     }
   };
   int ub = 0;
@@ -235,7 +219,7 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
     load_raw(scur.p0, 0, raw[0]);
     load_raw(scur.p0, 1, raw[1]);
     dma_stage(wcur, 1, 1);
-    gw_wait_vm<NDMA>();  // the uniform rows, stage 0 and the first source values landed; stage 1 may be in flight
+    mm_wait_vm<NDMA>();  // the uniform rows, stage 0 and the first source values landed; stage 1 may be in flight
     __builtin_amdgcn_s_barrier();
     read_u(0, 0, false);
     if constexpr (AMODE != MMMOT_A_PAIR) read_u(0, 0, true);
@@ -292,8 +276,8 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
         using B = std::integral_constant<int, g & 1>;
         using BN_ = std::integral_constant<int, (g & 1) ^ 1>;
         if constexpr (g == 3) {
-          gw_wait_vm<NRAW + NDMA>();
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          mm_wait_vm<NRAW + NDMA>();
+          mm_lds_wait();
           __builtin_amdgcn_s_barrier();
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -309,7 +293,7 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
         if constexpr (g == 0) {
           // the source rows of step nn + 1 (requested two steps ago) have landed: the weight requests of step nn + 1 and
           // the source rows of step nn + 2 behind them may stay in flight
-          gw_wait_vm<NDMA + NRAW>();
+          mm_wait_vm<NDMA + NRAW>();
           __builtin_amdgcn_sched_barrier(0);
         }
         gen_pair(JT{}, GC, top1);
@@ -414,7 +398,7 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
         s1 = mm_xor32_sum(s1);
         if (lane < 32) red[wq * BN + tn * 32 + lr] = s1;
       }
-      gw_lds_barrier();
+      mm_lds_barrier();
       {
         const int cl = tid & 255;  // 256 threads of the tile's four waves, 256 columns
         const float sum = (red[cl] + red[BN + cl]) + (red[2 * BN + cl] + red[3 * BN + cl]);
@@ -423,7 +407,7 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
           colmean[cl] = sum / (float)a.tile_nrows[t2];
         }
       }
-      gw_lds_barrier();
+      mm_lds_barrier();
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn) {
         const float mu = colmean[tn * 32 + lr];
@@ -445,13 +429,13 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
         s2 = mm_xor32_sum(s2);
         if (lane < 32) red[wq * BN + tn * 32 + lr] = s2;
       }
-      gw_lds_barrier();
+      mm_lds_barrier();
       {
         const int cl = tid & 255;
         const float sum = (red[cl] + red[BN + cl]) + (red[2 * BN + cl] + red[3 * BN + cl]);
         if (t2 < a.T) a.part[((long)t2 * 2 + 1) * a.N + n0 + cl] = sum;
       }
-      gw_lds_barrier();
+      mm_lds_barrier();
     }
     cur = nxt;
     scur = snxt;

@@ -29,18 +29,9 @@
 
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 #define WR_K 128
 
 static __device__ float wr_zeros[4096];  // stands in for absent bias / dbias rows (branch-free loads)
-
-__device__ __forceinline__ void wr_dma16(const void* src, unsigned char* dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
 
 #define WP_ROWS 64
 #define WP_PLANE (WP_ROWS * 256)  // one fp16 plane [64 rows][128 k]: 16 KB
@@ -92,9 +83,8 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
   // (scalar loads written out: the compiler turns these table reads into VECTOR loads - the kernel stores to global
   // memory, so it will not treat them as constant - and then waits vmcnt(0) for them, i.e. for every LDS-DMA request
   // in flight, right after the requests were issued)
-  // The four loads and their wait are ONE asm block with early-clobber outputs: with the wait in a separate statement
-  // the compiler does not know the destination registers are pending and may schedule a scalar move / select on them in
-  // between.  Optional tables read a valid word (the tile's row0) and are replaced by 0 afterwards.
+  // tile-table words of tile t by scalar loads (mm_sload4, common.h); optional tables read a valid word (the tile's row0)
+  // and are replaced by 0 afterwards
   auto tile_info = [&](int t) {
     Tile w;
     w.t = t;
@@ -103,15 +93,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
     const int* p2 = a.tile_group ? a.tile_group + t : p0;
     const int* p3 = a.dbias ? a.tile_dbrow + t : p0;
     int v0, v1, v2, v3;
-    asm volatile(
-        "s_load_dword %0, %4, 0x0\n\t"
-        "s_load_dword %1, %5, 0x0\n\t"
-        "s_load_dword %2, %6, 0x0\n\t"
-        "s_load_dword %3, %7, 0x0\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&s"(v0), "=&s"(v1), "=&s"(v2), "=&s"(v3)
-        : "s"(p0), "s"(p1), "s"(p2), "s"(p3)
-        : "memory");
+    mm_sload4(p0, p1, p2, p3, v0, v1, v2, v3);
     w.row0 = v0;
     w.nrows = v1;
     w.grp = a.tile_group ? v2 : 0;
@@ -130,12 +112,11 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
       const int q = wave * 4 + i;
       const int r = 2 * q + (lv >> 5);
       const unsigned off = (r < nr ? (unsigned)(64 * h + r) * (unsigned)a.ldx : 0u) + (unsigned)(lv & 31) * 4u;
-      wr_dma16(base + off, Raw + h * WP_RAW + q * 1024);
+      mm_dma16(base + off, Raw + h * WP_RAW + q * 1024);
     }
   };
   // conversion of one 32-row chunk (cb = 0 / 1) of a half tile: this thread's 8 k of row 32 cb + tid / 16
   const int kc = tid & 15, crow = tid >> 4;
-  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
   struct Conv {
     f32x2 x, s, h;  // two values at a time, written as 4-byte pieces (registers are what this kernel is short of)
     f16x2 hi, lo;
@@ -185,15 +166,15 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
     const int q = wave * 4 + i;
     const int r = 2 * q + (lv >> 5);
     const unsigned off = (r < nr ? (unsigned)(64 * h + r) * (unsigned)a.ldx : 0u) + (unsigned)(lv & 31) * 4u;
-    wr_dma16(base + off, Raw + h * WP_RAW + q * 1024);
+    mm_dma16(base + off, Raw + h * WP_RAW + q * 1024);
   };
   auto sc_dma = [&](const Tile& w, int sci) {  // wave 0: sc (lanes 0..31) and sh (32..63) of the tile's group -> SC[sci], 1 KB
     unsigned char* dst = reinterpret_cast<unsigned char*>(SC + sci * 256);  // a lane's 16 bytes land at dst + 16 lane
     int lv = lane;
     asm volatile("" : "+v"(lv));
     const unsigned off = (unsigned)(lv & 31) * 4u;
-    if (lv < 32) wr_dma16(a.sc + (long)w.grp * a.ldsc + off, dst);
-    else wr_dma16(a.sh + (long)w.grp * a.ldsc + off, dst);
+    if (lv < 32) mm_dma16(a.sc + (long)w.grp * a.ldsc + off, dst);
+    else mm_dma16(a.sh + (long)w.grp * a.ldsc + off, dst);
   };
   // the wave's epilogue vectors of a tile -> CB[buf]: lanes 0..15 bias, 16..31 the dbias row, 32..47 osc, 48..63 osh (64
   // channels = 256 B each); no registers, no wait - they are read a half tile later
@@ -203,10 +184,10 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
     asm volatile("" : "+v"(lv));
     const unsigned off = (unsigned)(lv & 15) * 4u;
     const int g = lv >> 4;
-    if (g == 0) wr_dma16(pbias + nbase + off, dst);
-    else if (g == 1) wr_dma16((a.dbias ? a.dbias + (long)w.dbrow * a.lddb + nbase : wr_zeros) + off, dst);
-    else if (g == 2) wr_dma16(a.osc + (long)w.grp * a.ldosc + nbase + off, dst);
-    else wr_dma16(a.osh + (long)w.grp * a.ldosc + nbase + off, dst);
+    if (g == 0) mm_dma16(pbias + nbase + off, dst);
+    else if (g == 1) mm_dma16((a.dbias ? a.dbias + (long)w.dbrow * a.lddb + nbase : wr_zeros) + off, dst);
+    else if (g == 2) mm_dma16(a.osc + (long)w.grp * a.ldosc + nbase + off, dst);
+    else mm_dma16(a.osh + (long)w.grp * a.ldosc + nbase + off, dst);
   };
   const unsigned cl = (unsigned)lr;
   auto tile_consts = [&](int buf, float* m1, float* m0) {  // from CB[buf] (requested a half tile ago, complete at the barrier)
@@ -317,7 +298,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
   dma_unit(cur, 1);
   if (wave == 0) sc_dma(cur, 0);
   cb_dma(cur, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  mm_wait_vm<0>();
   __syncthreads();
   convert_plain(0, 0, cur.nrows);
 
@@ -348,7 +329,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
     const int nrows = cur.nrows, nrnext = nxt.nrows;
     const int sci = q & 1;
     // ================= half 0: planes P0; converts half 1 of this tile (Raw1 -> P1) =================
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of Raw1 and CB[sci] (requested a half tile ago)
+    mm_wait_vm<0>();  // this wave's share of Raw1 and CB[sci] (requested a half tile ago)
     __syncthreads();
     park();
     first_frags(ah, al, 0);
@@ -363,7 +344,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
     stream(acc1, acc0, ah, al, 0, 1, false, m1, m0, run, 1, 1, sci, 32 + crow < nrows - 64, 0, nxt);  // + sums of block 0
     fix(acc0, nrows);
     // ================= half 1: planes P1; converts half 0 of the next tile (Raw0 -> P0) =================
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // Raw0 of the next tile
+    mm_wait_vm<0>();  // Raw0 of the next tile
     __syncthreads();
     const Tile nn = tile_info(q + 2 < ntile ? cur.t + 2 * stride : cur.t);  // used from the next half tile on
     park();
@@ -382,7 +363,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
   // ---- drain: the last block of the last tile ----
   epi_masked(acc1, m1, m0, run, nrprev - 96 - 4 * hh);
   store_sums(tprev, 1, run);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing may still be in flight towards this workgroup's LDS
+  mm_wait_vm<0>();  // nothing may still be in flight towards this workgroup's LDS
 }
 
 static std::atomic<int> g_ares_variant{0};

@@ -18,10 +18,6 @@
 // Arithmetic and summation order are those of gemm_ares (fp16 matrix cores, 3-term hi/lo split, fp32 accumulation).
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 #define WR_THREADS 512
 #define WR_NMAX 512
 #define WR_BM 128
@@ -107,7 +103,6 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64_kernel(mmmot_gemm_ares
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = sr + 32 * i;
-      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
       u32x2 hi, lo;
       float y[4];
 #pragma unroll
@@ -329,7 +324,7 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_are
   const int hend = h + q + (gw < rem ? 1 : 0);
   if (h >= hend) return;
 
-  // tile-table words of item hh by scalar loads (see gemm_wreg.hip: one asm block with its wait, early-clobber outputs)
+  // tile-table words of item hh by scalar loads (mm_sload4, common.h)
   auto item = [&](int hh) {
     const int t = hh >> 1;
     const int* p0 = a.tile_row0 + t;
@@ -337,15 +332,7 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_are
     const int* p2 = a.tile_group ? a.tile_group + t : p0;
     const int* p3 = a.dbias ? a.tile_dbrow + t : p0;
     int v0, v1, v2, v3;
-    asm volatile(
-        "s_load_dword %0, %4, 0x0\n\t"
-        "s_load_dword %1, %5, 0x0\n\t"
-        "s_load_dword %2, %6, 0x0\n\t"
-        "s_load_dword %3, %7, 0x0\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&s"(v0), "=&s"(v1), "=&s"(v2), "=&s"(v3)
-        : "s"(p0), "s"(p1), "s"(p2), "s"(p3)
-        : "memory");
+    mm_sload4(p0, p1, p2, p3, v0, v1, v2, v3);
     WiItem m;
     m.row0 = v0;
     m.nrows = v1;
@@ -474,8 +461,8 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_are
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         if (i < nblk) {
-          float m1i = tab[i], m0i = tab[i];  // -> (lanes 0-31 of tab[i], lanes 32-63 of tab[i]) on every lane
-          asm volatile("s_nop 3\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 3" : "+v"(m1i), "+v"(m0i));
+          const f32x2 m = mm_permlane32_swap(tab[i], tab[i]);  // (lanes 0-31, lanes 32-63 of tab[i]) on every lane
+          const float m1i = m[0], m0i = m[1];
           f32x16 acc[2];
           mma_block(acc, (i + 1) * 32 + lr, i + 1 < nblk);
           float s3 = mm_relu_sum32(acc[0], acc[1], m1i, m0i);

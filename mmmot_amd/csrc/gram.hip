@@ -16,8 +16,6 @@
 
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 #define GR_ROWS 128      // rows per sub-tile (fp32 accumulation length)
 #define GR_LD 136        // halves per transposed LDS row: [channel][row], 272 B
 #define GR_THREADS 256
@@ -92,7 +90,6 @@ __global__ __launch_bounds__(GR_THREADS) void gram_rows_kernel(const float* __re
     const int nr = min(GR_ROWS, nrows - r0);
     // ---- stage: normalise + ReLU + hi/lo split, transposed into LDS ([channel][row]) ----
     {
-      typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
       const float* ps = sc + (long)grp * ldsc + sq * CPT;
       const float* ph = sh + (long)grp * ldsc + sq * CPT;
 #pragma unroll
@@ -107,7 +104,7 @@ __global__ __launch_bounds__(GR_THREADS) void gram_rows_kernel(const float* __re
             float y = fminf(fmaxf(fmaf(xr[c4 / 4][rr][e], s4[e], h4[e]), 0.f), 65000.f);
             if (sr4 + rr >= nr) y = 0.f;  // rows past the end of the super-tile contribute nothing
             hi[rr] = (_Float16)y;
-            lo[rr] = (_Float16)(y - (float)hi[rr]);
+            lo[rr] = mm_hl_lo(y, hi[rr]);
           }
           const int c = sq * CPT + c4 + e;
           const int o = c * GR_LD + (gr_quad<CPT>(sr4 >> 2, c) << 2);
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(GR_THREADS) void gram_rows_kernel(const float* __re
         const f16x8 h = *reinterpret_cast<const f16x8*>(&Th[tid * GR_LD + r8]);
         const f16x8 l = *reinterpret_cast<const f16x8*>(&Tl[tid * GR_LD + r8]);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) acc += (float)h[e] + (float)l[e];
+        for (int e = 0; e < 8; ++e) acc += mm_hl_join(h[e], l[e]);
       }
       gr_acc(ss, scc, acc);
     }
@@ -277,8 +274,6 @@ __global__ __launch_bounds__(GR_THREADS, 2) void gram_rows128_kernel(const float
             y[rr] = __builtin_amdgcn_fmed3f(fmaf(xr[rr][e], s4[e], h4[e]), 0.f, 65000.f);  // ReLU + fp16 range clamp
             if (!full && sr4 + rr >= nr) y[rr] = 0.f;  // rows past the end of the super-tile contribute nothing
           }
-          typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-          typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
           const f16x2 h01 = {(_Float16)y[0], (_Float16)y[1]}, h23 = {(_Float16)y[2], (_Float16)y[3]};
           const u32x2 hi = {__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23)};
           const u32x2 lo = {mm_split_lo2(hi[0], y[0], y[1]), mm_split_lo2(hi[1], y[2], y[3])};
@@ -299,7 +294,7 @@ __global__ __launch_bounds__(GR_THREADS, 2) void gram_rows128_kernel(const float
         const f16x8 h = *reinterpret_cast<const f16x8*>(&Th[c * GR_LD + rb + r8]);
         const f16x8 l = *reinterpret_cast<const f16x8*>(&Tl[c * GR_LD + rb + r8]);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a += (float)h[e] + (float)l[e];
+        for (int e = 0; e < 8; ++e) a += mm_hl_join(h[e], l[e]);
       }
       sd += (double)a;
     }
@@ -423,7 +418,6 @@ __global__ __launch_bounds__(512, 1) void gram_rows128p_kernel(const float* __re
           y[rr] = __builtin_amdgcn_fmed3f(fmaf(src[q][rr][e], s4[e], h4[e]), 0.f, 65000.f);  // ReLU + fp16 range clamp
           if (!full && sr4 + rr >= nr) y[rr] = 0.f;
         }
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         unsigned h01, l01, h23, l23;
         mm_split2(y[0], y[1], h01, l01);
         mm_split2(y[2], y[3], h23, l23);
@@ -462,7 +456,7 @@ __global__ __launch_bounds__(512, 1) void gram_rows128p_kernel(const float* __re
         const f16x8 hh = *reinterpret_cast<const f16x8*>(&Th[c * GR_LD + rb + r8]);
         const f16x8 ll = *reinterpret_cast<const f16x8*>(&Tl[c * GR_LD + rb + r8]);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a += (float)hh[e] + (float)ll[e];
+        for (int e = 0; e < 8; ++e) a += mm_hl_join(hh[e], ll[e]);
       }
       sd += (double)a;
     }

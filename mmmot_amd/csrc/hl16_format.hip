@@ -16,17 +16,13 @@
 // inverse, exact).  The trunk kernel is conv3x3_hl16_patch.hip, the row GEMMs gemm_rows.hip / gemm_ares.hip.
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ void hl_split8(f32x8 v, u32x4& hi, u32x4& lo) {
   f16x8 h, l;
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const float x = fminf(fmaxf(v[e], -65000.f), 65000.f);  // stay finite in fp16 (activations are O(1..100))
     h[e] = (_Float16)x;
-    l[e] = (_Float16)(x - (float)h[e]);
+    l[e] = mm_hl_lo(x, h[e]);
   }
   hi = __builtin_bit_cast(u32x4, h);
   lo = __builtin_bit_cast(u32x4, l);
@@ -49,7 +45,7 @@ __global__ void hl16_unpack_kernel(const u32x4* __restrict__ x, float* __restric
   if (i >= nunits) return;
   const f16x8 h = __builtin_bit_cast(f16x8, x[i * 2]), l = __builtin_bit_cast(f16x8, x[i * 2 + 1]);
 #pragma unroll
-  for (int e = 0; e < 8; ++e) y[i * 8 + e] = (float)h[e] + (float)l[e];
+  for (int e = 0; e < 8; ++e) y[i * 8 + e] = mm_hl_join(h[e], l[e]);
 }
 
 extern "C" int mmmot_hl16_pack(const float* x, void* y, long n, void* stream) {
@@ -72,14 +68,11 @@ extern "C" int mmmot_hl16_unpack(const void* x, float* y, long n, void* stream) 
 // Device-side power-of-two scaling for the training step (no host round trip): a tensor whose magnitude is only known
 // on the device (a gradient: 1e-4 .. 1e-7; freshly updated weights) is multiplied by 2^(target - ex), amax = f * 2^ex
 // with f in [0.5, 1), before the split, so that its lo halves stay normal fp16 numbers; mmmot_pow2_oscale builds the
-// per-output-channel vector the consuming kernel multiplies its accumulators with to undo the scale(s) exactly.
-__device__ __forceinline__ int hl_pow2_shift(const float* amax, int target) {
-  return mm_pow2_shift(amax ? *amax : 0.f, target);
-}
-
+// per-output-channel vector the consuming kernel multiplies its accumulators with to undo the scale(s) exactly.  A NULL
+// amax means "unscaled" (mm_pow2_shift of 0).
 __global__ void hl16_pack_pow2_kernel(const float* __restrict__ x, u32x4* __restrict__ y, long nunits,
                                       const float* __restrict__ amax, int target) {
-  const float sd = ldexpf(1.f, hl_pow2_shift(amax, target));
+  const float sd = ldexpf(1.f, mm_pow2_shift(amax ? *amax : 0.f, target));
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nunits; i += (long)gridDim.x * blockDim.x) {
     f32x8 v = *reinterpret_cast<const f32x8*>(x + i * 8);
 #pragma unroll
@@ -105,7 +98,7 @@ __global__ void pow2_oscale_kernel(float* __restrict__ out, int C, const float* 
                                    const float* __restrict__ amax_b, int target_b) {
   // (each exponent is clamped to +-100 for degenerate maxima, mm_pow2_shift; their sum to +-126 so that the inverse scale
   // of two clamped operands stays a finite normal float - with such maxima exactness is moot, finiteness is not)
-  int ex = -(hl_pow2_shift(amax_a, target_a) + hl_pow2_shift(amax_b, target_b));
+  int ex = -(mm_pow2_shift(amax_a ? *amax_a : 0.f, target_a) + mm_pow2_shift(amax_b ? *amax_b : 0.f, target_b));
   ex = ex < -126 ? -126 : (ex > 126 ? 126 : ex);
   const float v = ldexpf(1.f, ex);
   for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < C; c += gridDim.x * blockDim.x) out[c] = v;

@@ -1,12 +1,8 @@
 // Shared device helpers of the trunk kernel (conv3x3_hl16_patch.hip): activation encoders (hl16 split, hq8 records),
-// the range guard of the reduced-range formats, barrier / DMA primitives, LDS swizzles, the block geometry of a tile
+// the range guard of the reduced-range formats, LDS swizzles, the block geometry of a tile
 // (PatchGeom: 16 x 16, 8 x 8 haloed blocks or whole 4 x 4 maps), the arguments of the fused first layer and the
 // constants of the hq8 arithmetic.  Included by that translation unit only.
 #pragma once
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
 
 static __device__ u32x4 pt_zero_page[16];  // zero-initialised: source of out-of-image patch pixels
 
@@ -97,35 +93,6 @@ __device__ __forceinline__ void pt_range_guard(const float* v, bool q8, unsigned
 __device__ __forceinline__ int pt_swz_b(int r) { return (r >> 1) & 7; }
 __device__ __forceinline__ int pt_swz_a(int py, int px) { return ((px >> 1) + 4 * (py & 1)) & 7; }
 
-template <int N>
-__device__ __forceinline__ void pt_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// workgroup barrier that orders LDS accesses only (no vmcnt drain)
-__device__ __forceinline__ void pt_lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-__device__ __forceinline__ void pt_dma16(const u32x4* src, unsigned char* dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-
-// LDS reads of the epilogue's staging area, written out.  The compiler cannot tell the staging buffer from the LDS-DMA
-// destinations of the successor tile (both are runtime offsets into one array), so it answers every LDS read it can see
-// with s_waitcnt vmcnt(0) - and vmcnt also counts this tile's own global STORES: each iteration of the store loop then
-// waited for the previous iteration's stores to reach the L2 (8 round trips per unpooled tile, ~10 % of the tile: the
-// "encode + issue stores" phase of profiles/HISTORY.md).  These reads are invisible to that pass; the buffer really is
-// disjoint from everything in flight (patch_setup.inc), and the wait for the reads themselves is written out too.
-__device__ __forceinline__ unsigned pt_lds_addr(const void* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
-__device__ __forceinline__ void pt_lds_read32(unsigned addr, f32x4& a, f32x4& b) {
-  asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16" : "=&v"(a), "=&v"(b) : "v"(addr));
-}
-__device__ __forceinline__ void pt_lds_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 template <int BS>
 struct PatchGeom {
   // WHOLE (BS <= 4): a block is a WHOLE feature map of at most BS x BS pixels (conv5 at 64-pixel crops: 4 x 4), so every
@@ -199,7 +166,6 @@ struct Fuse1Args {
 // K = 2 x 16) + ONE v_mfma_scale_f32_32x32x64_f8f6f4 whose 64 k-slots are [a8 . w_lo8 | a_lo8 . w8] with the
 // block scale 2^-3 - 2 instead of 3 f16-MFMA-equivalents per product.  Pieces stay 16 bytes, so loaders, DMA ring
 // and swizzles are unchanged.  Accuracy: tools/study_fp8_correction.py.
-typedef int i32x8 __attribute__((ext_vector_type(8)));
 #define Q8_ASHIFT 2      // fp8 copies of activations carry 2^-2 (range up to 1792)
 #define Q8_SCALE_A 124   // E8M0 exponent of the block scale 2^-3 = 2^-11 (lo) * 2^2 (activation copies) * 2^6 (weight copies)
 #define Q8_SCALE_B 127

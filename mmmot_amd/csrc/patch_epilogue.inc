@@ -54,7 +54,7 @@
   {
   // barriers of the epilogue order LDS traffic only (lgkmcnt): a __syncthreads() would also drain vmcnt, i.e.
   // wait for the successor's loads and for this tile's own global stores
-  pt_lds_barrier();  // every wave is past its last read of the buffer that becomes the staging area
+  mm_lds_barrier();  // every wave is past its last read of the buffer that becomes the staging area
   PT_STAMP(2)
   float* Cs = reinterpret_cast<float*>(smem + ((FUSE1 && !OVL) ? 0 : pcur));
   if constexpr (OVL) {
@@ -77,7 +77,7 @@
   }
 #pragma unroll
   for (int ch = 0; ch < NCH; ++ch) {
-  if (ch > 0) pt_lds_barrier();  // the previous chunk has been read by everyone
+  if (ch > 0) mm_lds_barrier();  // the previous chunk has been read by everyone
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
     const int rb = wm * TM + tm;  // 32-row block of the tile (wave-uniform)
@@ -99,21 +99,27 @@
           Cs[((rb % (8 / NCH)) * 32 + mm_acc_row(e, lane)) * CLD + wn * TN * 32 + tn * 32 + lr] = acc[tm][tn][e];
     }
   }
-  pt_lds_barrier();
+  mm_lds_barrier();
   if (ch == 0) { PT_STAMP(3) }
+  // The staged values are read with mm_lds_read32 / mm_lds_wait (common.h).  The compiler cannot tell the staging buffer
+  // from the LDS-DMA destinations of the successor tile (both are runtime offsets into one array), so it answers every LDS
+  // read it can see with s_waitcnt vmcnt(0) - and vmcnt also counts this tile's own global STORES: each iteration of the
+  // store loop then waited for the previous iteration's stores to reach the L2 (8 round trips per unpooled tile, ~10 % of
+  // the tile: the "encode + issue stores" phase of profiles/HISTORY.md).  The buffer really is disjoint from everything
+  // in flight (patch_setup.inc).
   if constexpr (Q8) {
     const int Hq = H >> 1, Wq = W >> 1;
     constexpr int NITEM = RCH;  // quads (pooled) or rows of one chunk
     constexpr int NIT16 = (NITEM + RSTEP16 - 1) / RSTEP16;
-    f32x4 vq[NIT16][4];  // 16 staged values per item, requested before the first store (pt_lds_read32: patch_common.h)
+    f32x4 vq[NIT16][4];  // 16 staged values per item, requested before the first store
 #pragma unroll
     for (int i = 0; i < NIT16; ++i) {
       const int itl = er16 + i * RSTEP16;
-      const unsigned ad = pt_lds_addr(&Cs[(itl < NITEM ? itl : 0) * CLD + eu16 * 16]);
-      pt_lds_read32(ad, vq[i][0], vq[i][1]);
-      pt_lds_read32(ad + 32, vq[i][2], vq[i][3]);
+      const unsigned ad = mm_lds_addr(&Cs[(itl < NITEM ? itl : 0) * CLD + eu16 * 16]);
+      mm_lds_read32(ad, vq[i][0], vq[i][1]);
+      mm_lds_read32(ad + 32, vq[i][2], vq[i][3]);
     }
-    pt_lds_wait();
+    mm_lds_wait();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < NIT16; ++i) {
@@ -161,13 +167,13 @@
     const int Hq = H >> 1, Wq = W >> 1;
     constexpr int NQ = RCH;  // quads of the (single) chunk
     constexpr int NIT = (NQ + RSTEP - 1) / RSTEP;
-    f32x4 va[NIT], vb[NIT];  // requested before the first store (pt_lds_read32: patch_common.h)
+    f32x4 va[NIT], vb[NIT];  // requested before the first store
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
       const int qdl = er0 + i * RSTEP;
-      pt_lds_read32(pt_lds_addr(&Cs[(qdl < NQ ? qdl : 0) * CLD + eu * 8]), va[i], vb[i]);
+      mm_lds_read32(mm_lds_addr(&Cs[(qdl < NQ ? qdl : 0) * CLD + eu * 8]), va[i], vb[i]);
     }
-    pt_lds_wait();
+    mm_lds_wait();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
@@ -196,12 +202,12 @@
       }
     }
   } else {
-    // the chunk's staged rows of this thread, all requested before the first store (pt_lds_read32: patch_common.h)
+    // the chunk's staged rows of this thread, all requested before the first store
     constexpr int NIT = RCH / RSTEP;
     f32x4 va[NIT], vb[NIT];
 #pragma unroll
-    for (int i = 0; i < NIT; ++i) pt_lds_read32(pt_lds_addr(&Cs[(er0 + i * RSTEP) * CLD + eu * 8]), va[i], vb[i]);
-    pt_lds_wait();
+    for (int i = 0; i < NIT; ++i) mm_lds_read32(mm_lds_addr(&Cs[(er0 + i * RSTEP) * CLD + eu * 8]), va[i], vb[i]);
+    mm_lds_wait();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
@@ -262,6 +268,6 @@
   }
   // LDS-only: the staging area is the successor's next patch buffer (FUSE1: the next tile's raw window / patches);
   // the tile's own stores drain under the next tile, the raw-window registers are waited for where they are used
-  pt_lds_barrier();
+  mm_lds_barrier();
   PT_STAMP(5)
   PT_COUNT_ITEM()

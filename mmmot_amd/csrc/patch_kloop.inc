@@ -45,9 +45,9 @@
     half1(std::integral_constant<int, 11>{});
     if constexpr (PRO && (tap == 1 || tap == 2)) {
       // the three raw-window loads of stage 0 are younger than the weights this barrier needs: they may stay in flight
-      if (rawfly) pt_wait_vm<prev_issued + 3>();
-      else pt_wait_vm<prev_issued>();
-    } else pt_wait_vm<prev_issued>();  // weights of stage t+1 (and every older load) landed
+      if (rawfly) mm_wait_vm<prev_issued + 3>();
+      else mm_wait_vm<prev_issued>();
+    } else mm_wait_vm<prev_issued>();  // weights of stage t+1 (and every older load) landed
     // lgkmcnt(0) as a compiler-visible s_waitcnt (vmcnt 63 / expcnt 7 / lgkmcnt 0): the waitcnt pass then
     // knows the second step's fragments have landed and does not re-wait after the next reads are issued
     __builtin_amdgcn_s_waitcnt(0xC07F);

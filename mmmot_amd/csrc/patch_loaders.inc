@@ -39,9 +39,9 @@
     constexpr int k = decltype(KC)::value;
     const u32x4* src = (poff[k] != ~0u) ? in + (poff[k] + (unsigned)(slab * 8)) : zsrc;
     if constexpr (k < G::FULL) {
-      pt_dma16(src, smem + pbuf + (k * 8 + wave) * 1024);
+      mm_dma16(src, smem + pbuf + (k * 8 + wave) * 1024);
     } else {
-      if (lane < G::RL) pt_dma16(src, smem + pbuf + G::FULL * 8192 + wave * (G::RL * 16));
+      if (lane < G::RL) mm_dma16(src, smem + pbuf + G::FULL * 8192 + wave * (G::RL * 16));
     }
   };
   // weight DMA instruction b (0..NBL-1) of stage (tap, slab) into ring slot `ringslot`
@@ -54,7 +54,7 @@
       const unsigned ub_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(ubl >> 32));
       const unsigned ub_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ubl);
       const u32x4* ub = (const u32x4*)(((unsigned long)ub_hi << 32) | (unsigned long)ub_lo);
-      pt_dma16(ub + boffl[b], smem + RING0 + ringslot * B_BYTES + (wave * NBL + b) * 1024);
+      mm_dma16(ub + boffl[b], smem + RING0 + ringslot * B_BYTES + (wave * NBL + b) * 1024);
     }
   };
   auto issue_b = [&](int tap, int slab, int ringslot) {

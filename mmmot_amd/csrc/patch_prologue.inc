@@ -96,7 +96,7 @@
         float v = R[rbase + roff[e]];
         if (e == 3 && kg1 == 3) v = 1.f;  // k = 27: the bias slot
         xh[e] = (_Float16)v;
-        xl[e] = (_Float16)(v - (float)xh[e]);
+        xl[e] = mm_hl_lo(v, xh[e]);
       }
     };
     auto mma1 = [&](const f16x8& xh, const f16x8& xl, f32x4 (&c1)[4]) {
@@ -117,7 +117,6 @@
       const bool inimg = (b0 < nblk) && ((unsigned)gy < (unsigned)H) && ((unsigned)gx < (unsigned)W);
       const float top = inimg ? 65504.f : 0.f;  // fp16 maximum (the guard below reports anything above PT_SAT_FP16)
       const int sw = pt_swz_a(ppy, ppx);
-      typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
       const int hh = kg1 & 1;  // which half (4 channels) of an 8-channel unit
 #pragma unroll
       for (int mb = 0; mb < 4; ++mb) {  // channels 16 mb + 4 kg1 .. + 3 = slab mb >> 1, unit q, half hh
@@ -132,7 +131,7 @@
           c11max = fmaxf(c11max, v);
           vv[r] = v;
           hi[r] = (_Float16)v;
-          lo[r] = (_Float16)(v - (float)hi[r]);
+          lo[r] = mm_hl_lo(v, hi[r]);
         }
         if constexpr (Q8) {
           // record = [fp16 hi: pieces 0..3 | e4m3(a/4): pieces 4,5 | e4m3(a_lo*512): pieces 6,7]
@@ -179,7 +178,7 @@
     }
     if (c11max > (Q8 ? PT_SAT_E4M3 : PT_SAT_FP16)) atomicAdd(&rng[2], 1u);
     c11max = 0.f;
-    pt_wait_vm<2 * NBL>();  // weight stage 0 landed (this wave's part)
+    mm_wait_vm<2 * NBL>();  // weight stage 0 landed (this wave's part)
     __syncthreads();        // both patch slabs are complete
     if constexpr (OVL) {
       if (has_next) {  // the successor's raw window (every wave is past its gathers from the old one)
@@ -194,7 +193,7 @@
     if (!primed) {  // first tile of this workgroup
       issue_tile_head(pcur);
       PT_STAMP(0)
-      pt_wait_vm<2 * NBL>();  // patch + weight stage 0 landed (this wave's part)
+      mm_wait_vm<2 * NBL>();  // patch + weight stage 0 landed (this wave's part)
       __builtin_amdgcn_s_barrier();
     }
     PT_STAMP(1)
@@ -222,8 +221,7 @@
   float pr_v[8];
   f16x8 pr_xh, pr_xl;
   f32x4 pr_c[4];
-  typedef _Float16 pr_f16x4 __attribute__((ext_vector_type(4)));
-  pr_f16x4 pr_hi, pr_lo;
+  f16x4 pr_hi, pr_lo;
   auto pro_slot = [&](auto SC, auto RC) {
     constexpr int sl = decltype(SC)::value;
     constexpr int rr = decltype(RC)::value;
@@ -277,13 +275,13 @@
         v = __builtin_amdgcn_fmed3f(v, 0.f, pr_top);
         c11max = fmaxf(c11max, v);
         pr_hi[r] = (_Float16)v;
-        pr_lo[r] = (_Float16)(v - (float)pr_hi[r]);
+        pr_lo[r] = mm_hl_lo(v, pr_hi[r]);
         if constexpr (r == 3) {
           const int kg1 = lane >> 4;
           const int q = (mb & 1) * 2 + (kg1 >> 1);
           const int rb = ((mb >> 1) == 0 ? bufZ : bufX) + pr_rec + (kg1 & 1) * 8;
-          *reinterpret_cast<pr_f16x4*>(smem + rb + (((2 * q) ^ pr_sw) << 4)) = pr_hi;
-          *reinterpret_cast<pr_f16x4*>(smem + rb + (((2 * q + 1) ^ pr_sw) << 4)) = pr_lo;
+          *reinterpret_cast<f16x4*>(smem + rb + (((2 * q) ^ pr_sw) << 4)) = pr_hi;
+          *reinterpret_cast<f16x4*>(smem + rb + (((2 * q + 1) ^ pr_sw) << 4)) = pr_lo;
         }
       }
     }

@@ -87,7 +87,7 @@
       if ((ln >> 4) == 3) {  // k = 24 .. 31 of this channel: element 3 = k 27 takes the bias (the window value there is 1)
         const float bs = fz.bias1[mb * 16 + (ln & 15)] * (1.f / fz.oscale1);  // oscale1 is a power of two
         const _Float16 bh = (_Float16)bs;
-        const _Float16 bl = (_Float16)(bs - (float)bh);
+        const _Float16 bl = mm_hl_lo(bs, bh);
         const unsigned bits = (unsigned)__builtin_bit_cast(unsigned short, hl == 0 ? bh : bl);
         wv[1] = (wv[1] & 0x0000ffffu) | (bits << 16);
       }

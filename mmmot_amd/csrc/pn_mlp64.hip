@@ -11,10 +11,6 @@
 // Arithmetic: fp16 matrix cores, 3-term hi/lo split (hl16 weights pre-scaled by 1/oscale), fp32 accumulation.
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 #define PM_K 64
 #define PM_LDT 72  // halves per LDS row (144 B): conflict-free ds_read_b128
 
@@ -70,7 +66,6 @@ __global__ __launch_bounds__(256) void pn_mlp64_kernel(const float* __restrict__
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int r = srow + 16 * i;
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         u32x2 hi, lo;
         float y[4];
 #pragma unroll

@@ -208,7 +208,6 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(
       // hq8 row: 128-byte record per 32 channels = [32 x fp16 hi | 32 x e4m3 (unused here) | 32 x e4m3(lo * 2^9)]
       const unsigned char* rec = reinterpret_cast<const unsigned char*>(X + ((long)start + (long)t * stride) * ldx) +
                                  (c >> 5) * 128;
-      typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
       const f16x4 h = *reinterpret_cast<const f16x4*>(rec + 2 * (c & 31));
       const int l = *reinterpret_cast<const int*>(rec + 96 + (c & 31));
       const auto p0 = __builtin_amdgcn_cvt_pk_f32_fp8(l, false);
@@ -220,11 +219,10 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(
     } else if (hl16) {
       // hl16 row (same bytes as fp32): unit u = c>>3 holds [hi8 | lo8] halves; this lane's 4 channels
       const _Float16* rowp = reinterpret_cast<const _Float16*>(X + ((long)start + (long)t * stride) * ldx);
-      typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
       const f16x4 h = *reinterpret_cast<const f16x4*>(rowp + (c >> 3) * 16 + (c & 7));
       const f16x4 l = *reinterpret_cast<const f16x4*>(rowp + (c >> 3) * 16 + 8 + (c & 7));
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (float)h[e] + (float)l[e];
+      for (int e = 0; e < 4; ++e) v[e] = mm_hl_join(h[e], l[e]);
     } else {
       v = *reinterpret_cast<const f32x4*>(&X[((long)start + (long)t * stride) * ldx + c]);
     }
@@ -280,7 +278,6 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(
 // per 8-pair step): a lane takes a whole 8-channel unit - [hi8 | lo8] = two 16-byte loads - instead of the 4 channels
 // (two 8-byte loads) of the general kernel, and all 64 lanes work whatever C is: UPR = C / 8 lanes cover a row, a wave
 // load instruction 64 / UPR rows.  Same result contract (mean over the segment, divisor seg_div or the row count).
-typedef _Float16 sm_f16x8 __attribute__((ext_vector_type(8)));
 template <int UPR>
 __global__ __launch_bounds__(256) void segment_mean_hl16_kernel(const float* __restrict__ X, int ldx,
                                                                  const int* __restrict__ seg_start,
@@ -298,10 +295,10 @@ __global__ __launch_bounds__(256) void segment_mean_hl16_kernel(const float* __r
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
   auto add_row = [&](int t) {
-    const sm_f16x8* p = reinterpret_cast<const sm_f16x8*>(X + ((long)start + (long)t * stride) * ldx) + 2 * u;
-    const sm_f16x8 h = p[0], l = p[1];
+    const f16x8* p = reinterpret_cast<const f16x8*>(X + ((long)start + (long)t * stride) * ldx) + 2 * u;
+    const f16x8 h = p[0], l = p[1];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] += (float)h[e] + (float)l[e];
+    for (int e = 0; e < 8; ++e) acc[e] += mm_hl_join(h[e], l[e]);
   };
   constexpr int STEP = 4 * RPW;  // rows per workgroup pass
   int t = wave * RPW + rsub;

@@ -257,8 +257,6 @@ extern "C" int mmmot_conv3x3_wgrad(const float* dZ, const float* A, int L, int H
 //     of rows four apart (eight lanes per bank); the epilogue undoes the relabelling.
 // 4 waves own 2 x 2 quadrants of the TN x TK tile, three accumulator sets each.  grid = (Cout / TN, Cin / TK, 3 * nsplit);
 // partial dW per pixel share in the fp32 kernel's layout [share][tap][Cout][Cin].
-typedef _Float16 wg_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int wg_u32x2 __attribute__((ext_vector_type(2)));
 #define WG_PX 64  // pixels per chunk
 #define WG_LD 72  // halves per LDS row: 144 B (36 dwords: 32 consecutive rows x 16 bytes touch every bank once)
 
@@ -332,15 +330,15 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16_kernel(const float* __r
         float y[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) y[r] = r < nv ? zr[i][r][e] * sd : 0.f;
-        wg_u32x2 hi, lo;
+        u32x2 hi, lo;
         unsigned h0, l0, h1, l1;
         mm_split2(y[0], y[1], h0, l0);
         mm_split2(y[2], y[3], h1, l1);
-        hi = wg_u32x2{h0, h1};
-        lo = wg_u32x2{l0, l1};
+        hi = u32x2{h0, h1};
+        lo = u32x2{l0, l1};
         const int off = (e * QN + cq) * WG_LD + 4 * pq;
-        *reinterpret_cast<wg_u32x2*>(&Dh[off]) = hi;
-        *reinterpret_cast<wg_u32x2*>(&Dl[off]) = lo;
+        *reinterpret_cast<u32x2*>(&Dh[off]) = hi;
+        *reinterpret_cast<u32x2*>(&Dl[off]) = lo;
       }
     }
 #pragma unroll
@@ -381,8 +379,8 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16_kernel(const float* __r
         const int off = (e * QK + cq) * WG_LD + 4 * pq;
 #pragma unroll
         for (int t = 0; t < 3; ++t) {  // copy dx = t - 1: pixel r reads slot r + t
-          *reinterpret_cast<wg_u32x2*>(&Ah[t][off]) = wg_u32x2{hp[t] & mk[t][0], hp[t + 2] & mk[t][1]};
-          *reinterpret_cast<wg_u32x2*>(&Al[t][off]) = wg_u32x2{lp[t] & mk[t][0], lp[t + 2] & mk[t][1]};
+          *reinterpret_cast<u32x2*>(&Ah[t][off]) = u32x2{hp[t] & mk[t][0], hp[t + 2] & mk[t][1]};
+          *reinterpret_cast<u32x2*>(&Al[t][off]) = u32x2{lp[t] & mk[t][0], lp[t + 2] & mk[t][1]};
         }
       }
     }
@@ -396,21 +394,21 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_f16_kernel(const float* __r
     if (c + 1 < c_hi) request(c + 1);  // lands under the MFMAs below
 #pragma unroll
     for (int k16 = 0; k16 < WG_PX / 16; ++k16) {
-      wg_f16x8 dh[WN], dl[WN];
+      f16x8 dh[WN], dl[WN];
 #pragma unroll
       for (int x = 0; x < WN; ++x) {
         const int off = ((wi * WN + x) * 32 + lr) * WG_LD + k16 * 16 + kh;
-        dh[x] = *reinterpret_cast<const wg_f16x8*>(&Dh[off]);
-        dl[x] = *reinterpret_cast<const wg_f16x8*>(&Dl[off]);
+        dh[x] = *reinterpret_cast<const f16x8*>(&Dh[off]);
+        dl[x] = *reinterpret_cast<const f16x8*>(&Dl[off]);
       }
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
-        wg_f16x8 ah[WK], al[WK];
+        f16x8 ah[WK], al[WK];
 #pragma unroll
         for (int y = 0; y < WK; ++y) {
           const int off = ((wj * WK + y) * 32 + lr) * WG_LD + k16 * 16 + kh;
-          ah[y] = *reinterpret_cast<const wg_f16x8*>(&Ah[t][off]);
-          al[y] = *reinterpret_cast<const wg_f16x8*>(&Al[t][off]);
+          ah[y] = *reinterpret_cast<const f16x8*>(&Ah[t][off]);
+          al[y] = *reinterpret_cast<const f16x8*>(&Al[t][off]);
         }
 #pragma unroll
         for (int x = 0; x < WN; ++x)
