@@ -12,6 +12,7 @@ chain of  GEMM(+stats epilogue) -> finalize -> next GEMM(normalise prologue).
 engine itself only allocates memory and orders launches.
 """
 import contextlib
+import itertools
 import os
 import threading
 import warnings
@@ -23,6 +24,7 @@ from .ops import (ACT_NONE, ACT_RELU, ACT_SIGMOID, A_NORM_RELU, A_PAIR, A_PLAIN,
                   SOFTMAX_MODES)
 
 EPS = 1e-5  # nn.GroupNorm / nn.BatchNorm default used everywhere in the reference
+_SERIALS = itertools.count(1)
 
 
 def check_crop_side(S):
@@ -58,6 +60,7 @@ class Engine:
             raise ValueError("trunk must be 'f16x3' (fp16 matrix cores, 3-term split), 'f16q8' (fp16 main term + "
                              "fp8 correction terms, include/mmmot_hip.h hq8) or 'f32' (exact fp32 MFMA)")
         self.trunk = trunk            # arithmetic the trunk currently runs in (the range guard may lower it)
+        self.serial = next(_SERIALS)  # identifies this engine in the stamps of appearance rows (TrackingNet.encode_appearance)
         self.trunk_requested = trunk
         # Range guard (include/mmmot_hip.h: mmmot_trunk_range_read).  The hq8 / hl16 activation formats have a finite
         # range: e4m3 copies saturate above 1792 (products of that element become fp16-class), the fp16 `hi` half
@@ -74,6 +77,7 @@ class Engine:
         self._n_forward = 0
         self._range_buf = self._range_host = self._range_pending = None
         self._range_win0 = 0  # first forward whose trunk launches no inspected / queued read-back covers yet
+        self._guard_plan = None  # plan of the latest guarded trunk (settle_range judges the counters against it)
         self.out_of_range_window = None  # (first, last) forward indices of the latest asynchronous detection
         self._busy = threading.Lock()  # see forward()
         self._last_stream = None
@@ -369,33 +373,16 @@ class Engine:
         first = self._n_forward == 0
         guard = self.trunk != 'f32' and not capturing
         # ---- verdict of the previous forward's asynchronous read-back -------------------------------------------
-        if guard and self._range_pending is not None:
-            ev, w0, w1 = self._range_pending
-            if ev is True or ev.query():
-                self._range_pending = None
-                v = [int(x) & 0xFFFFFFFF for x in self._range_host.tolist()[:3]]
-                sat, clamp, c11 = [(a - b) & 0xFFFFFFFF for a, b in zip(v, self._range_seen)]
-                self._range_seen = v
-                lower = self._range_verdict(plan, sat, clamp, c11, w1 - w0 + 1)
-                if lower is not None:
-                    self._range_event(plan, lower, sat, clamp, c11, recomputed=False, window=(w0, w1))
-                    guard = self.trunk != 'f32'
+        if guard and self._range_pending is not None and self._inspect_pending(plan):
+            guard = self.trunk != 'f32'
         sync = guard and (first or (self.range_check_every > 0 and self._n_forward % self.range_check_every == 0))
         if sync:
             # open the window of this forward.  What the counters hold at this point belongs to the forwards since the last
             # inspected read-back (an asynchronous copy that had not completed when this check came round is superseded
             # by this synchronous read): they get their verdict and event here instead of being dropped
-            sat, clamp, c11 = self.read_range(reset=True)
-            w0, w1 = self._range_win0, self._n_forward - 1
-            if self._range_pending is not None:  # the copy that did not complete: its forwards are in these counters too
-                w0 = min(w0, self._range_pending[1])
-            self._range_pending = None
-            if w1 >= w0:
-                lower = self._range_verdict(plan, sat, clamp, c11, w1 - w0 + 1)
-                if lower is not None:
-                    self._range_event(plan, lower, sat, clamp, c11, recomputed=False, window=(w0, w1))
-                    sync = self.trunk != 'f32'  # lowered to the exact arithmetic: nothing left to check
-            self._range_win0 = self._n_forward
+            self._check_window(plan)
+            sync = self.trunk != 'f32'  # lowered to the exact arithmetic: nothing left to check
+        self._guard_plan = plan
         ops.trunk_range_bind(blk)
         try:
             self.appearance(plan, crops, cat)
@@ -421,6 +408,55 @@ class Engine:
         elif sync:
             self._range_win0 = self._n_forward + 1  # checked (and, if need be, recomputed) synchronously
         self._n_forward += 1
+
+    def _inspect_pending(self, plan):
+        """Verdict of the queued asynchronous read-back once its copy has completed (no synchronisation).  Returns
+        True when it was inspected."""
+        ev, w0, w1 = self._range_pending
+        if not (ev is True or ev.query()):
+            return False
+        self._range_pending = None
+        v = [int(x) & 0xFFFFFFFF for x in self._range_host.tolist()[:3]]
+        sat, clamp, c11 = [(a - b) & 0xFFFFFFFF for a, b in zip(v, self._range_seen)]
+        self._range_seen = v
+        lower = self._range_verdict(plan, sat, clamp, c11, w1 - w0 + 1)
+        if lower is not None:
+            self._range_event(plan, lower, sat, clamp, c11, recomputed=False, window=(w0, w1))
+        return True
+
+    def _check_window(self, plan):
+        """Synchronous verdict on the counters of every trunk launch since the last inspected read-back (one 16-byte
+        read, which synchronises the stream); an event for those forwards when they left the range."""
+        sat, clamp, c11 = self.read_range(reset=True)
+        w0, w1 = self._range_win0, self._n_forward - 1
+        if self._range_pending is not None:  # the copy that did not complete: its forwards are in these counters too
+            w0 = min(w0, self._range_pending[1])
+        self._range_pending = None
+        if w1 >= w0:
+            lower = self._range_verdict(plan, sat, clamp, c11, w1 - w0 + 1)
+            if lower is not None:
+                self._range_event(plan, lower, sat, clamp, c11, recomputed=False, window=(w0, w1))
+        self._range_win0 = self._n_forward
+
+    def settle_range(self, upto=None):
+        """The range guard's verdict on this engine's trunk launches up to forward `upto` (default: all so far) now, not at
+        a later forward.  A queued read-back that covers `upto` is waited for and inspected (free once the caller has read
+        that forward's results); forwards no read-back covers yet are judged by a synchronous read of the counter block;
+        forwards already judged cost nothing.  TrackingNet.appearance_is_current calls it for the forward that made the
+        rows, so rows from an out-of-range trunk are recomputed before they are reused."""
+        plan = self._guard_plan
+        if (plan is None or not self.range_guard or self._range_buf is None or self.trunk == 'f32'
+                or not hasattr(self.ops, 'trunk_range_bind')):
+            return
+        upto = self._n_forward - 1 if upto is None else min(int(upto), self._n_forward - 1)
+        with self._exclusive():
+            pend = self._range_pending
+            if pend is not None and pend[1] <= upto <= pend[2]:
+                if pend[0] is not True:
+                    pend[0].synchronize()
+                self._inspect_pending(plan)
+            elif upto >= self._range_win0:
+                self._check_window(plan)
 
     def _skippool(self, plan, s, x, hw, C, cat, hl16=False):
         """reference modules/appear_net.py:9-32 for stage s -> cat[:, 128 s : 128 (s+1)]."""
@@ -652,8 +688,14 @@ class Engine:
         return link, ne[0], ne[1]
 
     # ---- whole forward -------------------------------------------------------
-    def forward(self, plan, crops=None, points=None):
-        """Returns dict(det [nR,Lt], link flat, new [nR,Lt], end [nR,Lt], feats F, cat)."""
+    def forward(self, plan, crops=None, points=None, appearance=None):
+        """Returns dict(det [nR,Lt], link flat, new [nR,Lt], end [nR,Lt], feats F, cat).
+
+        ``appearance``: precomputed appearance rows (fp32 [.., 512], contiguous, on the weights' device: the output of
+        TrackingNet.encode_appearance) in place of the image branch for some frames - (a) every row, [Lt, 512] with
+        crops=None: neither the trunk nor the SkipPool heads run; (b) the first frame's N rows of a B = 1 pair plan with
+        the crops of the second frame only: the trunk runs on those M crops into cat[N:].  The rows are copied into the
+        appearance half of `cat`; everything after it is the same launch sequence."""
         # One forward at a time per engine: the workspace arena (self.ws), the packed weights and the range-guard
         # block are mutable state behind the integer handle of the registered operators (mmmot_amd/torch_ops.py), which
         # an operator schema cannot express.  A second thread entering while a forward is being issued is refused; a
@@ -661,28 +703,44 @@ class Engine:
         # kernels still read and write the same workspace), so consecutive forwards are ordered whatever stream they
         # are launched on.  Outputs: det / link / new / end are freshly allocated per call; 'F' and 'cat' are views
         # of the workspace, valid until the next forward of this engine.
+        with self._exclusive():
+            pin = getattr(self.ops, 'on_current_stream', None)
+            if pin is None:
+                return self._forward(plan, crops, points, appearance)
+            cur = self._follow_stream(next((t for t in (crops, points, appearance) if t is not None), None))
+            with pin(cur):
+                return self._forward(plan, crops, points, appearance)
+
+    @contextlib.contextmanager
+    def _exclusive(self):
+        """one launch sequence at a time on this engine (see forward)"""
         if not self._busy.acquire(blocking=False):
             raise RuntimeError('mmmot_amd: concurrent forwards on one engine (its workspace arena is shared mutable state); '
                                'use one TrackingNet per thread, or serialise the calls')
         try:
-            pin = getattr(self.ops, 'on_current_stream', None)
-            if pin is None:
-                return self._forward(plan, crops, points)
-            ref = crops if crops is not None else points
-            cur = None
-            if ref is not None and ref.is_cuda:
-                cur = torch.cuda.current_stream(ref.device)
-                last = self._last_stream
-                if last is not None and last != cur and not torch.cuda.is_current_stream_capturing():
-                    cur.wait_stream(last)
-                self._last_stream = cur
-            with pin(cur):
-                return self._forward(plan, crops, points)
+            yield
         finally:
             self._busy.release()
 
-    def _check_crops(self, plan, crops):
-        Lt = plan.Lt
+    def _follow_stream(self, ref):
+        """torch's current stream on `ref`'s device, ordered behind the stream of this engine's previous launch sequence
+        (whose kernels still use the same workspace); None for host tensors"""
+        if ref is None or not ref.is_cuda:
+            return None
+        cur = torch.cuda.current_stream(ref.device)
+        last = self._last_stream
+        if last is not None and last != cur and not torch.cuda.is_current_stream_capturing():
+            cur.wait_stream(last)
+        self._last_stream = cur
+        return cur
+
+    def _pinned(self, cur):
+        """the operator backend's stream pinning for a launch sequence on `cur` (nothing for backends without it)"""
+        pin = getattr(self.ops, 'on_current_stream', None)
+        return contextlib.nullcontext() if pin is None else pin(cur)
+
+    def _check_crops(self, plan, crops, Lt=None):
+        Lt = plan.Lt if Lt is None else Lt
         ok_f32 = crops is not None and crops.dtype == torch.float32 and tuple(crops.shape) == (Lt, 3, plan.S, plan.S)
         ok_u8 = crops is not None and crops.dtype == torch.uint8 and tuple(crops.shape) == (Lt, plan.S, plan.S, 3)
         if not (ok_f32 or ok_u8) or not crops.is_contiguous():
@@ -690,25 +748,81 @@ class Engine:
                              'the uint8 [%d,%d,%d,3] crops of the resize' % (Lt, plan.S, plan.S, Lt, plan.S, plan.S))
         check_crop_side(plan.S)  # here, before any launch (appearance() repeats it for its direct callers)
 
-    def image_first(self, plan, crops):
+    def _check_appearance(self, plan, crops, appearance):
+        """Host checks of supplied appearance rows and the crops beside them, before anything is queued (see forward).
+        Returns the number of leading rows supplied: Lt (shape a) or the first frame's N (shape b)."""
+        if not ((0 in plan.rows) or (2 in plan.rows)):
+            raise ValueError('appearance rows given for a plan whose rows %r do not use the image branch' % (plan.rows,))
+        dev = next(t for t in self.P['vgg'][0].values() if torch.is_tensor(t)).device
+        if (not torch.is_tensor(appearance) or appearance.dtype != torch.float32 or appearance.dim() != 2
+                or appearance.shape[1] != 512 or not appearance.is_contiguous() or appearance.device != dev):
+            raise ValueError('appearance rows must be a contiguous fp32 [L,512] tensor on %s (TrackingNet.encode_appearance), '
+                             'got %s' % (dev, 'a %s %s tensor on %s' % (appearance.dtype, tuple(appearance.shape),
+                                                                       appearance.device)
+                                         if torch.is_tensor(appearance) else type(appearance).__name__))
+        n = int(appearance.shape[0])
+        if crops is None:
+            if n != plan.Lt:
+                raise ValueError('appearance rows without crops must cover every detection of the plan: [%d,512], got '
+                                 '[%d,512]' % (plan.Lt, n))
+            return n
+        if plan.B != 1 or len(plan.frame_counts[0]) != 2:
+            raise ValueError('appearance rows beside crops need a plan of one frame pair (B = 1, two frames)')
+        N, M = plan.frame_counts[0]
+        L = int(crops.shape[0]) if crops.dim() > 0 else -1
+        if n + L > plan.Lt:
+            raise ValueError('appearance rows (%d) and crops (%d) are given for the same frame: rows for the first frame '
+                             '(%d detections), crops for the second (%d)' % (n, L, N, M))
+        if n != N:
+            raise ValueError('appearance rows beside crops belong to the first frame: [%d,512], got [%d,512]' % (N, n))
+        self._check_crops(plan, crops, Lt=M)
+        if crops.device != dev:
+            raise ValueError('crops on %s, weights on %s' % (crops.device, dev))
+        return n
+
+    def _image_key(self, plan, crops, appearance):
+        """what image_first() leaves in `cat`: the next forward with the same inputs skips its image branch"""
+        key = (crops.data_ptr(), plan.Lt, plan.S, crops.dtype)
+        if appearance is not None:
+            key += (appearance.data_ptr(), int(appearance.shape[0]))
+        return key
+
+    def _image_branch(self, plan, crops, appearance, cat):
+        """the appearance half of `cat`: supplied rows copied in, the trunk (under the range guard) for the rest"""
+        if appearance is None:
+            self._guarded_appearance(plan, crops, cat)
+            return
+        n = int(appearance.shape[0])
+        cat[:n, 0:512].copy_(appearance)  # a device copy, no arithmetic
+        if n < plan.Lt:
+            self._guarded_appearance(plan.tail_crops(), crops, cat[n:])
+
+    def encode(self, plan, crops):
+        """The image branch of `plan`'s crops alone, under the range guard: owned fp32 rows [Lt, 512] (the appearance half
+        of `cat`) and the index of the forward they were computed in."""
+        with self._exclusive():
+            self._check_crops(plan, crops)
+            self._image_token = self._pre_image = None  # `cat` is overwritten: an image branch issued before is gone
+            cur = self._follow_stream(crops)
+            self.dev = crops.device
+            cat = self.buf('cat', plan.Lt, 1024)
+            with self._pinned(cur):
+                self._guarded_appearance(plan, crops, cat)
+            return cat[:, 0:512].clone(), self._n_forward - 1
+
+    def image_first(self, plan, crops, appearance=None):
         """Issue the image branch (trunk + SkipPool heads -> the appearance half of `cat`) of the NEXT ``forward`` now.
         The trunk needs the detections' counts only, not the point split: the reference-shaped call (TrackingNet.forward)
         launches it before it reads ``points_split`` back and builds the full plan, so that ~0.3 ms of host work hide
         behind ~2 ms of device work.  `plan` may be any plan with the same frame counts and crop side (its image tables are
-        the ones used); the next ``forward`` with the same crops tensor skips its own image branch."""
-        if not self._busy.acquire(blocking=False):
-            raise RuntimeError('mmmot_amd: concurrent forwards on one engine (its workspace arena is shared mutable state); '
-                               'use one TrackingNet per thread, or serialise the calls')
-        try:
-            self._check_crops(plan, crops)
-            pin = getattr(self.ops, 'on_current_stream', None)
-            cur = None
-            if crops.is_cuda:
-                cur = torch.cuda.current_stream(crops.device)
-                last = self._last_stream
-                if last is not None and last != cur and not torch.cuda.is_current_stream_capturing():
-                    cur.wait_stream(last)
-                self._last_stream = cur
+        the ones used); the next ``forward`` with the same crops tensor skips its own image branch.  ``appearance``: the
+        first frame's rows of shape (b) of ``forward`` - copied in, the trunk runs on the second frame's crops."""
+        with self._exclusive():
+            if appearance is None:
+                self._check_crops(plan, crops)
+            else:
+                self._check_appearance(plan, crops, appearance)
+            cur = self._follow_stream(crops)
             self.dev = crops.device
             cat = self.buf('cat', plan.Lt, 1024)
             # what was queued before the trunk: the point the LiDAR branch of the coming forward may start from (side stream)
@@ -716,28 +830,26 @@ class Engine:
             if cur is not None and self.pn_beside_trunk and not torch.cuda.is_current_stream_capturing():
                 self._pre_image = torch.cuda.Event()
                 self._pre_image.record(cur)
-            if pin is None:
-                self._guarded_appearance(plan, crops, cat)
-            else:
-                with pin(cur):
-                    self._guarded_appearance(plan, crops, cat)
-            self._image_token = (crops.data_ptr(), plan.Lt, plan.S, crops.dtype)
-        finally:
-            self._busy.release()
+            with self._pinned(cur):
+                self._image_branch(plan, crops, appearance, cat)
+            self._image_token = self._image_key(plan, crops, appearance)
 
-    def _forward(self, plan, crops=None, points=None):
+    def _forward(self, plan, crops=None, points=None, appearance=None):
         rows = plan.rows
         need_img = (0 in rows) or (2 in rows)
         need_pts = (1 in rows) or (2 in rows)
-        dev = crops.device if crops is not None else points.device
+        token, self._image_token = self._image_token, None
+        if appearance is not None:
+            self._check_appearance(plan, crops, appearance)
+        elif need_img:
+            self._check_crops(plan, crops)
+        dev = next(t for t in (crops, appearance, points) if t is not None).device
         self.dev = dev
         Lt = plan.Lt
         cat = self.buf('cat', Lt, 1024)
-        token, self._image_token = self._image_token, None
-        if need_img:
-            self._check_crops(plan, crops)
-        # image_first() ran the image branch of exactly these crops into `cat` already
-        img_done = need_img and token is not None and token == (crops.data_ptr(), Lt, plan.S, crops.dtype)
+        # image_first() ran the image branch of exactly these inputs into `cat` already
+        img_done = (need_img and crops is not None and token is not None
+                    and token == self._image_key(plan, crops, appearance))
         if need_pts:
             kin = int(self.P['pointnet']['w1'].shape[1])  # 3 (xyz) or 4 (xyz + reflectivity)
             if points is None or tuple(points.shape) != (plan.P, kin) or not points.is_contiguous():
@@ -769,11 +881,11 @@ class Engine:
             with self.ops.on_stream(side):
                 self.pointnet(plan, points, cat)
             if not img_done:
-                self._guarded_appearance(plan, crops, cat)
+                self._image_branch(plan, crops, appearance, cat)
             main.wait_stream(side)
         else:
             if need_img and not img_done:
-                self._guarded_appearance(plan, crops, cat)
+                self._image_branch(plan, crops, appearance, cat)
             if need_pts:
                 self.pointnet(plan, points, cat)
         F = self.buf('F', plan.nR, Lt, 512)

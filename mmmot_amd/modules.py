@@ -24,7 +24,7 @@ import torch.nn as nn
 from . import torch_ops
 from .engine import Engine, check_crop_layout
 from .pack import VGG_STAGES, pack_weights
-from .plan import BatchPlan
+from .plan import BatchPlan, CropPlan
 
 
 def _gn(groups, ch):
@@ -357,6 +357,31 @@ class GraphedForward:
         return self.result
 
 
+class StaleAppearanceError(ValueError):
+    """Appearance rows whose stamp no longer holds (TrackingNet.appearance_is_current): encode the frame again."""
+
+
+class AppearanceRows:
+    """Owned appearance rows of one frame's crops (``rows``: fp32 [L, 512] on the model's device, the image branch's
+    output) and the stamp they are valid under: ``stamp`` = (pack version, engine serial, trunk arithmetic, engine
+    forward index the rows were computed in, range events recorded by then).  See TrackingNet.encode_appearance."""
+    __slots__ = ('rows', 'stamp')
+
+    def __init__(self, rows, stamp):
+        self.rows, self.stamp = rows, stamp
+
+    def __len__(self):
+        return int(self.rows.shape[0])
+
+    def split(self, counts):
+        """per-frame AppearanceRows of rows encoded for several frames at once (views of this owned tensor)"""
+        out, r = [], 0
+        for n in counts:
+            out.append(AppearanceRows(self.rows[r:r + int(n)], self.stamp))
+            r += int(n)
+        return out
+
+
 class TrackingNet(nn.Module):
     """Reference-compatible tracking network (modules/tracking_net.py:15-193), HIP forward."""
 
@@ -397,6 +422,7 @@ class TrackingNet(nn.Module):
         self._engine_key = None
         self._plans = {}
         self._img_plans = {}   # image-only plans of forward()'s trunk-first launch, keyed by (frame counts, crop side)
+        self._crop_plans = {}  # CropPlans of encode_appearance, keyed by (crops, crop side, device)
         # forward(): launch the trunk before the point split is read back and the plan is built (MMMOT_IMAGE_FIRST=0: after)
         self.image_first = os.environ.get('MMMOT_IMAGE_FIRST', '1') != '0'
         self.freeze_appearance = False  # training mode: True = frozen eval-mode image features instead of the training trunk
@@ -565,22 +591,38 @@ class TrackingNet(nn.Module):
         return BatchPlan(samples, crop_hw, dev, rows=rows, use_points=(1 in rows or 2 in rows))
 
     # ---- batched entry (no reference counterpart: the reference batch is 1) --
-    def forward_batch(self, plan, crops, points):
+    def forward_batch(self, plan, crops, points, appearance=None):
         """crops [Lt,3,S,S], points [P,3] (device, concatenated over the plan's samples).
-        Returns per-sample reference-shaped tuples."""
+        Returns per-sample reference-shaped tuples.  ``appearance``: the detections' appearance rows [Lt, 512]
+        (``encode_appearance``; AppearanceRows or a tensor) in place of the crops (crops=None): the trunk and the SkipPool
+        heads do not run."""
+        return self._forward_batch(plan, crops, points, appearance)[0]
+
+    def _forward_batch(self, plan, crops, points, appearance=None):
+        """forward_batch -> (per-sample tuples, the trunk's rows [M, 512] of shape (b), else None)"""
+        if appearance is not None:
+            appearance = self._appearance_tensor(appearance)
         self._repack_if_trained()
         if self.training:
             raise NotImplementedError('forward_batch / forward_rows compute the eval-mode forward (call .eval()); the '
                                       'training-mode forward of tracking_model.py:50-66 is model(dets, det_info, dets_split) '
                                       'after .train() - mmmot_amd/train.py')
         eng = self.engine()
+        tail = None
         if eng.ops.name == 'hip':
             # the registered PyTorch-ROCm operator (mmmot_amd/torch_ops.py): CUDA dispatch key only, no CPU kernel
-            det_t, link_t, new_t, end_t = torch.ops.mmmot.forward_batch(
-                crops, points, torch_ops.engine_handle(eng), torch_ops.plan_handle(plan))
+            h = (torch_ops.engine_handle(eng), torch_ops.plan_handle(plan))
+            if appearance is None:
+                det_t, link_t, new_t, end_t = torch.ops.mmmot.forward_batch(crops, points, *h)
+            elif crops is None:
+                det_t, link_t, new_t, end_t = torch.ops.mmmot.forward_batch_appearance(appearance, points, *h)
+            else:
+                det_t, link_t, new_t, end_t, tail = torch.ops.mmmot.forward_pair_appearance(appearance, crops, points, *h)
             out = dict(det=det_t, link=link_t, new=new_t, end=end_t)
         else:  # an injected backend (tests: the torch emulation of the C-ABI)
-            out = eng.forward(plan, crops, points)
+            out = eng.forward(plan, crops, points, appearance=appearance)
+            if appearance is not None and crops is not None:
+                tail = out['cat'][int(appearance.shape[0]):, 0:512].clone()
         res = []
         pi = 0
         nR = plan.nR
@@ -593,7 +635,79 @@ class TrackingNet(nn.Module):
                 links.append(out['link'][o:o + nR * N * M].view(nR, N, M))
                 pi += 1
             res.append((out['det'][:, d0:d1], links, out['new'][:, d0:d1], out['end'][:, d0:d1]))
-        return res
+        return res, tail
+
+    # ---- appearance rows reused across the pairs of a sequence ---------------------------------------------------
+    def encode_appearance(self, crops):
+        """The image branch (VGG trunk + SkipPool heads) of one frame's crops - fp32 [L,3,S,S] or uint8 [L,S,S,3], like
+        ``forward`` - under the same range guard as a forward.  Returns AppearanceRows: owned rows [L, 512] (not a view of
+        the workspace) and their stamp.  In eval mode every crop's row is independent of the crops beside it (folded
+        BatchNorm, one-detection GroupNorm in SkipPool, fixed 256-row pooling chunks), so the rows equal bit for bit the
+        appearance half of a forward over any pair that holds these crops: ``forward_appearance`` / ``forward_batch(...,
+        appearance=)`` use them while ``appearance_is_current``."""
+        self._repack_if_trained()
+        if self.training:
+            raise NotImplementedError('encode_appearance computes the eval-mode image features (call .eval())')
+        S = check_crop_layout(crops)
+        crops = crops.contiguous()
+        eng = self.engine()
+        key = (int(crops.shape[0]), S, str(crops.device))
+        plan = self._crop_plans.get(key)
+        if plan is None:
+            if len(self._crop_plans) > 256:
+                self._crop_plans.clear()
+            plan = self._crop_plans[key] = CropPlan(key[0], S, crops.device)
+        if eng.ops.name == 'hip':
+            rows = torch.ops.mmmot.encode_appearance(crops, torch_ops.engine_handle(eng), torch_ops.plan_handle(plan))
+        else:
+            rows = eng.encode(plan, crops)[0]
+        return AppearanceRows(rows, self._stamp(eng))
+
+    def _stamp(self, eng):
+        """validity stamp of rows the engine's latest trunk launch computed (read after it: a synchronous recompute in a
+        lowered arithmetic is what the rows hold)"""
+        return (self._pack_version, eng.serial, eng.trunk, eng._n_forward - 1, len(eng.range_events))
+
+    def appearance_is_current(self, rows):
+        """True while AppearanceRows may stand in for their crops: same packed weights (no load_state_dict / invalidate
+        / set_trunk / .to() / training re-pack since), same trunk arithmetic, no range event recorded since they were
+        computed, eval mode.  The range guard's asynchronous check lags one forward, so its verdict on the forward that
+        made the rows is taken here first (Engine.settle_range: waits for that forward's read-back - free once its results
+        were read - or reads the counters).  Stale rows are encoded again, never reused: the forwards that take
+        AppearanceRows refuse them (StaleAppearanceError) before any launch."""
+        eng = self._engine
+        pv, serial, trunk, fwd, n_events = rows.stamp
+        if (self.training or eng is None or pv != self._pack_version or eng.serial != serial or eng.trunk != trunk
+                or getattr(self, '_trained_since_pack', False) or not self._packed_is_current()):
+            return False
+        eng.settle_range(upto=fwd)
+        return eng.trunk == trunk and len(eng.range_events) == n_events
+
+    def _appearance_tensor(self, appearance):
+        if isinstance(appearance, AppearanceRows):
+            if not self.appearance_is_current(appearance):
+                raise StaleAppearanceError('appearance rows are stale (weights re-packed, trunk arithmetic changed, a range '
+                                           'event since they were computed, or training mode): encode the frame again')
+            return appearance.rows
+        if not torch.is_tensor(appearance):
+            raise ValueError('appearance must be AppearanceRows (encode_appearance) or a tensor, got %s'
+                             % type(appearance).__name__)
+        return appearance
+
+    def forward_appearance(self, prev_rows, curr_crops, det_info, dets_split, return_rows=False):
+        """``forward(dets, det_info, dets_split)`` of one frame pair with the first frame's appearance rows (AppearanceRows
+        of ``encode_appearance`` or of the previous call) in place of its crops: the trunk runs on the second frame's crops
+        only.  ``det_info`` / ``dets_split`` are the pair's, as for ``forward``.  Returns the same tuple as ``forward``;
+        with return_rows=True also the second frame's AppearanceRows - the first frame's rows of the next pair."""
+        if self.training:
+            raise NotImplementedError('forward_appearance computes the eval-mode forward (call .eval())')
+        if prev_rows is None or curr_crops is None:
+            raise ValueError('forward_appearance needs the first frame\'s rows and the second frame\'s crops')
+        prev = self._appearance_tensor(prev_rows)
+        out, tail = self._forward_rows(curr_crops, det_info, dets_split, (0, 1, 2), prev)
+        if not return_rows:
+            return out
+        return out, AppearanceRows(tail, self._stamp(self._engine))
 
     def capture(self, plan, crops, points):
         """hipGraph of one ``forward_batch`` for a FIXED plan (the C-ABI entry points only launch: no allocation, no
@@ -620,7 +734,7 @@ class TrackingNet(nn.Module):
             return forward_train(self, dets, det_info, dets_split)
         return self.forward_rows(dets, det_info, dets_split, rows=(0, 1, 2))
 
-    def _trunk_first(self, fc, S, crops):
+    def _trunk_first(self, fc, S, crops, appearance=None):
         """The point split is on the HOST already (a pipeline that prepared the points itself, mmmot_amd/pipeline.py): no
         read-back to hide, but the image branch still launches first so that PointNet's small launches run on the engine's
         side stream beside the trunk instead of behind it.  Returns False when the engine is not the HIP one."""
@@ -635,10 +749,10 @@ class TrackingNet(nn.Module):
                 self._img_plans.clear()
             plan_img = BatchPlan([(fc, None)], S, crops.device, rows=(0,), use_points=False)
             self._img_plans[key] = plan_img
-        eng.image_first(plan_img, crops)
+        eng.image_first(plan_img, crops, appearance)
         return True
 
-    def _split_behind_trunk(self, ps_t, fc, S, crops):
+    def _split_behind_trunk(self, ps_t, fc, S, crops, appearance=None):
         """The point split (device tensor) is needed on the host to build the plan; the trunk is not waiting for it.  Copy it
         on a side stream, launch the image branch (Engine.image_first: its tables depend on the frame counts only and are
         cached per (counts, crop side)), then wait for the copy alone: the read-back and the plan build that follows run
@@ -667,13 +781,18 @@ class TrackingNet(nn.Module):
                 self._img_plans.clear()
             plan_img = BatchPlan([(fc, None)], S, dev, rows=(0,), use_points=False)
             self._img_plans[key] = plan_img
-        eng.image_first(plan_img, crops)
+        eng.image_first(plan_img, crops, appearance)
         ev.synchronize()
         return host[:n].numpy().astype(np.int64)
 
     def forward_rows(self, dets, det_info, dets_split, rows=(0, 1, 2)):
         """Single-modality variant: rows=(0,) image-only skips PointNet+fusion, rows=(1,) LiDAR-only
         skips VGG+fusion; the returned tensors hold only the requested modality rows."""
+        return self._forward_rows(dets, det_info, dets_split, rows)[0]
+
+    def _forward_rows(self, dets, det_info, dets_split, rows, appearance=None):
+        """forward_rows; `appearance`: the first frame's rows, `dets` the second frame's crops (forward_appearance).
+        Returns (the forward's tuple, the second frame's rows when appearance is given)."""
         fc = [int(d.item()) if torch.is_tensor(d) else int(d) for d in dets_split]
         rows = tuple(rows)
         need_pts = (1 in rows) or (2 in rows)
@@ -698,22 +817,22 @@ class TrackingNet(nn.Module):
             ps_t = det_info['points_split'].reshape(-1)
             if (need_img and ps_t.is_cuda and crops.is_cuda and self.image_first and not self.training
                     and not torch.cuda.is_current_stream_capturing()):
-                ps = self._split_behind_trunk(ps_t, fc, S, crops)
+                ps = self._split_behind_trunk(ps_t, fc, S, crops, appearance)
                 beside = ps is not None
             elif (need_img and not ps_t.is_cuda and crops.is_cuda and points.is_cuda and self.image_first
                   and not self.training and not torch.cuda.is_current_stream_capturing()):
-                beside = self._trunk_first(fc, S, crops)
+                beside = self._trunk_first(fc, S, crops, appearance)
             if ps is None:
                 ps = ps_t.detach().to('cpu').numpy().astype(np.int64)  # one D2H copy (reference: 2 .item() per detection)
         try:
-            return self._forward_rows_tail(fc, ps, S, rows, need_pts, crops, points, dets, beside)
+            return self._forward_rows_tail(fc, ps, S, rows, need_pts, crops, points, dets, beside, appearance)
         except BaseException:
             if beside and self._engine is not None:  # the image branch that was issued belongs to no forward any more
                 self._engine._image_token = None
                 self._engine._pre_image = None
             raise
 
-    def _forward_rows_tail(self, fc, ps, S, rows, need_pts, crops, points, dets, beside):
+    def _forward_rows_tail(self, fc, ps, S, rows, need_pts, crops, points, dets, beside, appearance=None):
         dev = points.device if points is not None else dets.device
         key = (tuple(fc), None if ps is None else ps.tobytes(), S, rows, str(dev))
         plan = self._plans.get(key)
@@ -730,6 +849,7 @@ class TrackingNet(nn.Module):
             else:
                 plan = BatchPlan([(fc, ps)], S, dev, rows=rows, use_points=need_pts)
             self._plans[key] = plan
-        det, links, new, end = self.forward_batch(plan, crops, points)[0]
+        res, tail = self._forward_batch(plan, crops, points, appearance)
+        det, links, new, end = res[0]
         trans = self.trans() if need_pts else None
-        return det, links, new, end, trans
+        return (det, links, new, end, trans), tail

@@ -14,6 +14,17 @@ the upload, the gather and the resize run beside / under the forward.  Both orde
 inputs: their outputs are bitwise equal (tests/test_pipeline_gpu.py).  The solver, ID bookkeeping and the ego-motion
 alignment of the reference's dataset code stay on the host and are not part of this module (the synthetic sequence has
 an identity ego motion; `FrameFeed(point_transform=...)` is the hook for the alignment of a frame's extracted points).  No CPU fallback: every stage is a C-ABI kernel sequence on the device.
+
+Every frame of a sequence is the second frame of one pair and the first of the next, so the per-pair order runs each
+frame's crops through the VGG trunk twice.  In eval mode a crop's appearance row does not depend on the crops beside it
+(TrackingNet.encode_appearance), and two opt-in orders compute each frame's rows once:
+  ``reuse_appearance=True`` (online): each pair runs the trunk on the new frame's crops only, beside the previous frame's
+      rows (TrackingNet.forward_appearance), and keeps the new rows for the next pair;
+  ``run_offline`` (the whole sequence known): the trunk over the crops of K frames per launch sequence, then the pairs B
+      at a time on the rows (forward_batch with appearance rows).
+Both return the scores of ``run`` bit for bit.  Rows are reused only while TrackingNet.appearance_is_current, which first
+takes the range guard's verdict on the forward that made them: after each hand-off the rows of both frames are checked,
+and rows from an out-of-range trunk, or from weights / an arithmetic that changed since, are encoded again with the pair.  ``stats`` counts the frames the trunk encoded.
 """
 import time
 
@@ -38,12 +49,16 @@ class FrameFeed:
 
 
 class SequencePipeline:
-    def __init__(self, model, size=224, overlap=True, without_reflectivity=True):
+    def __init__(self, model, size=224, overlap=True, without_reflectivity=True, reuse_appearance=False):
         self.model, self.size, self.overlap = model, int(size), bool(overlap)
         self.wo_refl = without_reflectivity
         self.dev = next(model.parameters()).device
         self.side = torch.cuda.Stream(self.dev) if overlap else None
         self.stage_events = None   # set to [] to record HIP events per stage (serial order only)
+        self.reuse_appearance = bool(reuse_appearance)
+        # frames run through the trunk (a frame of a per-pair pair counts once per pair), pairs scored, pairs whose rows
+        # were found stale after their hand-off and were computed again
+        self.stats = {'encoded_frames': 0, 'pairs': 0, 'recomputed_pairs': 0}
 
     # ---- stage A: one frame onto the device and through the two preparation kernels ---------------------------
     def _prepare(self, feed):
@@ -83,17 +98,25 @@ class SequencePipeline:
         return a
 
     # ---- stage B: the pair forward + the packed hand-off -------------------------------------------------------
-    def launch_pair(self, a, b):
-        """queue TrackingNet.forward on frames (a, b); returns the device outputs (nothing waits on the host)"""
+    def _wait(self, *frames):
         cur = torch.cuda.current_stream(self.dev)
-        for x in (a, b):
+        for x in frames:
             if x['ready'] is not None:
                 cur.wait_event(x['ready'])
-        crops = torch.cat([a['crops'], b['crops']])
+
+    @staticmethod
+    def _pair_info(a, b):
         points = torch.cat([a['points'], b['points']]).unsqueeze(0)
         split = np.concatenate([a['split'], a['split'][-1] + b['split'][1:]])
         # the split is on the host already (prep_points read it back): hand it over as a CPU tensor - no D2H in forward
-        det_info = {'points': points, 'points_split': torch.from_numpy(split.astype(np.float32)).unsqueeze(0)}
+        return {'points': points, 'points_split': torch.from_numpy(split.astype(np.float32)).unsqueeze(0)}
+
+    def launch_pair(self, a, b):
+        """queue TrackingNet.forward on frames (a, b); returns the device outputs (nothing waits on the host)"""
+        self._wait(a, b)
+        crops = torch.cat([a['crops'], b['crops']])
+        det_info = self._pair_info(a, b)
+        self.stats['encoded_frames'] += 2
         ev = self.stage_events
         if ev is not None:
             e0 = torch.cuda.Event(enable_timing=True)
@@ -113,6 +136,8 @@ class SequencePipeline:
     def run(self, feeds, on_scores=None):
         """All pairs (t-1, t) of the sequence.  Returns the list of host score tuples (det, [link], new, end) - what
         ``ortools_solve`` is called with; ``on_scores(t, scores)`` is where the host solver would run."""
+        if self.reuse_appearance:
+            return self._run_online(feeds, on_scores)
         res = []
         prev = self.prepare(feeds[0])
         nxt = self.prepare(feeds[1]) if len(feeds) > 1 else None
@@ -125,7 +150,121 @@ class SequencePipeline:
             if on_scores is not None:
                 on_scores(t, sc)
             res.append(sc)
+            self.stats['pairs'] += 1
             prev = cur
+        return res
+
+    # ---- appearance rows computed once per frame -----------------------------------------------------------------
+    def _current(self, a):
+        return a.get('rows') is not None and self.model.appearance_is_current(a['rows'])
+
+    def encode(self, frames):
+        """one trunk launch sequence over the crops of `frames`; each frame keeps its AppearanceRows under 'rows'"""
+        self._wait(*frames)
+        crops = frames[0]['crops'] if len(frames) == 1 else torch.cat([a['crops'] for a in frames])
+        with torch.no_grad():
+            rows = self.model.encode_appearance(crops)
+        for a, r in zip(frames, rows.split([a['n'] for a in frames])):
+            a['rows'] = r
+        self.stats['encoded_frames'] += len(frames)
+
+    def launch_pair_cached(self, a, b):
+        """queue the pair forward on frame a's rows and frame b's crops (TrackingNet.forward_appearance): the trunk runs
+        on b's crops only, and b keeps its rows for the next pair.  a's rows are encoded again first when stale."""
+        if not self._current(a):
+            self.encode([a])
+        self._wait(a, b)
+        with torch.no_grad():
+            out, b['rows'] = self.model.forward_appearance(a['rows'], b['crops'], self._pair_info(a, b),
+                                                           [torch.tensor([a['n']]), torch.tensor([b['n']])],
+                                                           return_rows=True)
+        self.stats['encoded_frames'] += 1
+        return out
+
+    def _checked_scores(self, prev, cur, sc):
+        """After the hand-off (the host has waited for the pair anyway): the range guard's verdict on the trunks that
+        made both frames' rows (appearance_is_current takes it).  Rows it rejects - or that a lowered arithmetic made
+        stale - are computed again and the pair with them; at most two rounds (the guard only lowers f16q8 -> f16x3 ->
+        f32)."""
+        for _ in range(3):
+            if self._current(prev) and self._current(cur):
+                return sc
+            self.stats['recomputed_pairs'] += 1
+            sc = self.hand_off(self.launch_pair_cached(prev, cur))
+        raise RuntimeError('mmmot_amd: the appearance rows of a pair stayed stale after recomputing it three times')
+
+    def _run_online(self, feeds, on_scores):
+        res = []
+        prev = self.prepare(feeds[0])
+        nxt = self.prepare(feeds[1]) if len(feeds) > 1 else None
+        if nxt is not None:
+            self.encode([prev])  # frame 0, once
+        for t in range(1, len(feeds)):
+            cur = nxt
+            out = self.launch_pair_cached(prev, cur)
+            # stage A of the next frame is queued before the host blocks on this pair's scores
+            nxt = self.prepare(feeds[t + 1]) if t + 1 < len(feeds) else None
+            sc = self._checked_scores(prev, cur, self.hand_off(out))
+            if on_scores is not None:
+                on_scores(t, sc)
+            res.append(sc)
+            self.stats['pairs'] += 1
+            prev = cur
+        return res
+
+    def _encode_all(self, frames, K):
+        """rows for every frame: K consecutive frames per trunk launch sequence (fewer where their crops would pass the
+        trunk's 32-bit offsets, Engine.appearance: L*S*S*16 < 2^31 - 64); stale groups again after the range verdict"""
+        cap = (2 ** 31 - 65) // (self.size * self.size * 16)
+        groups, i = [], 0
+        while i < len(frames):
+            j, n = i, 0
+            while j < len(frames) and j - i < K and n + frames[j]['n'] <= cap:
+                n += frames[j]['n']
+                j += 1
+            if j == i:
+                raise ValueError('frame %d: %d crops of %d pixels exceed one trunk launch sequence' % (i, frames[i]['n'],
+                                                                                                      self.size))
+            groups.append(frames[i:j])
+            i = j
+        for _ in range(3):
+            for g in groups:
+                if not all(self._current(a) for a in g):
+                    self.encode(g)
+            if all(self._current(a) for a in frames):
+                return
+        raise RuntimeError('mmmot_amd: the appearance rows of the sequence stayed stale after encoding it three times')
+
+    def run_offline(self, feeds, frames_per_encode=16, pairs_per_forward=8, on_scores=None):
+        """The whole sequence at once (every frame known up front): stage A for every frame, the trunk over the crops of
+        `frames_per_encode` frames per launch sequence (throughput-mode occupancy), then the pairs `pairs_per_forward` at
+        a time on the rows (forward_batch with appearance rows: PointNet, fusion and the head batched).  Returns the list
+        of ``run``; ``on_scores(t, scores)`` is called in pair order once each batch of pairs is on the host."""
+        K, B = int(frames_per_encode), int(pairs_per_forward)
+        if K < 1 or B < 1:
+            raise ValueError('frames_per_encode and pairs_per_forward must be >= 1')
+        frames = [self.prepare(f) for f in feeds]
+        if len(frames) < 2:
+            return []
+        self._encode_all(frames, K)
+        res = []
+        for g0 in range(1, len(frames), B):
+            ts = range(g0, min(g0 + B, len(frames)))
+            samples, rows, points = [], [], []
+            for t in ts:
+                a, b = frames[t - 1], frames[t]
+                samples.append(([a['n'], b['n']], np.concatenate([a['split'], a['split'][-1] + b['split'][1:]])))
+                rows += [a['rows'].rows, b['rows'].rows]
+                points += [a['points'], b['points']]
+            plan = self.model.make_plan(samples, self.size)
+            with torch.no_grad():
+                outs = self.model.forward_batch(plan, None, torch.cat(points), appearance=torch.cat(rows))
+            for t, o in zip(ts, outs):
+                sc = self.hand_off(tuple(o) + (None,))
+                if on_scores is not None:
+                    on_scores(t, sc)
+                res.append(sc)
+                self.stats['pairs'] += 1
         return res
 
 

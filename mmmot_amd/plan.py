@@ -304,3 +304,35 @@ class BatchPlan:
         if hw not in self.crop_segs:
             self._crop_segments(hw, self.device)
         return self.crop_segs[hw]
+
+    def tail_crops(self):
+        """CropPlan of the second frame of a B = 1 frame pair: the trunk tables when the first frame comes as appearance
+        rows (Engine.forward, shape (b)).  Built on first use and kept with the plan."""
+        if self.B != 1 or len(self.frame_counts[0]) != 2:
+            raise ValueError('appearance rows of the leading frame need a plan of one frame pair (B = 1, two frames)')
+        cp = self.__dict__.get('_tail_crops')
+        if cp is None:
+            cp = self._tail_crops = CropPlan(self.frame_counts[0][1], self.S, self.device)
+        return cp
+
+
+class CropPlan:
+    """The image tables of L crops of side S on their own - what Engine.appearance reads (Lt, S, det_tiles,
+    crop_segments): the trunk of one frame's crops without a pair around them (TrackingNet.encode_appearance,
+    BatchPlan.tail_crops).  The pooling chunks are the ones of BatchPlan, so a crop's rows do not depend on the plan."""
+
+    def __init__(self, L, S, device):
+        self.device = device
+        self.Lt, self.S = int(L), int(S)
+        if self.Lt < 1:
+            raise ValueError('a crop plan needs >= 1 crop')
+        up = TableUpload(device)
+        self.det_tiles = RowTiles([self.Lt], up)
+        self.crop_segs = {}
+        if self.S >= 32:
+            for sh in (4, 8, 16, 32):
+                self._crop_segments((self.S // sh) ** 2, up)
+        up.flush()
+
+    _crop_segments = BatchPlan._crop_segments
+    crop_segments = BatchPlan.crop_segments

@@ -10,6 +10,15 @@ CUDA (= HIP on ROCm) key only:
     mmmot::appearance(Tensor crops, int engine, int plan) -> Tensor      L x 512 image features (appear_net.py:178-190)
     mmmot::pointnet(Tensor points, int engine, int plan) -> Tensor       L x 512 LiDAR features (point_net.py:25-44)
 
+Appearance rows computed once per frame (TrackingNet.encode_appearance) and reused across the pairs of a sequence:
+    mmmot::encode_appearance(Tensor crops, int engine, int plan) -> Tensor
+        L x 512 image features of one frame's crops under the engine's range guard (plan: a CropPlan).
+    mmmot::forward_batch_appearance(Tensor appearance, Tensor? points, int engine, int plan) -> Tensor[]
+        forward_batch with every detection's appearance row given [Lt, 512]: no trunk, no SkipPool heads.
+    mmmot::forward_pair_appearance(Tensor appearance, Tensor crops, Tensor? points, int engine, int plan) -> Tensor[]
+        one frame pair (B = 1) with the first frame's N rows given and the second frame's M crops: the trunk runs on the
+        M crops.  Returns forward_batch's four outputs and the second frame's rows [M, 512] (for the next pair).
+
 ``engine`` / ``plan`` are handles into this module's registries: the packed weights + workspace arena (an
 ``Engine``) and the integer tile / segment tables of one batch shape (a ``BatchPlan``) are host objects that hold
 device memory; they are not tensors and do not belong in an operator signature.  There is no CPU kernel: CPU tensors
@@ -92,6 +101,34 @@ def _pointnet(points, engine, plan):
     return cat[:, 512:].clone()
 
 
+def _encode_appearance(crops, engine, plan):
+    eng, pl = _lookup(engine, plan)
+    return eng.encode(pl, crops)[0]
+
+
+def _forward_batch_appearance(appearance, points, engine, plan):
+    eng, pl = _lookup(engine, plan)
+    out = eng.forward(pl, None, points, appearance=appearance)
+    return [out['det'], out['link'], out['new'], out['end'].clone()]
+
+
+def _forward_batch_appearance_meta(appearance, points, engine, plan):
+    return _forward_batch_meta(appearance, points, engine, plan)
+
+
+def _forward_pair_appearance(appearance, crops, points, engine, plan):
+    eng, pl = _lookup(engine, plan)
+    out = eng.forward(pl, crops, points, appearance=appearance)
+    n = int(appearance.shape[0])
+    return [out['det'], out['link'], out['new'], out['end'].clone(), out['cat'][n:, 0:512].clone()]
+
+
+def _forward_pair_appearance_meta(appearance, crops, points, engine, plan):
+    _, pl = _lookup(engine, plan)
+    rows = appearance.new_empty((pl.Lt - int(appearance.shape[0]), 512), dtype=torch.float32)
+    return _forward_batch_meta(appearance, points, engine, plan) + [rows]
+
+
 def _feat_meta(x, engine, plan):
     _, pl = _lookup(engine, plan)
     return x.new_empty((pl.Lt, 512), dtype=torch.float32)
@@ -106,3 +143,12 @@ _LIB.impl('appearance', _feat_meta, 'Meta')
 _LIB.define('pointnet(Tensor points, int engine, int plan) -> Tensor')
 _LIB.impl('pointnet', _pointnet, 'CUDA')
 _LIB.impl('pointnet', _feat_meta, 'Meta')
+_LIB.define('encode_appearance(Tensor crops, int engine, int plan) -> Tensor')
+_LIB.impl('encode_appearance', _encode_appearance, 'CUDA')
+_LIB.impl('encode_appearance', _feat_meta, 'Meta')
+_LIB.define('forward_batch_appearance(Tensor appearance, Tensor? points, int engine, int plan) -> Tensor[]')
+_LIB.impl('forward_batch_appearance', _forward_batch_appearance, 'CUDA')
+_LIB.impl('forward_batch_appearance', _forward_batch_appearance_meta, 'Meta')
+_LIB.define('forward_pair_appearance(Tensor appearance, Tensor crops, Tensor? points, int engine, int plan) -> Tensor[]')
+_LIB.impl('forward_pair_appearance', _forward_pair_appearance, 'CUDA')
+_LIB.impl('forward_pair_appearance', _forward_pair_appearance_meta, 'Meta')

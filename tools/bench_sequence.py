@@ -1,0 +1,106 @@
+"""Frames/s of the three orders of a tracked sequence in one process (mmmot_amd/pipeline.py): per-pair (every frame
+through the trunk twice, what bench.py's extra.pipeline times), online with cached appearance rows (reuse_appearance=True:
+one trunk over the new frame's crops per pair) and offline (run_offline: the trunk over K frames per launch sequence, the
+pairs B at a time on the rows).  Workload = bench.py's pipeline leg: 100 synthetic KITTI-shaped frames
+(mmmot_amd.synth.make_frame(7000 + t, 120000, n_det), 10-12 detections), 224-pixel 8-bit crops, Fusion A, overlapped
+stage A.  Each repeat runs every mode once, in turn; the wall clock of a run ends in a synchronise; one untimed run of
+every mode first.  The scores of the three modes must be bitwise equal.  Writes <out>/bench_sequence.json.
+
+    python tools/bench_sequence.py --out <dir> [--repeats 3] [--trunk f16x3] [-K 16] [-B 8]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from mmmot_amd import TrackingNet  # noqa: E402
+from mmmot_amd.pipeline import FrameFeed, SequencePipeline  # noqa: E402
+from mmmot_amd.synth import make_frame  # noqa: E402
+from mmmot_amd.weights import init_module  # noqa: E402
+
+KW = dict(seq_len=2, score_arch='branch_cls', appear_arch='vgg', appear_len=512, appear_skippool=True, appear_fpn=False,
+          point_arch='v1', point_len=512, without_reflectivity=True, end_arch='v2', end_mode='avg', test_mode=2,
+          neg_threshold=0.2, dropblock=0, use_dropout=False, score_fusion_arch='A', affinity_op='multiply',
+          softmax_mode='none')
+
+
+def same(a, b):
+    return len(a) == len(b) and all(torch.equal(x[0], y[0]) and all(torch.equal(p, q) for p, q in zip(x[1], y[1]))
+                                    and torch.equal(x[2], y[2]) and torch.equal(x[3], y[3]) for x, y in zip(a, b))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--frames', type=int, default=100)
+    ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--trunk', default='f16x3')
+    ap.add_argument('-K', '--frames-per-encode', type=int, default=16)
+    ap.add_argument('-B', '--pairs-per-forward', type=int, default=8)
+    args = ap.parse_args()
+    if args.repeats < 3 or args.frames < 2:
+        raise SystemExit('--repeats must be >= 3 and --frames >= 2')
+    dev = torch.device('cuda', 0)
+    model = TrackingNet(**KW)
+    init_module(model, seed=0)
+    model.eval().to(dev)
+    model.set_trunk(args.trunk)
+    n = args.frames
+    ndet = np.random.default_rng(5).integers(10, 13, n)
+    with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as pool:
+        feeds = [FrameFeed(*f) for f in pool.map(lambda t: make_frame(7000 + t, 120000, int(ndet[t])), range(n))]
+    K, B = args.frames_per_encode, args.pairs_per_forward
+    modes = {
+        'per_pair': lambda p: p.run(feeds),
+        'online': lambda p: p.run(feeds),
+        'offline': lambda p: p.run_offline(feeds, frames_per_encode=K, pairs_per_forward=B),
+    }
+    make = {'per_pair': lambda: SequencePipeline(model, 224), 'offline': lambda: SequencePipeline(model, 224),
+            'online': lambda: SequencePipeline(model, 224, reuse_appearance=True)}
+    results, stats, fps = {}, {}, {k: [] for k in modes}
+    for name, run in modes.items():  # untimed: workspace growth, plan caches, first-forward range checks
+        results[name] = run(make[name]())
+    for _ in range(args.repeats):
+        for name, run in modes.items():
+            pipe = make[name]()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = run(pipe)
+            torch.cuda.synchronize()
+            fps[name].append((n - 1) / (time.perf_counter() - t0))
+            stats[name] = dict(pipe.stats)
+            if not same(res, results['per_pair']):
+                raise SystemExit('%s: scores differ from the per-pair order' % name)
+    med = {k: float(np.median(v)) for k, v in fps.items()}
+    rec = {
+        'frames_per_s': {k: round(v, 1) for k, v in med.items()},
+        'frames_per_s_runs': {k: [round(x, 1) for x in v] for k, v in fps.items()},
+        'spread': {k: round((max(v) - min(v)) / med[k], 4) for k, v in fps.items()},
+        'speedup_vs_per_pair': {k: round(med[k] / med['per_pair'], 3) for k in modes},
+        'bitwise_equal': True,
+        'stats': stats,
+        'trunk': model.engine().trunk,
+        'range_events': len(model.engine().range_events),
+        'frames': n, 'repeats': args.repeats, 'frames_per_encode': K, 'pairs_per_forward': B,
+        'device': torch.cuda.get_device_name(dev),
+        'workload': '%d synthetic KITTI-shaped frames (make_frame(7000 + t, 120000, n_det)), %d-%d detections (mean %.1f), '
+                    '224x224 8-bit crops, Fusion A, overlapped stage A; frames/s = (frames - 1) pairs per wall second, '
+                    'median of the repeats' % (n, ndet.min(), ndet.max(), ndet.mean()),
+    }
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_sequence.json'), 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
+if __name__ == '__main__':
+    main()
