@@ -25,20 +25,30 @@ returned (det / link / new / end scores of its pairs, float32 .npy, at most
 64 MB) to DIR.  The inputs and weights are seeded, so two builds run with the
 same arguments can be compared output for output.
 
-Arithmetic legs.  The headline (``value``, ``dtype``, ``roofline``) is the
+Plain run and ``--full``.  A plain run does only what the headline figure needs:
+it builds the headline workload, runs W warm-up and K timed steps, writes
+``--dump-outputs`` and prints the result line.  Everything else the benchmark
+measures or checks (the CPU baseline, parity against the goldens, the other
+arithmetic legs and configs, the per-launch-class tables, latency, pipeline and
+prep legs, telemetry, per-rank and solo figures) runs only with ``--full``, in
+the same process (the solo steps of an N-rank run before the headline leg, the
+rest after it).  ``--dry`` always fabricates the record of a ``--full`` run.
+
+Arithmetic legs (``--full``).  The headline (``value``, ``dtype``, ``roofline``) is the
 ``--trunk`` mode, by default ``f16x3`` - the fp32-class arithmetic (3-term fp16
 hi/lo split, 22 significand bits, score error ~3e-5 against the fp32 reference).
 The same run then times the other trunk mode(s) of ``--extra-trunks`` with the
 same warm-up / step counts and reports them under ``extra`` (``f16q8``: both
 correction terms on the fp8 matrix cores, score error ~3e-4 of the 1e-3 budget).
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+Prints ONE JSON line on rank 0 with the contract fields plus (every run)
   roofline     - the dominant kernel (VGG trunk implicit GEMM), measured with HIP events around every
                  trunk launch inside the timed region; traffic from the committed PMC passes
+  end_to_end   - F_ref / F_exec per pair and the whole-step fraction of the f16x3 ceiling (north_star: >= 0.50)
+and, with ``--full`` (null or absent in a plain run)
   cpu_baseline - the oracle (CPU restatement of the reference) on the host cores
   parity       - L-inf of pair 0 against the committed output of the IMPORTED reference (tests/golden/f_*.npz,
                  same seed) and of the CPU-baseline pairs against the oracle
-  end_to_end   - F_ref / F_exec per pair and the whole-step fraction of the f16x3 ceiling (north_star: >= 0.50)
   extra        - the other arithmetic legs; ``workloads``: the other BASELINE.json configs at their batch sizes
                  (cfg2 B=32, cfg4 32 pairs/GPU, cfg5 image-only 8 / LiDAR-only 32 pairs), each with value, roofline,
                  parity against its reference golden, clock / power telemetry; ``kernels``: per launch class of every
@@ -46,10 +56,12 @@ Prints ONE JSON line on rank 0 with the contract fields plus
                  peak - from HIP events around every operator call of two extra untimed steps (mmmot_amd/profiler.py);
                  ``prep``: point-cloud gather sweeps/s and crop-resize detections/s; ``rccl_world1``: the N-GPU step's
                  collective sequence on a one-rank nccl group (child process); latency of one reference-shaped call
-  host / per_rank - NUMA node and cores the rank bound itself to (sysfs of its GPU), mean shader clock and package power
-                 over the timed steps (hwmon); inputs: three synthetic input sets rotate over the steps (``--input-sets``)
+  host / per_rank - NUMA node and cores the rank bound itself to (sysfs of its GPU; host: every run), mean shader clock
+                 and package power over the timed steps (hwmon); inputs: three synthetic input sets rotate over the steps
+                 (``--input-sets``, every run)
 """
 import argparse
+import contextlib
 import json
 import os
 import socket
@@ -298,7 +310,7 @@ def emit(out, world, detail='stderr'):
 
 
 def dry_record(args, world, G, dt, per_rank, gather_ok, place):
-    """--dry: a record with EVERY key and table the GPU run produces (placeholder numbers, the real strings and the
+    """--dry: a record with EVERY key and table a --full GPU run produces (placeholder numbers, the real strings and the
     profiler's real launch-class names at 25 rows per leg), so that the size / key checks of the stdout line run on
     the real shape without a GPU (tests/test_bench_line.py, tests/test_dist_cpu.py)."""
     from mmmot_amd.profiler import COSTS  # noqa: F401 - the label strings below are the profiler's longest ones
@@ -367,24 +379,29 @@ def parse_args(argv=None):
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--workload', default='cfg3', choices=sorted(WORKLOADS))
     ap.add_argument('--pairs', type=int, default=16, help='frame pairs per step per GPU')
-    ap.add_argument('--cpu-pairs', type=int, default=3, help='timed pairs of the CPU baseline (0 disables)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline leg, also run everything else the benchmark measures or checks: CPU baseline, '
+                         'parity against the goldens, the other trunk modes and configs, hipGraph, latency, pipeline, '
+                         'per-launch-class tables, prep, telemetry, per-rank and solo figures.  A plain run does none of '
+                         'it; the options whose help starts with "--full:" shape only this part')
+    ap.add_argument('--cpu-pairs', type=int, default=3, help='--full: timed pairs of the CPU baseline (0 disables)')
     ap.add_argument('--no-gather', action='store_true')
     ap.add_argument('--graph', action='store_true', help='capture the launch sequence of one step in a hipGraph and replay it')
     ap.add_argument('--trunk', default=HEADLINE_TRUNK, choices=['f16q8', 'f16x3', 'f32'],
                     help="headline VGG trunk arithmetic: f16x3 = fp16 matrix cores, 3-term hi/lo split (fp32-class); "
                          "f16q8 = fp16 main term + fp8 correction terms; f32 = exact fp32 MFMA")
     ap.add_argument('--extra-trunks', default=None,
-                    help="comma list of further trunk modes timed in the same run and reported under 'extra' "
+                    help="--full: comma list of further trunk modes timed in the same run and reported under 'extra' "
                          "(default: the other one of f16x3 / f16q8; 'none' disables)")
-    ap.add_argument('--no-latency', action='store_true', help='skip the B=1 reference-call latency extra')
+    ap.add_argument('--no-latency', action='store_true', help='--full: skip the B=1 reference-call latency extra')
     ap.add_argument('--no-workloads', action='store_true',
-                    help='skip extra.workloads (the other BASELINE.json configs: cfg2 B=32, cfg4 32 pairs/GPU, cfg5 rows)')
+                    help='--full: skip extra.workloads (the other BASELINE.json configs: cfg2 B=32, cfg4 32 pairs/GPU, cfg5 rows)')
     ap.add_argument('--input-sets', type=int, default=3,
                     help='distinct synthetic input sets rotated over the steps (the last timed step runs set 0, the one the '
                          'parity checks look at): 3 x (100 MB crops + 50 MB points) at the default batch exceeds the 256 MiB '
                          'Infinity Cache, so no step finds its inputs cached by the step before')
     ap.add_argument('--no-profile', action='store_true',
-                    help='skip extra.kernels (HIP events around every operator call of a few extra, untimed steps) and '
+                    help='--full: skip extra.kernels (HIP events around every operator call of a few extra, untimed steps) and '
                          'extra.prep (point-cloud gather / crop-resize throughput)')
     ap.add_argument('--no-bind', action='store_true', help='leave the CPU affinity of the rank alone (default: the cores '
                     'of the NUMA node its GPU hangs off)')
@@ -1131,9 +1148,9 @@ def main():
         eng.conv_events = []
         del gather_ev[:]
         phase(steps)
-        with telemetry:
+        with telemetry if args.full else contextlib.nullcontext():  # clock / power sampling: --full only
             dt, res = time_steps(step, steps, barrier)
-        tele = telemetry.result()
+        tele = telemetry.result() if args.full else None
         if dump and rank == 0:
             dump_outputs(res, dump)
         events, eng.conv_events = eng.conv_events, None
@@ -1168,7 +1185,7 @@ def main():
                                             r.get('achieved'), r.get('frac')] for r in summ['classes']]}
             else:
                 torch.cuda.synchronize()
-        if dist_on:
+        if dist_on and args.full:
             # every rank's own wall time per step and the device time of its result gather (pack + RCCL all_gather +
             # unpack, HIP events): `value` uses the MAX over ranks; this shows which rank and which part set it
             import torch.distributed as dist
@@ -1183,7 +1200,7 @@ def main():
             allr = [None] * world
             dist.all_gather_object(allr, mine)
             leg['per_rank'] = {k: [x[k] for x in allr] for k in mine}
-        if rank == 0 and wl['gold'] is not None:
+        if rank == 0 and wl['gold'] is not None and args.full:
             leg['linf_vs_reference_golden'] = golden_linf(res[0], wl['gold'], wl['rows'])
         return leg, res, layers
 
@@ -1215,9 +1232,9 @@ def main():
 
     rows = tuple(int(r) for r in args.rows.split(',') if r != '')
     head_wl = build_workload(args.workload, B, rows, lo, total=G)
-    solo = solo_leg(head_wl, args.trunk, max(args.steps, 20)) if dist_on else None
+    solo = solo_leg(head_wl, args.trunk, max(args.steps, 20)) if dist_on and args.full else None
     model, ins = head_wl['model'], head_wl['ins']
-    do_prof = not args.no_profile
+    do_prof = args.full and not args.no_profile
     kernels = {}
     head, res, layers = run_leg(head_wl, args.trunk, args.steps, args.warmup, graph=args.graph, profile=do_prof,
                                 dump=args.dump_outputs)
@@ -1264,65 +1281,68 @@ def main():
         except OSError:
             pass
 
-    # ---- CPU baseline + parity on the same inputs (rank 0, single-GPU runs only) ----
-    if rank == 0 and world == 1 and args.cpu_pairs > 0 and rows == (0, 1, 2):
-        base, linf = cpu_baseline(model, ins, res, fusion, aff, sm, N, M, max(args.cpu_pairs, 1))
-        out['cpu_baseline'] = base
-        out['parity']['linf_vs_cpu_oracle'] = linf
+    if args.full:
+        # ---- CPU baseline + parity on the same inputs (rank 0, single-GPU runs only) ----
+        if rank == 0 and world == 1 and args.cpu_pairs > 0 and rows == (0, 1, 2):
+            base, linf = cpu_baseline(model, ins, res, fusion, aff, sm, N, M, max(args.cpu_pairs, 1))
+            out['cpu_baseline'] = base
+            out['parity']['linf_vs_cpu_oracle'] = linf
 
-    # ---- the other arithmetic legs, same run, same step counts ----
-    extra = args.extra_trunks
-    if extra is None:
-        extra = {'f16x3': 'f16q8', 'f16q8': 'f16x3'}.get(args.trunk, 'none')
-    out['extra'] = {}
-    for t in [t for t in extra.split(',') if t and t != 'none' and t != args.trunk]:
-        leg, _, _ = run_leg(head_wl, t, args.steps, args.warmup)
-        out['extra'][t] = leg
-    if not args.graph and extra != 'none':
-        # the headline arithmetic again, the step captured once in a hipGraph and replayed (same K / W; no per-launch
-        # HIP events inside a graph, so no roofline entry for this leg)
-        leg, _, _ = run_leg(head_wl, args.trunk, args.steps, args.warmup, graph=True)
-        out['extra'][args.trunk + '_hipgraph'] = {k: leg[k] for k in ('value', 'ms_per_step', 'dtype', 'linf_vs_reference_golden')
-                                                  if k in leg}
-    del head_wl, model, ins, res
-    torch.cuda.empty_cache()
+        # ---- the other arithmetic legs, same run, same step counts ----
+        extra = args.extra_trunks
+        if extra is None:
+            extra = {'f16x3': 'f16q8', 'f16q8': 'f16x3'}.get(args.trunk, 'none')
+        out['extra'] = {}
+        for t in [t for t in extra.split(',') if t and t != 'none' and t != args.trunk]:
+            leg, _, _ = run_leg(head_wl, t, args.steps, args.warmup)
+            out['extra'][t] = leg
+        if not args.graph and extra != 'none':
+            # the headline arithmetic again, the step captured once in a hipGraph and replayed (same K / W; no per-launch
+            # HIP events inside a graph, so no roofline entry for this leg)
+            leg, _, _ = run_leg(head_wl, args.trunk, args.steps, args.warmup, graph=True)
+            out['extra'][args.trunk + '_hipgraph'] = {k: leg[k] for k in ('value', 'ms_per_step', 'dtype',
+                                                                          'linf_vs_reference_golden') if k in leg}
+        del head_wl, model, ins, res
+        torch.cuda.empty_cache()
 
-    # ---- the other BASELINE.json configs at their batch sizes (same arithmetic, same K / W) ----
-    if not args.no_workloads and args.workload == 'cfg3' and rows == (0, 1, 2):
-        wls = {}
-        for key, name, Bw, wrows in EXTRA_WORKLOADS:
-            wl = build_workload(name, Bw, wrows, rank * Bw)
-            leg, _, _ = run_leg(wl, args.trunk, args.steps, args.warmup, profile=do_prof)
-            if 'kernels' in leg:
-                kernels[key] = leg.pop('kernels')
-            N_, M_, S_, pts_, fusion_ = wl['shape']
-            leg['config'] = '%s: Fusion %s, N=M=%d, %dx%d crops, %d pts/det, %d pairs/step/GPU, modality rows %s' % (
-                name, fusion_, N_, S_, S_, pts_, Bw, wrows)
-            leg['unit'] = 'frame-pairs/s'
-            wls[key] = leg
-            del wl
-            torch.cuda.empty_cache()
-        out['extra']['workloads'] = wls
+        # ---- the other BASELINE.json configs at their batch sizes (same arithmetic, same K / W) ----
+        if not args.no_workloads and args.workload == 'cfg3' and rows == (0, 1, 2):
+            wls = {}
+            for key, name, Bw, wrows in EXTRA_WORKLOADS:
+                wl = build_workload(name, Bw, wrows, rank * Bw)
+                leg, _, _ = run_leg(wl, args.trunk, args.steps, args.warmup, profile=do_prof)
+                if 'kernels' in leg:
+                    kernels[key] = leg.pop('kernels')
+                N_, M_, S_, pts_, fusion_ = wl['shape']
+                leg['config'] = '%s: Fusion %s, N=M=%d, %dx%d crops, %d pts/det, %d pairs/step/GPU, modality rows %s' % (
+                    name, fusion_, N_, S_, S_, pts_, Bw, wrows)
+                leg['unit'] = 'frame-pairs/s'
+                wls[key] = leg
+                del wl
+                torch.cuda.empty_cache()
+            out['extra']['workloads'] = wls
 
-    # ---- the collective path of the N-GPU run, executed on this one GPU (RCCL, world size 1) ----
-    if rank == 0 and world == 1 and not dist_on and not args.no_workloads:
-        out['extra']['rccl_world1'] = rccl_world1_leg(dev)
+        # ---- the collective path of the N-GPU run, executed on this one GPU (RCCL, world size 1) ----
+        if rank == 0 and world == 1 and not dist_on and not args.no_workloads:
+            out['extra']['rccl_world1'] = rccl_world1_leg(dev)
 
-    if rank == 0 and world == 1 and not args.no_latency:
-        out['extra']['latency'] = latency_b1(dev, args.trunk)
+        if rank == 0 and world == 1 and not args.no_latency:
+            out['extra']['latency'] = latency_b1(dev, args.trunk)
 
-    if rank == 0 and world == 1 and not args.no_latency and not args.no_workloads:
-        out['extra']['pipeline'] = pipeline_leg(dev, args.trunk)
+        if rank == 0 and world == 1 and not args.no_latency and not args.no_workloads:
+            out['extra']['pipeline'] = pipeline_leg(dev, args.trunk)
 
-    if rank == 0 and kernels:
-        out['extra']['kernels'] = dict(
-            kernels, columns=['launch class', 'launches per step', 'ms per step', 'bound', 'achieved', 'fraction of that peak'],
-            how='HIP events (torch.cuda.Event on the launch stream) around every operator call of %d untimed steps behind each '
-            'leg\'s timed region (mmmot_amd/profiler.py).  bound mfma: achieved = algorithmic TFLOP/s-equivalent against %.0f '
-            '(f16 MFMA dense peak / 3); hbm: algorithmic TB/s against %.0f; latency: under 5 us of roofline time per launch.  '
-            'device_ms_per_step = sum of the rows (compare the leg\'s ms_per_step)' % (PROFILE_STEPS, PEAK_F16_MFMA_TFLOPS / 3.0, 8.0))
-    if rank == 0 and world == 1 and do_prof and not args.no_workloads:
-        out['extra']['prep'] = prep_leg(dev)
+        if rank == 0 and kernels:
+            out['extra']['kernels'] = dict(
+                kernels,
+                columns=['launch class', 'launches per step', 'ms per step', 'bound', 'achieved', 'fraction of that peak'],
+                how='HIP events (torch.cuda.Event on the launch stream) around every operator call of %d untimed steps behind '
+                'each leg\'s timed region (mmmot_amd/profiler.py).  bound mfma: achieved = algorithmic TFLOP/s-equivalent '
+                'against %.0f (f16 MFMA dense peak / 3); hbm: algorithmic TB/s against %.0f; latency: under 5 us of roofline '
+                'time per launch.  device_ms_per_step = sum of the rows (compare the leg\'s ms_per_step)'
+                % (PROFILE_STEPS, PEAK_F16_MFMA_TFLOPS / 3.0, 8.0))
+        if rank == 0 and world == 1 and do_prof and not args.no_workloads:
+            out['extra']['prep'] = prep_leg(dev)
 
     if rank == 0:
         emit(out, world, args.detail)

@@ -128,3 +128,25 @@ def test_dump_outputs_writes_the_last_timed_step_the_same_on_every_run(tmp_path)
     idx = np.load(tmp_path / 's1' / 'pair_index.npy')
     assert np.array_equal(idx, np.load(tmp_path / 's2' / 'pair_index.npy')) and 1 < len(idx) < 40
     assert np.array_equal(np.load(tmp_path / 's1' / 'det.npy'), np.stack([res[int(i)][0].numpy() for i in idx]))
+
+
+def test_plain_run_record_fits_and_keeps_the_contract():
+    """A run without --full records the headline leg only: no cpu_baseline, no golden parity, no extra legs, no
+    telemetry.  Its line still carries every contract key (the --full-only blocks as null) and the headline figures."""
+    b = _bench()
+    assert b.parse_args([]).full is False and b.parse_args(['--full']).full is True
+    with open(os.path.join(ROOT, 'tests', 'golden', 'bench_record_r05.json')) as f:
+        full = json.load(f)
+    plain = {k: v for k, v in full.items() if k not in ('cpu_baseline', 'extra')}
+    plain['parity'] = {'tolerance': full['parity']['tolerance']}
+    plain['host'] = dict(full['host'], telemetry=None)
+    line = b.compact_line(plain)
+    assert len(line) <= b.LINE_LIMIT and '\n' not in line
+    c = json.loads(line)
+    for k in b.REQUIRED_KEYS:
+        assert k in c, k
+    assert c['cpu_baseline'] is None and c['parity'] == {'tolerance': 1e-3}
+    assert c['value'] == full['value'] and c['ms_per_step'] == full['ms_per_step'] and c['dtype'] == 'f16x3'
+    assert c['roofline']['frac'] == full['roofline']['frac'] and c['end_to_end']['whole_step_frac'] is not None
+    assert not set(c) & {'workloads', 'arithmetic_legs', 'kernels', 'latency_ms_b1', 'pipeline', 'rccl_world1', 'prep',
+                         'dropped_for_size'}

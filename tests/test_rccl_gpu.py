@@ -94,16 +94,16 @@ def test_uneven_shards_of_250_pairs_over_8_ranks_through_the_ragged_gather(one_r
 
 
 def test_bench_forced_dist_cfg4_end_to_end():
-    """`python bench.py --gpus 1 --force-dist --workload cfg4`: the N-GPU step (nccl process group, barrier, forward of
-    the rank's shard, flat all_gather of the scores, max-over-ranks timing) end to end on one GPU; the JSON carries every
-    rank's step time and the device time of its gather"""
+    """`python bench.py --gpus 1 --force-dist --workload cfg4 --full`: the N-GPU step (nccl process group, barrier, forward
+    of the rank's shard, flat all_gather of the scores, max-over-ranks timing) end to end on one GPU; the JSON carries every
+    rank's step time and the device time of its gather (per_rank and the golden parity: --full)"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--force-dist', '--workload', 'cfg4',
-                        '--pairs', '4', '--steps', '2', '--warmup', '1', '--cpu-pairs', '0', '--extra-trunks', 'none',
+                        '--pairs', '4', '--steps', '2', '--warmup', '1', '--full', '--cpu-pairs', '0', '--extra-trunks', 'none',
                         '--no-latency', '--no-workloads'], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][-1])

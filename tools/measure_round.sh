@@ -7,10 +7,11 @@ R=$PWD
 O=$R/gpurun_out/$tag
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-# (--no-profile: the rocprof passes count exactly warm-up + timed steps; extra.kernels comes from the default run above)
+# (--no-profile: the rocprof passes count exactly warm-up + timed steps; extra.kernels comes from the --full run above)
 Q="--cpu-pairs 0 --extra-trunks none --no-latency --no-workloads --no-profile"
-# the driver's command line (defaults: cfg3, 16 pairs/step, f16x3; extra: f16q8, hipGraph, the other BASELINE configs, RCCL, latency)
-timeout 600 python $R/bench.py --steps 20 --warmup 5 > $O/bench_default.out 2> $O/bench_default.err; cp $R/gpurun_out/bench_detail_n1.json $O/bench_detail_n1.json
+# every leg (defaults: cfg3, 16 pairs/step, f16x3; --full: f16q8, hipGraph, the other BASELINE configs, RCCL, latency)
+timeout 600 python $R/bench.py --full --steps 20 --warmup 5 > $O/bench_default.out 2> $O/bench_default.err
+grep '^BENCH_DETAIL ' $O/bench_default.err | cut -c14- > $O/bench_detail_n1.json  # the full record
 # kernel tables: the headline workload and the other BASELINE configs at their batch sizes
 stats() {  # name, bench arguments
   local name=$1; shift
