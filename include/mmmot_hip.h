@@ -634,6 +634,31 @@ int mmmot_score_loss(const float* x, int ldx, const float* y, const float* mrow,
 int mmmot_ghm_loss(const float* x, int ldx, const float* y, float ignore, float scale, int R, int C, int bins,
                    float momentum, double* acc_sum, float* g, int ldg, float* PL, int accumulate, void* stream);
 
+/* Frame-pair association (reference solvers.py:9-138, ortools_solve with det_split = [N, M]; csrc/assign.hip), exact,
+ * additive in ABI 10.  The binary program of the two frames is a maximum-weight bipartite matching: with, in fp64,
+ * a_i = det_i + new_i, ua_i = max(0, a_i + end_i) (i < N), b_j = det_{N+j} + end_{N+j}, vb_j = max(0, b_j + new_{N+j})
+ * (j < M) and g_ij = link_ij + a_i - ua_i + b_j - vb_j, its optimum is sum ua + sum vb + max over matchings of
+ * sum max(g_ij, 0).  One workgroup per pair runs a shortest-augmenting-path assignment with fp64 duals, ties to the
+ * smallest index: results are deterministic and do not depend on the pair's place in the batch.
+ *   det / new_score / end_score: fp32, pair p's L = N + M scores at [pairs[4p + 2], + L);
+ *   link: fp32, pair p's row-major N x M block at pairs[4p + 3];  pairs: int32 [B][4] = (N, M, score offset, link offset);
+ *   max_nm >= max over pairs of N and M, 1 <= max_nm <= 512 (LDS sizing; a pair outside [1, max_nm] is not solved and
+ *   gets a NaN objective);
+ *   out: fp32, pair p's block at out_off[p] = [det L | new L | end L | link N*M], the 0 / 1 values of ortools_solve's
+ *   assign_det / assign_new / assign_end / assign_link[0]: a matched (i, j) has det = 1 on both, new_i = end_j = 1,
+ *   end_i = new_j = 0, link_ij = 1 (only pairs with g_ij > 0 are matched); an unmatched frame-0 (frame-1) detection has
+ *   det = new = end = [ua_i > 0] ([vb_j > 0]);  objective: fp64 [B], the optimum of the program.
+ * Scores must be finite (a NaN gain counts as no gain).  Returns MMMOT_EINVAL on a null pointer, B < 1 or max_nm outside
+ * [1, 512] before any launch. */
+int mmmot_associate_pairs(const float* det, const float* new_score, const float* end_score, const float* link,
+                          const int* pairs, int B, int max_nm, float* out, const int* out_off, double* objective,
+                          void* stream);
+/* tests / A-B: which kernel serves mmmot_associate_pairs - 0 = automatic (max_nm <= 128: one wave with the link block
+ * staged in LDS; above: four waves reading it from global memory), 1 / 2 = one / four waves
+ * reading global memory, 3 / 4 = one / four waves with the LDS stage (max_nm <= 128, else MMMOT_EINVAL).  Results do not
+ * depend on it, bit for bit. */
+int mmmot_set_assign_variant(int variant);
+
 /* MFMA fragment-layout self test: C[32][32] = A[32][K] * B[32][K]^T through
  * the same fragment mapping the GEMM kernels use (K % 8 == 0). */
 int mmmot_selftest_mfma(const float* A, const float* B, float* C, int K, void* stream);

@@ -355,6 +355,14 @@ class HipOps:
                                           max_nm, mode, self._stream())
         _lib.check(st, 'mmmot_softmax_pairs')
 
+    # ---- frame-pair association (include/mmmot_hip.h, csrc/assign.hip) ------------------------------------------
+    def associate_pairs(self, det, new, end, link, pairs, B, max_nm, out, out_off, objective):
+        """B frame pairs solved exactly in one launch; see mmmot_associate_pairs.  pairs / out_off: int32 device tensors."""
+        st = self.lib.mmmot_associate_pairs(_ptr(det), _ptr(new), _ptr(end), _ptr(link), _iptr(pairs), int(B),
+                                            int(max_nm), _ptr(out), _iptr(out_off), _ptr(objective, torch.float64),
+                                            self._stream())
+        _lib.check(st, 'mmmot_associate_pairs')
+
     # ---- training backward of the pairwise block (include/mmmot_hip.h, csrc/backward.hip) -------------------
     def gn_bwd_partial(self, dA, Y, C, sc1, sh1, gamma, beta, relu, tiles, P):
         st = self.lib.mmmot_gn_bwd_partial(_ptr(dA), _ld(dA), _ptr(Y), _ld(Y), C, _ptr(sc1), _ptr(sh1), _ld(sc1),

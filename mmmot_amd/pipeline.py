@@ -25,6 +25,11 @@ frame's crops through the VGG trunk twice.  In eval mode a crop's appearance row
 Both return the scores of ``run`` bit for bit.  Rows are reused only while TrackingNet.appearance_is_current, which first
 takes the range guard's verdict on the forward that made them: after each hand-off the rows of both frames are checked,
 and rows from an out-of-range trunk, or from weights / an arithmetic that changed since, are encoded again with the pair.  ``stats`` counts the frames the trunk encoded.
+
+``associate=True`` adds the association step of ``TrackingModule.predict`` (the ``ortools_solve`` drop-in of
+mmmot_amd.association): each pair's solve is queued behind its forward (``run_offline``: one launch per batch of pairs),
+and the hand-off copies scores and assignment to the host together.  The runs then return (scores, assignment) per pair
+and call ``on_assign(t, assignment)`` beside ``on_scores(t, scores)``; the scores are those of ``associate=False``.
 """
 import time
 
@@ -33,7 +38,8 @@ import torch
 
 from .crops import crop_resize_u8
 from .points import prep_points_batched
-from .tracker_glue import scores_for_solver
+from .association import select
+from .tracker_glue import fetch_solve, queue_solve, scores_for_solver
 
 
 class FrameFeed:
@@ -49,13 +55,14 @@ class FrameFeed:
 
 
 class SequencePipeline:
-    def __init__(self, model, size=224, overlap=True, without_reflectivity=True, reuse_appearance=False):
+    def __init__(self, model, size=224, overlap=True, without_reflectivity=True, reuse_appearance=False, associate=False):
         self.model, self.size, self.overlap = model, int(size), bool(overlap)
         self.wo_refl = without_reflectivity
         self.dev = next(model.parameters()).device
         self.side = torch.cuda.Stream(self.dev) if overlap else None
         self.stage_events = None   # set to [] to record HIP events per stage (serial order only)
         self.reuse_appearance = bool(reuse_appearance)
+        self.associate = bool(associate)
         # frames run through the trunk (a frame of a per-pair pair counts once per pair), pairs scored, pairs whose rows
         # were found stale after their hand-off and were computed again
         self.stats = {'encoded_frames': 0, 'pairs': 0, 'recomputed_pairs': 0}
@@ -133,22 +140,40 @@ class SequencePipeline:
         det, links, new, end, _ = out
         return scores_for_solver(det, links, new, end, self.model.test_mode)
 
-    def run(self, feeds, on_scores=None):
+    def queue_hand_off(self, out, a, b):
+        """associate=True: queue the pair's solve behind its forward (returns the pending hand-off); else ``out``"""
+        if not self.associate:
+            return out
+        det, links, new, end, _ = out
+        return queue_solve([select(det, links, new, end, self.model.test_mode)], [(a['n'], b['n'])])
+
+    def finish_hand_off(self, pending):
+        """the host copy: scores, or (scores, assignment) with associate=True"""
+        return fetch_solve(pending)[0] if self.associate else self.hand_off(pending)
+
+    def _deliver(self, t, sc, on_scores, on_assign):
+        scores, asg = sc if self.associate else (sc, None)
+        if on_scores is not None:
+            on_scores(t, scores)
+        if on_assign is not None and self.associate:
+            on_assign(t, asg)
+
+    def run(self, feeds, on_scores=None, on_assign=None):
         """All pairs (t-1, t) of the sequence.  Returns the list of host score tuples (det, [link], new, end) - what
-        ``ortools_solve`` is called with; ``on_scores(t, scores)`` is where the host solver would run."""
+        ``ortools_solve`` is called with; ``on_scores(t, scores)`` is where the host solver would run.  associate=True:
+        the list of (scores, assignment), assignment as ``ortools_solve`` returns it; ``on_assign(t, assignment)``."""
         if self.reuse_appearance:
-            return self._run_online(feeds, on_scores)
+            return self._run_online(feeds, on_scores, on_assign)
         res = []
         prev = self.prepare(feeds[0])
         nxt = self.prepare(feeds[1]) if len(feeds) > 1 else None
         for t in range(1, len(feeds)):
             cur = nxt
-            out = self.launch_pair(prev, cur)
+            out = self.queue_hand_off(self.launch_pair(prev, cur), prev, cur)
             # stage A of the next frame is queued before the host blocks on this pair's scores
             nxt = self.prepare(feeds[t + 1]) if t + 1 < len(feeds) else None
-            sc = self.hand_off(out)
-            if on_scores is not None:
-                on_scores(t, sc)
+            sc = self.finish_hand_off(out)
+            self._deliver(t, sc, on_scores, on_assign)
             res.append(sc)
             self.stats['pairs'] += 1
             prev = cur
@@ -190,10 +215,10 @@ class SequencePipeline:
             if self._current(prev) and self._current(cur):
                 return sc
             self.stats['recomputed_pairs'] += 1
-            sc = self.hand_off(self.launch_pair_cached(prev, cur))
+            sc = self.finish_hand_off(self.queue_hand_off(self.launch_pair_cached(prev, cur), prev, cur))
         raise RuntimeError('mmmot_amd: the appearance rows of a pair stayed stale after recomputing it three times')
 
-    def _run_online(self, feeds, on_scores):
+    def _run_online(self, feeds, on_scores, on_assign):
         res = []
         prev = self.prepare(feeds[0])
         nxt = self.prepare(feeds[1]) if len(feeds) > 1 else None
@@ -201,12 +226,11 @@ class SequencePipeline:
             self.encode([prev])  # frame 0, once
         for t in range(1, len(feeds)):
             cur = nxt
-            out = self.launch_pair_cached(prev, cur)
+            out = self.queue_hand_off(self.launch_pair_cached(prev, cur), prev, cur)
             # stage A of the next frame is queued before the host blocks on this pair's scores
             nxt = self.prepare(feeds[t + 1]) if t + 1 < len(feeds) else None
-            sc = self._checked_scores(prev, cur, self.hand_off(out))
-            if on_scores is not None:
-                on_scores(t, sc)
+            sc = self._checked_scores(prev, cur, self.finish_hand_off(out))
+            self._deliver(t, sc, on_scores, on_assign)
             res.append(sc)
             self.stats['pairs'] += 1
             prev = cur
@@ -235,11 +259,12 @@ class SequencePipeline:
                 return
         raise RuntimeError('mmmot_amd: the appearance rows of the sequence stayed stale after encoding it three times')
 
-    def run_offline(self, feeds, frames_per_encode=16, pairs_per_forward=8, on_scores=None):
+    def run_offline(self, feeds, frames_per_encode=16, pairs_per_forward=8, on_scores=None, on_assign=None):
         """The whole sequence at once (every frame known up front): stage A for every frame, the trunk over the crops of
         `frames_per_encode` frames per launch sequence (throughput-mode occupancy), then the pairs `pairs_per_forward` at
         a time on the rows (forward_batch with appearance rows: PointNet, fusion and the head batched).  Returns the list
-        of ``run``; ``on_scores(t, scores)`` is called in pair order once each batch of pairs is on the host."""
+        of ``run``; ``on_scores(t, scores)`` is called in pair order once each batch of pairs is on the host.
+        associate=True: each batch of pairs is solved in one launch and copied back with its scores in one copy."""
         K, B = int(frames_per_encode), int(pairs_per_forward)
         if K < 1 or B < 1:
             raise ValueError('frames_per_encode and pairs_per_forward must be >= 1')
@@ -259,6 +284,14 @@ class SequencePipeline:
             plan = self.model.make_plan(samples, self.size)
             with torch.no_grad():
                 outs = self.model.forward_batch(plan, None, torch.cat(points), appearance=torch.cat(rows))
+            if self.associate:
+                sel = [select(o[0], o[1], o[2], o[3], self.model.test_mode) for o in outs]
+                done = fetch_solve(queue_solve(sel, [(frames[t - 1]['n'], frames[t]['n']) for t in ts]))
+                for t, sc in zip(ts, done):
+                    self._deliver(t, sc, on_scores, on_assign)
+                    res.append(sc)
+                    self.stats['pairs'] += 1
+                continue
             for t, o in zip(ts, outs):
                 sc = self.hand_off(tuple(o) + (None,))
                 if on_scores is not None:
@@ -268,9 +301,10 @@ class SequencePipeline:
         return res
 
 
-def time_sequence(model, feeds, size=224, overlap=True, warm=3):
-    """frames/s of the chain over ``feeds`` (wall clock, synchronised on both sides; ``warm`` untimed leading pairs)."""
-    pipe = SequencePipeline(model, size, overlap=overlap)
+def time_sequence(model, feeds, size=224, overlap=True, warm=3, associate=False):
+    """frames/s of the chain over ``feeds`` (wall clock, synchronised on both sides; ``warm`` untimed leading pairs);
+    ``associate``: with the device association of every pair (SequencePipeline(associate=True))."""
+    pipe = SequencePipeline(model, size, overlap=overlap, associate=associate)
     pipe.run(feeds[:warm + 1])
     torch.cuda.synchronize()
     t0 = time.perf_counter()

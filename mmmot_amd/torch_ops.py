@@ -38,6 +38,7 @@ Contract the schema cannot express (the handles hide mutable state):
 import itertools
 import weakref
 
+import numpy as np
 import torch
 
 _LIB = torch.library.Library('mmmot', 'DEF')
@@ -152,3 +153,66 @@ _LIB.impl('forward_batch_appearance', _forward_batch_appearance_meta, 'Meta')
 _LIB.define('forward_pair_appearance(Tensor appearance, Tensor crops, Tensor? points, int engine, int plan) -> Tensor[]')
 _LIB.impl('forward_pair_appearance', _forward_pair_appearance, 'CUDA')
 _LIB.impl('forward_pair_appearance', _forward_pair_appearance_meta, 'Meta')
+
+
+# ---- frame-pair association (mmmot_amd/association.py; csrc/assign.hip) --------------------------------------------
+#   mmmot::associate(Tensor det, Tensor new, Tensor end, Tensor link, Tensor pairs) -> Tensor[]
+#       B frame pairs solved exactly in one launch (mmmot_associate_pairs).  det / new / end / link: flat fp32 device
+#       tensors; pairs: a CPU int32 [B, 4] table (N, M, score offset, link offset) - host data, so that the output sizes
+#       are known without a device read (and the Meta kernel can give them).  Returns [out, objective]: out fp32, pair
+#       p's [det L | new L | end L | link N*M] at offset sum over q < p of 3 (N_q + M_q) + N_q M_q; objective fp64 [B].
+_ASSOC_OPS = []
+MAX_ASSOC = 512
+
+
+def associate_layout(pairs, n_scores=None, n_link=None):
+    """(total output floats, int64 [B] output offsets, max(N, M)) of a pair table; checks the table against the sizes of
+    the score / link buffers when given (the kernel reads what the table says)."""
+    if pairs.device.type != 'cpu' or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 4:
+        raise ValueError('mmmot::associate: pairs must be a CPU int32 [B, 4] table (N, M, score offset, link offset)')
+    if pairs.shape[0] < 1:
+        raise ValueError('mmmot::associate: no pairs')
+    t = pairs.numpy().astype(np.int64)  # host arithmetic in numpy: a few microseconds, not one torch op per line
+    N, M, so, lo = t[:, 0], t[:, 1], t[:, 2], t[:, 3]
+    if np.minimum(N, M).min() < 1 or np.maximum(N, M).max() > MAX_ASSOC:
+        raise ValueError('mmmot::associate: every pair needs 1 <= N, M <= %d' % MAX_ASSOC)
+    if np.minimum(so, lo).min() < 0:
+        raise ValueError('mmmot::associate: negative offset in the pair table')
+    if n_scores is not None and (so + N + M).max() > n_scores:
+        raise ValueError('mmmot::associate: a pair reads past the end of the score buffers')
+    if n_link is not None and (lo + N * M).max() > n_link:
+        raise ValueError('mmmot::associate: a pair reads past the end of the link buffer')
+    sizes = 3 * (N + M) + N * M
+    off = np.cumsum(sizes) - sizes
+    total = int(sizes.sum())
+    if total >= 2 ** 31:
+        raise ValueError('mmmot::associate: output block exceeds 32-bit offsets')
+    return total, torch.from_numpy(off), int(np.maximum(N, M).max())
+
+
+def _associate(det, new, end, link, pairs):
+    n_scores = min(int(det.numel()), int(new.numel()), int(end.numel()))
+    total, off, max_nm = associate_layout(pairs, n_scores, int(link.numel()))
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    B = int(pairs.shape[0])
+    # pair table + output offsets in one pinned block: an asynchronous copy (a pageable one would wait for the stream)
+    host = torch.empty(5 * B, dtype=torch.int32, pin_memory=True)
+    host[:4 * B] = pairs.reshape(-1)
+    host[4 * B:] = off
+    table = host.to(det.device, non_blocking=True)
+    out = torch.empty(total, dtype=torch.float32, device=det.device)
+    obj = torch.empty(B, dtype=torch.float64, device=det.device)
+    _ASSOC_OPS[0].associate_pairs(det, new, end, link, table[:4 * B], B, max_nm, out, table[4 * B:], obj)
+    return [out, obj]
+
+
+def _associate_meta(det, new, end, link, pairs):
+    total, _, _ = associate_layout(pairs)
+    return [det.new_empty((total,), dtype=torch.float32), det.new_empty((int(pairs.shape[0]),), dtype=torch.float64)]
+
+
+_LIB.define('associate(Tensor det, Tensor new, Tensor end, Tensor link, Tensor pairs) -> Tensor[]')
+_LIB.impl('associate', _associate, 'CUDA')
+_LIB.impl('associate', _associate_meta, 'Meta')

@@ -4,9 +4,12 @@
 ``test_mode`` and passes them to ``ortools_solve``, which reads every score with ``.item()``
 (solvers.py:32-45): O(N*M) device synchronisations once the scores live on the GPU.  ``scores_for_solver``
 does the same selection and moves the selected rows to the host in ONE packed copy, returning CPU tensors
-with exactly the shapes the solver indexes.  The solver itself stays the reference's.
+with exactly the shapes the solver indexes.  ``predict_assign`` also solves the association on the device
+(mmmot_amd.association, the ``ortools_solve`` drop-in) and brings scores and assignment back in one copy.
 """
 import torch
+
+from .association import associate, pairs_table, select, split_of, unpack
 
 
 def scores_for_solver(det_score, link_scores, new_score, end_score, test_mode):
@@ -32,3 +35,49 @@ def predict_scores(model, det_imgs, det_info, det_split):
     with torch.no_grad():
         det_score, link_score, new_score, end_score, _ = model(det_imgs, det_info, det_split)
     return scores_for_solver(det_score, link_score, new_score, end_score, model.test_mode)
+
+
+def queue_solve(selected, splits):
+    """Queue the association of B frame pairs behind their forward; nothing waits.  ``selected``: per pair the device
+    rows (det L, [link 1 x N x M], new L, end L) of ``association.select``; ``splits``: per pair (N, M).  Returns the
+    pending hand-off for ``fetch_solve``: one device buffer [det | new | end | link of every pair | solver output]."""
+    splits = [(int(N), int(M)) for N, M in splits]
+    if any(N == 0 or M == 0 for N, M in splits):  # an empty frame: nothing to link, answered on the host
+        return {'host': [scores_for_solver(d.unsqueeze(0), l, n.unsqueeze(0), e.unsqueeze(0), 0)
+                         for d, l, n, e in selected], 'splits': splits}
+    cat = lambda k: torch.cat([(s[k][0] if k == 1 else s[k]).reshape(-1) for s in selected])
+    det, new, end, link = cat(0), cat(2), cat(3), cat(1)
+    S, K = det.numel(), link.numel()
+    buf = torch.cat([det, new, end, link])
+    pairs, offs = pairs_table(splits)
+    out, _ = torch.ops.mmmot.associate(buf[0:S], buf[S:2 * S], buf[2 * S:3 * S], buf[3 * S:], pairs)
+    return {'flat': torch.cat([buf, out]), 'splits': splits, 'offs': offs, 'S': S, 'K': K}
+
+
+def fetch_solve(pending):
+    """The ONE device-to-host copy of ``queue_solve``'s buffer -> per pair (scores, assignment): scores as
+    ``scores_for_solver`` returns them, assignment as ``ortools_solve`` does (CPU tensors)."""
+    if 'host' in pending:
+        return [(sc, associate(sc[0], sc[1], sc[2], sc[3], split)) for sc, split in zip(pending['host'], pending['splits'])]
+    flat = pending['flat'].to('cpu')
+    S, K = pending['S'], pending['K']
+    res, so, lo = [], 0, 0
+    for (N, M), o in zip(pending['splits'], pending['offs']):
+        L = N + M
+        scores = (flat[so:so + L], [flat[3 * S + lo:3 * S + lo + N * M].view(1, N, M)], flat[S + so:S + so + L],
+                  flat[2 * S + so:2 * S + so + L])
+        o += 3 * S + K
+        res.append((scores, unpack(flat[o:o + 3 * L + N * M], N, M)))
+        so += L
+        lo += N * M
+    return res
+
+
+def predict_assign(model, det_imgs, det_info, det_split):
+    """``TrackingModule.predict`` up to the ID bookkeeping: forward, the ``test_mode`` selection and the association on
+    the device, then ONE device-to-host copy.  Returns (scores, assignment): the host scores of ``predict_scores`` and
+    what ``ortools_solve(*scores, det_split)`` returns."""
+    with torch.no_grad():
+        det_score, link_score, new_score, end_score, _ = model(det_imgs, det_info, det_split)
+    sel = select(det_score, link_score, new_score, end_score, model.test_mode)
+    return fetch_solve(queue_solve([sel], [split_of(det_split)]))[0]

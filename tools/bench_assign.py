@@ -1,0 +1,152 @@
+"""Cost of the device frame-pair association (csrc/assign.hip) beside its host stand-ins and inside a tracked sequence.
+
+* device: HIP-event time per launch (median of --iters after warm-up) of mmmot_associate_pairs for B in {1, 16, 64} x
+  N = M in {12, 64, 128} plus one uneven shape, for every kernel variant (0 = the automatic choice);
+* host: the same instances (one pair) through scipy.optimize.milp on the literal two-frame program (tests/association_ref,
+  what ortools' CBC would be handed; ortools itself is not installed) and through linear_sum_assignment on the reduction;
+* pipeline: frames/s of SequencePipeline.run with associate=True against False on tools/bench_sequence.py's workload
+  (synthetic KITTI-shaped frames, 10-12 detections, 224-pixel 8-bit crops, Fusion A), alternating, median of --repeats.
+
+Writes <out>/bench_assign.json and prints it.
+
+    python tools/bench_assign.py --out <dir> [--iters 50] [--frames 40] [--repeats 3]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'tests')):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from mmmot_amd import _lib  # noqa: E402
+from mmmot_amd.association import pairs_table  # noqa: E402
+from mmmot_amd.ops import HipOps  # noqa: E402
+from mmmot_amd.torch_ops import associate_layout  # noqa: E402
+
+
+def instances(B, N, M, seed):
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(B):
+        L = N + M
+        f = lambda *s: rng.standard_normal(s).astype(np.float32)
+        det, new, end, link = f(L), f(L), f(L), f(N, M)
+        new[:N] = 0
+        end[N:] = 0
+        out.append((N, M, (det, new, end, link)))
+    return out
+
+
+def device_ms(ops, insts, variant, iters):
+    splits = [(N, M) for N, M, _ in insts]
+    pairs, _ = pairs_table(splits)
+    cat = lambda k: torch.from_numpy(np.concatenate([x[2][k].reshape(-1) for x in insts])).cuda()
+    det, new, end, link = cat(0), cat(1), cat(2), cat(3)
+    total, off, max_nm = associate_layout(pairs, det.numel(), link.numel())
+    B = len(insts)
+    table = torch.cat([pairs.reshape(-1), off.to(torch.int32)]).cuda()
+    out = torch.empty(total, dtype=torch.float32, device='cuda')
+    obj = torch.empty(B, dtype=torch.float64, device='cuda')
+    assert _lib.load().mmmot_set_assign_variant(variant) == 0
+    try:
+        run = lambda: ops.associate_pairs(det, new, end, link, table[:4 * B], B, max_nm, out, table[4 * B:], obj)
+        for _ in range(3):
+            run()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+    finally:
+        _lib.load().mmmot_set_assign_variant(0)
+    return statistics.median(ts)
+
+
+def host_ms(fn, inst, reps):
+    N, M, (det, new, end, link) = inst
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn(det, new, end, link, N, M)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts)
+
+
+def pipeline_fps(frames, repeats):
+    from concurrent.futures import ThreadPoolExecutor
+
+    from bench_sequence import KW
+    from mmmot_amd import TrackingNet
+    from mmmot_amd.pipeline import FrameFeed, time_sequence
+    from mmmot_amd.synth import make_frame
+    from mmmot_amd.weights import init_module
+    model = TrackingNet(**KW)
+    init_module(model, seed=0)
+    model.eval().cuda()
+    ndet = np.random.default_rng(5).integers(10, 13, frames)
+    with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as pool:
+        feeds = [FrameFeed(*f) for f in pool.map(lambda t: make_frame(7000 + t, 120000, int(ndet[t])), range(frames))]
+    fps = {False: [], True: []}
+    for assoc in (False, True):  # untimed warm run of both
+        time_sequence(model, feeds[:6], 224, associate=assoc)
+    for _ in range(repeats):
+        for assoc in (False, True):
+            fps[assoc].append(time_sequence(model, feeds, 224, associate=assoc)[0])
+    return {'frames': frames, 'repeats': repeats, 'fps_associate_false': round(statistics.median(fps[False]), 2),
+            'fps_associate_true': round(statistics.median(fps[True]), 2),
+            'all_false': [round(x, 2) for x in fps[False]], 'all_true': [round(x, 2) for x in fps[True]]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--iters', type=int, default=50)
+    ap.add_argument('--frames', type=int, default=40)
+    ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--host-reps', type=int, default=3)
+    ap.add_argument('--no-pipeline', action='store_true')
+    args = ap.parse_args()
+    from association_ref import lsa_route, milp_route
+    ops = HipOps()
+    res = {'device_ms_per_launch': [], 'host_ms_per_pair': []}
+    shapes = [(12, 12), (64, 64), (128, 128), (12, 100)]
+    for N, M in shapes:
+        for B in (1, 16, 64):
+            insts = instances(B, N, M, seed=N * 1000 + M + B)
+            row = {'N': N, 'M': M, 'B': B}
+            for v in (0, 1, 2, 3, 4):
+                if v >= 3 and max(N, M) > 128:
+                    continue
+                row['variant%d' % v] = round(device_ms(ops, insts, v, args.iters), 4)
+            row['auto_us_per_pair'] = round(row['variant0'] * 1e3 / B, 2)
+            res['device_ms_per_launch'].append(row)
+            print(json.dumps(row), flush=True)
+        inst = instances(1, N, M, seed=N)[0]
+        h = {'N': N, 'M': M, 'lsa_ms': round(host_ms(lsa_route, inst, args.host_reps), 3)}
+        if N * M <= 64 * 64:  # the literal program at 128 x 128 takes HiGHS too long to be worth the wait
+            h['milp_ms'] = round(host_ms(milp_route, inst, args.host_reps), 3)
+        res['host_ms_per_pair'].append(h)
+        print(json.dumps(h), flush=True)
+    if not args.no_pipeline:
+        res['pipeline'] = pipeline_fps(args.frames, args.repeats)
+        print(json.dumps(res['pipeline']), flush=True)
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_assign.json'), 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
