@@ -15,14 +15,15 @@ import contextlib
 import itertools
 import os
 import threading
-import warnings
 
 import numpy as np
 import torch
 
 from .ops import (ACT_NONE, ACT_RELU, ACT_SIGMOID, A_NORM_RELU, A_PAIR, A_PLAIN, FUSION_MODES, PAIR_OPS,
                   SOFTMAX_MODES)
+from .range_guard import RangeGuard
 
+POOL_INPUT = {'f32': 0, 'hl16': 1, 'hq8': 2}  # the segment mean's `hl16` argument: the format its input rows are stored in
 EPS = 1e-5  # nn.GroupNorm / nn.BatchNorm default used everywhere in the reference
 _SERIALS = itertools.count(1)
 
@@ -59,25 +60,14 @@ class Engine:
         if trunk not in ('f16x3', 'f16q8', 'f32'):
             raise ValueError("trunk must be 'f16x3' (fp16 matrix cores, 3-term split), 'f16q8' (fp16 main term + "
                              "fp8 correction terms, include/mmmot_hip.h hq8) or 'f32' (exact fp32 MFMA)")
-        self.trunk = trunk            # arithmetic the trunk currently runs in (the range guard may lower it)
+        self.trunk = trunk            # arithmetic the trunk currently runs in
         self.serial = next(_SERIALS)  # identifies this engine in the stamps of appearance rows (TrackingNet.encode_appearance)
         self.trunk_requested = trunk
-        # Range guard (include/mmmot_hip.h: mmmot_trunk_range_read).  The hq8 / hl16 activation formats have a finite
-        # range: e4m3 copies saturate above 1792 (products of that element become fp16-class), the fp16 `hi` half
-        # clamps at 65000 (wrong value).  The trunk epilogues count both on the device; the engine reads the counters
-        # synchronously on its first forward (and repeats that forward's trunk when they are hit), asynchronously after
-        # every later one (a 16-byte read-back inspected at the next forward: no synchronisation, one step of lag),
-        # and moves the trunk f16q8 -> f16x3 -> f32 for good.  MMMOT_RANGE_CHECK_EVERY=n adds a synchronous
-        # check-and-recompute every n forwards; MMMOT_RANGE_GUARD=0 disables the guard.  See _guarded_appearance.
-        self.range_guard = os.environ.get('MMMOT_RANGE_GUARD', '1') != '0'
-        self.range_check_every = int(os.environ.get('MMMOT_RANGE_CHECK_EVERY', '0'))
-        self.q8_sat_limit = float(os.environ.get('MMMOT_Q8_SAT_LIMIT', '1e-4'))  # tolerated fraction of saturated elements
+        # the range guard (mmmot_amd/range_guard.py) lowers `trunk` for good when activations leave the range of the
+        # reduced formats, and records here what it found
+        self.guard = RangeGuard(self)
         self.range_events = []
         self.last_out_of_range_forward = None  # index of the latest forward whose out-of-range results were already returned
-        self._n_forward = 0
-        self._range_buf = self._range_host = self._range_pending = None
-        self._range_win0 = 0  # first forward whose trunk launches no inspected / queued read-back covers yet
-        self._guard_plan = None  # plan of the latest guarded trunk (settle_range judges the counters against it)
         self.out_of_range_window = None  # (first, last) forward indices of the latest asynchronous detection
         self._busy = threading.Lock()  # see forward()
         self._last_stream = None
@@ -133,25 +123,18 @@ class Engine:
         self.conv_events = None  # optional list collecting per-launch HIP events (bench.py)
 
     # ---- workspace arena ---------------------------------------------------
-    def buf(self, name, *shape, device=None):
+    def buf(self, name, *shape, device=None, dtype=torch.float32):
         n = 1
         for s in shape:
             n *= int(s)
         t = self.ws.get(name)
-        if t is None or t.numel() < n or (device is not None and t.device != torch.device(device)):
-            t = torch.empty(max(n, 4), dtype=torch.float32, device=device if device is not None else self.dev)
+        if t is None or t.numel() < n or t.dtype != dtype or (device is not None and t.device != torch.device(device)):
+            t = torch.empty(max(n, 4), dtype=dtype, device=device if device is not None else self.dev)
             self.ws[name] = t
         return t[:n].view(*shape)
 
     def buf64(self, name, *shape):
-        n = 1
-        for s in shape:
-            n *= int(s)
-        t = self.ws.get(name)
-        if t is None or t.numel() < n or t.dtype != torch.float64:
-            t = torch.empty(max(n, 4), dtype=torch.float64, device=self.dev)
-            self.ws[name] = t
-        return t[:n].view(*shape)
+        return self.buf(name, *shape, dtype=torch.float64)
 
     def _finalize(self, name, part, tiles, C, NG, gamma, beta):
         sc = self.buf(name + '_sc', tiles.G, C)
@@ -166,6 +149,14 @@ class Engine:
             self.ops.gemm(d[name + '_h16'], tiles, N, K, w_hl16=True, oscale=d[name + '_os'], **kw)
         else:
             self.ops.gemm(d[name], tiles, N, K, **kw)
+
+    def _gemm_gn(self, d, name, tiles, N, K, y, gn, NG, gamma, beta, **kw):
+        """_gemm into the workspace buffer `y` [tiles.R][N] with the statistics epilogue, then the GroupNorm (NG groups)
+        scale / shift of that output (workspace `gn`_sc / _sh): (Y, scale, shift) for the consumer's prologue."""
+        Y = self.buf(y, tiles.R, N)
+        part = self._part(tiles, N)
+        self._gemm(d, name, tiles, N, K, Y=Y, part=part, **kw)
+        return (Y,) + self._finalize(gn, part, tiles, N, NG, gamma, beta)
 
     @contextlib.contextmanager
     def fp32_mlp(self):
@@ -202,8 +193,7 @@ class Engine:
                              '(L*S*S*16 < 2^31): split the batch' % (Lt, S, S))
         x, H, W = crops, S, S
         u8 = crops.dtype == torch.uint8  # the 8-bit crops of the resize [Lt][S][S][3]: ToTensor + Normalize on the device
-        # q8: activations travel as hq8 records (fp16 hi + two e4m3 copies, same bytes)
-        q8 = (self.trunk == 'f16q8') and S >= self.q8_min_crop
+        q8 = self.q8_in_force(S)  # activations travel as hq8 records (fp16 hi + two e4m3 copies, same bytes)
         f16 = self.trunk in ('f16x3', 'f16q8')  # activations travel in the hl16 split-half / hq8 format (same bytes)
         vgg = self.P['vgg']
         # conv1_1 + conv1_2 + pool as one launch when the trunk has the VGG16 head (3 -> 64 -> 64, pool)
@@ -274,7 +264,7 @@ class Engine:
             x, H, W = out, Ho, Wo
             if cv['last']:
                 self._stash('vgg_stage%d' % cv['stage'], x)
-                self._skippool(plan, cv['stage'], x, H * W, cv['cout'], cat, hl16={'hq8': 2, 'hl16': 1, 'f32': 0}[fmt])
+                self._skippool(plan, cv['stage'], x, H * W, cv['cout'], cat, fmt)
 
     def _mean_std(self, dev):
         key = ('mean_std', str(dev))
@@ -282,6 +272,10 @@ class Engine:
             from .crops import MEAN, STD
             self.ws[key] = torch.tensor(list(MEAN) + list(STD), dtype=torch.float32, device=dev)
         return self.ws[key]
+
+    def q8_in_force(self, S):
+        """crops of side S run the hq8 arithmetic: an f16q8 trunk, and crops of at least q8_min_crop pixels"""
+        return self.trunk == 'f16q8' and S >= self.q8_min_crop
 
     def trunk_elements(self, plan):
         """activation elements the trunk writes per forward (the denominator of the range guard's fractions)"""
@@ -292,174 +286,9 @@ class Engine:
             n += plan.Lt * H * H * cv['cout']
         return n
 
-    # ---- range guard ----------------------------------------------------------
-    def _range_block(self, dev):
-        """this engine's own counter block (int32 [4] on `dev`) + its host mirror"""
-        dev = torch.device(dev)
-        if self._range_buf is None or self._range_buf.device != dev:
-            self._range_buf = torch.zeros(4, dtype=torch.int32, device=dev)
-            self._range_host = torch.zeros(4, dtype=torch.int32)
-            if dev.type == 'cuda':
-                self._range_host = self._range_host.pin_memory()
-            self._range_pending = None
-            self._range_seen = [0, 0, 0]  # counter values already accounted for (the block is cumulative)
-        return self._range_buf
-
-    def read_range(self, reset=True):
-        """Synchronous read of this engine's counters: (e4m3-saturated, fp16-clamped, conv1_1 hits) since the last
-        reset.  One stream synchronisation; GraphedForward.check_range() is the caller for captured forwards."""
-        if self._range_buf is None:
-            return 0, 0, 0
-        v = [int(x) & 0xFFFFFFFF for x in self._range_buf.cpu().tolist()[:3]]
-        d = [(a - b) & 0xFFFFFFFF for a, b in zip(v, self._range_seen)]
-        if reset:
-            self._range_seen = v
-        return d[0], d[1], d[2]
-
-    def _range_verdict(self, plan, sat, clamp, c11, window):
-        """arithmetic the counters call for (None: the current one holds)"""
-        q8 = self.trunk == 'f16q8' and plan.S >= self.q8_min_crop
-        if clamp > 0 or (c11 > 0 and not q8):
-            return 'f32'
-        if q8 and (sat > self.q8_sat_limit * self.trunk_elements(plan) * window or c11 > 0):
-            return 'f16x3'
-        return None
-
-    def _range_event(self, plan, lower, sat, clamp, c11, recomputed, window=None):
-        # `affected_forwards` = (first, last): indices (count of forwards of this engine, from 0) of the forwards whose
-        # trunk launches the counters that tripped cover.  recomputed=True: one forward, the current one, and its results
-        # were recomputed in the lowered arithmetic before they were returned.  False (asynchronous read-back): a read-back
-        # is recorded behind forward k and inspected once its copy has completed - possibly several forwards later, and no
-        # new one is queued meanwhile - so it covers every forward since the previous read-back up to k, NOT "the previous
-        # forward": `window` carries exactly that range, stored with the pending copy when it was recorded (ADVICE r4).
-        # Those results were ALREADY RETURNED: the caller discards / repeats the forwards first .. last
-        # (`Engine.forward_index` of a result = the value of `_n_forward - 1` after the call; `last_out_of_range_forward`
-        # = last and `out_of_range_window` = (first, last) keep the latest detection, None while there was none).
-        # `affected_forward` (the last index of the range) is kept for callers of the round-3 interface.
-        if recomputed or window is None:
-            window = (self._n_forward, self._n_forward)
-        ev = dict(forward=self._n_forward, affected_forward=window[1], affected_forwards=tuple(window), was=self.trunk,
-                  now=lower, e4m3_saturated=sat, fp16_clamped=clamp, conv1_1_hits=c11,
-                  trunk_elements=self.trunk_elements(plan), recomputed=recomputed)
-        self.range_events.append(ev)
-        if not recomputed:
-            self.last_out_of_range_forward = window[1]
-            self.out_of_range_window = tuple(window)
-        warnings.warn('mmmot_amd range guard: trunk arithmetic %(was)s -> %(now)s (%(e4m3_saturated)d activation '
-                      'elements beyond the e4m3 range, %(fp16_clamped)d beyond the fp16 range, of %(trunk_elements)d '
-                      'per forward); ' % ev + ('the trunk of this forward is recomputed' if recomputed else
-                                               'detected late: forwards %d..%d of this engine ran out of range and were '
-                                               'already returned' % tuple(window)),
-                      RuntimeWarning, stacklevel=4)
-        self.trunk = lower
-
-    def _guarded_appearance(self, plan, crops, cat):
-        """appearance() under the range guard (see __init__).  Every engine owns its counter block (bound around its
-        trunk launches: mmmot_trunk_range_bind), so engines sharing a device and captured graphs never mix windows.
-        First forward: synchronous check, the trunk is recomputed in the lowered arithmetic when it trips.  Every
-        later forward: the 16-byte block is copied to pinned host memory behind the trunk (asynchronous) and inspected
-        at the start of the NEXT forward - no synchronisation, detection lags by one step (the event says so);
-        `range_check_every` > 0 adds a synchronous check-and-recompute every that many forwards.  Never inside a
-        hipGraph capture: GraphedForward.check_range() reads the block of a captured forward."""
-        ops = self.ops
-        dev = crops.device
-        capturing = torch.cuda.is_current_stream_capturing() if crops.is_cuda else False
-        active = self.range_guard and hasattr(ops, 'trunk_range_bind')
-        if not active:
-            self.appearance(plan, crops, cat)
-            self._n_forward += 1
-            return
-        blk = self._range_block(dev)
-        first = self._n_forward == 0
-        guard = self.trunk != 'f32' and not capturing
-        # ---- verdict of the previous forward's asynchronous read-back -------------------------------------------
-        if guard and self._range_pending is not None and self._inspect_pending(plan):
-            guard = self.trunk != 'f32'
-        sync = guard and (first or (self.range_check_every > 0 and self._n_forward % self.range_check_every == 0))
-        if sync:
-            # open the window of this forward.  What the counters hold at this point belongs to the forwards since the last
-            # inspected read-back (an asynchronous copy that had not completed when this check came round is superseded
-            # by this synchronous read): they get their verdict and event here instead of being dropped (ADVICE r5)
-            self._check_window(plan)
-            sync = self.trunk != 'f32'  # lowered to the exact arithmetic: nothing left to check
-        self._guard_plan = plan
-        ops.trunk_range_bind(blk)
-        try:
-            self.appearance(plan, crops, cat)
-            while sync and self.trunk != 'f32':
-                sat, clamp, c11 = self.read_range(reset=True)
-                lower = self._range_verdict(plan, sat, clamp, c11, 1)
-                if lower is None:
-                    break
-                self._range_event(plan, lower, sat, clamp, c11, recomputed=True)
-                self.appearance(plan, crops, cat)
-        finally:
-            ops.trunk_range_bind(None)
-        if guard and not sync and self.trunk != 'f32' and self._range_pending is None:
-            # stream-ordered: copy the (cumulative) block out and mark the point - inspected by the next forward
-            self._range_host.copy_(blk, non_blocking=True)
-            e = True
-            if dev.type == 'cuda':
-                e = torch.cuda.Event()
-                e.record()
-            # the counters are cumulative: this copy covers the forwards since the previous read-back up to this one
-            self._range_pending = (e, self._range_win0, self._n_forward)
-            self._range_win0 = self._n_forward + 1
-        elif sync:
-            self._range_win0 = self._n_forward + 1  # checked (and, if need be, recomputed) synchronously
-        self._n_forward += 1
-
-    def _inspect_pending(self, plan):
-        """Verdict of the queued asynchronous read-back once its copy has completed (no synchronisation).  Returns
-        True when it was inspected."""
-        ev, w0, w1 = self._range_pending
-        if not (ev is True or ev.query()):
-            return False
-        self._range_pending = None
-        v = [int(x) & 0xFFFFFFFF for x in self._range_host.tolist()[:3]]
-        sat, clamp, c11 = [(a - b) & 0xFFFFFFFF for a, b in zip(v, self._range_seen)]
-        self._range_seen = v
-        lower = self._range_verdict(plan, sat, clamp, c11, w1 - w0 + 1)
-        if lower is not None:
-            self._range_event(plan, lower, sat, clamp, c11, recomputed=False, window=(w0, w1))
-        return True
-
-    def _check_window(self, plan):
-        """Synchronous verdict on the counters of every trunk launch since the last inspected read-back (one 16-byte
-        read, which synchronises the stream); an event for those forwards when they left the range."""
-        sat, clamp, c11 = self.read_range(reset=True)
-        w0, w1 = self._range_win0, self._n_forward - 1
-        if self._range_pending is not None:  # the copy that did not complete: its forwards are in these counters too
-            w0 = min(w0, self._range_pending[1])
-        self._range_pending = None
-        if w1 >= w0:
-            lower = self._range_verdict(plan, sat, clamp, c11, w1 - w0 + 1)
-            if lower is not None:
-                self._range_event(plan, lower, sat, clamp, c11, recomputed=False, window=(w0, w1))
-        self._range_win0 = self._n_forward
-
-    def settle_range(self, upto=None):
-        """The range guard's verdict on this engine's trunk launches up to forward `upto` (default: all so far) now, not at
-        a later forward.  A queued read-back that covers `upto` is waited for and inspected (free once the caller has read
-        that forward's results); forwards no read-back covers yet are judged by a synchronous read of the counter block;
-        forwards already judged cost nothing.  TrackingNet.appearance_is_current calls it for the forward that made the
-        rows, so rows from an out-of-range trunk are recomputed before they are reused."""
-        plan = self._guard_plan
-        if (plan is None or not self.range_guard or self._range_buf is None or self.trunk == 'f32'
-                or not hasattr(self.ops, 'trunk_range_bind')):
-            return
-        upto = self._n_forward - 1 if upto is None else min(int(upto), self._n_forward - 1)
-        with self._exclusive():
-            pend = self._range_pending
-            if pend is not None and pend[1] <= upto <= pend[2]:
-                if pend[0] is not True:
-                    pend[0].synchronize()
-                self._inspect_pending(plan)
-            elif upto >= self._range_win0:
-                self._check_window(plan)
-
-    def _skippool(self, plan, s, x, hw, C, cat, hl16=False):
-        """reference modules/appear_net.py:9-32 for stage s -> cat[:, 128 s : 128 (s+1)]."""
+    def _skippool(self, plan, s, x, hw, C, cat, fmt='f32'):
+        """reference modules/appear_net.py:9-32 for stage s -> cat[:, 128 s : 128 (s+1)]; `fmt`: the format x is stored in"""
+        hl16 = POOL_INPUT[fmt]
         ops, Lt, hd, T = self.ops, plan.Lt, self.P['skippool'][s], plan.det_tiles
         pooled = self.buf('sp_pool', Lt, C)
         first, second, npart = plan.crop_segments(hw)
@@ -492,8 +321,6 @@ class Engine:
         ops.pointnet_layer1(points, pn['w1'], pn['b1'], y1, part, T)
         sc1, sh1 = self._finalize('pn1', part, T, 64, 64, pn['g1'], pn['be1'])
         # conv2..conv5: each consumes relu(gn(previous)) through the GEMM prologue
-        fused = self.pn_fused
-        TD = plan.ptd_tiles if fused else T  # detection-aligned tiles for the fused epilogues
         x, sc, sh = y1, sc1, sh1
         for i, (N, K) in zip((2, 3, 4), ((64, 64), (64, 64), (128, 64))):
             y = self.buf('pn_y%d' % i, Pn, N)
@@ -506,93 +333,72 @@ class Engine:
             sc, sh = self._finalize('pn%d' % i, part, T, N, N, pn['g%d' % i], pn['be%d' % i])
             x = y
         # conv5 128->1024 + GN + ReLU + per-detection average (named max_feats in the reference,
-        # point_net.py:138-148).  Fused: the [P][1024] tensor (1 GiB per cfg3 pair) is never stored - one GEMM
-        # pass for the statistics, one that normalises in the epilogue and emits per-tile column sums.
-        seg1024 = self.buf('pn_seg1024', Lt, 1024)
-        ares = fused and self.mlp == 'f16x3' and 'w5_h16' in pn  # A-resident kernel (hl16 weights only)
-        TH = plan.ptd_half if ares else None
-        if ares:
-            if self.pn_gram:
-                # statistics of conv5's output from the second moments of its 128-channel input: no GEMM pass
-                GT = plan.gram_tiles
-                Gp, Sp = self.buf64('gram_G', GT.T, 128 * 128), self.buf64('gram_S', GT.T, 128)
-                ops.gram_rows(x, 128, sc, sh, GT, Gp, Sp)
-                sc5, sh5 = self.buf('pn5_sc', GT.G, 1024), self.buf('pn5_sh', GT.G, 1024)
-                ops.gn_finalize_gram(Gp, Sp, GT, 128, pn['w5'], pn['b5'], 1024, pn['g5'], pn['be5'], EPS,
-                                     self.buf64('gram_work', GT.G, 128 * 128 + 128), sc5, sh5)
-            else:
-                part = self._part(TH, 1024)
-                ops.gemm_ares(pn['w5_h16'], pn['w5_os'], TD, 1024, 128, x, sc, sh, bias=pn['b5'], part=part)
-                sc5, sh5 = self._finalize('pn5', part, TH, 1024, 1024, pn['g5'], pn['be5'])
-            cs = self.buf('pn_colsum', TH.T, 1024)
-            if self.conv_events is not None:  # bench.py: HIP events around PointNet's dominant launch
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            ops.gemm_ares(pn['w5_h16'], pn['w5_os'], TD, 1024, 128, x, sc, sh, bias=pn['b5'], osc=sc5, osh=sh5,
-                          colsum=cs)
-            if self.conv_events is not None:
-                e1.record()
-                self.conv_events.append(('pn5', Pn, 128, 1024, e0, e1))
-            ops.segment_mean(cs, 1024, plan.det_half_segs, seg1024)
-        elif fused:
-            part = self._part(TD, 1024)
-            self._gemm(pn, 'w5', TD, 1024, 128, X=x, bias=pn['b5'], part=part, sc=sc, sh=sh, amode=A_NORM_RELU)
-            sc5, sh5 = self._finalize('pn5', part, TD, 1024, 1024, pn['g5'], pn['be5'])
-            cs = self.buf('pn_colsum', TD.T, 1024)
-            self._gemm(pn, 'w5', TD, 1024, 128, X=x, bias=pn['b5'], sc=sc, sh=sh, amode=A_NORM_RELU,
-                       osc=sc5, osh=sh5, colsum=cs)
-            ops.segment_mean(cs, 1024, plan.det_tile_segs, seg1024)
-        else:
-            y = self.buf('pn_y5', Pn, 1024)
-            part = self._part(T, 1024)
-            self._gemm(pn, 'w5', T, 1024, 128, X=x, bias=pn['b5'], Y=y, part=part, sc=sc, sh=sh, amode=A_NORM_RELU)
-            sc5, sh5 = self._finalize('pn5', part, T, 1024, 1024, pn['g5'], pn['be5'])
-            ops.segment_mean(y, 1024, plan.det_segs, seg1024, sc=sc5, sh=sh5, relu=True)
+        # point_net.py:138-148)
+        seg1024 = self._norm_relu_pool(plan, 'w5', '5', 128, 1024, x, sc, sh)
         self._stash('pn_seg1024', seg1024)
         # PointNet_v1.conv1 split: per-detection 1024-channel part becomes a gathered bias
         dbias = self.buf('pn_dbias', Lt, 512)
         self._gemm(pn, 'wc1b', D, 512, 1024, X=seg1024, bias=pn['bc1'], Y=dbias)
-        seg512 = self.buf('pn_seg512', Lt, 512)
-        if ares:
-            if self.pn_gram and hasattr(ops, 'gn_finalize_gram_dbias'):
-                # statistics of v = W a + dbias[det] from the second moments of the 64-channel input a = relu(gn(y1)) over
-                # detection-aligned super-tiles: a pass over 256 B per point instead of the 64 -> 512 GEMM's statistics pass
-                GT = plan.gram64_tiles
-                Gp, Sp = self.buf64('gram64_G', GT.T, 64 * 64), self.buf64('gram64_S', GT.T, 64)
-                ops.gram_rows(y1, 64, sc1, sh1, GT, Gp, Sp)
-                scc, shc = self.buf('pnc1_sc', GT.G, 512), self.buf('pnc1_sh', GT.G, 512)
-                ops.gn_finalize_gram_dbias(Gp, Sp, GT, plan.gram64_tile_det, 64, pn['wc1a'], dbias, 512, pn['gc1'], pn['bec1'],
-                                           EPS, self.buf64('gram64_work', GT.G, 64 * 64 + 64), scc, shc)
-            else:
-                part = self._part(TH, 512)
-                ops.gemm_ares(pn['wc1a_h16'], pn['wc1a_os'], TD, 512, 64, y1, sc1, sh1, dbias=dbias,
-                              tile_dbrow=plan.tile_det, part=part)
-                scc, shc = self._finalize('pnc1', part, TH, 512, 512, pn['gc1'], pn['bec1'])
-            cs = self.buf('pn_colsum', TH.T, 512)
-            ops.gemm_ares(pn['wc1a_h16'], pn['wc1a_os'], TD, 512, 64, y1, sc1, sh1, dbias=dbias,
-                          tile_dbrow=plan.tile_det, osc=scc, osh=shc, colsum=cs)
-            ops.segment_mean(cs, 512, plan.det_half_segs, seg512)
-        elif fused:
-            part = self._part(TD, 512)
-            self._gemm(pn, 'wc1a', TD, 512, 64, X=y1, part=part, sc=sc1, sh=sh1, amode=A_NORM_RELU,
-                       dbias=dbias, rowidx=plan.row_det)
-            scc, shc = self._finalize('pnc1', part, TD, 512, 512, pn['gc1'], pn['bec1'])
-            cs = self.buf('pn_colsum', TD.T, 512)
-            self._gemm(pn, 'wc1a', TD, 512, 64, X=y1, sc=sc1, sh=sh1, amode=A_NORM_RELU, dbias=dbias,
-                       rowidx=plan.row_det, osc=scc, osh=shc, colsum=cs)
-            ops.segment_mean(cs, 512, plan.det_tile_segs, seg512)
-        else:
-            yc1 = self.buf('pn_yc1', Pn, 512)
-            part = self._part(T, 512)
-            self._gemm(pn, 'wc1a', T, 512, 64, X=y1, Y=yc1, part=part, sc=sc1, sh=sh1, amode=A_NORM_RELU,
-                       dbias=dbias, rowidx=plan.row_det)
-            scc, shc = self._finalize('pnc1', part, T, 512, 512, pn['gc1'], pn['bec1'])
-            ops.segment_mean(yc1, 512, plan.det_segs, seg512, sc=scc, sh=shc, relu=True)
-        yc2 = self.buf('pn_yc2', Lt, 512)
-        part = self._part(D, 512)
-        self._gemm(pn, 'wc2', D, 512, 512, X=seg512, bias=pn['bc2'], Y=yc2, part=part)
-        sc2, sh2 = self._finalize('pnc2', part, D, 512, 16, pn['gc2'], pn['bec2'])
+        seg512 = self._norm_relu_pool(plan, 'wc1a', 'c1', 64, 512, y1, sc1, sh1, dbias=dbias)
+        yc2, sc2, sh2 = self._gemm_gn(pn, 'wc2', D, 512, 512, 'pn_yc2', 'pnc2', 16, pn['gc2'], pn['bec2'], X=seg512,
+                                      bias=pn['bc2'])
         ops.affine_act(yc2, 512, sc2, sh2, D, ACT_RELU, cat[:, 512:1024])
+
+    def _norm_relu_pool(self, plan, w, s, K, N, x, sc, sh, dbias=None):
+        """One "normalise and pool" layer of PointNet over the points: v = pn[w] relu(gn(x)) + bias (conv5, s = '5') or
+        + dbias[detection of the row] (PointNet_v1.conv1, s = 'c1'), the GroupNorm statistics of v, then the per-detection
+        mean of relu(gn(v)) -> workspace 'pn_seg<N>' [Lt][N].  Fused (pn_fused): the [P][N] tensor (1 GiB per cfg3 pair for
+        conv5) is never stored - one pass for the statistics, one that normalises in the epilogue and emits per-tile column
+        sums; on the A-resident kernel (hl16 weights only) the statistics may come from the second moments of the
+        K-channel input instead (pn_gram: no GEMM pass).  Otherwise the tensor is materialised and pooled."""
+        ops, pn, T, Lt = self.ops, self.P['pointnet'], plan.pt_tiles, plan.Lt
+        name, g, be = 'pn' + s, pn['g' + s], pn['be' + s]
+        if dbias is None:
+            ares_kw = row_kw = dict(bias=pn['b' + s])
+        else:
+            ares_kw, row_kw = dict(dbias=dbias, tile_dbrow=plan.tile_det), dict(dbias=dbias, rowidx=plan.row_det)
+        seg = self.buf('pn_seg%d' % N, Lt, N)
+        if self.pn_fused and self.mlp == 'f16x3' and (w + '_h16') in pn:  # A-resident kernel
+            TD, TH = plan.ptd_tiles, plan.ptd_half  # detection-aligned tiles and their 64-row halves
+            if self.pn_gram and (dbias is None or hasattr(ops, 'gn_finalize_gram_dbias')):
+                # over (detection-aligned, for the gathered bias) super-tiles: a pass over 4 K bytes per point
+                GT, gram = (plan.gram_tiles, 'gram') if dbias is None else (plan.gram64_tiles, 'gram64')
+                Gp, Sp = self.buf64(gram + '_G', GT.T, K * K), self.buf64(gram + '_S', GT.T, K)
+                ops.gram_rows(x, K, sc, sh, GT, Gp, Sp)
+                osc, osh = self.buf(name + '_sc', GT.G, N), self.buf(name + '_sh', GT.G, N)
+                work = self.buf64(gram + '_work', GT.G, K * K + K)
+                if dbias is None:
+                    ops.gn_finalize_gram(Gp, Sp, GT, K, pn[w], pn['b' + s], N, g, be, EPS, work, osc, osh)
+                else:
+                    ops.gn_finalize_gram_dbias(Gp, Sp, GT, plan.gram64_tile_det, K, pn[w], dbias, N, g, be, EPS, work,
+                                               osc, osh)
+            else:
+                part = self._part(TH, N)
+                ops.gemm_ares(pn[w + '_h16'], pn[w + '_os'], TD, N, K, x, sc, sh, part=part, **ares_kw)
+                osc, osh = self._finalize(name, part, TH, N, N, g, be)
+            cs = self.buf('pn_colsum', TH.T, N)
+            timed = self.conv_events is not None and dbias is None  # bench.py: HIP events around PointNet's dominant launch
+            if timed:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            ops.gemm_ares(pn[w + '_h16'], pn[w + '_os'], TD, N, K, x, sc, sh, osc=osc, osh=osh, colsum=cs, **ares_kw)
+            if timed:
+                e1.record()
+                self.conv_events.append((name, plan.P, K, N, e0, e1))
+            ops.segment_mean(cs, N, plan.det_half_segs, seg)
+        elif self.pn_fused:
+            TD = plan.ptd_tiles
+            part = self._part(TD, N)
+            self._gemm(pn, w, TD, N, K, X=x, part=part, sc=sc, sh=sh, amode=A_NORM_RELU, **row_kw)
+            osc, osh = self._finalize(name, part, TD, N, N, g, be)
+            cs = self.buf('pn_colsum', TD.T, N)
+            self._gemm(pn, w, TD, N, K, X=x, sc=sc, sh=sh, amode=A_NORM_RELU, osc=osc, osh=osh, colsum=cs, **row_kw)
+            ops.segment_mean(cs, N, plan.det_tile_segs, seg)
+        else:
+            y, osc, osh = self._gemm_gn(pn, w, T, N, K, 'pn_y' + s, name, N, g, be, X=x, sc=sc, sh=sh, amode=A_NORM_RELU,
+                                        **row_kw)
+            ops.segment_mean(y, N, plan.det_segs, seg, sc=osc, sh=osh, relu=True)
+        return seg
 
     # ---- fusion module A / B / C --------------------------------------------
     def fuse(self, plan, cat, F):
@@ -601,19 +407,15 @@ class Engine:
         mode = FUSION_MODES[self.fusion]
         img, pts = cat[:, 0:512], cat[:, 512:1024]
         if self.fusion == 'A':
-            y0 = self.buf('fu_y0', Lt, 512)
-            part = self._part(D, 512)
-            self._gemm(fu, 'w0', D, 512, 1024, X=cat, bias=fu['b0'], Y=y0, part=part)
-            sc0, sh0 = self._finalize('fu0', part, D, 512, 512, fu['g0'], fu['be0'])
+            y0, sc0, sh0 = self._gemm_gn(fu, 'w0', D, 512, 1024, 'fu_y0', 'fu0', 512, fu['g0'], fu['be0'], X=cat,
+                                         bias=fu['b0'])
             ops.fusion_combine(mode, cat, y0, None, sc0, sh0, None, None, D, F, Lt, 512)
             return
         N = 512 if self.fusion == 'B' else 1024
         ys, scs, shs = [], [], []
         for j, x in enumerate((img, pts)):  # NB: *_p weights consume the IMAGE features
-            y = self.buf('fu_y%d' % j, Lt, N)
-            part = self._part(D, N)
-            self._gemm(fu, 'w%d' % j, D, N, 512, X=x, bias=fu['b%d' % j], Y=y, part=part)
-            sc, sh = self._finalize('fu%d' % j, part, D, N, N, fu['g%d' % j], fu['be%d' % j])
+            y, sc, sh = self._gemm_gn(fu, 'w%d' % j, D, N, 512, 'fu_y%d' % j, 'fu%d' % j, N, fu['g%d' % j],
+                                      fu['be%d' % j], X=x, bias=fu['b%d' % j])
             ys.append(y)
             scs.append(sc[:, N - 512:])
             shs.append(sh[:, N - 512:])
@@ -655,29 +457,18 @@ class Engine:
         ops.segment_mean(ya[:, 0:512], 512, plan.v_segs, V, sc=sc_ne, sh=sh_ne, relu=True,
                          take_max=(self.end_mode != 'avg'))
         self._stash('aff_v', V)
-        vh0 = self.buf('aff_vh0', VT.R, 512)
-        part = self._part(VT, 512)
-        self._gemm(lk, 'nw0', VT, 512, 512, X=V, bias=lk['nb0'], Y=vh0, part=part)
-        scv, shv = self._finalize('aff_v1', part, VT, 512, 1, lk['ng1'], lk['nbe1'])
-        vh1 = self.buf('aff_vh1', VT.R, 128)
-        part = self._part(VT, 128)
-        self._gemm(lk, 'nw3', VT, 128, 512, X=vh0, bias=lk['nb3'], Y=vh1, part=part, sc=scv, sh=shv,
-                 amode=A_NORM_RELU)
-        scv2, shv2 = self._finalize('aff_v4', part, VT, 128, 1, lk['ng4'], lk['nbe4'])
+        vh0, scv, shv = self._gemm_gn(lk, 'nw0', VT, 512, 512, 'aff_vh0', 'aff_v1', 1, lk['ng1'], lk['nbe1'], X=V,
+                                      bias=lk['nb0'])
+        vh1, scv2, shv2 = self._gemm_gn(lk, 'nw3', VT, 128, 512, 'aff_vh1', 'aff_v4', 1, lk['ng4'], lk['nbe4'], X=vh0,
+                                        bias=lk['nb3'], sc=scv, sh=shv, amode=A_NORM_RELU)
         ne = torch.zeros(2, nR, Lt, dtype=torch.float32, device=F.device)  # eval-mode zero padding (tracking_net.py:183-189)
         ops.rowdot(vh1, 128, lk['nw6'], lk['nb6'], VT, ne.view(-1), sc=scv2, sh=shv2, act=ACT_SIGMOID,
                    omap=plan.v_omap)
         # link branch
-        y3 = self.buf('aff_y3', R, 512)
-        part = self._part(PT, 512)
-        self._gemm(lk, 'w3', PT, 512, 512, X=ya[:, 512:1024], bias=lk['b3'], Y=y3, part=part, sc=sc1, sh=sh1,
-                 amode=A_NORM_RELU)
-        sc4, sh4 = self._finalize('aff_4', part, PT, 512, 512, lk['g4'], lk['be4'])
-        y6 = self.buf('aff_y6', R, 128)
-        part = self._part(PT, 128)
-        self._gemm(lk, 'w6', PT, 128, 512, X=y3, bias=lk['b6'], Y=y6, part=part, sc=sc4, sh=sh4,
-                 amode=A_NORM_RELU)
-        sc7, sh7 = self._finalize('aff_7', part, PT, 128, 128, lk['g7'], lk['be7'])
+        y3, sc4, sh4 = self._gemm_gn(lk, 'w3', PT, 512, 512, 'aff_y3', 'aff_4', 512, lk['g4'], lk['be4'],
+                                     X=ya[:, 512:1024], bias=lk['b3'], sc=sc1, sh=sh1, amode=A_NORM_RELU)
+        y6, sc7, sh7 = self._gemm_gn(lk, 'w6', PT, 128, 512, 'aff_y6', 'aff_7', 128, lk['g7'], lk['be7'], X=y3,
+                                     bias=lk['b6'], sc=sc4, sh=sh4, amode=A_NORM_RELU)
         logits = torch.empty(R, dtype=torch.float32, device=F.device)
         ops.rowdot(y6, 128, lk['w9'], lk['b9'], PT, logits, sc=sc7, sh=sh7)
         link = logits
@@ -790,12 +581,12 @@ class Engine:
     def _image_branch(self, plan, crops, appearance, cat):
         """the appearance half of `cat`: supplied rows copied in, the trunk (under the range guard) for the rest"""
         if appearance is None:
-            self._guarded_appearance(plan, crops, cat)
+            self.guard.run(self.appearance, plan, crops, cat)
             return
         n = int(appearance.shape[0])
         cat[:n, 0:512].copy_(appearance)  # a device copy, no arithmetic
         if n < plan.Lt:
-            self._guarded_appearance(plan.tail_crops(), crops, cat[n:])
+            self.guard.run(self.appearance, plan.tail_crops(), crops, cat[n:])
 
     def encode(self, plan, crops):
         """The image branch of `plan`'s crops alone, under the range guard: owned fp32 rows [Lt, 512] (the appearance half
@@ -807,8 +598,8 @@ class Engine:
             self.dev = crops.device
             cat = self.buf('cat', plan.Lt, 1024)
             with self._pinned(cur):
-                self._guarded_appearance(plan, crops, cat)
-            return cat[:, 0:512].clone(), self._n_forward - 1
+                self.guard.run(self.appearance, plan, crops, cat)
+            return cat[:, 0:512].clone(), self.guard.n_forward - 1
 
     def image_first(self, plan, crops, appearance=None):
         """Issue the image branch (trunk + SkipPool heads -> the appearance half of `cat`) of the NEXT ``forward`` now.

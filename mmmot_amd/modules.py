@@ -326,7 +326,7 @@ class GraphedForward:
         self._engine = eng
         self._model = model
         self._pack_version = model._pack_version
-        self._keep = list(eng.ws.values()) + _collect_tensors(eng.P) + [eng._range_buf]
+        self._keep = list(eng.ws.values()) + _collect_tensors(eng.P) + [eng.guard.block]
 
     def stale(self):
         m = self._model
@@ -338,7 +338,7 @@ class GraphedForward:
         this engine since the last check and raises if the captured arithmetic left its range (re-capture after
         ``model.set_trunk('f32')`` or with rescaled inputs)."""
         eng = self._engine
-        sat, clamp, c11 = eng.read_range(reset=True)
+        sat, clamp, c11 = eng.guard.read(reset=True)
         if clamp > 0 or (c11 > 0 and eng.trunk != 'f16q8'):
             raise RuntimeError('mmmot_amd: %d activation elements left the fp16 range inside a captured forward (trunk %s): '
                                'the replayed results are wrong; lower the trunk (set_trunk) and capture again'
@@ -666,13 +666,13 @@ class TrackingNet(nn.Module):
     def _stamp(self, eng):
         """validity stamp of rows the engine's latest trunk launch computed (read after it: a synchronous recompute in a
         lowered arithmetic is what the rows hold)"""
-        return (self._pack_version, eng.serial, eng.trunk, eng._n_forward - 1, len(eng.range_events))
+        return (self._pack_version, eng.serial, eng.trunk, eng.guard.n_forward - 1, len(eng.range_events))
 
     def appearance_is_current(self, rows):
         """True while AppearanceRows may stand in for their crops: same packed weights (no load_state_dict / invalidate
         / set_trunk / .to() / training re-pack since), same trunk arithmetic, no range event recorded since they were
         computed, eval mode.  The range guard's asynchronous check lags one forward, so its verdict on the forward that
-        made the rows is taken here first (Engine.settle_range: waits for that forward's read-back - free once its results
+        made the rows is taken here first (RangeGuard.settle: waits for that forward's read-back - free once its results
         were read - or reads the counters).  Stale rows are encoded again, never reused: the forwards that take
         AppearanceRows refuse them (StaleAppearanceError) before any launch."""
         eng = self._engine
@@ -680,7 +680,7 @@ class TrackingNet(nn.Module):
         if (self.training or eng is None or pv != self._pack_version or eng.serial != serial or eng.trunk != trunk
                 or getattr(self, '_trained_since_pack', False) or not self._packed_is_current()):
             return False
-        eng.settle_range(upto=fwd)
+        eng.guard.settle(upto=fwd)
         return eng.trunk == trunk and len(eng.range_events) == n_events
 
     def _appearance_tensor(self, appearance):

@@ -93,7 +93,7 @@ def test_stamp_follows_weights_trunk_mode_and_range_events():
     eng = m.engine()
     pv, serial, trunk, fwd, nev = r.stamp
     assert (pv, serial, trunk, nev) == (m._pack_version, eng.serial, 'f16x3', len(eng.range_events))
-    assert fwd == eng._n_forward - 1
+    assert fwd == eng.guard.n_forward - 1
     assert m.appearance_is_current(r)
     m.train()
     assert not m.appearance_is_current(r)
@@ -139,8 +139,8 @@ def test_settle_range_records_a_late_event_and_stales_the_rows():
         m.encode_appearance(dets)          # first forward: synchronous check
         r = m.encode_appearance(dets)      # second: asynchronous read-back queued
     eng = m.engine()
-    eng._range_buf[1] += 3                 # fp16-clamped elements counted by that trunk (what the epilogues count) ...
-    eng._range_host[1] += 3                # ... and the completed read-back queued behind it
+    eng.guard.block[1] += 3                # fp16-clamped elements counted by that trunk (what the epilogues count) ...
+    eng.guard.host[1] += 3                 # ... and the completed read-back queued behind it
     with pytest.warns(RuntimeWarning, match='detected late'):
         assert not m.appearance_is_current(r)   # takes the guard's verdict on the forward that made the rows
     ev = eng.range_events[-1]
@@ -157,8 +157,8 @@ def test_rows_the_guard_rejects_are_refused_before_they_are_used():
         m.encode_appearance(dets[N:])          # first forward: synchronous check
         r = m.encode_appearance(dets[:N])      # forward 1: asynchronous read-back queued ...
     eng = m.engine()
-    eng._range_buf[1] += 3                     # ... and its trunk left the fp16 range
-    eng._range_host[1] += 3
+    eng.guard.block[1] += 3                    # ... and its trunk left the fp16 range
+    eng.guard.host[1] += 3
     eng.ops = log = CallLog(eng.ops)
     with pytest.warns(RuntimeWarning, match='detected late'), pytest.raises(StaleAppearanceError):
         m.forward_appearance(r, dets[N:], info, ds)

@@ -275,11 +275,11 @@ def wild_f16q8_model():
     m.eval().to(DEV)
     m.set_trunk('f16q8')
     eng = m.engine()
-    eng.range_guard = False
+    eng.guard.enabled = False
     dets, info, ds = make_pair(2, 2, S, 5, seed=11)
     with torch.no_grad():
         m(dets.to(DEV), {k: v.to(DEV) for k, v in info.items()}, ds)
-    eng.range_guard = True
+    eng.guard.enabled = True
     return m, sd
 
 

@@ -237,8 +237,8 @@ def test_image_first_token_semantics():
     with torch.no_grad():
         want = {k: v.clone() for k, v in eng.forward(plan, crops, points).items() if k in ('det', 'link', 'new', 'end')}
         calls = []
-        orig = eng._guarded_appearance
-        eng._guarded_appearance = lambda *a, **k: (calls.append(1), orig(*a, **k))[1]
+        orig = eng.guard.run
+        eng.guard.run = lambda *a, **k: (calls.append(1), orig(*a, **k))[1]
         eng.image_first(plan_img, crops)
         assert len(calls) == 1 and eng._image_token is not None
         got = eng.forward(plan, crops, points)

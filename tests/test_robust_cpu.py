@@ -1,4 +1,4 @@
-"""Host logic of the trunk range guard (mmmot_amd/engine.py) and the trained-like weight profiles, on the torch
+"""Host logic of the trunk range guard (mmmot_amd/range_guard.py) and the trained-like weight profiles, on the torch
 emulation of the C-ABI (no GPU): the engine must notice activations beyond the e4m3 / fp16 range of the hq8 / hl16
 formats and lower the trunk arithmetic f16q8 -> f16x3 -> f32, so that the outputs stay inside the 1e-3 budget."""
 import warnings
@@ -60,7 +60,7 @@ def test_wild_statistics_trip_the_guard_and_the_result_stays_in_budget():
     assert len(eng.range_events) == n and linf(out2, ref) < 1e-3
     # with the guard off the same model is far outside the budget: the guard is what saves it
     m2, _, _ = build('wild', 0, 1.0)
-    m2.engine().range_guard = False
+    m2.engine().guard.enabled = False
     with torch.no_grad():
         bad = m2(dets, info, ds)
     assert linf(bad, ref) > 1e-2
@@ -105,10 +105,10 @@ def test_calibrated_statistics_do_not_trip_the_guard():
 def test_guard_checks_synchronously_on_the_first_forward_and_on_request():
     m, sd, ins = build('calibrated', 0, 1.0)
     eng = m.engine()
-    eng.range_check_every = 3
+    eng.guard.check_every = 3
     reads = []
-    orig = eng.read_range
-    eng.read_range = lambda reset=True: (reads.append(eng._n_forward), orig(reset))[1]
+    orig = eng.guard.read
+    eng.guard.read = lambda reset=True: (reads.append(eng.guard.n_forward), orig(reset))[1]
     with torch.no_grad():
         for _ in range(7):
             m(*ins)
@@ -130,7 +130,7 @@ def test_guard_detects_late_without_synchronising():
     other, _, _ = build('calibrated', 1, 1.0)  # a second engine on the same "device": its own counter block
     with torch.no_grad():
         other(dets, info, ds)
-    # blow conv3_1's gain up in the PACKED weights of the live engine (no re-pack: _n_forward keeps counting)
+    # blow conv3_1's gain up in the PACKED weights of the live engine (no re-pack: the guard's n_forward keeps counting)
     cv = eng.P['vgg'][4]
     cv['bias'] = cv['bias'] + 3000.0
     with torch.no_grad(), warnings.catch_warnings():
@@ -165,19 +165,19 @@ def test_late_read_back_reports_the_forwards_it_covers():
         m(dets, info, ds)                      # forward 0: synchronous check
         m(dets, info, ds)                      # forward 1: read-back queued (covers 1..1)
         m(dets, info, ds)                      # forward 2: inspects it, queues its own (covers 2..2)
-        assert eng._range_pending[1:] == (2, 2)
+        assert eng.guard.pending[1:] == (2, 2)
         slow = Slow()
-        eng._range_pending = (slow,) + eng._range_pending[1:]
+        eng.guard.pending = (slow,) + eng.guard.pending[1:]
         cv = eng.P['vgg'][4]
         good = cv['bias']
         m(dets, info, ds)                      # forwards 3, 4: the copy is still in flight, nothing new is queued
         cv['bias'] = good + 3000.0             # forward 4 leaves the range
         m(dets, info, ds)
         cv['bias'] = good
-        assert not eng.range_events and eng._range_pending[0] is slow
+        assert not eng.range_events and eng.guard.pending[0] is slow
         slow.done = True
         m(dets, info, ds)                      # forward 5: 2..2 was fine; queues a read-back that covers 3..5
-        assert not eng.range_events and eng._range_pending[1:] == (3, 5)
+        assert not eng.range_events and eng.guard.pending[1:] == (3, 5)
         with pytest.warns(RuntimeWarning, match='forwards 3..5'):
             m(dets, info, ds)                  # forward 6 inspects it
     ev = eng.range_events[0]
@@ -190,7 +190,7 @@ def test_synchronous_check_gives_the_superseded_read_back_its_verdict():
     verdict and an event naming them instead of being dropped without one."""
     m, sd, (dets, info, ds) = build('calibrated', 0, 1.0)
     eng = m.engine()
-    eng.range_check_every = 4
+    eng.guard.check_every = 4
 
     class Slow:
         def query(self):
@@ -199,7 +199,7 @@ def test_synchronous_check_gives_the_superseded_read_back_its_verdict():
     with torch.no_grad():
         m(dets, info, ds)                      # forward 0: synchronous
         m(dets, info, ds)                      # forward 1: read-back queued (1..1)
-        eng._range_pending = (Slow(),) + eng._range_pending[1:]   # ... and never completes
+        eng.guard.pending = (Slow(),) + eng.guard.pending[1:]   # ... and never completes
         cv = eng.P['vgg'][4]
         good = cv['bias']
         cv['bias'] = good + 3000.0

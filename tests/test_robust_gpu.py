@@ -36,7 +36,7 @@ def run_case(profile, seed, scale, trunk, q8_layers='default', N=6, M=5, S=64, p
     m.eval().to(DEV)
     m.set_trunk(trunk)
     eng = m.engine()
-    eng.range_guard = guard
+    eng.guard.enabled = guard
     if q8_layers != 'default':
         eng.q8_layers = q8_layers
     with torch.no_grad(), warnings.catch_warnings():

@@ -39,7 +39,7 @@ def run(profile, seed, scale, trunk, guard, N=6, M=5, S=64, pts=40):
     m.set_ops(TorchOps())
     m.set_trunk(trunk)
     eng = m.engine()
-    eng.range_guard = guard
+    eng.guard.enabled = guard
     cfg = dict(fusion='C', affinity_op='multiply', softmax_mode='none', neg_threshold=0.2, score_arch='branch_cls')
     with torch.no_grad(), warnings.catch_warnings():
         warnings.simplefilter('ignore')
