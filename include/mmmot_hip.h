@@ -659,6 +659,30 @@ int mmmot_associate_pairs(const float* det, const float* new_score, const float*
  * depend on it, bit for bit. */
 int mmmot_set_assign_variant(int variant);
 
+/* Track IDs from pair assignments (reference tracking_model.py:218-292 assign_det_id, then :109-216 align_id, restated
+ * by detection index; csrc/track_ids.hip), additive in ABI 10.  One workgroup walks the B CONSECUTIVE pairs of ONE
+ * sequence in order; queued behind mmmot_associate_pairs it reads that call's `out` / `pairs` / `out_off` as they are.
+ *   blocks: fp32, pair p's [det L | new L | end L | link N*M] at out_off[p] (0 / 1 values);  pairs: int32 [B][4], only
+ *   N and M are read, 0 <= N, M <= max_nm <= 512 (max_nm <= 128: one wave, above: four; same results);
+ *   frame_idx: int32 [B][2], the frame indices (>= 0) of each pair's two frames - a stored frame is "the pair's first
+ *   frame" when the indices are equal;
+ *   state: int32 [MMMOT_TRACK_STATE_INTS], the sequence's state, read and rewritten in full: [0] last_id, [1] index of
+ *   the stored frame or -1, [2] error flags (sticky), [3] detections of the stored frame, then its per-detection IDs
+ *   (-1: not kept / beyond the frame).  A new sequence starts from {0, -1, 0, 0, -1 ...};
+ *   ids_out: int32, pair after pair [ids of frame 0: N | ids of frame 1: M | frame_start | last_id after the pair]: an
+ *   ID of -1 marks a detection with assign_det != 1; frame_start = 1 when the stored frame was the pair's first frame
+ *   (only the second frame is emitted, as align_id returns it), else 0.
+ * A kept second-frame detection with new != 1 must have exactly one link, from a kept row (what a solver output always
+ * gives): otherwise it gets -1 and MMMOT_TRACK_EINFEASIBLE is set in state[2].  MMMOT_TRACK_ECONTRACT: a pair outside
+ * [0, max_nm] (the walk stops there) or a stored frame whose detection count differs from the pair's first frame.
+ * Returns MMMOT_EINVAL on a null pointer, B < 1 or max_nm outside [0, 512] before any launch. */
+#define MMMOT_TRACK_STATE_HEAD 4
+#define MMMOT_TRACK_STATE_INTS (MMMOT_TRACK_STATE_HEAD + 512)
+#define MMMOT_TRACK_EINFEASIBLE 1
+#define MMMOT_TRACK_ECONTRACT 2
+int mmmot_track_ids(const float* blocks, const int* pairs, const int* out_off, const int* frame_idx, int B, int max_nm,
+                    int* state, int* ids_out, void* stream);
+
 /* MFMA fragment-layout self test: C[32][32] = A[32][K] * B[32][K]^T through
  * the same fragment mapping the GEMM kernels use (K % 8 == 0). */
 int mmmot_selftest_mfma(const float* A, const float* B, float* C, int K, void* stream);

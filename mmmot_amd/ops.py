@@ -363,6 +363,13 @@ class HipOps:
                                             self._stream())
         _lib.check(st, 'mmmot_associate_pairs')
 
+    def track_ids(self, blocks, pairs, out_off, frame_idx, B, max_nm, state, ids_out):
+        """Track IDs of B consecutive pairs of one sequence from their solver blocks; see mmmot_track_ids.  pairs /
+        out_off / frame_idx / state / ids_out: int32 device tensors; state is updated in place."""
+        st = self.lib.mmmot_track_ids(_ptr(blocks), _iptr(pairs), _iptr(out_off), _iptr(frame_idx), int(B), int(max_nm),
+                                      _iptr(state), _iptr(ids_out), self._stream())
+        _lib.check(st, 'mmmot_track_ids')
+
     # ---- training backward of the pairwise block (include/mmmot_hip.h, csrc/backward.hip) -------------------
     def gn_bwd_partial(self, dA, Y, C, sc1, sh1, gamma, beta, relu, tiles, P):
         st = self.lib.mmmot_gn_bwd_partial(_ptr(dA), _ld(dA), _ptr(Y), _ld(Y), C, _ptr(sc1), _ptr(sh1), _ld(sc1),

@@ -30,6 +30,11 @@ and rows from an out-of-range trunk, or from weights / an arithmetic that change
 mmmot_amd.association): each pair's solve is queued behind its forward (``run_offline``: one launch per batch of pairs),
 and the hand-off copies scores and assignment to the host together.  The runs then return (scores, assignment) per pair
 and call ``on_assign(t, assignment)`` beside ``on_scores(t, scores)``; the scores are those of ``associate=False``.
+
+``track=True`` (with ``associate=True``) adds the last step of ``predict``, the ID bookkeeping (mmmot_amd.tracks): the ID
+launch is queued behind each solve, the sequence's ID state stays on the device, and the IDs come back in the same copy.
+Each run fills ``pipe.tracks`` - per frame an int64 array with one track ID per detection, -1 for a rejected one - and
+calls ``on_tracks(t, ids)`` per emitted frame; the runs return what they return without it.
 """
 import time
 
@@ -40,6 +45,7 @@ from .crops import crop_resize_u8
 from .points import prep_points_batched
 from .association import select
 from .tracker_glue import fetch_solve, queue_solve, scores_for_solver
+from .tracks import TrackState, merge_tracks
 
 
 class FrameFeed:
@@ -55,7 +61,10 @@ class FrameFeed:
 
 
 class SequencePipeline:
-    def __init__(self, model, size=224, overlap=True, without_reflectivity=True, reuse_appearance=False, associate=False):
+    def __init__(self, model, size=224, overlap=True, without_reflectivity=True, reuse_appearance=False, associate=False,
+                 track=False):
+        if track and not associate:
+            raise ValueError('SequencePipeline: track=True needs associate=True (the IDs come from the assignments)')
         self.model, self.size, self.overlap = model, int(size), bool(overlap)
         self.wo_refl = without_reflectivity
         self.dev = next(model.parameters()).device
@@ -63,6 +72,9 @@ class SequencePipeline:
         self.stage_events = None   # set to [] to record HIP events per stage (serial order only)
         self.reuse_appearance = bool(reuse_appearance)
         self.associate = bool(associate)
+        self.track = bool(track)
+        self.track_state = TrackState(self.dev) if self.track else None
+        self.tracks = None         # track=True: per frame the int64 track IDs of its detections (-1: rejected)
         # frames run through the trunk (a frame of a per-pair pair counts once per pair), pairs scored, pairs whose rows
         # were found stale after their hand-off and were computed again
         self.stats = {'encoded_frames': 0, 'pairs': 0, 'recomputed_pairs': 0}
@@ -140,41 +152,57 @@ class SequencePipeline:
         det, links, new, end, _ = out
         return scores_for_solver(det, links, new, end, self.model.test_mode)
 
-    def queue_hand_off(self, out, a, b):
-        """associate=True: queue the pair's solve behind its forward (returns the pending hand-off); else ``out``"""
+    def queue_hand_off(self, out, a, b, t=None):
+        """associate=True: queue the pair's solve behind its forward (returns the pending hand-off); else ``out``.
+        track=True: and the ID launch of pair (t-1, t) behind the solve."""
         if not self.associate:
             return out
         det, links, new, end, _ = out
-        return queue_solve([select(det, links, new, end, self.model.test_mode)], [(a['n'], b['n'])])
+        sel = [select(det, links, new, end, self.model.test_mode)]
+        if not self.track:
+            return queue_solve(sel, [(a['n'], b['n'])])
+        return queue_solve(sel, [(a['n'], b['n'])], track=self.track_state, frame_idx=[(t - 1, t)])
 
     def finish_hand_off(self, pending):
         """the host copy: scores, or (scores, assignment) with associate=True"""
         return fetch_solve(pending)[0] if self.associate else self.hand_off(pending)
 
-    def _deliver(self, t, sc, on_scores, on_assign):
-        scores, asg = sc if self.associate else (sc, None)
+    def _start_tracks(self, feeds):
+        if self.track:
+            self.track_state.reset()
+            self.tracks = [np.full(len(f.dets['bbox']), -1, np.int64) for f in feeds]
+
+    def _deliver(self, t, sc, on_scores, on_assign, on_tracks=None):
+        """the callbacks of pair (t-1, t); returns what the run returns for it"""
+        scores, asg = (sc[0], sc[1]) if self.associate else (sc, None)
         if on_scores is not None:
             on_scores(t, scores)
         if on_assign is not None and self.associate:
             on_assign(t, asg)
+        if self.track:
+            ids0, ids1, start, _ = sc[2]
+            merge_tracks(self.tracks, t, ids0, ids1, start, on_tracks)
+            return (scores, asg)
+        return sc
 
-    def run(self, feeds, on_scores=None, on_assign=None):
+    def run(self, feeds, on_scores=None, on_assign=None, on_tracks=None):
         """All pairs (t-1, t) of the sequence.  Returns the list of host score tuples (det, [link], new, end) - what
         ``ortools_solve`` is called with; ``on_scores(t, scores)`` is where the host solver would run.  associate=True:
-        the list of (scores, assignment), assignment as ``ortools_solve`` returns it; ``on_assign(t, assignment)``."""
+        the list of (scores, assignment), assignment as ``ortools_solve`` returns it; ``on_assign(t, assignment)``.
+        track=True: ``self.tracks`` is filled as well, ``on_tracks(t, ids)`` per emitted frame."""
+        self._start_tracks(feeds)
         if self.reuse_appearance:
-            return self._run_online(feeds, on_scores, on_assign)
+            return self._run_online(feeds, on_scores, on_assign, on_tracks)
         res = []
         prev = self.prepare(feeds[0])
         nxt = self.prepare(feeds[1]) if len(feeds) > 1 else None
         for t in range(1, len(feeds)):
             cur = nxt
-            out = self.queue_hand_off(self.launch_pair(prev, cur), prev, cur)
+            out = self.queue_hand_off(self.launch_pair(prev, cur), prev, cur, t)
             # stage A of the next frame is queued before the host blocks on this pair's scores
             nxt = self.prepare(feeds[t + 1]) if t + 1 < len(feeds) else None
             sc = self.finish_hand_off(out)
-            self._deliver(t, sc, on_scores, on_assign)
-            res.append(sc)
+            res.append(self._deliver(t, sc, on_scores, on_assign, on_tracks))
             self.stats['pairs'] += 1
             prev = cur
         return res
@@ -206,19 +234,21 @@ class SequencePipeline:
         self.stats['encoded_frames'] += 1
         return out
 
-    def _checked_scores(self, prev, cur, sc):
+    def _checked_scores(self, prev, cur, sc, t=None, snap=None):
         """After the hand-off (the host has waited for the pair anyway): the range guard's verdict on the trunks that
         made both frames' rows (appearance_is_current takes it).  Rows it rejects - or that a lowered arithmetic made
         stale - are computed again and the pair with them; at most two rounds (the guard only lowers f16q8 -> f16x3 ->
-        f32)."""
+        f32).  track=True: the pair's IDs are computed again too, from ``snap``, the ID state as it was before the pair."""
         for _ in range(3):
             if self._current(prev) and self._current(cur):
                 return sc
             self.stats['recomputed_pairs'] += 1
-            sc = self.finish_hand_off(self.queue_hand_off(self.launch_pair_cached(prev, cur), prev, cur))
+            if self.track:
+                self.track_state.restore(snap)
+            sc = self.finish_hand_off(self.queue_hand_off(self.launch_pair_cached(prev, cur), prev, cur, t))
         raise RuntimeError('mmmot_amd: the appearance rows of a pair stayed stale after recomputing it three times')
 
-    def _run_online(self, feeds, on_scores, on_assign):
+    def _run_online(self, feeds, on_scores, on_assign, on_tracks=None):
         res = []
         prev = self.prepare(feeds[0])
         nxt = self.prepare(feeds[1]) if len(feeds) > 1 else None
@@ -226,12 +256,12 @@ class SequencePipeline:
             self.encode([prev])  # frame 0, once
         for t in range(1, len(feeds)):
             cur = nxt
-            out = self.queue_hand_off(self.launch_pair_cached(prev, cur), prev, cur)
+            snap = self.track_state.snapshot() if self.track else None  # a recomputed pair starts from it again
+            out = self.queue_hand_off(self.launch_pair_cached(prev, cur), prev, cur, t)
             # stage A of the next frame is queued before the host blocks on this pair's scores
             nxt = self.prepare(feeds[t + 1]) if t + 1 < len(feeds) else None
-            sc = self._checked_scores(prev, cur, self.finish_hand_off(out))
-            self._deliver(t, sc, on_scores, on_assign)
-            res.append(sc)
+            sc = self._checked_scores(prev, cur, self.finish_hand_off(out), t, snap)
+            res.append(self._deliver(t, sc, on_scores, on_assign, on_tracks))
             self.stats['pairs'] += 1
             prev = cur
         return res
@@ -259,15 +289,18 @@ class SequencePipeline:
                 return
         raise RuntimeError('mmmot_amd: the appearance rows of the sequence stayed stale after encoding it three times')
 
-    def run_offline(self, feeds, frames_per_encode=16, pairs_per_forward=8, on_scores=None, on_assign=None):
+    def run_offline(self, feeds, frames_per_encode=16, pairs_per_forward=8, on_scores=None, on_assign=None,
+                    on_tracks=None):
         """The whole sequence at once (every frame known up front): stage A for every frame, the trunk over the crops of
         `frames_per_encode` frames per launch sequence (throughput-mode occupancy), then the pairs `pairs_per_forward` at
         a time on the rows (forward_batch with appearance rows: PointNet, fusion and the head batched).  Returns the list
         of ``run``; ``on_scores(t, scores)`` is called in pair order once each batch of pairs is on the host.
-        associate=True: each batch of pairs is solved in one launch and copied back with its scores in one copy."""
+        associate=True: each batch of pairs is solved in one launch and copied back with its scores in one copy;
+        track=True: one ID launch walks the batch's pairs behind that solve, and the IDs ride in the same copy."""
         K, B = int(frames_per_encode), int(pairs_per_forward)
         if K < 1 or B < 1:
             raise ValueError('frames_per_encode and pairs_per_forward must be >= 1')
+        self._start_tracks(feeds)
         frames = [self.prepare(f) for f in feeds]
         if len(frames) < 2:
             return []
@@ -286,10 +319,14 @@ class SequencePipeline:
                 outs = self.model.forward_batch(plan, None, torch.cat(points), appearance=torch.cat(rows))
             if self.associate:
                 sel = [select(o[0], o[1], o[2], o[3], self.model.test_mode) for o in outs]
-                done = fetch_solve(queue_solve(sel, [(frames[t - 1]['n'], frames[t]['n']) for t in ts]))
+                splits = [(frames[t - 1]['n'], frames[t]['n']) for t in ts]
+                if self.track:
+                    done = fetch_solve(queue_solve(sel, splits, track=self.track_state,
+                                                   frame_idx=[(t - 1, t) for t in ts]))
+                else:
+                    done = fetch_solve(queue_solve(sel, splits))
                 for t, sc in zip(ts, done):
-                    self._deliver(t, sc, on_scores, on_assign)
-                    res.append(sc)
+                    res.append(self._deliver(t, sc, on_scores, on_assign, on_tracks))
                     self.stats['pairs'] += 1
                 continue
             for t, o in zip(ts, outs):
@@ -301,10 +338,10 @@ class SequencePipeline:
         return res
 
 
-def time_sequence(model, feeds, size=224, overlap=True, warm=3, associate=False):
+def time_sequence(model, feeds, size=224, overlap=True, warm=3, associate=False, track=False):
     """frames/s of the chain over ``feeds`` (wall clock, synchronised on both sides; ``warm`` untimed leading pairs);
     ``associate``: with the device association of every pair (SequencePipeline(associate=True))."""
-    pipe = SequencePipeline(model, size, overlap=overlap, associate=associate)
+    pipe = SequencePipeline(model, size, overlap=overlap, associate=associate, track=track)
     pipe.run(feeds[:warm + 1])
     torch.cuda.synchronize()
     t0 = time.perf_counter()

@@ -216,3 +216,63 @@ def _associate_meta(det, new, end, link, pairs):
 _LIB.define('associate(Tensor det, Tensor new, Tensor end, Tensor link, Tensor pairs) -> Tensor[]')
 _LIB.impl('associate', _associate, 'CUDA')
 _LIB.impl('associate', _associate_meta, 'Meta')
+
+
+#   mmmot::track_ids(Tensor blocks, Tensor pairs, Tensor frame_idx, Tensor(a!) state, int max_nm) -> Tensor
+#       Track IDs of B consecutive pairs of ONE sequence (mmmot_track_ids) from the solver's output blocks: blocks = the
+#       `out` of mmmot::associate for the same pairs table (a CPU int32 [B, 4]; N or M may be 0 here); frame_idx: CPU
+#       int32 [B, 2]; state: the sequence's device int32 [TRACK_STATE_INTS] block, updated in place; max_nm: 0 = from
+#       the table, else >= every N and M (above 128 the four-wave kernel runs).  Returns int32
+#       [sum (N + M + 2)]: per pair [ids frame 0 | ids frame 1 | frame_start | last_id].
+TRACK_STATE_HEAD = 4
+TRACK_STATE_INTS = TRACK_STATE_HEAD + 512
+
+
+def track_layout(pairs, frame_idx, n_blocks=None):
+    """(total ids_out ints, int64 [B] block offsets, max(N, M)) of a pair table for mmmot::track_ids; checks the table."""
+    if pairs.device.type != 'cpu' or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 4 or \
+            pairs.shape[0] < 1:
+        raise ValueError('mmmot::track_ids: pairs must be a CPU int32 [B, 4] table (N, M, score offset, link offset)')
+    if frame_idx.device.type != 'cpu' or frame_idx.dtype != torch.int32 or tuple(frame_idx.shape) != (pairs.shape[0], 2):
+        raise ValueError('mmmot::track_ids: frame_idx must be a CPU int32 [B, 2] table')
+    if int(frame_idx.min()) < 0:
+        raise ValueError('mmmot::track_ids: frame indices must be >= 0')
+    t = pairs.numpy().astype(np.int64)
+    N, M = t[:, 0], t[:, 1]
+    if np.minimum(N, M).min() < 0 or np.maximum(N, M).max() > MAX_ASSOC:
+        raise ValueError('mmmot::track_ids: every pair needs 0 <= N, M <= %d' % MAX_ASSOC)
+    sizes = 3 * (N + M) + N * M
+    off = np.cumsum(sizes) - sizes
+    if n_blocks is not None and int(sizes.sum()) > n_blocks:
+        raise ValueError('mmmot::track_ids: a pair reads past the end of the solver blocks')
+    return int((N + M + 2).sum()), torch.from_numpy(off), int(np.maximum(N, M).max())
+
+
+def _track_ids(blocks, pairs, frame_idx, state, max_nm):
+    total, off, need = track_layout(pairs, frame_idx, int(blocks.numel()))
+    if state.dtype != torch.int32 or state.numel() != TRACK_STATE_INTS or not state.is_contiguous():
+        raise ValueError('mmmot::track_ids: state must be a contiguous int32 [%d] device block' % TRACK_STATE_INTS)
+    if max_nm and (max_nm < need or max_nm > MAX_ASSOC):
+        raise ValueError('mmmot::track_ids: max_nm %d does not cover the table (%d)' % (max_nm, need))
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    B = int(pairs.shape[0])
+    host = torch.empty(7 * B, dtype=torch.int32, pin_memory=True)  # one pinned block, one asynchronous copy
+    host[:4 * B] = pairs.reshape(-1)
+    host[4 * B:5 * B] = off
+    host[5 * B:] = frame_idx.reshape(-1)
+    table = host.to(blocks.device, non_blocking=True)
+    ids = torch.empty(total, dtype=torch.int32, device=blocks.device)
+    _ASSOC_OPS[0].track_ids(blocks, table[:4 * B], table[4 * B:5 * B], table[5 * B:], B, max_nm or need, state, ids)
+    return ids
+
+
+def _track_ids_meta(blocks, pairs, frame_idx, state, max_nm):
+    total, _, _ = track_layout(pairs, frame_idx)
+    return blocks.new_empty((total,), dtype=torch.int32)
+
+
+_LIB.define('track_ids(Tensor blocks, Tensor pairs, Tensor frame_idx, Tensor(a!) state, int max_nm) -> Tensor')
+_LIB.impl('track_ids', _track_ids, 'CUDA')
+_LIB.impl('track_ids', _track_ids_meta, 'Meta')

@@ -10,6 +10,7 @@ with exactly the shapes the solver indexes.  ``predict_assign`` also solves the 
 import torch
 
 from .association import associate, pairs_table, select, split_of, unpack
+from .tracks import queue_ids, split_ids
 
 
 def scores_for_solver(det_score, link_scores, new_score, end_score, test_mode):
@@ -37,37 +38,59 @@ def predict_scores(model, det_imgs, det_info, det_split):
     return scores_for_solver(det_score, link_score, new_score, end_score, model.test_mode)
 
 
-def queue_solve(selected, splits):
+def queue_solve(selected, splits, track=None, frame_idx=None):
     """Queue the association of B frame pairs behind their forward; nothing waits.  ``selected``: per pair the device
     rows (det L, [link 1 x N x M], new L, end L) of ``association.select``; ``splits``: per pair (N, M).  Returns the
-    pending hand-off for ``fetch_solve``: one device buffer [det | new | end | link of every pair | solver output]."""
+    pending hand-off for ``fetch_solve``: one device buffer [det | new | end | link of every pair | solver output].
+    ``track`` (a tracks.TrackState; the pairs are then CONSECUTIVE pairs of its sequence, ``frame_idx`` their frame
+    index pairs): the ID launch is queued behind the solve and its int32 result rides at the end of the same buffer."""
     splits = [(int(N), int(M)) for N, M in splits]
     if any(N == 0 or M == 0 for N, M in splits):  # an empty frame: nothing to link, answered on the host
-        return {'host': [scores_for_solver(d.unsqueeze(0), l, n.unsqueeze(0), e.unsqueeze(0), 0)
-                         for d, l, n, e in selected], 'splits': splits}
+        host = [scores_for_solver(d.unsqueeze(0), l, n.unsqueeze(0), e.unsqueeze(0), 0) for d, l, n, e in selected]
+        if track is None:
+            return {'host': host, 'splits': splits}
+        # the IDs still come from the kernel, so that the state stays on the device: the assignments are uploaded
+        done = [(sc, associate(sc[0], sc[1], sc[2], sc[3], split)) for sc, split in zip(host, splits)]
+        blocks = torch.cat([t.reshape(-1).to(torch.float32) for _, a in done for t in (a[0], a[2], a[3], a[1][0])])
+        return {'done': done, 'splits': splits, 'ids': queue_ids(track, blocks.to(track.buf.device), splits, frame_idx)}
     cat = lambda k: torch.cat([(s[k][0] if k == 1 else s[k]).reshape(-1) for s in selected])
     det, new, end, link = cat(0), cat(2), cat(3), cat(1)
     S, K = det.numel(), link.numel()
     buf = torch.cat([det, new, end, link])
     pairs, offs = pairs_table(splits)
     out, _ = torch.ops.mmmot.associate(buf[0:S], buf[S:2 * S], buf[2 * S:3 * S], buf[3 * S:], pairs)
-    return {'flat': torch.cat([buf, out]), 'splits': splits, 'offs': offs, 'S': S, 'K': K}
+    pending = {'splits': splits, 'offs': offs, 'S': S, 'K': K}
+    if track is None:
+        pending['flat'] = torch.cat([buf, out])
+    else:
+        ids = queue_ids(track, out, splits, frame_idx)
+        pending['flat'] = torch.cat([buf, out, ids.view(torch.float32)])  # the bits travel; no value is converted
+        pending['n_ids'] = ids.numel()
+    return pending
 
 
 def fetch_solve(pending):
     """The ONE device-to-host copy of ``queue_solve``'s buffer -> per pair (scores, assignment): scores as
-    ``scores_for_solver`` returns them, assignment as ``ortools_solve`` does (CPU tensors)."""
+    ``scores_for_solver`` returns them, assignment as ``ortools_solve`` does (CPU tensors).  Queued with ``track``: per
+    pair (scores, assignment, (ids0, ids1, frame_start, last_id)), the IDs as ``tracks.split_ids`` gives them."""
     if 'host' in pending:
         return [(sc, associate(sc[0], sc[1], sc[2], sc[3], split)) for sc, split in zip(pending['host'], pending['splits'])]
+    if 'done' in pending:
+        ids = split_ids(pending['ids'].cpu().numpy(), pending['splits'])
+        return [(sc, asg, i) for (sc, asg), i in zip(pending['done'], ids)]
     flat = pending['flat'].to('cpu')
     S, K = pending['S'], pending['K']
+    ids = None
+    if 'n_ids' in pending:
+        ids = split_ids(flat[flat.numel() - pending['n_ids']:].view(torch.int32).numpy(), pending['splits'])
     res, so, lo = [], 0, 0
-    for (N, M), o in zip(pending['splits'], pending['offs']):
+    for p, ((N, M), o) in enumerate(zip(pending['splits'], pending['offs'])):
         L = N + M
         scores = (flat[so:so + L], [flat[3 * S + lo:3 * S + lo + N * M].view(1, N, M)], flat[S + so:S + so + L],
                   flat[2 * S + so:2 * S + so + L])
         o += 3 * S + K
-        res.append((scores, unpack(flat[o:o + 3 * L + N * M], N, M)))
+        asg = unpack(flat[o:o + 3 * L + N * M], N, M)
+        res.append((scores, asg) if ids is None else (scores, asg, ids[p]))
         so += L
         lo += N * M
     return res

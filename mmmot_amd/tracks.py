@@ -1,0 +1,162 @@
+"""Track IDs on the device: the last step of the reference's ``TrackingModule.predict`` (tracking_model.py:77-81,
+``assign_det_id`` then ``align_id``), which turns each pair's 0/1 assignment into IDs that stay stable over a sequence.
+
+IDs are a chain over the pairs of a sequence (pair t needs the IDs pair t-1 gave frame t), so the step is one small
+launch (csrc/track_ids.hip, one workgroup walking B pairs in order) queued behind the solve, with the sequence's state
+(last ID, the stored frame and its per-detection IDs) in a device block that the launch updates in place:
+
+    state = TrackState('cuda')
+    ids_per_frame, frame_start = track_ids(state, assign_det, assign_link, assign_new, assign_end, det_split,
+                                           (frame_a, frame_b))        # instead of assign_det_id + align_id
+
+IDs are per DETECTION: ``ids[j] = -1`` where ``assign_det[j] != 1`` (the detection is in no track); the reference's
+``frames_id`` entry of a frame, which lists kept detections only, is ``ids[ids >= 0]``.  ``frame_start = 1`` when the
+pair's first frame was the stored one: only the second frame is emitted, as ``align_id`` returns it.
+
+Two deliberate differences from the reference.  It recognises "the same detection of frame t in both pairs" by exact
+equality of ``bbox`` (and ``location``), because its dataset prepares each frame twice; here a frame is prepared once and
+identity is the detection index - the same whenever the boxes within a frame are distinct.  And where the reference
+raises or stops in a debugger on an assignment no solver returns (a kept, non-new second-frame detection without
+exactly one link from a kept row), the kernel writes -1, sets the state's error flag, and ``TrackingError`` is raised
+when the result reaches the host.
+"""
+import numpy as np
+import torch
+
+from . import torch_ops
+from .association import pairs_table, split_of
+from .torch_ops import TRACK_STATE_HEAD, TRACK_STATE_INTS
+
+EINFEASIBLE, ECONTRACT = 1, 2
+KITTI_NAMES = ('Car', 'Van', 'Truck', 'Pedestrian', 'Person', 'Cyclist', 'Tram', 'Misc')
+
+
+class TrackingError(RuntimeError):
+    pass
+
+
+class TrackState:
+    """The ID state of ONE sequence on the device: int32 [last_id, stored frame or -1, error flags, detections of the
+    stored frame | its per-detection IDs x 512] (include/mmmot_hip.h, mmmot_track_ids)."""
+
+    def __init__(self, device='cuda'):
+        init = torch.full((TRACK_STATE_INTS,), -1, dtype=torch.int32)
+        init[0] = init[2] = init[3] = 0
+        self._init = init.to(device)
+        self.buf = self._init.clone()
+
+    def reset(self):
+        """start a new sequence (the reference's ``clear_mem``); queued on the current stream"""
+        self.buf.copy_(self._init)
+
+    def snapshot(self):
+        return self.buf.clone()
+
+    def restore(self, snap):
+        self.buf.copy_(snap)
+
+    def read(self):
+        """host view (waits for the stream): last_id, the stored frame (None: none) and its IDs, the error flags"""
+        h = self.buf.cpu().numpy()
+        n = int(h[3])
+        return {'last_id': int(h[0]), 'frame': None if h[1] < 0 else int(h[1]), 'flags': int(h[2]),
+                'ids': h[TRACK_STATE_HEAD:TRACK_STATE_HEAD + n].astype(np.int64)}
+
+
+def check_flags(flags):
+    if flags & EINFEASIBLE:
+        raise TrackingError('track_ids: a kept second-frame detection with new != 1 has not exactly one link from a kept '
+                            'detection of the first frame - not a solver output (tests/association_ref.feasible)')
+    if flags & ECONTRACT:
+        raise TrackingError('track_ids: the stored frame and the first frame of the next pair share a frame index but '
+                            'not a detection count, or a pair lies outside the launch limits')
+
+
+def frame_table(frame_idx, B):
+    t = torch.as_tensor(np.asarray(frame_idx, dtype=np.int64).reshape(-1, 2), dtype=torch.int32)
+    if t.shape[0] != B:
+        raise ValueError('track_ids: %d frame index pairs for %d pairs' % (t.shape[0], B))
+    return t
+
+
+def queue_ids(state, blocks, splits, frame_idx, max_nm=0):
+    """Queue the ID launch for B consecutive pairs of the state's sequence; nothing waits.  ``blocks``: the flat device
+    output of mmmot::associate for ``splits``.  Returns the device int32 buffer [per pair: ids N | ids M | frame_start |
+    last_id] with the state's error flags appended as the last element."""
+    pairs, _ = pairs_table(splits)
+    ids = torch.ops.mmmot.track_ids(blocks, pairs, frame_table(frame_idx, len(splits)), state.buf, int(max_nm))
+    return torch.cat([ids, state.buf[2:3]])
+
+
+def split_ids(flat, splits):
+    """host int32 buffer of ``queue_ids`` -> per pair (ids0 [N], ids1 [M], frame_start, last_id), int64 arrays; raises
+    ``TrackingError`` on the error flags"""
+    flat = np.asarray(flat)
+    check_flags(int(flat[-1]))
+    res, o = [], 0
+    for N, M in splits:
+        res.append((flat[o:o + N].astype(np.int64), flat[o + N:o + N + M].astype(np.int64), int(flat[o + N + M]),
+                    int(flat[o + N + M + 1])))
+        o += N + M + 2
+    return res
+
+
+def assign_ids(state, blocks, splits, frame_idx, max_nm=0):
+    """IDs of B consecutive pairs in one launch and one copy: per pair (ids0, ids1, frame_start, last_id)."""
+    splits = [(int(N), int(M)) for N, M in splits]
+    return split_ids(queue_ids(state, blocks, splits, frame_idx, max_nm).cpu().numpy(), splits)
+
+
+def track_ids(state, assign_det, assign_link, assign_new, assign_end, det_split, frame_idx):
+    """Drop-in for the reference's ``assign_det_id`` + ``align_id`` on one pair: takes what ``ortools_solve`` /
+    ``association.associate`` returns (CPU or device tensors) and the frame indices of the pair's two frames.  Returns
+    (ids_per_frame, frame_start): per EMITTED frame a CPU int64 tensor with one ID per detection (-1: rejected) - both
+    frames, or the second only when frame_start = 1."""
+    N, M = split_of(det_split)
+    L = N + M
+    link = assign_link[0]
+    if assign_det.numel() != L or assign_new.numel() != L or assign_end.numel() != L or link.numel() != N * M:
+        raise ValueError('track_ids: assignment does not match det_split [%d, %d]' % (N, M))
+    block = torch.cat([t.detach().reshape(-1).to(torch.float32) for t in (assign_det, assign_new, assign_end, link)])
+    ids0, ids1, start, _ = assign_ids(state, block.to(state.buf.device), [(N, M)], [frame_idx])[0]
+    frames = [torch.from_numpy(ids1)] if start else [torch.from_numpy(ids0), torch.from_numpy(ids1)]
+    return frames, start
+
+
+def merge_tracks(tracks, t, ids0, ids1, frame_start, on_tracks=None):
+    """pair (t-1, t) into the per-frame list: the last emission of a frame stands (a frame whose pair kept nothing is
+    emitted again by the next pair, as the reference does)"""
+    if not frame_start:
+        tracks[t - 1] = ids0
+        if on_tracks is not None:
+            on_tracks(t - 1, ids0)
+    tracks[t] = ids1
+    if on_tracks is not None:
+        on_tracks(t, ids1)
+
+
+def write_kitti_tracks(path, frames, ids, frame_idx=None):
+    """The reference's result file (utils/data_util.py:80-128 write_kitti_result + kitti_result_line) on the host:
+    ``frames``: per frame the detection dict the pipeline holds (FrameFeed.dets: bbox [n, 4], dimensions [n, 3] lhw,
+    location [n, 3], rotation_y [n]; optional name (KITTI class index or string), truncated, occluded, alpha, else the
+    format's "unknown" values); ``ids``: per frame the per-detection IDs (pipe.tracks).  Kept detections only,
+    dimensions lhw -> hwl, score 0.9, values at fp32 as the reference's tensors; ``frame_idx``: the frames' numbers
+    (default 0, 1, ..)."""
+    f4 = lambda v: '{:.4f}'.format(float(np.float32(v)))
+    lines = []
+    for t, (d, fid) in enumerate(zip(frames, ids)):
+        frame = t if frame_idx is None else int(frame_idx[t])
+        fid = np.asarray(fid)
+        for j in np.flatnonzero(fid >= 0):
+            name = d['name'][j] if 'name' in d else 0
+            name = name if isinstance(name, str) else KITTI_NAMES[int(name)]
+            dims = np.asarray(d['dimensions'][j])[[1, 2, 0]]
+            row = [str(frame), str(int(fid[j])), name,
+                   f4(d['truncated'][j]) if 'truncated' in d else '-1',
+                   str(int(d['occluded'][j])) if 'occluded' in d else '-1',
+                   f4(d['alpha'][j]) if 'alpha' in d else '-10']
+            row += [f4(v) for v in np.asarray(d['bbox'][j]).reshape(-1)] + [f4(v) for v in dims]
+            row += [f4(v) for v in np.asarray(d['location'][j]).reshape(-1)] + [f4(d['rotation_y'][j]), f4(0.9)]
+            lines.append(' '.join(row))
+    with open(path, 'w') as f:
+        f.write('\n'.join(lines))

@@ -5,8 +5,10 @@ pairs B at a time on the rows).  Workload = bench.py's pipeline leg: 100 synthet
 (mmmot_amd.synth.make_frame(7000 + t, 120000, n_det), 10-12 detections), 224-pixel 8-bit crops, Fusion A, overlapped
 stage A.  Each repeat runs every mode once, in turn; the wall clock of a run ends in a synchronise; one untimed run of
 every mode first.  The scores of the three modes must be bitwise equal.  Writes <out>/bench_sequence.json.
+--associate adds the device association to every pair (SequencePipeline(associate=True)), --track the track IDs as well
+(track=True; implies --associate): the tracks of the three modes must then be equal too.
 
-    python tools/bench_sequence.py --out <dir> [--repeats 3] [--trunk f16x3] [-K 16] [-B 8]
+    python tools/bench_sequence.py --out <dir> [--repeats 3] [--trunk f16x3] [-K 16] [-B 8] [--associate | --track]
 """
 import argparse
 import json
@@ -46,7 +48,11 @@ def main():
     ap.add_argument('--trunk', default='f16x3')
     ap.add_argument('-K', '--frames-per-encode', type=int, default=16)
     ap.add_argument('-B', '--pairs-per-forward', type=int, default=8)
+    ap.add_argument('--associate', action='store_true')
+    ap.add_argument('--track', action='store_true')
     args = ap.parse_args()
+    assoc = args.associate or args.track
+    kw = dict(associate=assoc, track=True) if args.track else dict(associate=assoc)
     if args.repeats < 3 or args.frames < 2:
         raise SystemExit('--repeats must be >= 3 and --frames >= 2')
     dev = torch.device('cuda', 0)
@@ -64,11 +70,17 @@ def main():
         'online': lambda p: p.run(feeds),
         'offline': lambda p: p.run_offline(feeds, frames_per_encode=K, pairs_per_forward=B),
     }
-    make = {'per_pair': lambda: SequencePipeline(model, 224), 'offline': lambda: SequencePipeline(model, 224),
-            'online': lambda: SequencePipeline(model, 224, reuse_appearance=True)}
-    results, stats, fps = {}, {}, {k: [] for k in modes}
+    make = {'per_pair': lambda: SequencePipeline(model, 224, **kw), 'offline': lambda: SequencePipeline(model, 224, **kw),
+            'online': lambda: SequencePipeline(model, 224, reuse_appearance=True, **kw)}
+    scores = (lambda res: [r[0] for r in res]) if assoc else (lambda res: res)
+    results, stats, fps, tracks = {}, {}, {k: [] for k in modes}, {}
     for name, run in modes.items():  # untimed: workspace growth, plan caches, first-forward range checks
-        results[name] = run(make[name]())
+        pipe = make[name]()
+        results[name] = scores(run(pipe))
+        tracks[name] = pipe.tracks
+    if args.track and not all(len(tracks[k]) == n and all(np.array_equal(x, y) for x, y in zip(tracks[k], tracks['per_pair']))
+                              for k in modes):
+        raise SystemExit('the tracks of the three orders differ')
     for _ in range(args.repeats):
         for name, run in modes.items():
             pipe = make[name]()
@@ -78,7 +90,7 @@ def main():
             torch.cuda.synchronize()
             fps[name].append((n - 1) / (time.perf_counter() - t0))
             stats[name] = dict(pipe.stats)
-            if not same(res, results['per_pair']):
+            if not same(scores(res), results['per_pair']):
                 raise SystemExit('%s: scores differ from the per-pair order' % name)
     med = {k: float(np.median(v)) for k, v in fps.items()}
     rec = {
@@ -87,6 +99,8 @@ def main():
         'spread': {k: round((max(v) - min(v)) / med[k], 4) for k, v in fps.items()},
         'speedup_vs_per_pair': {k: round(med[k] / med['per_pair'], 3) for k in modes},
         'bitwise_equal': True,
+        'associate': assoc, 'track': bool(args.track),
+        'last_track_id': int(max(int(x.max()) for x in tracks['per_pair'] if len(x))) if args.track else None,
         'stats': stats,
         'trunk': model.engine().trunk,
         'range_events': len(model.engine().range_events),
