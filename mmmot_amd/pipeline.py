@@ -35,6 +35,11 @@ and call ``on_assign(t, assignment)`` beside ``on_scores(t, scores)``; the score
 launch is queued behind each solve, the sequence's ID state stays on the device, and the IDs come back in the same copy.
 Each run fills ``pipe.tracks`` - per frame an int64 array with one track ID per detection, -1 for a rejected one - and
 calls ``on_tracks(t, ids)`` per emitted frame; the runs return what they return without it.
+
+All orders and modes share two steps.  ``queue_hand_off`` queues what the mode asks for behind the forward of one pair
+or a batch of pairs and returns a tracker_glue.HandOff; ``finish_hand_off`` is its host copy, one PairResult (scores,
+assignment, ids) per pair, and ``_deliver`` turns a PairResult into the callbacks, ``stats`` and the returned shape.
+``run`` is one loop (``_run_pairs``) with or without cached rows; ``run_offline`` hands off a batch of pairs at a time.
 """
 import time
 
@@ -44,7 +49,7 @@ import torch
 from .crops import crop_resize_u8
 from .points import prep_points_batched
 from .association import select
-from .tracker_glue import fetch_solve, queue_solve, scores_for_solver
+from .tracker_glue import queue_scores, queue_solve
 from .tracks import TrackState, merge_tracks
 
 
@@ -124,9 +129,14 @@ class SequencePipeline:
                 cur.wait_event(x['ready'])
 
     @staticmethod
+    def _pair_split(a, b):
+        """the point split of the pair's joined points: frame b's boundaries behind frame a's"""
+        return np.concatenate([a['split'], a['split'][-1] + b['split'][1:]])
+
+    @staticmethod
     def _pair_info(a, b):
         points = torch.cat([a['points'], b['points']]).unsqueeze(0)
-        split = np.concatenate([a['split'], a['split'][-1] + b['split'][1:]])
+        split = SequencePipeline._pair_split(a, b)
         # the split is on the host already (prep_points read it back): hand it over as a CPU tensor - no D2H in forward
         return {'points': points, 'points_split': torch.from_numpy(split.astype(np.float32)).unsqueeze(0)}
 
@@ -148,42 +158,57 @@ class SequencePipeline:
             ev.append(('forward', [e0, e1]))
         return out
 
-    def hand_off(self, out):
-        det, links, new, end, _ = out
-        return scores_for_solver(det, links, new, end, self.model.test_mode)
-
-    def queue_hand_off(self, out, a, b, t=None):
-        """associate=True: queue the pair's solve behind its forward (returns the pending hand-off); else ``out``.
-        track=True: and the ID launch of pair (t-1, t) behind the solve."""
+    def queue_hand_off(self, outs, pairs):
+        """Queue the hand-off of ``pairs`` = [(t, a, b)] (frames a = t-1, b = t) behind their forward outputs ``outs``;
+        returns the pending HandOff.  associate=True: with the pairs' solve in one launch; track=True: and the ID launch
+        of these consecutive pairs behind it."""
+        tm = self.model.test_mode
         if not self.associate:
-            return out
-        det, links, new, end, _ = out
-        sel = [select(det, links, new, end, self.model.test_mode)]
-        if not self.track:
-            return queue_solve(sel, [(a['n'], b['n'])])
-        return queue_solve(sel, [(a['n'], b['n'])], track=self.track_state, frame_idx=[(t - 1, t)])
+            return queue_scores(outs, tm)
+        sel = [select(o[0], o[1], o[2], o[3], tm) for o in outs]
+        return queue_solve(sel, [(a['n'], b['n']) for _, a, b in pairs], track=self.track_state,
+                           frame_idx=[(t - 1, t) for t, _, _ in pairs])
 
     def finish_hand_off(self, pending):
-        """the host copy: scores, or (scores, assignment) with associate=True"""
-        return fetch_solve(pending)[0] if self.associate else self.hand_off(pending)
+        """the host copy, the one place the host waits for the pairs: their PairResults"""
+        return pending.fetch()
 
     def _start_tracks(self, feeds):
         if self.track:
             self.track_state.reset()
             self.tracks = [np.full(len(f.dets['bbox']), -1, np.int64) for f in feeds]
 
-    def _deliver(self, t, sc, on_scores, on_assign, on_tracks=None):
-        """the callbacks of pair (t-1, t); returns what the run returns for it"""
-        scores, asg = (sc[0], sc[1]) if self.associate else (sc, None)
+    def _deliver(self, t, r, on_scores, on_assign, on_tracks):
+        """the callbacks and the bookkeeping of pair (t-1, t), a PairResult; returns what the run returns for it"""
         if on_scores is not None:
-            on_scores(t, scores)
-        if on_assign is not None and self.associate:
-            on_assign(t, asg)
-        if self.track:
-            ids0, ids1, start, _ = sc[2]
-            merge_tracks(self.tracks, t, ids0, ids1, start, on_tracks)
-            return (scores, asg)
-        return sc
+            on_scores(t, r.scores)
+        if on_assign is not None and r.assignment is not None:
+            on_assign(t, r.assignment)
+        if r.ids is not None:
+            merge_tracks(self.tracks, t, r.ids[0], r.ids[1], r.ids[2], on_tracks)
+        self.stats['pairs'] += 1
+        return (r.scores, r.assignment) if self.associate else r.scores
+
+    def _run_pairs(self, feeds, reuse, on_scores, on_assign, on_tracks):
+        """the pairs one after the other; ``reuse``: on cached appearance rows (the trunk on the new frame only)"""
+        launch = self.launch_pair_cached if reuse else self.launch_pair
+        res = []
+        prev = self.prepare(feeds[0])
+        nxt = self.prepare(feeds[1]) if len(feeds) > 1 else None
+        if reuse and nxt is not None:
+            self.encode([prev])  # frame 0, once
+        for t in range(1, len(feeds)):
+            cur = nxt
+            snap = self.track_state.snapshot() if reuse and self.track else None  # a recomputed pair starts from it again
+            pending = self.queue_hand_off([launch(prev, cur)], [(t, prev, cur)])
+            # stage A of the next frame is queued before the host blocks on this pair's scores
+            nxt = self.prepare(feeds[t + 1]) if t + 1 < len(feeds) else None
+            r = self.finish_hand_off(pending)[0]
+            if reuse:
+                r = self._checked_scores(prev, cur, r, t, snap)
+            res.append(self._deliver(t, r, on_scores, on_assign, on_tracks))
+            prev = cur
+        return res
 
     def run(self, feeds, on_scores=None, on_assign=None, on_tracks=None):
         """All pairs (t-1, t) of the sequence.  Returns the list of host score tuples (det, [link], new, end) - what
@@ -191,21 +216,7 @@ class SequencePipeline:
         the list of (scores, assignment), assignment as ``ortools_solve`` returns it; ``on_assign(t, assignment)``.
         track=True: ``self.tracks`` is filled as well, ``on_tracks(t, ids)`` per emitted frame."""
         self._start_tracks(feeds)
-        if self.reuse_appearance:
-            return self._run_online(feeds, on_scores, on_assign, on_tracks)
-        res = []
-        prev = self.prepare(feeds[0])
-        nxt = self.prepare(feeds[1]) if len(feeds) > 1 else None
-        for t in range(1, len(feeds)):
-            cur = nxt
-            out = self.queue_hand_off(self.launch_pair(prev, cur), prev, cur, t)
-            # stage A of the next frame is queued before the host blocks on this pair's scores
-            nxt = self.prepare(feeds[t + 1]) if t + 1 < len(feeds) else None
-            sc = self.finish_hand_off(out)
-            res.append(self._deliver(t, sc, on_scores, on_assign, on_tracks))
-            self.stats['pairs'] += 1
-            prev = cur
-        return res
+        return self._run_pairs(feeds, self.reuse_appearance, on_scores, on_assign, on_tracks)
 
     # ---- appearance rows computed once per frame -----------------------------------------------------------------
     def _current(self, a):
@@ -234,37 +245,19 @@ class SequencePipeline:
         self.stats['encoded_frames'] += 1
         return out
 
-    def _checked_scores(self, prev, cur, sc, t=None, snap=None):
+    def _checked_scores(self, prev, cur, r, t, snap=None):
         """After the hand-off (the host has waited for the pair anyway): the range guard's verdict on the trunks that
         made both frames' rows (appearance_is_current takes it).  Rows it rejects - or that a lowered arithmetic made
         stale - are computed again and the pair with them; at most two rounds (the guard only lowers f16q8 -> f16x3 ->
         f32).  track=True: the pair's IDs are computed again too, from ``snap``, the ID state as it was before the pair."""
         for _ in range(3):
             if self._current(prev) and self._current(cur):
-                return sc
+                return r
             self.stats['recomputed_pairs'] += 1
-            if self.track:
+            if snap is not None:
                 self.track_state.restore(snap)
-            sc = self.finish_hand_off(self.queue_hand_off(self.launch_pair_cached(prev, cur), prev, cur, t))
+            r = self.finish_hand_off(self.queue_hand_off([self.launch_pair_cached(prev, cur)], [(t, prev, cur)]))[0]
         raise RuntimeError('mmmot_amd: the appearance rows of a pair stayed stale after recomputing it three times')
-
-    def _run_online(self, feeds, on_scores, on_assign, on_tracks=None):
-        res = []
-        prev = self.prepare(feeds[0])
-        nxt = self.prepare(feeds[1]) if len(feeds) > 1 else None
-        if nxt is not None:
-            self.encode([prev])  # frame 0, once
-        for t in range(1, len(feeds)):
-            cur = nxt
-            snap = self.track_state.snapshot() if self.track else None  # a recomputed pair starts from it again
-            out = self.queue_hand_off(self.launch_pair_cached(prev, cur), prev, cur, t)
-            # stage A of the next frame is queued before the host blocks on this pair's scores
-            nxt = self.prepare(feeds[t + 1]) if t + 1 < len(feeds) else None
-            sc = self._checked_scores(prev, cur, self.finish_hand_off(out), t, snap)
-            res.append(self._deliver(t, sc, on_scores, on_assign, on_tracks))
-            self.stats['pairs'] += 1
-            prev = cur
-        return res
 
     def _encode_all(self, frames, K):
         """rows for every frame: K consecutive frames per trunk launch sequence (fewer where their crops would pass the
@@ -307,34 +300,15 @@ class SequencePipeline:
         self._encode_all(frames, K)
         res = []
         for g0 in range(1, len(frames), B):
-            ts = range(g0, min(g0 + B, len(frames)))
-            samples, rows, points = [], [], []
-            for t in ts:
-                a, b = frames[t - 1], frames[t]
-                samples.append(([a['n'], b['n']], np.concatenate([a['split'], a['split'][-1] + b['split'][1:]])))
-                rows += [a['rows'].rows, b['rows'].rows]
-                points += [a['points'], b['points']]
-            plan = self.model.make_plan(samples, self.size)
+            pairs = [(t, frames[t - 1], frames[t]) for t in range(g0, min(g0 + B, len(frames)))]
+            both = [f for _, a, b in pairs for f in (a, b)]
+            plan = self.model.make_plan([([a['n'], b['n']], self._pair_split(a, b)) for _, a, b in pairs], self.size)
             with torch.no_grad():
-                outs = self.model.forward_batch(plan, None, torch.cat(points), appearance=torch.cat(rows))
-            if self.associate:
-                sel = [select(o[0], o[1], o[2], o[3], self.model.test_mode) for o in outs]
-                splits = [(frames[t - 1]['n'], frames[t]['n']) for t in ts]
-                if self.track:
-                    done = fetch_solve(queue_solve(sel, splits, track=self.track_state,
-                                                   frame_idx=[(t - 1, t) for t in ts]))
-                else:
-                    done = fetch_solve(queue_solve(sel, splits))
-                for t, sc in zip(ts, done):
-                    res.append(self._deliver(t, sc, on_scores, on_assign, on_tracks))
-                    self.stats['pairs'] += 1
-                continue
-            for t, o in zip(ts, outs):
-                sc = self.hand_off(tuple(o) + (None,))
-                if on_scores is not None:
-                    on_scores(t, sc)
-                res.append(sc)
-                self.stats['pairs'] += 1
+                outs = self.model.forward_batch(plan, None, torch.cat([f['points'] for f in both]),
+                                                appearance=torch.cat([f['rows'].rows for f in both]))
+            done = self.finish_hand_off(self.queue_hand_off(outs, pairs))
+            for (t, _, _), r in zip(pairs, done):
+                res.append(self._deliver(t, r, on_scores, on_assign, on_tracks))
         return res
 
 

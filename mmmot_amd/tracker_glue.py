@@ -6,11 +6,21 @@
 does the same selection and moves the selected rows to the host in ONE packed copy, returning CPU tensors
 with exactly the shapes the solver indexes.  ``predict_assign`` also solves the association on the device
 (mmmot_amd.association, the ``ortools_solve`` drop-in) and brings scores and assignment back in one copy.
+
+A sequence queues before it waits: ``queue_solve`` (solve, and the track IDs with ``track=``) and ``queue_scores``
+(scores only) return a ``HandOff``, and ``HandOff.fetch()`` is the host copy, a list with one ``PairResult`` (scores,
+assignment, ids) per pair.  ``unpack_hand_off`` is the host-only reading of the copied buffer's layout.
 """
+from collections import namedtuple
+
 import torch
 
 from .association import associate, pairs_table, select, split_of, unpack
 from .tracks import queue_ids, split_ids
+
+# one pair on the host: scores as ``scores_for_solver`` returns them, assignment as ``ortools_solve`` does, ids =
+# (ids0, ids1, frame_start, last_id) of ``tracks.split_ids``; None where the stage was not asked for
+PairResult = namedtuple('PairResult', 'scores assignment ids')
 
 
 def scores_for_solver(det_score, link_scores, new_score, end_score, test_mode):
@@ -38,62 +48,81 @@ def predict_scores(model, det_imgs, det_info, det_split):
     return scores_for_solver(det_score, link_score, new_score, end_score, model.test_mode)
 
 
+class HandOff:
+    """B frame pairs queued behind their forward, one ``fetch()`` from the host.  ``flat``: the device buffer still to
+    be copied (None: nothing is left on the device), read by ``unpack_hand_off`` with ``layout`` = (splits, S, K,
+    n_ids).  ``done``: per pair the (scores, assignment) a pair with an empty frame was given on the host at queue time;
+    ``flat`` then holds the IDs alone.  ``outs`` (``queue_scores``): per pair the device outputs of a score-only hand-off."""
+
+    def __init__(self, layout=None, flat=None, done=None, outs=None, test_mode=0):
+        self.layout, self.flat, self.done, self.outs, self.test_mode = layout, flat, done, outs, test_mode
+
+    def fetch(self):
+        """the host copy -> per pair a ``PairResult``: ONE device-to-host copy of ``flat``; score-only: one per pair"""
+        if self.outs is not None:
+            return [PairResult(scores_for_solver(o[0], o[1], o[2], o[3], self.test_mode), None, None) for o in self.outs]
+        flat = None if self.flat is None else self.flat.to('cpu')
+        if self.done is None:
+            return unpack_hand_off(flat, *self.layout)
+        splits, _, _, n_ids = self.layout
+        return [PairResult(sc, asg, i) for (sc, asg), i in zip(self.done, unpack_ids(flat, splits, n_ids))]
+
+
+def unpack_ids(flat, splits, n_ids):
+    """the last ``n_ids`` elements of the host buffer (int32 bits, ``tracks.queue_ids``) -> per pair (ids0, ids1,
+    frame_start, last_id) as ``tracks.split_ids`` gives them; None per pair when no IDs were queued"""
+    if not n_ids:
+        return [None] * len(splits)
+    return split_ids(flat[flat.numel() - n_ids:].view(torch.int32).numpy(), splits)
+
+
+def unpack_hand_off(flat, splits, S, K, n_ids=0):
+    """Host fp32 buffer [det S | new S | end S | link K of every pair | per pair the solver block [det L | new L | end L
+    | link N*M] | n_ids int32 bits] -> per pair ``PairResult`` (views of ``flat``); S = sum of N + M, K = sum of N * M."""
+    ids = unpack_ids(flat, splits, n_ids)
+    res, so, lo = [], 0, 0
+    for (N, M), o, i in zip(splits, pairs_table(splits)[1], ids):
+        L = N + M
+        scores = (flat[so:so + L], [flat[3 * S + lo:3 * S + lo + N * M].view(1, N, M)], flat[S + so:S + so + L],
+                  flat[2 * S + so:2 * S + so + L])
+        o += 3 * S + K
+        res.append(PairResult(scores, unpack(flat[o:o + 3 * L + N * M], N, M), i))
+        so += L
+        lo += N * M
+    return res
+
+
+def queue_scores(outs, test_mode):
+    """The score-only hand-off of B pairs: ``outs`` per pair the device outputs (det 3xL, [link 3xNxM], new 3xL, end
+    3xL, ..) of the forward; ``fetch()`` runs ``scores_for_solver`` on each."""
+    return HandOff(outs=outs, test_mode=test_mode)
+
+
 def queue_solve(selected, splits, track=None, frame_idx=None):
     """Queue the association of B frame pairs behind their forward; nothing waits.  ``selected``: per pair the device
     rows (det L, [link 1 x N x M], new L, end L) of ``association.select``; ``splits``: per pair (N, M).  Returns the
-    pending hand-off for ``fetch_solve``: one device buffer [det | new | end | link of every pair | solver output].
+    pending ``HandOff``: one device buffer [det | new | end | link of every pair | solver output].
     ``track`` (a tracks.TrackState; the pairs are then CONSECUTIVE pairs of its sequence, ``frame_idx`` their frame
     index pairs): the ID launch is queued behind the solve and its int32 result rides at the end of the same buffer."""
     splits = [(int(N), int(M)) for N, M in splits]
     if any(N == 0 or M == 0 for N, M in splits):  # an empty frame: nothing to link, answered on the host
         host = [scores_for_solver(d.unsqueeze(0), l, n.unsqueeze(0), e.unsqueeze(0), 0) for d, l, n, e in selected]
-        if track is None:
-            return {'host': host, 'splits': splits}
-        # the IDs still come from the kernel, so that the state stays on the device: the assignments are uploaded
         done = [(sc, associate(sc[0], sc[1], sc[2], sc[3], split)) for sc, split in zip(host, splits)]
+        if track is None:
+            return HandOff((splits, 0, 0, 0), done=done)
+        # the IDs still come from the kernel, so that the state stays on the device: the assignments are uploaded
         blocks = torch.cat([t.reshape(-1).to(torch.float32) for _, a in done for t in (a[0], a[2], a[3], a[1][0])])
-        return {'done': done, 'splits': splits, 'ids': queue_ids(track, blocks.to(track.buf.device), splits, frame_idx)}
+        ids = queue_ids(track, blocks.to(track.buf.device), splits, frame_idx)
+        return HandOff((splits, 0, 0, ids.numel()), ids.view(torch.float32), done)
     cat = lambda k: torch.cat([(s[k][0] if k == 1 else s[k]).reshape(-1) for s in selected])
     det, new, end, link = cat(0), cat(2), cat(3), cat(1)
     S, K = det.numel(), link.numel()
     buf = torch.cat([det, new, end, link])
-    pairs, offs = pairs_table(splits)
-    out, _ = torch.ops.mmmot.associate(buf[0:S], buf[S:2 * S], buf[2 * S:3 * S], buf[3 * S:], pairs)
-    pending = {'splits': splits, 'offs': offs, 'S': S, 'K': K}
+    out, _ = torch.ops.mmmot.associate(buf[0:S], buf[S:2 * S], buf[2 * S:3 * S], buf[3 * S:], pairs_table(splits)[0])
     if track is None:
-        pending['flat'] = torch.cat([buf, out])
-    else:
-        ids = queue_ids(track, out, splits, frame_idx)
-        pending['flat'] = torch.cat([buf, out, ids.view(torch.float32)])  # the bits travel; no value is converted
-        pending['n_ids'] = ids.numel()
-    return pending
-
-
-def fetch_solve(pending):
-    """The ONE device-to-host copy of ``queue_solve``'s buffer -> per pair (scores, assignment): scores as
-    ``scores_for_solver`` returns them, assignment as ``ortools_solve`` does (CPU tensors).  Queued with ``track``: per
-    pair (scores, assignment, (ids0, ids1, frame_start, last_id)), the IDs as ``tracks.split_ids`` gives them."""
-    if 'host' in pending:
-        return [(sc, associate(sc[0], sc[1], sc[2], sc[3], split)) for sc, split in zip(pending['host'], pending['splits'])]
-    if 'done' in pending:
-        ids = split_ids(pending['ids'].cpu().numpy(), pending['splits'])
-        return [(sc, asg, i) for (sc, asg), i in zip(pending['done'], ids)]
-    flat = pending['flat'].to('cpu')
-    S, K = pending['S'], pending['K']
-    ids = None
-    if 'n_ids' in pending:
-        ids = split_ids(flat[flat.numel() - pending['n_ids']:].view(torch.int32).numpy(), pending['splits'])
-    res, so, lo = [], 0, 0
-    for p, ((N, M), o) in enumerate(zip(pending['splits'], pending['offs'])):
-        L = N + M
-        scores = (flat[so:so + L], [flat[3 * S + lo:3 * S + lo + N * M].view(1, N, M)], flat[S + so:S + so + L],
-                  flat[2 * S + so:2 * S + so + L])
-        o += 3 * S + K
-        asg = unpack(flat[o:o + 3 * L + N * M], N, M)
-        res.append((scores, asg) if ids is None else (scores, asg, ids[p]))
-        so += L
-        lo += N * M
-    return res
+        return HandOff((splits, S, K, 0), torch.cat([buf, out]))
+    ids = queue_ids(track, out, splits, frame_idx)
+    return HandOff((splits, S, K, ids.numel()), torch.cat([buf, out, ids.view(torch.float32)]))  # bits, not values
 
 
 def predict_assign(model, det_imgs, det_info, det_split):
@@ -103,4 +132,4 @@ def predict_assign(model, det_imgs, det_info, det_split):
     with torch.no_grad():
         det_score, link_score, new_score, end_score, _ = model(det_imgs, det_info, det_split)
     sel = select(det_score, link_score, new_score, end_score, model.test_mode)
-    return fetch_solve(queue_solve([sel], [split_of(det_split)]))[0]
+    return queue_solve([sel], [split_of(det_split)]).fetch()[0][:2]

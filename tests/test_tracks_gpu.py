@@ -232,7 +232,7 @@ def test_sequence_pipeline_tracks_in_three_orders():
 
 def test_queue_solve_with_an_empty_frame():
     """a frame without detections is answered on the host; its IDs still come from the kernel and the state"""
-    from mmmot_amd.tracker_glue import fetch_solve, queue_solve
+    from mmmot_amd.tracker_glue import queue_solve
     rng = np.random.default_rng(3)
     t = lambda x: torch.from_numpy(x).cuda()
     state, ref, counts = TrackState('cuda'), Tracker(), [4, 0, 3, 5]
@@ -240,8 +240,8 @@ def test_queue_solve_with_an_empty_frame():
         N, M = counts[p], counts[p + 1]
         det, new, end, link = (t(x) for x in random_instance(rng, N, M, 1.0, 'eval'))
         sel = [(det, [link.view(1, N, M)], new, end)]
-        plain = fetch_solve(queue_solve(sel, [(N, M)]))[0]
-        sc, asg, (ids0, ids1, start, last) = fetch_solve(queue_solve(sel, [(N, M)], track=state, frame_idx=[(p, p + 1)]))[0]
+        plain = queue_solve(sel, [(N, M)]).fetch()[0]
+        sc, asg, (ids0, ids1, start, last) = queue_solve(sel, [(N, M)], track=state, frame_idx=[(p, p + 1)]).fetch()[0]
         assert all(torch.equal(x, y) for x, y in zip((asg[0], asg[1][0], asg[2], asg[3]),
                                                      (plain[1][0], plain[1][1][0], plain[1][2], plain[1][3])))
         w0, w1, ws = ref.pair(asg[0].numpy(), asg[1][0].numpy(), asg[2].numpy(), N, M, p, p + 1)

@@ -85,19 +85,14 @@ def host_ms(fn, inst, reps):
 
 
 def pipeline_fps(frames, repeats):
-    from concurrent.futures import ThreadPoolExecutor
-
-    from bench_sequence import KW
     from mmmot_amd import TrackingNet
-    from mmmot_amd.pipeline import FrameFeed, time_sequence
-    from mmmot_amd.synth import make_frame
+    from mmmot_amd.pipeline import time_sequence
     from mmmot_amd.weights import init_module
+    from seq_workload import KW, sequence_feeds
     model = TrackingNet(**KW)
     init_module(model, seed=0)
     model.eval().cuda()
-    ndet = np.random.default_rng(5).integers(10, 13, frames)
-    with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as pool:
-        feeds = [FrameFeed(*f) for f in pool.map(lambda t: make_frame(7000 + t, 120000, int(ndet[t])), range(frames))]
+    feeds = sequence_feeds(frames)
     fps = {False: [], True: []}
     for assoc in (False, True):  # untimed warm run of both
         time_sequence(model, feeds[:6], 224, associate=assoc)

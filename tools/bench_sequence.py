@@ -15,7 +15,6 @@ import json
 import os
 import sys
 import time
-from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -25,14 +24,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from mmmot_amd import TrackingNet  # noqa: E402
-from mmmot_amd.pipeline import FrameFeed, SequencePipeline  # noqa: E402
-from mmmot_amd.synth import make_frame  # noqa: E402
+from mmmot_amd.pipeline import SequencePipeline  # noqa: E402
 from mmmot_amd.weights import init_module  # noqa: E402
-
-KW = dict(seq_len=2, score_arch='branch_cls', appear_arch='vgg', appear_len=512, appear_skippool=True, appear_fpn=False,
-          point_arch='v1', point_len=512, without_reflectivity=True, end_arch='v2', end_mode='avg', test_mode=2,
-          neg_threshold=0.2, dropblock=0, use_dropout=False, score_fusion_arch='A', affinity_op='multiply',
-          softmax_mode='none')
+from seq_workload import KW, detections, sequence_feeds  # noqa: E402
 
 
 def same(a, b):
@@ -61,9 +55,7 @@ def main():
     model.eval().to(dev)
     model.set_trunk(args.trunk)
     n = args.frames
-    ndet = np.random.default_rng(5).integers(10, 13, n)
-    with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as pool:
-        feeds = [FrameFeed(*f) for f in pool.map(lambda t: make_frame(7000 + t, 120000, int(ndet[t])), range(n))]
+    ndet, feeds = detections(n), sequence_feeds(n)
     K, B = args.frames_per_encode, args.pairs_per_forward
     modes = {
         'per_pair': lambda p: p.run(feeds),
