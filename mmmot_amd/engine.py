@@ -22,6 +22,7 @@ import torch
 from .ops import (ACT_NONE, ACT_RELU, ACT_SIGMOID, A_NORM_RELU, A_PAIR, A_PLAIN, FUSION_MODES, PAIR_OPS,
                   SOFTMAX_MODES)
 from .range_guard import RangeGuard
+from .tape import norm_layer
 
 POOL_INPUT = {'f32': 0, 'hl16': 1, 'hq8': 2}  # the segment mean's `hl16` argument: the format its input rows are stored in
 EPS = 1e-5  # nn.GroupNorm / nn.BatchNorm default used everywhere in the reference
@@ -54,6 +55,8 @@ def check_crop_layout(dets):
 
 
 class Engine:
+    eps = EPS
+
     def __init__(self, packed, ops, fusion='A', affinity_op='multiply', softmax_mode='none',
                  neg_threshold=0.0, score_arch='branch_cls', end_mode='avg', trunk=None):
         trunk = trunk or os.environ.get('MMMOT_TRUNK', 'f16x3')
@@ -120,10 +123,16 @@ class Engine:
         self.ws = {}
         self.dev = None
         self.keep = None         # optional dict collecting per-stage tensors (tests)
+        self._tape = None        # recording(): the dict the running schedule records its layers in
         self.conv_events = None  # optional list collecting per-launch HIP events (bench.py)
 
     # ---- workspace arena ---------------------------------------------------
     def buf(self, name, *shape, device=None, dtype=torch.float32):
+        if self._tape is not None:  # recording(): owned storage, a tape must survive the next forward
+            return torch.empty(*shape, dtype=dtype, device=device if device is not None else self.dev)
+        return self._arena(name, *shape, device=device, dtype=dtype)
+
+    def _arena(self, name, *shape, device=None, dtype=torch.float32):
         n = 1
         for s in shape:
             n *= int(s)
@@ -136,10 +145,14 @@ class Engine:
     def buf64(self, name, *shape):
         return self.buf(name, *shape, dtype=torch.float64)
 
-    def _finalize(self, name, part, tiles, C, NG, gamma, beta):
+    def _finalize(self, name, part, tiles, C, NG, gamma, beta, Y=None):
+        """GroupNorm (NG groups) scale / shift of the layer `name` from its per-tile statistics `part`.  `Y`: the layer's
+        pre-norm output, for the tape.Layer that recording() keeps under `name`."""
         sc = self.buf(name + '_sc', tiles.G, C)
         sh = self.buf(name + '_sh', tiles.G, C)
         self.ops.gn_finalize(part, tiles, C, NG, gamma, beta, EPS, sc, sh)
+        if self._tape is not None:
+            self._tape[name] = norm_layer(self, part, tiles, Y, C, NG, gamma, beta, sc, sh)
         return sc, sh
 
     def _gemm(self, d, name, tiles, N, K, **kw):
@@ -156,7 +169,19 @@ class Engine:
         Y = self.buf(y, tiles.R, N)
         part = self._part(tiles, N)
         self._gemm(d, name, tiles, N, K, Y=Y, part=part, **kw)
-        return (Y,) + self._finalize(gn, part, tiles, N, NG, gamma, beta)
+        return (Y,) + self._finalize(gn, part, tiles, N, NG, gamma, beta, Y=Y)
+
+    @contextlib.contextmanager
+    def recording(self):
+        """The training forward is the forward, recorded.  Inside the block buf() hands out owned tensors instead of arena
+        views (the statistics scratch `part` stays in the arena: the finalize right behind the GEMM consumes it), every
+        _finalize also computes the unit statistics and keeps a tape.Layer under its name, and _stash keeps its tensor
+        under its key.  Yields that dict: {'aff_1': Layer, ..., 'aff_v': tensor, ...}."""
+        prev, self._tape = self._tape, {}
+        try:
+            yield self._tape
+        finally:
+            self._tape = prev
 
     @contextlib.contextmanager
     def fp32_mlp(self):
@@ -176,11 +201,13 @@ class Engine:
         return st
 
     def _part(self, tiles, N):
-        return self.buf('part', tiles.T, 2, N)
+        return self._arena('part', tiles.T, 2, N)
 
     def _stash(self, key, t):
         if self.keep is not None:
             self.keep[key] = t.detach().clone()
+        if self._tape is not None:
+            self._tape[key] = t
 
     # ---- image branch: VGG16-BN trunk + SkipPool heads ---------------------
     def appearance(self, plan, crops, cat):
@@ -450,8 +477,8 @@ class Engine:
         part = self._part(PT, 1024)
         self._gemm(lk, 'wa', PT, 1024, 512, FA=Ff, FB=Ff, pair=pair, amode=A_PAIR,
                  pairop=PAIR_OPS[self.affinity_op], bias=lk['ba'], Y=ya, part=part)
-        sc_ne, sh_ne = self._finalize('aff_ne0', part[:, :, 0:512], PT, 512, 1, lk['g_ne0'], lk['be_ne0'])
-        sc1, sh1 = self._finalize('aff_1', part[:, :, 512:1024], PT, 512, 512, lk['g1'], lk['be1'])
+        sc_ne, sh_ne = self._finalize('aff_ne0', part[:, :, 0:512], PT, 512, 1, lk['g_ne0'], lk['be_ne0'], Y=ya[:, 0:512])
+        sc1, sh1 = self._finalize('aff_1', part[:, :, 512:1024], PT, 512, 512, lk['g1'], lk['be1'], Y=ya[:, 512:1024])
         # new / end vectors: strided means of relu(gn(conv0)) over the prev / curr axis
         V = self.buf('aff_v', VT.R, 512)
         ops.segment_mean(ya[:, 0:512], 512, plan.v_segs, V, sc=sc_ne, sh=sh_ne, relu=True,
@@ -471,6 +498,7 @@ class Engine:
                                      bias=lk['b6'], sc=sc4, sh=sh4, amode=A_NORM_RELU)
         logits = torch.empty(R, dtype=torch.float32, device=F.device)
         ops.rowdot(y6, 128, lk['w9'], lk['b9'], PT, logits, sc=sc7, sh=sh7)
+        self._stash('aff_logits', logits)
         link = logits
         if self.softmax_mode != 'none':
             link = torch.empty_like(logits)

@@ -2,7 +2,7 @@
 
 The reference's training step is ``tracking_model.py:50-66``: training-mode ``TrackingNet.forward`` ->
 ``generate_gt`` (host) -> ``TrackingLoss`` (``cost.py:134-185``) -> ``loss.backward()`` -> ``optimizer.step()``.
-``mmmot_amd/backward.py`` built the head (fusion, w_det in training mode, the pairwise block); this file adds
+``mmmot_amd/backward.py`` is the head (fusion, w_det in training mode, the pairwise block); this file adds
 
 * ``pointnet_autograd(model, plan, points)``: ``PointNet_v1.forward`` (reference modules/point_net.py:25-44, 115-153)
   as a differentiable operator.  PointNet contains GroupNorm only (no BatchNorm; dropout is off in every config), so its
@@ -31,11 +31,13 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as Fn
 
-from .backward import _aux, _colsum, _current_engine, _gn_backward, _norm_layer, dgrad_gemm, head_autograd
+from .backward import current_engine, head_autograd
 from .ops import ACT_RELU, A_NORM_RELU, A_PLAIN, LOSS_KINDS
 from .plan import Segments
+from .tape import colsum, dgrad_gemm, gn_backward, norm_layer, taped, weight_grad
+from .train_vgg import appearance_autograd
 
-# folded tensor name -> produced by fold_pointnet(); order = argument order of _PointNetFn
+# folded tensor name -> produced by fold_pointnet(); order = parameter order of pointnet_autograd's taped function
 FOLDED = ('w1', 'b1', 'g1', 'be1', 'w2', 'b2', 'g2', 'be2', 'w3', 'b3', 'g3', 'be3', 'w4', 'b4', 'g4', 'be4',
           'w5', 'b5', 'g5', 'be5', 'wc1a', 'wc1b', 'bc1', 'gc1', 'bec1', 'wc2', 'bc2', 'gc2', 'bec2')
 
@@ -83,18 +85,6 @@ def _paux(plan):
     return plan._pn_bwd_aux
 
 
-def _weight_grad(eng, dY, tiles, N, K, **kw):
-    """(dW [N][K], db [N]) = (dY^T A, column sums of dY); rows split into shares whose partials are added (deterministic)"""
-    dev = dY.device
-    ns = max(1, min(16, tiles.T // 8))
-    dWp = torch.empty(ns, N * K, dtype=torch.float32, device=dev)
-    dbp = torch.empty(ns, N, dtype=torch.float32, device=dev)
-    eng.ops.gemm_tn(dY, tiles, N, K, dWp, dbp, nsplit=ns, **kw)
-    if ns > 1:
-        return _colsum(eng, dWp).view(N, K), _colsum(eng, dbp)
-    return dWp.view(N, K), dbp.view(N)
-
-
 def pointnet_forward_train(eng, plan, points, W):
     """points [P][3 | 4], W = folded fp32 tensors (fold_pointnet) -> (features [Lt][512], tape)."""
     ops, T, D, Pn, Lt = eng.ops, plan.pt_tiles, plan.det_tiles, plan.P, plan.Lt
@@ -103,12 +93,12 @@ def pointnet_forward_train(eng, plan, points, W):
     t = {}
     y1, part = new(Pn, 64), new(T.T, 2, 64)
     ops.pointnet_layer1(points, W['w1'], W['b1'], y1, part, T)
-    L = t['p1'] = _norm_layer(eng, part, T, y1, 64, 64, W['g1'], W['be1'])
+    L = t['p1'] = norm_layer(eng, part, T, y1, 64, 64, W['g1'], W['be1'])
     x = y1
     for i, (N, K) in zip((2, 3, 4, 5), ((64, 64), (64, 64), (128, 64), (1024, 128))):
         y, part = new(Pn, N), new(T.T, 2, N)
         ops.gemm(W['w%d' % i], T, N, K, X=x, bias=W['b%d' % i], Y=y, part=part, sc=L.sc, sh=L.sh, amode=A_NORM_RELU)
-        L = t['p%d' % i] = _norm_layer(eng, part, T, y, N, N, W['g%d' % i], W['be%d' % i])
+        L = t['p%d' % i] = norm_layer(eng, part, T, y, N, N, W['g%d' % i], W['be%d' % i])
         x = y
     seg1024 = new(Lt, 1024)
     ops.segment_mean(x, 1024, plan.det_segs, seg1024, sc=L.sc, sh=L.sh, relu=True)      # point_net.py:139-146
@@ -117,12 +107,12 @@ def pointnet_forward_train(eng, plan, points, W):
     yc1, part = new(Pn, 512), new(T.T, 2, 512)
     ops.gemm(W['wc1a'], T, 512, 64, X=y1, Y=yc1, part=part, sc=t['p1'].sc, sh=t['p1'].sh, amode=A_NORM_RELU,
              dbias=dbias, rowidx=plan.row_det)
-    t['c1'] = _norm_layer(eng, part, T, yc1, 512, 512, W['gc1'], W['bec1'])
+    t['c1'] = norm_layer(eng, part, T, yc1, 512, 512, W['gc1'], W['bec1'])
     seg512 = new(Lt, 512)
     ops.segment_mean(yc1, 512, plan.det_segs, seg512, sc=t['c1'].sc, sh=t['c1'].sh, relu=True)  # point_net.py:32-39
     yc2, part = new(Lt, 512), new(D.T, 2, 512)
     ops.gemm(W['wc2'], D, 512, 512, X=seg512, bias=W['bc2'], Y=yc2, part=part)
-    t['c2'] = _norm_layer(eng, part, D, yc2, 512, 16, W['gc2'], W['bec2'])
+    t['c2'] = norm_layer(eng, part, D, yc2, 512, 16, W['gc2'], W['bec2'])
     out = new(Lt, 512)
     ops.affine_act(yc2, 512, t['c2'].sc, t['c2'].sh, D, ACT_RELU, out)
     t.update(seg1024=seg1024, seg512=seg512)
@@ -138,18 +128,16 @@ def pointnet_backward(eng, plan, points, W, t, dOut):
     g = {}
     p1 = t['p1']
     # ---- PointNet_v1 head: conv2 + GroupNorm(16) + ReLU over the detections (point_net.py:40) ----
-    dyc2, g['gc2'], g['bec2'] = _gn_backward(eng, plan, t['c2'], dOut)
-    g['wc2'], g['bc2'] = _weight_grad(eng, dyc2, D, 512, 512, X=t['seg512'], amode=A_PLAIN)
-    dseg512 = new(Lt, 512)
-    dgrad_gemm(eng, W['wc2'], D, dyc2, dseg512)
+    dseg512, g['wc2'], g['bc2'], g['gc2'], g['bec2'] = t['c2'].backward(eng, plan, dOut, W['wc2'], X=t['seg512'],
+                                                                        amode=A_PLAIN)
     # ---- per-detection average of relu(gn(conv1)) (point_net.py:32-39), conv1 1088 -> 512 + GroupNorm(512) ----
     dAc1 = new(Pn, 512)
     ops.rows_gather_scale(dseg512, plan.row_det, aux.inv_cnt, dAc1, 512)
-    dyc1, g['gc1'], g['bec1'] = _gn_backward(eng, plan, t['c1'], dAc1)
-    g['wc1a'], _ = _weight_grad(eng, dyc1, T, 512, 64, X=p1.Y, sc=p1.sc, sh=p1.sh, amode=A_NORM_RELU)
+    dyc1, g['gc1'], g['bec1'] = gn_backward(eng, plan, t['c1'], dAc1)
+    g['wc1a'], _ = weight_grad(eng, dyc1, T, 512, 64, X=p1.Y, sc=p1.sc, sh=p1.sh, amode=A_NORM_RELU)
     ddbias = new(Lt, 512)  # the 1024 broadcast channels act as a per-detection bias: its gradient is the row SUM
     ops.segment_mean(dyc1, 512, aux.det_sum, ddbias, use_group=False)
-    g['wc1b'], g['bc1'] = _weight_grad(eng, ddbias, D, 512, 1024, X=t['seg1024'], amode=A_PLAIN)
+    g['wc1b'], g['bc1'] = weight_grad(eng, ddbias, D, 512, 1024, X=t['seg1024'], amode=A_PLAIN)
     dseg1024 = new(Lt, 1024)
     dgrad_gemm(eng, W['wc1b'], D, ddbias, dseg1024)
     dA1c = new(Pn, 64)
@@ -157,37 +145,19 @@ def pointnet_backward(eng, plan, points, W, t, dOut):
     # ---- PointNetfeatGN: average of relu(gn5(conv5)) back to the points, then the conv5 .. conv2 chain ----
     dA = new(Pn, 1024)
     ops.rows_gather_scale(dseg1024, plan.row_det, aux.inv_cnt, dA, 1024)
-    for i, (N, K) in zip((5, 4, 3, 2), ((1024, 128), (128, 64), (64, 64), (64, 64))):
+    for i in (5, 4, 3, 2):
         Li, Lp = t['p%d' % i], t['p%d' % (i - 1)]
-        dy, g['g%d' % i], g['be%d' % i] = _gn_backward(eng, plan, Li, dA)
-        g['w%d' % i], g['b%d' % i] = _weight_grad(eng, dy, T, N, K, X=Lp.Y, sc=Lp.sc, sh=Lp.sh, amode=A_NORM_RELU)
-        dA = new(Pn, K)
-        dgrad_gemm(eng, W['w%d' % i], T, dy, dA)
+        dA, g['w%d' % i], g['b%d' % i], g['g%d' % i], g['be%d' % i] = Li.backward(
+            eng, plan, dA, W['w%d' % i], X=Lp.Y, sc=Lp.sc, sh=Lp.sh, amode=A_NORM_RELU)
     dA1 = new(Pn, 64)
     ops.add_rows(dA, dA1c, dA1, 64)  # relu(gn1(.)) feeds conv2 and the 64-channel skip of PointNet_v1.conv1
-    dy1, g['g1'], g['be1'] = _gn_backward(eng, plan, p1, dA1)
+    dy1, g['g1'], g['be1'] = gn_backward(eng, plan, p1, dA1)
     kin = int(points.shape[1])
     PW = new(T.T, 64 * (kin + 1))
     ops.pointnet_layer1_bwd(dy1, points, T, PW)
-    pw = _colsum(eng, PW).view(64, kin + 1)
+    pw = colsum(eng, PW).view(64, kin + 1)
     g['w1'], g['b1'] = pw[:, :kin], pw[:, kin]
     return g
-
-
-class _PointNetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, points, eng, plan, *folded):
-        W = {k: v.detach().to(torch.float32).contiguous() for k, v in zip(FOLDED, folded)}
-        pts = points.detach().contiguous()
-        out, tape = pointnet_forward_train(eng, plan, pts, W)
-        ctx.eng, ctx.plan, ctx.W, ctx.tape, ctx.pts = eng, plan, W, tape, pts
-        ctx.shapes = [tuple(v.shape) for v in folded]
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        g = pointnet_backward(ctx.eng, ctx.plan, ctx.pts, ctx.W, ctx.tape, d_out.contiguous())
-        return (None, None, None) + tuple(g[k].reshape(s) for k, s in zip(FOLDED, ctx.shapes))
 
 
 def pointnet_autograd(model, plan, points):
@@ -195,7 +165,14 @@ def pointnet_autograd(model, plan, points):
     (features [Lt][512] on the autograd graph of every ``point_net.*`` parameter, [trans1, trans2])."""
     eng = model.engine()
     W, trans = fold_pointnet(model.point_net)
-    out = _PointNetFn.apply(points, eng, plan, *[W[k] for k in FOLDED])
+
+    def fwd(pts, folded):
+        Wd = {k: v.to(torch.float32).contiguous() for k, v in zip(FOLDED, folded)}
+        out, tape = pointnet_forward_train(eng, plan, pts, Wd)
+        return (out,), (Wd, tape)
+
+    out, = taped(points, FOLDED, [W[k] for k in FOLDED], fwd,
+                 lambda pts, t, d_out: (None, pointnet_backward(eng, plan, pts, t[0], t[1], d_out)))
     return out, trans
 
 
@@ -235,7 +212,7 @@ class _ScoreLossFn(torch.autograd.Function):
 
 class TrackingLoss(nn.Module):
     """reference cost.py:134-185, same constructor and call signature.  ``detloss_type`` / ``endloss_type``: 'bce',
-    'l2', 'l1' (DetLoss, cost.py:97-131; 'ghm' is not built), ``linkloss_type`` 'l2' or 'l1' (LinkLoss, cost.py:66-94;
+    'l2', 'l1', 'ghm' (DetLoss, cost.py:97-131), ``linkloss_type`` 'l2' or 'l1' (LinkLoss, cost.py:66-94;
     like the reference, the constructor's own default 'l2_softmax' fails cost.py:73's assert - pass the config's value).  Scores are device tensors of the training-mode forward (``forward_train``)."""
 
     def __init__(self, smooth_ratio=0, detloss_type='bce', endloss_type='l2', det_ratio=0.4, trans_ratio=0.4,
@@ -358,9 +335,8 @@ def forward_train(model, dets, det_info, dets_split):
         while len(cache) >= cap:
             cache.popitem(last=False)
         plan = cache[key] = BatchPlan([(fc, ps)], S, points.device, rows=(0, 1, 2), use_points=True)
-    eng = _current_engine(model)
+    eng = current_engine(model)
     if not getattr(model, 'freeze_appearance', False):
-        from .train_vgg import appearance_autograd
         img = appearance_autograd(model, plan, dets)   # training-mode trunk: batch-statistics BatchNorm2d, differentiable
     else:                                              # frozen image branch: the eval-mode (folded) inference trunk
         with torch.no_grad():

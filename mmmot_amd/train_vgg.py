@@ -18,13 +18,12 @@ scaling of the stage outputs and of their gradients runs on the device (_dropblo
 import numpy as np
 import torch
 
-from .backward import _colsum, _gn_backward, _norm_layer, det_batch_stats, dgrad_gemm
 from .ops import ACT_NONE, ACT_RELU, A_NORM_RELU, A_PLAIN
 from .pack import VGG_STAGES
 from .plan import RowTiles, Segments
-from .train import _weight_grad
+from .tape import colsum, gn_backward, norm_layer, taped
+from .tape import update_running_stats as momentum_update  # appearance_autograd has a flag of that name
 
-EPS = 1e-5
 HEAD_KEYS = ('0.weight', '0.bias', '1.weight', '1.bias', '2.weight', '2.bias', '4.weight', '4.bias', '5.weight', '5.bias')
 
 
@@ -42,11 +41,6 @@ def _ident_rows(cache, n, dev):
     if key not in cache:
         cache[key] = torch.arange(n, dtype=torch.int32, device=dev)
     return cache[key]
-
-
-def _colsum_big(eng, X):
-    """column sums of a tall [rows][C] tensor (the bias gradient of a trunk layer): _colsum's levels of 128-row chunks"""
-    return _colsum(eng, X)
 
 
 def _f16_convs(ops):
@@ -116,7 +110,7 @@ def appearance_forward_train(eng, model, plan, crops, P):
         T = _tiles(cache, rows, dev)
         part = new(T.T, 2, cout)
         ops.rows_stats(Z, cout, T, part)
-        Lyr = _norm_layer(eng, part, T, Z, cout, cout, P[pre + '%d.weight' % (cidx + 1)], P[pre + '%d.bias' % (cidx + 1)])
+        Lyr = norm_layer(eng, part, T, Z, cout, cout, P[pre + '%d.weight' % (cidx + 1)], P[pre + '%d.bias' % (cidx + 1)])
         Ho, Wo = (H // 2, W // 2) if pool else (H, W)
         A = new(L * Ho * Wo, cout)
         ops.bn_relu_pool(Z, cout, Lyr.sc, Lyr.sh, L, H, W, pool, A)
@@ -186,40 +180,31 @@ def _head_forward(eng, plan, cache, s, x, hw, C, P, feats, drop=None):
         ops.segment_mean(x, C, seg, Pm, use_group=False)
     part = new(T1.T, 2, C)
     ops.rows_stats(Pm, C, T1, part)
-    L0 = _norm_layer(eng, part, T1, Pm, C, 1, P[pre + '0.weight'], P[pre + '0.bias'])
+    L0 = norm_layer(eng, part, T1, Pm, C, 1, P[pre + '0.weight'], P[pre + '0.bias'])
     x0 = new(L, C)
     ops.affine_act(Pm, C, L0.sc, L0.sh, T1, ACT_NONE, x0)      # GroupNorm(1, C), no ReLU
     w1 = P[pre + '1.weight'].flatten(1).contiguous()
     C4 = w1.shape[0]
     h1, part = new(L, C4), new(T1.T, 2, C4)
     ops.gemm(w1, T1, C4, C, X=x0, bias=P[pre + '1.bias'], Y=h1, part=part)
-    L2 = _norm_layer(eng, part, T1, h1, C4, 1, P[pre + '2.weight'], P[pre + '2.bias'])
+    L2 = norm_layer(eng, part, T1, h1, C4, 1, P[pre + '2.weight'], P[pre + '2.bias'])
     w4 = P[pre + '4.weight'].flatten(1).contiguous()
     h2, part = new(L, 128), new(T1.T, 2, 128)
     ops.gemm(w4, T1, 128, C4, X=h1, bias=P[pre + '4.bias'], Y=h2, part=part, sc=L2.sc, sh=L2.sh, amode=A_NORM_RELU)
-    L5 = _norm_layer(eng, part, T1, h2, 128, 1, P[pre + '5.weight'], P[pre + '5.bias'])
+    L5 = norm_layer(eng, part, T1, h2, 128, 1, P[pre + '5.weight'], P[pre + '5.bias'])
     ops.affine_act(h2, 128, L5.sc, L5.sh, T1, ACT_RELU, feats[:, 128 * s:128 * (s + 1)])
     return dict(L0=L0, L2=L2, L5=L5, x0=x0, w1=w1, w4=w4, C=C, C4=C4, hw=hw, T1=T1, stage=s, drop=drop)
 
 
 def _head_backward(eng, plan, hd, dOut, g):
     """dOut [L][128] (a column slice of d feats) -> d(stage output) as per-crop rows [L][C] (to be spread over hw pixels)"""
-    ops, L = eng.ops, plan.Lt
-    dev = dOut.device
-    new = lambda *s_: torch.empty(*s_, dtype=torch.float32, device=dev)
     pre = 'global_pool.%d.fc.' % hd['stage']
-    T1, C, C4 = hd['T1'], hd['C'], hd['C4']
-    dOutc = dOut.contiguous()
-    dh2, g[pre + '5.weight'], g[pre + '5.bias'] = _gn_backward(eng, plan, hd['L5'], dOutc)
     L2 = hd['L2']
-    g[pre + '4.weight'], g[pre + '4.bias'] = _weight_grad(eng, dh2, T1, 128, C4, X=L2.Y, sc=L2.sc, sh=L2.sh, amode=A_NORM_RELU)
-    dA1 = new(L, C4)
-    dgrad_gemm(eng, hd['w4'], T1, dh2, dA1)
-    dh1, g[pre + '2.weight'], g[pre + '2.bias'] = _gn_backward(eng, plan, L2, dA1)
-    g[pre + '1.weight'], g[pre + '1.bias'] = _weight_grad(eng, dh1, T1, C4, C, X=hd['x0'], amode=A_PLAIN)
-    dx0 = new(L, C)
-    dgrad_gemm(eng, hd['w1'], T1, dh1, dx0)
-    dP, g[pre + '0.weight'], g[pre + '0.bias'] = _gn_backward(eng, plan, hd['L0'], dx0, relu=False)
+    dA1, g[pre + '4.weight'], g[pre + '4.bias'], g[pre + '5.weight'], g[pre + '5.bias'] = hd['L5'].backward(
+        eng, plan, dOut.contiguous(), hd['w4'], X=L2.Y, sc=L2.sc, sh=L2.sh, amode=A_NORM_RELU)
+    dx0, g[pre + '1.weight'], g[pre + '1.bias'], g[pre + '2.weight'], g[pre + '2.bias'] = L2.backward(
+        eng, plan, dA1, hd['w1'], X=hd['x0'], amode=A_PLAIN)
+    dP, g[pre + '0.weight'], g[pre + '0.bias'] = gn_backward(eng, plan, hd['L0'], dx0, relu=False)
     return dP
 
 
@@ -275,14 +260,14 @@ def appearance_backward(eng, model, plan, crops, tape, dF):
         else:
             dApre = dA
         cidx = ly['cidx']
-        dZ, g[pre + '%d.weight' % (cidx + 1)], g[pre + '%d.bias' % (cidx + 1)] = _gn_backward(eng, plan, Lyr, dApre)
-        g[pre + '%d.bias' % cidx] = _colsum_big(eng, dZ)
+        dZ, g[pre + '%d.weight' % (cidx + 1)], g[pre + '%d.bias' % (cidx + 1)] = gn_backward(eng, plan, Lyr, dApre)
+        g[pre + '%d.bias' % cidx] = colsum(eng, dZ)
         rows = ly['rows']
         if ly['first']:
             nb = max(1, min(1024, rows // 512))
             PW = new(nb, 64 * 28)
             ops.conv3x3_first_wgrad(dZ, ly['x'], L, H, W, PW)
-            pw = _colsum(eng, PW).view(64, 28)
+            pw = colsum(eng, PW).view(64, 28)
             g[pre + '%d.weight' % cidx] = pw[:, :27].reshape(64, 3, 3, 3).permute(0, 3, 1, 2)  # [n][ky][kx][c] -> [n][c][ky][kx]
             dA = None
         else:
@@ -295,7 +280,7 @@ def appearance_backward(eng, model, plan, crops, tape, dF):
                 ops.conv3x3_wgrad(dZ, ly['x'], L, H, W, cin, cout, ns, dWp, amax=amz)
             else:
                 ops.conv3x3_wgrad(dZ, ly['x'], L, H, W, cin, cout, ns, dWp)
-            dW = _colsum(eng, dWp) if ns > 1 else dWp[0]
+            dW = colsum(eng, dWp) if ns > 1 else dWp[0]
             g[pre + '%d.weight' % cidx] = dW.view(3, 3, cout, cin).permute(2, 3, 0, 1)
             # input gradient: the same convolution kernel on dZ with the taps flipped and Cin / Cout swapped
             wflip = ly['wp'].flip(0).permute(0, 2, 1).contiguous()  # [tap][Cin][Cout]
@@ -315,41 +300,21 @@ def appearance_backward(eng, model, plan, crops, tape, dF):
     return g
 
 
-class _AppearanceFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, crops, eng, model, plan, keys, *params):
-        P = {k: p.detach().to(torch.float32).contiguous() for k, p in zip(keys, params)}
-        c = crops.detach().contiguous()
-        feats, tape = appearance_forward_train(eng, model, plan, c, P)
-        eng._last_vgg_tape = tape
-        ctx.eng, ctx.model, ctx.plan, ctx.tape, ctx.keys, ctx.crops = eng, model, plan, tape, keys, c
-        ctx.shapes = [tuple(p.shape) for p in params]
-        return feats
-
-    @staticmethod
-    def backward(ctx, dF):
-        g = appearance_backward(ctx.eng, ctx.model, ctx.plan, ctx.crops, ctx.tape, dF.contiguous())
-        out = []
-        for k, s in zip(ctx.keys, ctx.shapes):
-            out.append(g[k].reshape(s) if k in g else None)
-        return (None, None, None, None, None) + tuple(out)
-
-
 def appearance_autograd(model, plan, crops, update_running_stats=True):
     """Differentiable training-mode ``model.appearance``: crops [L][3][S][S] -> features [L][512]; with
     ``update_running_stats`` every BatchNorm2d buffer takes PyTorch's training-mode momentum update."""
     eng = model.engine()
     keys, ts = _param_list(model)
-    eng._last_vgg_tape = None
-    out = _AppearanceFn.apply(crops, eng, model, plan, tuple(keys), *ts)
-    tape, eng._last_vgg_tape = eng._last_vgg_tape, None
-    if update_running_stats and tape is not None:
-        with torch.no_grad():
-            for ly in tape['layers']:
-                bn = ly['bn']
-                mean, var = det_batch_stats(ly['L'], ly['rows'])
-                m = bn.momentum if bn.momentum is not None else 0.1
-                bn.running_mean.mul_(1 - m).add_(m * mean)
-                bn.running_var.mul_(1 - m).add_(m * var)
-                bn.num_batches_tracked += 1
+    tapes = []
+
+    def fwd(c, params):
+        P = {k: p.to(torch.float32).contiguous() for k, p in zip(keys, params)}
+        feats, tape = appearance_forward_train(eng, model, plan, c, P)
+        tapes.append(tape)
+        return (feats,), tape
+
+    out, = taped(crops, keys, ts, fwd, lambda c, tape, dF: (None, appearance_backward(eng, model, plan, c, tape, dF)))
+    if update_running_stats:
+        for ly in tapes[0]['layers']:
+            momentum_update(ly['bn'], ly['L'], ly['rows'])
     return out

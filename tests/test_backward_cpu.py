@@ -9,6 +9,7 @@ import torch
 from common import build_model, get_case
 from fake_ops import TorchOps
 from mmmot_amd.backward import affinity_autograd, affinity_backward, affinity_forward_train
+from mmmot_amd.synth import make_pair
 from oracle import restatement as R
 
 
@@ -196,30 +197,141 @@ def test_two_level_segment_sums_equal_the_direct_sums():
     """long strided sums (the per-tile partials of a full-resolution trunk layer: thousands of rows per segment) are
     summed in two levels - chunks, then chunk sums; short ones keep their single table"""
     import numpy as np
-    from mmmot_amd.backward import SEGSUM_CHUNK, _chunked_segments, _colsum, _segsum
+    from mmmot_amd.tape import SEGSUM_CHUNK, chunked_segments, colsum, segsum
     c, base = get_case('s2_C_multiply_none')
     eng = build_model(c, base, ops=TorchOps(torch.float64)).engine()
     g = torch.Generator().manual_seed(5)
     T, C = 5 * SEGSUM_CHUNK + 37, 8
     X = torch.randn(2 * T + 6, C, generator=g, dtype=torch.float64).float()
-    segs = _chunked_segments(np.array([0, 1, 2 * T]), np.array([T, T, 3]), 2, 'cpu')
+    segs = chunked_segments(np.array([0, 1, 2 * T]), np.array([T, T, 3]), 2, 'cpu')
     assert isinstance(segs, tuple) and segs[0].n == 2 * 6 + 1 and segs[1].n == 3
     out = torch.zeros(3, C)
-    _segsum(eng, X, C, segs, out)
+    segsum(eng, X, C, segs, out)
     want = torch.stack([X[0:2 * T:2].double().sum(0), X[1:2 * T:2].double().sum(0), X[2 * T:2 * T + 6:2].double().sum(0)])
     assert (out.double() - want).abs().max().item() < 1e-4
-    short = _chunked_segments(np.array([0, 1]), np.array([40, 40]), 2, 'cpu')
+    short = chunked_segments(np.array([0, 1]), np.array([40, 40]), 2, 'cpu')
     assert not isinstance(short, tuple)
     tall = torch.randn(9000, C, generator=g)
-    assert (_colsum(eng, tall).double() - tall.double().sum(0)).abs().max().item() < 1e-3
+    assert (colsum(eng, tall).double() - tall.double().sum(0)).abs().max().item() < 1e-3
     # 9000 x 8 is viewed as 1125 rows of 64 (three halvings, 1125 is odd), summed as 9 chunks of 128 rows, then the 9 chunk
     # sums, then the eight row classes are folded
     assert eng._colsum_segs[(1125, 'cpu')].n == 9 and eng._colsum_segs[(9, 'cpu')].n == 1
     assert (9000, 'cpu') not in eng._colsum_segs
     odd = torch.randn(1001, 12, generator=g)                      # odd row count: no folding, 8 chunks, then one segment
-    assert (_colsum(eng, odd).double() - odd.double().sum(0)).abs().max().item() < 1e-3
+    assert (colsum(eng, odd).double() - odd.double().sum(0)).abs().max().item() < 1e-3
     assert eng._colsum_segs[(1001, 'cpu')].n == 8
     wide = torch.randn(4096, 520, generator=g)[:, :512]           # a column slice (not contiguous): summed as it lies
-    assert (_colsum(eng, wide).double() - wide.double().sum(0)).abs().max().item() < 2e-3
+    assert (colsum(eng, wide).double() - wide.double().sum(0)).abs().max().item() < 2e-3
     small = torch.randn(7, 16, generator=g)
-    assert (_colsum(eng, small).double() - small.double().sum(0)).abs().max().item() < 1e-5
+    assert (colsum(eng, small).double() - small.double().sum(0)).abs().max().item() < 1e-5
+
+
+# ---- the head's training forward is the engine's forward, recorded (Engine.recording) ---------------------------------
+def tape_tensors(obj):
+    """every tensor reachable from a tape: through dicts, lists, tuples and tape.Layer records"""
+    from mmmot_amd.tape import Layer
+    if torch.is_tensor(obj):
+        yield obj
+    elif isinstance(obj, dict):
+        for v in obj.values():
+            yield from tape_tensors(v)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            yield from tape_tensors(v)
+    elif isinstance(obj, Layer):
+        yield from tape_tensors(vars(obj))
+
+
+def check_tape_owns_its_storage(m, device):
+    """head_forward_train -> an eval forward of OTHER inputs through the same engine (it overwrites the whole workspace
+    arena) -> head_backward: the gradients are those of the backward with no forward in between, bit for bit, and nothing
+    on the tape lives in the arena"""
+    from mmmot_amd.backward import head_backward, head_forward_train
+    c, _ = get_case('s2_C_multiply_none')
+    eng = m.engine()
+    ins = make_pair(c['N'], c['M'], c['S'], c['pts'], seed=c['seed'] + 1, ragged=True)
+    plan = m.make_plan([([c['N'], c['M']], ins[1]['points_split'].reshape(-1).long().numpy())], c['S'])
+    g = torch.Generator().manual_seed(8)
+    cat = (torch.randn(plan.Lt, 1024, generator=g) * 0.8).to(device)
+    w = [torch.randn(3, plan.Lt, generator=g).to(device), torch.randn(plan.pair_tiles.R, generator=g).to(device),
+         torch.randn(3, plan.Lt, generator=g).to(device), torch.randn(3, plan.Lt, generator=g).to(device)]
+    det, link, new, end, tape = head_forward_train(eng, m, plan, cat)
+    dcat0, grads0 = head_backward(eng, m, plan, cat, tape, *w)
+    with torch.no_grad():
+        m.forward_batch(plan, ins[0].to(device), ins[1]['points'].reshape(-1, 3).contiguous().to(device))
+    dcat1, grads1 = head_backward(eng, m, plan, cat, tape, *w)
+    assert torch.equal(dcat0, dcat1), 'dcat'
+    assert set(grads0) == set(grads1)
+    for k in grads0:
+        assert torch.equal(grads0[k], grads1[k]), k
+    arena = {t.untyped_storage().data_ptr() for t in tape_tensors(list(eng.ws.values()))}
+    assert len(arena) > 10  # the eval forward filled it
+    on_tape = list(tape_tensors(tape))
+    assert len(on_tape) > 50
+    for t in on_tape:
+        assert t.untyped_storage().data_ptr() not in arena
+
+
+def test_a_tape_owns_its_storage():
+    c, base = get_case('s2_C_multiply_none')
+    check_tape_owns_its_storage(build_model(c, base, ops=TorchOps()), 'cpu')
+
+
+HEAD_CASES = [('A', 'multiply', 'none'), ('B', 'minus_abs', 'dual_add'), ('C', 'multiply', 'none'),
+              ('C', 'minus_abs', 'dual_add')]  # those of test_head_backward_matches_autograd
+
+
+def check_recorded_forward_is_the_eval_forward(m, counts, device):
+    """fusion_forward_train / affinity_forward_train against Engine.fuse / Engine.affinity on the same inputs, both on
+    the fp32 weights: F, link, new and end bit for bit"""
+    from mmmot_amd.backward import fusion_forward_train
+    from mmmot_amd.plan import BatchPlan
+    eng = m.engine()
+    plan = BatchPlan([(counts, None)], 32, device, use_points=False)
+    assert plan.pair_uniform32 == (counts[1] % 32 == 0)
+    cat = (torch.randn(plan.Lt, 1024, generator=torch.Generator().manual_seed(6)) * 0.8).to(device)
+    with eng.fp32_mlp():
+        F, _ = fusion_forward_train(eng, plan, cat)
+        link, new, end, _ = affinity_forward_train(eng, plan, F)
+        F_eval = eng.buf('F', 3, plan.Lt, 512)
+        eng.fuse(plan, cat, F_eval)
+        link_eval, new_eval, end_eval = eng.affinity(plan, F_eval)
+    assert torch.equal(F, F_eval), 'F'
+    assert torch.equal(link, link_eval) and torch.equal(new, new_eval) and torch.equal(end, end_eval)
+
+
+@pytest.mark.parametrize('counts', [[32, 32], [5, 3]])
+@pytest.mark.parametrize('fusion,op,sm', HEAD_CASES)
+def test_recorded_forward_is_the_eval_forward(fusion, op, sm, counts):
+    c, base = get_case('s2_C_multiply_none')
+    m = build_model(dict(c, fusion=fusion, aff=op, sm=sm), base, ops=TorchOps())
+    check_recorded_forward_is_the_eval_forward(m, counts, 'cpu')
+
+
+def test_weight_grad_share_rule():
+    """weight_grad splits the row reduction into one share per 8 tiles, at most 16; shares=1 is one launch with nsplit 1"""
+    import types
+    from mmmot_amd.plan import RowTiles
+    from mmmot_amd.tape import weight_grad
+
+    class Stub:
+        def __init__(self):
+            self.calls = []
+
+        def gemm_tn(self, dY, tiles, N, K, dW, db, nsplit=1, **kw):
+            self.calls.append(nsplit)
+            dW.zero_(), db.zero_()
+
+        def segment_mean(self, X, C, segs, out, **kw):
+            out.zero_()
+
+    eng = types.SimpleNamespace(ops=Stub())
+    for T, want in ((7, 1), (8, 1), (200, 16)):
+        tiles = RowTiles([T * 128], 'cpu')
+        assert tiles.T == T
+        dY, X = torch.zeros(tiles.R, 64), torch.zeros(tiles.R, 64)
+        dW, db = weight_grad(eng, dY, tiles, 64, 64, X=X)
+        assert eng.ops.calls == [want] and dW.shape == (64, 64) and db.shape == (64,)
+        dW, db = weight_grad(eng, dY, tiles, 64, 64, shares=1, X=X)
+        assert eng.ops.calls == [want, 1] and dW.shape == (64, 64) and db.shape == (64,)
+        eng.ops.calls.clear()

@@ -11,7 +11,8 @@ from common import build_model, get_case
 from fake_ops import TorchOps
 from mmmot_amd.backward import affinity_autograd, affinity_backward, affinity_forward_train
 from mmmot_amd.plan import BatchPlan, RowTiles
-from test_backward_cpu import reference_grads
+from test_backward_cpu import (HEAD_CASES, check_recorded_forward_is_the_eval_forward, check_tape_owns_its_storage,
+                               reference_grads)
 from test_kernels_gpu import close, hip, rnd  # noqa: F401  (hip is a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -303,3 +304,17 @@ def test_sgd_on_the_head_reduces_a_loss():
         m.refresh_head()  # re-pack the 3 M head parameters only
     print('head SGD losses', ['%.4f' % v for v in losses])
     assert losses[-1] < 0.9 * losses[0] and all(b < a * 1.02 for a, b in zip(losses, losses[1:]))
+
+
+# ---- the head's training forward is the engine's forward, recorded (Engine.recording) ---------------------------------
+def test_a_tape_owns_its_storage():
+    c, base = get_case('s2_C_multiply_none')
+    check_tape_owns_its_storage(build_model(c, base, device=DEV), DEV)
+
+
+@pytest.mark.parametrize('counts', [[32, 32], [5, 3]])
+@pytest.mark.parametrize('fusion,op,sm', HEAD_CASES)
+def test_recorded_forward_is_the_eval_forward(fusion, op, sm, counts):
+    c, base = get_case('s2_C_multiply_none')
+    m = build_model(dict(c, fusion=fusion, aff=op, sm=sm), base, device=DEV)
+    check_recorded_forward_is_the_eval_forward(m, counts, DEV)

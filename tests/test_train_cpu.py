@@ -265,7 +265,7 @@ def test_transposed_weight_cache_survives_address_reuse():
     """dgrad_gemm caches W^T per (address, version, shape).  A freed weight's address is handed to the next tensor of the
     same size (version 0 again): the cache must not serve the old transpose for it.  An entry therefore pins
     its weight - the address cannot come back while the entry lives."""
-    from mmmot_amd.backward import dgrad_gemm
+    from mmmot_amd.tape import dgrad_gemm
     from mmmot_amd.plan import RowTiles
     c, base = get_case('s2_C_multiply_none')
     eng = build_model(c, base, ops=TorchOps()).engine()
