@@ -683,6 +683,31 @@ int mmmot_set_assign_variant(int variant);
 int mmmot_track_ids(const float* blocks, const int* pairs, const int* out_off, const int* frame_idx, int B, int max_nm,
                     int* state, int* ids_out, void* stream);
 
+/* CLEAR-MOT evaluation of tracked sequences (reference kitti_devkit/evaluate_tracking.py:393-792
+ * compute3rdPartyMetrics; csrc/clear_mot.hip), additive in ABI 10.  Four launches: one workgroup per frame (Hungarian
+ * association of ground truth and tracker boxes on c = 1 - IoU gated at min_overlap, the ignore logic and the per-frame
+ * counters), one lane per ground-truth trajectory (ID switches, fragments, MT / PT / ML), one workgroup per sequence and
+ * one lane for the totals.  All frames of all S sequences of the call go in one launch.
+ *   boxes: fp64 [nG + nT + nD][4] (x1, y1, x2, y2): the ground-truth objects, then the tracker objects, then the
+ *   DontCare areas, each frame's contiguous;
+ *   frames: int32 [NF][6] = first object and count of the frame in the three sections (g_off, G, t_off, T, d_off, D),
+ *   0 <= G, T <= 128, 0 <= D <= 64; a frame outside these limits or the sections gets -1 counters and NaN sums;
+ *   g_attr: int32 [nG][3] = truncation, occlusion, class code (1 = the neighbouring class: van / person_sitting);
+ *   t_attr: int32 [nT][2] = track ID, class code;
+ *   traj_off: int32 [NTr + 1], traj_obj: int32 [nG]: trajectory k's objects in frame order are
+ *   traj_obj[traj_off[k] .. traj_off[k + 1]) (indices into the ground-truth section);
+ *   seq_off: int32 [S + 1][2] = first frame and first trajectory of each sequence (row S: NF, NTr).
+ * Outputs, every element written: frame_d fp64 [NF][2] = sum of 1 - c over the matches, MODP_t; frame_i int32 [NF][6] =
+ * tp (ignored ones included), itp, fn, ifn, fp, ignored trackers; gt_out int32 [nG][2] = matched tracker ID or -1,
+ * ignored flag; traj_i int32 [NTr][4] = ignored, ID switches, fragments, 0 MT / 1 PT / 2 ML / -1 ignored;
+ * seq_d fp64 [S + 1][2] = sum of 1 - c, sum of MODP_t; seq_i int32 [S + 1][12] = tp, itp, fn, ifn, fp, ignored trackers,
+ * ID switches, fragments, MT, PT, ML, ignored trajectories; row S holds the totals.  The sums of a sequence do not depend
+ * on what else the call holds.  Returns MMMOT_EINVAL on a missing or misaligned pointer, a negative count or S < 1. */
+int mmmot_clear_mot(const double* boxes, int nG, int nT, int nD, const int* frames, int NF, const int* g_attr,
+                    const int* t_attr, const int* traj_off, const int* traj_obj, int NTr, const int* seq_off, int S,
+                    double min_overlap, double min_height, double max_truncation, double max_occlusion,
+                    double* frame_d, int* frame_i, int* gt_out, int* traj_i, double* seq_d, int* seq_i, void* stream);
+
 /* MFMA fragment-layout self test: C[32][32] = A[32][K] * B[32][K]^T through
  * the same fragment mapping the GEMM kernels use (K % 8 == 0). */
 int mmmot_selftest_mfma(const float* A, const float* B, float* C, int K, void* stream);

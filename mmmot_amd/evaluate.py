@@ -1,0 +1,394 @@
+"""CLEAR-MOT evaluation of tracked sequences on the device: the reference's ``kitti_devkit.evaluate_tracking.evaluate``
+(the call behind every validation epoch of main.py and eval_seq.py:124), which turns a KITTI result file into MOTA,
+MOTP, ID switches, fragments and MT / PT / ML.
+
+    from mmmot_amd.evaluate import evaluate            # instead of kitti_devkit.evaluate_tracking
+    MOTA, MOTP, recall, prec, F1, fp, fn, id_switches = evaluate(step, result_path, part, gt_path='./data/tracking')
+
+or, without files, straight from what the pipeline holds:
+
+    tr = labels_from_tracks(feed_dets, pipe.tracks)
+    m = evaluate_sequences(load_kitti(label_file, 'car', n_frames, True), tr)     # m.MOTA, m.id_switches, ...
+
+The Hungarian association of every frame, the ignore logic, the per-frame counters and the trajectory scan run in
+csrc/clear_mot.hip (one workgroup per frame, one lane per ground-truth trajectory); a call is one upload, four
+launches and one read-back.  The host parses the label files into packed tables (``Labels``), sorts the ground-truth
+objects into trajectories, and forms the dozen ratios of evaluate_tracking.py:745-791 from the totals.
+
+Kept from the reference: class selection by substring (car + van, pedestrian + person_sitting, always DontCare);
+non-DontCare rows with track ID -1 are dropped; tracker frames past the ground truth's are loaded (they count for the
+tracker's trajectories) but not evaluated; FAR and MODP divide by the seqmap's frame counts.  Different: a tracker
+file that repeats a (frame, ID) raises ``ValueError`` (there: ``return False``), and so does a frame with more than 128
+boxes on a side or 64 DontCare areas.  Equal-cost matchings are broken by column index, not munkres's way.
+"""
+import math
+import os
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from .torch_ops import CLEAR_MOT_MAX_BOXES, CLEAR_MOT_MAX_DONTCARE, CLEAR_MOT_SEQ_INTS, clear_mot_layout
+
+TRAIN_SEQ_ID = ['0003', '0001', '0013', '0009', '0004', '0020', '0006', '0015', '0008', '0012']
+VALID_SEQ_ID = ['0005', '0007', '0017', '0011', '0002', '0014', '0000', '0010', '0016', '0019', '0018']
+TRAINVAL_SEQ_ID = ['%04d' % i for i in range(21)]
+# columns of Labels.rows
+SEQ, FRAME, TID, CLS, TRUNC, OCC, X1, Y1, X2, Y2 = range(10)
+MAIN, NEIGHBOUR, DONTCARE = 0, 1, 2  # class codes
+
+
+def class_names(cls):
+    """(loaded class substrings, the neighbouring class) of evaluate_tracking.py:257-263 / :521"""
+    c = cls.lower()
+    if 'car' in c:
+        return ['car', 'van', 'dontcare'], 'van' if c == 'car' else None
+    if 'pedestrian' in c:
+        return ['pedestrian', 'person_sitting', 'dontcare'], 'person_sitting' if c == 'pedestrian' else None
+    return [c, 'dontcare'], None
+
+
+def class_code(name, cls):
+    """class code of a lower-case object type, or None when the evaluation of ``cls`` does not load it"""
+    loaded, neighbour = class_names(cls)
+    if not any(s in name for s in loaded):
+        return None
+    return DONTCARE if name == 'dontcare' else (NEIGHBOUR if name == neighbour else MAIN)
+
+
+@dataclass
+class Labels:
+    """Packed label tables of S sequences.  rows: float64 [n, 10] = sequence, frame, track ID, class code, truncation,
+    occlusion, x1, y1, x2, y2 in file order; n_frames: the seqmap's frame counts; length: frames held (n_frames, or more
+    where a row lies beyond); n_traj: distinct non-DontCare track IDs per sequence."""
+    rows: np.ndarray
+    n_frames: np.ndarray
+    length: np.ndarray
+    n_traj: np.ndarray
+    cls: str = 'car'
+    ground_truth: bool = False
+
+    @property
+    def n_sequences(self):
+        return len(self.n_frames)
+
+
+def concat(labels):
+    """several Labels (one per sequence, say) as one"""
+    labels = list(labels)
+    rows, o = [], 0
+    for lb in labels:
+        r = lb.rows.copy()
+        r[:, SEQ] += o
+        o += lb.n_sequences
+        rows.append(r)
+    cat = lambda k: np.concatenate([getattr(lb, k) for lb in labels])
+    return Labels(np.concatenate(rows).reshape(-1, 10), cat('n_frames'), cat('length'), cat('n_traj'), labels[0].cls,
+                  labels[0].ground_truth)
+
+
+def _finish(parsed, cls, n_frames, ground_truth, what):
+    """rows (frame, id, code, trunc, occ, box) of ONE sequence -> Labels: the bookkeeping of _loadData :293-328"""
+    length, seen, ids, rows = int(n_frames), set(), set(), []
+    for frame, tid, code, trunc, occ, box in parsed:
+        if tid == -1 and code != DONTCARE:
+            continue
+        if frame < 0:
+            raise ValueError('%s: negative frame index %d' % (what, frame))
+        if frame >= length:
+            if frame - length >= 500:  # the reference's list grows by max(500, frame - length) and then misses the frame
+                raise ValueError('%s: frame %d lies 500 or more frames past the sequence (%d)' % (what, frame, length))
+            length += 500
+        if not ground_truth:
+            if (frame, tid) in seen:
+                raise ValueError('%s: track ids are not unique: id %d occurs twice in frame %d' % (what, tid, frame))
+            seen.add((frame, tid))
+        if code != DONTCARE:
+            ids.add(tid)
+        rows.append([0, frame, tid, code, trunc, occ] + list(box))
+    return Labels(np.asarray(rows, np.float64).reshape(-1, 10), np.asarray([n_frames], np.int64),
+                  np.asarray([length], np.int64), np.asarray([len(ids)], np.int64), cls, bool(ground_truth))
+
+
+def load_kitti(path, cls, n_frames, ground_truth):
+    """One KITTI tracking label / result file as Labels (evaluate_tracking.py:227-361 _loadData for one sequence)."""
+    parsed = []
+    with open(path, 'r') as f:
+        for line in f:
+            fields = line.strip().split(' ')
+            if len(fields) < 3:
+                continue
+            code = class_code(fields[2].lower(), cls)
+            if code is None:
+                continue
+            if len(fields) < 17 or (not ground_truth and len(fields) > 18):
+                raise ValueError('%s: file is not in KITTI format' % path)
+            parsed.append((int(float(fields[0])), int(float(fields[1])), code, int(float(fields[3])),
+                           int(float(fields[4])), [float(v) for v in fields[6:10]]))
+    return _finish(parsed, cls, n_frames, ground_truth, path)
+
+
+def labels_from_tracks(frames, ids, frame_idx=None, cls='car', n_frames=None, ground_truth=False):
+    """The Labels that ``load_kitti`` reads from the file ``tracks.write_kitti_tracks(path, frames, ids, frame_idx)``
+    writes, without the file: kept detections only, values through the same '{:.4f}' of the fp32 value.  ``n_frames``:
+    the sequence's frame count (default: one past the last frame)."""
+    from .tracks import KITTI_NAMES
+    f4 = lambda v: float('{:.4f}'.format(float(np.float32(v))))
+    parsed, last = [], -1
+    for t, (d, fid) in enumerate(zip(frames, ids)):
+        frame = t if frame_idx is None else int(frame_idx[t])
+        last = max(last, frame)
+        fid = np.asarray(fid)
+        for j in np.flatnonzero(fid >= 0):
+            name = d['name'][j] if 'name' in d else 0
+            name = name if isinstance(name, str) else KITTI_NAMES[int(name)]
+            code = class_code(name.lower(), cls)
+            if code is None:
+                continue
+            trunc = int(f4(d['truncated'][j])) if 'truncated' in d else -1
+            occ = int(d['occluded'][j]) if 'occluded' in d else -1
+            parsed.append((frame, int(fid[j]), code, trunc, occ, [f4(v) for v in np.asarray(d['bbox'][j]).reshape(-1)]))
+    return _finish(parsed, cls, last + 1 if n_frames is None else n_frames, ground_truth, 'labels_from_tracks')
+
+
+@dataclass
+class ClearMot:
+    """What compute3rdPartyMetrics leaves on the reference's evaluation object, under the same names."""
+    cls: str = 'car'
+    MOTA: float = 0.0
+    MOTP: float = 0.0
+    MOTAL: float = 0.0
+    MODA: float = 0.0
+    MODP: object = 0.0
+    recall: float = 0.0
+    precision: float = 0.0
+    F1: float = 0.0
+    FAR: object = 0.0
+    MT: float = 0.0
+    PT: float = 0.0
+    ML: float = 0.0
+    tp: int = 0
+    fp: int = 0
+    fn: int = 0
+    id_switches: int = 0
+    fragments: int = 0
+    n_gt: int = 0
+    n_gt_trajectories: int = 0
+    n_tr: int = 0
+    n_tr_trajectories: int = 0
+    itp: int = 0
+    ifn: int = 0
+    n_igt: int = 0
+    n_itr: int = 0
+    total_cost: float = 0.0
+    n_mt: int = 0
+    n_pt: int = 0
+    n_ml: int = 0
+    n_ignored_trajectories: int = 0
+    tps: list = field(default_factory=list)
+    itps: list = field(default_factory=list)
+    fps: list = field(default_factory=list)
+    fns: list = field(default_factory=list)
+    ifns: list = field(default_factory=list)
+    n_gts: list = field(default_factory=list)
+    n_trs: list = field(default_factory=list)
+    n_igts: list = field(default_factory=list)
+    n_itrs: list = field(default_factory=list)
+    seq_costs: list = field(default_factory=list)      # per sequence: sum of 1 - c over the matches
+    seq_modp: list = field(default_factory=list)       # per sequence: sum of MODP_t
+    seq_id_switches: list = field(default_factory=list)
+    seq_fragments: list = field(default_factory=list)
+    MODP_t: np.ndarray = None            # [frames]
+    gt_tracker: np.ndarray = None        # per ground-truth object, sorted by (sequence, track ID, frame): matched ID or -1
+    gt_ignored: np.ndarray = None        # the same order: ignored flag
+    traj_key: np.ndarray = None          # [trajectories, 3]: sequence, track ID, objects
+
+    def stats(self):
+        """the 21 values of the devkit's stats_<cls>.txt line (:885-889)"""
+        return (self.MOTA, self.MOTP, self.MOTAL, self.MODA, self.MODP, self.recall, self.precision, self.F1, self.FAR,
+                self.MT, self.PT, self.ML, self.tp, self.fp, self.fn, self.id_switches, self.fragments, self.n_gt,
+                self.n_gt_trajectories, self.n_tr, self.n_tr_trajectories)
+
+    def stats_line(self):
+        return '%.6f ' * 21 % self.stats()
+
+    def summary(self):
+        """the tuple the reference's ``evaluate`` returns"""
+        return self.MOTA, self.MOTP, self.recall, self.precision, self.F1, self.fp, self.fn, self.id_switches
+
+
+def pack(gt, tracker):
+    """Labels of the ground truth and the tracker -> the tables of mmmot_clear_mot: a dict of numpy arrays plus the host
+    side's bookkeeping.  Raises ValueError on frames beyond the kernel's limits, before anything reaches the device."""
+    gt = concat(gt) if isinstance(gt, (list, tuple)) else gt
+    tracker = concat(tracker) if isinstance(tracker, (list, tuple)) else tracker
+    S = gt.n_sequences
+    if tracker.n_sequences != S:
+        raise ValueError('evaluate: %d ground-truth sequences, %d tracker sequences' % (S, tracker.n_sequences))
+    if np.any(tracker.length < gt.length):
+        raise ValueError('evaluate: the ground truth holds frames the tracker table does not reach')
+    F = gt.length.astype(np.int64)
+    foff = np.concatenate([[0], np.cumsum(F)])
+    NF = int(foff[-1])
+
+    def by_frame(rows):
+        """rows in frame order (stable: file order within a frame), their global frame index, per-frame offset / count"""
+        fr = foff[rows[:, SEQ].astype(np.int64)] + rows[:, FRAME].astype(np.int64)
+        order = np.argsort(fr, kind='stable')
+        rows, fr = rows[order], fr[order]
+        cnt = np.bincount(fr, minlength=NF).astype(np.int64)
+        return rows, fr, np.cumsum(cnt) - cnt, cnt
+
+    g_rows, g_fr, g_off, g_cnt = by_frame(gt.rows[gt.rows[:, CLS] != DONTCARE])
+    d_rows, _, d_off, d_cnt = by_frame(gt.rows[gt.rows[:, CLS] == DONTCARE])
+    tr = tracker.rows
+    t_rows, _, t_off, t_cnt = by_frame(tr[tr[:, FRAME] < F[tr[:, SEQ].astype(np.int64)]])
+    if NF and (max(g_cnt.max(), t_cnt.max()) > CLEAR_MOT_MAX_BOXES or d_cnt.max() > CLEAR_MOT_MAX_DONTCARE):
+        raise ValueError('evaluate: a frame holds more than %d boxes on a side or more than %d DontCare areas'
+                         % (CLEAR_MOT_MAX_BOXES, CLEAR_MOT_MAX_DONTCARE))
+    nG, nT, nD = len(g_rows), len(t_rows), len(d_rows)
+    # trajectories: the ground-truth objects sorted by (sequence, track ID, frame)
+    traj_obj = np.lexsort((g_rows[:, TID], g_rows[:, SEQ]))  # stable: frame order within a key
+    key = g_rows[traj_obj][:, [SEQ, TID]].astype(np.int64)
+    first = np.flatnonzero(np.r_[True, np.any(key[1:] != key[:-1], axis=1)]) if nG else np.zeros(0, np.int64)
+    NTr = len(first)
+    traj_off = np.r_[first, nG].astype(np.int64)
+    traj_seq = key[first, 0] if NTr else np.zeros(0, np.int64)
+    toff = np.searchsorted(traj_seq, np.arange(S + 1))
+    frames = np.stack([g_off, g_cnt, t_off, t_cnt, d_off, d_cnt], axis=1) if NF else np.zeros((0, 6), np.int64)
+    return {
+        'sizes': [nG, nT, nD, NF, NTr, S],
+        'boxes': np.concatenate([g_rows[:, X1:], t_rows[:, X1:], d_rows[:, X1:]]).astype(np.float64),
+        'frames': frames, 'g_attr': g_rows[:, [TRUNC, OCC, CLS]], 't_attr': t_rows[:, [TID, CLS]],
+        'traj_off': traj_off, 'traj_obj': traj_obj, 'seq_off': np.stack([foff, toff], axis=1),
+        'g_cnt': g_cnt, 't_cnt': t_cnt, 'foff': foff,
+        'traj_key': np.stack([traj_seq, key[first, 1] if NTr else traj_seq, np.diff(traj_off)], axis=1),
+        'n_frames': gt.n_frames, 'n_gt_trajectories': int(gt.n_traj.sum()),
+        'n_tr_trajectories': int(tracker.n_traj.sum()), 'cls': gt.cls,
+    }
+
+
+def finish(p, out):
+    """the packed tables and the device's output sections (numpy) -> ClearMot: per-sequence lists, totals and the
+    ratios of evaluate_tracking.py:745-791"""
+    nG, nT, nD, NF, NTr, S = p['sizes']
+    seq_i = out['seq_i'].reshape(S + 1, CLEAR_MOT_SEQ_INTS).astype(np.int64)
+    seq_d = out['seq_d'].reshape(S + 1, 2)
+    frame_i = out['frame_i'].reshape(NF, 6)
+    if NF and frame_i.min() < 0 or NTr and out['traj_i'].min() < -1:
+        raise RuntimeError('mmmot_clear_mot: a frame or a trajectory outside the launch limits reached the kernel')
+    foff = p['foff']
+    per_seq = lambda cnt: [int(cnt[foff[s]:foff[s + 1]].sum()) for s in range(S)]
+    m = ClearMot(cls=p['cls'])
+    tp_all, m.itps, m.fns, m.ifns, m.fps, m.n_itrs = (seq_i[:S, q].tolist() for q in range(6))
+    m.tps = [a - b for a, b in zip(tp_all, m.itps)]  # the per-sequence list leaves the ignored ones out, the total does not
+    m.n_igts = [a + b for a, b in zip(m.ifns, m.itps)]
+    m.n_gts, m.n_trs = per_seq(p['g_cnt']), per_seq(p['t_cnt'])
+    m.seq_costs, m.seq_modp = seq_d[:S, 0].tolist(), seq_d[:S, 1].tolist()
+    m.seq_id_switches, m.seq_fragments = seq_i[:S, 6].tolist(), seq_i[:S, 7].tolist()
+    tot = [int(v) for v in seq_i[S]]
+    m.tp, m.itp, m.fn, m.ifn, m.fp, m.n_itr, m.id_switches, m.fragments = tot[:8]
+    m.n_mt, m.n_pt, m.n_ml, m.n_ignored_trajectories = tot[8:12]
+    m.n_igt = m.ifn + m.itp
+    m.n_gt = nG - m.n_igt
+    m.n_tr = nT
+    m.total_cost = float(seq_d[S, 0])
+    m.n_gt_trajectories, m.n_tr_trajectories = p['n_gt_trajectories'], p['n_tr_trajectories']
+    m.MODP_t = out['frame_d'].reshape(NF, 2)[:, 1].copy()
+    gt_out = out['gt_out'].reshape(nG, 2)[p['traj_obj']]
+    m.gt_tracker, m.gt_ignored = gt_out[:, 0].astype(np.int64), gt_out[:, 1].astype(bool)
+    m.traj_key = p['traj_key']
+
+    n_tracked = m.n_gt_trajectories - m.n_ignored_trajectories
+    if n_tracked == 0:
+        m.MT = m.PT = m.ML = 0.
+    else:
+        m.MT, m.PT, m.ML = m.n_mt / float(n_tracked), m.n_pt / float(n_tracked), m.n_ml / float(n_tracked)
+    if (m.fp + m.tp) == 0 or (m.tp + m.fn) == 0:
+        m.recall = m.precision = 0.
+    else:
+        m.recall = m.tp / float(m.tp + m.fn)
+        m.precision = m.tp / float(m.fp + m.tp)
+    m.F1 = 0. if (m.recall + m.precision) == 0 else 2. * (m.precision * m.recall) / (m.precision + m.recall)
+    n_frames = int(np.sum(p['n_frames']))
+    m.FAR = 'n/a' if n_frames == 0 else m.fp / float(n_frames)
+    if m.n_gt == 0:
+        m.MOTA = m.MODA = m.MOTAL = -float('inf')
+    else:
+        m.MOTA = 1 - (m.fn + m.fp + m.id_switches) / float(m.n_gt)
+        m.MODA = 1 - (m.fn + m.fp) / float(m.n_gt)
+        m.MOTAL = m.MOTA if m.id_switches == 0 else 1 - (m.fn + m.fp + math.log10(m.id_switches)) / float(m.n_gt)
+    m.MOTP = float('inf') if m.tp == 0 else m.total_cost / float(m.tp)
+    m.MODP = 'n/a' if n_frames == 0 else float(seq_d[S, 1]) / float(n_frames)
+    return m
+
+
+def evaluate_sequences(gt, tracker, cls='car', min_overlap=0.5, max_truncation=0, min_height=25, max_occlusion=2,
+                       device='cuda'):
+    """CLEAR-MOT statistics of tracker Labels against ground-truth Labels (one Labels of S sequences, or a list with
+    one per sequence) on the device: one upload, the launches of mmmot_clear_mot, one read-back."""
+    import torch
+    p = pack(gt, tracker)
+    p['cls'] = cls
+    inp, outl, n_in, n_out = clear_mot_layout(p['sizes'])
+    host = torch.empty(n_in, dtype=torch.int32, pin_memory=True)
+    h = host.numpy()
+    for name, (o, n) in inp.items():
+        if name == 'boxes':
+            h[o:o + n].view(np.float64)[:] = p['boxes'].reshape(-1)
+        else:
+            h[o:o + n] = np.asarray(p[name]).reshape(-1)
+    dev = host.to(device, non_blocking=True)
+    res = torch.ops.mmmot.clear_mot(dev, p['sizes'], [float(min_overlap), float(min_height), float(max_truncation),
+                                                      float(max_occlusion)])
+    r = res.cpu().numpy()
+    out = {name: (r[o:o + n].view(np.float64) if name.endswith('_d') else r[o:o + n]) for name, (o, n) in outl.items()}
+    return finish(p, out)
+
+
+def sequences_of(part, gt_path):
+    """(names, frame counts) of the sequences of ``part`` in the seqmap under ``gt_path`` (:106-123)"""
+    ids = {'val': VALID_SEQ_ID, 'train': TRAIN_SEQ_ID, 'all': TRAINVAL_SEQ_ID}.get(part, [])
+    names, n_frames = [], []
+    with open(os.path.join(gt_path, 'evaluate_tracking.seqmap'), 'r') as fh:
+        for line in fh:
+            fields = line.split(' ')
+            if len(fields) < 4:
+                continue
+            seq_id = '%04d' % int(fields[0])
+            if seq_id in ids:
+                names.append(seq_id)
+                n_frames.append(int(fields[3]) - int(fields[2]) + 1)
+    return names, n_frames
+
+
+def evaluate(result_sha, root, part='all', gt_path='./data/tracking', cls=None, device='cuda'):
+    """Drop-in for the reference's ``kitti_devkit.evaluate_tracking.evaluate(result_sha, root, part)``: evaluates
+    ``root/result_sha/part/<sequence>.txt`` against ``gt_path/label_02`` for car, then pedestrian (``cls``: one class
+    only), writes ``eval/<cls>/stats_<cls>.txt`` beside the results in the devkit's format and returns
+    (MOTA, MOTP, recall, precision, F1, fp, fn, id_switches) of the last class evaluated, or False when the tracker
+    holds neither class.  The pretty summary and the mail object are not built."""
+    names, n_frames = sequences_of(part, gt_path)
+    if not names:
+        raise ValueError('evaluate: the seqmap under %s holds no sequence of part %r' % (gt_path, part))
+    t_path = os.path.join(root, str(result_sha), part)
+    last = None
+    for c in (('car', 'pedestrian') if cls is None else (cls,)):
+        try:
+            tracker = concat([load_kitti(os.path.join(t_path, '%s.txt' % s), c, n, False)
+                              for s, n in zip(names, n_frames)])
+        except IOError:
+            continue
+        if tracker.n_traj.sum() == 0:  # no trajectory of the class: the class is skipped
+            continue
+        try:
+            gt = concat([load_kitti(os.path.join(gt_path, 'label_02', '%s.txt' % s), c, n, True)
+                         for s, n in zip(names, n_frames)])
+        except IOError:
+            raise ValueError('Ground truth not found.')
+        m = evaluate_sequences(gt, tracker, cls=c, device=device)
+        eval_dir = os.path.join(t_path, 'eval', c)
+        os.makedirs(eval_dir, exist_ok=True)
+        with open(os.path.join(eval_dir, 'stats_%s.txt' % c), 'w') as f:
+            f.write(m.stats_line() + '\n')
+        last = m
+    return False if last is None else last.summary()

@@ -370,6 +370,18 @@ class HipOps:
                                       _iptr(state), _iptr(ids_out), self._stream())
         _lib.check(st, 'mmmot_track_ids')
 
+    def clear_mot(self, boxes, nG, nT, nD, frames, NF, g_attr, t_attr, traj_off, traj_obj, NTr, seq_off, S, params,
+                  frame_d, frame_i, gt_out, traj_i, seq_d, seq_i):
+        """CLEAR-MOT evaluation of S sequences in four launches; see mmmot_clear_mot.  boxes / frame_d / seq_d: fp64
+        device tensors, the rest int32; params: (min_overlap, min_height, max_truncation, max_occlusion)."""
+        d = torch.float64
+        st = self.lib.mmmot_clear_mot(_ptr(boxes, d), int(nG), int(nT), int(nD), _iptr(frames), int(NF), _iptr(g_attr),
+                                      _iptr(t_attr), _iptr(traj_off), _iptr(traj_obj), int(NTr), _iptr(seq_off), int(S),
+                                      float(params[0]), float(params[1]), float(params[2]), float(params[3]),
+                                      _ptr(frame_d, d), _iptr(frame_i), _iptr(gt_out), _iptr(traj_i), _ptr(seq_d, d),
+                                      _iptr(seq_i), self._stream())
+        _lib.check(st, 'mmmot_clear_mot')
+
     # ---- training backward of the pairwise block (include/mmmot_hip.h, csrc/backward.hip) -------------------
     def gn_bwd_partial(self, dA, Y, C, sc1, sh1, gamma, beta, relu, tiles, P):
         st = self.lib.mmmot_gn_bwd_partial(_ptr(dA), _ld(dA), _ptr(Y), _ld(Y), C, _ptr(sc1), _ptr(sh1), _ld(sc1),

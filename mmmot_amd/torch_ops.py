@@ -276,3 +276,68 @@ def _track_ids_meta(blocks, pairs, frame_idx, state, max_nm):
 _LIB.define('track_ids(Tensor blocks, Tensor pairs, Tensor frame_idx, Tensor(a!) state, int max_nm) -> Tensor')
 _LIB.impl('track_ids', _track_ids, 'CUDA')
 _LIB.impl('track_ids', _track_ids_meta, 'Meta')
+
+
+# ---- CLEAR-MOT evaluation (mmmot_amd/evaluate.py; csrc/clear_mot.hip) ----------------------------------------------
+#   mmmot::clear_mot(Tensor packed, int[] sizes, float[] params) -> Tensor
+#       Evaluates S sequences (mmmot_clear_mot: frame, trajectory, sequence and total launches).  packed: ONE device
+#       int32 block holding the call's tables in the order of clear_mot_layout()[0] (the fp64 boxes first, as their bit
+#       patterns), so that a call is one upload; sizes = [nG, nT, nD, NF, NTr, S]; params = [min_overlap, min_height,
+#       max_truncation, max_occlusion].  Returns ONE int32 block in the order of clear_mot_layout()[1] (the fp64 sums
+#       first), so that a call is one read-back.  The frame limits (128 boxes a side, 64 DontCare areas) are the
+#       caller's to check on the host (evaluate.pack); the kernel marks a frame outside them instead of reading it.
+CLEAR_MOT_SEQ_INTS = 12
+CLEAR_MOT_MAX_BOXES, CLEAR_MOT_MAX_DONTCARE = 128, 64
+
+
+def clear_mot_layout(sizes):
+    """({input section: (offset, int32 count)}, {output section: (offset, int32 count)}, input ints, output ints) of a
+    call with sizes = [nG, nT, nD, NF, NTr, S]; fp64 sections come first in both blocks (8-byte aligned)."""
+    if len(sizes) != 6 or min(sizes) < 0 or sizes[5] < 1:
+        raise ValueError('mmmot::clear_mot: sizes must be [nG, nT, nD, NF, NTr, S] with S >= 1, got %s' % (list(sizes),))
+    nG, nT, nD, NF, NTr, S = (int(v) for v in sizes)
+
+    def lay(parts):
+        out, o = {}, 0
+        for name, n in parts:
+            out[name] = (o, n)
+            o += n
+        if o >= 2 ** 31:
+            raise ValueError('mmmot::clear_mot: block exceeds 32-bit offsets')
+        return out, o
+
+    inp, n_in = lay([('boxes', 8 * (nG + nT + nD)), ('frames', 6 * NF), ('g_attr', 3 * nG), ('t_attr', 2 * nT),
+                     ('traj_off', NTr + 1), ('traj_obj', nG), ('seq_off', 2 * (S + 1))])
+    out, n_out = lay([('frame_d', 4 * NF), ('seq_d', 4 * (S + 1)), ('frame_i', 6 * NF), ('gt_out', 2 * nG),
+                      ('traj_i', 4 * NTr), ('seq_i', CLEAR_MOT_SEQ_INTS * (S + 1))])
+    return inp, out, n_in, n_out
+
+
+def _clear_mot(packed, sizes, params):
+    inp, outl, n_in, n_out = clear_mot_layout(sizes)
+    if packed.dtype != torch.int32 or packed.dim() != 1 or packed.numel() != n_in or not packed.is_contiguous():
+        raise ValueError('mmmot::clear_mot: packed must be a contiguous int32 [%d] block for sizes %s' % (n_in, list(sizes)))
+    if len(params) != 4:
+        raise ValueError('mmmot::clear_mot: params = [min_overlap, min_height, max_truncation, max_occlusion]')
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    nG, nT, nD, NF, NTr, S = (int(v) for v in sizes)
+    res = torch.empty(n_out, dtype=torch.int32, device=packed.device)
+    sec = lambda buf, lay, name: buf[lay[name][0]:lay[name][0] + lay[name][1]]
+    i = lambda name: sec(packed, inp, name)
+    o = lambda name: sec(res, outl, name)
+    _ASSOC_OPS[0].clear_mot(i('boxes').view(torch.float64), nG, nT, nD, i('frames'), NF, i('g_attr'), i('t_attr'),
+                            i('traj_off'), i('traj_obj'), NTr, i('seq_off'), S, params,
+                            o('frame_d').view(torch.float64), o('frame_i'), o('gt_out'), o('traj_i'),
+                            o('seq_d').view(torch.float64), o('seq_i'))
+    return res
+
+
+def _clear_mot_meta(packed, sizes, params):
+    return packed.new_empty((clear_mot_layout(sizes)[3],), dtype=torch.int32)
+
+
+_LIB.define('clear_mot(Tensor packed, int[] sizes, float[] params) -> Tensor')
+_LIB.impl('clear_mot', _clear_mot, 'CUDA')
+_LIB.impl('clear_mot', _clear_mot_meta, 'Meta')
