@@ -403,7 +403,11 @@ class HipOps:
 
     def gemm_tn(self, dY, tiles, N, K, dW, db=None, X=None, sc=None, sh=None, FA=None, FB=None, pair=None,
                 amode=A_PLAIN, pairop=0, nsplit=1):
-        """dW [nsplit][N][K] / db [nsplit][N]: per-share partial sums when nsplit > 1 (see mmmot_gemm_tn)."""
+        """dW [nsplit][N][K] / db [nsplit][N]: per-share partial sums when nsplit > 1 (see mmmot_gemm_tn).  `tiles` of at
+        most 128 rows: mmmot_gemm_tn_f16 stages 128 rows of a tile and would drop the rest (the fp32 kernel would not, but
+        one contract for both arithmetics)."""
+        if tiles.T and int(tiles.h_nrows.max()) > 128:
+            raise ValueError('gemm_tn needs tiles of at most 128 rows, got %d' % int(tiles.h_nrows.max()))
         a = _lib.GemmTnArgs()
         a.nsplit = int(nsplit)
         a.dY, a.lddy = _ptr(dY), _ld(dY)

@@ -329,8 +329,8 @@ class TorchOps:
         dz, yh, _ = self._dz_yhat(dA, Y, C, sc1, sh1, gamma, beta, relu, tiles)
         for t in range(tiles.T):
             r0, n = int(tiles.h_row0[t]), int(tiles.h_nrows[t])
-            P[t, 0, :C] = dz[r0:r0 + n].sum(0).float()
-            P[t, 1, :C] = (dz[r0:r0 + n] * yh[r0:r0 + n]).sum(0).float()
+            P[t, 0, :C] = dz[r0:r0 + n].sum(0).to(P.dtype)
+            P[t, 1, :C] = (dz[r0:r0 + n] * yh[r0:r0 + n]).sum(0).to(P.dtype)
 
     def gn_bwd_finalize(self, S, tiles, C, NG, gamma, M):
         S3 = S.view(tiles.G, 2, C).double()
@@ -339,20 +339,17 @@ class TorchOps:
             cnt = float(tiles.h_g_count[g]) * CG
             for k in range(2):
                 m = (S3[g, k] * gamma[:C].double()).view(NG, CG).sum(1) / cnt
-                M[g, k, :C] = m.repeat_interleave(CG).float()
+                M[g, k, :C] = m.repeat_interleave(CG).to(M.dtype)
 
     def gn_bwd_apply(self, dA, Y, C, sc1, sh1, gamma, beta, relu, M, tiles, dY):
         dz, yh, grp = self._dz_yhat(dA, Y, C, sc1, sh1, gamma, beta, relu, tiles)
         m1, m2 = M[grp, 0, :C].double(), M[grp, 1, :C].double()
-        dY[:tiles.R, :C] = (sc1[grp, :C].double() * (gamma[:C].double() * dz - m1 - yh * m2)).float()
+        dY[:tiles.R, :C] = (sc1[grp, :C].double() * (gamma[:C].double() * dz - m1 - yh * m2)).to(dY.dtype)
 
     def _a_operand(self, tiles, K, X, sc, sh, FA, FB, pair, amode, pairop):
         grp = _rows_groups(tiles)
         R = tiles.R
         if amode == 2:  # pair
-            rows = []
-            for g in range(len(pair['row0'])):
-                N = None
             A = torch.zeros(R, K, dtype=torch.float64)
             row0, gM, aoff, boff = [t.cpu().numpy() for t in (pair['row0'], pair['M'], pair['aoff'], pair['boff'])]
             for t in range(tiles.T):
@@ -369,6 +366,8 @@ class TorchOps:
 
     def gemm_tn(self, dY, tiles, N, K, dW, db=None, X=None, sc=None, sh=None, FA=None, FB=None, pair=None, amode=0,
                 pairop=0, nsplit=1):
+        if tiles.T and int(tiles.h_nrows.max()) > 128:  # one contract for both arithmetics (mmmot_gemm_tn_f16 stages 128 rows)
+            raise ValueError('gemm_tn needs tiles of at most 128 rows, got %d' % int(tiles.h_nrows.max()))
         A = self._a_operand(tiles, K, X, sc, sh, FA, FB, pair, amode, pairop)
         d = dY[:tiles.R, :N].double()
         dWv = dW.view(nsplit, N, K)
@@ -380,9 +379,9 @@ class TorchOps:
                 r_hi = int(tiles.h_row0[t_hi - 1]) + int(tiles.h_nrows[t_hi - 1])
             else:
                 r_lo = r_hi = 0
-            dWv[s_] = (d[r_lo:r_hi].t() @ A[r_lo:r_hi]).float()
+            dWv[s_] = (d[r_lo:r_hi].t() @ A[r_lo:r_hi]).to(dW.dtype)
             if dbv is not None:
-                dbv[s_] = d[r_lo:r_hi].sum(0).float()
+                dbv[s_] = d[r_lo:r_hi].sum(0).to(db.dtype)
 
     def pair_bwd(self, dX, F, dF, C, row0, gN, gM, aoff, boff, blk_group, blk_idx, pairop, side):
         for g in range(row0.numel()):
@@ -397,9 +396,9 @@ class TorchOps:
             else:
                 wa, wb = torch.full((N, M, C), 0.5, dtype=torch.float64), torch.full((N, M, C), -0.5, dtype=torch.float64)
             if side == 0:
-                dF[ao:ao + N, :C] += (d * wa).sum(1).float()
+                dF[ao:ao + N, :C] += (d * wa).sum(1).to(dF.dtype)
             else:
-                dF[bo:bo + M, :C] += (d * wb).sum(0).float()
+                dF[bo:bo + M, :C] += (d * wb).sum(0).to(dF.dtype)
 
     def pair_expand_bwd(self, dV, dA, C, tiles, row0, gN, gM, vrow0):
         for g in range(row0.numel()):

@@ -335,3 +335,136 @@ def test_weight_grad_share_rule():
         dW, db = weight_grad(eng, dY, tiles, 64, 64, shares=1, X=X)
         assert eng.ops.calls == [want, 1] and dW.shape == (64, 64) and db.shape == (64,)
         eng.ops.calls.clear()
+
+
+# ---- the executable specification of the backward kernels (tests/fake_ops.py) against torch.autograd, float64 -----------
+# tests/test_backward_kernels_gpu.py compares the HIP kernels with these functions at their edge forms; here the edge
+# forms of the specification itself are pinned (float64 against float64: 1e-10 of the tensor's maximum).
+def _same64(got, ref, what):
+    scale = max(ref.abs().max().item(), 1e-30)
+    assert (got.double() - ref.double()).abs().max().item() <= 1e-10 * scale, what
+
+
+@pytest.mark.parametrize('relu', [True, False])
+@pytest.mark.parametrize('C,NG', [(8, 8), (8, 1), (12, 3)])
+def test_gn_backward_spec_matches_autograd_on_column_slices(C, NG, relu):
+    """gn_bwd_partial -> per-group sums -> gn_bwd_finalize -> gn_bwd_apply on the views Layer.columns() hands out
+    (Y[:, c0:], gamma[c0:], sc1[:, c0:]), with and without the ReLU mask, one channel per norm group and one norm group"""
+    from mmmot_amd.plan import RowTiles
+    emu, eps, c0 = TorchOps(torch.float64), 1e-5, 4
+    tiles = RowTiles([5, 130, 1], 'cpu')
+    R, G, CG = tiles.R, tiles.G, C // NG
+    g = torch.Generator().manual_seed(21)
+    r64 = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    Yw, dAw, gw, bw = r64(R, c0 + C), r64(R, c0 + C), r64(c0 + C) + 1.0, r64(c0 + C) * 0.3
+    sc1w, sh1w = torch.zeros(G, c0 + C, dtype=torch.float64), torch.zeros(G, c0 + C, dtype=torch.float64)
+    y = Yw[:, c0:].clone().requires_grad_(True)
+    gamma, beta = gw[c0:].clone().requires_grad_(True), bw[c0:].clone().requires_grad_(True)
+    loss = 0.0
+    for gi in range(G):
+        r0, n = int(tiles.h_g_row0[gi]), int(tiles.h_g_count[gi])
+        v = y[r0:r0 + n].view(n, NG, CG)
+        mean = v.mean(dim=(0, 2), keepdim=True)
+        rstd = 1.0 / torch.sqrt(((v - mean) ** 2).mean(dim=(0, 2), keepdim=True) + eps)
+        z = ((v - mean) * rstd).reshape(n, C) * gamma + beta
+        loss = loss + ((torch.relu(z) if relu else z) * dAw[r0:r0 + n, c0:]).sum()
+        sc1w[gi, c0:] = rstd.detach().reshape(NG, 1).expand(NG, CG).reshape(C)
+        sh1w[gi, c0:] = (-mean * rstd).detach().reshape(NG, 1).expand(NG, CG).reshape(C)
+    dy_ref, dgamma_ref, dbeta_ref = torch.autograd.grad(loss, (y, gamma, beta))
+    views = (dAw[:, c0:], Yw[:, c0:], C, sc1w[:, c0:], sh1w[:, c0:], gw[c0:], bw[c0:], relu)
+    P = torch.zeros(tiles.T, 2, C, dtype=torch.float64)
+    emu.gn_bwd_partial(*views, tiles, P)
+    _same64(P[:, 1].sum(0), dgamma_ref, 'dgamma')
+    _same64(P[:, 0].sum(0), dbeta_ref, 'dbeta')
+    S = torch.stack([P[int(tiles.h_g_tile0[k]):int(tiles.h_g_tile0[k]) + int(tiles.h_g_ntiles[k])].sum(0) for k in range(G)])
+    M = torch.zeros(G, 2, C, dtype=torch.float64)
+    emu.gn_bwd_finalize(S.reshape(G * 2, C), tiles, C, NG, gw[c0:], M)
+    dYw = torch.full((R, c0 + C), float('nan'), dtype=torch.float64)
+    emu.gn_bwd_apply(*views, M, tiles, dYw[:, c0:])
+    _same64(dYw[:, c0:], dy_ref, 'dY')
+    assert torch.isnan(dYw[:, :c0]).all()
+
+
+@pytest.mark.parametrize('pairop', [0, 1, 2])
+def test_pair_bwd_spec_matches_autograd_with_ties(pairop):
+    """pair_bwd (both sides, on top of a non-zero dF; the middle frame of a 3-frame sample gets both) against autograd of
+    the pairwise operand; with a == b exactly in a few columns, where |a - b| has the sub-gradient 0 (torch's choice too)"""
+    from mmmot_amd.backward import _aux
+    from mmmot_amd.plan import BatchPlan
+    emu, C = TorchOps(torch.float64), 8
+    plan = BatchPlan([([3, 2, 4], None), ([1, 1], None)], 32, 'cpu', rows=(0,), use_points=False)
+    aux, PT = _aux(plan), plan.pair_tiles
+    g = torch.Generator().manual_seed(22)
+    F = torch.randn(plan.Lt, C, generator=g, dtype=torch.float64)
+    F[3, 2:5] = F[0, 2:5]     # frame 0 row 0 == frame 1 row 0 (pair 0: a_0 == b_0)
+    F[6, 0:3] = F[4, 0:3]     # frame 1 row 1 == frame 2 row 1 (pair 1: a_1 == b_1)
+    F[10] = F[9]              # the 1 x 1 pair: every column ties
+    dX = torch.randn(PT.R, C, generator=g, dtype=torch.float64)
+    dF0 = torch.randn(plan.Lt, C, generator=g, dtype=torch.float64)
+    f = F.clone().requires_grad_(True)
+    loss = 0.0
+    for k in range(PT.G):
+        N, M, r0 = int(plan.h_pg_N[k]), int(plan.h_pg_M[k]), int(PT.h_g_row0[k])
+        a, b = f[int(plan.h_pg_aoff[k]):][:N].unsqueeze(1), f[int(plan.h_pg_boff[k]):][:M].unsqueeze(0)
+        x = a * b if pairop == 0 else ((a - b).abs() / 2 if pairop == 1 else (a - b) / 2)
+        loss = loss + (x * dX[r0:r0 + N * M].view(N, M, C)).sum()
+    (ref,) = torch.autograd.grad(loss, f)
+    dF = dF0.clone()
+    for side, (bg, bi) in enumerate([(aux.a_grp, aux.a_idx), (aux.b_grp, aux.b_idx)]):
+        emu.pair_bwd(dX, F, dF, C, PT.g_row0, plan.pg_N, plan.pg_M, plan.pg_aoff, plan.pg_boff, bg, bi, pairop, side)
+    _same64(dF, dF0 + ref, 'dF')
+    if pairop == 1:  # the ties contribute nothing: the 1 x 1 pair's rows keep their start value
+        assert torch.equal(dF[9:11], dF0[9:11])
+
+
+@pytest.mark.parametrize('nsplit', [1, 4, 7])
+def test_gemm_tn_spec_shares_match_autograd(nsplit):
+    """share s of gemm_tn holds the tiles [T*s/nsplit, T*(s+1)/nsplit): every share against autograd over its own rows,
+    empty shares (nsplit > T = 4) exact zeros, and the shares add up to the whole gradient"""
+    from mmmot_amd.plan import RowTiles
+    emu, N, K = TorchOps(torch.float64), 6, 5
+    tiles = RowTiles([5, 130, 1], 'cpu')
+    T = tiles.T
+    assert T == 4
+    g = torch.Generator().manual_seed(23)
+    r64 = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    X, dY, sc, sh = r64(tiles.R, K), r64(tiles.R, N), r64(tiles.G, K) + 1.0, r64(tiles.G, K) * 0.5
+    dW, db = torch.full((nsplit, N, K), float('nan'), dtype=torch.float64), torch.full((nsplit, N), float('nan'), dtype=torch.float64)
+    emu.gemm_tn(dY, tiles, N, K, dW, db, X=X, sc=sc, sh=sh, amode=1, nsplit=nsplit)
+    grp = torch.repeat_interleave(torch.arange(tiles.G), torch.as_tensor(tiles.h_g_count).long())
+    A = torch.relu(X * sc[grp] + sh[grp])
+    W = torch.zeros(N, K, dtype=torch.float64, requires_grad=True)
+    bias = torch.zeros(N, dtype=torch.float64, requires_grad=True)
+    n_empty = 0
+    for s in range(nsplit):
+        lo, hi = T * s // nsplit, T * (s + 1) // nsplit
+        if hi == lo:
+            n_empty += 1
+            assert (dW[s] == 0).all() and (db[s] == 0).all()
+            continue
+        r_lo, r_hi = int(tiles.h_row0[lo]), int(tiles.h_row0[hi - 1]) + int(tiles.h_nrows[hi - 1])
+        gw, gb = torch.autograd.grad(((A[r_lo:r_hi] @ W.t() + bias) * dY[r_lo:r_hi]).sum(), (W, bias))
+        _same64(dW[s], gw, 'share %d dW' % s)
+        _same64(db[s], gb, 'share %d db' % s)
+    assert n_empty == max(0, nsplit - T)
+    gw, gb = torch.autograd.grad(((A @ W.t() + bias) * dY).sum(), (W, bias))
+    _same64(dW.sum(0), gw, 'dW summed')
+    _same64(db.sum(0), gb, 'db summed')
+
+
+def test_gemm_tn_refuses_tiles_longer_than_128_rows():
+    """mmmot_gemm_tn_f16 stages 128 rows of a tile: a Gram-style tiling (RowTiles(..., tile=512 / 2048)) would lose the
+    rest without a word, so both backends refuse it before anything runs - in both arithmetics"""
+    from mmmot_amd.ops import HipOps
+    from mmmot_amd.plan import RowTiles
+    long_tiles, ok_tiles = RowTiles([300], 'cpu', tile=512), RowTiles([300], 'cpu')
+    assert long_tiles.T == 1 and int(long_tiles.h_nrows.max()) == 300 and int(ok_tiles.h_nrows.max()) == 128
+    dY, X, dW = torch.zeros(300, 64), torch.zeros(300, 64), torch.zeros(64, 64)
+    with pytest.raises(ValueError, match='128 rows'):
+        TorchOps().gemm_tn(dY, long_tiles, 64, 64, dW, X=X)
+    TorchOps().gemm_tn(dY, ok_tiles, 64, 64, dW, X=X)
+    hip = object.__new__(HipOps)  # no library needed: the refusal comes before the first pointer is taken
+    for f16 in (True, False):
+        hip.tn_f16 = f16
+        with pytest.raises(ValueError, match='128 rows'):
+            hip.gemm_tn(dY, long_tiles, 64, 64, dW, X=X)
