@@ -468,6 +468,32 @@ int mmmot_points_scatter_batched(const float* pts, int F, int NS, int NPOLY, int
                                  const int* cnt, const int* split, float* out, int Fo, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Ego-motion alignment of extracted points: align_points (reference utils/data_util.py:512-520, called per pair at
+ * dataset/test_seq_dataset.py:209 for the pair's second frame) with lidar_to_imu / imu_to_lidar
+ * (point_cloud/box_np_ops.py:599-611).  One thread per row, several segments (frames) per launch.
+ *   pts      [Q][F] fp32, F = 3 or 4, xyz first; rows of segment s = [seg_row0[s], seg_row0[s+1])
+ *   seg_row0 [NS+1] ints, seg_row0[0] = 0, non-decreasing (an empty segment is allowed), seg_row0[NS] = Q
+ *   xf       [NS][MMMOT_ALIGN_REC] fp64, one transform record per segment:
+ *              [0, 16)   A = inv(imu2velo.T), row-major 4x4
+ *              [16, 64)  up to MMMOT_ALIGN_MAX_CHAIN steps of 12: R row-major 3x3, then T; step 0 is applied first, so
+ *                        the caller stores the reference's lists R, T from LAST to FIRST (align_points' loop order);
+ *                        only the first `chain` steps are read
+ *              [64, 80)  B = imu2velo.T, row-major 4x4
+ *   out      row i goes to out + (out_row0 + i) * ldo, F floats (ldo >= F): a slice of a larger buffer is written in
+ *            place, rows outside [out_row0, out_row0 + Q) and columns >= F are not touched
+ * Arithmetic per row, fp64, every product and sum rounded on its own (no FMA contraction), sums in k order:
+ *   p = (x, y, z, 1);  q[j] = ((p0*A[0][j] + p1*A[1][j]) + p2*A[2][j]) + A[3][j], j < 3;
+ *   per step q[j] <- ((q0*R[j][0] + q1*R[j][1]) + q2*R[j][2]) + T[j];  then the row x B like the row x A;
+ *   ONE rounding to fp32 at the store.  With F = 4 the fourth column is copied bit for bit.  Every row is transformed,
+ *   the all-zero row of an empty box included (the reference aligns it too).
+ * Returns MMMOT_EINVAL for F outside {3, 4}, a negative Q / NS / out_row0, chain outside [0, 4], and with Q > 0 for a
+ * null pointer, NS < 1 or ldo < F.  Q = 0 is a no-op that returns 0. */
+#define MMMOT_ALIGN_MAX_CHAIN 4
+#define MMMOT_ALIGN_REC 80
+int mmmot_align_points(const float* pts, int F, int Q, int NS, const int* seg_row0, const double* xf, int chain,
+                       float* out, long out_row0, int ldo, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Per-detection image preparation: crop with zero padding -> antialiased bilinear
  * resize to S x S -> to_tensor -> normalize = the model input ``dets`` [N][3][S][S].  Replaces, per
  * detection, PIL img.crop(box).resize((S, S), Image.BILINEAR) + torchvision ToTensor/Normalize

@@ -11,9 +11,18 @@ Here, per frame t:   H2D (image, sweep)  ->  ``prep_points``  ->  ``crop_resize_
       per pair:      ``TrackingNet.forward`` on (A[t-1], A[t])  ->  ``scores_for_solver``    [stage B]
 ``overlap=True`` queues stage A of frame t+1 on a side stream BEFORE the host waits for the scores of pair (t-1, t), so
 the upload, the gather and the resize run beside / under the forward.  Both orders launch the same kernels on the same
-inputs: their outputs are bitwise equal (tests/test_pipeline_gpu.py).  The solver, ID bookkeeping and the ego-motion
-alignment of the reference's dataset code stay on the host and are not part of this module (the synthetic sequence has
-an identity ego motion; `FrameFeed(point_transform=...)` is the hook for the alignment of a frame's extracted points).  No CPU fallback: every stage is a C-ABI kernel sequence on the device.
+inputs: their outputs are bitwise equal (tests/test_pipeline_gpu.py).  No CPU fallback: every stage is a C-ABI kernel
+sequence on the device.
+
+Ego motion (``FrameFeed(..., pose=(pos, rad))``): the reference moves the points of a pair's SECOND
+frame into the first frame's coordinates (``align_points``, dataset/test_seq_dataset.py:199-210) and leaves the first
+frame's as they are, so a frame enters two pairs with two different point sets.  A prepared frame therefore keeps both:
+``points``, the gather's rows, used when the frame is the first of a pair, and ``points_aligned``, the same rows aligned
+to the previous frame (mmmot_amd.points.align_points_batched, one launch), used when it is the second.  The alignment of
+frame t needs the pose of frame t-1 only - host data - so it is queued in stage A of frame t, once per frame, on the side
+stream with ``overlap=True``; the sequence's first frame gets no aligned copy.  Either every frame of a sequence carries
+a pose or none does.  ``FrameFeed(point_transform=...)`` is the older hook: one function applied to a frame's extracted
+points in BOTH of its roles, which cannot express the reference's alignment; it stays for other uses.
 
 Every frame of a sequence is the second frame of one pair and the first of the next, so the per-pair order runs each
 frame's crops through the VGG trunk twice.  In eval mode a crop's appearance row does not depend on the crops beside it
@@ -47,7 +56,8 @@ import numpy as np
 import torch
 
 from .crops import crop_resize_u8
-from .points import prep_points_batched
+from . import ego
+from .points import align_points_batched, prep_points_batched
 from .association import select
 from .tracker_glue import queue_scores, queue_solve
 from .tracks import TrackState, merge_tracks
@@ -56,13 +66,41 @@ from .tracks import TrackState, merge_tracks
 class FrameFeed:
     """Host side of one frame: pinned staging copies of the image and the sweep (what a loader thread would hand over)."""
 
-    def __init__(self, img, sweep, info, dets, point_transform=None):
+    def __init__(self, img, sweep, info, dets, point_transform=None, pose=None):
+        if pose is not None:
+            if point_transform is not None:
+                raise ValueError('FrameFeed: give pose= (the ego-motion alignment of the second frame of a pair) or '
+                                 'point_transform= (one function for both roles of the frame), not both')
+            if 'calib/Tr_imu_to_velo' not in info:
+                raise ValueError("FrameFeed: pose= needs info['calib/Tr_imu_to_velo']")
+            pos, rad = (np.array(v, dtype=np.float64).reshape(-1) for v in pose)
+            if pos.shape != (3,) or rad.shape != (3,):
+                raise ValueError('FrameFeed: pose = (pos [3], rad [3]), got %s and %s' % (pos.shape, rad.shape))
+            pose = (pos, rad)
         self.img = torch.from_numpy(np.ascontiguousarray(img)).pin_memory()
         self.sweep = torch.from_numpy(np.ascontiguousarray(sweep, dtype=np.float32)).pin_memory()
         self.info, self.dets = info, dets
         # optional: applied to the EXTRACTED points (device tensor [Q, 3|4]) of this frame - where the reference aligns the
         # second frame of a pair to the first one's coordinates (align_points, dataset/test_seq_dataset.py:199-210)
         self.point_transform = point_transform
+        # optional: (pos, rad) of the frame as the reference's get_pos returns them.  With poses the pipeline aligns the
+        # frame's points to the previous frame for its role as the SECOND frame of a pair (module docstring)
+        self.pose = pose
+
+
+def _check_poses(feeds):
+    """every frame of a sequence carries a pose, or none does; True when they do"""
+    n = sum(1 for f in feeds if f.pose is not None)
+    if 0 < n < len(feeds):
+        raise ValueError('SequencePipeline: %d of %d frames carry a pose; the ego-motion alignment needs the pose of '
+                         'every frame (or of none)' % (n, len(feeds)))
+    return n > 0
+
+
+def _pair_record(prev_feed, feed):
+    """the transform record that aligns ``feed``'s points to ``prev_feed`` (one (R, T) step, ego.transform_record)"""
+    R, T = ego.pair_motion(prev_feed.pose, feed.pose)
+    return ego.transform_record([R], [T], feed.info['calib/Tr_imu_to_velo'])
 
 
 class SequencePipeline:
@@ -85,7 +123,7 @@ class SequencePipeline:
         self.stats = {'encoded_frames': 0, 'pairs': 0, 'recomputed_pairs': 0}
 
     # ---- stage A: one frame onto the device and through the two preparation kernels ---------------------------
-    def _prepare(self, feed):
+    def _prepare(self, feed, prev_feed=None):
         ev = self.stage_events
         marks = []
 
@@ -101,25 +139,42 @@ class SequencePipeline:
         # the image-frustum filter and the per-box gather in ONE launch sequence, one split read-back
         pc = prep_points_batched([sweep], [feed.info], [feed.dets], without_reflectivity=self.wo_refl)[0]
         pts = pc['points'] if feed.point_transform is None else feed.point_transform(pc['points']).contiguous()
+        # with poses: the copy for the frame's role as the second frame of pair (prev_feed, feed)
+        aligned = None
+        if prev_feed is not None and feed.pose is not None:
+            aligned = align_points_batched(pts, [0, int(pts.shape[0])], _pair_record(prev_feed, feed)[np.newaxis], 1)
         mark()
         crops = crop_resize_u8(img, feed.dets['bbox'], self.size)
         mark()
         if ev is not None:
             ev.append(('prep', marks))
-        return {'crops': crops, 'points': pts, 'split': np.asarray(pc['points_split'], dtype=np.int64),
-                'n': int(crops.shape[0]), 'ready': None}
+        return {'crops': crops, 'points': pts, 'points_aligned': aligned,
+                'split': np.asarray(pc['points_split'], dtype=np.int64), 'n': int(crops.shape[0]), 'ready': None}
 
-    def prepare(self, feed):
+    def prepare(self, feed, prev_feed=None):
+        """stage A of ``feed``; ``prev_feed``: the frame before it in the sequence (None for the first one) - with poses
+        the frame's points are aligned to it as well"""
         if not self.overlap:
-            return self._prepare(feed)
+            return self._prepare(feed, prev_feed)
         cur = torch.cuda.current_stream(self.dev)
         with torch.cuda.stream(self.side):
-            a = self._prepare(feed)
+            a = self._prepare(feed, prev_feed)
             a['ready'] = torch.cuda.Event()
             a['ready'].record(self.side)
-        for t in (a['crops'], a['points']):
-            t.record_stream(cur)   # allocated on the side stream, consumed on the main one
+        for t in (a['crops'], a['points'], a['points_aligned']):
+            if t is not None:
+                t.record_stream(cur)   # allocated on the side stream, consumed on the main one
         return a
+
+    def _align_group(self, frames, feeds, t0, t1):
+        """run_offline with poses: ``points_aligned`` of frames [t0, t1) (t0 >= 1) in ONE launch, each aligned to the
+        frame before it"""
+        self._wait(*frames[t0:t1])
+        rows = np.concatenate([[0], np.cumsum([int(frames[t]['points'].shape[0]) for t in range(t0, t1)])])
+        rec = np.stack([_pair_record(feeds[t - 1], feeds[t]) for t in range(t0, t1)])
+        out = align_points_batched(torch.cat([frames[t]['points'] for t in range(t0, t1)]), rows, rec, 1)
+        for i, t in enumerate(range(t0, t1)):
+            frames[t]['points_aligned'] = out[int(rows[i]):int(rows[i + 1])]
 
     # ---- stage B: the pair forward + the packed hand-off -------------------------------------------------------
     def _wait(self, *frames):
@@ -134,8 +189,14 @@ class SequencePipeline:
         return np.concatenate([a['split'], a['split'][-1] + b['split'][1:]])
 
     @staticmethod
+    def _second(b):
+        """the points of frame b as the SECOND frame of a pair: aligned to the pair's first frame when the sequence has
+        poses"""
+        return b['points'] if b['points_aligned'] is None else b['points_aligned']
+
+    @staticmethod
     def _pair_info(a, b):
-        points = torch.cat([a['points'], b['points']]).unsqueeze(0)
+        points = torch.cat([a['points'], SequencePipeline._second(b)]).unsqueeze(0)
         split = SequencePipeline._pair_split(a, b)
         # the split is on the host already (prep_points read it back): hand it over as a CPU tensor - no D2H in forward
         return {'points': points, 'points_split': torch.from_numpy(split.astype(np.float32)).unsqueeze(0)}
@@ -194,7 +255,7 @@ class SequencePipeline:
         launch = self.launch_pair_cached if reuse else self.launch_pair
         res = []
         prev = self.prepare(feeds[0])
-        nxt = self.prepare(feeds[1]) if len(feeds) > 1 else None
+        nxt = self.prepare(feeds[1], feeds[0]) if len(feeds) > 1 else None
         if reuse and nxt is not None:
             self.encode([prev])  # frame 0, once
         for t in range(1, len(feeds)):
@@ -202,7 +263,7 @@ class SequencePipeline:
             snap = self.track_state.snapshot() if reuse and self.track else None  # a recomputed pair starts from it again
             pending = self.queue_hand_off([launch(prev, cur)], [(t, prev, cur)])
             # stage A of the next frame is queued before the host blocks on this pair's scores
-            nxt = self.prepare(feeds[t + 1]) if t + 1 < len(feeds) else None
+            nxt = self.prepare(feeds[t + 1], feeds[t]) if t + 1 < len(feeds) else None
             r = self.finish_hand_off(pending)[0]
             if reuse:
                 r = self._checked_scores(prev, cur, r, t, snap)
@@ -215,6 +276,7 @@ class SequencePipeline:
         ``ortools_solve`` is called with; ``on_scores(t, scores)`` is where the host solver would run.  associate=True:
         the list of (scores, assignment), assignment as ``ortools_solve`` returns it; ``on_assign(t, assignment)``.
         track=True: ``self.tracks`` is filled as well, ``on_tracks(t, ids)`` per emitted frame."""
+        _check_poses(feeds)
         self._start_tracks(feeds)
         return self._run_pairs(feeds, self.reuse_appearance, on_scores, on_assign, on_tracks)
 
@@ -293,10 +355,14 @@ class SequencePipeline:
         K, B = int(frames_per_encode), int(pairs_per_forward)
         if K < 1 or B < 1:
             raise ValueError('frames_per_encode and pairs_per_forward must be >= 1')
+        moving = _check_poses(feeds)
         self._start_tracks(feeds)
         frames = [self.prepare(f) for f in feeds]
         if len(frames) < 2:
             return []
+        if moving:  # one align launch per K frames, queued in front of their trunk launches
+            for t0 in range(1, len(frames), K):
+                self._align_group(frames, feeds, t0, min(t0 + K, len(frames)))
         self._encode_all(frames, K)
         res = []
         for g0 in range(1, len(frames), B):
@@ -304,7 +370,8 @@ class SequencePipeline:
             both = [f for _, a, b in pairs for f in (a, b)]
             plan = self.model.make_plan([([a['n'], b['n']], self._pair_split(a, b)) for _, a, b in pairs], self.size)
             with torch.no_grad():
-                outs = self.model.forward_batch(plan, None, torch.cat([f['points'] for f in both]),
+                outs = self.model.forward_batch(plan, None,
+                                                torch.cat([p for _, a, b in pairs for p in (a['points'], self._second(b))]),
                                                 appearance=torch.cat([f['rows'].rows for f in both]))
             done = self.finish_hand_off(self.queue_hand_off(outs, pairs))
             for (t, _, _), r in zip(pairs, done):

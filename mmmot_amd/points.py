@@ -270,3 +270,81 @@ def prep_points_batched(sweeps, infos, dets_list, use_frustum=False, without_ref
         res.append({'points': out[lo:hi], 'points_split': (split[p0:p0 + c + 1] - lo).tolist()})
         p0 += c
     return res
+
+
+# ---- ego-motion alignment of extracted points (csrc/align_points.hip) ------------------------------------------------
+def align_points_batched(points, seg_rows, records, chain, out=None, out_row0=0):
+    """Several frames' rows aligned in ONE launch of ``mmmot_align_points``.
+
+    points: device fp32 [Q, F] (F = 3 or 4), the segments' rows one after the other; seg_rows: NS + 1 row offsets
+    (0 first, Q last; an empty segment is allowed); records: float64 [NS, ego.RECORD], one ``ego.transform_record`` per
+    segment; chain: the number of (R, T) steps every record holds (1..4).  The rows are written to ``out`` rows
+    [out_row0, out_row0 + Q): a device fp32 tensor with at least that many rows, F or more columns and unit inner
+    stride (a slice of a joined buffer is written in place; its other rows and columns are not touched).  Without
+    ``out`` a new [Q, F] tensor.  Returns the [Q, F] view of the written rows.  Nothing waits on the host: the tables
+    travel in one pinned buffer and one asynchronous copy on the current stream.  No CPU fallback."""
+    from . import ego
+    if not points.is_cuda:
+        raise RuntimeError('align_points needs a device tensor; there is no CPU fallback')
+    if points.dim() != 2 or points.shape[1] not in (3, 4):
+        raise ValueError('align_points: points must be [Q, 3] or [Q, 4], got %s' % (tuple(points.shape),))
+    lib = _lib.load()
+    points = points.contiguous()
+    Q, F = int(points.shape[0]), int(points.shape[1])
+    seg = np.ascontiguousarray(seg_rows, dtype=np.int64)
+    rec = np.ascontiguousarray(records, dtype=np.float64)
+    NS = len(seg) - 1
+    if NS < 1 or rec.shape != (NS, ego.RECORD):
+        raise ValueError('align_points: %d row offsets need %d records of %d doubles, got %s'
+                         % (len(seg), max(NS, 0), ego.RECORD, rec.shape))
+    if seg[0] != 0 or seg[-1] != Q or (np.diff(seg) < 0).any():
+        raise ValueError('align_points: the row offsets must run from 0 to %d without decreasing' % Q)
+    if not 1 <= int(chain) <= ego.MAX_CHAIN:
+        raise ValueError('align_points: a chain of 1..%d steps, got %d' % (ego.MAX_CHAIN, chain))
+    out_row0 = int(out_row0)
+    if out is None:
+        if out_row0 != 0:
+            raise ValueError('align_points: out_row0 needs out')
+        out = torch.empty(Q, F, dtype=torch.float32, device=points.device)
+    else:
+        if out.device != points.device or out.dtype != torch.float32 or out.dim() != 2:
+            raise ValueError('align_points: out must be a 2-D fp32 tensor on the device of the points')
+        if out_row0 < 0 or out.shape[0] < out_row0 + Q or out.shape[1] < F or (out.shape[1] > 1 and out.stride(1) != 1):
+            raise ValueError('align_points: out %s (strides %s) does not hold rows [%d, %d) of %d columns'
+                             % (tuple(out.shape), out.stride(), out_row0, out_row0 + Q, F))
+        if out.untyped_storage().data_ptr() == points.untyped_storage().data_ptr():
+            raise ValueError('align_points: out must not share the storage of the points (a separate buffer)')
+    if Q == 0:
+        return out[out_row0:out_row0, :F]
+    ldo = int(out.stride(0)) if out.shape[0] > 1 else max(F, int(out.shape[1]))
+    if ldo < F:
+        raise ValueError('align_points: the rows of out overlap (row stride %d < %d columns)' % (ldo, F))
+    # ONE upload: the fp64 records, then the int32 row offsets, in a pinned buffer of this call's own (the host allocator
+    # keeps it until the copy queued here has run)
+    nrec = rec.nbytes
+    stage = torch.empty(nrec + 4 * (NS + 1), dtype=torch.uint8, pin_memory=True)
+    hb = stage.numpy()
+    hb[:nrec] = rec.view(np.uint8).reshape(-1)
+    hb[nrec:] = seg.astype(np.int32).view(np.uint8)
+    dbuf = stage.to(points.device, non_blocking=True)
+    stream = torch.cuda.current_stream(points.device).cuda_stream
+    _lib.check(lib.mmmot_align_points(_ptr(points), F, Q, NS, _iptr(dbuf[nrec:].view(torch.int32)),
+                                      dbuf[:nrec].view(torch.float64).data_ptr(), int(chain), _ptr(out), out_row0, ldo,
+                                      stream), 'mmmot_align_points')
+    return out[out_row0:out_row0 + Q, :F]
+
+
+def align_points(R, T, imu2velo, points, out=None):
+    """``align_points`` (reference utils/data_util.py:512-520) on a device tensor: the rows of a pair's second frame
+    [Q, 3|4] moved into the first frame's coordinates.  R, T: the reference's lists of (3x3, 3) steps, equal length <= 4,
+    applied from last to first; an empty list returns ``points`` itself, like the reference.  imu2velo: the frame's
+    ``info['calib/Tr_imu_to_velo']`` (4x4).  The arithmetic is float64 on the device, rounded to fp32 once at the store
+    (the reference rounds at the same place, where it writes the result back into its fp32 array); a fourth column is
+    copied.  ``out``: an fp32 device view [Q, F] with unit inner stride to write into (a slice of a larger buffer)."""
+    from . import ego
+    if len(R) != len(T):
+        raise ValueError('align_points: R and T must have the same length (%d, %d)' % (len(R), len(T)))
+    if len(R) == 0:
+        return points
+    rec = ego.transform_record(R, T, imu2velo)
+    return align_points_batched(points, [0, int(points.shape[0])], rec[np.newaxis], len(R), out=out)

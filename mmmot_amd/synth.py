@@ -113,7 +113,43 @@ def make_frame(seed, n_pts=120000, n_det=11, hw=KITTI_HW):
     return img, pts.astype(np.float32), info, dets
 
 
-def make_sequence(n_frames, seed=0, n_pts=120000, det_range=(10, 12), hw=KITTI_HW):
-    """``n_frames`` frames with det_range[0]..det_range[1] detections each (BASELINE cfg1's shape: N ~ 10-12)."""
+# KITTI raw calib_imu_to_velo.txt (public dataset constants), 4x4 like the reference's info['calib/Tr_imu_to_velo']
+KITTI_IMU2VELO = np.array([[9.999976e-01, 7.553071e-04, -2.035826e-03, -8.086759e-01],
+                           [-7.854027e-04, 9.998898e-01, -1.482298e-02, 3.195559e-01],
+                           [2.024406e-03, 1.482454e-02, 9.998881e-01, -7.997231e-01], [0.0, 0.0, 0.0, 1.0]])
+
+
+def ego_poses(n_frames, seed=0):
+    """A smooth synthetic drive in the form ``get_pos`` (reference utils/data_util.py:486-494) returns per frame:
+    ``pos`` = (x, y, altitude) with x, y at web-mercator magnitude (Karlsruhe: about 9.3e5, 6.3e6) and ``rad`` = (roll,
+    pitch, yaw).  0.8-1.4 m per frame along the heading (30-50 km/h at 10 Hz), a yaw rate that drifts slowly within
+    +-0.02 rad per frame, roll / pitch noise of a few mrad and a few cm of altitude noise.  Returns a list of
+    (pos, rad) float64 pairs."""
+    rng = np.random.default_rng([0x5eb, int(seed)])
+    pos = np.array([9.35e5 + rng.uniform(-2e3, 2e3), 6.275e6 + rng.uniform(-2e3, 2e3), 115.0 + rng.uniform(-2, 2)])
+    yaw, rate, speed = rng.uniform(-np.pi, np.pi), rng.uniform(-0.01, 0.01), rng.uniform(0.9, 1.3)
+    poses = []
+    for _ in range(n_frames):
+        rad = np.array([rng.normal(0, 0.004), rng.normal(0, 0.004), yaw])
+        poses.append((pos.copy(), rad))
+        rate = float(np.clip(rate + rng.normal(0, 0.002), -0.02, 0.02))
+        speed = float(np.clip(speed + rng.normal(0, 0.03), 0.8, 1.4))
+        yaw += rate
+        pos = pos + np.array([speed * np.cos(yaw), speed * np.sin(yaw), rng.normal(0, 0.02)])
+    return poses
+
+
+def make_sequence(n_frames, seed=0, n_pts=120000, det_range=(10, 12), hw=KITTI_HW, ego=None):
+    """``n_frames`` frames with det_range[0]..det_range[1] detections each (BASELINE cfg1's shape: N ~ 10-12).
+    ``ego=None``: a standing camera, the frames as ``make_frame`` returns them.  ``ego=seed``: a moving one - every
+    frame's info also carries ``'pos'`` / ``'rad'`` of ``ego_poses(n_frames, ego)`` and a KITTI-like
+    ``'calib/Tr_imu_to_velo'``, as the reference's ``get_frame_info`` does; the caller hands them to
+    ``FrameFeed(..., pose=(info['pos'], info['rad']))``."""
     rng = np.random.default_rng([0x5ea, int(seed)])
-    return [make_frame(1000 * seed + t, n_pts, int(rng.integers(det_range[0], det_range[1] + 1)), hw) for t in range(n_frames)]
+    frames = [make_frame(1000 * seed + t, n_pts, int(rng.integers(det_range[0], det_range[1] + 1)), hw) for t in range(n_frames)]
+    if ego is None:
+        return frames
+    out = []
+    for (img, pts, info, dets), (pos, rad) in zip(frames, ego_poses(n_frames, ego)):
+        out.append((img, pts, dict(info, **{'calib/Tr_imu_to_velo': KITTI_IMU2VELO, 'pos': pos, 'rad': rad}), dets))
+    return out

@@ -6,9 +6,11 @@ pairs B at a time on the rows).  Workload = bench.py's pipeline leg: 100 synthet
 stage A.  Each repeat runs every mode once, in turn; the wall clock of a run ends in a synchronise; one untimed run of
 every mode first.  The scores of the three modes must be bitwise equal.  Writes <out>/bench_sequence.json.
 --associate adds the device association to every pair (SequencePipeline(associate=True)), --track the track IDs as well
-(track=True; implies --associate): the tracks of the three modes must then be equal too.
+(track=True; implies --associate): the tracks of the three modes must then be equal too.  --ego gives every frame a pose
+of a synthetic drive (mmmot_amd.synth.ego_poses), so each frame's points are aligned to the previous frame on the device
+(DESIGN section 14); without it the camera stands still and nothing is aligned.
 
-    python tools/bench_sequence.py --out <dir> [--repeats 3] [--trunk f16x3] [-K 16] [-B 8] [--associate | --track]
+    python tools/bench_sequence.py --out <dir> [--repeats 3] [--trunk f16x3] [-K 16] [-B 8] [--associate | --track] [--ego]
 """
 import argparse
 import json
@@ -44,6 +46,7 @@ def main():
     ap.add_argument('-B', '--pairs-per-forward', type=int, default=8)
     ap.add_argument('--associate', action='store_true')
     ap.add_argument('--track', action='store_true')
+    ap.add_argument('--ego', action='store_true', help='a moving camera: align every frame to the one before it')
     args = ap.parse_args()
     assoc = args.associate or args.track
     kw = dict(associate=assoc, track=True) if args.track else dict(associate=assoc)
@@ -55,7 +58,7 @@ def main():
     model.eval().to(dev)
     model.set_trunk(args.trunk)
     n = args.frames
-    ndet, feeds = detections(n), sequence_feeds(n)
+    ndet, feeds = detections(n), sequence_feeds(n, ego=0 if args.ego else None)
     K, B = args.frames_per_encode, args.pairs_per_forward
     modes = {
         'per_pair': lambda p: p.run(feeds),
@@ -91,7 +94,7 @@ def main():
         'spread': {k: round((max(v) - min(v)) / med[k], 4) for k, v in fps.items()},
         'speedup_vs_per_pair': {k: round(med[k] / med['per_pair'], 3) for k in modes},
         'bitwise_equal': True,
-        'associate': assoc, 'track': bool(args.track),
+        'associate': assoc, 'track': bool(args.track), 'ego': bool(args.ego),
         'last_track_id': int(max(int(x.max()) for x in tracks['per_pair'] if len(x))) if args.track else None,
         'stats': stats,
         'trunk': model.engine().trunk,

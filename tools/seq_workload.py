@@ -17,10 +17,17 @@ def detections(frames):
     return np.random.default_rng(5).integers(10, 13, frames)
 
 
-def sequence_feeds(frames):
-    """``frames`` FrameFeeds (pinned host copies), generated on up to 16 threads"""
+def sequence_feeds(frames, ego=None):
+    """``frames`` FrameFeeds (pinned host copies), generated on up to 16 threads.  ``ego=seed``: the same frames seen from
+    a moving camera - every feed carries a pose of mmmot_amd.synth.ego_poses(frames, seed) and a KITTI-like
+    Tr_imu_to_velo, so the pipeline aligns each frame's points to the frame before it."""
     from mmmot_amd.pipeline import FrameFeed
     from mmmot_amd.synth import make_frame
     ndet = detections(frames)
     with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as pool:
-        return [FrameFeed(*f) for f in pool.map(lambda t: make_frame(7000 + t, 120000, int(ndet[t])), range(frames))]
+        made = list(pool.map(lambda t: make_frame(7000 + t, 120000, int(ndet[t])), range(frames)))
+    if ego is None:
+        return [FrameFeed(*f) for f in made]
+    from mmmot_amd.synth import KITTI_IMU2VELO, ego_poses
+    return [FrameFeed(img, sweep, dict(info, **{'calib/Tr_imu_to_velo': KITTI_IMU2VELO}), dets, pose=pose)
+            for (img, sweep, info, dets), pose in zip(made, ego_poses(frames, ego))]
