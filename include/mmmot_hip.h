@@ -685,6 +685,35 @@ int mmmot_associate_pairs(const float* det, const float* new_score, const float*
  * depend on it, bit for bit. */
 int mmmot_set_assign_variant(int variant);
 
+/* Association of chains of T >= 2 frames (reference solvers.py:9-138, ortools_solve with any len(det_split);
+ * csrc/assign_chain.hip), exact, additive in ABI 10.  The program - binaries det_i / new_i / end_i per detection and
+ * link_t[j][k] per adjacent frame pair, maximise the scored sum under end + sum_k link_t[j][k] = det (t < T - 1),
+ * new + sum_j link_{t-1}[j][k] = det (t > 0), new = det in frame 0 and end = det in frame T - 1 - is a min-cost flow on
+ * the layered network source -> in(v) (-new_v), in(v) -> out(v) (capacity 1, -det_v), out(t, j) -> in(t + 1, k)
+ * (-link_t[j][k]), out(v) -> sink (-end_v): a unit of flow is a trajectory.  One workgroup per chain augments along
+ * successive shortest paths (Dijkstra on fp64 reduced costs, ties to the smallest node index, in(v) = v, out(v) = L + v,
+ * sink = 2L) until the cheapest path gains nothing: results are deterministic and do not depend on the chain's place in
+ * the batch.
+ *   det / new_score / end_score: fp32, chain c's L = sum n_t scores at [score offset, + L), frame after frame;
+ *   link: fp32, chain c's row-major blocks link_0 (n_0 x n_1) .. link_{T-2}, one after the other from its link offset;
+ *   chains: int32 [B][MMMOT_CHAIN_ROW] = (T, score offset, link offset, n_0 .. n_7), 2 <= T <= 8, entries past n_{T-1}
+ *   ignored; 0 <= n_t <= max_n <= 512 (an empty frame carries no trajectory across it), 1 <= L <= max_L <= 1024 (LDS
+ *   sizing; a chain outside these limits is not solved and gets a NaN objective, nothing else of it is written);
+ *   out: fp32, chain c's block at out_off[c] = [det L | new L | end L | link_0 | .. | link_{T-2}], the 0 / 1 values of
+ *   ortools_solve's assign_det / assign_new / assign_end / assign_link, every element written;
+ *   objective: fp64 [B], the optimum of the program.
+ * A NaN score means "variable absent" (its edge does not exist); infinite scores are clamped to +-1e30.  Returns
+ * MMMOT_EINVAL on a null pointer, B < 1, max_n outside [1, 512], max_L outside [max_n, min(1024, 8 max_n)] before any
+ * launch. */
+#define MMMOT_CHAIN_MAXT 8
+#define MMMOT_CHAIN_ROW (3 + MMMOT_CHAIN_MAXT)
+int mmmot_associate_chains(const float* det, const float* new_score, const float* end_score, const float* link,
+                           const int* chains, int B, int max_n, int max_L, float* out, const int* out_off,
+                           double* objective, void* stream);
+/* tests / A-B: which kernel serves mmmot_associate_chains - 0 = automatic (2 max_L + 1 <= 256 nodes: one wave; above:
+ * four waves), 1 / 2 = one / four waves.  Results do not depend on it, bit for bit. */
+int mmmot_set_chain_variant(int variant);
+
 /* Track IDs from pair assignments (reference tracking_model.py:218-292 assign_det_id, then :109-216 align_id, restated
  * by detection index; csrc/track_ids.hip), additive in ABI 10.  One workgroup walks the B CONSECUTIVE pairs of ONE
  * sequence in order; queued behind mmmot_associate_pairs it reads that call's `out` / `pairs` / `out_off` as they are.

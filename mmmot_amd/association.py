@@ -11,13 +11,23 @@ dtype and device of ``det_score``.  Ties go to the smallest index; the answer is
     assign_det, assign_link, assign_new, assign_end = associate(det, [link], new, end, det_split)
 
 CPU scores go to the device in one copy and come back in one; device scores stay there (nothing waits on the host).
-``associate_batch`` solves B pairs (e.g. the rows of one ``forward_batch``) in one launch.  Chains of more than two
-frames (a min-cost flow) and the ``gt`` loss-augmented objective are not supported.
+``associate_batch`` solves B pairs (e.g. the rows of one ``forward_batch``) in one launch.  ``associate`` itself refuses
+chains of more than two frames and the ``gt`` loss-augmented objective.
+
+Those are ``associate_chain``'s: ``ortools_solve`` for any ``len(det_split) >= 2`` (``sample_max_len > 2``), the program
+as a min-cost flow on the layered network of the frames ("Chains"; csrc/assign_chain.hip, one workgroup per
+chain), with ``gt=`` the loss-augmented objective of training-time inference:
+
+    from mmmot_amd.association import associate_chain
+    assign_det, assign_links, assign_new, assign_end = associate_chain(det, links, new, end, det_split, gt=None)
+
+``associate_chain_batch`` solves B chains in one launch and ``select_chain`` picks the ``test_mode`` rows of every link
+block of a ``TrackingNet(seq_len > 2)`` forward.
 """
 import numpy as np
 import torch
 
-from . import torch_ops  # noqa: F401  (registers mmmot::associate)
+from . import torch_ops  # noqa: F401  (registers mmmot::associate and mmmot::associate_chains)
 
 
 def split_of(det_split):
@@ -109,4 +119,122 @@ def associate_batch(det_scores, link_scores, new_scores, end_scores, det_splits,
     res = []
     for (N, M), o, d, l in zip(splits, offs, det_scores, link_scores):
         res.append(unpack(out[o:o + 3 * (N + M) + N * M], N, M, d, l[0].size()))
+    return (res, obj) if return_objective else res
+
+
+# ---- chains of T >= 2 frames -------------------------------------------------------------------------------------------
+def chain_of(det_split):
+    """[n_0 .. n_{T-1}] of a ``det_split`` of T >= 2 frames (ints or 1-element tensors)."""
+    split = [int(n) for n in det_split]
+    if len(split) < 2:
+        raise ValueError('associate_chain: det_split must have at least 2 entries, got %d' % len(split))
+    return split
+
+
+def select_chain(det_score, link_scores, new_score, end_score, test_mode):
+    """The ``test_mode`` rows of a forward over T frames, every one of the T - 1 link blocks included (the reference's
+    ``predict`` slices ``link_score[0]`` only): (det L, [link 1 x n_t x n_{t+1} ...], new L, end L), device views."""
+    tm = int(test_mode)
+    return det_score[tm], [l[tm:tm + 1] for l in link_scores], new_score[tm], end_score[tm]
+
+
+def chains_table(splits):
+    """CPU int32 [B, 11] (T, score offset, link offset, n_0 .. n_7) of chains packed one after the other, and the
+    output offsets."""
+    rows, so, lo, oo, offs = [], 0, 0, 0, []
+    for split in splits:
+        if len(split) > torch_ops.CHAIN_MAX_T:
+            raise ValueError('associate_chain: at most %d frames, got %d' % (torch_ops.CHAIN_MAX_T, len(split)))
+        K = sum(a * b for a, b in zip(split[:-1], split[1:]))
+        rows.append([len(split), so, lo] + list(split) + [0] * (torch_ops.CHAIN_MAX_T - len(split)))
+        offs.append(oo)
+        so += sum(split)
+        lo += K
+        oo += 3 * sum(split) + K
+    return torch.tensor(rows, dtype=torch.int32), offs
+
+
+def chain_block_size(split):
+    return 3 * sum(split) + sum(a * b for a, b in zip(split[:-1], split[1:]))
+
+
+def unpack_chain(block, split, like=None, link_sizes=None):
+    """One chain's output block [det L | new L | end L | link_0 | .. | link_{T-2}] -> the ortools_solve tuple (views)."""
+    L = sum(split)
+    det, new, end = block[0:L], block[L:2 * L], block[2 * L:3 * L]
+    links, o = [], 3 * L
+    for a, b in zip(split[:-1], split[1:]):
+        links.append(block[o:o + a * b].view(1, a, b))
+        o += a * b
+    if like is not None:
+        det, new, end = (t.view(like.size()).to(like.dtype) for t in (det, new, end))
+        links = [l.view(sz).to(like.dtype) for l, sz in zip(links, link_sizes)]
+    return det, links, new, end
+
+
+def _check_chain(det_score, link_scores, new_score, end_score, split):
+    L = sum(split)
+    if len(link_scores) != len(split) - 1 or any(t.numel() != L for t in (det_score, new_score, end_score)) or \
+            any(l.numel() != a * b for l, a, b in zip(link_scores, split[:-1], split[1:])):
+        raise ValueError('associate_chain: scores do not match det_split %s' % (split,))
+
+
+def _flat_scores(det_score, link_scores, new_score, end_score, gt):
+    """[det | new | end | link_0 | ..] fp32 on the scores' device; with ``gt`` the loss-augmented scores of
+    solvers.py:50-81: the objective gains gt - y * gt_eff per variable, gt_eff = gt + (gt == 0) * -1, so every score
+    drops by gt_eff (the constant sum of gt does not move the arg-max) - one fused expression."""
+    flat = torch.cat([t.detach().reshape(-1).to(torch.float32) for t in (det_score, new_score, end_score, *link_scores)])
+    if gt is None:
+        return flat
+    g = torch.cat([t.detach().reshape(-1).to(torch.float32) for t in (gt[0], gt[1], gt[2], *gt[3])]).to(flat.device)
+    if g.numel() != flat.numel():
+        raise ValueError('associate_chain: gt does not match the scores')
+    return flat - (g + g.eq(0).float().mul(-1))
+
+
+def associate_chain(det_score, link_scores, new_score, end_score, det_split, gt=None):
+    """Drop-in for reference ``ortools_solve(det_score, link_score, new_score, end_score, det_split, gt)`` with any
+    ``len(det_split) >= 2``: det / new / end [L], link_scores = [link 1 x n_t x n_{t+1} ...]; ``gt`` = (gt_det, gt_new,
+    gt_end, [gt_link ...]) selects the loss-augmented objective.  Returns (assign_det, [assign_link ...], assign_new,
+    assign_end) with the dtype, device and shapes of the scores."""
+    split = chain_of(det_split)
+    _check_chain(det_score, link_scores, new_score, end_score, split)
+    L = sum(split)
+    if L == 0:
+        z = det_score.new_zeros(det_score.size())
+        return z, [det_score.new_zeros(l.size()) for l in link_scores], z.clone(), z.clone()
+    flat = _flat_scores(det_score, link_scores, new_score, end_score, gt)
+    on_host = not det_score.is_cuda
+    if on_host:
+        flat = flat.to('cuda')  # one host-to-device copy
+    chains, _ = chains_table([split])
+    out, _ = torch.ops.mmmot.associate_chains(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:], chains)
+    if on_host:
+        out = out.cpu()  # one device-to-host copy
+    return unpack_chain(out, split, det_score, [l.size() for l in link_scores])
+
+
+def associate_chain_batch(det_scores, link_scores, new_scores, end_scores, det_splits, gts=None,
+                          return_objective=False):
+    """B chains in one launch.  Per chain c: det_scores[c] / new_scores[c] / end_scores[c] [L_c], link_scores[c] = [link
+    1 x n_t x n_{t+1} ...] (the ``select_chain`` rows), all on one device; ``gts``: None or per chain a ``gt`` tuple (or
+    None).  Returns the list of ortools_solve tuples (on that device), and the fp64 optima [B] of the solved scores when
+    ``return_objective``."""
+    splits = [chain_of(s) for s in det_splits]
+    if not splits:
+        raise ValueError('associate_chain_batch: no chains')
+    if any(sum(s) == 0 for s in splits):
+        raise ValueError('associate_chain_batch: every chain needs a detection (use associate_chain for empty chains)')
+    gts = gts if gts is not None else [None] * len(splits)
+    flats = []
+    for d, l, n, e, s, g in zip(det_scores, link_scores, new_scores, end_scores, splits, gts):
+        _check_chain(d, l, n, e, s)
+        flats.append(_flat_scores(d, l, n, e, g))
+    Ls = [sum(s) for s in splits]
+    cat = lambda k: torch.cat([f[k * L:(k + 1) * L] for f, L in zip(flats, Ls)])
+    link = torch.cat([f[3 * L:] for f, L in zip(flats, Ls)])
+    chains, offs = chains_table(splits)
+    out, obj = torch.ops.mmmot.associate_chains(cat(0), cat(1), cat(2), link, chains)
+    res = [unpack_chain(out[o:o + chain_block_size(s)], s, d, [x.size() for x in l])
+           for s, o, d, l in zip(splits, offs, det_scores, link_scores)]
     return (res, obj) if return_objective else res

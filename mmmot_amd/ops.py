@@ -363,6 +363,14 @@ class HipOps:
                                             self._stream())
         _lib.check(st, 'mmmot_associate_pairs')
 
+    def associate_chains(self, det, new, end, link, chains, B, max_n, max_L, out, out_off, objective):
+        """B chains of 2 .. 8 frames solved exactly in one launch; see mmmot_associate_chains.  chains / out_off: int32
+        device tensors."""
+        st = self.lib.mmmot_associate_chains(_ptr(det), _ptr(new), _ptr(end), _ptr(link), _iptr(chains), int(B),
+                                             int(max_n), int(max_L), _ptr(out), _iptr(out_off),
+                                             _ptr(objective, torch.float64), self._stream())
+        _lib.check(st, 'mmmot_associate_chains')
+
     def track_ids(self, blocks, pairs, out_off, frame_idx, B, max_nm, state, ids_out):
         """Track IDs of B consecutive pairs of one sequence from their solver blocks; see mmmot_track_ids.  pairs /
         out_off / frame_idx / state / ids_out: int32 device tensors; state is updated in place."""

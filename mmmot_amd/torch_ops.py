@@ -218,6 +218,81 @@ _LIB.impl('associate', _associate, 'CUDA')
 _LIB.impl('associate', _associate_meta, 'Meta')
 
 
+# ---- chain association (mmmot_amd/association.py; csrc/assign_chain.hip) --------------------------------------------
+#   mmmot::associate_chains(Tensor det, Tensor new, Tensor end, Tensor link, Tensor chains) -> Tensor[]
+#       B chains of 2 .. 8 frames solved exactly in one launch (mmmot_associate_chains).  det / new / end / link: flat
+#       fp32 device tensors; chains: a CPU int32 [B, 11] table (T, score offset, link offset, n_0 .. n_7) - host data,
+#       like the pair table of mmmot::associate.  Returns [out, objective]: out fp32, chain c's [det L | new L | end L |
+#       link_0 | .. | link_{T-2}] one after the other; objective fp64 [B].
+CHAIN_MAX_T = 8
+CHAIN_ROW = 3 + CHAIN_MAX_T
+CHAIN_MAX_L = 1024
+
+
+def chain_layout(chains, n_scores=None, n_link=None):
+    """(total output floats, int64 [B] output offsets, max n_t, max L) of a chain table; checks the table, and against
+    the sizes of the score / link buffers when given (the kernel reads what the table says)."""
+    if chains.device.type != 'cpu' or chains.dtype != torch.int32 or chains.dim() != 2 or chains.shape[1] != CHAIN_ROW:
+        raise ValueError('mmmot::associate_chains: chains must be a CPU int32 [B, %d] table (T, score offset, link '
+                         'offset, n_0 .. n_7)' % CHAIN_ROW)
+    if chains.shape[0] < 1:
+        raise ValueError('mmmot::associate_chains: no chains')
+    t = chains.numpy().astype(np.int64)
+    T, so, lo = t[:, 0], t[:, 1], t[:, 2]
+    if T.min() < 2 or T.max() > CHAIN_MAX_T:
+        raise ValueError('mmmot::associate_chains: every chain needs 2 <= T <= %d frames' % CHAIN_MAX_T)
+    n = np.where(np.arange(CHAIN_MAX_T)[None, :] < T[:, None], t[:, 3:], 0)  # entries past n_{T-1} are ignored
+    if n.min() < 0 or n.max() > MAX_ASSOC:
+        raise ValueError('mmmot::associate_chains: every frame needs 0 <= n_t <= %d' % MAX_ASSOC)
+    L = n.sum(1)
+    if L.min() < 1 or L.max() > CHAIN_MAX_L:
+        raise ValueError('mmmot::associate_chains: every chain needs 1 <= L <= %d detections' % CHAIN_MAX_L)
+    if np.minimum(so, lo).min() < 0:
+        raise ValueError('mmmot::associate_chains: negative offset in the chain table')
+    K = (n[:, :-1] * n[:, 1:]).sum(1)
+    if n_scores is not None and (so + L).max() > n_scores:
+        raise ValueError('mmmot::associate_chains: a chain reads past the end of the score buffers')
+    if n_link is not None and (lo + K).max() > n_link:
+        raise ValueError('mmmot::associate_chains: a chain reads past the end of the link buffer')
+    sizes = 3 * L + K
+    off = np.cumsum(sizes) - sizes
+    total = int(sizes.sum())
+    if total >= 2 ** 31:
+        raise ValueError('mmmot::associate_chains: output block exceeds 32-bit offsets')
+    return total, torch.from_numpy(off), int(n.max()), int(L.max())
+
+
+def _associate_chains(det, new, end, link, chains):
+    n_scores = min(int(det.numel()), int(new.numel()), int(end.numel()))
+    total, off, max_n, max_L = chain_layout(chains, n_scores, int(link.numel()))
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    B = int(chains.shape[0])
+    if link.numel() == 0:  # no chain has a link (an empty frame between the others): never read, but not a null pointer
+        link = det
+    # chain table + output offsets in one pinned block: an asynchronous copy (a pageable one would wait for the stream)
+    host = torch.empty((CHAIN_ROW + 1) * B, dtype=torch.int32, pin_memory=True)
+    host[:CHAIN_ROW * B] = chains.reshape(-1)
+    host[CHAIN_ROW * B:] = off
+    table = host.to(det.device, non_blocking=True)
+    out = torch.empty(total, dtype=torch.float32, device=det.device)
+    obj = torch.empty(B, dtype=torch.float64, device=det.device)
+    _ASSOC_OPS[0].associate_chains(det, new, end, link, table[:CHAIN_ROW * B], B, max_n, max_L, out,
+                                   table[CHAIN_ROW * B:], obj)
+    return [out, obj]
+
+
+def _associate_chains_meta(det, new, end, link, chains):
+    total, _, _, _ = chain_layout(chains)
+    return [det.new_empty((total,), dtype=torch.float32), det.new_empty((int(chains.shape[0]),), dtype=torch.float64)]
+
+
+_LIB.define('associate_chains(Tensor det, Tensor new, Tensor end, Tensor link, Tensor chains) -> Tensor[]')
+_LIB.impl('associate_chains', _associate_chains, 'CUDA')
+_LIB.impl('associate_chains', _associate_chains_meta, 'Meta')
+
+
 #   mmmot::track_ids(Tensor blocks, Tensor pairs, Tensor frame_idx, Tensor(a!) state, int max_nm) -> Tensor
 #       Track IDs of B consecutive pairs of ONE sequence (mmmot_track_ids) from the solver's output blocks: blocks = the
 #       `out` of mmmot::associate for the same pairs table (a CPU int32 [B, 4]; N or M may be 0 here); frame_idx: CPU

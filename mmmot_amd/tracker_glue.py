@@ -5,7 +5,8 @@
 (solvers.py:32-45): O(N*M) device synchronisations once the scores live on the GPU.  ``scores_for_solver``
 does the same selection and moves the selected rows to the host in ONE packed copy, returning CPU tensors
 with exactly the shapes the solver indexes.  ``predict_assign`` also solves the association on the device
-(mmmot_amd.association, the ``ortools_solve`` drop-in) and brings scores and assignment back in one copy.
+(mmmot_amd.association, the ``ortools_solve`` drop-in) and brings scores and assignment back in one copy;
+``predict_assign_chain`` is the same for a model of ``seq_len > 2`` (every link block selected, the chain solver).
 
 A sequence queues before it waits: ``queue_solve`` (solve, and the track IDs with ``track=``) and ``queue_scores``
 (scores only) return a ``HandOff``, and ``HandOff.fetch()`` is the host copy, a list with one ``PairResult`` (scores,
@@ -15,7 +16,8 @@ from collections import namedtuple
 
 import torch
 
-from .association import associate, pairs_table, select, split_of, unpack
+from .association import (associate, chain_block_size, chain_of, chains_table, pairs_table, select, select_chain,
+                          split_of, unpack, unpack_chain)
 from .tracks import queue_ids, split_ids
 
 # one pair on the host: scores as ``scores_for_solver`` returns them, assignment as ``ortools_solve`` does, ids =
@@ -133,3 +135,27 @@ def predict_assign(model, det_imgs, det_info, det_split):
         det_score, link_score, new_score, end_score, _ = model(det_imgs, det_info, det_split)
     sel = select(det_score, link_score, new_score, end_score, model.test_mode)
     return queue_solve([sel], [split_of(det_split)]).fetch()[0][:2]
+
+
+def predict_assign_chain(model, det_imgs, det_info, det_split):
+    """``predict_assign`` for a model of any ``seq_len >= 2``: forward, the ``test_mode`` rows of all T - 1 link blocks
+    (``select_chain``) and the chain association on the device, then ONE device-to-host copy.  Returns (scores,
+    assignment): host (det L, [link 1 x n_t x n_{t+1} ...], new L, end L) and what ``ortools_solve(*scores, det_split)``
+    returns."""
+    with torch.no_grad():
+        det_score, link_score, new_score, end_score, _ = model(det_imgs, det_info, det_split)
+    split = chain_of(det_split)
+    det, links, new, end = select_chain(det_score, link_score, new_score, end_score, model.test_mode)
+    L = sum(split)
+    buf = torch.cat([t.reshape(-1) for t in (det, new, end, *links)])
+    if L == 0:
+        raise ValueError('predict_assign_chain: no detections')
+    out, _ = torch.ops.mmmot.associate_chains(buf[0:L], buf[L:2 * L], buf[2 * L:3 * L], buf[3 * L:],
+                                              chains_table([split])[0])
+    flat = torch.cat([buf, out]).to('cpu')  # scores and assignment in one copy
+    scores = flat[0:L], [], flat[L:2 * L], flat[2 * L:3 * L]
+    o = 3 * L
+    for a, b in zip(split[:-1], split[1:]):
+        scores[1].append(flat[o:o + a * b].view(1, a, b))
+        o += a * b
+    return scores, unpack_chain(flat[o:o + chain_block_size(split)], split)

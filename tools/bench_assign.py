@@ -10,6 +10,14 @@
 Writes <out>/bench_assign.json and prints it.
 
     python tools/bench_assign.py --out <dir> [--iters 50] [--frames 40] [--repeats 3]
+
+``--chain`` measures the chain association (csrc/assign_chain.hip) instead, with the same HIP-event timing per launch:
+mmmot_associate_chains for B in {1, 16, 64} x three frames of 12 / 64 / 128 detections for either kernel variant; the
+chain kernel at T = 2 against mmmot_associate_pairs on the identical instances (12 x 12, 64 x 64, 128 x 128); and the
+host stand-ins for CBC, scipy's linprog and milp on the literal program (tests/association_chain_ref).  Writes
+<out>/bench_assign_chain.json.
+
+    python tools/bench_assign.py --chain --out <dir> [--iters 200]
 """
 import argparse
 import json
@@ -74,6 +82,86 @@ def device_ms(ops, insts, variant, iters):
     return statistics.median(ts)
 
 
+def chain_instances(B, split, seed):
+    """B chains of the 'eval' kind (new = 0 in the first frame, end = 0 in the last), standard normal scores"""
+    from association_chain_ref import random_chain
+    rng = np.random.default_rng(seed)
+    return [(list(split), random_chain(rng, split, 1.0, 'eval')) for _ in range(B)]
+
+
+def chain_device_ms(ops, insts, variant, iters):
+    from mmmot_amd.association import chains_table
+    from mmmot_amd.torch_ops import chain_layout
+    chains, _ = chains_table([s for s, _ in insts])
+    cat = lambda k: torch.from_numpy(np.concatenate([sc[k].reshape(-1) for _, sc in insts])).cuda()
+    det, new, end = cat(0), cat(1), cat(2)
+    link = torch.from_numpy(np.concatenate([l.reshape(-1) for _, sc in insts for l in sc[3]])).cuda()
+    total, off, max_n, max_L = chain_layout(chains, det.numel(), link.numel())
+    B = len(insts)
+    table = torch.cat([chains.reshape(-1), off.to(torch.int32)]).cuda()
+    out = torch.empty(total, dtype=torch.float32, device='cuda')
+    obj = torch.empty(B, dtype=torch.float64, device='cuda')
+    assert _lib.load().mmmot_set_chain_variant(variant) == 0
+    try:
+        run = lambda: ops.associate_chains(det, new, end, link, table[:11 * B], B, max_n, max_L, out, table[11 * B:], obj)
+        for _ in range(3):
+            run()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+    finally:
+        _lib.load().mmmot_set_chain_variant(0)
+    return statistics.median(ts)
+
+
+def chain_main(args):
+    from association_chain_ref import lp_route, milp_route
+    ops = HipOps()
+    res = {'instances': "random_chain(.., scale 1, 'eval')", 'iters': args.iters, 'chain_ms_per_launch': [],
+           'two_frames_ms_per_launch': [], 'host_ms_per_chain': []}
+    for n in (12, 64, 128):
+        split = [n, n, n]
+        for B in (1, 16, 64):
+            insts = chain_instances(B, split, seed=n * 1000 + B)
+            row = {'split': split, 'B': B}
+            for v in (0, 1, 2):
+                row['variant%d' % v] = round(chain_device_ms(ops, insts, v, args.iters), 4)
+            row['auto_us_per_chain'] = round(row['variant0'] * 1e3 / B, 2)
+            res['chain_ms_per_launch'].append(row)
+            print(json.dumps(row), flush=True)
+        _, (det, new, end, links) = chain_instances(1, split, seed=n)[0]
+        h = {'split': split}
+        for name, fn in (('linprog_ms', lp_route), ('milp_ms', milp_route)):
+            ts = []
+            for _ in range(args.host_reps):
+                t0 = time.perf_counter()
+                fn(det, new, end, links, split)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            h[name] = round(statistics.median(ts), 3)
+        res['host_ms_per_chain'].append(h)
+        print(json.dumps(h), flush=True)
+    for n in (12, 64, 128):  # T = 2: the chain kernel and the pair kernel on the identical instances
+        for B in (1, 16, 64):
+            insts = chain_instances(B, [n, n], seed=n * 77 + B)
+            pair_insts = [(n, n, (sc[0], sc[1], sc[2], sc[3][0])) for _, sc in insts]
+            row = {'N': n, 'M': n, 'B': B, 'pairs_auto': round(device_ms(ops, pair_insts, 0, args.iters), 4)}
+            for v in (0, 1, 2):
+                row['chain_variant%d' % v] = round(chain_device_ms(ops, insts, v, args.iters), 4)
+            row['chain_over_pairs'] = round(row['chain_variant0'] / row['pairs_auto'], 2)
+            res['two_frames_ms_per_launch'].append(row)
+            print(json.dumps(row), flush=True)
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_assign_chain.json'), 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def host_ms(fn, inst, reps):
     N, M, (det, new, end, link) = inst
     ts = []
@@ -112,7 +200,10 @@ def main():
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--host-reps', type=int, default=3)
     ap.add_argument('--no-pipeline', action='store_true')
+    ap.add_argument('--chain', action='store_true', help='measure the chain association instead')
     args = ap.parse_args()
+    if args.chain:
+        return chain_main(args)
     from association_ref import lsa_route, milp_route
     ops = HipOps()
     res = {'device_ms_per_launch': [], 'host_ms_per_pair': []}
