@@ -763,6 +763,41 @@ int mmmot_clear_mot(const double* boxes, int nG, int nT, int nD, const int* fram
                     double min_overlap, double min_height, double max_truncation, double max_occlusion,
                     double* frame_d, int* frame_i, int* gt_out, int* traj_i, double* seq_d, int* seq_i, void* stream);
 
+/* Training targets of chains (reference tracking_model.py:294-351, TrackingModule.generate_gt, restated literally;
+ * csrc/labels.hip), additive in ABI 10.  One workgroup per chain, ids and classes staged in LDS, every output element
+ * written once by a plain store: results are deterministic and do not depend on the chain's place in the batch.
+ *   ids / cls: int32, chain c's L = sum n_t values at [score offset, + L), frame after frame;
+ *   chains: the int32 [B][MMMOT_CHAIN_ROW] table of mmmot_associate_chains (T, score offset, link offset, n_0 .. n_7; the
+ *   link offset is not read), 2 <= T <= 8, 0 <= n_t <= max_n <= 512, 1 <= L <= max_L <= 1024;
+ *   out: fp32, chain c's block at out_off[c] = [gt_det L | gt_new L | gt_end L | link_0 | .. | link_{T-2}] (link_t
+ *   row-major n_t x n_{t+1}), 0 / 1 values, every element written, zeros included: the caller does not clear it.
+ * For detection j of frame t with pos = (cls == 1): gt_det = pos; succ = the smallest k of frame t + 1 with an equal id -
+ * by id alone, whatever that detection's class, and -1 equals -1; link_t[j][k] = pos && k == succ; gt_end = pos && (t ==
+ * T - 1 || no succ); gt_new = pos && (t == 0 || no equal id in frame t - 1).  An empty neighbour frame matches nothing.
+ * A chain outside the limits gets a NaN in the first element of its block (gt_det[0]) and nothing else of it is written.
+ * Returns MMMOT_EINVAL on a null pointer, B < 1, max_n outside [1, 512], max_L outside [max_n, min(1024, 8 max_n)] before
+ * any launch. */
+int mmmot_generate_gt(const int* ids, const int* cls, const int* chains, int B, int max_n, int max_L, float* out,
+                      const int* out_off, void* stream);
+
+/* Ground-truth identity and class of every detection (reference dataset/common.py:82-111, generate_det_id_matrix with
+ * calculate_distance, restated literally; csrc/labels.hip), NF frames in one launch, one workgroup per frame, additive
+ * in ABI 10.
+ *   det_xywh / gt_xywh: fp64 [.][4] boxes as x, y, w, h (finite), 8-byte aligned;  gt_id / gt_name: int32 per gt box;
+ *   frames: int32 [NF][4] = (det offset, n_det, gt offset, n_gt) in boxes, 0 <= n_det, n_gt <= max_n <= 512;
+ *   det_id / det_cls: int32 per detection, written for every detection of every frame.
+ * Per (gt i, det d), in fp64 with one IEEE operation per step (no FMA contraction): isect = the product over both axes
+ * of max(min(br) - max(tl), 0) with br = tl + size, union = a_gt + a_det - isect, dist = 1 - isect / union; union == 0
+ * or dist > max_iou count as 10; the value is rounded to fp32.  Gt i points at arg-min over d of these fp32 values, ties
+ * to the smallest d - a gt that overlaps nothing (a row of 10s) points at det 0.  Det d takes the LARGEST i that points
+ * at it (the reference overwrites in the order of i): det_id = gt_id[i], det_cls = 1 if gt_name[i] == car_code, -1 if
+ * == dontcare_code, else 0; a det nobody points at gets id -1, cls 0 (so n_gt = 0 gives that to every det).  n_det = 0
+ * writes nothing; neither does a frame outside the limits or with a negative offset.
+ * Returns MMMOT_EINVAL on a null or misaligned pointer, NF < 1 or max_n outside [1, 512] before any launch. */
+int mmmot_match_dets(const double* det_xywh, const double* gt_xywh, const int* gt_id, const int* gt_name,
+                     const int* frames, int NF, int car_code, int dontcare_code, double max_iou, int max_n, int* det_id,
+                     int* det_cls, void* stream);
+
 /* MFMA fragment-layout self test: C[32][32] = A[32][K] * B[32][K]^T through
  * the same fragment mapping the GEMM kernels use (K % 8 == 0). */
 int mmmot_selftest_mfma(const float* A, const float* B, float* C, int K, void* stream);

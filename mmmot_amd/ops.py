@@ -390,6 +390,23 @@ class HipOps:
                                       _iptr(seq_i), self._stream())
         _lib.check(st, 'mmmot_clear_mot')
 
+    def generate_gt(self, ids, cls, chains, B, max_n, max_L, out, out_off):
+        """Training targets of B chains in one launch; see mmmot_generate_gt.  ids / cls / chains / out_off: int32 device
+        tensors; out: fp32."""
+        st = self.lib.mmmot_generate_gt(_iptr(ids), _iptr(cls), _iptr(chains), int(B), int(max_n), int(max_L), _ptr(out),
+                                        _iptr(out_off), self._stream())
+        _lib.check(st, 'mmmot_generate_gt')
+
+    def match_dets(self, det_xywh, gt_xywh, gt_id, gt_name, frames, NF, car_code, dontcare_code, max_iou, max_n, det_id,
+                   det_cls):
+        """Ground-truth id and class of the detections of NF frames in one launch; see mmmot_match_dets.  det_xywh /
+        gt_xywh: fp64 device tensors, the rest int32."""
+        d = torch.float64
+        st = self.lib.mmmot_match_dets(_ptr(det_xywh, d), _ptr(gt_xywh, d), _iptr(gt_id), _iptr(gt_name), _iptr(frames),
+                                       int(NF), int(car_code), int(dontcare_code), float(max_iou), int(max_n),
+                                       _iptr(det_id), _iptr(det_cls), self._stream())
+        _lib.check(st, 'mmmot_match_dets')
+
     # ---- training backward of the pairwise block (include/mmmot_hip.h, csrc/backward.hip) -------------------
     def gn_bwd_partial(self, dA, Y, C, sc1, sh1, gamma, beta, relu, tiles, P):
         st = self.lib.mmmot_gn_bwd_partial(_ptr(dA), _ld(dA), _ptr(Y), _ld(Y), C, _ptr(sc1), _ptr(sh1), _ld(sc1),

@@ -229,36 +229,37 @@ CHAIN_ROW = 3 + CHAIN_MAX_T
 CHAIN_MAX_L = 1024
 
 
-def chain_layout(chains, n_scores=None, n_link=None):
+def chain_layout(chains, n_scores=None, n_link=None, op='associate_chains'):
     """(total output floats, int64 [B] output offsets, max n_t, max L) of a chain table; checks the table, and against
-    the sizes of the score / link buffers when given (the kernel reads what the table says)."""
+    the sizes of the score / link buffers when given (the kernel reads what the table says).  ``op``: the operator the
+    table is for (mmmot::associate_chains and mmmot::generate_gt share it), named in the refusals."""
     if chains.device.type != 'cpu' or chains.dtype != torch.int32 or chains.dim() != 2 or chains.shape[1] != CHAIN_ROW:
-        raise ValueError('mmmot::associate_chains: chains must be a CPU int32 [B, %d] table (T, score offset, link '
-                         'offset, n_0 .. n_7)' % CHAIN_ROW)
+        raise ValueError('mmmot::%s: chains must be a CPU int32 [B, %d] table (T, score offset, link offset, '
+                         'n_0 .. n_7)' % (op, CHAIN_ROW))
     if chains.shape[0] < 1:
-        raise ValueError('mmmot::associate_chains: no chains')
+        raise ValueError('mmmot::%s: no chains' % op)
     t = chains.numpy().astype(np.int64)
     T, so, lo = t[:, 0], t[:, 1], t[:, 2]
     if T.min() < 2 or T.max() > CHAIN_MAX_T:
-        raise ValueError('mmmot::associate_chains: every chain needs 2 <= T <= %d frames' % CHAIN_MAX_T)
+        raise ValueError('mmmot::%s: every chain needs 2 <= T <= %d frames' % (op, CHAIN_MAX_T))
     n = np.where(np.arange(CHAIN_MAX_T)[None, :] < T[:, None], t[:, 3:], 0)  # entries past n_{T-1} are ignored
     if n.min() < 0 or n.max() > MAX_ASSOC:
-        raise ValueError('mmmot::associate_chains: every frame needs 0 <= n_t <= %d' % MAX_ASSOC)
+        raise ValueError('mmmot::%s: every frame needs 0 <= n_t <= %d' % (op, MAX_ASSOC))
     L = n.sum(1)
     if L.min() < 1 or L.max() > CHAIN_MAX_L:
-        raise ValueError('mmmot::associate_chains: every chain needs 1 <= L <= %d detections' % CHAIN_MAX_L)
+        raise ValueError('mmmot::%s: every chain needs 1 <= L <= %d detections' % (op, CHAIN_MAX_L))
     if np.minimum(so, lo).min() < 0:
-        raise ValueError('mmmot::associate_chains: negative offset in the chain table')
+        raise ValueError('mmmot::%s: negative offset in the chain table' % op)
     K = (n[:, :-1] * n[:, 1:]).sum(1)
     if n_scores is not None and (so + L).max() > n_scores:
-        raise ValueError('mmmot::associate_chains: a chain reads past the end of the score buffers')
+        raise ValueError('mmmot::%s: a chain reads past the end of the score buffers' % op)
     if n_link is not None and (lo + K).max() > n_link:
-        raise ValueError('mmmot::associate_chains: a chain reads past the end of the link buffer')
+        raise ValueError('mmmot::%s: a chain reads past the end of the link buffer' % op)
     sizes = 3 * L + K
     off = np.cumsum(sizes) - sizes
     total = int(sizes.sum())
     if total >= 2 ** 31:
-        raise ValueError('mmmot::associate_chains: output block exceeds 32-bit offsets')
+        raise ValueError('mmmot::%s: output block exceeds 32-bit offsets' % op)
     return total, torch.from_numpy(off), int(n.max()), int(L.max())
 
 
@@ -416,3 +417,105 @@ def _clear_mot_meta(packed, sizes, params):
 _LIB.define('clear_mot(Tensor packed, int[] sizes, float[] params) -> Tensor')
 _LIB.impl('clear_mot', _clear_mot, 'CUDA')
 _LIB.impl('clear_mot', _clear_mot_meta, 'Meta')
+
+
+# ---- training labels (mmmot_amd/labels.py; csrc/labels.hip) ---------------------------------------------------------
+#   mmmot::generate_gt(Tensor ids, Tensor cls, Tensor chains) -> Tensor
+#       The targets of B chains in one launch (mmmot_generate_gt).  ids / cls: flat int32 device tensors, chain c's L
+#       values at its score offset; chains: the CPU int32 [B, 11] table of mmmot::associate_chains (the link offset is not
+#       read).  Returns out fp32: chain c's [gt_det L | gt_new L | gt_end L | link_0 | .. | link_{T-2}] one after the
+#       other, at the offsets of chain_layout - the block of association.unpack_chain.
+def _generate_gt(ids, cls, chains):
+    if ids.dtype != torch.int32 or cls.dtype != torch.int32 or ids.dim() != 1 or cls.dim() != 1:
+        raise ValueError('mmmot::generate_gt: ids and cls must be flat int32 tensors')
+    total, off, max_n, max_L = chain_layout(chains, min(int(ids.numel()), int(cls.numel())), op='generate_gt')
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    B = int(chains.shape[0])
+    # chain table + output offsets in one pinned block: an asynchronous copy (a pageable one would wait for the stream)
+    host = torch.empty((CHAIN_ROW + 1) * B, dtype=torch.int32, pin_memory=True)
+    host[:CHAIN_ROW * B] = chains.reshape(-1)
+    host[CHAIN_ROW * B:] = off
+    table = host.to(ids.device, non_blocking=True)
+    out = torch.empty(total, dtype=torch.float32, device=ids.device)
+    _ASSOC_OPS[0].generate_gt(ids.contiguous(), cls.contiguous(), table[:CHAIN_ROW * B], B, max_n, max_L, out,
+                              table[CHAIN_ROW * B:])
+    return out
+
+
+def _generate_gt_meta(ids, cls, chains):
+    return ids.new_empty((chain_layout(chains, op='generate_gt')[0],), dtype=torch.float32)
+
+
+_LIB.define('generate_gt(Tensor ids, Tensor cls, Tensor chains) -> Tensor')
+_LIB.impl('generate_gt', _generate_gt, 'CUDA')
+_LIB.impl('generate_gt', _generate_gt_meta, 'Meta')
+
+
+#   mmmot::match_dets(Tensor det_xywh, Tensor gt_xywh, Tensor gt_id, Tensor gt_name, Tensor frames, int car, int dontcare,
+#                     float max_iou) -> Tensor
+#       generate_det_id_matrix for NF frames in one launch (mmmot_match_dets).  det_xywh / gt_xywh: fp64 device [.][4]
+#       boxes (x, y, w, h); gt_id / gt_name: int32 device, one per gt box; frames: a CPU int32 [NF, 4] table (det offset,
+#       n_det, gt offset, n_gt).  Returns int32 [2, number of det boxes]: row 0 the ids, row 1 the classes (a detection
+#       that no frame of the table covers keeps -1 / 0).
+def match_layout(frames, n_det=None, n_gt=None):
+    """max(n_det, n_gt, 1) of a frame table; checks the table, and against the box counts when given (the kernel reads
+    and writes what the table says)."""
+    if frames.device.type != 'cpu' or frames.dtype != torch.int32 or frames.dim() != 2 or frames.shape[1] != 4:
+        raise ValueError('mmmot::match_dets: frames must be a CPU int32 [NF, 4] table (det offset, n_det, gt offset, n_gt)')
+    if frames.shape[0] < 1:
+        raise ValueError('mmmot::match_dets: no frames')
+    t = frames.numpy().astype(np.int64)
+    do, nd, go, ng = t[:, 0], t[:, 1], t[:, 2], t[:, 3]
+    if t.min() < 0:
+        raise ValueError('mmmot::match_dets: negative entry in the frame table')
+    if max(nd.max(), ng.max()) > MAX_ASSOC:
+        raise ValueError('mmmot::match_dets: every frame needs n_det, n_gt <= %d' % MAX_ASSOC)
+    if n_det is not None and (do + nd).max() > n_det:
+        raise ValueError('mmmot::match_dets: a frame reaches past the end of the detection boxes')
+    if n_gt is not None and (go + ng).max() > n_gt:
+        raise ValueError('mmmot::match_dets: a frame reads past the end of the ground-truth boxes')
+    order = np.argsort(do, kind='stable')  # two frames must not write the same detections
+    if ((do + nd)[order][:-1] > do[order][1:]).any():
+        raise ValueError('mmmot::match_dets: the detection ranges of two frames overlap')
+    return int(max(nd.max(), ng.max(), 1))
+
+
+def _match_dets(det_xywh, gt_xywh, gt_id, gt_name, frames, car, dontcare, max_iou):
+    f64 = lambda t: t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == 4
+    if not f64(det_xywh) or not f64(gt_xywh):
+        raise ValueError('mmmot::match_dets: boxes must be fp64 [n, 4] tensors')
+    if gt_id.dtype != torch.int32 or gt_name.dtype != torch.int32:
+        raise ValueError('mmmot::match_dets: gt_id and gt_name must be int32 tensors')
+    n_det = int(det_xywh.shape[0])
+    n_gt = min(int(gt_xywh.shape[0]), int(gt_id.numel()), int(gt_name.numel()))
+    max_n = match_layout(frames, n_det, n_gt)
+    res = torch.empty((2, n_det), dtype=torch.int32, device=det_xywh.device)
+    res[0].fill_(-1)
+    res[1].zero_()
+    if n_det == 0:
+        return res
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    NF = int(frames.shape[0])
+    host = torch.empty(4 * NF, dtype=torch.int32, pin_memory=True)
+    host.copy_(frames.reshape(-1))
+    table = host.to(det_xywh.device, non_blocking=True)
+    if n_gt == 0:  # never read (every n_gt is 0), but not a null pointer
+        gt_xywh, gt_id, gt_name = det_xywh, res[0], res[0]
+    _ASSOC_OPS[0].match_dets(det_xywh.contiguous(), gt_xywh.contiguous(), gt_id.contiguous(), gt_name.contiguous(), table,
+                             NF, car, dontcare, max_iou, max_n, res[0], res[1])
+    return res
+
+
+def _match_dets_meta(det_xywh, gt_xywh, gt_id, gt_name, frames, car, dontcare, max_iou):
+    match_layout(frames)
+    return det_xywh.new_empty((2, int(det_xywh.shape[0])), dtype=torch.int32)
+
+
+_LIB.define('match_dets(Tensor det_xywh, Tensor gt_xywh, Tensor gt_id, Tensor gt_name, Tensor frames, int car, '
+            'int dontcare, float max_iou) -> Tensor')
+_LIB.impl('match_dets', _match_dets, 'CUDA')
+_LIB.impl('match_dets', _match_dets_meta, 'Meta')
