@@ -39,7 +39,7 @@ def chunked_segments(start, count, stride, device):
 def segsum(eng, X, C, segs, out):
     """segment sums through mmmot_segment_mean (divisor 1); `segs`: a Segments or a two-level pair of chunked_segments"""
     if isinstance(segs, tuple):
-        part = torch.empty(segs[0].n, C, dtype=torch.float32, device=X.device)
+        part = torch.empty(segs[0].n, C, dtype=X.dtype, device=X.device)
         eng.ops.segment_mean(X, C, segs[0], part, use_group=False)
         eng.ops.segment_mean(part, C, segs[1], out, use_group=False)
     else:
@@ -94,17 +94,17 @@ def colsum(eng, X):
             else:
                 seg = Segments([0], [rows], [1], [0], X.device, div=[1])
             cache[key] = seg
-        out = torch.empty(seg.n, C, dtype=torch.float32, device=X.device)
+        out = torch.empty(seg.n, C, dtype=X.dtype, device=X.device)
         eng.ops.segment_mean(X, C, seg, out, use_group=False)
         if seg.n == 1:
             return out[0] if fold == 1 else out.view(fold, C0).sum(0)
         X, rows = out, seg.n
 
 
-def unit(eng, C, dev):
-    key = ('unit', C, str(dev))
+def unit(eng, C, dev, dtype=torch.float32):
+    key = ('unit', C, str(dev)) if dtype == torch.float32 else ('unit', C, str(dev), dtype)
     if key not in eng.ws:
-        eng.ws[key] = (torch.ones(C, dtype=torch.float32, device=dev), torch.zeros(C, dtype=torch.float32, device=dev))
+        eng.ws[key] = (torch.ones(C, dtype=dtype, device=dev), torch.zeros(C, dtype=dtype, device=dev))
     return eng.ws[key]
 
 
@@ -151,19 +151,20 @@ def weight_grad(eng, dY, tiles, N, K, shares=None, **operand):
 
 def gn_backward(eng, plan, L, dA, out=None, relu=True):
     """dA = gradient w.r.t. relu(GroupNorm(Y)) (or GroupNorm(Y) when ``relu`` is False) -> (dY, dgamma [C],
-    dbeta [C]).  ``out``: view to write dY into."""
+    dbeta [C]).  ``out``: view to write dY into.  Buffers take dA's dtype (fp32 on the device; the float64 emulation of the
+    tests keeps float64 between the operators that way)."""
     ops, tiles, C, dev = eng.ops, L.tiles, L.C, dA.device
-    P = torch.empty(tiles.T, 2, C, dtype=torch.float32, device=dev)
+    P = torch.empty(tiles.T, 2, C, dtype=dA.dtype, device=dev)
     ops.gn_bwd_partial(dA, L.Y, C, L.sc1, L.sh1, L.gamma, L.beta, relu, tiles, P)
     seg_g, seg_t = tile_sums(plan, tiles, dev)
-    S = torch.empty(tiles.G * 2, C, dtype=torch.float32, device=dev)
-    tot = torch.empty(2, C, dtype=torch.float32, device=dev)
+    S = torch.empty(tiles.G * 2, C, dtype=dA.dtype, device=dev)
+    tot = torch.empty(2, C, dtype=dA.dtype, device=dev)
     P2 = P.view(2 * tiles.T, C)
     segsum(eng, P2, C, seg_g, S)
     segsum(eng, P2, C, seg_t, tot)
-    M = torch.empty(tiles.G, 2, C, dtype=torch.float32, device=dev)
+    M = torch.empty(tiles.G, 2, C, dtype=dA.dtype, device=dev)
     ops.gn_bwd_finalize(S, tiles, C, L.NG, L.gamma, M)
-    dY = out if out is not None else torch.empty(tiles.R, C, dtype=torch.float32, device=dev)
+    dY = out if out is not None else torch.empty(tiles.R, C, dtype=dA.dtype, device=dev)
     ops.gn_bwd_apply(dA, L.Y, C, L.sc1, L.sh1, L.gamma, L.beta, relu, M, tiles, dY)
     return dY, tot[1], tot[0]
 
@@ -198,12 +199,12 @@ class Layer:
 def norm_layer(eng, part, tiles, Y, C, NG, gamma, beta, sc=None, sh=None):
     """The Layer of a pre-norm output Y with per-tile statistics `part`: finalize twice, (gamma, beta) -> sc / sh for the
     consumer's prologue (unless the caller has them already), (1, 0) -> sc1 = rstd, sh1 = -mean * rstd."""
-    new = lambda: torch.empty(tiles.G, C, dtype=torch.float32, device=Y.device)
+    new = lambda: torch.empty(tiles.G, C, dtype=Y.dtype, device=Y.device)
     if sc is None:
         sc, sh = new(), new()
         eng.ops.gn_finalize(part, tiles, C, NG, gamma, beta, eng.eps, sc, sh)
     sc1, sh1 = new(), new()
-    one, zero = unit(eng, C, Y.device)
+    one, zero = unit(eng, C, Y.device, Y.dtype)
     eng.ops.gn_finalize(part, tiles, C, NG, one, zero, eng.eps, sc1, sh1)
     return Layer(Y, C, NG, gamma, beta, sc, sh, sc1, sh1, tiles, eng.eps)
 

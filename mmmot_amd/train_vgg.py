@@ -69,6 +69,98 @@ def _param_list(model):
     return keys, ts
 
 
+def dgrad_weights(wp):
+    """the weights that turn the forward convolution kernel into its input gradient: wp [tap][Cout][Cin] with the taps in
+    reverse order (tap (ky, kx) of the gradient is tap (2 - ky, 2 - kx) of the forward) and every tap transposed ->
+    [tap][Cin][Cout], for a launch with Cin and Cout exchanged"""
+    return wp.flip(0).permute(0, 2, 1).contiguous()
+
+
+def layer_forward_train(eng, cache, x, w, b, gamma, beta, L, H, W, cin, cout, pool, first):
+    """One trunk layer in training mode: conv3x3 (w [Cout][Cin][3][3], b) -> BatchNorm on the statistics of the batch (gamma,
+    beta) -> ReLU (-> 2x2 max-pool).  x: the crops [L][3][H][W] (``first``) or NHWC rows [L * H * W][Cin]; ``cache``: the
+    dict that keeps the row tilings.  Returns (A [L * Ho * Wo][Cout], the layer's tape record for layer_backward_train).
+    Buffers take x's dtype (fp32 on the device)."""
+    ops, dev = eng.ops, x.device
+    new = lambda *s: torch.empty(*s, dtype=x.dtype, device=dev)
+    if first:  # [Cout][3][3][3] (n, c, ky, kx) -> [Cout][k = (ky*3+kx)*3 + c], padded to 32
+        wp = torch.zeros(cout, 32, dtype=x.dtype, device=dev)
+        wp[:, :27] = w.permute(0, 2, 3, 1).reshape(cout, 27)
+    else:      # -> [tap][Cout][Cin]
+        wp = w.permute(2, 3, 0, 1).reshape(9, cout, cin).contiguous()
+    rows = L * H * W
+    Z = new(rows, cout)
+    amw = None
+    if _f16_convs(ops) and not first:
+        # f16x3 (round 4): activations split once (hl16), weights scaled by a device-side power of two (max |w| ->
+        # [2^13, 2^14): their lo halves stay normal fp16 numbers) and split, the trunk kernel of the inference path with
+        # a raw fp32 output.  Nothing crosses the host: the step's weights are whatever the optimizer left on the device.
+        x16, w16, amw, osc = new(x.shape[0], cin), torch.empty_like(wp), new(1), new(cout)
+        ops.hl16_pack(x, x16)
+        ops.absmax(wp, amw)
+        ops.hl16_pack_pow2(wp, w16, amw, 14)
+        ops.pow2_oscale(osc, amw, 14)
+        ops.conv3x3_raw_hl16(x16, w16, b, Z, L, H, W, cin, cout, osc)
+    else:
+        ops.conv3x3_raw(x, wp, b, Z, L, H, W, cin, cout, first)
+    T = _tiles(cache, rows, dev)
+    part = new(T.T, 2, cout)
+    ops.rows_stats(Z, cout, T, part)
+    Lyr = norm_layer(eng, part, T, Z, cout, cout, gamma, beta)
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+    A = new(L * Ho * Wo, cout)
+    ops.bn_relu_pool(Z, cout, Lyr.sc, Lyr.sh, L, H, W, pool, A)
+    return A, dict(L=Lyr, x=x, wp=wp, H=H, W=W, Ho=Ho, Wo=Wo, cin=cin, cout=cout, pool=pool, first=first, rows=rows, amw=amw)
+
+
+def layer_backward_train(eng, plan, ly, dA, L):
+    """Backward of layer_forward_train from dA [L * Ho * Wo][Cout], the gradient w.r.t. the layer's output; ``ly``: its tape
+    record, ``plan``: any object whose __dict__ may keep the summation tables.  Returns (dX [L * H * W][Cin] - None for the
+    first layer, whose input is the crops -, dW [Cout][Cin][3][3], db, dgamma, dbeta)."""
+    ops, dev = eng.ops, dA.device
+    new = lambda *s_: torch.empty(*s_, dtype=dA.dtype, device=dev)
+    Lyr, H, W, cin, cout, rows = ly['L'], ly['H'], ly['W'], ly['cin'], ly['cout'], ly['rows']
+    if ly['pool']:
+        dApre = new(L * H * W, cout)
+        ops.maxpool_bwd(Lyr.Y, cout, Lyr.sc, Lyr.sh, dA, L, H, W, dApre)
+    else:
+        dApre = dA
+    dZ, dgamma, dbeta = gn_backward(eng, plan, Lyr, dApre)
+    db = colsum(eng, dZ)
+    if ly['first']:
+        nb = max(1, min(1024, rows // 512))
+        PW = new(nb, 64 * 28)
+        ops.conv3x3_first_wgrad(dZ, ly['x'], L, H, W, PW)
+        pw = colsum(eng, PW).view(64, 28)
+        return None, pw[:, :27].reshape(64, 3, 3, 3).permute(0, 3, 1, 2), db, dgamma, dbeta  # [n][ky][kx][c] -> [n][c][ky][kx]
+    f16 = _f16_convs(ops) and ly['amw'] is not None
+    ns = _wgrad_shares(dev, cin, cout, rows, f16)
+    dWp = new(ns, 9 * cout * cin)
+    if f16:
+        amz = new(1)
+        ops.absmax(dZ, amz)  # one maximum for both uses of dZ
+        ops.conv3x3_wgrad(dZ, ly['x'], L, H, W, cin, cout, ns, dWp, amax=amz)
+    else:
+        ops.conv3x3_wgrad(dZ, ly['x'], L, H, W, cin, cout, ns, dWp)
+    dW = colsum(eng, dWp) if ns > 1 else dWp[0]
+    # input gradient: the same convolution kernel on dZ with the taps flipped and Cin / Cout swapped
+    wflip = dgrad_weights(ly['wp'])  # [tap][Cin][Cout]
+    zero = torch.zeros(cin, dtype=dA.dtype, device=dev)
+    dX = new(L * H * W, cin)
+    if f16:
+        # f16x3: dZ scaled by the power of two that puts its maximum at 2^10 (gradients of 1e-6 sit in fp16's
+        # subnormals otherwise - what broke the SGD-step parity of the unscaled attempt of round 3), the weights
+        # by theirs; the epilogue's per-channel vector undoes both exactly
+        dz16, wf16, osc = new(rows, cout), torch.empty_like(wflip), new(cin)
+        ops.hl16_pack_pow2(dZ, dz16, amz, 11)
+        ops.hl16_pack_pow2(wflip, wf16, ly['amw'], 14)
+        ops.pow2_oscale(osc, amz, 11, ly['amw'], 14)
+        ops.conv3x3_raw_hl16(dz16, wf16, zero, dX, L, H, W, cout, cin, osc)
+    else:
+        ops.conv3x3_raw(dZ, wflip, zero, dX, L, H, W, cout, cin, False)
+    return dX, dW.view(3, 3, cout, cin).permute(2, 3, 0, 1), db, dgamma, dbeta
+
+
 def appearance_forward_train(eng, model, plan, crops, P):
     """crops [L][3][S][S]; P: {appearance-relative key: detached fp32 tensor}.  Returns (feats [L][512], tape)."""
     ops, L, S = eng.ops, plan.Lt, plan.S
@@ -78,45 +170,18 @@ def appearance_forward_train(eng, model, plan, crops, P):
         raise NotImplementedError('training-mode trunk: one sample per call (BatchNorm2d statistics are those of the forward)')
     dropblock = int(getattr(model.appearance, 'dropblock', 0) or 0)  # block size; stages 2 / 3 (appear_net.py:143-152)
     cache = plan.__dict__.setdefault('_vgg_train_tiles', {})
-    f16 = _f16_convs(ops)
     feats = new(L, 512)
     tape = dict(layers=[], heads=[])
     x, H, W = crops.contiguous(), S, S
     first = True
     for li, (s, cidx, bn, cin, cout, pool, last) in enumerate(_conv_params(model)):
         pre = 'layers.%d.' % s
-        w = P[pre + '%d.weight' % cidx]
-        b = P[pre + '%d.bias' % cidx]
-        if first:  # [Cout][3][3][3] (n, c, ky, kx) -> [Cout][k = (ky*3+kx)*3 + c], padded to 32
-            wp = torch.zeros(cout, 32, dtype=torch.float32, device=dev)
-            wp[:, :27] = w.permute(0, 2, 3, 1).reshape(cout, 27)
-        else:      # -> [tap][Cout][Cin]
-            wp = w.permute(2, 3, 0, 1).reshape(9, cout, cin).contiguous()
-        rows = L * H * W
-        Z = new(rows, cout)
-        amw = None
-        if f16 and not first:
-            # f16x3 (round 4): activations split once (hl16), weights scaled by a device-side power of two (max |w| ->
-            # [2^13, 2^14): their lo halves stay normal fp16 numbers) and split, the trunk kernel of the inference path with
-            # a raw fp32 output.  Nothing crosses the host: the step's weights are whatever the optimizer left on the device.
-            x16, w16, amw, osc = new(x.shape[0], cin), torch.empty_like(wp), new(1), new(cout)
-            ops.hl16_pack(x, x16)
-            ops.absmax(wp, amw)
-            ops.hl16_pack_pow2(wp, w16, amw, 14)
-            ops.pow2_oscale(osc, amw, 14)
-            ops.conv3x3_raw_hl16(x16, w16, b, Z, L, H, W, cin, cout, osc)
-        else:
-            ops.conv3x3_raw(x, wp, b, Z, L, H, W, cin, cout, first)
-        T = _tiles(cache, rows, dev)
-        part = new(T.T, 2, cout)
-        ops.rows_stats(Z, cout, T, part)
-        Lyr = norm_layer(eng, part, T, Z, cout, cout, P[pre + '%d.weight' % (cidx + 1)], P[pre + '%d.bias' % (cidx + 1)])
-        Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-        A = new(L * Ho * Wo, cout)
-        ops.bn_relu_pool(Z, cout, Lyr.sc, Lyr.sh, L, H, W, pool, A)
-        tape['layers'].append(dict(L=Lyr, x=x, wp=wp, H=H, W=W, cin=cin, cout=cout, pool=pool, first=first, stage=s,
-                                   last=last, cidx=cidx, bn=bn, rows=rows, amw=amw))
-        x, H, W, first = A, Ho, Wo, False
+        A, ly = layer_forward_train(eng, cache, x, P[pre + '%d.weight' % cidx], P[pre + '%d.bias' % cidx],
+                                    P[pre + '%d.weight' % (cidx + 1)], P[pre + '%d.bias' % (cidx + 1)], L, H, W, cin, cout,
+                                    pool, first)
+        ly.update(stage=s, last=last, cidx=cidx, bn=bn)
+        tape['layers'].append(ly)
+        x, H, W, first = A, ly['Ho'], ly['Wo'], False
         if last:
             tape['heads'].append(_head_forward(eng, plan, cache, s, x, H * W, cout, P, feats,
                                                drop=_dropblock_scale(L, H, W, dropblock, dev) if (dropblock and s >= 2) else None))
@@ -232,8 +297,7 @@ def appearance_backward(eng, model, plan, crops, tape, dF):
     heads = {hd['stage']: hd for hd in tape['heads']}
     dA = None  # gradient w.r.t. the current layer's OUTPUT (post BatchNorm / ReLU / pool), [L * Ho * Wo][Cout]
     for ly in reversed(tape['layers']):
-        Lyr, H, W, cin, cout, pool = ly['L'], ly['H'], ly['W'], ly['cin'], ly['cout'], ly['pool']
-        Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+        cout, Ho, Wo = ly['cout'], ly['Ho'], ly['Wo']
         pre = 'layers.%d.' % ly['stage']
         if ly['last']:
             hd = heads[ly['stage']]
@@ -254,49 +318,9 @@ def appearance_backward(eng, model, plan, crops, tape, dF):
                 both = new(L * hw, cout)
                 ops.add_rows(dA, dpool, both, cout)
                 dA = both
-        if pool:
-            dApre = new(L * H * W, cout)
-            ops.maxpool_bwd(Lyr.Y, cout, Lyr.sc, Lyr.sh, dA, L, H, W, dApre)
-        else:
-            dApre = dA
         cidx = ly['cidx']
-        dZ, g[pre + '%d.weight' % (cidx + 1)], g[pre + '%d.bias' % (cidx + 1)] = gn_backward(eng, plan, Lyr, dApre)
-        g[pre + '%d.bias' % cidx] = colsum(eng, dZ)
-        rows = ly['rows']
-        if ly['first']:
-            nb = max(1, min(1024, rows // 512))
-            PW = new(nb, 64 * 28)
-            ops.conv3x3_first_wgrad(dZ, ly['x'], L, H, W, PW)
-            pw = colsum(eng, PW).view(64, 28)
-            g[pre + '%d.weight' % cidx] = pw[:, :27].reshape(64, 3, 3, 3).permute(0, 3, 1, 2)  # [n][ky][kx][c] -> [n][c][ky][kx]
-            dA = None
-        else:
-            f16 = _f16_convs(ops) and ly['amw'] is not None
-            ns = _wgrad_shares(dev, cin, cout, rows, f16)
-            dWp = new(ns, 9 * cout * cin)
-            if f16:
-                amz = new(1)
-                ops.absmax(dZ, amz)  # one maximum for both uses of dZ
-                ops.conv3x3_wgrad(dZ, ly['x'], L, H, W, cin, cout, ns, dWp, amax=amz)
-            else:
-                ops.conv3x3_wgrad(dZ, ly['x'], L, H, W, cin, cout, ns, dWp)
-            dW = colsum(eng, dWp) if ns > 1 else dWp[0]
-            g[pre + '%d.weight' % cidx] = dW.view(3, 3, cout, cin).permute(2, 3, 0, 1)
-            # input gradient: the same convolution kernel on dZ with the taps flipped and Cin / Cout swapped
-            wflip = ly['wp'].flip(0).permute(0, 2, 1).contiguous()  # [tap][Cin][Cout]
-            zero = torch.zeros(cin, dtype=torch.float32, device=dev)
-            dA = new(L * H * W, cin)
-            if f16:
-                # f16x3: dZ scaled by the power of two that puts its maximum at 2^10 (gradients of 1e-6 sit in fp16's
-                # subnormals otherwise - what broke the SGD-step parity of the unscaled attempt of round 3), the weights
-                # by theirs; the epilogue's per-channel vector undoes both exactly
-                dz16, wf16, osc = new(rows, cout), torch.empty_like(wflip), new(cin)
-                ops.hl16_pack_pow2(dZ, dz16, amz, 11)
-                ops.hl16_pack_pow2(wflip, wf16, ly['amw'], 14)
-                ops.pow2_oscale(osc, amz, 11, ly['amw'], 14)
-                ops.conv3x3_raw_hl16(dz16, wf16, zero, dA, L, H, W, cout, cin, osc)
-            else:
-                ops.conv3x3_raw(dZ, wflip, zero, dA, L, H, W, cout, cin, False)
+        dA, g[pre + '%d.weight' % cidx], g[pre + '%d.bias' % cidx], g[pre + '%d.weight' % (cidx + 1)], \
+            g[pre + '%d.bias' % (cidx + 1)] = layer_backward_train(eng, plan, ly, dA, L)
     return g
 
 

@@ -286,8 +286,8 @@ class TorchOps:
             var = m2 / (cnt * CG)
             rstd = 1.0 / torch.sqrt(var + eps)
             scv = gamma.double() * rstd.repeat_interleave(CG)
-            sc[g, :C] = scv.float()
-            sh[g, :C] = (beta.double() - s1.repeat_interleave(CG) * scv).float()
+            sc[g, :C] = scv.to(sc.dtype)
+            sh[g, :C] = (beta.double() - s1.repeat_interleave(CG) * scv).to(sh.dtype)
 
     def segment_mean(self, X, C, segs, out, sc=None, sh=None, relu=False, use_group=True, hl16=False, take_max=False):
         if int(hl16) == 2:
@@ -501,14 +501,17 @@ class TorchOps:
         dW.reshape(nsplit, 9, Cout, Cin)[0] = gw.permute(2, 3, 0, 1).reshape(9, Cout, Cin).to(dW.dtype)
 
     def conv3x3_first_wgrad(self, dZ, X, L, H, W, PW):
-        with torch.enable_grad():
-            w = torch.zeros(64, 3, 3, 3, dtype=torch.float64, requires_grad=True)
-            y = torch.nn.functional.conv2d(X.reshape(L, 3, H, W).double(), w, None, padding=1)
-            g = dZ.reshape(-1)[:L * H * W * 64].view(L, H, W, 64).permute(0, 3, 1, 2).double()
-            (gw,) = torch.autograd.grad(y, w, g)
+        """PW[b]: block b's share, the pixels P * b // nb .. P * (b + 1) // nb of the (crop, y, x) order - the split the
+        kernel documents; the sum over the blocks is the whole gradient whatever nb is"""
+        nb, P = PW.shape[0], L * H * W
+        gz = dZ.reshape(-1)[:P * 64].view(P, 64).double()
+        win = torch.nn.functional.unfold(X.reshape(L, 3, H, W).double(), 3, padding=1)     # [L][colour * 9 + tap][H * W]
+        win = win.view(L, 3, 9, H * W).permute(0, 3, 2, 1).reshape(P, 27)                  # [pixel][k = tap * 3 + colour]
         PW.zero_()
-        PW[0].view(64, 28)[:, :27] = gw.permute(0, 2, 3, 1).reshape(64, 27).to(PW.dtype)  # k = (ky*3+kx)*3 + colour
-        PW[0].view(64, 28)[:, 27] = g.sum(dim=(0, 2, 3)).to(PW.dtype)
+        for b in range(nb):
+            lo, hi = P * b // nb, P * (b + 1) // nb
+            PW[b].view(64, 28)[:, :27] = (gz[lo:hi].t() @ win[lo:hi]).to(PW.dtype)
+            PW[b].view(64, 28)[:, 27] = gz[lo:hi].sum(0).to(PW.dtype)
 
     # ---- training step, second slice (csrc/train.hip) ----
     def rows_gather_scale(self, S, rowidx, scale, X, C):
