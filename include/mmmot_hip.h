@@ -798,6 +798,45 @@ int mmmot_match_dets(const double* det_xywh, const double* gt_xywh, const int* g
                      const int* frames, int NF, int car_code, int dontcare_code, double max_iou, int max_n, int* det_id,
                      int* det_cls, void* stream);
 
+/* Adam step of every tensor of an optimizer in ONE launch (torch.optim.Adam's single-tensor arithmetic with the fastai
+ * OptimWrapper's decoupled decay folded in; csrc/adam_step.hip), additive in ABI 10.
+ * Multi-tensor apply: `table` holds one row per tensor, `chunks` one int32 (tensor index, chunk index) row per
+ * MMMOT_ADAM_CHUNK elements of a tensor; one workgroup of 256 threads serves one chunk.  With t the tensor's own step
+ * count after increment, its row carries (computed in double on the host, rounded to fp32 once)
+ *   step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), decay = 1 - wd*lr (decoupled decay) or 1,
+ *   l2 = wd (decay added to the gradient) or 0,
+ * and every element goes through, in fp32 with one IEEE operation per step (no FMA contraction):
+ *   p = p * decay (skipped when decay == 1);  g' = g + l2 * p (skipped when l2 == 0);  m = m + (1 - beta1) * (g' - m);
+ *   v = v * beta2 + (1 - beta2) * g' * g';  p = p - step_size * (m / (sqrt(v) / bc2_sqrt + eps)).
+ * A row without MMMOT_ADAM_HAS_GRAD is decayed (p = p * decay) and nothing else of it is read or written.  NaN and Inf
+ * propagate.  16-byte loads and stores where the row's four bases are 16-byte aligned (p alone for a row without a
+ * gradient), one element per access otherwise.  Every element is read and written by exactly one lane: the result does
+ * not depend on the chunk geometry or on the order of either table.  A chunk row that names no tensor of the table or
+ * starts behind its tensor's end touches nothing.  The tensors must not overlap.
+ * Returns MMMOT_EINVAL before any launch on a null or misaligned table, n_tensors < 1, n_chunks < 1, a beta outside
+ * [0, 1), or an eps that is negative, infinite or above FLT_MAX (NaN included for all three). */
+#define MMMOT_ADAM_CHUNK 4096
+#define MMMOT_ADAM_HAS_GRAD 1
+typedef struct mmmot_adam_row {
+  float* p;        /* parameter, updated in place */
+  const float* g;  /* gradient (not read without MMMOT_ADAM_HAS_GRAD) */
+  float* m;        /* exp_avg, updated in place */
+  float* v;        /* exp_avg_sq, updated in place */
+  long long numel;
+  float step_size, bc2_sqrt, decay, l2;
+  int flags, reserved;
+} mmmot_adam_row; /* 64 bytes */
+int mmmot_adam_step(const mmmot_adam_row* table, int n_tensors, const int* chunks, int n_chunks, double beta1,
+                    double beta2, double eps, void* stream);
+/* MMMOT_ADAM_CHUNK of the library that is loaded. */
+int mmmot_adam_chunk_elems(void);
+/* The chunk table of mmmot_adam_step for tensors of h_numel[0 .. n_tensors) elements, built on the HOST (h_*: host
+ * pointers; it depends on the sizes only - build and upload it once): *h_count = the number of rows, and, when h_chunks
+ * is given, cap >= *h_count rows of two int32 are written, tensor after tensor.  h_chunks == NULL (cap 0) asks for the
+ * count alone.  Returns MMMOT_EINVAL on a null h_numel / h_count, n_tensors < 1, a numel < 1, cap < the count, or more
+ * than 2^31 - 1 rows. */
+int mmmot_adam_chunks(const long long* h_numel, int n_tensors, int* h_chunks, long long cap, long long* h_count);
+
 /* MFMA fragment-layout self test: C[32][32] = A[32][K] * B[32][K]^T through
  * the same fragment mapping the GEMM kernels use (K % 8 == 0). */
 int mmmot_selftest_mfma(const float* A, const float* B, float* C, int K, void* stream);

@@ -10,7 +10,10 @@ from .modules import (AppearanceNet, NewEndIndicator_v2, PointNet_v1, SkipPool, 
 from .train import TrackingLoss  # noqa: E402,F401  (reference cost.py:134-185; mmmot_amd/train.py)
 from . import labels  # noqa: E402,F401  (reference tracking_model.py:294-351, dataset/common.py:95-111; mmmot_amd/labels.py)
 
-__all__ = ['TrackingLoss', 'labels', 'build_criterion', 'TrackingNet', 'AppearanceNet', 'PointNet_v1', 'SkipPool', 'NewEndIndicator_v2', 'affinity_module',
+from . import optim  # noqa: E402,F401  (reference utils/optim_util.py, learning_schedules_fastai.py; mmmot_amd/optim.py)
+from .optim import build_lr_scheduler, build_optim  # noqa: E402,F401  (reference utils/build_util.py:28-59)
+
+__all__ = ['TrackingLoss', 'labels', 'optim', 'build_optim', 'build_lr_scheduler', 'build_criterion', 'TrackingNet', 'AppearanceNet', 'PointNet_v1', 'SkipPool', 'NewEndIndicator_v2', 'affinity_module',
            'fusion_module_A', 'fusion_module_B', 'fusion_module_C', 'build_model', 'model_kwargs_from_config']
 
 

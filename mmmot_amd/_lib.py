@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('MMMOT_LIB_PATH', os.path.join(_HERE, 'libmmmot_hip.so'))  # override: tools' timing-experiment builds
 SOURCES = ['conv3x3.hip', 'hl16_format.hip', 'conv3x3_hl16_patch.hip', 'gemm_rows.hip', 'gemm_wide.hip',
            'gemm_ares.hip', 'gemm_wres.hip', 'gemm_wreg.hip', 'pn_mlp64.hip', 'gram.hip', 'points_gather.hip', 'crop_resize.hip', 'small_kernels.hip', 'backward.hip', 'train.hip', 'train_vgg.hip', 'gemm_tn_f16.hip',
-           'assign.hip', 'assign_chain.hip', 'track_ids.hip', 'clear_mot.hip', 'align_points.hip', 'labels.hip']
+           'assign.hip', 'assign_chain.hip', 'track_ids.hip', 'clear_mot.hip', 'align_points.hip', 'labels.hip', 'adam_step.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 HIPFLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 
@@ -171,6 +171,11 @@ SIGNATURES = {
     'mmmot_generate_gt': [c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f],
     # det_xywh, gt_xywh, gt_id, gt_name, frames, NF, car_code, dontcare_code, max_iou, max_n, det_id, det_cls, stream
     'mmmot_match_dets': [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_double, c_i, c_f, c_f, c_f],
+    # table, n_tensors, chunks, n_chunks, beta1, beta2, eps, stream
+    'mmmot_adam_step': [c_f, c_i, c_f, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_f],
+    'mmmot_adam_chunk_elems': [],
+    # h_numel, n_tensors, h_chunks, cap, h_count  (host pointers)
+    'mmmot_adam_chunks': [c_f, c_i, c_f, ctypes.c_longlong, c_f],
 }
 
 

@@ -407,6 +407,21 @@ class HipOps:
                                        _iptr(det_id), _iptr(det_cls), self._stream())
         _lib.check(st, 'mmmot_match_dets')
 
+    def adam_step(self, chunks, ptrs, scal, beta1, beta2, eps):
+        """One Adam step of T tensors in one launch; see mmmot_adam_step and mmmot::adam_step (torch_ops.py).  chunks: the
+        device int32 [n, 2] chunk table; ptrs / scal: the step's HOST tables, int64 [T, 6] (p, g, m, v, numel, flags) and
+        float64 [T, 4] (step_size, bc2_sqrt, decay, l2), packed into mmmot_adam_row rows and uploaded here."""
+        from . import torch_ops
+        T = torch_ops.adam_tables(chunks, ptrs, scal, beta1, beta2, eps)
+        self.adam_step_table(torch_ops.adam_pack(ptrs, scal, chunks.device), T, chunks, int(chunks.shape[0]), beta1, beta2,
+                             eps)
+
+    def adam_step_table(self, table, T, chunks, n_chunks, beta1, beta2, eps):
+        """The launch alone, on a packed table: the device uint8 block of T 64-byte mmmot_adam_row rows."""
+        st = self.lib.mmmot_adam_step(_ptr(table, torch.uint8), int(T), _iptr(chunks), int(n_chunks), float(beta1),
+                                      float(beta2), float(eps), self._stream())
+        _lib.check(st, 'mmmot_adam_step')
+
     # ---- training backward of the pairwise block (include/mmmot_hip.h, csrc/backward.hip) -------------------
     def gn_bwd_partial(self, dA, Y, C, sc1, sh1, gamma, beta, relu, tiles, P):
         st = self.lib.mmmot_gn_bwd_partial(_ptr(dA), _ld(dA), _ptr(Y), _ld(Y), C, _ptr(sc1), _ptr(sh1), _ld(sc1),

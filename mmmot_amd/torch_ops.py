@@ -519,3 +519,74 @@ _LIB.define('match_dets(Tensor det_xywh, Tensor gt_xywh, Tensor gt_id, Tensor gt
             'int dontcare, float max_iou) -> Tensor')
 _LIB.impl('match_dets', _match_dets, 'CUDA')
 _LIB.impl('match_dets', _match_dets_meta, 'Meta')
+
+
+# ---- optimizer step (mmmot_amd/optim.py; csrc/adam_step.hip) --------------------------------------------------------
+#   mmmot::adam_step(Tensor chunks, Tensor ptrs, Tensor scal, float beta1, float beta2, float eps) -> ()
+#       One Adam step of T tensors in one launch (mmmot_adam_step).  chunks: the device int32 [n, 2] chunk table
+#       (tensor index, chunk index) of mmmot_adam_chunks - it depends on the sizes only and is uploaded once by its
+#       owner; ptrs: a CPU int64 [T, 6] table (p, g, m, v addresses, numel, flags); scal: a CPU float64 [T, 4] table
+#       (step_size, bc2_sqrt, decay, l2) - host data of THIS step, packed here into the 64-byte rows of mmmot_adam_row
+#       (the doubles are rounded to fp32 once) and uploaded by one pinned asynchronous copy.  Returns nothing: the
+#       tensors behind the addresses are updated in place, which the schema cannot say - the caller (optim.Adam) owns
+#       them, keeps them alive and advances the version counters of the parameters it had written.
+ADAM_ROW = np.dtype([('p', '<u8'), ('g', '<u8'), ('m', '<u8'), ('v', '<u8'), ('numel', '<i8'), ('step_size', '<f4'),
+                     ('bc2_sqrt', '<f4'), ('decay', '<f4'), ('l2', '<f4'), ('flags', '<i4'), ('reserved', '<i4')])
+ADAM_HAS_GRAD = 1
+
+
+def adam_tables(chunks, ptrs, scal, beta1, beta2, eps):
+    """T of an adam_step call; checks what the host can see of its tables (the kernel follows the addresses)."""
+    if chunks.dtype != torch.int32 or chunks.dim() != 2 or chunks.shape[1] != 2 or chunks.shape[0] < 1 or \
+            not chunks.is_contiguous():
+        raise ValueError('mmmot::adam_step: chunks must be a contiguous int32 [n, 2] table with n >= 1')
+    if ptrs.device.type != 'cpu' or ptrs.dtype != torch.int64 or ptrs.dim() != 2 or ptrs.shape[1] != 6 or ptrs.shape[0] < 1:
+        raise ValueError('mmmot::adam_step: ptrs must be a CPU int64 [T, 6] table (p, g, m, v, numel, flags), T >= 1')
+    T = int(ptrs.shape[0])
+    if scal.device.type != 'cpu' or scal.dtype != torch.float64 or tuple(scal.shape) != (T, 4):
+        raise ValueError('mmmot::adam_step: scal must be a CPU float64 [%d, 4] table (step_size, bc2_sqrt, decay, l2)' % T)
+    t = ptrs.numpy()
+    if t[:, 4].min() < 1:
+        raise ValueError('mmmot::adam_step: every tensor needs numel >= 1')
+    has = (t[:, 5] & ADAM_HAS_GRAD) != 0
+    if (t[:, 0] == 0).any() or (t[has, 1:4] == 0).any():
+        raise ValueError('mmmot::adam_step: null address in the tensor table')
+    if (t[:, 0] & 3).any() or (t[has, 1:4] & 3).any():
+        raise ValueError('mmmot::adam_step: an address that is not 4-byte aligned')
+    if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+        raise ValueError('mmmot::adam_step: betas must lie in [0, 1), got (%r, %r)' % (beta1, beta2))
+    if not eps >= 0.0:
+        raise ValueError('mmmot::adam_step: eps must be >= 0, got %r' % (eps,))
+    return T
+
+
+def adam_pack(ptrs, scal, device):
+    """The step's rows (mmmot_adam_row) in one pinned block, on their way to ``device`` by an asynchronous copy (a
+    pageable one would wait for the stream)."""
+    T = int(ptrs.shape[0])
+    host = torch.empty(T * ADAM_ROW.itemsize, dtype=torch.uint8, pin_memory=True)
+    rows = host.numpy().view(ADAM_ROW)
+    t, s = ptrs.numpy(), scal.numpy()
+    for j, k in enumerate(('p', 'g', 'm', 'v', 'numel')):
+        rows[k] = t[:, j]
+    for j, k in enumerate(('step_size', 'bc2_sqrt', 'decay', 'l2')):
+        rows[k] = s[:, j]  # rounded to fp32 here, once
+    rows['flags'] = t[:, 5]
+    rows['reserved'] = 0
+    return host.to(device, non_blocking=True)
+
+
+def _adam_step(chunks, ptrs, scal, beta1, beta2, eps):
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    _ASSOC_OPS[0].adam_step(chunks, ptrs, scal, beta1, beta2, eps)  # checks the tables, packs, uploads, launches
+
+
+def _adam_step_meta(chunks, ptrs, scal, beta1, beta2, eps):
+    return None
+
+
+_LIB.define('adam_step(Tensor chunks, Tensor ptrs, Tensor scal, float beta1, float beta2, float eps) -> ()')
+_LIB.impl('adam_step', _adam_step, 'CUDA')
+_LIB.impl('adam_step', _adam_step_meta, 'Meta')

@@ -5,9 +5,18 @@ ragged ~300 pts/det) and at a cfg2-like sample (N=M=32, 64x64 crops, 512 pts/det
 
     python tools/bench_train.py
     python tools/bench_train.py --labels    # the label step alone on the same samples
+    python tools/bench_train.py --optim     # the optimizer step alone at the full model's 216 tensors
 
 ``--labels`` times mmmot_amd.labels.generate_gt alone instead of the step, class / id tensors and targets on the device
 as in the reference's ``step``.  The reference's own host loop is not timed here: the repository holds no copy of it.
+
+``--optim`` times one optimizer step under ``true_wd`` at the 216 trainable tensors of the network, every one with a
+gradient: (a) the path before optim.Adam - optim.OptimWrapper over torch.optim.Adam, which takes the wrapper's loop of
+one ``mul_`` per parameter and then torch's step - and (b) mmmot_amd.build_optim's wrapper over optim.Adam, one launch.  Wall time with a
+device synchronise inside the timed window, 200 calls behind 20 warm-up calls, three runs of each.  The kernel alone is
+timed with events around 50 back-to-back launches on a prepared table, and launch by launch behind a pass over another
+1 GB (the back-to-back launches find part of their data in the last-level cache), against the 28 bytes an element it
+must move.
 """
 import argparse
 import os
@@ -56,13 +65,114 @@ def time_labels(dev):
             name, times[len(times) // 2] * 1e3, times[0] * 1e3, times[(9 * len(times)) // 10] * 1e3, len(times)))
 
 
+def time_optim(dev):
+    import functools
+    from mmmot_amd import optim, torch_ops
+    from mmmot_amd.ops import HipOps
+    cfg = dict(lr_scheduler=dict(optim='Adam', base_lr=3e-4), weight_decay=0.01, fixed_wd=True)
+
+    def fresh():
+        model = TrackingNet(**dict(bench.BASE_KW, score_fusion_arch='C', affinity_op='minus_abs', softmax_mode='dual_add'))
+        init_module(model, seed=0)
+        model.to(dev)
+        g = torch.Generator(device=dev).manual_seed(3)
+        for p in model.parameters():
+            if p.requires_grad:
+                p.grad = torch.randn(p.shape, generator=g, device=dev) * 1e-3
+        return model
+
+    def timed(step):
+        times = []
+        for it in range(220):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            if it >= 20:
+                times.append(time.perf_counter() - t0)
+        times.sort()
+        return times[len(times) // 2] * 1e3, times[0] * 1e3, times[(9 * len(times)) // 10] * 1e3
+
+    model = fresh()
+    w = optim.build_optim(model, cfg)
+    groups = [g['params'] for g in w.opt.param_groups]
+    n_t, n_el = sum(len(g) for g in groups), sum(p.numel() for g in groups for p in g)
+    print('optimizer step, true_wd: %d tensors in groups of %s, %d elements, %.1f MB to move at 28 B an element' % (
+        n_t, [len(g) for g in groups], n_el, n_el * 28 / 1e6))
+    res = {'a': [], 'b': []}
+    for run in range(3):
+        model_a = fresh()
+        wa = optim.OptimWrapper.create(functools.partial(torch.optim.Adam, betas=(0.9, 0.99)), 3e-4,
+                                       optim.get_layer_groups(model_a), wd=0.01, true_wd=True, bn_wd=True)
+        assert [len(g['params']) for g in wa.opt.param_groups] == [len(g) for g in groups]
+        res['a'].append(timed(wa.step))
+        del model_a, wa
+        model_b = fresh()
+        wb = optim.build_optim(model_b, cfg)
+        res['b'].append(timed(wb.step))
+        del model_b, wb
+        for k, what in (('a', '(a) mul_ loop + torch.optim.Adam'), ('b', '(b) optim.Adam, one launch      ')):
+            print('run %d  %s  median %.3f ms, min %.3f ms, 90th percentile %.3f ms over 200 calls' % ((run + 1, what) + res[k][-1]))
+    med = lambda k: sorted(r[0] for r in res[k])[1]
+    print('median of the three runs: (a) %.3f ms, (b) %.3f ms, (a) / (b) = %.2f' % (med('a'), med('b'), med('a') / med('b')))
+
+    # the kernel alone: the tables of one step, recorded from the optimizer, launched back to back
+    class Recorder:
+        name, dtype = 'recorder', torch.float32
+
+        def adam_step(self, *a):
+            self.args = a
+    rec = Recorder()
+    wr = optim.build_optim(model, cfg, ops=rec)
+    wr.step()
+    chunks, ptrs, scal, b1, b2, eps = rec.args
+    table, chunks = torch_ops.adam_pack(ptrs, scal, dev), chunks.to(dev)
+    ops = HipOps()
+    launch = lambda: ops.adam_step_table(table, int(ptrs.shape[0]), chunks, int(chunks.shape[0]), b1, b2, eps)
+    for _ in range(5):
+        launch()
+    rates = []
+    for run in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(50):
+            launch()
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / 50
+        rates.append(n_el * 28 / (ms * 1e-3) / 1e12)
+        print('kernel run %d: %.4f ms a launch over 50 back-to-back launches of %d workgroups, %.2f TB/s, %.0f %% of the 6.29 TB/s '
+              'copy rate' % (run + 1, ms, int(chunks.shape[0]), rates[-1], 100 * rates[-1] / 6.29))
+    # back-to-back launches find part of their 340 MB in the last-level cache; behind a pass over another 1 GB they do not
+    flush = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+    cold = []
+    for _ in range(12):
+        flush.add_(1.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+        torch.cuda.synchronize()
+        cold.append(e0.elapsed_time(e1))
+    cold = sorted(cold[2:])
+    ms = cold[len(cold) // 2]
+    print('kernel behind a 1 GB cache flush, one launch between two events: median %.4f ms (min %.4f, max %.4f) over 10, '
+          '%.2f TB/s, %.0f %% of the 6.29 TB/s copy rate' % (ms, cold[0], cold[-1], n_el * 28 / (ms * 1e-3) / 1e12,
+                                                           100 * n_el * 28 / (ms * 1e-3) / 1e12 / 6.29))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--optim', action='store_true', help='time the optimizer step alone: torch.optim.Adam under the '
+                    'wrapper against optim.Adam')
     ap.add_argument('--labels', action='store_true', help='time the label step (labels.generate_gt) alone')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     if args.labels:
         return time_labels(dev)
+    if args.optim:
+        return time_optim(dev)
     for name, (N, M, S, pts, ragged) in SHAPES.items():
         model = TrackingNet(**dict(bench.BASE_KW, score_fusion_arch='C', affinity_op='multiply', softmax_mode='none'))
         init_module(model, seed=0)
