@@ -74,8 +74,9 @@ class Engine:
         self.out_of_range_window = None  # (first, last) forward indices of the latest asynchronous detection
         self._busy = threading.Lock()  # see forward()
         self._last_stream = None
-        self._image_token = None  # image_first(): the image branch of the next forward is already in the workspace
-        self._pre_image = None    # ... and the event recorded in front of it (where the LiDAR branch may start from)
+        # image_first(): (key of the image branch that is already in the workspace for the next forward, the event recorded
+        # in front of it - where the LiDAR branch may start from - or None)
+        self._head_start = None
         # f16q8 only: trunk layers (indices into P['vgg'], 1..12) that run the hq8 arithmetic; None = all of them
         # (MMMOT_Q8_LAYERS=all).  The others run f16x3; at a boundary the activation tensor is re-encoded (hq8 <-> hl16,
         # two small kernels).  Default: conv3_1 .. conv5_3 (layers 4..12).  Measured on trained-like statistics
@@ -523,11 +524,8 @@ class Engine:
         # are launched on.  Outputs: det / link / new / end are freshly allocated per call; 'F' and 'cat' are views
         # of the workspace, valid until the next forward of this engine.
         with self._exclusive():
-            pin = getattr(self.ops, 'on_current_stream', None)
-            if pin is None:
-                return self._forward(plan, crops, points, appearance)
             cur = self._follow_stream(next((t for t in (crops, points, appearance) if t is not None), None))
-            with pin(cur):
+            with self._pinned(cur):
                 return self._forward(plan, crops, points, appearance)
 
     @contextlib.contextmanager
@@ -621,7 +619,7 @@ class Engine:
         of `cat`) and the index of the forward they were computed in."""
         with self._exclusive():
             self._check_crops(plan, crops)
-            self._image_token = self._pre_image = None  # `cat` is overwritten: an image branch issued before is gone
+            self.drop_head_start()  # `cat` is overwritten: an image branch issued before is gone
             cur = self._follow_stream(crops)
             self.dev = crops.device
             cat = self.buf('cat', plan.Lt, 1024)
@@ -644,20 +642,25 @@ class Engine:
             cur = self._follow_stream(crops)
             self.dev = crops.device
             cat = self.buf('cat', plan.Lt, 1024)
+            self._head_start = None
             # what was queued before the trunk: the point the LiDAR branch of the coming forward may start from (side stream)
-            self._pre_image = None
+            pre = None
             if cur is not None and self.pn_beside_trunk and not torch.cuda.is_current_stream_capturing():
-                self._pre_image = torch.cuda.Event()
-                self._pre_image.record(cur)
+                pre = torch.cuda.Event()
+                pre.record(cur)
             with self._pinned(cur):
                 self._image_branch(plan, crops, appearance, cat)
-            self._image_token = self._image_key(plan, crops, appearance)
+            self._head_start = (self._image_key(plan, crops, appearance), pre)
+
+    def drop_head_start(self):
+        """forget the image branch image_first() issued: the forward it was meant for does not come, or `cat` is reused"""
+        self._head_start = None
 
     def _forward(self, plan, crops=None, points=None, appearance=None):
         rows = plan.rows
         need_img = (0 in rows) or (2 in rows)
         need_pts = (1 in rows) or (2 in rows)
-        token, self._image_token = self._image_token, None
+        (token, pre), self._head_start = self._head_start or (None, None), None  # taken by this forward, whatever follows
         if appearance is not None:
             self._check_appearance(plan, crops, appearance)
         elif need_img:
@@ -678,7 +681,6 @@ class Engine:
         # all its LDS and registers) - the branches never share a CU, only PointNet's small-grid launches and the
         # uneven tail of a trunk layer leave CUs to the other stream.  Fork / join are events: capturable in a hipGraph.
         side = None
-        pre, self._pre_image = self._pre_image, None
         if (img_done and need_pts and pre is not None and dev.type == 'cuda' and hasattr(self.ops, 'on_stream')
                 and not torch.cuda.is_current_stream_capturing()):
             # the trunk of this forward is already running (image_first): the LiDAR branch goes beside it - it starts from

@@ -9,11 +9,14 @@ the reference key names and ``load_state_dict`` semantics); none of their
 ``forward`` methods is ever called.  All arithmetic happens in
 libmmmot_hip.so through ``Engine``; CPU tensors are rejected (no fallback).
 
-Inference (eval mode) only: the north-star path is the forward.  ``train()`` /
-``eval()`` only record the flag like any ``nn.Module`` (the reference's
-``TrackingModule`` toggles them around validation, tracking_model.py:32-48,
-eval_seq.py:127); a forward in training mode raises - batch-statistics
-BatchNorm, dropout and the backward are not built.
+The north-star path is the eval-mode forward.  ``train()`` / ``eval()`` record
+the flag like any ``nn.Module`` (the reference's ``TrackingModule`` toggles them
+around validation, tracking_model.py:32-48, eval_seq.py:127).  In training mode
+``forward`` is the differentiable forward of mmmot_amd/train.py (batch-statistics
+BatchNorm, backward kernels behind autograd); the batched, single-modality and
+appearance-row entry points stay eval-only and raise.  After an optimizer step
+``refresh_head`` / ``refresh_head_device`` bring the packed head up to date; the
+next eval-mode forward re-packs whatever else was trained.
 """
 import os
 
@@ -23,8 +26,8 @@ import torch.nn as nn
 
 from . import torch_ops
 from .engine import Engine, check_crop_layout
-from .pack import VGG_STAGES, pack_weights
-from .plan import BatchPlan, CropPlan
+from .pack import FUSION_LAYOUT, LINK_LAYOUT, VGG_STAGES, build_head, pack_weights
+from .plan import BatchPlan, CropPlan, PlanCache
 
 
 def _gn(groups, ch):
@@ -302,6 +305,30 @@ def _copy_packed_(dst, src):
     return dst == src
 
 
+class PackSnapshot:
+    """What a live engine was packed from: EVERY parameter and buffer of the model, their versions at packing time, and
+    which of them belong to the head modules (the head's versions alone miss encoder-only training and the
+    'eval, one training step, eval' flow).  The tensor list is kept so that the per-forward check is one list
+    comprehension (25 us), not a module walk (0.4 ms)."""
+
+    def __init__(self, model, heads):
+        head = set()
+        for name in heads:
+            m = getattr(model, name)
+            head.update(id(t) for t in list(m.parameters()) + list(m.buffers()))
+        self.tensors = list(model.parameters()) + list(model.buffers())
+        self.versions = [t._version for t in self.tensors]
+        self.head = [i for i, t in enumerate(self.tensors) if id(t) in head]
+
+    def head_is_current(self):
+        return all(self.tensors[i]._version == self.versions[i] for i in self.head)
+
+    def head_refreshed(self):
+        """the head was packed again from the live tensors; the encoders keep their versions"""
+        for i in self.head:
+            self.versions[i] = self.tensors[i]._version
+
+
 class GraphedForward:
     """See ``TrackingNet.capture``."""
 
@@ -420,14 +447,16 @@ class TrackingNet(nn.Module):
         self._ops = None       # operator backend (HipOps unless a test injects another)
         self._engine = None
         self._engine_key = None
-        self._plans = {}
-        self._img_plans = {}   # image-only plans of forward()'s trunk-first launch, keyed by (frame counts, crop side)
-        self._crop_plans = {}  # CropPlans of encode_appearance, keyed by (crops, crop side, device)
+        self._plans = PlanCache(64)        # BatchPlans of the reference-shaped call, keyed by the whole sample layout
+        self._img_plans = PlanCache(256)   # image-only plans of forward()'s trunk-first launch, by (frame counts, crop side)
+        self._crop_plans = PlanCache(256)  # CropPlans of encode_appearance, keyed by (crops, crop side, device)
+        self._train_plans = PlanCache(os.environ.get('MMMOT_TRAIN_PLAN_CACHE', '8'))  # mmmot_amd/train.py::forward_train
         # forward(): launch the trunk before the point split is read back and the plan is built (MMMOT_IMAGE_FIRST=0: after)
         self.image_first = os.environ.get('MMMOT_IMAGE_FIRST', '1') != '0'
         self.freeze_appearance = False  # training mode: True = frozen eval-mode image features instead of the training trunk
         self._pack_version = 0     # bumped whenever packed weights are REPLACED (captured graphs go stale)
-        self._head_versions = None  # parameter versions the live engine's head was packed from
+        self._packed = None        # PackSnapshot of the live engine
+        self._trained_since_pack = False  # refresh_head_device(): the head's fp16-split copies are stale
 
     # ---- backend / packing ---------------------------------------------------
     def set_ops(self, ops):
@@ -448,44 +477,24 @@ class TrackingNet(nn.Module):
             self._engine = Engine(packed, self._ops, fusion=self.score_fusion_arch, affinity_op=self.affinity_op,
                                   softmax_mode=self.softmax_mode, neg_threshold=self.neg_threshold,
                                   score_arch=self.score_arch, end_mode=self.end_mode, trunk=self.trunk)
-            self._plans = {}
+            self._plans.clear()
             self._pack_version += 1
-            self._head_versions = self._current_head_versions()
-            self._snapshot_versions()
+            self._packed = PackSnapshot(self, self._HEADS)
+            self._trained_since_pack = False
         return self._engine
 
-    def _snapshot_versions(self):
-        """Versions of EVERY parameter and buffer the live engine was packed from (the head's versions alone
-        miss encoder-only training and the 'eval, one training step, eval' flow).  The tensor list is kept so that the
-        per-forward check is one list comprehension (25 us), not a module walk (0.4 ms)."""
-        heads = set()
-        for name in self._HEADS:
-            m = getattr(self, name)
-            heads.update(id(t) for t in list(m.parameters()) + list(m.buffers()))
-        self._packed_tensors = list(self.parameters()) + list(self.buffers())
-        self._packed_is_head = [id(t) in heads for t in self._packed_tensors]
-        self._packed_versions = [t._version for t in self._packed_tensors]
-
     def _packed_is_current(self):
-        return self._engine is None or [t._version for t in self._packed_tensors] == self._packed_versions
+        p = self._packed  # (compared here, not behind another call: this runs in every forward)
+        return self._engine is None or [t._version for t in p.tensors] == p.versions
 
     def _repack_if_trained(self):
         """Eval-mode entry points: everything the inference engine holds (folded BatchNorm, fp16-split copies, folded
         transforms) is stale once any parameter / buffer was modified in place since it was packed - by an optimizer step,
         a training-mode BatchNorm update, or by hand."""
-        if getattr(self, '_trained_since_pack', False) or not self._packed_is_current():
-            self._trained_since_pack = False
+        if self._trained_since_pack or not self._packed_is_current():
             self.invalidate()
 
     _HEADS = ('fusion_module', 'w_det', 'w_link')
-
-    def _current_head_versions(self):
-        # parameters and buffers of the three head modules, in module order (a state_dict() walk costs 15 ms)
-        out = []
-        for name in self._HEADS:
-            m = getattr(self, name)
-            out += [p._version for p in m.parameters()] + [b._version for b in m.buffers()]
-        return tuple(out)
 
     def refresh_head_device(self):
         """What a TRAINING step needs after ``optimizer.step()``: the fp32 packed tensors of fusion_module and w_link
@@ -496,43 +505,23 @@ class TrackingNet(nn.Module):
         next EVAL forward re-packs everything (``_trained_since_pack``)."""
         eng = self.engine()
         with torch.no_grad():
-            fm, lk = self.fusion_module, self.w_link
-            fl = lambda conv: conv.weight.detach().flatten(1)
-            fu = eng.P['fusion']
-            new = {}
-            if self.score_fusion_arch == 'A':
-                new.update(w0=fl(fm.input_w[0]), b0=fm.input_w[0].bias, g0=fm.input_w[1].weight, be0=fm.input_w[1].bias)
-            elif self.score_fusion_arch == 'B':
-                for j, m in enumerate((fm.input_p, fm.input_i)):
-                    new.update({'w%d' % j: fl(m[0]), 'b%d' % j: m[0].bias, 'g%d' % j: m[1].weight, 'be%d' % j: m[1].bias})
-            else:
-                for j, (gt, inp) in enumerate(((fm.gate_p, fm.input_p), (fm.gate_i, fm.input_i))):
-                    one, zero = torch.ones_like(inp[1].weight), torch.zeros_like(inp[1].bias)
-                    new.update({'w%d' % j: torch.cat([fl(gt[0]), fl(inp[0])], 0), 'b%d' % j: torch.cat([gt[0].bias, inp[0].bias], 0),
-                                'g%d' % j: torch.cat([one, inp[1].weight], 0), 'be%d' % j: torch.cat([zero, inp[1].bias], 0)})
-            for k, v in new.items():
-                fu[k].copy_(v.detach())
-            ne, c1, P = lk.w_new_end, lk.conv1, eng.P['w_link']
-            pairs = dict(wa=torch.cat([fl(ne.conv0[0]), fl(c1[0])], 0), ba=torch.cat([ne.conv0[0].bias, c1[0].bias], 0),
-                         g_ne0=ne.conv0[1].weight, be_ne0=ne.conv0[1].bias, g1=c1[1].weight, be1=c1[1].bias,
-                         w3=fl(c1[3]), b3=c1[3].bias, g4=c1[4].weight, be4=c1[4].bias, w6=fl(c1[6]), b6=c1[6].bias,
-                         g7=c1[7].weight, be7=c1[7].bias, w9=c1[9].weight.reshape(-1),
-                         nw0=fl(ne.conv1[0]), nb0=ne.conv1[0].bias, ng1=ne.conv1[1].weight, nbe1=ne.conv1[1].bias,
-                         nw3=fl(ne.conv1[3]), nb3=ne.conv1[3].bias, ng4=ne.conv1[4].weight, nbe4=ne.conv1[4].bias,
-                         nw6=ne.conv1[6].weight.reshape(-1))
-            for k, v in pairs.items():
-                P[k].copy_(v.detach())
-            P['b9'], P['nb6'] = float(c1[9].bias.item()), float(ne.conv1[6].bias.item())
-        eng._h16_head_stale = True
+            live = {k: p for name in ('fusion_module', 'w_link') for k, p in getattr(self, name).named_parameters(name)}
+            for section, layout in (('fusion', FUSION_LAYOUT[self.score_fusion_arch]), ('w_link', LINK_LAYOUT)):
+                P = eng.P[section]
+                for k, v in build_head(layout, live.__getitem__).items():
+                    if torch.is_tensor(v):
+                        P[k].copy_(v)
+                    else:
+                        P[k] = v  # the two scalar output biases: one .item() each
         self._trained_since_pack = True
         self._pack_version += 1  # a captured eval graph would replay the stale fp16-split copies
-        self._head_versions = self._current_head_versions()
+        self._packed.head_refreshed()
         return eng
 
     def head_is_current(self):
         """False once a head parameter / buffer was modified in place (``optimizer.step()``, the BatchNorm momentum
         update) after the engine packed it."""
-        return self._engine is not None and self._head_versions == self._current_head_versions()
+        return self._engine is not None and self._packed.head_is_current()
 
     def set_trunk(self, trunk):
         """Arithmetic of the VGG trunk (the other GEMMs follow: f16x3, or exact fp32 with 'f32'):
@@ -549,8 +538,8 @@ class TrackingNet(nn.Module):
 
     def invalidate(self):
         self._engine = None
-        self._plans = {}
-        self.__dict__.pop('_train_plans', None)  # training-mode plans (mmmot_amd/train.py::forward_train)
+        for cache in (self._plans, self._img_plans, self._crop_plans, self._train_plans):
+            cache.clear()
         self._pack_version += 1
 
     def refresh_head(self):
@@ -570,10 +559,7 @@ class TrackingNet(nn.Module):
                 inplace = False
         if not inplace:
             self._pack_version += 1
-        self._head_versions = self._current_head_versions()
-        for i, t in enumerate(self._packed_tensors):  # the head is current again; the encoders keep their snapshot
-            if self._packed_is_head[i]:
-                self._packed_versions[i] = t._version
+        self._packed.head_refreshed()
         return eng
 
     def _apply(self, fn, *a, **k):
@@ -652,11 +638,7 @@ class TrackingNet(nn.Module):
         crops = crops.contiguous()
         eng = self.engine()
         key = (int(crops.shape[0]), S, str(crops.device))
-        plan = self._crop_plans.get(key)
-        if plan is None:
-            if len(self._crop_plans) > 256:
-                self._crop_plans.clear()
-            plan = self._crop_plans[key] = CropPlan(key[0], S, crops.device)
+        plan = self._crop_plans.get(key, lambda: CropPlan(key[0], S, crops.device))
         if eng.ops.name == 'hip':
             rows = torch.ops.mmmot.encode_appearance(crops, torch_ops.engine_handle(eng), torch_ops.plan_handle(plan))
         else:
@@ -678,7 +660,7 @@ class TrackingNet(nn.Module):
         eng = self._engine
         pv, serial, trunk, fwd, n_events = rows.stamp
         if (self.training or eng is None or pv != self._pack_version or eng.serial != serial or eng.trunk != trunk
-                or getattr(self, '_trained_since_pack', False) or not self._packed_is_current()):
+                or self._trained_since_pack or not self._packed_is_current()):
             return False
         eng.guard.settle(upto=fwd)
         return eng.trunk == trunk and len(eng.range_events) == n_events
@@ -742,15 +724,13 @@ class TrackingNet(nn.Module):
         eng = self.engine()
         if eng.ops.name != 'hip':
             return False
-        key = (tuple(fc), S, str(crops.device))
-        plan_img = self._img_plans.get(key)
-        if plan_img is None:
-            if len(self._img_plans) > 256:
-                self._img_plans.clear()
-            plan_img = BatchPlan([(fc, None)], S, crops.device, rows=(0,), use_points=False)
-            self._img_plans[key] = plan_img
-        eng.image_first(plan_img, crops, appearance)
+        eng.image_first(self._image_plan(fc, S, crops.device), crops, appearance)
         return True
+
+    def _image_plan(self, fc, S, dev):
+        """the image-only plan of Engine.image_first: its tables depend on the frame counts and the crop side only"""
+        return self._img_plans.get((tuple(fc), S, str(dev)),
+                                   lambda: BatchPlan([(fc, None)], S, dev, rows=(0,), use_points=False))
 
     def _split_behind_trunk(self, ps_t, fc, S, crops, appearance=None):
         """The point split (device tensor) is needed on the host to build the plan; the trunk is not waiting for it.  Copy it
@@ -774,14 +754,7 @@ class TrackingNet(nn.Module):
         with torch.cuda.stream(side):
             host[:n].copy_(ps_t.detach(), non_blocking=True)
             ev.record(side)
-        key = (tuple(fc), S, str(dev))
-        plan_img = self._img_plans.get(key)
-        if plan_img is None:
-            if len(self._img_plans) > 256:
-                self._img_plans.clear()
-            plan_img = BatchPlan([(fc, None)], S, dev, rows=(0,), use_points=False)
-            self._img_plans[key] = plan_img
-        eng.image_first(plan_img, crops, appearance)
+        eng.image_first(self._image_plan(fc, S, dev), crops, appearance)
         ev.synchronize()
         return host[:n].numpy().astype(np.int64)
 
@@ -828,28 +801,25 @@ class TrackingNet(nn.Module):
             return self._forward_rows_tail(fc, ps, S, rows, need_pts, crops, points, dets, beside, appearance)
         except BaseException:
             if beside and self._engine is not None:  # the image branch that was issued belongs to no forward any more
-                self._engine._image_token = None
-                self._engine._pre_image = None
+                self._engine.drop_head_start()
             raise
 
     def _forward_rows_tail(self, fc, ps, S, rows, need_pts, crops, points, dets, beside, appearance=None):
         dev = points.device if points is not None else dets.device
         key = (tuple(fc), None if ps is None else ps.tobytes(), S, rows, str(dev))
-        plan = self._plans.get(key)
-        if plan is None:
-            if len(self._plans) > 64:
-                self._plans.clear()
-            if beside:
-                # the plan's tables are uploaded on the engine's side stream - the stream the LiDAR branch will run on -
-                # instead of behind the trunk; the main stream (pairwise head) waits for that upload alone
-                side = self.engine()._side_stream(dev)
-                with torch.cuda.stream(side):
-                    plan = BatchPlan([(fc, ps)], S, dev, rows=rows, use_points=need_pts)
-                torch.cuda.current_stream(dev).wait_stream(side)
-            else:
+
+        def build():
+            if not beside:
+                return BatchPlan([(fc, ps)], S, dev, rows=rows, use_points=need_pts)
+            # the plan's tables are uploaded on the engine's side stream - the stream the LiDAR branch will run on -
+            # instead of behind the trunk; the main stream (pairwise head) waits for that upload alone
+            side = self.engine()._side_stream(dev)
+            with torch.cuda.stream(side):
                 plan = BatchPlan([(fc, ps)], S, dev, rows=rows, use_points=need_pts)
-            self._plans[key] = plan
-        res, tail = self._forward_batch(plan, crops, points, appearance)
+            torch.cuda.current_stream(dev).wait_stream(side)
+            return plan
+
+        res, tail = self._forward_batch(self._plans.get(key, build), crops, points, appearance)
         det, links, new, end = res[0]
         trans = self.trans() if need_pts else None
         return (det, links, new, end, trans), tail

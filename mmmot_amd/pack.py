@@ -166,6 +166,59 @@ VGG_STAGES = [
 ]
 
 
+# ---- the head's packed layout: P['fusion'] (modes A / B / C) and P['w_link'] ----
+# packed key -> (how, reference-keyed sources ...):
+#   'mat'   every source flattened to [N][K], concatenated along 0 (weights that consume the same input, stacked along N);
+#   'vec'   every source reshaped to a vector, concatenated along 0; a number stands for a constant vector as long as the
+#           source behind it (fusion C: the gate rows pass the GroupNorm of the input rows with gain one, shift zero);
+#   'float' the python float of a one-element tensor (the rowdot kernels take their output bias by value).
+def _conv_norm(w, b, g, be, conv, norm):
+    return {w: ('mat', conv + '.weight'), b: ('vec', conv + '.bias'),
+            g: ('vec', norm + '.weight'), be: ('vec', norm + '.bias')}
+
+
+def _gated(j, gate, inp):
+    gate, inp = 'fusion_module.%s.' % gate, 'fusion_module.%s.' % inp
+    return {'w%d' % j: ('mat', gate + '0.weight', inp + '0.weight'), 'b%d' % j: ('vec', gate + '0.bias', inp + '0.bias'),
+            'g%d' % j: ('vec', 1.0, inp + '1.weight'), 'be%d' % j: ('vec', 0.0, inp + '1.bias')}
+
+
+_FM, _WL, _NE = 'fusion_module.', 'w_link.conv1.', 'w_link.w_new_end.'
+FUSION_LAYOUT = {
+    'A': _conv_norm('w0', 'b0', 'g0', 'be0', _FM + 'input_w.0', _FM + 'input_w.1'),           # w0 [512][1024]
+    # NB reference naming trap: *_p is applied to feats[:1] = IMAGE
+    'B': {**_conv_norm('w0', 'b0', 'g0', 'be0', _FM + 'input_p.0', _FM + 'input_p.1'),
+          **_conv_norm('w1', 'b1', 'g1', 'be1', _FM + 'input_i.0', _FM + 'input_i.1')},
+    'C': {**_gated(0, 'gate_p', 'input_p'), **_gated(1, 'gate_i', 'input_i')},                # w0, w1 [1024][512]
+}
+LINK_LAYOUT = {
+    'wa': ('mat', _NE + 'conv0.0.weight', _WL + '0.weight'),                                   # [1024][512]
+    'ba': ('vec', _NE + 'conv0.0.bias', _WL + '0.bias'),
+    'g_ne0': ('vec', _NE + 'conv0.1.weight'), 'be_ne0': ('vec', _NE + 'conv0.1.bias'),
+    'g1': ('vec', _WL + '1.weight'), 'be1': ('vec', _WL + '1.bias'),
+    **_conv_norm('w3', 'b3', 'g4', 'be4', _WL + '3', _WL + '4'),
+    **_conv_norm('w6', 'b6', 'g7', 'be7', _WL + '6', _WL + '7'),
+    'w9': ('vec', _WL + '9.weight'), 'b9': ('float', _WL + '9.bias'),
+    **_conv_norm('nw0', 'nb0', 'ng1', 'nbe1', _NE + 'conv1.0', _NE + 'conv1.1'),
+    **_conv_norm('nw3', 'nb3', 'ng4', 'nbe4', _NE + 'conv1.3', _NE + 'conv1.4'),
+    'nw6': ('vec', _NE + 'conv1.6.weight'), 'nb6': ('float', _NE + 'conv1.6.bias'),
+}
+
+
+def build_head(layout, get):
+    """The entries of a head layout from ``get(reference key) -> tensor``, in the tensors' own dtype and on their own
+    device: pack_weights hands in fp64 host copies, TrackingNet.refresh_head_device the live fp32 parameters."""
+    out = {}
+    for k, (how, *src) in layout.items():
+        if how == 'float':
+            out[k] = float(get(src[0]).item())
+            continue
+        ts = [s if isinstance(s, float) else get(s).flatten(1) if how == 'mat' else get(s).reshape(-1) for s in src]
+        ts = [torch.full_like(ts[i + 1], t) if isinstance(t, float) else t for i, t in enumerate(ts)]
+        out[k] = ts[0] if len(ts) == 1 else torch.cat(ts, 0)
+    return out
+
+
 def pack_weights(sd, fusion, device, eps=1e-5):
     """sd: reference-keyed state_dict (TrackingNet).  Returns dict of fp32 device tensors."""
     f32 = lambda t: t.to(torch.float32).contiguous().to(device)
@@ -250,31 +303,17 @@ def pack_weights(sd, fusion, device, eps=1e-5):
         pn['bec2'] = f32(_d(sd['point_net.bn2.bias']))
         P['pointnet'] = pn
 
-    # ---- fusion ------------------------------------------------------------
-    fm = 'fusion_module.'
-    C = 512
-    fu = dict(mode=fusion)
-    cw = lambda name: _d(sd[name]).flatten(1)
-    if fusion == 'A' and fm + 'input_w.0.weight' in sd:
-        fu['w0'] = f32(cw(fm + 'input_w.0.weight'))              # [512][1024]
-        fu['b0'] = f32(_d(sd[fm + 'input_w.0.bias']))
-        fu['g0'] = f32(_d(sd[fm + 'input_w.1.weight']))
-        fu['be0'] = f32(_d(sd[fm + 'input_w.1.bias']))
-    elif fusion == 'B' and fm + 'input_p.0.weight' in sd:
-        # NB reference naming trap: *_p is applied to feats[:1] = IMAGE
-        for j, nm in enumerate(('input_p', 'input_i')):
-            fu['w%d' % j] = f32(cw(fm + nm + '.0.weight'))
-            fu['b%d' % j] = f32(_d(sd[fm + nm + '.0.bias']))
-            fu['g%d' % j] = f32(_d(sd[fm + nm + '.1.weight']))
-            fu['be%d' % j] = f32(_d(sd[fm + nm + '.1.bias']))
-    elif fusion == 'C' and fm + 'gate_p.0.weight' in sd:
-        for j, (gn, inn) in enumerate((('gate_p', 'input_p'), ('gate_i', 'input_i'))):
-            fu['w%d' % j] = f32(torch.cat([cw(fm + gn + '.0.weight'), cw(fm + inn + '.0.weight')], 0))  # [1024][512]
-            fu['b%d' % j] = f32(torch.cat([_d(sd[fm + gn + '.0.bias']), _d(sd[fm + inn + '.0.bias'])], 0))
-            one, zero = torch.ones(C, dtype=torch.float64), torch.zeros(C, dtype=torch.float64)
-            fu['g%d' % j] = f32(torch.cat([one, _d(sd[fm + inn + '.1.weight'])], 0))
-            fu['be%d' % j] = f32(torch.cat([zero, _d(sd[fm + inn + '.1.bias'])], 0))
-    P['fusion'] = fu
+    # ---- fusion, w_link: pure data movement, written down once (FUSION_LAYOUT / LINK_LAYOUT) ----
+    def head(layout):
+        """the entries of a head layout from `sd` in fp64, rounded once to fp32; none when sd lacks the module"""
+        if not all(s in sd for _, *src in layout.values() for s in src if isinstance(s, str)):
+            return {}
+        return {k: f32(v) if torch.is_tensor(v) else v for k, v in build_head(layout, lambda key: _d(sd[key])).items()}
+
+    P['fusion'] = dict(mode=fusion, **head(FUSION_LAYOUT.get(fusion, {})))
+    lk = head(LINK_LAYOUT)
+    if lk:
+        P['w_link'] = lk
 
     # ---- w_det (BatchNorm1d folded) ---------------------------------------
     if 'w_det.0.weight' in sd:
@@ -285,25 +324,5 @@ def pack_weights(sd, fusion, device, eps=1e-5):
         P['w_det'] = dict(w0=f32(w0.flatten(1)), b0=f32(b0), w3=f32(w3.flatten(1)), b3=f32(b3),
                           w6=f32(_d(sd['w_det.6.weight']).reshape(-1)), b6=float(sd['w_det.6.bias'].item()))
 
-    # ---- w_link (affinity + new/end) --------------------------------------
-    if 'w_link.conv1.0.weight' in sd:
-        wl = 'w_link.'
-        ne = wl + 'w_new_end.'
-        lk = {}
-        lk['wa'] = f32(torch.cat([cw(ne + 'conv0.0.weight'), cw(wl + 'conv1.0.weight')], 0))   # [1024][512]
-        lk['ba'] = f32(torch.cat([_d(sd[ne + 'conv0.0.bias']), _d(sd[wl + 'conv1.0.bias'])], 0))
-        lk['g_ne0'] = f32(_d(sd[ne + 'conv0.1.weight'])); lk['be_ne0'] = f32(_d(sd[ne + 'conv0.1.bias']))
-        lk['g1'] = f32(_d(sd[wl + 'conv1.1.weight'])); lk['be1'] = f32(_d(sd[wl + 'conv1.1.bias']))
-        lk['w3'] = f32(cw(wl + 'conv1.3.weight')); lk['b3'] = f32(_d(sd[wl + 'conv1.3.bias']))
-        lk['g4'] = f32(_d(sd[wl + 'conv1.4.weight'])); lk['be4'] = f32(_d(sd[wl + 'conv1.4.bias']))
-        lk['w6'] = f32(cw(wl + 'conv1.6.weight')); lk['b6'] = f32(_d(sd[wl + 'conv1.6.bias']))
-        lk['g7'] = f32(_d(sd[wl + 'conv1.7.weight'])); lk['be7'] = f32(_d(sd[wl + 'conv1.7.bias']))
-        lk['w9'] = f32(_d(sd[wl + 'conv1.9.weight']).reshape(-1)); lk['b9'] = float(sd[wl + 'conv1.9.bias'].item())
-        lk['nw0'] = f32(cw(ne + 'conv1.0.weight')); lk['nb0'] = f32(_d(sd[ne + 'conv1.0.bias']))
-        lk['ng1'] = f32(_d(sd[ne + 'conv1.1.weight'])); lk['nbe1'] = f32(_d(sd[ne + 'conv1.1.bias']))
-        lk['nw3'] = f32(cw(ne + 'conv1.3.weight')); lk['nb3'] = f32(_d(sd[ne + 'conv1.3.bias']))
-        lk['ng4'] = f32(_d(sd[ne + 'conv1.4.weight'])); lk['nbe4'] = f32(_d(sd[ne + 'conv1.4.bias']))
-        lk['nw6'] = f32(_d(sd[ne + 'conv1.6.weight']).reshape(-1)); lk['nb6'] = float(sd[ne + 'conv1.6.bias'].item())
-        P['w_link'] = lk
     _add_hl16_copies(P, device)
     return P

@@ -16,6 +16,8 @@ Row spaces (all "position-major", channels contiguous):
   pairs   sum nR*N*M group = (assoc pair, row)      (affinity N x M blocks)
   V       sum nR*(M+N) group = (pair, row, new|end) (new/end heads)
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -336,3 +338,29 @@ class CropPlan:
 
     _crop_segments = BatchPlan._crop_segments
     crop_segments = BatchPlan.crop_segments
+
+
+class PlanCache:
+    """The ``capacity`` most recently used plans by key.  Plans hold device tables, so the bound is on live plans: the
+    least recently used one goes when a new one comes in."""
+
+    def __init__(self, capacity):
+        self.capacity = max(int(capacity), 1)
+        self._plans = collections.OrderedDict()
+
+    def get(self, key, build):
+        """the plan kept under `key`, else ``build()`` - kept under it and returned"""
+        plan = self._plans.get(key)
+        if plan is not None:
+            self._plans.move_to_end(key)
+            return plan
+        while len(self._plans) >= self.capacity:
+            self._plans.popitem(last=False)
+        plan = self._plans[key] = build()
+        return plan
+
+    def clear(self):
+        self._plans.clear()
+
+    def __len__(self):
+        return len(self._plans)

@@ -214,7 +214,7 @@ def test_every_value_error_comes_before_any_launch():
             with torch.no_grad():
                 call()
         assert log.calls == [], (what, log.calls)
-        assert eng._image_token is None, what
+        assert eng._head_start is None, what
 
 
 def test_meta_kernels_give_the_output_shapes():

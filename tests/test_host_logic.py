@@ -240,9 +240,9 @@ def test_image_first_token_semantics():
         orig = eng.guard.run
         eng.guard.run = lambda *a, **k: (calls.append(1), orig(*a, **k))[1]
         eng.image_first(plan_img, crops)
-        assert len(calls) == 1 and eng._image_token is not None
+        assert len(calls) == 1 and eng._head_start is not None
         got = eng.forward(plan, crops, points)
-        assert len(calls) == 1 and eng._image_token is None          # skipped its own image branch, token consumed
+        assert len(calls) == 1 and eng._head_start is None          # skipped its own image branch, token consumed
         for k in want:
             assert torch.equal(got[k], want[k]), k
         eng.forward(plan, crops, points)
@@ -250,7 +250,7 @@ def test_image_first_token_semantics():
         eng.image_first(plan_img, crops)
         other = crops.clone()
         eng.forward(plan, other, points)
-        assert len(calls) == 4 and eng._image_token is None          # other tensor: not taken, and dropped
+        assert len(calls) == 4 and eng._head_start is None          # other tensor: not taken, and dropped
 
 
 def test_conv1_weight_shift_keeps_weights_and_bias_inside_fp16():

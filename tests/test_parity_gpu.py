@@ -166,7 +166,7 @@ def test_trunk_first_launch_order_is_bitwise_neutral():
     with torch.no_grad():
         assert m.image_first
         first = [m(*to_dev(x)) for x in (a, b, a)]
-        assert m.engine()._image_token is None  # consumed by the forward it was issued for
+        assert m.engine()._head_start is None  # consumed by the forward it was issued for
         m.image_first = False
         plain = [m(*to_dev(x)) for x in (a, b, a)]
     for (d1, l1, n1, e1, _), (d2, l2, n2, e2, _) in zip(first, plain):

@@ -73,7 +73,7 @@ def test_training_forward_refuses_uint8_crops_first():
     m.train()
     with pytest.raises(ValueError, match='uint8'):
         m(u8, info, ds)
-    assert log.calls == [] and m.__dict__.get('_train_plans') is None, 'work was queued before the check'
+    assert log.calls == [] and len(m._train_plans) == 0, 'work was queued before the check'
     m.eval()
 
 
