@@ -738,6 +738,26 @@ int mmmot_set_chain_variant(int variant);
 int mmmot_track_ids(const float* blocks, const int* pairs, const int* out_off, const int* frame_idx, int B, int max_nm,
                     int* state, int* ids_out, void* stream);
 
+/* Track IDs from the assignments of WINDOWS of 2 .. 8 frames (assign_det_id + align_id on len(det_split) frames;
+ * csrc/track_chain_ids.hip), additive in ABI 10.  One workgroup walks the B CONSECUTIVE windows of ONE sequence in order;
+ * queued behind mmmot_associate_chains it reads that call's `out` / `chains` / `out_off` as they are.
+ *   blocks: fp32, window c's [det L | new L | end L | link_0 | .. | link_{T-2}] at out_off[c] (0 / 1 values);
+ *   chains: int32 [B][11] (T, score offset, link offset, n_0 .. n_7), only T and n_0 .. n_{T-1} are read, 2 <= T <= 8,
+ *   0 <= n_t <= max_n <= 512 (max_n <= 128: one wave, above: four; same results);
+ *   frame_idx: int32 [B][8], the frame indices (>= 0) of each window's T frames;
+ *   state: the block of mmmot_track_ids, read and rewritten in full - pair and window launches may alternate on it;
+ *   ids_out: int32, window after window [ids of all L detections, frame after frame | frame_start | last_id after the
+ *   window | stored]: frame_start = 1 when the stored frame was the window's frame 0 (frames 1 .. T-1 are emitted);
+ *   stored = 1 when the window's last frame became the stored frame: always unless frame_start = 1 and frame 1 keeps no
+ *   detection - then the state keeps its frame (only last_id moves) and the window's frames are NOT part of the tracks,
+ *   the reference's behaviour.  For T = 2 the first L + 2 words and the state are those of mmmot_track_ids.
+ * A kept detection of a frame t >= 1 with new != 1 must have exactly one link from frame t-1, from a row with an ID:
+ * otherwise it gets -1 and MMMOT_TRACK_EINFEASIBLE is set.  MMMOT_TRACK_ECONTRACT: a window outside 2 <= T <= 8,
+ * 0 <= n_t <= max_n (the walk stops there) or a stored frame whose detection count differs from the window's frame 0.
+ * Returns MMMOT_EINVAL on a null pointer, B < 1 or max_n outside [0, 512] before any launch. */
+int mmmot_track_chain_ids(const float* blocks, const int* chains, const int* out_off, const int* frame_idx, int B,
+                          int max_n, int* state, int* ids_out, void* stream);
+
 /* CLEAR-MOT evaluation of tracked sequences (reference kitti_devkit/evaluate_tracking.py:393-792
  * compute3rdPartyMetrics; csrc/clear_mot.hip), additive in ABI 10.  Four launches: one workgroup per frame (Hungarian
  * association of ground truth and tracker boxes on c = 1 - IoU gated at min_overlap, the ignore logic and the per-frame

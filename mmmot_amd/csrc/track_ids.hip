@@ -11,35 +11,9 @@
 //   then a kept frame-1 detection with new = 1 takes the next fresh ID in order of j, any other kept one the ID of the
 //   one kept row that links to it.  Case c stores frame 1 only when it keeps a detection (the reference's quirk: the
 //   next pair then runs as case b); a and b always store it.
-#include "common.h"
-
-#define TK_MAXN 512
+#include "track_rank.h"  // TK_MAXN, tk_rank
 
 namespace {
-
-// exclusive count of `p` over the threads before this one, and the workgroup's total (every thread calls it)
-template <int NW>
-__device__ __forceinline__ int tk_rank(bool p, int& total, int* red) {
-  const unsigned long long b = __ballot(p);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int r = __popcll(b & ((1ull << lane) - 1ull));
-  if (NW == 1) {
-    total = __popcll(b);
-    return r;
-  }
-  if (lane == 0) red[wv] = __popcll(b);
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    const int c = red[w];
-    before += w < wv ? c : 0;
-    all += c;
-  }
-  __syncthreads();  // red is free for the next call
-  total = all;
-  return r + before;
-}
 
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void track_ids_kernel(const float* __restrict__ blocks,

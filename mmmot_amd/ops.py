@@ -378,6 +378,14 @@ class HipOps:
                                       _iptr(state), _iptr(ids_out), self._stream())
         _lib.check(st, 'mmmot_track_ids')
 
+    def track_chain_ids(self, blocks, chains, out_off, frame_idx, B, max_n, state, ids_out):
+        """Track IDs of B consecutive windows (2 .. 8 frames) of one sequence from their solver blocks; see
+        mmmot_track_chain_ids.  chains / out_off / frame_idx / state / ids_out: int32 device tensors; state is updated in
+        place."""
+        st = self.lib.mmmot_track_chain_ids(_ptr(blocks), _iptr(chains), _iptr(out_off), _iptr(frame_idx), int(B),
+                                            int(max_n), _iptr(state), _iptr(ids_out), self._stream())
+        _lib.check(st, 'mmmot_track_chain_ids')
+
     def clear_mot(self, boxes, nG, nT, nD, frames, NF, g_attr, t_attr, traj_off, traj_obj, NTr, seq_off, S, params,
                   frame_d, frame_i, gt_out, traj_i, seq_d, seq_i):
         """CLEAR-MOT evaluation of S sequences in four launches; see mmmot_clear_mot.  boxes / frame_d / seq_d: fp64

@@ -49,6 +49,19 @@ All orders and modes share two steps.  ``queue_hand_off`` queues what the mode a
 or a batch of pairs and returns a tracker_glue.HandOff; ``finish_hand_off`` is its host copy, one PairResult (scores,
 assignment, ids) per pair, and ``_deliver`` turns a PairResult into the callbacks, ``stats`` and the returned shape.
 ``run`` is one loop (``_run_pairs``) with or without cached rows; ``run_offline`` hands off a batch of pairs at a time.
+
+Windows (``SequencePipeline(window=T)``, 3 <= T <= 8): the model scores T frames at once and the chain
+solver (association.associate_chain) decides them together, so a weak detection that both neighbours support can
+stay.  Windows start at frames 0, T-1, 2 (T-1), .. - neighbours share one frame - and the last one is shorter (at least
+2 frames) when the sequence does not divide; the reference's dataset drops those trailing frames instead.  Per window:
+one ``TrackingNet.forward`` over the T frames' crops and joined points, ``select_chain`` -> ``queue_solve_chains`` ->
+``fetch``, with the frames of the next window prepared before the host blocks.  With poses frame k of a window is
+aligned to the window's frame 0 by a k-step record (``ego.transform_record([R_1 .. R_k], [T_1 .. T_k], ..)``, the
+accumulation of dataset/test_seq_dataset.py:200-210), all frames of a window in one launch; a frame keeps its raw rows
+for its role as a window's frame 0.  The runs return one entry per window, the callbacks get the index of the window's
+last frame, and ``pipe.tracks`` is filled through ``tracks.merge_chain_tracks``: as in the reference, a window whose
+frame 0 continues the stored frame and whose frame 1 keeps no detection is not stored at all - its frames keep the IDs
+they had (-1 if none) and the next window starts a new stretch of IDs.  ``window=2`` is the pair path above, unchanged.
 """
 import time
 
@@ -58,9 +71,9 @@ import torch
 from .crops import crop_resize_u8
 from . import ego
 from .points import align_points_batched, prep_points_batched
-from .association import select
-from .tracker_glue import queue_scores, queue_solve
-from .tracks import TrackState, merge_tracks
+from .association import select, select_chain
+from .tracker_glue import queue_scores, queue_solve, queue_solve_chains
+from .tracks import TrackState, merge_chain_tracks, merge_tracks, window_starts
 
 
 class FrameFeed:
@@ -103,9 +116,26 @@ def _pair_record(prev_feed, feed):
     return ego.transform_record([R], [T], feed.info['calib/Tr_imu_to_velo'])
 
 
+def _window_records(feeds, steps):
+    """per frame k = 1 .. len(feeds) - 1 of a window the record that aligns it to the window's frame 0: the k steps
+    (R_1, T_1) .. (R_k, T_k) of the frames up to it, as the reference accumulates them, behind ``steps`` - k identity
+    steps, which leave every coordinate as it is, so that one launch of ``steps`` steps serves all frames"""
+    R, T, rec = [], [], []
+    for k in range(1, len(feeds)):
+        r, t = ego.pair_motion(feeds[k - 1].pose, feeds[k].pose)
+        R.append(r)
+        T.append(t)
+        pad = steps - k
+        rec.append(ego.transform_record([np.eye(3)] * pad + R, [np.zeros(3)] * pad + T,
+                                        feeds[k].info['calib/Tr_imu_to_velo']))
+    return np.stack(rec)
+
+
 class SequencePipeline:
     def __init__(self, model, size=224, overlap=True, without_reflectivity=True, reuse_appearance=False, associate=False,
-                 track=False):
+                 track=False, window=2):
+        if not 2 <= int(window) <= 8:
+            raise ValueError('SequencePipeline: window must lie in 2 .. 8 frames, got %s' % (window,))
         if track and not associate:
             raise ValueError('SequencePipeline: track=True needs associate=True (the IDs come from the assignments)')
         self.model, self.size, self.overlap = model, int(size), bool(overlap)
@@ -116,6 +146,7 @@ class SequencePipeline:
         self.reuse_appearance = bool(reuse_appearance)
         self.associate = bool(associate)
         self.track = bool(track)
+        self.window = int(window)  # frames scored and solved together; 2: the pair path
         self.track_state = TrackState(self.dev) if self.track else None
         self.tracks = None         # track=True: per frame the int64 track IDs of its detections (-1: rejected)
         # frames run through the trunk (a frame of a per-pair pair counts once per pair), pairs scored, pairs whose rows
@@ -276,9 +307,97 @@ class SequencePipeline:
         ``ortools_solve`` is called with; ``on_scores(t, scores)`` is where the host solver would run.  associate=True:
         the list of (scores, assignment), assignment as ``ortools_solve`` returns it; ``on_assign(t, assignment)``.
         track=True: ``self.tracks`` is filled as well, ``on_tracks(t, ids)`` per emitted frame."""
-        _check_poses(feeds)
+        moving = _check_poses(feeds)
+        if self.window > 2:
+            if self.reuse_appearance:
+                raise ValueError('SequencePipeline.run: reuse_appearance=True runs the pair-shaped cached-rows forward; '
+                                 'with window > 2 use run_offline, which encodes every frame once')
+            self._check_window_poses(moving)
+            self._start_tracks(feeds)
+            return self._run_windows(feeds, moving, on_scores, on_assign, on_tracks)
         self._start_tracks(feeds)
         return self._run_pairs(feeds, self.reuse_appearance, on_scores, on_assign, on_tracks)
+
+    # ---- windows of 3 .. 8 frames ------------------------------------------------------------------------------------
+    def _check_window_poses(self, moving):
+        if moving and self.window - 1 > ego.MAX_CHAIN:
+            raise ValueError('SequencePipeline: window=%d with poses needs a chain of %d alignment steps; at most %d '
+                             '(window <= %d)' % (self.window, self.window - 1, ego.MAX_CHAIN, ego.MAX_CHAIN + 1))
+
+    def _window_points(self, frames, feeds, moving):
+        """the point rows of a window's frames, joined: frame 0's as they are, frame k's aligned to frame 0 when the
+        sequence has poses - all of them in ONE launch"""
+        pts = [f['points'] for f in frames]
+        if not moving:
+            return torch.cat(pts)
+        rows = np.concatenate([[0], np.cumsum([int(p.shape[0]) for p in pts[1:]])])
+        out = torch.empty((int(pts[0].shape[0]) + int(rows[-1]), int(pts[0].shape[1])), dtype=pts[0].dtype,
+                          device=pts[0].device)
+        out[:pts[0].shape[0]] = pts[0]
+        align_points_batched(torch.cat(pts[1:]), rows, _window_records(feeds, len(frames) - 1), len(frames) - 1,
+                             out=out, out_row0=int(pts[0].shape[0]))
+        return out
+
+    @staticmethod
+    def _window_split(frames):
+        """the point split of the window's joined points: every frame's boundaries behind the frames before it"""
+        split = frames[0]['split']
+        for f in frames[1:]:
+            split = np.concatenate([split, split[-1] + f['split'][1:]])
+        return split
+
+    def launch_window(self, frames, feeds, moving):
+        """queue TrackingNet.forward on the T frames of one window; returns the device outputs (nothing waits)"""
+        self._wait(*frames)
+        crops = torch.cat([f['crops'] for f in frames])
+        split = self._window_split(frames)
+        det_info = {'points': self._window_points(frames, feeds, moving).unsqueeze(0),
+                    'points_split': torch.from_numpy(split.astype(np.float32)).unsqueeze(0)}
+        self.stats['encoded_frames'] += len(frames)
+        with torch.no_grad():
+            return self.model(crops, det_info, [torch.tensor([f['n']]) for f in frames])
+
+    def queue_window_hand_off(self, outs, wins):
+        """Queue the hand-off of ``wins`` = [(first frame, frames)] behind their forward outputs ``outs``; returns the
+        pending hand-off.  associate=True: with the windows' chain solve in one launch; track=True: and the ID launch
+        of these consecutive windows behind it."""
+        tm = self.model.test_mode
+        if not self.associate:
+            return queue_scores(outs, tm)
+        sel = [select_chain(o[0], o[1], o[2], o[3], tm) for o in outs]
+        return queue_solve_chains(sel, [[f['n'] for f in fr] for _, fr in wins], track=self.track_state,
+                                  frame_idx=[list(range(s, s + len(fr))) for s, fr in wins])
+
+    def _deliver_window(self, s, k, r, on_scores, on_assign, on_tracks):
+        """the callbacks and the bookkeeping of the window of k frames from frame s; returns what the run returns"""
+        t = s + k - 1
+        if on_scores is not None:
+            on_scores(t, r.scores)
+        if on_assign is not None and r.assignment is not None:
+            on_assign(t, r.assignment)
+        if r.ids is not None:
+            merge_chain_tracks(self.tracks, range(s, s + k), r.ids[0], r.ids[1], r.ids[3], on_tracks)
+        self.stats['windows'] = self.stats.get('windows', 0) + 1
+        return (r.scores, r.assignment) if self.associate else r.scores
+
+    def _run_windows(self, feeds, moving, on_scores, on_assign, on_tracks):
+        """the windows one after the other, each frame prepared once"""
+        wins = window_starts(len(feeds), self.window)
+        res, frames = [], {}
+        if wins:
+            for t in range(wins[0][1]):
+                frames[t] = self.prepare(feeds[t])
+        for w, (s, k) in enumerate(wins):
+            fr = [frames[t] for t in range(s, s + k)]
+            pending = self.queue_window_hand_off([self.launch_window(fr, feeds[s:s + k], moving)], [(s, fr)])
+            # stage A of the next window's new frames is queued before the host blocks on this window's scores
+            for t in range(s + k, sum(wins[w + 1]) if w + 1 < len(wins) else 0):
+                frames[t] = self.prepare(feeds[t])
+            r = pending.fetch()[0]
+            res.append(self._deliver_window(s, k, r, on_scores, on_assign, on_tracks))
+            for t in range(s, s + k - 1):
+                del frames[t]
+        return res
 
     # ---- appearance rows computed once per frame -----------------------------------------------------------------
     def _current(self, a):
@@ -345,21 +464,28 @@ class SequencePipeline:
         raise RuntimeError('mmmot_amd: the appearance rows of the sequence stayed stale after encoding it three times')
 
     def run_offline(self, feeds, frames_per_encode=16, pairs_per_forward=8, on_scores=None, on_assign=None,
-                    on_tracks=None):
+                    on_tracks=None, windows_per_forward=4):
         """The whole sequence at once (every frame known up front): stage A for every frame, the trunk over the crops of
         `frames_per_encode` frames per launch sequence (throughput-mode occupancy), then the pairs `pairs_per_forward` at
         a time on the rows (forward_batch with appearance rows: PointNet, fusion and the head batched).  Returns the list
         of ``run``; ``on_scores(t, scores)`` is called in pair order once each batch of pairs is on the host.
         associate=True: each batch of pairs is solved in one launch and copied back with its scores in one copy;
-        track=True: one ID launch walks the batch's pairs behind that solve, and the IDs ride in the same copy."""
+        track=True: one ID launch walks the batch's pairs behind that solve, and the IDs ride in the same copy.
+        window > 2: the rows are encoded once per frame all the same, then ``windows_per_forward`` windows at a time
+        run through forward_batch on plans of T-frame samples, with one chain solve and one ID launch per batch."""
         K, B = int(frames_per_encode), int(pairs_per_forward)
-        if K < 1 or B < 1:
-            raise ValueError('frames_per_encode and pairs_per_forward must be >= 1')
+        if K < 1 or B < 1 or int(windows_per_forward) < 1:
+            raise ValueError('frames_per_encode, pairs_per_forward and windows_per_forward must be >= 1')
         moving = _check_poses(feeds)
+        if self.window > 2:
+            self._check_window_poses(moving)
         self._start_tracks(feeds)
         frames = [self.prepare(f) for f in feeds]
         if len(frames) < 2:
             return []
+        if self.window > 2:
+            return self._offline_windows(frames, feeds, moving, K, int(windows_per_forward), on_scores, on_assign,
+                                         on_tracks)
         if moving:  # one align launch per K frames, queued in front of their trunk launches
             for t0 in range(1, len(frames), K):
                 self._align_group(frames, feeds, t0, min(t0 + K, len(frames)))
@@ -376,6 +502,24 @@ class SequencePipeline:
             done = self.finish_hand_off(self.queue_hand_off(outs, pairs))
             for (t, _, _), r in zip(pairs, done):
                 res.append(self._deliver(t, r, on_scores, on_assign, on_tracks))
+        return res
+
+
+    def _offline_windows(self, frames, feeds, moving, K, B, on_scores, on_assign, on_tracks):
+        self._encode_all(frames, K)
+        wins = window_starts(len(frames), self.window)
+        res = []
+        for g0 in range(0, len(wins), B):
+            grp = [(s, frames[s:s + k]) for s, k in wins[g0:g0 + B]]
+            self._wait(*[f for _, fr in grp for f in fr])
+            plan = self.model.make_plan([([f['n'] for f in fr], self._window_split(fr)) for _, fr in grp], self.size)
+            points = torch.cat([self._window_points(fr, feeds[s:s + len(fr)], moving) for s, fr in grp])
+            with torch.no_grad():
+                outs = self.model.forward_batch(plan, None, points,
+                                                appearance=torch.cat([f['rows'].rows for _, fr in grp for f in fr]))
+            done = self.queue_window_hand_off(outs, grp).fetch()
+            for (s, fr), r in zip(grp, done):
+                res.append(self._deliver_window(s, len(fr), r, on_scores, on_assign, on_tracks))
         return res
 
 

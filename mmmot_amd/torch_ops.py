@@ -354,6 +354,79 @@ _LIB.impl('track_ids', _track_ids, 'CUDA')
 _LIB.impl('track_ids', _track_ids_meta, 'Meta')
 
 
+#   mmmot::track_chain_ids(Tensor blocks, Tensor chains, Tensor frame_idx, Tensor(a!) state, int max_n) -> Tensor
+#       Track IDs of B consecutive WINDOWS of 2 .. 8 frames of ONE sequence (mmmot_track_chain_ids): blocks = the `out` of
+#       mmmot::associate_chains for the same chains table (a CPU int32 [B, 11]; any n_t may be 0 here); frame_idx: CPU
+#       int32 [B, 8], the first T of a row are read; state: the block of mmmot::track_ids; max_n: 0 = from the table,
+#       else >= every n_t (above 128 the four-wave kernel runs).  Returns int32 [sum (L + 3)]: per window [ids of its L
+#       detections | frame_start | last_id | stored].
+def track_chain_layout(chains, frame_idx, n_blocks=None):
+    """(total ids_out ints, int64 [B] block offsets, max n_t) of a chain table for mmmot::track_chain_ids; checks it."""
+    if chains.device.type != 'cpu' or chains.dtype != torch.int32 or chains.dim() != 2 or \
+            chains.shape[1] != CHAIN_ROW or chains.shape[0] < 1:
+        raise ValueError('mmmot::track_chain_ids: chains must be a CPU int32 [B, %d] table (T, score offset, link offset, '
+                         'n_0 .. n_7)' % CHAIN_ROW)
+    if frame_idx.device.type != 'cpu' or frame_idx.dtype != torch.int32 or \
+            tuple(frame_idx.shape) != (chains.shape[0], CHAIN_MAX_T):
+        raise ValueError('mmmot::track_chain_ids: frame_idx must be a CPU int32 [B, %d] table' % CHAIN_MAX_T)
+    t = chains.numpy().astype(np.int64)
+    T = t[:, 0]
+    if T.min() < 2 or T.max() > CHAIN_MAX_T:
+        raise ValueError('mmmot::track_chain_ids: every window needs 2 <= T <= %d frames' % CHAIN_MAX_T)
+    used = np.arange(CHAIN_MAX_T)[None, :] < T[:, None]  # entries past frame T-1 are ignored
+    if np.where(used, frame_idx.numpy(), 0).min() < 0:
+        raise ValueError('mmmot::track_chain_ids: frame indices must be >= 0')
+    n = np.where(used, t[:, 3:], 0)
+    if n.min() < 0 or n.max() > MAX_ASSOC:
+        raise ValueError('mmmot::track_chain_ids: every frame needs 0 <= n_t <= %d' % MAX_ASSOC)
+    L = n.sum(1)
+    sizes = 3 * L + (n[:, :-1] * n[:, 1:]).sum(1)
+    off = np.cumsum(sizes) - sizes
+    if int(sizes.sum()) >= 2 ** 31:
+        raise ValueError('mmmot::track_chain_ids: the solver blocks exceed 32-bit offsets')
+    if n_blocks is not None and int(sizes.sum()) > n_blocks:
+        raise ValueError('mmmot::track_chain_ids: a window reads past the end of the solver blocks')
+    return int((L + 3).sum()), torch.from_numpy(off), int(n.max())
+
+
+def _track_chain_ids(blocks, chains, frame_idx, state, max_n):
+    total, off, need = track_chain_layout(chains, frame_idx, int(blocks.numel()))
+    if blocks.dtype != torch.float32 or not blocks.is_contiguous():
+        raise ValueError('mmmot::track_chain_ids: blocks must be a contiguous fp32 device tensor')
+    if state.dtype != torch.int32 or state.numel() != TRACK_STATE_INTS or not state.is_contiguous() or \
+            state.device != blocks.device:
+        raise ValueError('mmmot::track_chain_ids: state must be a contiguous int32 [%d] block on the blocks\' device'
+                         % TRACK_STATE_INTS)
+    if max_n and (max_n < need or max_n > MAX_ASSOC):
+        raise ValueError('mmmot::track_chain_ids: max_n %d does not cover the table (%d)' % (max_n, need))
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    B = int(chains.shape[0])
+    R = CHAIN_ROW
+    host = torch.empty((R + 1 + CHAIN_MAX_T) * B, dtype=torch.int32, pin_memory=True)  # one pinned block, one copy
+    host[:R * B] = chains.reshape(-1)
+    host[R * B:(R + 1) * B] = off
+    host[(R + 1) * B:] = frame_idx.reshape(-1)
+    table = host.to(blocks.device, non_blocking=True)
+    ids = torch.empty(total, dtype=torch.int32, device=blocks.device)
+    if blocks.numel() == 0:  # windows without a detection: never read, but not a null pointer
+        blocks = table.view(torch.float32)
+    _ASSOC_OPS[0].track_chain_ids(blocks, table[:R * B], table[R * B:(R + 1) * B], table[(R + 1) * B:], B,
+                                  max_n or need, state, ids)
+    return ids
+
+
+def _track_chain_ids_meta(blocks, chains, frame_idx, state, max_n):
+    total, _, _ = track_chain_layout(chains, frame_idx)
+    return blocks.new_empty((total,), dtype=torch.int32)
+
+
+_LIB.define('track_chain_ids(Tensor blocks, Tensor chains, Tensor frame_idx, Tensor(a!) state, int max_n) -> Tensor')
+_LIB.impl('track_chain_ids', _track_chain_ids, 'CUDA')
+_LIB.impl('track_chain_ids', _track_chain_ids_meta, 'Meta')
+
+
 # ---- CLEAR-MOT evaluation (mmmot_amd/evaluate.py; csrc/clear_mot.hip) ----------------------------------------------
 #   mmmot::clear_mot(Tensor packed, int[] sizes, float[] params) -> Tensor
 #       Evaluates S sequences (mmmot_clear_mot: frame, trajectory, sequence and total launches).  packed: ONE device

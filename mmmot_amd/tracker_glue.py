@@ -11,6 +11,8 @@ with exactly the shapes the solver indexes.  ``predict_assign`` also solves the 
 A sequence queues before it waits: ``queue_solve`` (solve, and the track IDs with ``track=``) and ``queue_scores``
 (scores only) return a ``HandOff``, and ``HandOff.fetch()`` is the host copy, a list with one ``PairResult`` (scores,
 assignment, ids) per pair.  ``unpack_hand_off`` is the host-only reading of the copied buffer's layout.
+``queue_solve_chains`` is the same for WINDOWS of 2 .. 8 frames (one chain solve and one ID launch per batch of
+windows); its ``ChainHandOff.fetch()`` gives one ``ChainResult`` per window.
 """
 from collections import namedtuple
 
@@ -18,7 +20,7 @@ import torch
 
 from .association import (associate, chain_block_size, chain_of, chains_table, pairs_table, select, select_chain,
                           split_of, unpack, unpack_chain)
-from .tracks import queue_ids, split_ids
+from .tracks import queue_chain_ids, queue_ids, split_chain_ids, split_ids
 
 # one pair on the host: scores as ``scores_for_solver`` returns them, assignment as ``ortools_solve`` does, ids =
 # (ids0, ids1, frame_start, last_id) of ``tracks.split_ids``; None where the stage was not asked for
@@ -125,6 +127,78 @@ def queue_solve(selected, splits, track=None, frame_idx=None):
         return HandOff((splits, S, K, 0), torch.cat([buf, out]))
     ids = queue_ids(track, out, splits, frame_idx)
     return HandOff((splits, S, K, ids.numel()), torch.cat([buf, out, ids.view(torch.float32)]))  # bits, not values
+
+
+# one window on the host: scores (det L, [link 1 x n_t x n_{t+1} ...], new L, end L), assignment as ``ortools_solve``
+# returns it for the window, ids = (ids_per_frame, frame_start, last_id, stored) of ``tracks.split_chain_ids`` or None
+ChainResult = namedtuple('ChainResult', 'scores assignment ids')
+
+
+class ChainHandOff:
+    """B windows queued behind their forward, one ``fetch()`` from the host: the sibling of ``HandOff`` for
+    ``queue_solve_chains``.  ``flat``: the device buffer [det S | new S | end S | links K | solver blocks | n_ids int32
+    bits] (None: every window is empty and no IDs were queued), ``splits``: per window [n_0 .. n_{T-1}]."""
+
+    def __init__(self, splits, flat, S, K, n_ids):
+        self.splits, self.flat, self.S, self.K, self.n_ids = splits, flat, S, K, n_ids
+
+    def fetch(self):
+        """the host copy -> per window a ``ChainResult``: ONE device-to-host copy"""
+        flat = torch.zeros(0) if self.flat is None else self.flat.to('cpu')
+        return unpack_chain_hand_off(flat, self.splits, self.S, self.K, self.n_ids)
+
+
+def unpack_chain_hand_off(flat, splits, S, K, n_ids=0):
+    """Host fp32 buffer of ``queue_solve_chains`` -> per window ``ChainResult`` (views of ``flat``); S = sum of the
+    windows' L, K = sum of their link sizes.  A window without detections has empty scores and an empty assignment."""
+    ids = [None] * len(splits)
+    if n_ids:
+        ids = split_chain_ids(flat[flat.numel() - n_ids:].view(torch.int32).numpy(), splits)
+    res, so, lo, oo = [], 0, 3 * S, 3 * S + K
+    for split, i in zip(splits, ids):
+        L = sum(split)
+        scores = (flat[so:so + L], [], flat[S + so:S + so + L], flat[2 * S + so:2 * S + so + L])
+        for a, b in zip(split[:-1], split[1:]):
+            scores[1].append(flat[lo:lo + a * b].view(1, a, b))
+            lo += a * b
+        n = chain_block_size(split)
+        res.append(ChainResult(scores, unpack_chain(flat[oo:oo + n], split), i))
+        so += L
+        oo += n
+    return res
+
+
+def queue_solve_chains(selected, splits, track=None, frame_idx=None):
+    """Queue the association of B windows of 2 .. 8 frames behind their forward; nothing waits.  ``selected``: per window
+    the device rows (det L, [link 1 x n_t x n_{t+1} ...], new L, end L) of ``association.select_chain``; ``splits``: per
+    window [n_0 .. n_{T-1}].  One ``associate_chains`` launch solves the windows that hold a detection (a frame without
+    detections inside such a window goes to the device with it); a window with L = 0 has nothing to solve and is
+    answered on the host with an empty assignment.  Returns the pending ``ChainHandOff``.
+    ``track`` (a tracks.TrackState; the windows are then CONSECUTIVE windows of its sequence, ``frame_idx`` per window
+    its T frame indices): the ID launch walks ALL B windows behind the solve - the empty ones too, so that the state
+    stays on the device - and its int32 result rides at the end of the same buffer."""
+    splits = [chain_of(s) for s in splits]
+    if not splits:
+        raise ValueError('queue_solve_chains: no windows')
+    full = [(s, sel) for s, sel in zip(splits, selected) if sum(s) > 0]
+    if full:
+        cat = lambda k: torch.cat([sel[k].reshape(-1) for _, sel in full])
+        det, new, end = cat(0), cat(2), cat(3)
+        links = [l.reshape(-1) for _, sel in full for l in sel[1]]
+        S, K = det.numel(), sum(l.numel() for l in links)
+        buf = torch.cat([det, new, end] + links)
+        # the blocks of the solved windows one after the other: with the empty windows' blocks of size 0 between them
+        # this is the layout of ALL windows, which the ID launch reads
+        out, _ = torch.ops.mmmot.associate_chains(buf[0:S], buf[S:2 * S], buf[2 * S:3 * S], buf[3 * S:],
+                                                  chains_table([s for s, _ in full])[0])
+        parts = [buf, out]
+    else:
+        dev = track.buf.device if track is not None else None
+        S, K, out, parts = 0, 0, torch.empty(0, dtype=torch.float32, device=dev), []
+    if track is None:
+        return ChainHandOff(splits, torch.cat(parts) if parts else None, S, K, 0)
+    ids = queue_chain_ids(track, out, splits, frame_idx)
+    return ChainHandOff(splits, torch.cat(parts + [ids.view(torch.float32)]), S, K, ids.numel())  # bits, not values
 
 
 def predict_assign(model, det_imgs, det_info, det_split):

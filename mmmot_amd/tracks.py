@@ -19,12 +19,18 @@ identity is the detection index - the same whenever the boxes within a frame are
 raises or stops in a debugger on an assignment no solver returns (a kept, non-new second-frame detection without
 exactly one link from a kept row), the kernel writes -1, sets the state's error flag, and ``TrackingError`` is raised
 when the result reaches the host.
+
+Windows of 2 .. 8 frames (what ``association.associate_chain`` solves; csrc/track_chain_ids.hip) go the same way on the
+same state: ``track_chain_ids`` is the drop-in, ``queue_chain_ids`` / ``split_chain_ids`` / ``assign_chain_ids`` the
+batched form, ``merge_chain_tracks`` the per-frame list, ``window_starts`` the schedule of a sequence's windows.  One
+behaviour of the reference is kept: a window whose frame 0 continues the stored frame and whose frame 1 keeps nothing
+is not stored (``stored`` = 0) - only ``last_id`` moves, and its frames are not part of the tracks.
 """
 import numpy as np
 import torch
 
 from . import torch_ops
-from .association import pairs_table, split_of
+from .association import chain_of, chains_table, pairs_table, split_of
 from .torch_ops import TRACK_STATE_HEAD, TRACK_STATE_INTS
 
 EINFEASIBLE, ECONTRACT = 1, 2
@@ -133,6 +139,93 @@ def merge_tracks(tracks, t, ids0, ids1, frame_start, on_tracks=None):
     tracks[t] = ids1
     if on_tracks is not None:
         on_tracks(t, ids1)
+
+
+# ---- windows of 2 .. 8 frames (csrc/track_chain_ids.hip) ------------------------------------------------------------
+def window_starts(n_frames, window):
+    """The window schedule as a pure function: [(first frame, frame count)] of the windows of a sequence of
+    ``n_frames`` frames.  Windows of ``window`` frames start at 0, window - 1, 2 (window - 1), .. (neighbours share a
+    frame); the last one is shorter (at least 2 frames) when the sequence does not divide."""
+    n_frames, window = int(n_frames), int(window)
+    if not 2 <= window <= torch_ops.CHAIN_MAX_T:
+        raise ValueError('window must lie in 2 .. %d, got %d' % (torch_ops.CHAIN_MAX_T, window))
+    return [(s, min(window, n_frames - s)) for s in range(0, n_frames - 1, window - 1)]
+
+
+def chain_frame_table(frame_idx, splits):
+    """CPU int32 [B, 8]: per window its T frame indices, padded with 0"""
+    if len(frame_idx) != len(splits):
+        raise ValueError('track_chain_ids: %d frame index rows for %d windows' % (len(frame_idx), len(splits)))
+    t = np.zeros((len(splits), torch_ops.CHAIN_MAX_T), np.int32)
+    for r, (f, s) in enumerate(zip(frame_idx, splits)):
+        f = np.asarray(f, dtype=np.int64).reshape(-1)
+        if len(f) != len(s):
+            raise ValueError('track_chain_ids: window %d has %d frame indices for %d frames' % (r, len(f), len(s)))
+        t[r, :len(f)] = f
+    return torch.from_numpy(t)
+
+
+def queue_chain_ids(state, blocks, splits, frame_idx, max_n=0):
+    """Queue the ID launch for B consecutive windows of the state's sequence; nothing waits.  ``blocks``: the flat
+    device output of mmmot::associate_chains for ``splits`` (per window [n_0 .. n_{T-1}]); ``frame_idx``: per window its
+    T frame indices.  Returns the device int32 buffer [per window: ids L | frame_start | last_id | stored] with the
+    state's error flags appended as the last element."""
+    chains, _ = chains_table(splits)
+    ids = torch.ops.mmmot.track_chain_ids(blocks, chains, chain_frame_table(frame_idx, splits), state.buf, int(max_n))
+    return torch.cat([ids, state.buf[2:3]])
+
+
+def split_chain_ids(flat, splits):
+    """host int32 buffer of ``queue_chain_ids`` -> per window (ids_per_frame: T int64 arrays, frame_start, last_id,
+    stored); raises ``TrackingError`` on the error flags"""
+    flat = np.asarray(flat)
+    check_flags(int(flat[-1]))
+    res, o = [], 0
+    for split in splits:
+        ids = []
+        for n in split:
+            ids.append(flat[o:o + n].astype(np.int64))
+            o += n
+        res.append((ids, int(flat[o]), int(flat[o + 1]), int(flat[o + 2])))
+        o += 3
+    return res
+
+
+def assign_chain_ids(state, blocks, splits, frame_idx, max_n=0):
+    """IDs of B consecutive windows in one launch and one copy: per window (ids_per_frame, frame_start, last_id,
+    stored)."""
+    splits = [[int(n) for n in s] for s in splits]
+    return split_chain_ids(queue_chain_ids(state, blocks, splits, frame_idx, max_n).cpu().numpy(), splits)
+
+
+def track_chain_ids(state, assign_det, assign_links, assign_new, assign_end, det_split, frame_idx):
+    """Drop-in for the reference's ``assign_det_id`` + ``align_id`` on one window of ``len(det_split)`` = 2 .. 8 frames:
+    takes what ``ortools_solve`` / ``association.associate_chain`` returns (CPU or device tensors) and the window's T
+    frame indices.  Returns (ids_per_frame, frame_start): per EMITTED frame a CPU int64 tensor with one ID per detection
+    (-1: rejected) - all T frames, or frames 1 .. T-1 when frame_start = 1.  As in the reference, a window with
+    frame_start = 1 whose frame 1 keeps nothing does not enter the sequence's tracks (``assign_chain_ids`` reports it as
+    ``stored`` = 0; ``merge_chain_tracks`` honours it)."""
+    split = chain_of(det_split)
+    L = sum(split)
+    if assign_det.numel() != L or assign_new.numel() != L or assign_end.numel() != L or \
+            len(assign_links) != len(split) - 1 or \
+            any(l.numel() != a * b for l, a, b in zip(assign_links, split[:-1], split[1:])):
+        raise ValueError('track_chain_ids: assignment does not match det_split %s' % (split,))
+    block = torch.cat([t.detach().reshape(-1).to(torch.float32)
+                       for t in (assign_det, assign_new, assign_end, *assign_links)])
+    ids, start, _, _ = assign_chain_ids(state, block.to(state.buf.device), [split], [frame_idx])[0]
+    return [torch.from_numpy(i) for i in ids[start:]], start
+
+
+def merge_chain_tracks(tracks, frames, ids, frame_start, stored, on_tracks=None):
+    """one window into the per-frame list: ``frames`` = the window's positions in ``tracks``, ``ids`` its per-frame IDs.
+    Frames ``frame_start ..`` are written, and only when ``stored``; the last emission of a frame stands."""
+    if not stored:
+        return
+    for t, i in list(zip(frames, ids))[int(frame_start):]:
+        tracks[t] = i
+        if on_tracks is not None:
+            on_tracks(t, i)
 
 
 def write_kitti_tracks(path, frames, ids, frame_idx=None):

@@ -9,8 +9,13 @@ every mode first.  The scores of the three modes must be bitwise equal.  Writes 
 (track=True; implies --associate): the tracks of the three modes must then be equal too.  --ego gives every frame a pose
 of a synthetic drive (mmmot_amd.synth.ego_poses), so each frame's points are aligned to the previous frame on the device
 (DESIGN section 14); without it the camera stands still and nothing is aligned.
+--window T [T ..] measures the windowed path instead (SequencePipeline(window=T), DESIGN section 12, always with
+association and track IDs): frames/s of ``run`` and ``run_offline`` for the pair path (window 2) and for every T given,
+each repeat running all of them in turn; the two orders of a window must give bitwise equal scores and equal tracks.
+Writes <out>/bench_sequence_windows.json.
 
     python tools/bench_sequence.py --out <dir> [--repeats 3] [--trunk f16x3] [-K 16] [-B 8] [--associate | --track] [--ego]
+    python tools/bench_sequence.py --out <dir> --window 3 5 [--repeats 3] [-K 16] [-B 8] [-W 4] [--ego]
 """
 import argparse
 import json
@@ -36,6 +41,59 @@ def same(a, b):
                                     and torch.equal(x[2], y[2]) and torch.equal(x[3], y[3]) for x, y in zip(a, b))
 
 
+def flat(res):
+    return [t for sc, a in res for t in (sc[0], sc[2], sc[3], *sc[1], a[0], a[2], a[3], *a[1])]
+
+
+def bench_windows(args, model, dev):
+    """frames/s of the windowed path beside the pair path, both orders, in one process"""
+    n = args.frames
+    ndet, feeds = detections(n), sequence_feeds(n, ego=0 if args.ego else None)
+    K, B, W = args.frames_per_encode, args.pairs_per_forward, args.windows_per_forward
+    modes = {}
+    for T in [2] + sorted(set(args.window) - {2}):
+        modes['window%d_run' % T] = (T, lambda p: p.run(feeds))
+        modes['window%d_offline' % T] = (T, lambda p: p.run_offline(feeds, frames_per_encode=K, pairs_per_forward=B,
+                                                                   windows_per_forward=W))
+    make = lambda T: SequencePipeline(model, 224, associate=True, track=True, window=T)
+    first, fps, stats, last_id = {}, {k: [] for k in modes}, {}, {}
+    for name, (T, run) in modes.items():  # untimed: workspace growth, plan caches, first-forward range checks
+        pipe = make(T)
+        res = run(pipe)
+        ref = first.setdefault(T, (flat(res), pipe.tracks))
+        if len(ref[0]) != len(flat(res)) or not all(torch.equal(x, y) for x, y in zip(ref[0], flat(res))):
+            raise SystemExit('%s: scores or assignments differ between the orders' % name)
+        if not all(np.array_equal(x, y) for x, y in zip(ref[1], pipe.tracks)):
+            raise SystemExit('%s: tracks differ between the orders' % name)
+        last_id[T] = int(max(int(x.max()) for x in pipe.tracks if len(x)))
+    for _ in range(args.repeats):
+        for name, (T, run) in modes.items():
+            pipe = make(T)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(pipe)
+            torch.cuda.synchronize()
+            fps[name].append((n - 1) / (time.perf_counter() - t0))
+            stats[name] = dict(pipe.stats)
+    med = {k: float(np.median(v)) for k, v in fps.items()}
+    rec = {
+        'frames_per_s': {k: round(v, 1) for k, v in med.items()},
+        'frames_per_s_runs': {k: [round(x, 1) for x in v] for k, v in fps.items()},
+        'spread': {k: round((max(v) - min(v)) / med[k], 4) for k, v in fps.items()},
+        'orders_bitwise_equal': True, 'ego': bool(args.ego), 'last_track_id': last_id, 'stats': stats,
+        'trunk': model.engine().trunk, 'range_events': len(model.engine().range_events),
+        'frames': n, 'repeats': args.repeats, 'frames_per_encode': K, 'pairs_per_forward': B, 'windows_per_forward': W,
+        'device': torch.cuda.get_device_name(dev),
+        'workload': '%d synthetic KITTI-shaped frames (make_frame(7000 + t, 120000, n_det)), %d-%d detections (mean %.1f), '
+                    '224x224 8-bit crops, Fusion A, overlapped stage A, association and track IDs on; frames/s = '
+                    '(frames - 1) per wall second, median of the repeats' % (n, ndet.min(), ndet.max(), ndet.mean()),
+    }
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_sequence_windows.json'), 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', required=True)
@@ -47,6 +105,9 @@ def main():
     ap.add_argument('--associate', action='store_true')
     ap.add_argument('--track', action='store_true')
     ap.add_argument('--ego', action='store_true', help='a moving camera: align every frame to the one before it')
+    ap.add_argument('--window', type=int, nargs='+', default=None,
+                    help='measure the windowed path for these window lengths (3 .. 8) beside the pair path')
+    ap.add_argument('-W', '--windows-per-forward', type=int, default=4)
     args = ap.parse_args()
     assoc = args.associate or args.track
     kw = dict(associate=assoc, track=True) if args.track else dict(associate=assoc)
@@ -57,6 +118,8 @@ def main():
     init_module(model, seed=0)
     model.eval().to(dev)
     model.set_trunk(args.trunk)
+    if args.window:
+        return bench_windows(args, model, dev)
     n = args.frames
     ndet, feeds = detections(n), sequence_feeds(n, ego=0 if args.ego else None)
     K, B = args.frames_per_encode, args.pairs_per_forward
