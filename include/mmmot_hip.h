@@ -739,7 +739,8 @@ int mmmot_track_ids(const float* blocks, const int* pairs, const int* out_off, c
                     int* state, int* ids_out, void* stream);
 
 /* Track IDs from the assignments of WINDOWS of 2 .. 8 frames (assign_det_id + align_id on len(det_split) frames;
- * csrc/track_chain_ids.hip), additive in ABI 10.  One workgroup walks the B CONSECUTIVE windows of ONE sequence in order;
+ * csrc/track_ids.hip: the kernel body of mmmot_track_ids on the chain table), additive in ABI 10.  One workgroup walks
+ * the B CONSECUTIVE windows of ONE sequence in order;
  * queued behind mmmot_associate_chains it reads that call's `out` / `chains` / `out_off` as they are.
  *   blocks: fp32, window c's [det L | new L | end L | link_0 | .. | link_{T-2}] at out_off[c] (0 / 1 values);
  *   chains: int32 [B][11] (T, score offset, link offset, n_0 .. n_7), only T and n_0 .. n_{T-1} are read, 2 <= T <= 8,

@@ -58,14 +58,9 @@ def pairs_table(splits):
 
 
 def unpack(block, N, M, like=None, link_size=None):
-    """One pair's output block [det L | new L | end L | link N*M] -> the ortools_solve tuple (views of ``block``)."""
-    L = N + M
-    det, new, end = block[0:L], block[L:2 * L], block[2 * L:3 * L]
-    link = block[3 * L:3 * L + N * M].view(1, N, M)
-    if like is not None:
-        det, new, end = (t.view(like.size()).to(like.dtype) for t in (det, new, end))
-        link = link.view(link_size).to(like.dtype)
-    return det, [link], new, end
+    """One pair's output block [det L | new L | end L | link N*M] -> the ortools_solve tuple (views of ``block``): the
+    two-frame case of ``unpack_chain``."""
+    return unpack_chain(block, [N, M], like, None if like is None else [link_size])
 
 
 def _host_unmatched(det_score, link_score, new_score, end_score, N, M):

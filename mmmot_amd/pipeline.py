@@ -45,10 +45,14 @@ launch is queued behind each solve, the sequence's ID state stays on the device,
 Each run fills ``pipe.tracks`` - per frame an int64 array with one track ID per detection, -1 for a rejected one - and
 calls ``on_tracks(t, ids)`` per emitted frame; the runs return what they return without it.
 
-All orders and modes share two steps.  ``queue_hand_off`` queues what the mode asks for behind the forward of one pair
-or a batch of pairs and returns a tracker_glue.HandOff; ``finish_hand_off`` is its host copy, one PairResult (scores,
-assignment, ids) per pair, and ``_deliver`` turns a PairResult into the callbacks, ``stats`` and the returned shape.
-``run`` is one loop (``_run_pairs``) with or without cached rows; ``run_offline`` hands off a batch of pairs at a time.
+All orders and modes, pairs and windows, share their steps.  ``queue_hand_off`` queues what the mode asks for behind the
+forward of one pair or window, or a batch of them, and returns a tracker_glue.HandOff; ``finish_hand_off`` is its host
+copy - the one place the host waits - with one result (scores, assignment, ids) each, and ``_deliver`` turns a result
+into the callbacks, ``stats`` and the returned shape.  ``run`` is one loop (``_run_online``) over
+``tracks.window_starts`` - for ``window=2`` the list of pairs - and ``run_offline`` one loop over batches of them.  A pair
+differs from a window in three places: stage A aligns a frame to the one before it (a window aligns at launch;
+``run_offline`` aligns K frames per launch in front of the trunk), the forward (``launch_pair`` with the stage events,
+``launch_pair_cached`` on cached rows; ``launch_window`` otherwise), and the recompute check of ``reuse_appearance``.
 
 Windows (``SequencePipeline(window=T)``, 3 <= T <= 8): the model scores T frames at once and the chain
 solver (association.associate_chain) decides them together, so a weak detection that both neighbours support can
@@ -61,7 +65,8 @@ accumulation of dataset/test_seq_dataset.py:200-210), all frames of a window in 
 for its role as a window's frame 0.  The runs return one entry per window, the callbacks get the index of the window's
 last frame, and ``pipe.tracks`` is filled through ``tracks.merge_chain_tracks``: as in the reference, a window whose
 frame 0 continues the stored frame and whose frame 1 keeps no detection is not stored at all - its frames keep the IDs
-they had (-1 if none) and the next window starts a new stretch of IDs.  ``window=2`` is the pair path above, unchanged.
+they had (-1 if none) and the next window starts a new stretch of IDs.  ``window=2`` is the pair path above: the pair
+solver, the pair ID entry point, a pair's ``ids`` tuple.
 """
 import time
 
@@ -215,11 +220,6 @@ class SequencePipeline:
                 cur.wait_event(x['ready'])
 
     @staticmethod
-    def _pair_split(a, b):
-        """the point split of the pair's joined points: frame b's boundaries behind frame a's"""
-        return np.concatenate([a['split'], a['split'][-1] + b['split'][1:]])
-
-    @staticmethod
     def _second(b):
         """the points of frame b as the SECOND frame of a pair: aligned to the pair's first frame when the sequence has
         poses"""
@@ -228,7 +228,7 @@ class SequencePipeline:
     @staticmethod
     def _pair_info(a, b):
         points = torch.cat([a['points'], SequencePipeline._second(b)]).unsqueeze(0)
-        split = SequencePipeline._pair_split(a, b)
+        split = SequencePipeline._window_split([a, b])
         # the split is on the host already (prep_points read it back): hand it over as a CPU tensor - no D2H in forward
         return {'points': points, 'points_split': torch.from_numpy(split.astype(np.float32)).unsqueeze(0)}
 
@@ -250,19 +250,23 @@ class SequencePipeline:
             ev.append(('forward', [e0, e1]))
         return out
 
-    def queue_hand_off(self, outs, pairs):
-        """Queue the hand-off of ``pairs`` = [(t, a, b)] (frames a = t-1, b = t) behind their forward outputs ``outs``;
-        returns the pending HandOff.  associate=True: with the pairs' solve in one launch; track=True: and the ID launch
-        of these consecutive pairs behind it."""
+    def queue_hand_off(self, outs, groups):
+        """Queue the hand-off of ``groups`` = [(first frame, frames)], pairs or windows, behind their forward outputs
+        ``outs``; returns the pending HandOff.  associate=True: with the groups' solve in one launch (the pair solver for
+        window = 2, the chain solver above); track=True: and the ID launch of these consecutive groups behind it."""
         tm = self.model.test_mode
         if not self.associate:
             return queue_scores(outs, tm)
-        sel = [select(o[0], o[1], o[2], o[3], tm) for o in outs]
-        return queue_solve(sel, [(a['n'], b['n']) for _, a, b in pairs], track=self.track_state,
-                           frame_idx=[(t - 1, t) for t, _, _ in pairs])
+        if self.window == 2:
+            sel = [select(o[0], o[1], o[2], o[3], tm) for o in outs]
+            return queue_solve(sel, [(a['n'], b['n']) for _, (a, b) in groups], track=self.track_state,
+                               frame_idx=[(s, s + 1) for s, _ in groups])
+        sel = [select_chain(o[0], o[1], o[2], o[3], tm) for o in outs]
+        return queue_solve_chains(sel, [[f['n'] for f in fr] for _, fr in groups], track=self.track_state,
+                                  frame_idx=[list(range(s, s + len(fr))) for s, fr in groups])
 
     def finish_hand_off(self, pending):
-        """the host copy, the one place the host waits for the pairs: their PairResults"""
+        """the host copy, the one place the host waits for the pairs or windows: one result for each"""
         return pending.fetch()
 
     def _start_tracks(self, feeds):
@@ -270,55 +274,73 @@ class SequencePipeline:
             self.track_state.reset()
             self.tracks = [np.full(len(f.dets['bbox']), -1, np.int64) for f in feeds]
 
-    def _deliver(self, t, r, on_scores, on_assign, on_tracks):
-        """the callbacks and the bookkeeping of pair (t-1, t), a PairResult; returns what the run returns for it"""
+    def _deliver(self, s, k, r, on_scores, on_assign, on_tracks):
+        """the callbacks and the bookkeeping of the pair or window of k frames from frame s, a hand-off result; returns
+        what the run returns for it"""
+        t = s + k - 1
         if on_scores is not None:
             on_scores(t, r.scores)
         if on_assign is not None and r.assignment is not None:
             on_assign(t, r.assignment)
         if r.ids is not None:
-            merge_tracks(self.tracks, t, r.ids[0], r.ids[1], r.ids[2], on_tracks)
-        self.stats['pairs'] += 1
+            if self.window == 2:
+                merge_tracks(self.tracks, t, r.ids[0], r.ids[1], r.ids[2], on_tracks)
+            else:
+                merge_chain_tracks(self.tracks, range(s, s + k), r.ids[0], r.ids[1], r.ids[3], on_tracks)
+        key = 'pairs' if self.window == 2 else 'windows'
+        self.stats[key] = self.stats.get(key, 0) + 1
         return (r.scores, r.assignment) if self.associate else r.scores
 
-    def _run_pairs(self, feeds, reuse, on_scores, on_assign, on_tracks):
-        """the pairs one after the other; ``reuse``: on cached appearance rows (the trunk on the new frame only)"""
-        launch = self.launch_pair_cached if reuse else self.launch_pair
-        res = []
-        prev = self.prepare(feeds[0])
-        nxt = self.prepare(feeds[1], feeds[0]) if len(feeds) > 1 else None
-        if reuse and nxt is not None:
-            self.encode([prev])  # frame 0, once
-        for t in range(1, len(feeds)):
-            cur = nxt
+    def _stage_a(self, feeds, t):
+        """stage A of frame t of the sequence; for pairs with its alignment to frame t-1 (windows align at launch)"""
+        return self.prepare(feeds[t], feeds[t - 1] if self.window == 2 and t > 0 else None)
+
+    def _launch(self, fr, feeds, moving):
+        if self.window > 2:
+            return self.launch_window(fr, feeds, moving)
+        return (self.launch_pair_cached if self.reuse_appearance else self.launch_pair)(*fr)
+
+    def _run_online(self, feeds, moving, on_scores, on_assign, on_tracks):
+        """the pairs or windows one after the other, each frame prepared once; with ``reuse_appearance`` (pairs) on
+        cached appearance rows (the trunk on the new frame only)"""
+        reuse = self.reuse_appearance
+        wins = window_starts(len(feeds), self.window)
+        res, frames = [], {}
+        for t in range(wins[0][1] if wins else len(feeds)):
+            frames[t] = self._stage_a(feeds, t)
+        if reuse and wins:
+            self.encode([frames[0]])  # frame 0, once
+        for w, (s, k) in enumerate(wins):
+            fr = [frames[t] for t in range(s, s + k)]
             snap = self.track_state.snapshot() if reuse and self.track else None  # a recomputed pair starts from it again
-            pending = self.queue_hand_off([launch(prev, cur)], [(t, prev, cur)])
-            # stage A of the next frame is queued before the host blocks on this pair's scores
-            nxt = self.prepare(feeds[t + 1], feeds[t]) if t + 1 < len(feeds) else None
+            pending = self.queue_hand_off([self._launch(fr, feeds[s:s + k], moving)], [(s, fr)])
+            # stage A of the next one's new frames is queued before the host blocks on this one's scores
+            for t in range(s + k, sum(wins[w + 1]) if w + 1 < len(wins) else 0):
+                frames[t] = self._stage_a(feeds, t)
             r = self.finish_hand_off(pending)[0]
             if reuse:
-                r = self._checked_scores(prev, cur, r, t, snap)
-            res.append(self._deliver(t, r, on_scores, on_assign, on_tracks))
-            prev = cur
+                r = self._checked_scores(fr[0], fr[1], r, s + 1, snap)
+            res.append(self._deliver(s, k, r, on_scores, on_assign, on_tracks))
+            for t in range(s, s + k - 1):
+                del frames[t]
         return res
 
     def run(self, feeds, on_scores=None, on_assign=None, on_tracks=None):
         """All pairs (t-1, t) of the sequence.  Returns the list of host score tuples (det, [link], new, end) - what
         ``ortools_solve`` is called with; ``on_scores(t, scores)`` is where the host solver would run.  associate=True:
         the list of (scores, assignment), assignment as ``ortools_solve`` returns it; ``on_assign(t, assignment)``.
-        track=True: ``self.tracks`` is filled as well, ``on_tracks(t, ids)`` per emitted frame."""
+        track=True: ``self.tracks`` is filled as well, ``on_tracks(t, ids)`` per emitted frame.  window > 2: one entry
+        per window, the callbacks with the index of the window's last frame."""
         moving = _check_poses(feeds)
         if self.window > 2:
             if self.reuse_appearance:
                 raise ValueError('SequencePipeline.run: reuse_appearance=True runs the pair-shaped cached-rows forward; '
                                  'with window > 2 use run_offline, which encodes every frame once')
             self._check_window_poses(moving)
-            self._start_tracks(feeds)
-            return self._run_windows(feeds, moving, on_scores, on_assign, on_tracks)
         self._start_tracks(feeds)
-        return self._run_pairs(feeds, self.reuse_appearance, on_scores, on_assign, on_tracks)
+        return self._run_online(feeds, moving, on_scores, on_assign, on_tracks)
 
-    # ---- windows of 3 .. 8 frames ------------------------------------------------------------------------------------
+    # ---- the forward of a window of 3 .. 8 frames --------------------------------------------------------------------
     def _check_window_poses(self, moving):
         if moving and self.window - 1 > ego.MAX_CHAIN:
             raise ValueError('SequencePipeline: window=%d with poses needs a chain of %d alignment steps; at most %d '
@@ -356,48 +378,6 @@ class SequencePipeline:
         self.stats['encoded_frames'] += len(frames)
         with torch.no_grad():
             return self.model(crops, det_info, [torch.tensor([f['n']]) for f in frames])
-
-    def queue_window_hand_off(self, outs, wins):
-        """Queue the hand-off of ``wins`` = [(first frame, frames)] behind their forward outputs ``outs``; returns the
-        pending hand-off.  associate=True: with the windows' chain solve in one launch; track=True: and the ID launch
-        of these consecutive windows behind it."""
-        tm = self.model.test_mode
-        if not self.associate:
-            return queue_scores(outs, tm)
-        sel = [select_chain(o[0], o[1], o[2], o[3], tm) for o in outs]
-        return queue_solve_chains(sel, [[f['n'] for f in fr] for _, fr in wins], track=self.track_state,
-                                  frame_idx=[list(range(s, s + len(fr))) for s, fr in wins])
-
-    def _deliver_window(self, s, k, r, on_scores, on_assign, on_tracks):
-        """the callbacks and the bookkeeping of the window of k frames from frame s; returns what the run returns"""
-        t = s + k - 1
-        if on_scores is not None:
-            on_scores(t, r.scores)
-        if on_assign is not None and r.assignment is not None:
-            on_assign(t, r.assignment)
-        if r.ids is not None:
-            merge_chain_tracks(self.tracks, range(s, s + k), r.ids[0], r.ids[1], r.ids[3], on_tracks)
-        self.stats['windows'] = self.stats.get('windows', 0) + 1
-        return (r.scores, r.assignment) if self.associate else r.scores
-
-    def _run_windows(self, feeds, moving, on_scores, on_assign, on_tracks):
-        """the windows one after the other, each frame prepared once"""
-        wins = window_starts(len(feeds), self.window)
-        res, frames = [], {}
-        if wins:
-            for t in range(wins[0][1]):
-                frames[t] = self.prepare(feeds[t])
-        for w, (s, k) in enumerate(wins):
-            fr = [frames[t] for t in range(s, s + k)]
-            pending = self.queue_window_hand_off([self.launch_window(fr, feeds[s:s + k], moving)], [(s, fr)])
-            # stage A of the next window's new frames is queued before the host blocks on this window's scores
-            for t in range(s + k, sum(wins[w + 1]) if w + 1 < len(wins) else 0):
-                frames[t] = self.prepare(feeds[t])
-            r = pending.fetch()[0]
-            res.append(self._deliver_window(s, k, r, on_scores, on_assign, on_tracks))
-            for t in range(s, s + k - 1):
-                del frames[t]
-        return res
 
     # ---- appearance rows computed once per frame -----------------------------------------------------------------
     def _current(self, a):
@@ -437,7 +417,7 @@ class SequencePipeline:
             self.stats['recomputed_pairs'] += 1
             if snap is not None:
                 self.track_state.restore(snap)
-            r = self.finish_hand_off(self.queue_hand_off([self.launch_pair_cached(prev, cur)], [(t, prev, cur)]))[0]
+            r = self.finish_hand_off(self.queue_hand_off([self.launch_pair_cached(prev, cur)], [(t - 1, [prev, cur])]))[0]
         raise RuntimeError('mmmot_amd: the appearance rows of a pair stayed stale after recomputing it three times')
 
     def _encode_all(self, frames, K):
@@ -473,8 +453,8 @@ class SequencePipeline:
         track=True: one ID launch walks the batch's pairs behind that solve, and the IDs ride in the same copy.
         window > 2: the rows are encoded once per frame all the same, then ``windows_per_forward`` windows at a time
         run through forward_batch on plans of T-frame samples, with one chain solve and one ID launch per batch."""
-        K, B = int(frames_per_encode), int(pairs_per_forward)
-        if K < 1 or B < 1 or int(windows_per_forward) < 1:
+        K, B = int(frames_per_encode), int(pairs_per_forward if self.window == 2 else windows_per_forward)
+        if K < 1 or int(pairs_per_forward) < 1 or int(windows_per_forward) < 1:
             raise ValueError('frames_per_encode, pairs_per_forward and windows_per_forward must be >= 1')
         moving = _check_poses(feeds)
         if self.window > 2:
@@ -483,43 +463,25 @@ class SequencePipeline:
         frames = [self.prepare(f) for f in feeds]
         if len(frames) < 2:
             return []
-        if self.window > 2:
-            return self._offline_windows(frames, feeds, moving, K, int(windows_per_forward), on_scores, on_assign,
-                                         on_tracks)
-        if moving:  # one align launch per K frames, queued in front of their trunk launches
+        if moving and self.window == 2:  # one align launch per K frames, queued in front of their trunk launches
             for t0 in range(1, len(frames), K):
                 self._align_group(frames, feeds, t0, min(t0 + K, len(frames)))
-        self._encode_all(frames, K)
-        res = []
-        for g0 in range(1, len(frames), B):
-            pairs = [(t, frames[t - 1], frames[t]) for t in range(g0, min(g0 + B, len(frames)))]
-            both = [f for _, a, b in pairs for f in (a, b)]
-            plan = self.model.make_plan([([a['n'], b['n']], self._pair_split(a, b)) for _, a, b in pairs], self.size)
-            with torch.no_grad():
-                outs = self.model.forward_batch(plan, None,
-                                                torch.cat([p for _, a, b in pairs for p in (a['points'], self._second(b))]),
-                                                appearance=torch.cat([f['rows'].rows for f in both]))
-            done = self.finish_hand_off(self.queue_hand_off(outs, pairs))
-            for (t, _, _), r in zip(pairs, done):
-                res.append(self._deliver(t, r, on_scores, on_assign, on_tracks))
-        return res
-
-
-    def _offline_windows(self, frames, feeds, moving, K, B, on_scores, on_assign, on_tracks):
-        self._encode_all(frames, K)
+        self._encode_all(frames, K)  # waits for stage A of every frame
         wins = window_starts(len(frames), self.window)
         res = []
         for g0 in range(0, len(wins), B):
             grp = [(s, frames[s:s + k]) for s, k in wins[g0:g0 + B]]
-            self._wait(*[f for _, fr in grp for f in fr])
             plan = self.model.make_plan([([f['n'] for f in fr], self._window_split(fr)) for _, fr in grp], self.size)
-            points = torch.cat([self._window_points(fr, feeds[s:s + len(fr)], moving) for s, fr in grp])
+            if self.window == 2:  # aligned in front of the trunk launches
+                points = [p for _, (a, b) in grp for p in (a['points'], self._second(b))]
+            else:
+                points = [self._window_points(fr, feeds[s:s + len(fr)], moving) for s, fr in grp]
             with torch.no_grad():
-                outs = self.model.forward_batch(plan, None, points,
+                outs = self.model.forward_batch(plan, None, torch.cat(points),
                                                 appearance=torch.cat([f['rows'].rows for _, fr in grp for f in fr]))
-            done = self.queue_window_hand_off(outs, grp).fetch()
+            done = self.finish_hand_off(self.queue_hand_off(outs, grp))
             for (s, fr), r in zip(grp, done):
-                res.append(self._deliver_window(s, len(fr), r, on_scores, on_assign, on_tracks))
+                res.append(self._deliver(s, len(fr), r, on_scores, on_assign, on_tracks))
         return res
 
 

@@ -294,14 +294,38 @@ _LIB.impl('associate_chains', _associate_chains, 'CUDA')
 _LIB.impl('associate_chains', _associate_chains_meta, 'Meta')
 
 
+# ---- track IDs (mmmot_amd/tracks.py; csrc/track_ids.hip) -------------------------------------------------------------
 #   mmmot::track_ids(Tensor blocks, Tensor pairs, Tensor frame_idx, Tensor(a!) state, int max_nm) -> Tensor
 #       Track IDs of B consecutive pairs of ONE sequence (mmmot_track_ids) from the solver's output blocks: blocks = the
 #       `out` of mmmot::associate for the same pairs table (a CPU int32 [B, 4]; N or M may be 0 here); frame_idx: CPU
 #       int32 [B, 2]; state: the sequence's device int32 [TRACK_STATE_INTS] block, updated in place; max_nm: 0 = from
 #       the table, else >= every N and M (above 128 the four-wave kernel runs).  Returns int32
 #       [sum (N + M + 2)]: per pair [ids frame 0 | ids frame 1 | frame_start | last_id].
+#   mmmot::track_chain_ids(Tensor blocks, Tensor chains, Tensor frame_idx, Tensor(a!) state, int max_n) -> Tensor
+#       The same for B consecutive WINDOWS of 2 .. 8 frames (mmmot_track_chain_ids): blocks = the `out` of
+#       mmmot::associate_chains for the same chains table (a CPU int32 [B, 11]; any n_t may be 0 here); frame_idx: CPU
+#       int32 [B, 8], the first T of a row are read; max_n: 0 = from the table, else >= every n_t.  Returns int32
+#       [sum (L + 3)]: per window [ids of its L detections | frame_start | last_id | stored].
+#   Both layouts reduce their table to per entry the counts and frame indices ([B, T] with zeros behind an entry's
+#   frames); _track_sizes and _track_launch are the rest, once.
 TRACK_STATE_HEAD = 4
 TRACK_STATE_INTS = TRACK_STATE_HEAD + 512
+
+
+def _track_sizes(op, what, n, frames, tail, n_blocks):
+    """(total ids_out ints, int64 [B] block offsets, max count) from int64 [B, T] counts and frame indices"""
+    if frames.min() < 0:
+        raise ValueError('mmmot::%s: frame indices must be >= 0' % op)
+    if n.min() < 0 or n.max() > MAX_ASSOC:
+        raise ValueError('mmmot::%s: every frame of a %s needs 0 <= n_t <= %d' % (op, what, MAX_ASSOC))
+    L = n.sum(1)
+    sizes = 3 * L + (n[:, :-1] * n[:, 1:]).sum(1)
+    off = np.cumsum(sizes) - sizes
+    if int(sizes.sum()) >= 2 ** 31:
+        raise ValueError('mmmot::%s: the solver blocks exceed 32-bit offsets' % op)
+    if n_blocks is not None and int(sizes.sum()) > n_blocks:
+        raise ValueError('mmmot::%s: a %s reads past the end of the solver blocks' % (op, what))
+    return int((L + tail).sum()), torch.from_numpy(off), int(n.max())
 
 
 def track_layout(pairs, frame_idx, n_blocks=None):
@@ -311,55 +335,9 @@ def track_layout(pairs, frame_idx, n_blocks=None):
         raise ValueError('mmmot::track_ids: pairs must be a CPU int32 [B, 4] table (N, M, score offset, link offset)')
     if frame_idx.device.type != 'cpu' or frame_idx.dtype != torch.int32 or tuple(frame_idx.shape) != (pairs.shape[0], 2):
         raise ValueError('mmmot::track_ids: frame_idx must be a CPU int32 [B, 2] table')
-    if int(frame_idx.min()) < 0:
-        raise ValueError('mmmot::track_ids: frame indices must be >= 0')
-    t = pairs.numpy().astype(np.int64)
-    N, M = t[:, 0], t[:, 1]
-    if np.minimum(N, M).min() < 0 or np.maximum(N, M).max() > MAX_ASSOC:
-        raise ValueError('mmmot::track_ids: every pair needs 0 <= N, M <= %d' % MAX_ASSOC)
-    sizes = 3 * (N + M) + N * M
-    off = np.cumsum(sizes) - sizes
-    if n_blocks is not None and int(sizes.sum()) > n_blocks:
-        raise ValueError('mmmot::track_ids: a pair reads past the end of the solver blocks')
-    return int((N + M + 2).sum()), torch.from_numpy(off), int(np.maximum(N, M).max())
+    return _track_sizes('track_ids', 'pair', pairs.numpy()[:, :2].astype(np.int64), frame_idx.numpy(), 2, n_blocks)
 
 
-def _track_ids(blocks, pairs, frame_idx, state, max_nm):
-    total, off, need = track_layout(pairs, frame_idx, int(blocks.numel()))
-    if state.dtype != torch.int32 or state.numel() != TRACK_STATE_INTS or not state.is_contiguous():
-        raise ValueError('mmmot::track_ids: state must be a contiguous int32 [%d] device block' % TRACK_STATE_INTS)
-    if max_nm and (max_nm < need or max_nm > MAX_ASSOC):
-        raise ValueError('mmmot::track_ids: max_nm %d does not cover the table (%d)' % (max_nm, need))
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
-    B = int(pairs.shape[0])
-    host = torch.empty(7 * B, dtype=torch.int32, pin_memory=True)  # one pinned block, one asynchronous copy
-    host[:4 * B] = pairs.reshape(-1)
-    host[4 * B:5 * B] = off
-    host[5 * B:] = frame_idx.reshape(-1)
-    table = host.to(blocks.device, non_blocking=True)
-    ids = torch.empty(total, dtype=torch.int32, device=blocks.device)
-    _ASSOC_OPS[0].track_ids(blocks, table[:4 * B], table[4 * B:5 * B], table[5 * B:], B, max_nm or need, state, ids)
-    return ids
-
-
-def _track_ids_meta(blocks, pairs, frame_idx, state, max_nm):
-    total, _, _ = track_layout(pairs, frame_idx)
-    return blocks.new_empty((total,), dtype=torch.int32)
-
-
-_LIB.define('track_ids(Tensor blocks, Tensor pairs, Tensor frame_idx, Tensor(a!) state, int max_nm) -> Tensor')
-_LIB.impl('track_ids', _track_ids, 'CUDA')
-_LIB.impl('track_ids', _track_ids_meta, 'Meta')
-
-
-#   mmmot::track_chain_ids(Tensor blocks, Tensor chains, Tensor frame_idx, Tensor(a!) state, int max_n) -> Tensor
-#       Track IDs of B consecutive WINDOWS of 2 .. 8 frames of ONE sequence (mmmot_track_chain_ids): blocks = the `out` of
-#       mmmot::associate_chains for the same chains table (a CPU int32 [B, 11]; any n_t may be 0 here); frame_idx: CPU
-#       int32 [B, 8], the first T of a row are read; state: the block of mmmot::track_ids; max_n: 0 = from the table,
-#       else >= every n_t (above 128 the four-wave kernel runs).  Returns int32 [sum (L + 3)]: per window [ids of its L
-#       detections | frame_start | last_id | stored].
 def track_chain_layout(chains, frame_idx, n_blocks=None):
     """(total ids_out ints, int64 [B] block offsets, max n_t) of a chain table for mmmot::track_chain_ids; checks it."""
     if chains.device.type != 'cpu' or chains.dtype != torch.int32 or chains.dim() != 2 or \
@@ -374,47 +352,50 @@ def track_chain_layout(chains, frame_idx, n_blocks=None):
     if T.min() < 2 or T.max() > CHAIN_MAX_T:
         raise ValueError('mmmot::track_chain_ids: every window needs 2 <= T <= %d frames' % CHAIN_MAX_T)
     used = np.arange(CHAIN_MAX_T)[None, :] < T[:, None]  # entries past frame T-1 are ignored
-    if np.where(used, frame_idx.numpy(), 0).min() < 0:
-        raise ValueError('mmmot::track_chain_ids: frame indices must be >= 0')
-    n = np.where(used, t[:, 3:], 0)
-    if n.min() < 0 or n.max() > MAX_ASSOC:
-        raise ValueError('mmmot::track_chain_ids: every frame needs 0 <= n_t <= %d' % MAX_ASSOC)
-    L = n.sum(1)
-    sizes = 3 * L + (n[:, :-1] * n[:, 1:]).sum(1)
-    off = np.cumsum(sizes) - sizes
-    if int(sizes.sum()) >= 2 ** 31:
-        raise ValueError('mmmot::track_chain_ids: the solver blocks exceed 32-bit offsets')
-    if n_blocks is not None and int(sizes.sum()) > n_blocks:
-        raise ValueError('mmmot::track_chain_ids: a window reads past the end of the solver blocks')
-    return int((L + 3).sum()), torch.from_numpy(off), int(n.max())
+    return _track_sizes('track_chain_ids', 'window', np.where(used, t[:, 3:], 0), np.where(used, frame_idx.numpy(), 0), 3,
+                        n_blocks)
 
 
-def _track_chain_ids(blocks, chains, frame_idx, state, max_n):
-    total, off, need = track_chain_layout(chains, frame_idx, int(blocks.numel()))
+def _track_launch(op, layout, blocks, table, frame_idx, state, max_n):
+    """the op behind both schemas: the layout's checks, the tensors', one pinned block [table | block offsets |
+    frame_idx] in one asynchronous copy, and the launch"""
+    total, off, need = layout(table, frame_idx, int(blocks.numel()))
     if blocks.dtype != torch.float32 or not blocks.is_contiguous():
-        raise ValueError('mmmot::track_chain_ids: blocks must be a contiguous fp32 device tensor')
+        raise ValueError('mmmot::%s: blocks must be a contiguous fp32 device tensor' % op)
     if state.dtype != torch.int32 or state.numel() != TRACK_STATE_INTS or not state.is_contiguous() or \
             state.device != blocks.device:
-        raise ValueError('mmmot::track_chain_ids: state must be a contiguous int32 [%d] block on the blocks\' device'
-                         % TRACK_STATE_INTS)
+        raise ValueError('mmmot::%s: state must be a contiguous int32 [%d] block on the blocks\' device'
+                         % (op, TRACK_STATE_INTS))
     if max_n and (max_n < need or max_n > MAX_ASSOC):
-        raise ValueError('mmmot::track_chain_ids: max_n %d does not cover the table (%d)' % (max_n, need))
+        raise ValueError('mmmot::%s: max_n %d does not cover the table (%d)' % (op, max_n, need))
     if not _ASSOC_OPS:
         from .ops import HipOps
         _ASSOC_OPS.append(HipOps())
-    B = int(chains.shape[0])
-    R = CHAIN_ROW
-    host = torch.empty((R + 1 + CHAIN_MAX_T) * B, dtype=torch.int32, pin_memory=True)  # one pinned block, one copy
-    host[:R * B] = chains.reshape(-1)
-    host[R * B:(R + 1) * B] = off
-    host[(R + 1) * B:] = frame_idx.reshape(-1)
-    table = host.to(blocks.device, non_blocking=True)
+    B = int(table.shape[0])
+    a, b = table.numel(), table.numel() + B
+    host = torch.empty(b + frame_idx.numel(), dtype=torch.int32, pin_memory=True)
+    host[:a] = table.reshape(-1)
+    host[a:b] = off
+    host[b:] = frame_idx.reshape(-1)
+    dev = host.to(blocks.device, non_blocking=True)
     ids = torch.empty(total, dtype=torch.int32, device=blocks.device)
-    if blocks.numel() == 0:  # windows without a detection: never read, but not a null pointer
-        blocks = table.view(torch.float32)
-    _ASSOC_OPS[0].track_chain_ids(blocks, table[:R * B], table[R * B:(R + 1) * B], table[(R + 1) * B:], B,
-                                  max_n or need, state, ids)
+    if blocks.numel() == 0:  # entries without a detection: never read, but not a null pointer
+        blocks = dev.view(torch.float32)
+    getattr(_ASSOC_OPS[0], op)(blocks, dev[:a], dev[a:b], dev[b:], B, max_n or need, state, ids)
     return ids
+
+
+def _track_ids(blocks, pairs, frame_idx, state, max_nm):
+    return _track_launch('track_ids', track_layout, blocks, pairs, frame_idx, state, max_nm)
+
+
+def _track_ids_meta(blocks, pairs, frame_idx, state, max_nm):
+    total, _, _ = track_layout(pairs, frame_idx)
+    return blocks.new_empty((total,), dtype=torch.int32)
+
+
+def _track_chain_ids(blocks, chains, frame_idx, state, max_n):
+    return _track_launch('track_chain_ids', track_chain_layout, blocks, chains, frame_idx, state, max_n)
 
 
 def _track_chain_ids_meta(blocks, chains, frame_idx, state, max_n):
@@ -422,6 +403,9 @@ def _track_chain_ids_meta(blocks, chains, frame_idx, state, max_n):
     return blocks.new_empty((total,), dtype=torch.int32)
 
 
+_LIB.define('track_ids(Tensor blocks, Tensor pairs, Tensor frame_idx, Tensor(a!) state, int max_nm) -> Tensor')
+_LIB.impl('track_ids', _track_ids, 'CUDA')
+_LIB.impl('track_ids', _track_ids_meta, 'Meta')
 _LIB.define('track_chain_ids(Tensor blocks, Tensor chains, Tensor frame_idx, Tensor(a!) state, int max_n) -> Tensor')
 _LIB.impl('track_chain_ids', _track_chain_ids, 'CUDA')
 _LIB.impl('track_chain_ids', _track_chain_ids_meta, 'Meta')

@@ -8,23 +8,25 @@ with exactly the shapes the solver indexes.  ``predict_assign`` also solves the 
 (mmmot_amd.association, the ``ortools_solve`` drop-in) and brings scores and assignment back in one copy;
 ``predict_assign_chain`` is the same for a model of ``seq_len > 2`` (every link block selected, the chain solver).
 
-A sequence queues before it waits: ``queue_solve`` (solve, and the track IDs with ``track=``) and ``queue_scores``
-(scores only) return a ``HandOff``, and ``HandOff.fetch()`` is the host copy, a list with one ``PairResult`` (scores,
-assignment, ids) per pair.  ``unpack_hand_off`` is the host-only reading of the copied buffer's layout.
-``queue_solve_chains`` is the same for WINDOWS of 2 .. 8 frames (one chain solve and one ID launch per batch of
-windows); its ``ChainHandOff.fetch()`` gives one ``ChainResult`` per window.
+A sequence queues before it waits: ``queue_solve`` (pairs: the pair solver, and the track IDs with ``track=``),
+``queue_solve_chains`` (WINDOWS of 2 .. 8 frames: one chain solve and one ID launch per batch of windows) and
+``queue_scores`` (scores only) return a ``HandOff``, and ``HandOff.fetch()`` is the host copy, a list with one result
+(scores, assignment, ids) per pair or window.  The copied buffer has one layout for both, a pair being a window of two
+frames; ``unpack_chain_hand_off`` is its host-only reading and ``unpack_hand_off`` the same with a pair's ``ids`` tuple.
 """
 from collections import namedtuple
 
 import torch
 
 from .association import (associate, chain_block_size, chain_of, chains_table, pairs_table, select, select_chain,
-                          split_of, unpack, unpack_chain)
+                          split_of, unpack_chain)
 from .tracks import queue_chain_ids, queue_ids, split_chain_ids, split_ids
 
-# one pair on the host: scores as ``scores_for_solver`` returns them, assignment as ``ortools_solve`` does, ids =
-# (ids0, ids1, frame_start, last_id) of ``tracks.split_ids``; None where the stage was not asked for
-PairResult = namedtuple('PairResult', 'scores assignment ids')
+# one pair or window on the host: scores (det L, [link 1 x n_t x n_{t+1} ...], new L, end L) as ``scores_for_solver``
+# returns them, assignment as ``ortools_solve`` does, ids = (ids0, ids1, frame_start, last_id) of ``tracks.split_ids``
+# for a pair, (ids_per_frame, frame_start, last_id, stored) of ``tracks.split_chain_ids`` for a window; None where the
+# stage was not asked for
+PairResult = ChainResult = namedtuple('HandOffResult', 'scores assignment ids')
 
 
 def scores_for_solver(det_score, link_scores, new_score, end_score, test_mode):
@@ -53,107 +55,42 @@ def predict_scores(model, det_imgs, det_info, det_split):
 
 
 class HandOff:
-    """B frame pairs queued behind their forward, one ``fetch()`` from the host.  ``flat``: the device buffer still to
-    be copied (None: nothing is left on the device), read by ``unpack_hand_off`` with ``layout`` = (splits, S, K,
-    n_ids).  ``done``: per pair the (scores, assignment) a pair with an empty frame was given on the host at queue time;
-    ``flat`` then holds the IDs alone.  ``outs`` (``queue_scores``): per pair the device outputs of a score-only hand-off."""
+    """B frame pairs or windows queued behind their forward, one ``fetch()`` from the host.  ``flat``: the device buffer
+    still to be copied (None: nothing is left on the device), read by ``unpack_chain_hand_off`` with ``layout`` =
+    (splits, S, K, n_ids); ``pairs``: the entries are pairs, whose ``ids`` come back as ``tracks.split_ids`` gives them.
+    ``done``: per pair the (scores, assignment) a pair with an empty frame was given on the host at queue time; ``flat``
+    then holds the IDs alone.  ``outs`` (``queue_scores``): per entry the device outputs of a score-only hand-off."""
 
-    def __init__(self, layout=None, flat=None, done=None, outs=None, test_mode=0):
+    def __init__(self, layout=None, flat=None, done=None, outs=None, test_mode=0, pairs=True):
         self.layout, self.flat, self.done, self.outs, self.test_mode = layout, flat, done, outs, test_mode
+        self.split_ids = split_ids if pairs else split_chain_ids
 
     def fetch(self):
-        """the host copy -> per pair a ``PairResult``: ONE device-to-host copy of ``flat``; score-only: one per pair"""
+        """the host copy -> per entry a result: ONE device-to-host copy of ``flat``; score-only: one per entry"""
         if self.outs is not None:
             return [PairResult(scores_for_solver(o[0], o[1], o[2], o[3], self.test_mode), None, None) for o in self.outs]
-        flat = None if self.flat is None else self.flat.to('cpu')
+        flat = torch.zeros(0) if self.flat is None else self.flat.to('cpu')
         if self.done is None:
-            return unpack_hand_off(flat, *self.layout)
+            return unpack_chain_hand_off(flat, *self.layout, split_ids=self.split_ids)
         splits, _, _, n_ids = self.layout
-        return [PairResult(sc, asg, i) for (sc, asg), i in zip(self.done, unpack_ids(flat, splits, n_ids))]
+        return [PairResult(sc, asg, i) for (sc, asg), i in zip(self.done, unpack_ids(flat, splits, n_ids, self.split_ids))]
 
 
-def unpack_ids(flat, splits, n_ids):
-    """the last ``n_ids`` elements of the host buffer (int32 bits, ``tracks.queue_ids``) -> per pair (ids0, ids1,
-    frame_start, last_id) as ``tracks.split_ids`` gives them; None per pair when no IDs were queued"""
+def unpack_ids(flat, splits, n_ids, split_ids=split_ids):
+    """the last ``n_ids`` elements of the host buffer (int32 bits, ``tracks.queue_ids`` / ``queue_chain_ids``) -> per
+    entry what ``split_ids`` (``tracks.split_ids`` or ``tracks.split_chain_ids``) gives; None per entry when no IDs
+    were queued"""
     if not n_ids:
         return [None] * len(splits)
     return split_ids(flat[flat.numel() - n_ids:].view(torch.int32).numpy(), splits)
 
 
-def unpack_hand_off(flat, splits, S, K, n_ids=0):
-    """Host fp32 buffer [det S | new S | end S | link K of every pair | per pair the solver block [det L | new L | end L
-    | link N*M] | n_ids int32 bits] -> per pair ``PairResult`` (views of ``flat``); S = sum of N + M, K = sum of N * M."""
-    ids = unpack_ids(flat, splits, n_ids)
-    res, so, lo = [], 0, 0
-    for (N, M), o, i in zip(splits, pairs_table(splits)[1], ids):
-        L = N + M
-        scores = (flat[so:so + L], [flat[3 * S + lo:3 * S + lo + N * M].view(1, N, M)], flat[S + so:S + so + L],
-                  flat[2 * S + so:2 * S + so + L])
-        o += 3 * S + K
-        res.append(PairResult(scores, unpack(flat[o:o + 3 * L + N * M], N, M), i))
-        so += L
-        lo += N * M
-    return res
-
-
-def queue_scores(outs, test_mode):
-    """The score-only hand-off of B pairs: ``outs`` per pair the device outputs (det 3xL, [link 3xNxM], new 3xL, end
-    3xL, ..) of the forward; ``fetch()`` runs ``scores_for_solver`` on each."""
-    return HandOff(outs=outs, test_mode=test_mode)
-
-
-def queue_solve(selected, splits, track=None, frame_idx=None):
-    """Queue the association of B frame pairs behind their forward; nothing waits.  ``selected``: per pair the device
-    rows (det L, [link 1 x N x M], new L, end L) of ``association.select``; ``splits``: per pair (N, M).  Returns the
-    pending ``HandOff``: one device buffer [det | new | end | link of every pair | solver output].
-    ``track`` (a tracks.TrackState; the pairs are then CONSECUTIVE pairs of its sequence, ``frame_idx`` their frame
-    index pairs): the ID launch is queued behind the solve and its int32 result rides at the end of the same buffer."""
-    splits = [(int(N), int(M)) for N, M in splits]
-    if any(N == 0 or M == 0 for N, M in splits):  # an empty frame: nothing to link, answered on the host
-        host = [scores_for_solver(d.unsqueeze(0), l, n.unsqueeze(0), e.unsqueeze(0), 0) for d, l, n, e in selected]
-        done = [(sc, associate(sc[0], sc[1], sc[2], sc[3], split)) for sc, split in zip(host, splits)]
-        if track is None:
-            return HandOff((splits, 0, 0, 0), done=done)
-        # the IDs still come from the kernel, so that the state stays on the device: the assignments are uploaded
-        blocks = torch.cat([t.reshape(-1).to(torch.float32) for _, a in done for t in (a[0], a[2], a[3], a[1][0])])
-        ids = queue_ids(track, blocks.to(track.buf.device), splits, frame_idx)
-        return HandOff((splits, 0, 0, ids.numel()), ids.view(torch.float32), done)
-    cat = lambda k: torch.cat([(s[k][0] if k == 1 else s[k]).reshape(-1) for s in selected])
-    det, new, end, link = cat(0), cat(2), cat(3), cat(1)
-    S, K = det.numel(), link.numel()
-    buf = torch.cat([det, new, end, link])
-    out, _ = torch.ops.mmmot.associate(buf[0:S], buf[S:2 * S], buf[2 * S:3 * S], buf[3 * S:], pairs_table(splits)[0])
-    if track is None:
-        return HandOff((splits, S, K, 0), torch.cat([buf, out]))
-    ids = queue_ids(track, out, splits, frame_idx)
-    return HandOff((splits, S, K, ids.numel()), torch.cat([buf, out, ids.view(torch.float32)]))  # bits, not values
-
-
-# one window on the host: scores (det L, [link 1 x n_t x n_{t+1} ...], new L, end L), assignment as ``ortools_solve``
-# returns it for the window, ids = (ids_per_frame, frame_start, last_id, stored) of ``tracks.split_chain_ids`` or None
-ChainResult = namedtuple('ChainResult', 'scores assignment ids')
-
-
-class ChainHandOff:
-    """B windows queued behind their forward, one ``fetch()`` from the host: the sibling of ``HandOff`` for
-    ``queue_solve_chains``.  ``flat``: the device buffer [det S | new S | end S | links K | solver blocks | n_ids int32
-    bits] (None: every window is empty and no IDs were queued), ``splits``: per window [n_0 .. n_{T-1}]."""
-
-    def __init__(self, splits, flat, S, K, n_ids):
-        self.splits, self.flat, self.S, self.K, self.n_ids = splits, flat, S, K, n_ids
-
-    def fetch(self):
-        """the host copy -> per window a ``ChainResult``: ONE device-to-host copy"""
-        flat = torch.zeros(0) if self.flat is None else self.flat.to('cpu')
-        return unpack_chain_hand_off(flat, self.splits, self.S, self.K, self.n_ids)
-
-
-def unpack_chain_hand_off(flat, splits, S, K, n_ids=0):
-    """Host fp32 buffer of ``queue_solve_chains`` -> per window ``ChainResult`` (views of ``flat``); S = sum of the
-    windows' L, K = sum of their link sizes.  A window without detections has empty scores and an empty assignment."""
-    ids = [None] * len(splits)
-    if n_ids:
-        ids = split_chain_ids(flat[flat.numel() - n_ids:].view(torch.int32).numpy(), splits)
+def unpack_chain_hand_off(flat, splits, S, K, n_ids=0, split_ids=split_chain_ids):
+    """Host fp32 buffer [det S | new S | end S | links K of every entry | per entry the solver block [det L | new L |
+    end L | link_0 | .. | link_{T-2}] | n_ids int32 bits] -> per entry a result (views of ``flat``); ``splits``: per
+    entry [n_0 .. n_{T-1}], S = sum of the entries' L, K = sum of their link sizes.  A window without detections has
+    empty scores and an empty assignment."""
+    ids = unpack_ids(flat, splits, n_ids, split_ids)
     res, so, lo, oo = [], 0, 3 * S, 3 * S + K
     for split, i in zip(splits, ids):
         L = sum(split)
@@ -168,12 +105,58 @@ def unpack_chain_hand_off(flat, splits, S, K, n_ids=0):
     return res
 
 
+def unpack_hand_off(flat, splits, S, K, n_ids=0):
+    """``unpack_chain_hand_off`` for pairs: ``splits`` per pair (N, M), ``ids`` as ``tracks.split_ids`` gives them"""
+    return unpack_chain_hand_off(flat, splits, S, K, n_ids, split_ids)
+
+
+def queue_scores(outs, test_mode):
+    """The score-only hand-off of B pairs or windows: ``outs`` per entry the device outputs (det 3xL, [link 3 x n_t x
+    n_{t+1} ...], new 3xL, end 3xL, ..) of the forward; ``fetch()`` runs ``scores_for_solver`` on each."""
+    return HandOff(outs=outs, test_mode=test_mode)
+
+
+def _hand_off(parts, out, splits, S, K, track, frame_idx, pairs, done=None):
+    """the common tail of ``queue_solve`` and ``queue_solve_chains``: with ``track`` the ID launch behind the solver
+    blocks ``out``, its int32 result appended to ``parts`` (bits, not values), and the pending ``HandOff``"""
+    n_ids = 0
+    if track is not None:
+        ids = (queue_ids if pairs else queue_chain_ids)(track, out, splits, frame_idx)
+        parts, n_ids = parts + [ids.view(torch.float32)], ids.numel()
+    flat = None if not parts else parts[0] if len(parts) == 1 else torch.cat(parts)
+    return HandOff((splits, S, K, n_ids), flat, done, pairs=pairs)
+
+
+def queue_solve(selected, splits, track=None, frame_idx=None):
+    """Queue the association of B frame pairs behind their forward; nothing waits.  ``selected``: per pair the device
+    rows (det L, [link 1 x N x M], new L, end L) of ``association.select``; ``splits``: per pair (N, M).  Returns the
+    pending ``HandOff``: one device buffer [det | new | end | link of every pair | solver output].
+    ``track`` (a tracks.TrackState; the pairs are then CONSECUTIVE pairs of its sequence, ``frame_idx`` their frame
+    index pairs): the ID launch is queued behind the solve and its int32 result rides at the end of the same buffer."""
+    splits = [(int(N), int(M)) for N, M in splits]
+    if any(N == 0 or M == 0 for N, M in splits):  # an empty frame: nothing to link, answered on the host
+        host = [scores_for_solver(d.unsqueeze(0), l, n.unsqueeze(0), e.unsqueeze(0), 0) for d, l, n, e in selected]
+        done = [(sc, associate(sc[0], sc[1], sc[2], sc[3], split)) for sc, split in zip(host, splits)]
+        blocks = None
+        if track is not None:
+            # the IDs still come from the kernel, so that the state stays on the device: the assignments are uploaded
+            blocks = torch.cat([t.reshape(-1).to(torch.float32) for _, a in done for t in (a[0], a[2], a[3], a[1][0])])
+            blocks = blocks.to(track.buf.device)
+        return _hand_off([], blocks, splits, 0, 0, track, frame_idx, True, done)
+    cat = lambda k: torch.cat([(s[k][0] if k == 1 else s[k]).reshape(-1) for s in selected])
+    det, new, end, link = cat(0), cat(2), cat(3), cat(1)
+    S, K = det.numel(), link.numel()
+    buf = torch.cat([det, new, end, link])
+    out, _ = torch.ops.mmmot.associate(buf[0:S], buf[S:2 * S], buf[2 * S:3 * S], buf[3 * S:], pairs_table(splits)[0])
+    return _hand_off([buf, out], out, splits, S, K, track, frame_idx, True)
+
+
 def queue_solve_chains(selected, splits, track=None, frame_idx=None):
     """Queue the association of B windows of 2 .. 8 frames behind their forward; nothing waits.  ``selected``: per window
     the device rows (det L, [link 1 x n_t x n_{t+1} ...], new L, end L) of ``association.select_chain``; ``splits``: per
     window [n_0 .. n_{T-1}].  One ``associate_chains`` launch solves the windows that hold a detection (a frame without
     detections inside such a window goes to the device with it); a window with L = 0 has nothing to solve and is
-    answered on the host with an empty assignment.  Returns the pending ``ChainHandOff``.
+    answered on the host with an empty assignment.  Returns the pending ``HandOff``.
     ``track`` (a tracks.TrackState; the windows are then CONSECUTIVE windows of its sequence, ``frame_idx`` per window
     its T frame indices): the ID launch walks ALL B windows behind the solve - the empty ones too, so that the state
     stays on the device - and its int32 result rides at the end of the same buffer."""
@@ -195,10 +178,7 @@ def queue_solve_chains(selected, splits, track=None, frame_idx=None):
     else:
         dev = track.buf.device if track is not None else None
         S, K, out, parts = 0, 0, torch.empty(0, dtype=torch.float32, device=dev), []
-    if track is None:
-        return ChainHandOff(splits, torch.cat(parts) if parts else None, S, K, 0)
-    ids = queue_chain_ids(track, out, splits, frame_idx)
-    return ChainHandOff(splits, torch.cat(parts + [ids.view(torch.float32)]), S, K, ids.numel())  # bits, not values
+    return _hand_off(parts, out, splits, S, K, track, frame_idx, False)
 
 
 def predict_assign(model, det_imgs, det_info, det_split):
@@ -219,17 +199,7 @@ def predict_assign_chain(model, det_imgs, det_info, det_split):
     with torch.no_grad():
         det_score, link_score, new_score, end_score, _ = model(det_imgs, det_info, det_split)
     split = chain_of(det_split)
-    det, links, new, end = select_chain(det_score, link_score, new_score, end_score, model.test_mode)
-    L = sum(split)
-    buf = torch.cat([t.reshape(-1) for t in (det, new, end, *links)])
-    if L == 0:
+    if sum(split) == 0:
         raise ValueError('predict_assign_chain: no detections')
-    out, _ = torch.ops.mmmot.associate_chains(buf[0:L], buf[L:2 * L], buf[2 * L:3 * L], buf[3 * L:],
-                                              chains_table([split])[0])
-    flat = torch.cat([buf, out]).to('cpu')  # scores and assignment in one copy
-    scores = flat[0:L], [], flat[L:2 * L], flat[2 * L:3 * L]
-    o = 3 * L
-    for a, b in zip(split[:-1], split[1:]):
-        scores[1].append(flat[o:o + a * b].view(1, a, b))
-        o += a * b
-    return scores, unpack_chain(flat[o:o + chain_block_size(split)], split)
+    sel = select_chain(det_score, link_score, new_score, end_score, model.test_mode)
+    return queue_solve_chains([sel], [split]).fetch()[0][:2]

@@ -20,11 +20,13 @@ raises or stops in a debugger on an assignment no solver returns (a kept, non-ne
 exactly one link from a kept row), the kernel writes -1, sets the state's error flag, and ``TrackingError`` is raised
 when the result reaches the host.
 
-Windows of 2 .. 8 frames (what ``association.associate_chain`` solves; csrc/track_chain_ids.hip) go the same way on the
-same state: ``track_chain_ids`` is the drop-in, ``queue_chain_ids`` / ``split_chain_ids`` / ``assign_chain_ids`` the
+Windows of 2 .. 8 frames (what ``association.associate_chain`` solves; the same kernel body on the chain table) go the
+same way on the same state: ``track_chain_ids`` is the drop-in, ``queue_chain_ids`` / ``split_chain_ids`` / ``assign_chain_ids`` the
 batched form, ``merge_chain_tracks`` the per-frame list, ``window_starts`` the schedule of a sequence's windows.  One
 behaviour of the reference is kept: a window whose frame 0 continues the stored frame and whose frame 1 keeps nothing
-is not stored (``stored`` = 0) - only ``last_id`` moves, and its frames are not part of the tracks.
+is not stored (``stored`` = 0) - only ``last_id`` moves, and its frames are not part of the tracks.  The pair forms are
+the two-frame readings of the window forms: ``split_ids`` of ``split_chain_ids``, ``merge_tracks`` of
+``merge_chain_tracks`` (a pair has no ``stored`` word and is always written).
 """
 import numpy as np
 import torch
@@ -97,14 +99,7 @@ def queue_ids(state, blocks, splits, frame_idx, max_nm=0):
 def split_ids(flat, splits):
     """host int32 buffer of ``queue_ids`` -> per pair (ids0 [N], ids1 [M], frame_start, last_id), int64 arrays; raises
     ``TrackingError`` on the error flags"""
-    flat = np.asarray(flat)
-    check_flags(int(flat[-1]))
-    res, o = [], 0
-    for N, M in splits:
-        res.append((flat[o:o + N].astype(np.int64), flat[o + N:o + N + M].astype(np.int64), int(flat[o + N + M]),
-                    int(flat[o + N + M + 1])))
-        o += N + M + 2
-    return res
+    return [(i[0], i[1], start, last) for i, start, last in split_chain_ids(flat, splits, tail=2)]
 
 
 def assign_ids(state, blocks, splits, frame_idx, max_nm=0):
@@ -131,17 +126,12 @@ def track_ids(state, assign_det, assign_link, assign_new, assign_end, det_split,
 
 def merge_tracks(tracks, t, ids0, ids1, frame_start, on_tracks=None):
     """pair (t-1, t) into the per-frame list: the last emission of a frame stands (a frame whose pair kept nothing is
-    emitted again by the next pair, as the reference does)"""
-    if not frame_start:
-        tracks[t - 1] = ids0
-        if on_tracks is not None:
-            on_tracks(t - 1, ids0)
-    tracks[t] = ids1
-    if on_tracks is not None:
-        on_tracks(t, ids1)
+    emitted again by the next pair, as the reference does).  A pair is always written: the two-frame, ``stored`` = 1
+    call of ``merge_chain_tracks``"""
+    merge_chain_tracks(tracks, (t - 1, t), (ids0, ids1), frame_start, 1, on_tracks)
 
 
-# ---- windows of 2 .. 8 frames (csrc/track_chain_ids.hip) ------------------------------------------------------------
+# ---- windows of 2 .. 8 frames (a pair's IDs are read as the two-frame case, with two trailing words) -----------------
 def window_starts(n_frames, window):
     """The window schedule as a pure function: [(first frame, frame count)] of the windows of a sequence of
     ``n_frames`` frames.  Windows of ``window`` frames start at 0, window - 1, 2 (window - 1), .. (neighbours share a
@@ -175,9 +165,9 @@ def queue_chain_ids(state, blocks, splits, frame_idx, max_n=0):
     return torch.cat([ids, state.buf[2:3]])
 
 
-def split_chain_ids(flat, splits):
+def split_chain_ids(flat, splits, tail=3):
     """host int32 buffer of ``queue_chain_ids`` -> per window (ids_per_frame: T int64 arrays, frame_start, last_id,
-    stored); raises ``TrackingError`` on the error flags"""
+    stored); raises ``TrackingError`` on the error flags.  ``tail`` = 2: the buffer of ``queue_ids``, without ``stored``"""
     flat = np.asarray(flat)
     check_flags(int(flat[-1]))
     res, o = [], 0
@@ -186,8 +176,8 @@ def split_chain_ids(flat, splits):
         for n in split:
             ids.append(flat[o:o + n].astype(np.int64))
             o += n
-        res.append((ids, int(flat[o]), int(flat[o + 1]), int(flat[o + 2])))
-        o += 3
+        res.append((ids, *(int(w) for w in flat[o:o + tail])))
+        o += tail
     return res
 
 

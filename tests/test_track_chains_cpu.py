@@ -201,7 +201,7 @@ def test_library_exports_track_chain_ids_and_header_declares_it():
     with open(os.path.join(ROOT, 'include', 'mmmot_hip.h')) as f:
         header = f.read()
     assert re.search(r'\bint mmmot_track_chain_ids\(const float\* blocks, const int\* chains,', header)
-    assert len(_lib.SIGNATURES['mmmot_track_chain_ids']) == 9 and 'track_chain_ids.hip' in _lib.SOURCES
+    assert len(_lib.SIGNATURES['mmmot_track_chain_ids']) == 9 and 'track_ids.hip' in _lib.SOURCES
 
 
 def test_abi_version_and_argument_checks():

@@ -1,4 +1,4 @@
-"""Track IDs of windows of 2 .. 8 frames on the device (csrc/track_chain_ids.hip through mmmot::track_chain_ids /
+"""Track IDs of windows of 2 .. 8 frames on the device (csrc/track_ids.hip through mmmot::track_chain_ids /
 mmmot_amd.tracks) against the fixtures the reference produced (tests/golden/track_chain_ids_*.npz): exact IDs,
 frame_start and last_id after every window and the final tracks, whatever the launch size and the kernel; two-frame
 windows against mmmot::track_ids bit for bit; state and outputs written in full; the error flag; the drop-in on host and

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from mmmot_amd.association import pairs_table
-from mmmot_amd.tracker_glue import PairResult, scores_for_solver, unpack_hand_off
+from mmmot_amd.tracker_glue import ChainResult, PairResult, scores_for_solver, unpack_chain_hand_off, unpack_hand_off
 from mmmot_amd.tracks import ECONTRACT, EINFEASIBLE, TrackingError, split_ids
 
 
@@ -66,3 +66,31 @@ def test_hand_off_layout_unpacks_per_pair():
         tail[-1] = flag
         with pytest.raises(TrackingError):
             unpack_hand_off(torch.from_numpy(np.concatenate([head, tail.view(np.float32)])), splits, S, K, tail.size)
+
+
+@pytest.mark.parametrize('with_ids', [False, True])
+def test_pair_buffer_reads_as_two_frame_windows(with_ids):
+    """a packed pair buffer is the buffer of two-frame windows: ``unpack_hand_off`` and ``unpack_chain_hand_off`` on the
+    same bytes give the same scores and assignment, element for element; the ID tail of a pair has two trailing words"""
+    splits = [(3, 4), (0, 2), (5, 1)]
+    rng = np.random.default_rng(5)
+    S, K = sum(N + M for N, M in splits), sum(N * M for N, M in splits)
+    head = rng.standard_normal(3 * S + K + sum(3 * (N + M) + N * M for N, M in splits)).astype(np.float32)
+    tail = np.zeros(0, np.int32)
+    if with_ids:
+        tail = np.concatenate([rng.integers(-1, 40, N + M + 2) for N, M in splits] + [np.zeros(1)]).astype(np.int32)
+    flat = torch.from_numpy(np.concatenate([head, tail.view(np.float32)]))
+    pairs = unpack_hand_off(flat, splits, S, K, tail.size)
+    wins = unpack_chain_hand_off(flat, [list(s) for s in splits], S, K, 0)   # the pair tail is not a window's: not read
+    assert len(pairs) == len(wins) == len(splits)
+    for p, w, (N, M) in zip(pairs, wins, splits):
+        assert isinstance(p, PairResult) and isinstance(w, ChainResult) and isinstance(p, ChainResult)
+        for a, b in ((p.scores, w.scores), (p.assignment, w.assignment)):
+            assert len(a) == len(b) == 4 and len(a[1]) == len(b[1]) == 1 and a[1][0].shape == b[1][0].shape == (1, N, M)
+            for x, y in zip((a[0], a[1][0], a[2], a[3]), (b[0], b[1][0], b[2], b[3])):
+                assert x.shape == y.shape and torch.equal(x, y)
+            assert a[0].numel() == a[2].numel() == a[3].numel() == N + M
+        assert w.ids is None and (p.ids is None) == (not with_ids)
+    if with_ids:
+        assert [len(p.ids) for p in pairs] == [4] * 3
+        assert all(np.array_equal(x, y) for p, i in zip(pairs, split_ids(tail, splits)) for x, y in zip(p.ids, i))

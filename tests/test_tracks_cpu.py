@@ -153,3 +153,19 @@ def test_meta_kernel_gives_the_output_size():
     state = torch.empty(TRACK_STATE_INTS, dtype=torch.int32, device='meta')
     ids = torch.ops.mmmot.track_ids(blocks, pairs, fidx, state, 0)
     assert ids.shape == (3 + 4 + 2 + 4 + 0 + 2,) and ids.dtype == torch.int32 and ids.device.type == 'meta'
+
+
+@pytest.mark.parametrize('frame_start', [0, 1])
+def test_merge_tracks_is_the_stored_two_frame_merge_of_windows(frame_start):
+    from mmmot_amd.tracks import merge_chain_tracks, merge_tracks
+    ids0, ids1 = np.array([3, -1, 4]), np.array([-1, -1])   # a second frame that keeps nothing is written all the same
+    got, want = [[None] * 4, []], [[None] * 4, []]
+    merge_tracks(got[0], 2, ids0, ids1, frame_start, on_tracks=lambda t, i: got[1].append((t, i.tolist())))
+    merge_chain_tracks(want[0], [1, 2], [ids0, ids1], frame_start, stored=1,
+                       on_tracks=lambda t, i: want[1].append((t, i.tolist())))
+    assert got[1] == want[1] == ([(2, [-1, -1])] if frame_start else [(1, [3, -1, 4]), (2, [-1, -1])])
+    assert len(got[0]) == len(want[0]) == 4
+    for a, b in zip(got[0], want[0]):
+        assert (a is None and b is None) or np.array_equal(a, b)
+    assert got[0][0] is None and got[0][3] is None and (got[0][1] is None) == bool(frame_start) and got[0][2] is ids1
+    merge_tracks(got[0], 2, ids0, ids1, frame_start)   # without a callback

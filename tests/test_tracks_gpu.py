@@ -248,6 +248,32 @@ def test_queue_solve_with_an_empty_frame():
         assert np.array_equal(ids0, w0) and np.array_equal(ids1, w1) and start == ws and last == ref.last_id
 
 
+def test_queue_solve_with_a_pair_without_detections():
+    """N = M = 0 between two ordinary pairs of the `start` fixture: the empty pair has no solver block at all, and its
+    IDs (none), frame_start, last_id and the state still come from the kernel - an empty ``blocks`` is not a null
+    pointer.  Expected: tests/tracking_ref.Tracker over the same three pairs."""
+    from mmmot_amd.tracker_glue import queue_solve
+    first, third = fixture('start')[:2]
+    state, ref = TrackState('cuda'), Tracker()
+    empty = torch.empty(0, device='cuda')
+    for p in (first, None, third):
+        if p is None:
+            f0, f1 = 1000, 1001   # frames of their own: the stored frame has detections, this one has none
+            r = queue_solve([(empty, [empty.view(1, 0, 0)], empty, empty)], [(0, 0)], track=state, frame_idx=[(f0, f1)])
+            sc, asg, (ids0, ids1, start, last) = r.fetch()[0]
+            assert sc[0].numel() == 0 and asg[0].numel() == 0 and asg[1][0].shape == (1, 0, 0)
+            w0, w1, ws = ref.pair(np.zeros(0), np.zeros((0, 0)), np.zeros(0), 0, 0, f0, f1)
+        else:
+            ids0, ids1, start, last = assign_ids(state, torch.from_numpy(p['block']).cuda(), [(p['N'], p['M'])],
+                                                 [(p['f0'], p['f1'])])[0]
+            w0, w1, ws = ref.pair(p['det'], p['link'], p['new'], p['N'], p['M'], p['f0'], p['f1'])
+        assert ids0.dtype == np.int64 and np.array_equal(ids0, w0) and np.array_equal(ids1, w1)
+        assert start == ws and last == ref.last_id
+    s = state.read()
+    assert s['flags'] == 0 and s['last_id'] == ref.last_id and s['frame'] == ref.stored
+    assert np.array_equal(s['ids'], ref.stored_ids)
+
+
 def test_forced_recompute_gives_the_same_tracks():
     """rows made stale between a pair's hand-off and its check (a trunk change, the mechanism of
     tests/test_appearance_reuse_gpu.py): the pair is computed again and its IDs start from the state before it"""

@@ -1,6 +1,6 @@
 """The tracker's ID bookkeeping on WINDOWS of 2 .. 8 frames (reference tracking_model.py assign_det_id + align_id, which
 are written for len(det_split) frames) restated by detection index in plain numpy - the host oracle of the window tests.
-Serial loops on purpose: nothing here is shared with mmmot_amd.tracks or csrc/track_chain_ids.hip, and
+Serial loops on purpose: nothing here is shared with mmmot_amd.tracks or csrc/track_ids.hip, and
 tests/golden/track_chain_ids_*.npz (made by the reference itself, tools/gen_golden_track_chains.py) arbitrate."""
 import numpy as np
 
