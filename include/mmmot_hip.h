@@ -858,6 +858,31 @@ int mmmot_adam_chunk_elems(void);
  * than 2^31 - 1 rows. */
 int mmmot_adam_chunks(const long long* h_numel, int n_tensors, int* h_chunks, long long cap, long long* h_count);
 
+/* ---------------------------------------------------------------------------
+ * Dropout of the LiDAR encoder in training mode (reference modules/point_net.py:28-39: nn.Dropout(p) over points x
+ * channels between relu(bn1(conv1)) and the per-detection average pool; csrc/dropout.hip),
+ * additive in ABI 10.  The mask is generated in registers and never stored:
+ *   w = philox4x32_10(counter = (r, c >> 2, 0, 0), key = (seed & 0xffffffff, seed >> 32))    (csrc/philox.h)
+ *   keep(r, c) = w[c & 3] >= threshold     (unsigned; threshold = min(round(p * 2^32), 0xFFFFFFFF), 0 keeps everything)
+ * for row r (< 2^32) and channel c of a [R][C] tensor - a function of (seed, r, c) alone, whatever the grid.
+ *
+ * mmmot_segment_mean_dropout: out[s][c] = (1 / seg_count[s]) * sum_t keep(r, c) * scale * relu(X[r][c] * sc[g][c] + sh[g][c])
+ * with r = seg_start[s] + t, g = seg_group[s] (NULL: 0); contiguous fp32 rows.  Decomposition and summation order of
+ * mmmot_segment_mean: with threshold = 0, scale = 1 it is bit-identical to mmmot_segment_mean(relu = 1).
+ * mmmot_rows_gather_scale_dropout: X[r][c] = keep(r, c) * dscale * (S[rowidx[r]][c] * scale[rowidx[r]]) (scale NULL: 1),
+ * the inner product as mmmot_rows_gather_scale forms it.
+ * mmmot_dropout_mask: out[r][c] = keep(r, c) as a byte, out a contiguous [R][C] array.
+ * All three: C % 4 == 0, leading dimensions multiples of 4 and >= C, 16-byte aligned pointers, R < 2^32; MMMOT_EINVAL
+ * otherwise.  Nothing is allocated, nothing synchronises. */
+int mmmot_segment_mean_dropout(const float* X, int ldx, int C, const int* seg_start, const int* seg_count,
+                               const int* seg_group, int nseg, const float* sc, const float* sh, int ldsc,
+                               unsigned long long seed, unsigned threshold, float scale, float* out, int ldo,
+                               void* stream);
+int mmmot_rows_gather_scale_dropout(const float* S, int lds, const int* rowidx, const float* scale, float* X, int ldx,
+                                    long R, int C, unsigned long long seed, unsigned threshold, float dscale,
+                                    void* stream);
+int mmmot_dropout_mask(unsigned long long seed, unsigned threshold, long R, int C, unsigned char* out, void* stream);
+
 /* MFMA fragment-layout self test: C[32][32] = A[32][K] * B[32][K]^T through
  * the same fragment mapping the GEMM kernels use (K % 8 == 0). */
 int mmmot_selftest_mfma(const float* A, const float* B, float* C, int K, void* stream);

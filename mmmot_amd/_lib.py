@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('MMMOT_LIB_PATH', os.path.join(_HERE, 'libmmmot_hip.so'))  # override: tools' timing-experiment builds
 SOURCES = ['conv3x3.hip', 'hl16_format.hip', 'conv3x3_hl16_patch.hip', 'gemm_rows.hip', 'gemm_wide.hip',
            'gemm_ares.hip', 'gemm_wres.hip', 'gemm_wreg.hip', 'pn_mlp64.hip', 'gram.hip', 'points_gather.hip', 'crop_resize.hip', 'small_kernels.hip', 'backward.hip', 'train.hip', 'train_vgg.hip', 'gemm_tn_f16.hip',
-           'assign.hip', 'assign_chain.hip', 'track_ids.hip', 'clear_mot.hip', 'align_points.hip', 'labels.hip', 'adam_step.hip']
+           'assign.hip', 'assign_chain.hip', 'track_ids.hip', 'clear_mot.hip', 'align_points.hip', 'labels.hip', 'adam_step.hip', 'dropout.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 HIPFLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 
@@ -178,6 +178,14 @@ SIGNATURES = {
     'mmmot_adam_chunk_elems': [],
     # h_numel, n_tensors, h_chunks, cap, h_count  (host pointers)
     'mmmot_adam_chunks': [c_f, c_i, c_f, ctypes.c_longlong, c_f],
+    # X, ldx, C, seg_start, seg_count, seg_group, nseg, sc, sh, ldsc, seed, threshold, scale, out, ldo, stream
+    'mmmot_segment_mean_dropout': [c_f, c_i, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_i, ctypes.c_ulonglong, ctypes.c_uint,
+                                   ctypes.c_float, c_f, c_i, c_f],
+    # S, lds, rowidx, scale, X, ldx, R, C, seed, threshold, dscale, stream
+    'mmmot_rows_gather_scale_dropout': [c_f, c_i, c_f, c_f, c_f, c_i, ctypes.c_long, c_i, ctypes.c_ulonglong, ctypes.c_uint,
+                                        ctypes.c_float, c_f],
+    # seed, threshold, R, C, out, stream
+    'mmmot_dropout_mask': [ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_long, c_i, c_f, c_f],
 }
 
 

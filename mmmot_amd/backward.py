@@ -5,7 +5,8 @@ The pairwise block is ``affinity_module.forward`` + ``NewEndIndicator_v2.forward
 ``TrackingNet.associate`` (reference modules/gcn.py:68-82, new_end.py:62-82, tracking_net.py:106-126); its gradients go
 to the fused features F (3 x L x 512 in the reference, [nR*Lt][512] here) and to every ``w_link.*`` parameter - the part
 of the training step ``tracking_model.py:50-66`` (forward -> loss -> backward) that runs over the N x M pair space.  In
-training mode this block and the fusion module are identical to eval mode (GroupNorm only: no BatchNorm, no dropout), so
+training mode this block and the fusion module are identical to eval mode (GroupNorm only: no BatchNorm, and the network's
+one dropout sits in the LiDAR encoder - ``use_dropout``, mmmot_amd/train.py - not here), so
 their training forward IS ``Engine.affinity`` / ``Engine.fuse``, run under ``Engine.recording()``: the engine's own
 schedule, with the pre-norm tensors kept on a tape under the engine's layer names.  w_det normalises with the batch
 statistics in training mode, which is not the eval arithmetic: ``det_forward_train`` is a schedule of its own.

@@ -2,7 +2,8 @@
 // `affinity_module.forward` + `NewEndIndicator_v2.forward` + the softmax modes of `TrackingNet.associate`
 // (reference modules/gcn.py:68-82, new_end.py:62-82, tracking_net.py:106-126; the training step that needs them is
 // tracking_model.py:50-66).  In training mode this block behaves exactly like in eval mode (GroupNorm only, no
-// BatchNorm, no dropout), so the forward is the inference forward with the pre-norm tensors kept.
+// BatchNorm; the network's one dropout - `use_dropout`, on in the reference's rrc config - sits in the LiDAR encoder:
+// csrc/dropout.hip), so the forward is the inference forward with the pre-norm tensors kept.
 //
 // Layout as in the forward: position-major rows, channels contiguous.  Every layer of the block is
 //     y = A W^T + b,   yhat = (y - mean) * rstd,   z = yhat * gamma + beta,   a = relu(z)

@@ -131,7 +131,9 @@ class PointNet_v1(nn.Module):
         self.bn1 = _gn(512, 512)
         self.bn2 = _gn(16, out_channels)
         self.avg_bn = _gn(512, 512)  # unused by the reference forward too; kept for key parity
-        self.dropout = None  # eval-only path; reference dropout is identity in eval (point_net.py:29-30)
+        # point_net.py:18-21,29-30: identity in eval mode; in training mode the pool behind it drops on the device
+        # (mmmot_amd/train.py).  No parameters: the state_dict keys do not depend on the flag
+        self.dropout = nn.Dropout(p=0.5) if use_dropout else None
 
     def forward(self, x, point_split):
         """x: 1 x 3 x P, point_split: (L+1,) -> (L x 512, [1x3x3, 1x64x64]) (HIP)."""

@@ -519,6 +519,30 @@ class HipOps:
                                               self._stream())
         _lib.check(st, 'mmmot_rows_gather_scale')
 
+    # ---- dropout of the LiDAR encoder (csrc/dropout.hip): keep(r, c) = philox(seed; r, c >> 2)[c & 3] >= threshold ----
+    def segment_mean_dropout(self, X, C, segs, out, sc, sh, seed, threshold, scale, use_group=True):
+        """segment_mean(relu=True) over the dropped rows: mean_t keep(r, c) * scale * relu(X[r][c] * sc + sh)"""
+        st = self.lib.mmmot_segment_mean_dropout(_ptr(X), _ld(X), C, _iptr(segs.start), _iptr(segs.count),
+                                                 _iptr(segs.group) if use_group else None, segs.n, _ptr(sc), _ptr(sh),
+                                                 _ld(sc), int(seed), int(threshold), float(scale), _ptr(out), _ld(out),
+                                                 self._stream())
+        _lib.check(st, 'mmmot_segment_mean_dropout')
+
+    def rows_gather_scale_dropout(self, S, rowidx, scale, X, C, seed, threshold, dscale):
+        """rows_gather_scale times the mask: X[r][:C] = keep(r, c) * dscale * (S[rowidx[r]][:C] * scale[rowidx[r]])"""
+        st = self.lib.mmmot_rows_gather_scale_dropout(_ptr(S), _ld(S), _iptr(rowidx), _ptr(scale), _ptr(X), _ld(X),
+                                                      X.shape[0], C, int(seed), int(threshold), float(dscale),
+                                                      self._stream())
+        _lib.check(st, 'mmmot_rows_gather_scale_dropout')
+
+    def dropout_mask(self, seed, threshold, out):
+        """out uint8 [R][C] contiguous <- keep(r, c): the mask exactly as the two kernels above see it"""
+        if out.dim() != 2 or not out.is_contiguous():
+            raise ValueError('dropout_mask writes a contiguous [R][C] uint8 tensor')
+        st = self.lib.mmmot_dropout_mask(int(seed), int(threshold), out.shape[0], out.shape[1], _ptr(out, torch.uint8),
+                                         self._stream())
+        _lib.check(st, 'mmmot_dropout_mask')
+
     def pointnet_layer1_bwd(self, dY, X, tiles, PW):
         """PW [T][64 * (K + 1)] per-tile partials of (dW1 [64][K] | db1 [64]) interleaved per channel; K = X.shape[1]"""
         st = self.lib.mmmot_pointnet_layer1_bwd(_ptr(dY), _ptr(X), int(X.shape[1]), _iptr(tiles.row0), _iptr(tiles.nrows),

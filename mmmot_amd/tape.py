@@ -141,8 +141,8 @@ def weight_grad(eng, dY, tiles, N, K, shares=None, **operand):
     tiles (one workgroup walks one share for one 64 x 64 tile of dW; default: one per 8 tiles, at most 16) whose partial
     sums are added by the strided-sum kernel: deterministic."""
     ns = max(1, min(16, tiles.T // 8)) if shares is None else shares
-    dWp = torch.empty(ns, N * K, dtype=torch.float32, device=dY.device)
-    dbp = torch.empty(ns, N, dtype=torch.float32, device=dY.device)
+    dWp = torch.empty(ns, N * K, dtype=dY.dtype, device=dY.device)  # dY's dtype, like gn_backward's buffers
+    dbp = torch.empty(ns, N, dtype=dY.dtype, device=dY.device)
     eng.ops.gemm_tn(dY, tiles, N, K, dWp, dbp, nsplit=ns, **operand)
     if ns > 1:
         return colsum(eng, dWp).view(N, K), colsum(eng, dbp)
@@ -191,7 +191,7 @@ class Layer:
         K = int(W.shape[1])
         dY, dgamma, dbeta = gn_backward(eng, plan, self, dA, out=out, relu=relu)
         dW, db = weight_grad(eng, dY, self.tiles, self.C, K, shares, **operand)
-        dX = torch.empty(self.tiles.R, K, dtype=torch.float32, device=dA.device)
+        dX = torch.empty(self.tiles.R, K, dtype=dA.dtype, device=dA.device)
         dgrad_gemm(eng, W, self.tiles, dY, dX)
         return dX, dW, db, dgamma, dbeta
 

@@ -5,9 +5,12 @@ The reference's training step is ``tracking_model.py:50-66``: training-mode ``Tr
 ``mmmot_amd/backward.py`` is the head (fusion, w_det in training mode, the pairwise block); this file adds
 
 * ``pointnet_autograd(model, plan, points)``: ``PointNet_v1.forward`` (reference modules/point_net.py:25-44, 115-153)
-  as a differentiable operator.  PointNet contains GroupNorm only (no BatchNorm; dropout is off in every config), so its
-  training forward is the inference arithmetic - run here in its MATERIALISING form (the pre-norm tensors
-  of every layer are the tape; the inference engine never stores the [P][1024] / [P][512] ones) and with exact-fp32
+  as a differentiable operator.  PointNet contains GroupNorm only (no BatchNorm), so apart from dropout its training
+  forward is the inference arithmetic.  ``use_dropout: True`` (the reference's rrc_pfv_40e_subabs_dualadd_C config; the
+  pp_* configs set False) puts nn.Dropout(0.5) between relu(bn1(conv1)) and the last per-detection average pool: here the
+  pool's launch and its backward's launch generate the mask in registers from (seed, row, channel) - csrc/dropout.hip,
+  DESIGN.md section 17 - so there is no extra pass over the [P][512] tensor and no stored mask.
+  The forward is run here in its MATERIALISING form (the pre-norm tensors of every layer are the tape; the inference engine never stores the [P][1024] / [P][512] ones) and with exact-fp32
   matrix-core GEMMs on the unscaled weights (no per-step hl16 re-packing).  Backward per layer: the GroupNorm(+ReLU)
   backward, ``dW = dY^T A`` and ``dA = dY W`` kernels of csrc/backward.hip, plus the two kernels of csrc/train.hip
   (average-pool backward, first-layer weight gradient).
@@ -71,9 +74,16 @@ class _PointAux:
     def __init__(self, plan):
         cnt = np.diff(plan.pt_split)
         self.inv_cnt = torch.from_numpy((1.0 / cnt).astype(np.float32)).to(plan.device)
+        self._cnt = cnt
         det_sample = np.repeat(np.arange(plan.B), plan.L)
         # SUM of a detection's point rows (the gradient of a per-detection bias added to each of them)
         self.det_sum = Segments(plan.pt_split[:-1], cnt, np.ones(plan.Lt), det_sample, plan.device, div=np.ones(plan.Lt))
+
+    def inv(self, dtype):
+        """1 / point count per detection: the fp32 device table, or (the tests' float64 emulation) unrounded"""
+        if dtype == torch.float32:
+            return self.inv_cnt
+        return torch.from_numpy(1.0 / self._cnt).to(self.inv_cnt.device, dtype)
 
 
 def _paux(plan):
@@ -82,11 +92,27 @@ def _paux(plan):
     return plan._pn_bwd_aux
 
 
-def pointnet_forward_train(eng, plan, points, W):
-    """points [P][3 | 4], W = folded fp32 tensors (fold_pointnet) -> (features [Lt][512], tape)."""
+def dropout_constants(p):
+    """nn.Dropout(p) -> (threshold, scale) of the device mask: keep where a uniform 32-bit word >= threshold =
+    min(round(p * 2^32), 0xFFFFFFFF), kept values times scale = 1 / (1 - p)"""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError('dropout probability %r: the device mask needs 0 <= p < 1 (p = 1 has no finite scale)' % (p,))
+    return min(int(round(p * 2.0 ** 32)), 0xFFFFFFFF), 1.0 / (1.0 - p)
+
+
+def draw_dropout_seed():
+    """one 63-bit draw from the global torch generator, on the host (the DropBlock convention: the same
+    torch.manual_seed gives the same masks, nothing waits on the device)"""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+
+
+def pointnet_forward_train(eng, plan, points, W, drop=None):
+    """points [P][3 | 4], W = folded fp32 tensors (fold_pointnet) -> (features [Lt][512], tape).  ``drop``: (seed,
+    threshold, scale) of the dropout in front of the last pool, or None."""
     ops, T, D, Pn, Lt = eng.ops, plan.pt_tiles, plan.det_tiles, plan.P, plan.Lt
     dev = points.device
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    new = lambda *s: torch.empty(*s, dtype=points.dtype, device=dev)  # fp32 on the device; float64: the tests' emulation
     t = {}
     y1, part = new(Pn, 64), new(T.T, 2, 64)
     ops.pointnet_layer1(points, W['w1'], W['b1'], y1, part, T)
@@ -106,13 +132,16 @@ def pointnet_forward_train(eng, plan, points, W):
              dbias=dbias, rowidx=plan.row_det)
     t['c1'] = norm_layer(eng, part, T, yc1, 512, 512, W['gc1'], W['bec1'])
     seg512 = new(Lt, 512)
-    ops.segment_mean(yc1, 512, plan.det_segs, seg512, sc=t['c1'].sc, sh=t['c1'].sh, relu=True)  # point_net.py:32-39
+    if drop is None:
+        ops.segment_mean(yc1, 512, plan.det_segs, seg512, sc=t['c1'].sc, sh=t['c1'].sh, relu=True)  # point_net.py:32-39
+    else:  # point_net.py:29-30: the pool of the dropped rows, the mask generated in the pool's registers
+        ops.segment_mean_dropout(yc1, 512, plan.det_segs, seg512, t['c1'].sc, t['c1'].sh, *drop)
     yc2, part = new(Lt, 512), new(D.T, 2, 512)
     ops.gemm(W['wc2'], D, 512, 512, X=seg512, bias=W['bc2'], Y=yc2, part=part)
     t['c2'] = norm_layer(eng, part, D, yc2, 512, 16, W['gc2'], W['bec2'])
     out = new(Lt, 512)
     ops.affine_act(yc2, 512, t['c2'].sc, t['c2'].sh, D, ACT_RELU, out)
-    t.update(seg1024=seg1024, seg512=seg512)
+    t.update(seg1024=seg1024, seg512=seg512, drop=drop)
     return out, t
 
 
@@ -121,7 +150,8 @@ def pointnet_backward(eng, plan, points, W, t, dOut):
     ops, T, D, Pn, Lt = eng.ops, plan.pt_tiles, plan.det_tiles, plan.P, plan.Lt
     dev = points.device
     aux = _paux(plan)
-    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    inv_cnt = aux.inv(points.dtype)
+    new = lambda *s: torch.empty(*s, dtype=points.dtype, device=dev)  # fp32 on the device; float64: the tests' emulation
     g = {}
     p1 = t['p1']
     # ---- PointNet_v1 head: conv2 + GroupNorm(16) + ReLU over the detections (point_net.py:40) ----
@@ -129,7 +159,10 @@ def pointnet_backward(eng, plan, points, W, t, dOut):
                                                                         amode=A_PLAIN)
     # ---- per-detection average of relu(gn(conv1)) (point_net.py:32-39), conv1 1088 -> 512 + GroupNorm(512) ----
     dAc1 = new(Pn, 512)
-    ops.rows_gather_scale(dseg512, plan.row_det, aux.inv_cnt, dAc1, 512)
+    if t['drop'] is None:
+        ops.rows_gather_scale(dseg512, plan.row_det, inv_cnt, dAc1, 512)
+    else:  # the forward's mask again, from the same seed
+        ops.rows_gather_scale_dropout(dseg512, plan.row_det, inv_cnt, dAc1, 512, *t['drop'])
     dyc1, g['gc1'], g['bec1'] = gn_backward(eng, plan, t['c1'], dAc1)
     g['wc1a'], _ = weight_grad(eng, dyc1, T, 512, 64, X=p1.Y, sc=p1.sc, sh=p1.sh, amode=A_NORM_RELU)
     ddbias = new(Lt, 512)  # the 1024 broadcast channels act as a per-detection bias: its gradient is the row SUM
@@ -141,7 +174,7 @@ def pointnet_backward(eng, plan, points, W, t, dOut):
     dgrad_gemm(eng, W['wc1a'], T, dyc1, dA1c)
     # ---- PointNetfeatGN: average of relu(gn5(conv5)) back to the points, then the conv5 .. conv2 chain ----
     dA = new(Pn, 1024)
-    ops.rows_gather_scale(dseg1024, plan.row_det, aux.inv_cnt, dA, 1024)
+    ops.rows_gather_scale(dseg1024, plan.row_det, inv_cnt, dA, 1024)
     for i in (5, 4, 3, 2):
         Li, Lp = t['p%d' % i], t['p%d' % (i - 1)]
         dA, g['w%d' % i], g['b%d' % i], g['g%d' % i], g['be%d' % i] = Li.backward(
@@ -157,15 +190,26 @@ def pointnet_backward(eng, plan, points, W, t, dOut):
     return g
 
 
-def pointnet_autograd(model, plan, points):
+def pointnet_dropout_active(model):
+    return model.point_net.dropout is not None and model.point_net.training
+
+
+def pointnet_autograd(model, plan, points, dropout_seed=None):
     """Differentiable ``model.point_net`` (a TrackingNet's PointNet_v1 on the device): points [P][3 | 4] ->
-    (features [Lt][512] on the autograd graph of every ``point_net.*`` parameter, [trans1, trans2])."""
+    (features [Lt][512] on the autograd graph of every ``point_net.*`` parameter, [trans1, trans2]).  With
+    ``point_net.dropout`` set and the module in training mode the last pool drops (``dropout_seed``: the mask's 64-bit
+    seed; None = one draw from the global torch generator)."""
     eng = model.engine()
     W, trans = fold_pointnet(model.point_net)
+    drop = None
+    if pointnet_dropout_active(model):
+        thr, scale = dropout_constants(model.point_net.dropout.p)
+        seed = draw_dropout_seed() if dropout_seed is None else int(dropout_seed) & 0xFFFFFFFFFFFFFFFF
+        drop = (seed, thr, scale)
 
     def fwd(pts, folded):
-        Wd = {k: v.to(torch.float32).contiguous() for k, v in zip(FOLDED, folded)}
-        out, tape = pointnet_forward_train(eng, plan, pts, Wd)
+        Wd = {k: v.to(pts.dtype).contiguous() for k, v in zip(FOLDED, folded)}
+        out, tape = pointnet_forward_train(eng, plan, pts, Wd, drop)
         return (out,), (Wd, tape)
 
     out, = taped(points, FOLDED, [W[k] for k in FOLDED], fwd,
@@ -335,6 +379,8 @@ def forward_train(model, dets, det_info, dets_split):
                 cat0 = eng.buf('cat', plan.Lt, 1024)
                 eng.appearance(plan, dets.contiguous(), cat0)
                 img = cat0[:, :512].clone()
+    # use_dropout models in training mode: the mask seed is drawn from the global generator in here, AFTER the image
+    # branch - DropBlock's draws for stages 2 and 3 keep their positions; no draw at all when dropout is off
     pts_feat, trans = pointnet_autograd(model, plan, points)
     cat = torch.cat([img, pts_feat], dim=1)
     det, link, new, end = head_autograd(model, plan, cat)

@@ -12,8 +12,9 @@ matrix cores): per layer ``mmmot_conv3x3_raw`` -> ``mmmot_rows_stats`` + ``mmmot
 the per-channel GroupNorm with one group) -> ``mmmot_bn_relu_pool``; backward ``mmmot_maxpool_bwd`` -> the GroupNorm
 backward kernels of csrc/backward.hip -> ``mmmot_conv3x3_wgrad`` (dW) and ``mmmot_conv3x3_raw`` on the flipped / transposed
 weights (dX).  Everything numeric is in libmmmot_hip.so; torch permutes weights (data movement) and keeps the graph.
-DropBlock (``dropblock`` > 0; every shipped config sets 0): the seed masks are drawn on the host like the reference's, the
-scaling of the stage outputs and of their gradients runs on the device (_dropblock_scale).
+DropBlock (``dropblock`` > 0: the reference's rrc_pfv_40e_subabs_dualadd_C config sets 5, its pp_* configs 0): the seed
+masks are drawn on the host like the reference's, the scaling of the stage outputs and of their gradients runs on the
+device (_dropblock_scale).  That config's other regulariser, ``use_dropout``, is the LiDAR encoder's: mmmot_amd/train.py.
 """
 import numpy as np
 import torch

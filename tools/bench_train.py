@@ -6,6 +6,7 @@ ragged ~300 pts/det) and at a cfg2-like sample (N=M=32, 64x64 crops, 512 pts/det
     python tools/bench_train.py
     python tools/bench_train.py --labels    # the label step alone on the same samples
     python tools/bench_train.py --optim     # the optimizer step alone at the full model's 216 tensors
+    python tools/bench_train.py --dropout   # the step with use_dropout on against off, and the two dropout launches
 
 ``--labels`` times mmmot_amd.labels.generate_gt alone instead of the step, class / id tensors and targets on the device
 as in the reference's ``step``.  The reference's own host loop is not timed here: the repository holds no copy of it.
@@ -17,6 +18,11 @@ device synchronise inside the timed window, 200 calls behind 20 warm-up calls, t
 timed with events around 50 back-to-back launches on a prepared table, and launch by launch behind a pass over another
 1 GB (the back-to-back launches find part of their data in the last-level cache), against the 28 bytes an element it
 must move.
+
+``--dropout`` times the cfg1 training step (image branch frozen and whole network) with ``use_dropout=True`` against
+the same step with it off - 30 steps behind 5 warm-up steps each, the two models taking turns, three rounds - and the
+two dropout launches (csrc/dropout.hip) beside the launches they extend, on [P][512] rows: at cfg1's P and at 64 times
+that (past the last-level cache), events around 50 back-to-back launches, three runs.
 """
 import argparse
 import os
@@ -162,8 +168,91 @@ def time_optim(dev):
                                                            100 * n_el * 28 / (ms * 1e-3) / 1e12 / 6.29))
 
 
+def time_dropout(dev):
+    import numpy as np
+    from mmmot_amd.ops import HipOps
+    from mmmot_amd.plan import Segments
+    N, M, S, pts, ragged = SHAPES['cfg1 N=10 M=12 224x224']
+    dets, info, ds = make_pair(N, M, S, pts, seed=4000, ragged=ragged)
+    dets, info = dets.to(dev), {k: v.to(dev) for k, v in info.items()}
+    g = torch.Generator().manual_seed(1)
+    L = N + M
+    gt_det = (torch.rand(L, generator=g) > 0.3).float().to(dev)
+    gt_new, gt_end = (torch.rand(L, generator=g) > 0.6).float().to(dev), (torch.rand(L, generator=g) > 0.6).float().to(dev)
+    gt_link = [(torch.rand(1, N, M, generator=g) > 0.9).float().to(dev)]
+    crit = TrackingLoss(detloss_type='bce', linkloss_type='l2', det_ratio=1.5, trans_ratio=0.001)
+    models = {}
+    for flag in (False, True):
+        m = TrackingNet(**dict(bench.BASE_KW, score_fusion_arch='C', affinity_op='multiply', softmax_mode='none',
+                               use_dropout=flag))
+        init_module(m, seed=0)
+        models[flag] = (m.to(dev).train(), torch.optim.SGD(m.parameters(), lr=1e-4))
+
+    def steps(flag, n):
+        model, opt = models[flag]
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            det, links, new, end, trans = model(dets, info, ds)
+            loss = crit(ds, gt_det, gt_link, gt_new, gt_end, det, links, new, end, trans)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return sorted(ts)
+    for frozen in (True, False):
+        for flag in (False, True):
+            models[flag][0].freeze_appearance = frozen
+            steps(flag, 5)
+        for rnd in range(3):
+            for flag in (False, True):
+                ts = steps(flag, 30)
+                print('cfg1 %-19s round %d  use_dropout=%-5s step median %.2f ms, min %.2f ms, 90th percentile %.2f ms over 30' % (
+                    'image branch frozen' if frozen else 'whole network', rnd + 1, flag, ts[15] * 1e3, ts[0] * 1e3, ts[27] * 1e3))
+    # ---- the launches: [P][512] rows, cfg1's detections (and 64 copies of them: 440 MB, past the last-level cache) ----
+    ops = HipOps()
+    cnt1 = np.diff(info['points_split'].reshape(-1).cpu().numpy().astype(np.int64))
+    for copies in (1, 64):
+        cnt = np.tile(cnt1, copies)
+        P, Lt, C = int(cnt.sum()), len(cnt), 512
+        start = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+        segs = Segments(start, cnt, np.ones(Lt), np.zeros(Lt), dev)
+        X = torch.randn(P, C, device=dev)
+        sc, sh = torch.rand(1, C, device=dev) + 0.5, torch.randn(1, C, device=dev) * 0.1
+        out, dS, dX = torch.empty(Lt, C, device=dev), torch.randn(Lt, C, device=dev), torch.empty(P, C, device=dev)
+        row_det = torch.from_numpy(np.repeat(np.arange(Lt), cnt).astype(np.int32)).to(dev)
+        inv = torch.from_numpy((1.0 / cnt).astype(np.float32)).to(dev)
+        launches = [
+            ('segment_mean(relu)', lambda: ops.segment_mean(X, C, segs, out, sc=sc, sh=sh, relu=True)),
+            ('segment_mean_dropout', lambda: ops.segment_mean_dropout(X, C, segs, out, sc, sh, 12345, 0x80000000, 2.0)),
+            ('rows_gather_scale', lambda: ops.rows_gather_scale(dS, row_det, inv, dX, C)),
+            ('rows_gather_scale_dropout', lambda: ops.rows_gather_scale_dropout(dS, row_det, inv, dX, C, 12345, 0x80000000, 2.0)),
+        ]
+        print('[P][512] rows: P = %d in %d segments, %.1f MB' % (P, Lt, P * C * 4 / 1e6))
+        for name, fn in launches:
+            for _ in range(5):
+                fn()
+            ms = []
+            for run in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(50):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ms.append(e0.elapsed_time(e1) / 50)
+            med = sorted(ms)[1]
+            print('  %-26s %.4f / %.4f / %.4f ms a launch (three runs of 50), median %.2f TB/s of the tensor' % (
+                name, ms[0], ms[1], ms[2], P * C * 4 / (med * 1e-3) / 1e12))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--dropout', action='store_true', help='time the training step with use_dropout on against off, and '
+                    'the two dropout launches beside the launches they extend')
     ap.add_argument('--optim', action='store_true', help='time the optimizer step alone: torch.optim.Adam under the '
                     'wrapper against optim.Adam')
     ap.add_argument('--labels', action='store_true', help='time the label step (labels.generate_gt) alone')
@@ -171,6 +260,8 @@ def main():
     dev = torch.device('cuda', 0)
     if args.labels:
         return time_labels(dev)
+    if args.dropout:
+        return time_dropout(dev)
     if args.optim:
         return time_optim(dev)
     for name, (N, M, S, pts, ragged) in SHAPES.items():
