@@ -360,7 +360,11 @@ int mmmot_gn_finalize(const float* part, const int* grp_tile0, const int* grp_nt
  * seg_div (v2, may be NULL): divide the segment sum by seg_div[s] instead of count[s] (rows of X
  * that are already per-tile partial sums, see mmmot_gemm_args.colsum).
  * relu is a flag word (v4): bit 0 = ReLU after the affine, bit 1 = MAXIMUM over the segment instead of the
- * mean (end_mode 'max' of NewEndIndicator_v2, modules/new_end.py:72-74). */
+ * mean (end_mode 'max' of NewEndIndicator_v2, modules/new_end.py:72-74); seg_div does not enter a maximum.
+ * Every segment holds at least one row: count[s] >= 1 is the caller's to guarantee and is not checked (the counts
+ * live on the device).  The batch plan guarantees it - every frame has a detection, every detection a point, every
+ * pooling chunk a row (mmmot_amd/plan.py refuses anything else) - and the result for count[s] == 0 is unspecified
+ * (the mean would be 0 / 0, the maximum the accumulators' start value). */
 int mmmot_segment_mean(const float* X, int ldx, int C,
                        const int* seg_start, const int* seg_count, const int* seg_stride,
                        const int* seg_group, const int* seg_div, int nseg,
