@@ -515,6 +515,20 @@ int mmmot_u8_normalize(const unsigned char* u8, int N, int S, const float* mean_
 int mmmot_crop_resize_norm(const unsigned char* img, int H, int W, const int* boxes, int N, int S, int kmax,
                            const float* mean_std, int* work, float* out, unsigned char* out_u8, void* stream);
 
+/* Training augmentation of those 8-bit crops (reference utils/build_util.py:110-144 train_transform behind
+ * dataset/patchwise_dataset.py:161-171): per crop torchvision's resized_crop(img, top, left, h, w, (S, S), BILINEAR) -
+ * for a PIL image img.crop((left, top, left + w, top + h)).resize((S, S), BILINEAR) - then hflip when flip is set
+ * (out[.., x] = res[.., S - 1 - x]), then to_tensor + normalize.  Pillow's arithmetic as above; the region lies inside
+ * the crop, so there is no padding and at most 3 taps per output index.  One launch for all L crops, no scratch.
+ *   crops_u8 [L][S][S][3] uint8 (out_u8 of mmmot_crop_resize_norm)
+ *   params   [L][5] int, device: top, left, h, w, flip (0 | 1) with 0 <= top, 1 <= h, top + h <= S, the same for
+ *            left / w.  The caller validates the table; the kernel clamps a region to the crop all the same.
+ *   mean_std [6] floats (needed with out)
+ *   out      [L][3][S][S] fp32 model input, or NULL      out_u8 [L][S][S][3] the augmented 8-bit crop, or NULL (not both)
+ * MMMOT_EINVAL before any launch: crops_u8 or params NULL, both outputs NULL, L < 1, S < 1 or S > 256. */
+int mmmot_crop_augment(const unsigned char* crops_u8, const int* params, int L, int S, const float* mean_std,
+                       float* out, unsigned char* out_u8, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Training backward of the pairwise block (first slice; ABI 5): gradients of
  * affinity_module.forward + NewEndIndicator_v2.forward + the softmax modes of TrackingNet.associate

@@ -8,6 +8,10 @@ dataset/test_seq_dataset.py:212-218) with the valid-transform of utils/build_uti
 
 One launch pair for all detections of a frame (csrc/crop_resize.hip); the result is bit-identical to the
 Pillow / torchvision pipeline and stays on the device.  No CPU fallback.
+
+Training (dataset/patchwise_dataset.py:161-171 with the train-transform of utils/build_util.py:113-131): the same 8-bit
+crop, then ``augment_crops`` - RandomResizedCrop + RandomHorizontalFlip + ToTensor + Normalize for given parameters, one
+launch for all crops of a sample (csrc/crop_augment.hip; the parameters come from mmmot_amd.augment).
 """
 import math
 
@@ -59,3 +63,64 @@ def crop_resize_normalize(frame, bboxes, size=224, mean=MEAN, std=STD, return_u8
                                     torch.cuda.current_stream().cuda_stream)
     _lib.check(st, 'mmmot_crop_resize_norm')
     return u8 if only_u8 else ((out, u8) if return_u8 else out)
+
+
+def u8_normalize(crops_u8, mean=MEAN, std=STD):
+    """ToTensor + Normalize of device uint8 crops [L, S, S, 3] -> device fp32 [L, 3, S, S] (``mmmot_u8_normalize``): the
+    evaluation transform's second half, for the training-mode forward, which does not take the bytes"""
+    if not crops_u8.is_cuda:
+        raise RuntimeError('u8_normalize needs device crops; there is no CPU fallback')
+    if crops_u8.dtype != torch.uint8 or crops_u8.dim() != 4 or crops_u8.shape[3] != 3 or crops_u8.shape[1] != crops_u8.shape[2]:
+        raise TypeError('u8_normalize: crops_u8 must be uint8 [L, S, S, 3]')
+    lib = _lib.load()
+    crops_u8 = crops_u8.contiguous()
+    L, S = int(crops_u8.shape[0]), int(crops_u8.shape[1])
+    out = torch.empty(L, 3, S, S, dtype=torch.float32, device=crops_u8.device)
+    if L:
+        ms = torch.tensor(list(mean) + list(std), dtype=torch.float32, device=crops_u8.device)
+        _lib.check(lib.mmmot_u8_normalize(crops_u8.data_ptr(), L, S, _ptr(ms), _ptr(out),
+                                          torch.cuda.current_stream(crops_u8.device).cuda_stream), 'mmmot_u8_normalize')
+    return out
+
+
+def augment_crops(crops_u8, params, mean=MEAN, std=STD, return_u8=False):
+    """The reference's training transform (utils/build_util.py:113-131: RandomResizedCrop, RandomHorizontalFlip, ToTensor,
+    Normalize) of the 8-bit crops, with the random parameters given: crops_u8 device uint8 [L, S, S, 3] (``crop_resize_u8``),
+    params a host integer table [L, 5] of (top, left, h, w, flip) - ``augment.RandomResizedCropFlip.draw`` or
+    ``augment.identity_params``.  One launch for all crops (csrc/crop_augment.hip).  Returns device fp32 [L, 3, S, S], the
+    input of the training-mode forward; with ``return_u8`` also the augmented 8-bit crops [L, S, S, 3], bit for bit
+    Pillow's ``crop((left, top, left + w, top + h)).resize((S, S), BILINEAR)`` (``.transpose(FLIP_LEFT_RIGHT)``).  The
+    table is validated here, before anything is queued: ValueError for a region that leaves the crop."""
+    from .augment import check_params
+    if not torch.is_tensor(crops_u8) or crops_u8.dtype != torch.uint8 or crops_u8.dim() != 4 or crops_u8.shape[3] != 3 \
+            or crops_u8.shape[1] != crops_u8.shape[2]:
+        raise TypeError('augment_crops: crops_u8 must be uint8 [L, S, S, 3]')
+    L, S = int(crops_u8.shape[0]), int(crops_u8.shape[1])
+    if not 1 <= S <= 256:
+        raise ValueError('augment_crops: crops of side 1 .. 256, got %d' % S)
+    table = check_params(params, L, S)
+    if not crops_u8.is_cuda:
+        raise RuntimeError('augment_crops needs device crops; there is no CPU fallback')
+    lib = _lib.load()
+    crops_u8 = crops_u8.contiguous()
+    dev = crops_u8.device
+    out = torch.empty(L, 3, S, S, dtype=torch.float32, device=dev)
+    u8 = torch.empty(L, S, S, 3, dtype=torch.uint8, device=dev) if return_u8 else None
+    if L == 0:
+        return (out, u8) if return_u8 else out
+    # ONE upload: the table and the six floats behind it, in a pinned buffer of this call's own
+    stage = torch.empty(L * 5 + 6, dtype=torch.int32, pin_memory=True)
+    stage[:L * 5] = torch.from_numpy(table).reshape(-1)
+    stage[L * 5:].view(torch.float32).copy_(torch.tensor(list(mean) + list(std), dtype=torch.float32))
+    dbuf = stage.to(dev, non_blocking=True)
+    st = lib.mmmot_crop_augment(crops_u8.data_ptr(), _iptr(dbuf[:L * 5]), L, S, _ptr(dbuf[L * 5:].view(torch.float32)),
+                                _ptr(out), None if u8 is None else u8.data_ptr(),
+                                torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, 'mmmot_crop_augment')
+    return (out, u8) if return_u8 else out
+
+
+def crop_resize_augment(frame, bboxes, params, size=224, mean=MEAN, std=STD, return_u8=False):
+    """frame + boxes -> the augmented model input: ``crop_resize_u8`` then ``augment_crops`` (two resamplings with
+    Pillow's 8-bit crop between them, like the reference's dataset)."""
+    return augment_crops(crop_resize_u8(frame, bboxes, size), params, mean, std, return_u8)

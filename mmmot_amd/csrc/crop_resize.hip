@@ -9,14 +9,7 @@
 // compiled for baseline x86-64), normalised, 22-bit fixed point, two separable passes with an 8-bit
 // intermediate - so the uint8 result and the float32 tensor are bit-identical to the reference pipeline.
 // Byte work, HBM-bound on the float32 output (3*S*S*4 B per detection); crops are read through L2.
-#include "common.h"
-
-#define CR_PREC 22
-
-__device__ __forceinline__ double cr_tri(double x) {
-  if (x < 0.0) x = -x;
-  return x < 1.0 ? __dsub_rn(1.0, x) : 0.0;
-}
+#include "crop_coeff.h"  // cr_tri, cr_coeffs, cr_clip8, cr_norm: shared with crop_augment.hip
 
 // grid (N, 2): axis 0 = horizontal (crop width), 1 = vertical (crop height); thread = output index.
 // work layout per (n, axis): bounds [S][2] ints, then kk [S][kmax] ints.
@@ -34,34 +27,7 @@ __global__ void cr_coeff_kernel(const int* __restrict__ boxes, int S, int kmax, 
     bounds[1] = 0;
     return;
   }
-  const double scale = __ddiv_rn((double)(float)in_size, (double)S);
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = filterscale;  // 1.0 * filterscale
-  const double ss = __ddiv_rn(1.0, filterscale);
-  const double center = __dmul_rn(__dadd_rn((double)xx, 0.5), scale);  // in0 = 0
-  int xmin = (int)__dadd_rn(__dsub_rn(center, support), 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)__dadd_rn(__dadd_rn(center, support), 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) {
-    const double w = cr_tri(__dmul_rn(__dadd_rn(__dsub_rn((double)(x + xmin), center), 0.5), ss));
-    ww = __dadd_rn(ww, w);
-  }
-  for (int x = 0; x < xmax; ++x) {
-    double w = cr_tri(__dmul_rn(__dadd_rn(__dsub_rn((double)(x + xmin), center), 0.5), ss));
-    if (ww != 0.0) w = __ddiv_rn(w, ww);
-    kk[x] = (int)__dadd_rn(0.5, __dmul_rn(w, (double)(1 << CR_PREC)));  // triangle weights are >= 0
-  }
-  for (int x = xmax; x < kmax; ++x) kk[x] = 0;
-  bounds[0] = xmin;
-  bounds[1] = xmax;
-}
-
-__device__ __forceinline__ int cr_clip8(int acc) {
-  const int v = acc >> CR_PREC;  // arithmetic shift, like Pillow's lookup on in >> PRECISION_BITS
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
+  cr_coeffs(in_size, S, xx, kmax, bounds, kk);
 }
 
 // grid (N, S): one output row per workgroup, one output column per thread.
@@ -105,8 +71,7 @@ __global__ __launch_bounds__(256) void cr_resize_kernel(const unsigned char* __r
     const int v8 = cr_clip8(acc[c]);
     if (out_u8) out_u8[(((long)n * S + oy) * S + ox) * 3 + c] = (unsigned char)v8;
     if (out) {
-      const float x = __fdiv_rn((float)v8, 255.f);                       // to_tensor
-      out[(((long)n * 3 + c) * S + oy) * S + ox] = __fdiv_rn(__fsub_rn(x, ms[c]), ms[3 + c]);  // normalize
+      out[(((long)n * 3 + c) * S + oy) * S + ox] = cr_norm(v8, ms[c], ms[3 + c]);  // to_tensor, normalize
     }
   }
 }
@@ -132,8 +97,7 @@ __global__ __launch_bounds__(256) void cr_u8_normalize_kernel(const unsigned cha
     const int r = (int)(p - n * S2);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float x = __fdiv_rn((float)u8[p * 3 + c], 255.f);
-      out[(n * 3 + c) * S2 + r] = __fdiv_rn(__fsub_rn(x, ms[c]), ms[3 + c]);
+      out[(n * 3 + c) * S2 + r] = cr_norm(u8[p * 3 + c], ms[c], ms[3 + c]);
     }
   }
 }

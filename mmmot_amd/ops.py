@@ -162,6 +162,13 @@ class HipOps:
         st = self.lib.mmmot_u8_normalize(_ptr(crops_u8, torch.uint8), N, S, _ptr(mean_std), _ptr(out), self._stream())
         _lib.check(st, 'mmmot_u8_normalize')
 
+    def crop_augment(self, crops_u8, params, mean_std, out, out_u8, L, S):
+        """random-resized-crop + flip + ToTensor / Normalize of the 8-bit crops [L][S][S][3]: params the device int32
+        [L][5] table (top, left, h, w, flip); out fp32 [L][3][S][S] and / or out_u8 [L][S][S][3]"""
+        st = self.lib.mmmot_crop_augment(_ptr(crops_u8, torch.uint8), _iptr(params), L, S, _ptr(mean_std), _ptr(out),
+                                         _ptr(out_u8, torch.uint8), self._stream())
+        _lib.check(st, 'mmmot_crop_augment')
+
     def trunk_range_read(self, device, reset=True):
         """(e4m3-saturated, fp16-clamped, conv1_1 hits, 0) activation-element counters of the trunk epilogues on
         ``device`` since the last reset; synchronises the current stream (see mmmot_trunk_range_read)."""

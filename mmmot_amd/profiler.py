@@ -134,6 +134,9 @@ COSTS = {
     'fusion_combine': _latency('fusion combine'),
     'softmax_pairs': _latency('pair softmax'),
     'u8_normalize': _latency('8-bit crops -> fp32'),
+    # crops_u8, params, mean_std, out, out_u8, L, S: reads the bytes once, writes the fp32 tensor and / or the bytes
+    'crop_augment': lambda a, k: ('augmented 8-bit crops -> fp32', 0.0,
+                                  1.0 * a[5] * a[6] * a[6] * (3 + (12 if a[3] is not None else 0) + (3 if a[4] is not None else 0))),
     'hq8_pack': _latency('hq8 / hl16 re-encode'), 'hq8_unpack': _latency('hq8 / hl16 re-encode'),
     'hl16_pack': _latency('hq8 / hl16 re-encode'), 'hl16_unpack': _latency('hq8 / hl16 re-encode'),
 }

@@ -7,6 +7,15 @@ ragged ~300 pts/det) and at a cfg2-like sample (N=M=32, 64x64 crops, 512 pts/det
     python tools/bench_train.py --labels    # the label step alone on the same samples
     python tools/bench_train.py --optim     # the optimizer step alone at the full model's 216 tensors
     python tools/bench_train.py --dropout   # the step with use_dropout on against off, and the two dropout launches
+    python tools/bench_train.py --feed      # the training feed: step alone, TrainingPipeline.run serial / overlapped
+
+``--feed`` builds 8 two-frame samples of cfg1's shape from ``synth.make_sequence`` (poses, jittered boxes, 224 x 224
+crops, random-resized-crop + flip) and times (a) ``TrainingPipeline.step`` alone on one prepared sample (30 steps behind
+5, a device synchronise inside the timed window, three runs), (b) ``run`` over 16 samples with ``overlap=False`` and (c)
+with ``overlap=True`` (wall clock per step, the two taking turns, three runs), ``prepare`` alone, and the augment launch
+alone (events around 50 back-to-back launches at the sample's L and at 32 copies of it) as GB/s of the 15 bytes a pixel it
+must move.  The step is the whole network under the one-launch Adam; the default mode's step (SGD on ``make_pair``
+inputs) is the yardstick for (a).
 
 ``--labels`` times mmmot_amd.labels.generate_gt alone instead of the step, class / id tensors and targets on the device
 as in the reference's ``step``.  The reference's own host loop is not timed here: the repository holds no copy of it.
@@ -249,8 +258,107 @@ def time_dropout(dev):
                 name, ms[0], ms[1], ms[2], P * C * 4 / (med * 1e-3) / 1e12))
 
 
+def time_feed(dev):
+    import numpy as np
+    from mmmot_amd import augment, build_optim
+    from mmmot_amd.crops import crop_resize_u8
+    from mmmot_amd.ops import HipOps
+    from mmmot_amd.pipeline import FrameFeed
+    from mmmot_amd.synth import make_sequence
+    from mmmot_amd.train_pipeline import TrainingPipeline, TrainSample
+    S, NS = 224, 8
+    frames = make_sequence(NS + 1, 4000, ego=1)  # cfg1's shape: 10-12 detections, 120k-point sweeps, 375 x 1242 frames
+    rng = np.random.default_rng(1)
+
+    def sample(fr):
+        feeds = [FrameFeed(img, sweep, info, dets, pose=(info['pos'], info['rad'])) for img, sweep, info, dets in fr]
+        gts = [{'bbox': f[3]['bbox'], 'id': np.arange(len(f[3]['bbox'])), 'name': np.zeros(len(f[3]['bbox']), np.int64)}
+               for f in fr]
+        return TrainSample(feeds, gts, [f[3]['bbox'] + rng.uniform(-3, 3, f[3]['bbox'].shape) for f in fr])
+    samples = [sample(frames[k:k + 2]) for k in range(NS)]
+    cfg = dict(lr_scheduler=dict(optim='Adam', base_lr=3e-4), weight_decay=0.01, fixed_wd=True)
+    crit = TrackingLoss(detloss_type='bce', linkloss_type='l2', det_ratio=1.5, trans_ratio=0.001)
+
+    def pipe(overlap):
+        model = TrackingNet(**dict(bench.BASE_KW, score_fusion_arch='C', affinity_op='multiply', softmax_mode='none'))
+        init_module(model, seed=0)
+        model.to(dev).train()
+        return TrainingPipeline(model, crit, build_optim(model, cfg), size=S, augment=augment.RandomResizedCropFlip(S),
+                                seed=0, overlap=overlap)
+    pipes = {False: pipe(False), True: pipe(True)}
+    L = sum(len(f.dets['bbox']) for f in samples[0].feeds)
+    print('training feed, cfg1 shape: %d samples of 2 frames, %d crops of %d x %d in the first' % (NS, L, S, S))
+    # (a) the step alone on one prepared sample
+    for run in range(3):
+        p = pipes[False]
+        prepared = p.prepare(samples[0])
+        ts = []
+        for it in range(35):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            loss = p.step(prepared)
+            torch.cuda.synchronize()
+            if it >= 5:
+                ts.append(time.perf_counter() - t0)
+        ts.sort()
+        print('(a) run %d  step alone on a prepared sample: median %.2f ms, min %.2f ms, 90th percentile %.2f ms over 30; '
+              'loss %.4f' % (run + 1, ts[15] * 1e3, ts[0] * 1e3, ts[27] * 1e3, loss.item()))
+    # (b) / (c): run() over the samples, serial and overlapped, taking turns
+    for p in pipes.values():
+        p.run(samples)
+    for run in range(3):
+        for overlap in (False, True):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            losses = pipes[overlap].run(samples + samples)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            assert bool(torch.isfinite(losses).all())
+            print('(%s) run %d  run(overlap=%-5s): %.2f ms a step over %d steps (prepare + step, wall clock)' % (
+                'c' if overlap else 'b', run + 1, overlap, dt / (2 * NS) * 1e3, 2 * NS))
+    # prepare alone, serial: what (b) adds to (a)
+    ts = []
+    for it in range(12):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pipes[False].prepare(samples[it % NS])
+        torch.cuda.synchronize()
+        if it >= 2:
+            ts.append(time.perf_counter() - t0)
+    ts.sort()
+    print('prepare alone (serial, synchronised): median %.2f ms, min %.2f ms over 10' % (ts[5] * 1e3, ts[0] * 1e3))
+    # the augment launch alone: at the sample's L and at 32 copies of it (past the last-level cache)
+    ops = HipOps()
+    ms_ = torch.tensor([0.485, 0.456, 0.406, 0.229, 0.224, 0.225], device=dev)
+    u8 = torch.cat([crop_resize_u8(f.img.to(dev), b, S) for f, b in zip(samples[0].feeds, samples[0].boxes)])
+    for copies in (1, 32):
+        x = u8.repeat(copies, 1, 1, 1)
+        Lc = int(x.shape[0])
+        table = torch.from_numpy(augment.RandomResizedCropFlip(S).draw(Lc, torch.Generator().manual_seed(2))).to(dev)
+        out = torch.empty(Lc, 3, S, S, device=dev)
+        nbytes = Lc * S * S * (3 + 12)
+        for _ in range(5):
+            ops.crop_augment(x, table, ms_, out, None, Lc, S)
+        rates = []
+        for run in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(50):
+                ops.crop_augment(x, table, ms_, out, None, Lc, S)
+            e1.record()
+            torch.cuda.synchronize()
+            ms = e0.elapsed_time(e1) / 50
+            rates.append(nbytes / (ms * 1e-3) / 1e9)
+            print('augment launch, L = %d: run %d  %.4f ms a launch over 50 back-to-back launches, %.0f GB/s of the %.1f MB it '
+                  'must move, %.1f %% of the 6.29 TB/s copy rate' % (Lc, run + 1, ms, rates[-1], nbytes / 1e6,
+                                                                    100 * rates[-1] / 6290))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--feed', action='store_true', help='time the training feed: the step alone, TrainingPipeline.run '
+                    'serial and overlapped, and the augment launch alone')
     ap.add_argument('--dropout', action='store_true', help='time the training step with use_dropout on against off, and '
                     'the two dropout launches beside the launches they extend')
     ap.add_argument('--optim', action='store_true', help='time the optimizer step alone: torch.optim.Adam under the '
@@ -258,6 +366,8 @@ def main():
     ap.add_argument('--labels', action='store_true', help='time the label step (labels.generate_gt) alone')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
+    if args.feed:
+        return time_feed(dev)
     if args.labels:
         return time_labels(dev)
     if args.dropout:
