@@ -128,8 +128,10 @@ __device__ __forceinline__ void mm_stage(const float* __restrict__ As, const flo
 }
 
 // C/D mapping of the 32x32 MFMA: lane l, register e holds
-// row = (e&3) + 8*(e>>2) + 4*(l>>5), col = l&31.
-__device__ __forceinline__ int mm_acc_row(int e, int lane) { return (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5); }
+// row = mm_acc_row0(e) + 4*(l>>5), col = l&31.  mm_acc_row0 is the lane-independent part (a compile-time constant in
+// an unrolled loop over e).
+constexpr int mm_acc_row0(int e) { return (e & 3) + 8 * (e >> 2); }
+__device__ __forceinline__ int mm_acc_row(int e, int lane) { return mm_acc_row0(e) + 4 * (lane >> 5); }
 
 // ---- register epilogues of a 64-row x 32-channel wave tile (two 32x32 accumulators; a lane holds 32 of its column's
 // 64 rows, lane ^ 32 the other 32).  The half-wave exchange is v_permlane32_swap (gfx950), a VALU instruction, instead of
@@ -182,6 +184,15 @@ __device__ __forceinline__ float mm_relu_sum32(const f32x16& a, const f32x16& b,
 #pragma unroll
   for (int e = 0; e < 16; ++e) s += fmaxf(fmaf(b[e], m1, m0), 0.f);
   return s;
+}
+
+// Largest magnitude handed to the fp16 `hi` half of an hl16 split (fp16 overflows to inf above 65504).
+#define MM_F16_CLAMP 65000.f
+
+// Prologue value of the normalise + ReLU kernels: relu(x * s + h), clamped to the fp16 range.  Zeroing rows past a
+// tile's end and the hi / lo split (mm_split2) are the caller's.
+__device__ __forceinline__ float mm_norm_relu(float x, float s, float h) {
+  return fminf(fmaxf(fmaf(x, s, h), 0.f), MM_F16_CLAMP);
 }
 
 // lo half of the hl16 split of one value, given its hi half (f16)y: (f16)(y - (float)hi) - convert back, subtract, convert

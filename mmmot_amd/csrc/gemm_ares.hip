@@ -21,10 +21,10 @@
 // at 34 % of the ceiling, LDS-read bound (a weight-resident variant, a deferred epilogue and counted-vmcnt role copies
 // all left it there).  Now a wave owns 64 rows x 64 channels (channel tile 256, weight stage 256 channels x 32 k = the
 // same 32 KB): 4 + 4 fragment reads feed 12 MFMAs.
-#include <cstdlib>
+#include <atomic>
 #include <type_traits>
 
-#include "common.h"
+#include "ares_common.h"
 
 #define AR_BM 128
 #define AR_BN 256   // channels per channel tile: a wave owns 64 rows x 64 channels (2 x 2 MFMA blocks)
@@ -33,8 +33,6 @@
 #define AR_LDB 40   // halves per LDS row of a weight stage (32 k + pad: 80 B - 16 consecutive rows hit 16 distinct
                     // 16-byte bank groups)
 #define AR_THREADS 512
-
-static __device__ float ar_zeros[4096];  // stands in for absent bias / dbias / osc / osh rows (branch-free loads)
 
 // KS = K / 64; MODE bit 0: statistics (part), bit 1: normalise + ReLU + column sums (colsum).
 // Every global load of the K loop is unconditional (indices clamped at the end): with a fixed number of
@@ -61,34 +59,10 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
   // wraps around (stage NS continues with stage 0 of the next tile), the next tile's activation rows are
   // fetched into registers during the current tile's last stages, so a tile switch costs one conversion
   // pass + one barrier instead of a cold prologue (measured fixed cost before: 8 us of a 31 us tile).
-  struct TileMeta {
-    int row0, nrows, grp, dbrow;
-  };
-  auto meta_of = [&](int tt) {
-    TileMeta m;
-    m.row0 = a.tile_row0[tt];
-    m.nrows = a.tile_nrows[tt];
-    // unconditional loads (an absent table reads tile_row0 instead, discarded in scalar()): a conditional load makes
-    // the number of loads in flight path-dependent and turns later counted waits into vmcnt(0)
-    m.grp = (a.tile_group ? a.tile_group : a.tile_row0)[tt];
-    m.dbrow = (a.dbias ? a.tile_dbrow : a.tile_row0)[tt];
-    return m;
-  };
-  // the table words are wave-uniform: held as scalars, and those of tile t + 2 * gridDim.x are requested a whole tile
-  // before they are needed (a lookup at the tile switch is two dependent L2 round trips in front of the switch, and
-  // its vmcnt(0) also drains the two weight stages that are meant to stay in flight)
-  auto scalar = [&](const TileMeta& v) {
-    TileMeta m;
-    m.row0 = __builtin_amdgcn_readfirstlane(v.row0);
-    m.nrows = __builtin_amdgcn_readfirstlane(v.nrows);
-    m.grp = a.tile_group ? __builtin_amdgcn_readfirstlane(v.grp) : 0;
-    m.dbrow = a.dbias ? __builtin_amdgcn_readfirstlane(v.dbrow) : 0;
-    return m;
-  };
   int t = blockIdx.x;
   if (t >= a.T) return;
   const int gstep = gridDim.x;
-  TileMeta cur = scalar(meta_of(t));
+  AresTile cur = ares_tile_scalar(a, ares_tile_request(a, t));  // (ares_common.h)
 
   // ---- wave roles.  vmcnt retires in order PER WAVE: activation rows (HBM, a CU completes only ~30 line misses
   // per microsecond) requested by a wave that also stages weights sit in front of every weight-stage wait, and
@@ -126,7 +100,7 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
   // ---- activation rows (waves 4-7): raw rows -> registers (load_x), normalise + ReLU + hi/lo split -> LDS (stage_a)
   // thread tx -> (rows tx >> 2 and (tx >> 2) + 64, quarter q of the K axis: 16 * KS consecutive channels)
   const int ar = (tid & 255) >> 2, aq = tid & 3;
-  auto load_x = [&](const TileMeta& m) {
+  auto load_x = [&](const AresTile& m) {
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       const int row = ar + 64 * r;
@@ -138,7 +112,7 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
       }
     }
   };
-  auto stage_a = [&](const TileMeta& m) {
+  auto stage_a = [&](const AresTile& m) {
     const float* psc = a.sc + (long)m.grp * a.ldsc + aq * (16 * KS);
     const float* psh = a.sh + (long)m.grp * a.ldsc + aq * (16 * KS);
 #pragma unroll
@@ -155,8 +129,8 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
         float y[8];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          y[e] = fminf(fmaxf(fmaf(x0[e], s0[e], h0[e]), 0.f), 65000.f);
-          y[4 + e] = fminf(fmaxf(fmaf(x1[e], s1[e], h1[e]), 0.f), 65000.f);
+          y[e] = mm_norm_relu(x0[e], s0[e], h0[e]);
+          y[4 + e] = mm_norm_relu(x1[e], s1[e], h1[e]);
           if (!rv) y[e] = y[4 + e] = 0.f;
         }
 #pragma unroll
@@ -207,12 +181,11 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
 
     // per-tile epilogue state (set by begin_tile)
     int nrows = 0, nsub = 0, grp = 0;
-    int lim = 0;  // accumulator element (tm, e) is a valid row <=> tm * 32 + (e & 3) + 8 * (e >> 2) < lim (immediates
-                  // against one register instead of 32 hoisted row indices)
+    int lim = 0;  // valid rows of the half tile - 4 * (lane >> 5): the masked epilogue's bound (ares_common.h)
     float inv_nsub = 0.f;
     long prow = 0;
     bool full = false;
-    const float* pbias = a.bias ? a.bias : ar_zeros;
+    const float* pbias = a.bias ? a.bias : ares_zeros;
     // per-channel epilogue constants of a channel tile (two 32-channel blocks per wave): combined bias, output scale /
     // shift.  They are loaded one channel tile ahead (for the last channel tile: those of the NEXT row tile) and BEFORE
     // the weight loads of that stage: vmcnt retires in order, so a load issued at epilogue time would also wait
@@ -220,10 +193,10 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
     struct EpiC {
       float cb[2], os[2], oh[2];
     };
-    auto epi_consts = [&](const TileMeta& m, int nt, EpiC& c) {
-      const float* pdb = a.dbias ? a.dbias + (long)m.dbrow * a.lddb : ar_zeros;
-      const float* posc = (MODE & 2) ? a.osc + (long)m.grp * a.ldosc : ar_zeros;
-      const float* posh = (MODE & 2) ? a.osh + (long)m.grp * a.ldosc : ar_zeros;
+    auto epi_consts = [&](const AresTile& m, int nt, EpiC& c) {
+      const float* pdb = a.dbias ? a.dbias + (long)m.dbrow * a.lddb : ares_zeros;
+      const float* posc = (MODE & 2) ? a.osc + (long)m.grp * a.ldosc : ares_zeros;
+      const float* posh = (MODE & 2) ? a.osh + (long)m.grp * a.ldosc : ares_zeros;
   #pragma unroll
       for (int tn = 0; tn < 2; ++tn) {
         const int n = nt * AR_BN + wn * 64 + tn * 32 + lr;
@@ -235,9 +208,9 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
     EpiC ec, en;
     epi_consts(cur, 0, ec);
     en = ec;
-    TileMeta nxt = cur, raw2 = cur;
-    if (t + gstep < a.T) nxt = scalar(meta_of(t + gstep));
-    auto begin_tile = [&](const TileMeta& m, int tt) {
+    AresTile nxt = cur, raw2 = cur;
+    if (t + gstep < a.T) nxt = ares_tile_scalar(a, ares_tile_request(a, t + gstep));
+    auto begin_tile = [&](const AresTile& m, int tt) {
       nrows = m.nrows;
       grp = m.grp;
       nsub = min(max(nrows - 64 * wm, 0), 64);  // valid rows of this wave's half tile
@@ -258,7 +231,7 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
       const int nt = s / SPT;
       if constexpr (kq == 0) {
         const bool last_nt = nt + 1 >= ntn;  // then: first channel tile of the next row tile (same loads, other rows)
-        TileMeta m = cur;
+        AresTile m = cur;
         if (last_nt) m = nxt;
         // (handing these constants from waves 0-3 to waves 4-7 through LDS, so that they do not queue behind the
         // activation rows, measured slower than loading them in every wave)
@@ -328,57 +301,21 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
   #undef AR_MM
       if constexpr (kq == SPT - 1) {
         // ---- channel tile nt finished: register-only epilogue for this wave's 64 rows x 2 x 32 channels ----
-        // v = acc*oscale + cb is never formed for full half tiles: the sums are taken on the raw accumulators
-        // and rescaled (S = oscale*sum(acc) + n*cb, M2 = oscale^2 * M2(acc), relu(v*os+oh) = relu(acc*(oscale*os)
-        // + (cb*os+oh))); 3 VALU ops per value.
+        // (sums on the raw accumulators, rescaled here: ares_common.h)
   #pragma unroll
         for (int tn = 0; tn < 2; ++tn) {
           const int n = nt * AR_BN + wn * 64 + tn * 32 + lr;
           const float cb = ec.cb[tn], os = ec.os[tn], oh = ec.oh[tn];  // fetched one channel tile ahead
           if constexpr (MODE & 1) {
-            float s1 = 0.f;
-            if (full) {
-              s1 = mm_sum32(acc[0][tn], acc[1][tn]);
-            } else {
-  #pragma unroll
-              for (int tm = 0; tm < 2; ++tm)
-  #pragma unroll
-                for (int e = 0; e < 16; ++e)
-                  if (tm * 32 + (e & 3) + 8 * (e >> 2) < lim) s1 += acc[tm][tn][e];
-            }
-            s1 = mm_xor32_sum(s1);
-            const float mu = s1 * inv_nsub;  // mean of the raw accumulators over the half tile
-            float s2 = 0.f;
-            if (full) {
-              s2 = mm_m2_32(acc[0][tn], acc[1][tn], mu);
-            } else {
-  #pragma unroll
-              for (int tm = 0; tm < 2; ++tm)
-  #pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                  const float d = acc[tm][tn][e] - mu;
-                  if (tm * 32 + (e & 3) + 8 * (e >> 2) < lim) s2 = fmaf(d, d, s2);
-                }
-            }
-            s2 = mm_xor32_sum(s2);
+            float s1, s2;
+            ares_half_stats(acc[0][tn], acc[1][tn], full, lim, inv_nsub, s1, s2);
             if (lane < 32) {
               a.part[(prow * 2 + 0) * a.N + n] = fmaf(s1, a.oscale, (float)nsub * cb);
               a.part[(prow * 2 + 1) * a.N + n] = s2 * a.oscale * a.oscale;
             }
           }
           if constexpr (MODE & 2) {
-            const float m1 = a.oscale * os, m0 = fmaf(cb, os, oh);
-            float s3 = 0.f;
-            if (full) {
-              s3 = mm_relu_sum32(acc[0][tn], acc[1][tn], m1, m0);
-            } else {
-  #pragma unroll
-              for (int tm = 0; tm < 2; ++tm)
-  #pragma unroll
-                for (int e = 0; e < 16; ++e)
-                  if (tm * 32 + (e & 3) + 8 * (e >> 2) < lim) s3 += fmaxf(fmaf(acc[tm][tn][e], m1, m0), 0.f);
-            }
-            s3 = mm_xor32_sum(s3);
+            const float s3 = ares_half_relu_sum(acc[0][tn], acc[1][tn], full, lim, a.oscale * os, fmaf(cb, os, oh));
             if (lane < 32) a.colsum[prow * a.N + n] = s3;
           }
         }
@@ -394,7 +331,7 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
       // but the small per-channel constants)
       // table words of the tile after the next: unconditional (clamped) so that the number of loads in flight stays fixed;
       // consumed a whole tile later
-      raw2 = meta_of(more2 ? tn + gstep : tn < a.T ? tn : t);
+      raw2 = ares_tile_request(a, more2 ? tn + gstep : tn < a.T ? tn : t);
       for (int s = 0; s < NS; s += SPT) {
         if constexpr (!WS)
           if (more && s == 0) load_x(nxt);
@@ -410,7 +347,7 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
       if constexpr (!WS) stage_a(nxt);
       __syncthreads();  // NS is even: the LDS buffer parity of stage 0 repeats, the weight stream simply continues
       cur = nxt;
-      if (more2) nxt = scalar(raw2);
+      if (more2) nxt = ares_tile_scalar(a, raw2);
       t = tn;
       begin_tile(cur, t);
     }
@@ -419,9 +356,14 @@ __global__ __launch_bounds__(AR_THREADS) void gemm_ares_kernel(mmmot_gemm_ares_a
   else run(std::false_type{});
 }
 
-int mmmot_gemm_wres64_launch(const mmmot_gemm_ares_args* a, int mode, int n_cu, hipStream_t s);  // gemm_wres.hip
-int mmmot_gemm_wreg128_try(const mmmot_gemm_ares_args* a, int mode, int n_cu, hipStream_t s, int* status);  // gemm_wreg.hip
-int mmmot_ares_variant();                                                                                  // gemm_wreg.hip
+static std::atomic<int> g_ares_variant{0};
+// Test knob (include/mmmot_hip.h; the values are explained at mmmot_ares_choose, ares_choice.h).  Results do not depend
+// on it (bit for bit).
+extern "C" int mmmot_set_gemm_ares_variant(int v) {
+  if (v < 0 || v > 3) return MMMOT_EINVAL;
+  g_ares_variant.store(v);
+  return MMMOT_OK;
+}
 
 extern "C" int mmmot_gemm_ares(const mmmot_gemm_ares_args* a, void* stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -436,18 +378,11 @@ extern "C" int mmmot_gemm_ares(const mmmot_gemm_ares_args* a, void* stream) {
   const int mode = (a->part ? 1 : 0) | (a->colsum ? 2 : 0);
   const int n_cu = mm_num_cu();
   if (n_cu <= 0) return MMMOT_EINVAL;
-  // K = 64 with the whole weight matrix in LDS (N <= 512): the weight-resident kernel; MMMOT_ARES_WRES=0 (read once)
-  // keeps the streaming kernel for A/B timing (tools/bench_ares.py)
-  static const bool use_wres = [] {
-    const char* e = getenv("MMMOT_ARES_WRES");
-    return !(e && e[0] == '0');
-  }();
-  const bool stream_only = mmmot_ares_variant() == 1 && a->N % AR_BN == 0;  // mmmot_set_gemm_ares_variant(1)
-  if (use_wres && !stream_only && a->K == 64 && a->N <= 512) return mmmot_gemm_wres64_launch(a, mode, n_cu, s);
-  // K = 128 consumer pass on a launch that fills the chip: the wave's weights live in registers (gemm_wreg.hip)
-  int wst = MMMOT_OK;
-  if (mmmot_gemm_wreg128_try(a, mode, n_cu, s, &wst)) return wst;
-  if (a->N % AR_BN != 0) return MMMOT_EINVAL;  // the streaming kernel walks 256-channel tiles
+  const mmmot_ares_kernel which = mmmot_ares_choose(a, mode, n_cu, g_ares_variant.load());
+  if (which == ARES_REFUSE) return MMMOT_EINVAL;
+  if (which == ARES_WEIGHT_RESIDENT || which == ARES_INDEPENDENT_WAVE)
+    return mmmot_gemm_wres64_launch(a, mode, which == ARES_INDEPENDENT_WAVE, n_cu, s);
+  if (which == ARES_WEIGHTS_IN_REGISTERS) return mmmot_gemm_wreg128_launch(a, n_cu, s);
   const int grid = a->T < n_cu ? a->T : n_cu;  // persistent: one workgroup per CU
 #define AR_LAUNCH(KSV, MODEV) \
   hipLaunchKernelGGL((gemm_ares_kernel<KSV, MODEV>), dim3(grid), dim3(AR_THREADS), 0, s, *a)

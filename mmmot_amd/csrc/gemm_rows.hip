@@ -171,7 +171,7 @@ __global__ __launch_bounds__(MM_THREADS, 2) void gemm_rows_kernel(mmmot_gemm_arg
         const f32x4 x0 = a_value(i, 0), x1 = a_value(i, 1);
         // fp16 range clamp and the zeroing of rows beyond the tile in ONE v_med3_f32 per value (bound 0 for such rows;
         // NORM_RELU values are >= 0 already, so the lower bound does no harm there)
-        const float top = rval[i] ? 65000.f : 0.f;
+        const float top = rval[i] ? MM_F16_CLAMP : 0.f;
         u32x4 h, l;
         float y[8];
 #pragma unroll

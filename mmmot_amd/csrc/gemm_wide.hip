@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256 * NH, 2 / NH) void gemm_wide_kernel(mmmot_gemm_
     const int r = wq * 32 + lr;
     const bool ok = r < I.nrows;
     const int rr = ok ? r : 0;
-    S.top = ok ? 65000.f : 0.f;
+    S.top = ok ? MM_F16_CLAMP : 0.f;
     if constexpr (AMODE == MMMOT_A_PAIR) {
       const int q = I.row0 + rr - a.grp_row0[I.grp];
       const int M = a.grp_M[I.grp];

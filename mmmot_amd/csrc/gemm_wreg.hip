@@ -24,14 +24,9 @@
 // pinned in place with scheduling barriers; one __syncthreads per half tile.  Round 4 history (profiles/README.md):
 // converting at the tile switch and summing after each block, all waves together, left the matrix pipe idle for a
 // quarter of the launch (3.0 ms per 4.2 M points, 46 % MFMA-busy); this form 2.44 ms.
-#include <atomic>
-#include <cstdlib>
-
-#include "common.h"
+#include "ares_common.h"
 
 #define WR_K 128
-
-static __device__ float wr_zeros[4096];  // stands in for absent bias / dbias rows (branch-free loads)
 
 #define WP_ROWS 64
 #define WP_PLANE (WP_ROWS * 256)  // one fp16 plane [64 rows][128 k]: 16 KB
@@ -74,32 +69,13 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
       }
     }
   }
-  const float* pbias = a.bias ? a.bias : wr_zeros;
+  const float* pbias = a.bias ? a.bias : ares_zeros;
 
   // the table words of a tile (wave-uniform: scalar registers), fetched a tile ahead of their first use
-  struct Tile {
-    int t, row0, nrows, grp, dbrow;
+  struct Tile : AresTile {
+    int t;
   };
-  // (scalar loads written out: the compiler turns these table reads into VECTOR loads - the kernel stores to global
-  // memory, so it will not treat them as constant - and then waits vmcnt(0) for them, i.e. for every LDS-DMA request
-  // in flight, right after the requests were issued)
-  // tile-table words of tile t by scalar loads (mm_sload4, common.h); optional tables read a valid word (the tile's row0)
-  // and are replaced by 0 afterwards
-  auto tile_info = [&](int t) {
-    Tile w;
-    w.t = t;
-    const int* p0 = a.tile_row0 + t;
-    const int* p1 = a.tile_nrows + t;
-    const int* p2 = a.tile_group ? a.tile_group + t : p0;
-    const int* p3 = a.dbias ? a.tile_dbrow + t : p0;
-    int v0, v1, v2, v3;
-    mm_sload4(p0, p1, p2, p3, v0, v1, v2, v3);
-    w.row0 = v0;
-    w.nrows = v1;
-    w.grp = a.tile_group ? v2 : 0;
-    w.dbrow = a.dbias ? v3 : 0;
-    return w;
-  };
+  auto tile_info = [&](int t) { return Tile{ares_tile_sload(a, t), t}; };
   // raw rows of half h of a tile -> Raw[h]: 4 instructions of 1 KB (2 rows) per wave; rows past the tile read its first row
   // (addresses: a wave-uniform base pointer plus a 32-bit lane offset, nothing 64-bit per lane kept across the loop)
   auto dma_unit = [&](const Tile& w, int h) {
@@ -128,7 +104,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
     c.h = *reinterpret_cast<const f32x2*>(SC + sci * 256 + 128 + kc * 8 + 2 * part);
   };
   auto conv_val = [&](Conv& c, int e, int part, bool rv) {
-    float y = fminf(fmaxf(fmaf(c.x[e], c.s[e], c.h[e]), 0.f), 65000.f);
+    float y = mm_norm_relu(c.x[e], c.s[e], c.h[e]);
     if (!rv) y = 0.f;
     c.x[e] = y;  // (the raw value is dead: its register carries the normalised one to the split)
     if (e == 1) {  // both values of the piece are there: hi = one v_cvt_pk, lo = one v_fma_mix per value (common.h)
@@ -185,7 +161,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
     const unsigned off = (unsigned)(lv & 15) * 4u;
     const int g = lv >> 4;
     if (g == 0) mm_dma16(pbias + nbase + off, dst);
-    else if (g == 1) mm_dma16((a.dbias ? a.dbias + (long)w.dbrow * a.lddb + nbase : wr_zeros) + off, dst);
+    else if (g == 1) mm_dma16((a.dbias ? a.dbias + (long)w.dbrow * a.lddb + nbase : ares_zeros) + off, dst);
     else if (g == 2) mm_dma16(a.osc + (long)w.grp * a.ldosc + nbase + off, dst);
     else mm_dma16(a.osh + (long)w.grp * a.ldosc + nbase + off, dst);
   };
@@ -203,13 +179,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
   // masked epilogue of a block (rows past the half tile's end do not count): not interleaved, rare
   auto epi_masked = [&](const f32x16* acc, const float* m1, const float* m0, float* run, int lim) {
 #pragma unroll
-    for (int tn = 0; tn < 2; ++tn) {
-      float s = run[tn];
-#pragma unroll
-      for (int e = 0; e < 16; ++e)
-        if ((e & 3) + 8 * (e >> 2) < lim) s += fmaxf(fmaf(acc[tn][e], m1[tn], m0[tn]), 0.f);
-      run[tn] = s;
-    }
+    for (int tn = 0; tn < 2; ++tn) run[tn] = ares_relu_sum_masked<0>(acc[tn], lim, m1[tn], m0[tn], run[tn]);
   };
   auto store_sums = [&](int t, int h, float* run) {
 #pragma unroll
@@ -366,27 +336,9 @@ __global__ __launch_bounds__(512, 1) void gemm_wreg128_kernel(mmmot_gemm_ares_ar
   mm_wait_vm<0>();  // nothing may still be in flight towards this workgroup's LDS
 }
 
-static std::atomic<int> g_ares_variant{0};
-// Test knob: 0 = automatic (K = 128: the register-resident kernel for the consumer pass when the launch fills the chip;
-// K = 64: the independent-wave kernel of gemm_wres.hip for a column-sum pass that gives every wave a run of half tiles),
-// 1 = the streaming kernel only, 2 = the register-resident / independent-wave kernel whenever the layer is eligible,
-// 3 = K = 64: the two-barrier weight-resident kernel only (K = 128: as 0).  Results do not depend on it (bit for bit).
-extern "C" int mmmot_set_gemm_ares_variant(int v) {
-  if (v < 0 || v > 3) return MMMOT_EINVAL;
-  g_ares_variant.store(v);
-  return MMMOT_OK;
-}
-int mmmot_ares_variant() { return g_ares_variant.load(); }
-
-// Called by mmmot_gemm_ares after its argument checks; returns 1 when this kernel took the launch.
-int mmmot_gemm_wreg128_try(const mmmot_gemm_ares_args* a, int mode, int n_cu, hipStream_t s, int* status) {
-  const int variant = g_ares_variant.load();
-  if (variant == 1 || a->K != WR_K || mode != 2 || a->N % 512 != 0 || a->N > 4096) return 0;
-  if (a->ldx % 4 != 0 || a->ldx < WR_K) return 0;
-  if (a->ldosc % 4 != 0 || a->ldsc % 4 != 0 || (a->dbias && a->lddb % 4 != 0)) return 0;  // 16-byte LDS-DMA pieces
+// N % 512 == 0, 16-byte-aligned rows (mmmot_ares_choose): grid sizing and the launch
+int mmmot_gemm_wreg128_launch(const mmmot_gemm_ares_args* a, int n_cu, hipStream_t s) {
   const int nh = a->N / 512;
-  // the launch must fill the chip with whole (tile sequence x channel half) groups of 8 workgroups per XCD
-  if (variant != 2 && (long)a->T * nh < 2L * n_cu) return 0;
   int groups = n_cu / (8 * nh);                 // sequences of 8 workgroups per channel half
   if (groups < 1) groups = 1;
   const int need = (a->T + 7) / 8;              // sequences of 8 tiles there are
@@ -394,6 +346,5 @@ int mmmot_gemm_wreg128_try(const mmmot_gemm_ares_args* a, int mode, int n_cu, hi
   const int grid = groups * 8 * nh;
   const int nseq = a->T < 8 * groups ? a->T : 8 * groups;  // sequence starts that exist
   hipLaunchKernelGGL(gemm_wreg128_kernel, dim3(grid), dim3(512), 0, s, *a, nh, nseq);
-  *status = mm_check(hipGetLastError());
-  return 1;
+  return mm_check(hipGetLastError());
 }

@@ -16,18 +16,54 @@
 // 1.7 GHz the chip holds under this load (profiles/README.md r02 "weight-resident conv1").  Tried without gain: a
 // fixed issue priority or an s_sleep skew for one wave of each SIMD, four accumulator chains instead of two.
 // Arithmetic and summation order are those of gemm_ares (fp16 matrix cores, 3-term hi/lo split, fp32 accumulation).
-#include "common.h"
+#include "ares_common.h"
 
 #define WR_THREADS 512
 #define WR_NMAX 512
 #define WR_BM 128
 
-static __device__ float wr_zeros[WR_NMAX];  // stands in for absent bias / dbias / osc / osh rows (branch-free loads)
-
 // [row][64 halves] planes without padding: 16-byte chunk c of row r lives at chunk c ^ ((r >> 1) & 7).  Sixteen lanes
 // reading chunk c of sixteen consecutive rows then touch every bank exactly once (rows alternate between the two bank
 // halves, the XOR spreads the eight even / odd rows over the eight chunks of a half).
 __device__ __forceinline__ int wr_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3); }
+
+// the weights: hl16 rows of 8 units [hi8 | lo8] -> swizzled hi / lo planes, once per workgroup
+__device__ __forceinline__ void wr_fill_planes(const void* W, int N, _Float16* Wh, _Float16* Wl, int tid) {
+  const u32x4* wp = reinterpret_cast<const u32x4*>(W);
+  for (int idx = tid; idx < N * 8; idx += WR_THREADS) {
+    const int n = idx >> 3, u = idx & 7;
+    const u32x4 hi = wp[(long)idx * 2], lo = wp[(long)idx * 2 + 1];
+    *reinterpret_cast<u32x4*>(&Wh[wr_off(n, u)]) = hi;
+    *reinterpret_cast<u32x4*>(&Wl[wr_off(n, u)]) = lo;
+  }
+}
+
+// A wave's 64-row x 32-channel x K = 64 block of 24 MFMAs.  af: its activation fragments [k16 step][hi rows 0-31, lo
+// rows 0-31, hi rows 32-63, lo rows 32-63]; bh / bl: its weight fragments, two slots, filled by the kernel's
+// read_b(channel, k16 step, slot) - a lambda over the kernel's own planes: handing the planes' addresses to a function
+// instead costs 5 - 11 VGPRs in these kernels.  The fragments of step j + 1 of this lane's channel n - or of step 0 of the
+// next block, channel n_next - are read before the MFMAs of step j issue; the caller reads step 0 of the first block
+// into slot 0.
+template <class ReadB>
+__device__ __forceinline__ void wr_mma_block(f32x16 (&acc)[2], const f16x8 (&af)[4][4], const f16x8 (&bh)[2],
+                                             const f16x8 (&bl)[2], ReadB read_b, int n, int n_next, bool have_next) {
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[tm][e] = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int sl = j & 1;
+    if (j < 3) read_b(n, j + 1, sl ^ 1);
+    else if (have_next) read_b(n_next, 0, sl ^ 1);
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][1], bh[sl], acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][3], bh[sl], acc[1], 0, 0, 0);
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][0], bl[sl], acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][2], bl[sl], acc[1], 0, 0, 0);
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][0], bh[sl], acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][2], bh[sl], acc[1], 0, 0, 0);
+  }
+}
 
 // MODE bit 0: statistics (part), bit 1: normalise + ReLU + column sums (colsum).
 template <int MODE>
@@ -42,50 +78,19 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64_kernel(mmmot_gemm_ares
   const int nbw = a.N >> 7;  // 32-channel blocks per wave: 1 .. 4
 
   // Tile tables: the four words of tile t + 2 * gridDim.x are requested during tile t and taken (as scalars) at the start
-  // of tile t + 1, where the loads of tile t + 2's rows need them: a table lookup in front of those loads would be two
-  // dependent L2 round trips with the matrix cores idle.
-  struct TileMeta {
-    int row0, nrows, grp, dbrow;
-  };
-  auto meta_of = [&](int tt) {
-    TileMeta m;
-    m.row0 = a.tile_row0[tt];
-    m.nrows = a.tile_nrows[tt];
-    // unconditional loads (an absent table reads tile_row0 instead, discarded in scalar()): a conditional load makes
-    // the number of loads in flight path-dependent and turns later counted waits into vmcnt(0)
-    m.grp = (a.tile_group ? a.tile_group : a.tile_row0)[tt];
-    m.dbrow = (a.dbias ? a.tile_dbrow : a.tile_row0)[tt];
-    return m;
-  };
-  auto scalar = [&](const TileMeta& v) {
-    TileMeta m;
-    m.row0 = __builtin_amdgcn_readfirstlane(v.row0);
-    m.nrows = __builtin_amdgcn_readfirstlane(v.nrows);
-    m.grp = a.tile_group ? __builtin_amdgcn_readfirstlane(v.grp) : 0;
-    m.dbrow = a.dbias ? __builtin_amdgcn_readfirstlane(v.dbrow) : 0;
-    return m;
-  };
+  // of tile t + 1, where the loads of tile t + 2's rows need them (ares_common.h).
   int t = blockIdx.x;
   if (t >= a.T) return;
   const int gstep = gridDim.x;
-  TileMeta cur = scalar(meta_of(t)), nxt = cur, raw2 = cur;
-  if (t + gstep < a.T) nxt = scalar(meta_of(t + gstep));
+  AresTile cur = ares_tile_scalar(a, ares_tile_request(a, t)), nxt = cur, raw2 = cur;
+  if (t + gstep < a.T) nxt = ares_tile_scalar(a, ares_tile_request(a, t + gstep));
 
-  // ---- the weights: hl16 rows of 8 units [hi8 | lo8] -> swizzled hi / lo planes, once ----
-  {
-    const u32x4* wp = reinterpret_cast<const u32x4*>(a.W);
-    for (int idx = tid; idx < a.N * 8; idx += WR_THREADS) {
-      const int n = idx >> 3, u = idx & 7;
-      const u32x4 hi = wp[(long)idx * 2], lo = wp[(long)idx * 2 + 1];
-      *reinterpret_cast<u32x4*>(&Wh[wr_off(n, u)]) = hi;
-      *reinterpret_cast<u32x4*>(&Wl[wr_off(n, u)]) = lo;
-    }
-  }
+  wr_fill_planes(a.W, a.N, Wh, Wl, tid);
   // ---- activation rows: thread -> (rows (tid >> 4) + 32 i, channels 4 (tid & 15) .. + 3); a wave's load instruction
   // covers four whole rows (1 KB contiguous)
   const int sr = tid >> 4, sch = tid & 15;
   f32x4 x[4];
-  auto load_x = [&](const TileMeta& m) {
+  auto load_x = [&](const AresTile& m) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = sr + 32 * i;
@@ -99,7 +104,7 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64_kernel(mmmot_gemm_ares
     s4 = *reinterpret_cast<const f32x4*>(a.sc + (long)grp * a.ldsc + sch * 4);
     h4 = *reinterpret_cast<const f32x4*>(a.sh + (long)grp * a.ldsc + sch * 4);
   };
-  auto stage_a = [&](const TileMeta& m) {
+  auto stage_a = [&](const AresTile& m) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = sr + 32 * i;
@@ -107,7 +112,7 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64_kernel(mmmot_gemm_ares
       float y[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        y[e] = fminf(fmaxf(fmaf(x[i][e], s4[e], h4[e]), 0.f), 65000.f);
+        y[e] = mm_norm_relu(x[i][e], s4[e], h4[e]);
         if (r >= m.nrows) y[e] = 0.f;
       }
       unsigned h0_, l0_, h1_, l1_;
@@ -126,8 +131,8 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64_kernel(mmmot_gemm_ares
   // arithmetic touches them until the tile switch, where they become cb (combined bias) and m1 / m0 (the consumer's
   // relu(acc * m1 + m0)).
   float pb[4], cb[4], m1[4], m0[4], dbn[4], osn[4], ohn[4];
-  auto load_consts = [&](const TileMeta& m) {
-    const float* pdb = a.dbias ? a.dbias + (long)m.dbrow * a.lddb : wr_zeros;
+  auto load_consts = [&](const AresTile& m) {
+    const float* pdb = a.dbias ? a.dbias + (long)m.dbrow * a.lddb : ares_zeros;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       dbn[i] = osn[i] = ohn[i] = 0.f;
@@ -177,39 +182,27 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64_kernel(mmmot_gemm_ares
     const float inv_nsub = nsub > 0 ? 1.f / (float)nsub : 0.f;
     const long prow = (long)(2 * t + wm);
     const bool full = (nsub == 64);
-    // row of accumulator element (tm, e) in the tile = wm * 64 + tm * 32 + mm_acc_row(e, lane); valid <=> the
-    // compile-time part < lim (one register instead of 32 hoisted row indices)
-    const int lim = nrows - (wm * 64 + 4 * lh);
+    const int row_l = wm * 64 + 4 * lh;  // first row of the lane's accumulator elements in the tile
 
-    // weight fragments: step j + 1 (or step 0 of the next block) is read before the MFMAs of step j issue
     f16x8 bh[2], bl[2];
-    auto read_b = [&](int blk, int j, int slot) {
-      const int n = (wn + 4 * blk) * 32 + lr;
+    auto read_b = [&](int n, int j, int slot) {
       bh[slot] = *reinterpret_cast<const f16x8*>(&Wh[wr_off(n, 2 * j + lh)]);
       bl[slot] = *reinterpret_cast<const f16x8*>(&Wl[wr_off(n, 2 * j + lh)]);
     };
-    read_b(0, 0, 0);
+    read_b(wn * 32 + lr, 0, 0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (i >= nbw) break;
       const int n = (wn + 4 * i) * 32 + lr;
       f32x16 acc[2];
-#pragma unroll
-      for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[tm][e] = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int sl = j & 1;
-        if (j < 3) read_b(i, j + 1, sl ^ 1);
-        else if (i + 1 < nbw) read_b(i + 1, 0, sl ^ 1);
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][1], bh[sl], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][3], bh[sl], acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][0], bl[sl], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][2], bl[sl], acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][0], bh[sl], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][2], bh[sl], acc[1], 0, 0, 0);
-      }
+      wr_mma_block(acc, af, bh, bl, read_b, n, n + 128, i + 1 < nbw);
+      // The masked epilogue's bound (ares_common.h), from a copy of nrows that is opaque per block.  With one bound for
+      // the four blocks the compiler hoists the 32 compares of the rare masked forms in front of the branches, onto the
+      // path of full tiles: ~36 VALU instructions per tile and wave that overlap nothing (measured on the statistics
+      // pass over 4 M rows, N = 512: 0.858 -> 0.881 ms).
+      int nr = nrows;
+      asm("" : "+s"(nr));
+      const int lim = nr - row_l;
       if (i == 0 && more) {
         // the next tile's requests (constants first, then its rows, then the table words of the tile after it) are
         // issued in the shadow of this block's MFMAs - ~25 VMEM instructions cost ~800 issue cycles (s_memtime) that
@@ -217,55 +210,20 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64_kernel(mmmot_gemm_ares
         __builtin_amdgcn_sched_barrier(0);
         load_consts(nxt);
         load_x(nxt);
-        if (tn + gstep < a.T) raw2 = meta_of(tn + gstep);
+        if (tn + gstep < a.T) raw2 = ares_tile_request(a, tn + gstep);
         __builtin_amdgcn_sched_barrier(0);
       }
       // ---- register-only epilogue of 64 rows x 32 channels (as gemm_ares: sums on the raw accumulators, rescaled) ----
-      const float cbi = cb[i];
       if constexpr (MODE & 1) {
-        float s1 = 0.f;
-        if (full) {
-          s1 = mm_sum32(acc[0], acc[1]);
-        } else {
-#pragma unroll
-          for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-              if (tm * 32 + (e & 3) + 8 * (e >> 2) < lim) s1 += acc[tm][e];
-        }
-        s1 = mm_xor32_sum(s1);
-        const float mu = s1 * inv_nsub;  // mean of the raw accumulators over the half tile
-        float s2 = 0.f;
-        if (full) {
-          s2 = mm_m2_32(acc[0], acc[1], mu);
-        } else {
-#pragma unroll
-          for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              const float d = acc[tm][e] - mu;
-              if (tm * 32 + (e & 3) + 8 * (e >> 2) < lim) s2 = fmaf(d, d, s2);
-            }
-        }
-        s2 = mm_xor32_sum(s2);
+        float s1, s2;
+        ares_half_stats(acc[0], acc[1], full, lim, inv_nsub, s1, s2);
         if (lane < 32) {
-          a.part[(prow * 2 + 0) * a.N + n] = fmaf(s1, a.oscale, (float)nsub * cbi);
+          a.part[(prow * 2 + 0) * a.N + n] = fmaf(s1, a.oscale, (float)nsub * cb[i]);
           a.part[(prow * 2 + 1) * a.N + n] = s2 * a.oscale * a.oscale;
         }
       }
       if constexpr (MODE & 2) {
-        const float m1i = m1[i], m0i = m0[i];
-        float s3 = 0.f;
-        if (full) {
-          s3 = mm_relu_sum32(acc[0], acc[1], m1i, m0i);
-        } else {
-#pragma unroll
-          for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-              if (tm * 32 + (e & 3) + 8 * (e >> 2) < lim) s3 += fmaxf(fmaf(acc[tm][e], m1i, m0i), 0.f);
-        }
-        s3 = mm_xor32_sum(s3);
+        const float s3 = ares_half_relu_sum(acc[0], acc[1], full, lim, m1[i], m0[i]);
         if (lane < 32) a.colsum[prow * a.N + n] = s3;
       }
     }
@@ -273,7 +231,7 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64_kernel(mmmot_gemm_ares
     take_consts();
     if (nxt.grp != cur.grp) load_norm(nxt.grp);
     cur = nxt;
-    nxt = scalar(raw2);
+    nxt = ares_tile_scalar(a, raw2);
     t = tn;
   }
 }
@@ -295,10 +253,6 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64_kernel(mmmot_gemm_ares
 // Same MFMA order per accumulator, same per-lane summation order, same half-wave exchange as above and as gemm_ares:
 // the column sums are bit-identical (tests/test_kernels_gpu.py).  Ragged half tiles (a detection's tail) take a compact
 // loop with the constants read per block.
-struct WiItem {
-  int row0, nrows, grp, dbrow;  // of the item's 128-row tile
-};
-
 __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_ares_args a) {
   __shared__ __attribute__((aligned(16))) _Float16 Wh[WR_NMAX * 64];
   __shared__ __attribute__((aligned(16))) _Float16 Wl[WR_NMAX * 64];
@@ -307,15 +261,7 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_are
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 31, lh = lane >> 5;
   const int nblk = a.N >> 5;  // 32-channel blocks: 4, 8, 12 or 16
-  {
-    const u32x4* wp = reinterpret_cast<const u32x4*>(a.W);
-    for (int idx = tid; idx < a.N * 8; idx += WR_THREADS) {
-      const int n = idx >> 3, u = idx & 7;
-      const u32x4 hi = wp[(long)idx * 2], lo = wp[(long)idx * 2 + 1];
-      *reinterpret_cast<u32x4*>(&Wh[wr_off(n, u)]) = hi;
-      *reinterpret_cast<u32x4*>(&Wl[wr_off(n, u)]) = lo;
-    }
-  }
+  wr_fill_planes(a.W, a.N, Wh, Wl, tid);
   __syncthreads();  // the only one
   // this wave's run of half tiles: [h, hend)
   const int H = 2 * a.T, nw = gridDim.x * (WR_THREADS / 64), gw = blockIdx.x * (WR_THREADS / 64) + wave;
@@ -324,26 +270,12 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_are
   const int hend = h + q + (gw < rem ? 1 : 0);
   if (h >= hend) return;
 
-  // tile-table words of item hh by scalar loads (mm_sload4, common.h)
-  auto item = [&](int hh) {
-    const int t = hh >> 1;
-    const int* p0 = a.tile_row0 + t;
-    const int* p1 = a.tile_nrows + t;
-    const int* p2 = a.tile_group ? a.tile_group + t : p0;
-    const int* p3 = a.dbias ? a.tile_dbrow + t : p0;
-    int v0, v1, v2, v3;
-    mm_sload4(p0, p1, p2, p3, v0, v1, v2, v3);
-    WiItem m;
-    m.row0 = v0;
-    m.nrows = v1;
-    m.grp = a.tile_group ? v2 : 0;
-    m.dbrow = a.dbias ? v3 : 0;
-    return m;
-  };
+  // tile-table words of item hh (a half of tile hh >> 1) by scalar loads
+  auto item = [&](int hh) { return ares_tile_sload(a, hh >> 1); };
   // the item's 64 rows in fragment layout: lane (lr, lh) holds k = 16 j + 8 lh .. + 7 of rows lr and 32 + lr; rows past
   // the tile read its first row (their fragments are zeroed)
   f32x4 raw[2][4][2];
-  auto request = [&](const WiItem& m, int wm) {
+  auto request = [&](const AresTile& m, int wm) {
     const float* base = a.X + (long)m.row0 * a.ldx;
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -369,8 +301,8 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_are
         float y[8];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          y[e] = fminf(fmaxf(fmaf(raw[b][j][0][e], s0[e], t0[e]), 0.f), 65000.f);
-          y[4 + e] = fminf(fmaxf(fmaf(raw[b][j][1][e], s1[e], t1[e]), 0.f), 65000.f);
+          y[e] = mm_norm_relu(raw[b][j][0][e], s0[e], t0[e]);
+          y[4 + e] = mm_norm_relu(raw[b][j][1][e], s1[e], t1[e]);
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e)
@@ -384,16 +316,16 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_are
     }
   };
   // epilogue constants of channel n under (grp, dbrow): the consumer's relu(acc * m1 + m0), as in the kernel above
-  auto consts_of = [&](const WiItem& m, int n, float& m1v, float& m0v) {
+  auto consts_of = [&](const AresTile& m, int n, float& m1v, float& m0v) {
     const float pb = a.bias ? a.bias[n] : 0.f;
-    const float db = (a.dbias ? a.dbias + (long)m.dbrow * a.lddb : wr_zeros)[n];
+    const float db = (a.dbias ? a.dbias + (long)m.dbrow * a.lddb : ares_zeros)[n];
     const float o = a.osc[(long)m.grp * a.ldosc + n];
     const float cb = pb + db;
     m1v = a.oscale * o;
     m0v = fmaf(cb, o, a.osh[(long)m.grp * a.ldosc + n]);
   };
   float tab[16];
-  auto build_tab = [&](const WiItem& m) {
+  auto build_tab = [&](const AresTile& m) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       tab[i] = 0.f;
@@ -409,26 +341,11 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_are
     bh[slot] = *reinterpret_cast<const f16x8*>(&Wh[wr_off(n, 2 * j + lh)]);
     bl[slot] = *reinterpret_cast<const f16x8*>(&Wl[wr_off(n, 2 * j + lh)]);
   };
-  auto mma_block = [&](f32x16 (&acc)[2], int n_next, bool have_next) {
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[tm][e] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int sl = j & 1;
-      if (j < 3) read_b(n_next - 32, j + 1, sl ^ 1);
-      else if (have_next) read_b(n_next, 0, sl ^ 1);
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][1], bh[sl], acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][3], bh[sl], acc[1], 0, 0, 0);
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][0], bl[sl], acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][2], bl[sl], acc[1], 0, 0, 0);
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][0], bh[sl], acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j][2], bh[sl], acc[1], 0, 0, 0);
-    }
+  auto mma_block = [&](f32x16 (&acc)[2], int i) {  // block i; reads ahead into block i + 1
+    wr_mma_block(acc, af, bh, bl, read_b, i * 32 + lr, (i + 1) * 32 + lr, i + 1 < nblk);
   };
 
-  WiItem cur = item(h), nxt = cur;
+  AresTile cur = item(h), nxt = cur;
   if (h + 1 < hend) nxt = item(h + 1);
   request(cur, h & 1);
   int tab_grp = -1, tab_db = -1, nrm_grp = -1;
@@ -450,7 +367,7 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_are
       }
       convert(nsub);
     }
-    WiItem nn = nxt;
+    AresTile nn = nxt;
     if (more) {
       request(nxt, (h + 1) & 1);
       if (h + 2 < hend) nn = item(h + 2);
@@ -464,27 +381,20 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_are
           const f32x2 m = mm_permlane32_swap(tab[i], tab[i]);  // (lanes 0-31, lanes 32-63 of tab[i]) on every lane
           const float m1i = m[0], m0i = m[1];
           f32x16 acc[2];
-          mma_block(acc, (i + 1) * 32 + lr, i + 1 < nblk);
-          float s3 = mm_relu_sum32(acc[0], acc[1], m1i, m0i);
-          s3 = mm_xor32_sum(s3);
+          mma_block(acc, i);
+          const float s3 = ares_half_relu_sum(acc[0], acc[1], true, 64, m1i, m0i);
           if (lane < 32) out[i * 32 + lr] = s3;
         }
       }
     } else if (nsub > 0) {
-      const int lim = nsub - 4 * lh;  // row of accumulator element (tm, e) = tm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh
+      const int lim = nsub - 4 * lh;  // the masked epilogue's bound (ares_common.h)
       read_b(lr, 0, 0);
       for (int i = 0; i < nblk; ++i) {
         float m1i, m0i;
         consts_of(cur, i * 32 + lr, m1i, m0i);
         f32x16 acc[2];
-        mma_block(acc, (i + 1) * 32 + lr, i + 1 < nblk);
-        float s3 = 0.f;
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-          for (int e = 0; e < 16; ++e)
-            if (tm * 32 + (e & 3) + 8 * (e >> 2) < lim) s3 += fmaxf(fmaf(acc[tm][e], m1i, m0i), 0.f);
-        s3 = mm_xor32_sum(s3);
+        mma_block(acc, i);
+        const float s3 = ares_half_relu_sum(acc[0], acc[1], false, lim, m1i, m0i);
         if (lane < 32) out[i * 32 + lr] = s3;
       }
     } else {
@@ -498,14 +408,9 @@ __global__ __launch_bounds__(WR_THREADS) void gemm_wres64i_kernel(mmmot_gemm_are
   }
 }
 
-int mmmot_ares_variant();  // gemm_wreg.hip
-
-// K = 64, N <= 512: called by mmmot_gemm_ares (gemm_ares.hip) after its argument checks
-int mmmot_gemm_wres64_launch(const mmmot_gemm_ares_args* a, int mode, int n_cu, hipStream_t s) {
-  // column-sum pass: independent waves when every wave gets a run of half tiles (a small launch is better balanced in
-  // 128-row tiles over eight waves); variant 2 = whenever eligible, 3 = never (tests, A/B).  Bit-identical either way.
-  const int variant = mmmot_ares_variant();
-  if (mode == 2 && variant != 3 && (variant == 2 || 2L * a->T >= 4L * 8 * n_cu)) {
+// K = 64, N <= 512.  waves: the independent-wave kernel (column-sum pass only), else the two-barrier kernel
+int mmmot_gemm_wres64_launch(const mmmot_gemm_ares_args* a, int mode, bool waves, int n_cu, hipStream_t s) {
+  if (waves) {
     const int wgs = (2 * a->T + 7) / 8;
     hipLaunchKernelGGL(gemm_wres64i_kernel, dim3(wgs < n_cu ? wgs : n_cu), dim3(WR_THREADS), 0, s, *a);
     return mm_check(hipGetLastError());

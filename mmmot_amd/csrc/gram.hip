@@ -101,7 +101,7 @@ __global__ __launch_bounds__(GR_THREADS) void gram_rows_kernel(const float* __re
           f16x4 hi, lo;
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {
-            float y = fminf(fmaxf(fmaf(xr[c4 / 4][rr][e], s4[e], h4[e]), 0.f), 65000.f);
+            float y = mm_norm_relu(xr[c4 / 4][rr][e], s4[e], h4[e]);
             if (sr4 + rr >= nr) y = 0.f;  // rows past the end of the super-tile contribute nothing
             hi[rr] = (_Float16)y;
             lo[rr] = mm_hl_lo(y, hi[rr]);

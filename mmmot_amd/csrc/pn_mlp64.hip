@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void pn_mlp64_kernel(const float* __restrict__
         float y[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          y[e] = fminf(fmaxf(fmaf(x[i][e], s0[e], h0[e]), 0.f), 65000.f);
+          y[e] = mm_norm_relu(x[i][e], s0[e], h0[e]);
           if (r >= nrows) y[e] = 0.f;
         }
         unsigned h0_, l0_, h1_, l1_;

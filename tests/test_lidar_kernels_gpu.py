@@ -22,7 +22,8 @@ Tile sets, detection-aligned (RowTiles(counts, sub_counts=dets)), two samples wi
         gemm_wres64_kernel), 2 n_cu (pn_mlp64's grid; T * nh >= 2 n_cu of the register kernel; T <= 2 n_cu of the pipelined
         Gram kernel) and 16 n_cu (2T >= 32 n_cu of the independent-wave kernel)
 
-Case -> branch (the launcher conditions are in mmmot_gemm_ares, mmmot_gemm_wres64_launch, mmmot_gemm_wreg128_try):
+Case -> branch (the conditions are one function, mmmot_ares_choose of csrc/ares_choice.h; tests/test_ares_choice_cpu.py
+asks it for the kernel of each of these cases without a GPU):
   gemm_ares_kernel<2, 1 / 2 / 3>  test_gemm_ares_edge[K128-N256] modes 1, 2, 3 (K = 128, mode 2 with N % 512 != 0 never goes
                                   to the register kernel); [K128-N1024] modes 1, 3 and mode 2 under variants 1 and 0
                                   (T * nh = 28 < 2 n_cu); test_gemm_ares_many[K128-N256] modes 1, 3 and [K128-N512] mode 2
@@ -37,9 +38,9 @@ Case -> branch (the launcher conditions are in mmmot_gemm_ares, mmmot_gemm_wres6
                                   items per wave, table rebuilt per detection); ..._without_a_group_table
   gemm_wreg128_kernel             test_gemm_ares_edge[K128-N512 / N1024 / N1536] mode 2 under variant 2 (nh = 1, 2, 3);
                                   ..._many[K128-N512] automatic (T >= 2 n_cu); ..._n4096 (nh = 8); ..._without_a_group_table
-  absent operands                 every EDGE case runs with / without bias x with / without dbias (ar_zeros / wr_zeros
-                                  stand-ins); tile_group = NULL in ..._without_a_group_table (mmmot_gemm_ares called with
-                                  _lib.GemmAresArgs directly); N = 4096 without bias rows reads all of ar_zeros / wr_zeros
+  absent operands                 every EDGE case runs with / without bias x with / without dbias (the ares_zeros
+                                  stand-in); tile_group = NULL in ..._without_a_group_table (mmmot_gemm_ares called with
+                                  _lib.GemmAresArgs directly); N = 4096 without bias rows reads all of ares_zeros
   fallback of the register kernel test_gemm_ares_odd_lddb_falls_back_to_the_streaming_kernel (lddb = 525)
   pn_mlp64_kernel<64>, <128>      test_pn_mlp64[N64 / N128]: plain tiles of 1 / 31 / 32 / 33 / 127 / 128 / 129 rows (7 groups) with and
                                   without bias; 2 n_cu + 5 one-row groups and one of 129 rows: T > gridDim.x (grid-stride
@@ -306,7 +307,7 @@ def test_gemm_ares_many(hip, knobs, case):
 
 
 def test_gemm_ares_n4096_on_one_short_tile_without_bias_rows(hip, knobs):
-    """N = 4096: the whole of the zero stand-ins is read (ar_zeros / wr_zeros [4096]); one tile of 5 rows; K = 128 mode 2 on the
+    """N = 4096: the whole of the zero stand-in is read (ares_zeros[4096]); one tile of 5 rows; K = 128 mode 2 on the
     streaming kernel and on the register kernel (nh = 8), K = 64 on the streaming kernel"""
     tl = DetTiles([[5]])
     for K in (128, 64):
@@ -315,7 +316,7 @@ def test_gemm_ares_n4096_on_one_short_tile_without_bias_rows(hip, knobs):
 
 
 def test_gemm_ares_odd_lddb_falls_back_to_the_streaming_kernel(hip, knobs):
-    """lddb = 525: the register kernel's 16-byte LDS-DMA pieces cannot fetch such rows, mmmot_gemm_wreg128_try declines and
+    """lddb = 525: the register kernel's 16-byte LDS-DMA pieces cannot fetch such rows, mmmot_ares_choose passes it over and
     the streaming kernel serves variant 2 - the same bits as variant 1, and the float64 values"""
     tl = tiling('EDGE', 0)
     d = Layer(tl, 128, 512, seed=1400, dbias_extra=9)
