@@ -80,7 +80,8 @@ extern "C" {
  * mmmot_pointnet_layer1 takes K = 3 | 4; mmmot_pn_mlp64 added (additive, still 5);
  * 6 = mmmot_trunk_range_bind (per-caller range-guard counter blocks); 7 - 9: see the entry points marked so below;
  * 10 = mmmot_gram_rows at K = 128 writes the 32 x 32 blocks on and above the block diagonal of Gout only (the finalize
- * entry point mirrors), mmmot_set_gemm_rows_variant: 2 rejected, 3 / 4 = the two forms of the wide kernel. */
+ * entry point mirrors), mmmot_set_gemm_rows_variant: 2 rejected, 3 / 4 = the two forms of the wide kernel;
+ * mmmot_segment_argmax, mmmot_pair_expand_max_bwd added (backward of end_mode 'max'; additive, still 10). */
 int mmmot_abi_version(void);
 /* returns 0 and fills cu_count / gcn arch string (<=32 bytes) of device 0..; */
 int mmmot_device_info(int device, int* cu_count, char* arch, int arch_len);
@@ -591,6 +592,27 @@ int mmmot_pair_bwd(const float* dX, int lddx, const float* F, int ldf, float* dF
 int mmmot_pair_expand_bwd(const float* dV, int lddv, float* dA, int ldda, int C, const int* tile_row0,
                           const int* tile_nrows, const int* tile_group, int T, const int* grp_row0,
                           const int* grp_N, const int* grp_M, const int* grp_vrow0, void* stream);
+/* end_mode 'max' (new_end.py:72-74; additive, still ABI 10): the backward of the strided MAXIMA that make the new / end
+ * vectors, in two launches.  The forward (mmmot_segment_mean, flag bit 1) records nothing; the indices are recomputed.
+ * mmmot_segment_argmax: idx_out[s][c] (int32, row stride ldo) = the FIRST t in [0, count[s]) that attains
+ *   max_t a(t),  a(t) = f(X[start[s] + t*stride[s]][c]),  f = the affine (sc / sh, may both be NULL) and ReLU (relu = 1)
+ * of mmmot_segment_mean in the same fmaf / fmaxf form: a(idx) is bit-equal to what the forward wrote.  First maximum is
+ * torch's rule for max(dim), which the reference differentiates through.  fp32 rows only; segment tables and the
+ * count[s] >= 1 contract as for mmmot_segment_mean.  MMMOT_EINVAL before any launch: X / seg_start / seg_count / idx_out
+ * NULL, nseg <= 0, C <= 0 or C % 4, a leading dimension that is no multiple of 4 or below C, a pointer off 16 bytes,
+ * only one of sc / sh, relu outside 0 / 1. */
+int mmmot_segment_argmax(const float* X, int ldx, int C, const int* seg_start, const int* seg_count,
+                         const int* seg_stride, const int* seg_group, int nseg, const float* sc, const float* sh,
+                         int ldsc, int relu, int* idx_out, int ldo, void* stream);
+/* mmmot_pair_expand_max_bwd: the counterpart of mmmot_pair_expand_bwd (same tile and group tables; idx = the table of
+ * mmmot_segment_argmax over plan.v_segs, rows as dV):
+ *   dA[(g,i,j)][c] = (idx[vrow0[g] + j][c] == i ? dV[vrow0[g] + j][c] : 0)
+ *                  + (idx[vrow0[g] + M + i][c] == j ? dV[vrow0[g] + M + i][c] : 0)
+ * Every element of dA is written exactly once (no zero-fill, no atomics): deterministic.  C % 4 == 0. */
+int mmmot_pair_expand_max_bwd(const float* dV, int lddv, const int* idx, int ldi, float* dA, int ldda, int C,
+                              const int* tile_row0, const int* tile_nrows, const int* tile_group, int T,
+                              const int* grp_row0, const int* grp_N, const int* grp_M, const int* grp_vrow0,
+                              void* stream);
 /* backward of mmmot_rowdot (a = relu(X*sc + sh), act NONE or SIGMOID): gpre[r] = gout[gidx ? gidx[r] : r] * act';
  * dA[r][k] = gpre[r] w[k]; PW[t][k] = sum_{r in tile t} gpre[r] a(r,k) (k < K), PW[t][K] = sum_r gpre[r]. */
 int mmmot_rowdot_bwd(const float* X, int ldx, int K, const float* w, float b, const float* sc, const float* sh,

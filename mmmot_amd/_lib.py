@@ -144,6 +144,10 @@ SIGNATURES = {
     'mmmot_absmax': [c_f, c_i, ctypes.c_long, c_i, c_f, c_f],
     'mmmot_pair_bwd': [c_f, c_i, c_f, c_i, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f],
     'mmmot_pair_expand_bwd': [c_f, c_i, c_f, c_i, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f],
+    # X, ldx, C, seg_start, seg_count, seg_stride, seg_group, nseg, sc, sh, ldsc, relu, idx_out, ldo, stream
+    'mmmot_segment_argmax': [c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_f, c_i, c_f],
+    # dV, lddv, idx, ldi, dA, ldda, C, tile_row0, tile_nrows, tile_group, T, grp_row0, grp_N, grp_M, grp_vrow0, stream
+    'mmmot_pair_expand_max_bwd': [c_f, c_i, c_f, c_i, c_f, c_i, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f],
     'mmmot_rowdot_bwd': [c_f, c_i, c_i, c_f, ctypes.c_float, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_i,
                          c_f, c_i, c_f],
     'mmmot_softmax_pairs_bwd': [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f],

@@ -68,8 +68,6 @@ def _aux(plan):
 def affinity_forward_train(eng, plan, F):
     """Engine.affinity, recorded: the tape the backward needs.  F: [nR, Lt, 512] (contiguous).  Returns
     (link flat [R], new [nR, Lt], end [nR, Lt], tape)."""
-    if eng.end_mode != 'avg':
-        raise NotImplementedError("the backward of end_mode='max' is not built")
     eng.dev = F.device
     with eng.recording() as tape:
         link, new, end = eng.affinity(plan, F)
@@ -115,7 +113,14 @@ def affinity_backward(eng, plan, F, t, d_link, d_new, d_end):
                                                                 amode=A_NORM_RELU)
     dV, g['nw0'], g['nb0'], g['ng1'], g['nbe1'] = V1.backward(eng, plan, dAv0, lk['nw0'], X=t['aff_v'], amode=A_PLAIN)
     dAne = new(R, 512)
-    ops.pair_expand_bwd(dV, dAne, 512, PT, PT.g_row0, plan.pg_N, plan.pg_M, aux.vrow0)
+    if eng.end_mode == 'avg':
+        ops.pair_expand_bwd(dV, dAne, 512, PT, PT.g_row0, plan.pg_N, plan.pg_M, aux.vrow0)
+    else:
+        # maxima (new_end.py:72-74): the forward keeps no indices - the first-maximum row of every (vector, channel) is
+        # recomputed from the tape with Engine.affinity's own segment_mean arguments, then dV goes to that row alone
+        idx = torch.empty(VT.R, 512, dtype=torch.int32, device=dev)
+        ops.segment_argmax(NE0.Y, 512, plan.v_segs, idx, sc=NE0.sc, sh=NE0.sh, relu=True)
+        ops.pair_expand_max_bwd(dV, idx, dAne, 512, PT, PT.g_row0, plan.pg_N, plan.pg_M, aux.vrow0)
     _, g['g_ne0'], g['be_ne0'] = gn_backward(eng, plan, NE0, dAne, out=dYa[:, 0:512])
     # ---- the stacked first layer over the pairwise tensor, and the pairwise operand generation ----
     pair = dict(row0=PT.g_row0, M=plan.pg_M, aoff=plan.pg_aoff, boff=plan.pg_boff)

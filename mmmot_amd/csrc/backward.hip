@@ -368,6 +368,141 @@ extern "C" int mmmot_pair_expand_bwd(const float* dV, int lddv, float* dA, int l
 }
 
 // ---------------------------------------------------------------------------
+// end_mode 'max' (new_end.py:72-74): the new / end vectors are maxima over the prev / curr axis, and torch's max(dim)
+// sends the gradient to the FIRST row that attains the maximum.  The forward (segment_mean_kernel, flag bit 1) is not
+// touched and records no indices; the backward recomputes them from the tape:
+//   idx[s][c] = min { t : a(t) = max_u a(u) },  a(t) = relu(fmaf(X[start + t*stride][c], sc[g][c], sh[g][c]))
+// with the forward's fmaf / fmaxf expression, so that a(idx) is the value the forward wrote, bit for bit.
+// Decomposition of segment_mean_kernel (small_kernels.hip): grid = (nseg, ceil(C/256)), 4 waves split the rows of the
+// segment (wave w takes t = w, w + 4, ...), every lane owns 4 consecutive channels.  A wave keeps (value, index) with a
+// strict > over its increasing t; the waves are combined on (larger value, then LOWER INDEX) - not the lower wave: rows 1
+// and 4 sit in waves 1 and 0.  A wave without rows (count < 4) carries index -1 and never enters the combine.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(256) void segment_argmax_kernel(
+    const float* __restrict__ X, int ldx, int C, const int* __restrict__ seg_start, const int* __restrict__ seg_count,
+    const int* __restrict__ seg_stride, const int* __restrict__ seg_group, const float* __restrict__ sc,
+    const float* __restrict__ sh, int ldsc, int relu, int* __restrict__ idx_out, int ldo) {
+  __shared__ __attribute__((aligned(16))) float redv[4][256];
+  __shared__ __attribute__((aligned(16))) int redi[4][256];
+  const int s = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = blockIdx.y * 256 + lane * 4;
+  const bool cv = c < C;
+  const int start = seg_start[s], count = seg_count[s], stride = seg_stride ? seg_stride[s] : 1;
+  const int g = seg_group ? seg_group[s] : 0;
+  f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, h4 = {0.f, 0.f, 0.f, 0.f};
+  const bool norm = (sc != nullptr);
+  if (norm && cv) {
+    s4 = *reinterpret_cast<const f32x4*>(&sc[(long)g * ldsc + c]);
+    h4 = *reinterpret_cast<const f32x4*>(&sh[(long)g * ldsc + c]);
+  }
+  auto ld = [&](int t) -> f32x4 {
+    f32x4 v = *reinterpret_cast<const f32x4*>(&X[((long)start + (long)t * stride) * ldx + c]);
+    if (norm) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], s4[e], h4[e]);
+    }
+    if (relu) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+    }
+    return v;
+  };
+  f32x4 best = {0.f, 0.f, 0.f, 0.f};
+  i32x4 bi = {-1, -1, -1, -1};
+  if (cv && wave < count) {
+    best = ld(wave);
+    bi = i32x4{wave, wave, wave, wave};
+    for (int t = wave + 4; t < count; t += 4) {
+      const f32x4 v = ld(t);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (v[e] > best[e]) {
+          best[e] = v[e];
+          bi[e] = t;
+        }
+    }
+  }
+  *reinterpret_cast<f32x4*>(&redv[wave][lane * 4]) = best;
+  *reinterpret_cast<i32x4*>(&redi[wave][lane * 4]) = bi;
+  __syncthreads();
+  if (wave == 0 && cv) {
+    // wave 0 holds row 0 (count >= 1 is the caller's to guarantee, as for mmmot_segment_mean)
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(&redv[w][lane * 4]);
+      const i32x4 k = *reinterpret_cast<const i32x4*>(&redi[w][lane * 4]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (k[e] >= 0 && (v[e] > best[e] || (v[e] == best[e] && k[e] < bi[e]))) {
+          best[e] = v[e];
+          bi[e] = k[e];
+        }
+    }
+    *reinterpret_cast<i32x4*>(&idx_out[(long)s * ldo + c]) = bi;
+  }
+}
+
+extern "C" int mmmot_segment_argmax(const float* X, int ldx, int C, const int* seg_start, const int* seg_count,
+                                    const int* seg_stride, const int* seg_group, int nseg, const float* sc,
+                                    const float* sh, int ldsc, int relu, int* idx_out, int ldo, void* stream) {
+  if (!X || !seg_start || !seg_count || !idx_out || nseg <= 0 || C <= 0) return MMMOT_EINVAL;
+  if (relu < 0 || relu > 1) return MMMOT_EINVAL;
+  if (C % 4 != 0 || ldx % 4 != 0 || ldo % 4 != 0 || ldx < C || ldo < C || !mm_al16(X) || !mm_al16(idx_out)) return MMMOT_EINVAL;
+  if ((sc == nullptr) != (sh == nullptr)) return MMMOT_EINVAL;
+  if (sc && (ldsc % 4 != 0 || ldsc < C || !mm_al16(sc) || !mm_al16(sh))) return MMMOT_EINVAL;
+  hipLaunchKernelGGL(segment_argmax_kernel, dim3(nseg, (C + 255) / 256), dim3(256), 0, (hipStream_t)stream, X, ldx, C,
+                     seg_start, seg_count, seg_stride, seg_group, sc, sh, ldsc, relu, idx_out, ldo);
+  return mm_check(hipGetLastError());
+}
+
+// Backward of the strided maxima, the counterpart of pair_expand_bwd_kernel: pair row (g, i, j) receives the gradient of
+// "new" vector j where it is that vector's arg-max row (i) and of "end" vector i where it is that one's (j):
+//   dA[(g,i,j)][c] = (idx[v0 + j][c] == i ? dV[v0 + j][c] : 0) + (idx[v0 + M + i][c] == j ? dV[v0 + M + i][c] : 0)
+// One pass over dA, every element written once (no zero-fill, no atomics): deterministic.
+__global__ __launch_bounds__(256) void pair_expand_max_bwd_kernel(const float* __restrict__ dV, int lddv,
+                                                                  const int* __restrict__ idx, int ldi,
+                                                                  float* __restrict__ dA, int ldda, int C,
+                                                                  const int* __restrict__ tile_row0,
+                                                                  const int* __restrict__ tile_nrows,
+                                                                  const int* __restrict__ tile_group,
+                                                                  const int* __restrict__ grp_row0,
+                                                                  const int* __restrict__ grp_M,
+                                                                  const int* __restrict__ grp_vrow0) {
+  const int t = blockIdx.x;
+  const int row0 = tile_row0[t], nrows = tile_nrows[t], g = tile_group[t];
+  const int M = grp_M[g], v0 = grp_vrow0[g], base = row0 - grp_row0[g];
+  for (int q = threadIdx.x; q < nrows * (C / 4); q += 256) {
+    const int r = q / (C / 4), c = (q - r * (C / 4)) * 4;
+    const int local = base + r;
+    const int i = local / M, j = local - i * M;
+    const long vn = (long)v0 + j, ve = (long)v0 + M + i;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(&dV[vn * lddv + c]);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(&dV[ve * lddv + c]);
+    const i32x4 ka = *reinterpret_cast<const i32x4*>(&idx[vn * ldi + c]);
+    const i32x4 kb = *reinterpret_cast<const i32x4*>(&idx[ve * ldi + c]);
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (ka[e] == i ? a[e] : 0.f) + (kb[e] == j ? b[e] : 0.f);
+    *reinterpret_cast<f32x4*>(&dA[(long)(row0 + r) * ldda + c]) = o;
+  }
+}
+
+extern "C" int mmmot_pair_expand_max_bwd(const float* dV, int lddv, const int* idx, int ldi, float* dA, int ldda, int C,
+                                         const int* tile_row0, const int* tile_nrows, const int* tile_group, int T,
+                                         const int* grp_row0, const int* grp_N, const int* grp_M, const int* grp_vrow0,
+                                         void* stream) {
+  if (!dV || !idx || !dA || !tile_row0 || !tile_nrows || !tile_group || !grp_row0 || !grp_N || !grp_M || !grp_vrow0)
+    return MMMOT_EINVAL;
+  if (T <= 0 || C <= 0 || C % 4 != 0 || lddv % 4 != 0 || ldi % 4 != 0 || ldda % 4 != 0) return MMMOT_EINVAL;
+  if (lddv < C || ldi < C || ldda < C || !mm_al16(dV) || !mm_al16(idx) || !mm_al16(dA)) return MMMOT_EINVAL;
+  hipLaunchKernelGGL(pair_expand_max_bwd_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, dV, lddv, idx, ldi, dA,
+                     ldda, C, tile_row0, tile_nrows, tile_group, grp_row0, grp_M, grp_vrow0);
+  return mm_check(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
 // Backward of the 1-channel output layers (mmmot_rowdot): out[r] = act(sum_k a(r,k) w[k] + b), a = relu(X*sc + sh).
 //   gpre[r] = gout[gidx ? gidx[r] : r] * act'(out[r]);  dA[r][k] = gpre[r] * w[k];
 //   PW[t][k] = sum_{r in tile t} gpre[r] * a(r,k)  (k < K),  PW[t][K] = sum_r gpre[r]   (reduce over tiles: dw, db)

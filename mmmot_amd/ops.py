@@ -497,6 +497,20 @@ class HipOps:
                                             _iptr(gM), _iptr(vrow0), self._stream())
         _lib.check(st, 'mmmot_pair_expand_bwd')
 
+    def segment_argmax(self, X, C, segs, idx, sc=None, sh=None, relu=False, use_group=True):
+        """idx int32 [segs.n][>= C] <- the first row (0 .. count - 1) of every segment that attains the maximum
+        segment_mean(take_max=True) writes for the same arguments"""
+        st = self.lib.mmmot_segment_argmax(_ptr(X), _ld(X), C, _iptr(segs.start), _iptr(segs.count), _iptr(segs.stride),
+                                           _iptr(segs.group) if use_group else None, segs.n, _ptr(sc), _ptr(sh),
+                                           _ld(sc), int(bool(relu)), _iptr(idx), _ld(idx), self._stream())
+        _lib.check(st, 'mmmot_segment_argmax')
+
+    def pair_expand_max_bwd(self, dV, idx, dA, C, tiles, row0, gN, gM, vrow0):
+        st = self.lib.mmmot_pair_expand_max_bwd(_ptr(dV), _ld(dV), _iptr(idx), _ld(idx), _ptr(dA), _ld(dA), C,
+                                                _iptr(tiles.row0), _iptr(tiles.nrows), _iptr(tiles.group), tiles.T,
+                                                _iptr(row0), _iptr(gN), _iptr(gM), _iptr(vrow0), self._stream())
+        _lib.check(st, 'mmmot_pair_expand_max_bwd')
+
     def rowdot_bwd(self, X, K, w, b, sc, sh, tiles, act, gout, gidx, dA, PW):
         st = self.lib.mmmot_rowdot_bwd(_ptr(X), _ld(X), K, _ptr(w), float(b), _ptr(sc), _ptr(sh), _ld(sc),
                                        _iptr(tiles.row0), _iptr(tiles.nrows), _iptr(tiles.group), tiles.T, act,

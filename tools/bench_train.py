@@ -8,6 +8,7 @@ ragged ~300 pts/det) and at a cfg2-like sample (N=M=32, 64x64 crops, 512 pts/det
     python tools/bench_train.py --optim     # the optimizer step alone at the full model's 216 tensors
     python tools/bench_train.py --dropout   # the step with use_dropout on against off, and the two dropout launches
     python tools/bench_train.py --feed      # the training feed: step alone, TrainingPipeline.run serial / overlapped
+    python tools/bench_train.py --end-max   # the two launches of the end_mode='max' backward beside pair_expand_bwd
 
 ``--feed`` builds 8 two-frame samples of cfg1's shape from ``synth.make_sequence`` (poses, jittered boxes, 224 x 224
 crops, random-resized-crop + flip) and times (a) ``TrainingPipeline.step`` alone on one prepared sample (30 steps behind
@@ -32,6 +33,11 @@ must move.
 the same step with it off - 30 steps behind 5 warm-up steps each, the two models taking turns, three rounds - and the
 two dropout launches (csrc/dropout.hip) beside the launches they extend, on [P][512] rows: at cfg1's P and at 64 times
 that (past the last-level cache), events around 50 back-to-back launches, three runs.
+
+``--end-max`` times the backward of the new / end pool in both end modes on the pair rows of one sample (three modality
+rows): ``pair_expand_bwd`` (end_mode 'avg') against ``segment_argmax`` + ``pair_expand_max_bwd`` (end_mode 'max'), with
+``segment_mean(take_max)`` - the forward's pool, which reads the same rows as the arg-max pass - beside them; at cfg1's
+N = 10, M = 12 and at N = M = 32 and 128, events around 50 back-to-back launches, three runs.
 """
 import argparse
 import os
@@ -258,6 +264,42 @@ def time_dropout(dev):
                 name, ms[0], ms[1], ms[2], P * C * 4 / (med * 1e-3) / 1e12))
 
 
+def time_end_max(dev):
+    from mmmot_amd.backward import _aux
+    from mmmot_amd.ops import HipOps
+    from mmmot_amd.plan import BatchPlan
+    ops, C = HipOps(), 512
+    for N, M in ((10, 12), (32, 32), (128, 128)):
+        plan = BatchPlan([([N, M], None)], 32, dev, use_points=False)
+        PT, VT, aux = plan.pair_tiles, plan.v_tiles, _aux(plan)
+        ya = torch.randn(PT.R, 1024, device=dev)           # the stacked layer's output: the pool reads its first half
+        sc, sh = torch.rand(PT.G, C, device=dev) + 0.5, torch.randn(PT.G, C, device=dev) * 0.1
+        V, dV = torch.empty(VT.R, C, device=dev), torch.randn(VT.R, C, device=dev)
+        idx, dA = torch.empty(VT.R, C, dtype=torch.int32, device=dev), torch.empty(PT.R, C, device=dev)
+        common = (PT, PT.g_row0, plan.pg_N, plan.pg_M, aux.vrow0)
+        launches = [
+            ('segment_mean(take_max)', lambda: ops.segment_mean(ya[:, :C], C, plan.v_segs, V, sc=sc, sh=sh, relu=True, take_max=True)),
+            ('pair_expand_bwd', lambda: ops.pair_expand_bwd(dV, dA, C, *common)),
+            ('segment_argmax', lambda: ops.segment_argmax(ya[:, :C], C, plan.v_segs, idx, sc=sc, sh=sh, relu=True)),
+            ('pair_expand_max_bwd', lambda: ops.pair_expand_max_bwd(dV, idx, dA, C, *common)),
+        ]
+        print('N = %d, M = %d: %d pair rows x 512 (%.2f MB), %d new / end vectors' % (N, M, PT.R, PT.R * C * 4 / 1e6, VT.R))
+        for name, fn in launches:
+            for _ in range(5):
+                fn()
+            ms = []
+            for run in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(50):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ms.append(e0.elapsed_time(e1) / 50)
+            print('  %-24s %.4f / %.4f / %.4f ms a launch (three runs of 50)' % (name, ms[0], ms[1], ms[2]))
+
+
 def time_feed(dev):
     import numpy as np
     from mmmot_amd import augment, build_optim
@@ -364,10 +406,14 @@ def main():
     ap.add_argument('--optim', action='store_true', help='time the optimizer step alone: torch.optim.Adam under the '
                     'wrapper against optim.Adam')
     ap.add_argument('--labels', action='store_true', help='time the label step (labels.generate_gt) alone')
+    ap.add_argument('--end-max', action='store_true', help="time the two launches of the end_mode='max' backward beside "
+                    'pair_expand_bwd')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     if args.feed:
         return time_feed(dev)
+    if args.end_max:
+        return time_end_max(dev)
     if args.labels:
         return time_labels(dev)
     if args.dropout:
