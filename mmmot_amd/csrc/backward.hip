@@ -14,7 +14,7 @@
 // yhat is recomputed from the stored y with sc1 = rstd, sh1 = -mean*rstd (mmmot_gn_finalize with gamma = 1,
 // beta = 0).  Kernels here are plain fp32 (exact fp32 MFMA for dW): this slice is about correct gradients, checked
 // against torch.autograd on the oracle (tests/test_backward_gpu.py), not yet about speed.
-#include "common.h"
+#include "segpool.h"
 
 // ---------------------------------------------------------------------------
 // GroupNorm(+ReLU) backward pass 1: per-tile partial sums.  One workgroup per tile, thread -> 4 channels.
@@ -332,28 +332,33 @@ extern "C" int mmmot_pair_bwd(const float* dX, int lddx, const float* F, int ldf
 }
 
 // ---------------------------------------------------------------------------
+// The index walk of the two new / end backward kernels: element q of a pair tile -> its row of dA, its 4 channels, its
+// place (i, j) in the group's N x M block, and the rows of dV that hold "new" vector j and "end" vector i.
+struct PairExpandAt {
+  long row, vn, ve;
+  int c, i, j;
+};
+__device__ __forceinline__ PairExpandAt mm_pair_expand_at(int q, int C, int row0, int base, int M, int v0) {
+  const int r = q / (C / 4), local = base + r, i = local / M, j = local - i * M;  // base: the tile's first row in its group
+  return PairExpandAt{row0 + r, (long)v0 + j, (long)v0 + M + i, (q - r * (C / 4)) * 4, i, j};
+}
+
 // Backward of the strided means that make the new / end vectors (new_end.py:70-71): pair row (g, i, j) is one of the
 // N rows averaged into "new" vector j and one of the M rows averaged into "end" vector i of its group:
 //   dA[(g,i,j)][c] = dV[vrow0[g] + j][c] / N + dV[vrow0[g] + M + i][c] / M
-__global__ __launch_bounds__(256) void pair_expand_bwd_kernel(const float* __restrict__ dV, int lddv,
-                                                              float* __restrict__ dA, int ldda, int C,
-                                                              const int* __restrict__ tile_row0,
-                                                              const int* __restrict__ tile_nrows,
-                                                              const int* __restrict__ tile_group,
-                                                              const int* __restrict__ grp_row0,
-                                                              const int* __restrict__ grp_N, const int* __restrict__ grp_M,
-                                                              const int* __restrict__ grp_vrow0) {
+__global__ __launch_bounds__(256) void pair_expand_bwd_kernel(
+    const float* __restrict__ dV, int lddv, float* __restrict__ dA, int ldda, int C, const int* __restrict__ tile_row0,
+    const int* __restrict__ tile_nrows, const int* __restrict__ tile_group, const int* __restrict__ grp_row0,
+    const int* __restrict__ grp_N, const int* __restrict__ grp_M, const int* __restrict__ grp_vrow0) {
   const int t = blockIdx.x;
   const int row0 = tile_row0[t], nrows = tile_nrows[t], g = tile_group[t];
-  const int N = grp_N[g], M = grp_M[g], v0 = grp_vrow0[g];
+  const int N = grp_N[g], M = grp_M[g], v0 = grp_vrow0[g], base = row0 - grp_row0[g];
   const float in = 1.f / (float)N, im = 1.f / (float)M;
-  for (int idx = threadIdx.x; idx < nrows * (C / 4); idx += 256) {
-    const int r = idx / (C / 4), c = (idx - r * (C / 4)) * 4;
-    const int local = row0 + r - grp_row0[g];
-    const int i = local / M, j = local - i * M;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(&dV[((long)v0 + j) * lddv + c]);
-    const f32x4 b = *reinterpret_cast<const f32x4*>(&dV[((long)v0 + M + i) * lddv + c]);
-    *reinterpret_cast<f32x4*>(&dA[(long)(row0 + r) * ldda + c]) = a * in + b * im;
+  for (int q = threadIdx.x; q < nrows * (C / 4); q += 256) {
+    const PairExpandAt p = mm_pair_expand_at(q, C, row0, base, M, v0);
+    const f32x4 a = *reinterpret_cast<const f32x4*>(&dV[p.vn * lddv + p.c]);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(&dV[p.ve * lddv + p.c]);
+    *reinterpret_cast<f32x4*>(&dA[p.row * ldda + p.c]) = a * in + b * im;
   }
 }
 
@@ -372,86 +377,24 @@ extern "C" int mmmot_pair_expand_bwd(const float* dV, int lddv, float* dA, int l
 // sends the gradient to the FIRST row that attains the maximum.  The forward (segment_mean_kernel, flag bit 1) is not
 // touched and records no indices; the backward recomputes them from the tape:
 //   idx[s][c] = min { t : a(t) = max_u a(u) },  a(t) = relu(fmaf(X[start + t*stride][c], sc[g][c], sh[g][c]))
-// with the forward's fmaf / fmaxf expression, so that a(idx) is the value the forward wrote, bit for bit.
-// Decomposition of segment_mean_kernel (small_kernels.hip): grid = (nseg, ceil(C/256)), 4 waves split the rows of the
-// segment (wave w takes t = w, w + 4, ...), every lane owns 4 consecutive channels.  A wave keeps (value, index) with a
-// strict > over its increasing t; the waves are combined on (larger value, then LOWER INDEX) - not the lower wave: rows 1
-// and 4 sit in waves 1 and 0.  A wave without rows (count < 4) carries index -1 and never enters the combine.
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
+// a(t) is mm_seg_row of segpool.h - the function the forward calls - so a(idx) is the value the forward wrote, bit for
+// bit; the (value, index) rules of the waves are mm_seg_argmax_store there.
 __global__ __launch_bounds__(256) void segment_argmax_kernel(
     const float* __restrict__ X, int ldx, int C, const int* __restrict__ seg_start, const int* __restrict__ seg_count,
     const int* __restrict__ seg_stride, const int* __restrict__ seg_group, const float* __restrict__ sc,
     const float* __restrict__ sh, int ldsc, int relu, int* __restrict__ idx_out, int ldo) {
   __shared__ __attribute__((aligned(16))) float redv[4][256];
   __shared__ __attribute__((aligned(16))) int redi[4][256];
-  const int s = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c = blockIdx.y * 256 + lane * 4;
-  const bool cv = c < C;
-  const int start = seg_start[s], count = seg_count[s], stride = seg_stride ? seg_stride[s] : 1;
-  const int g = seg_group ? seg_group[s] : 0;
-  f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, h4 = {0.f, 0.f, 0.f, 0.f};
   const bool norm = (sc != nullptr);
-  if (norm && cv) {
-    s4 = *reinterpret_cast<const f32x4*>(&sc[(long)g * ldsc + c]);
-    h4 = *reinterpret_cast<const f32x4*>(&sh[(long)g * ldsc + c]);
-  }
-  auto ld = [&](int t) -> f32x4 {
-    f32x4 v = *reinterpret_cast<const f32x4*>(&X[((long)start + (long)t * stride) * ldx + c]);
-    if (norm) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], s4[e], h4[e]);
-    }
-    if (relu) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-    }
-    return v;
-  };
-  f32x4 best = {0.f, 0.f, 0.f, 0.f};
-  i32x4 bi = {-1, -1, -1, -1};
-  if (cv && wave < count) {
-    best = ld(wave);
-    bi = i32x4{wave, wave, wave, wave};
-    for (int t = wave + 4; t < count; t += 4) {
-      const f32x4 v = ld(t);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (v[e] > best[e]) {
-          best[e] = v[e];
-          bi[e] = t;
-        }
-    }
-  }
-  *reinterpret_cast<f32x4*>(&redv[wave][lane * 4]) = best;
-  *reinterpret_cast<i32x4*>(&redi[wave][lane * 4]) = bi;
-  __syncthreads();
-  if (wave == 0 && cv) {
-    // wave 0 holds row 0 (count >= 1 is the caller's to guarantee, as for mmmot_segment_mean)
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(&redv[w][lane * 4]);
-      const i32x4 k = *reinterpret_cast<const i32x4*>(&redi[w][lane * 4]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (k[e] >= 0 && (v[e] > best[e] || (v[e] == best[e] && k[e] < bi[e]))) {
-          best[e] = v[e];
-          bi[e] = k[e];
-        }
-    }
-    *reinterpret_cast<i32x4*>(&idx_out[(long)s * ldo + c]) = bi;
-  }
+  const SegPool k = mm_seg_pool(C, seg_start, seg_count, seg_stride, seg_group, norm, sc, sh, ldsc);
+  mm_seg_argmax_store(k, [&](int t) { return mm_seg_row(k, X, ldx, t, 0, norm, relu); }, redv, redi, idx_out, ldo);
 }
 
 extern "C" int mmmot_segment_argmax(const float* X, int ldx, int C, const int* seg_start, const int* seg_count,
                                     const int* seg_stride, const int* seg_group, int nseg, const float* sc,
                                     const float* sh, int ldsc, int relu, int* idx_out, int ldo, void* stream) {
-  if (!X || !seg_start || !seg_count || !idx_out || nseg <= 0 || C <= 0) return MMMOT_EINVAL;
+  if (!mm_seg_args_ok(X, ldx, C, seg_start, seg_count, nseg, sc, sh, ldsc, idx_out, ldo, true)) return MMMOT_EINVAL;
   if (relu < 0 || relu > 1) return MMMOT_EINVAL;
-  if (C % 4 != 0 || ldx % 4 != 0 || ldo % 4 != 0 || ldx < C || ldo < C || !mm_al16(X) || !mm_al16(idx_out)) return MMMOT_EINVAL;
-  if ((sc == nullptr) != (sh == nullptr)) return MMMOT_EINVAL;
-  if (sc && (ldsc % 4 != 0 || ldsc < C || !mm_al16(sc) || !mm_al16(sh))) return MMMOT_EINVAL;
   hipLaunchKernelGGL(segment_argmax_kernel, dim3(nseg, (C + 255) / 256), dim3(256), 0, (hipStream_t)stream, X, ldx, C,
                      seg_start, seg_count, seg_stride, seg_group, sc, sh, ldsc, relu, idx_out, ldo);
   return mm_check(hipGetLastError());
@@ -461,31 +404,23 @@ extern "C" int mmmot_segment_argmax(const float* X, int ldx, int C, const int* s
 // "new" vector j where it is that vector's arg-max row (i) and of "end" vector i where it is that one's (j):
 //   dA[(g,i,j)][c] = (idx[v0 + j][c] == i ? dV[v0 + j][c] : 0) + (idx[v0 + M + i][c] == j ? dV[v0 + M + i][c] : 0)
 // One pass over dA, every element written once (no zero-fill, no atomics): deterministic.
-__global__ __launch_bounds__(256) void pair_expand_max_bwd_kernel(const float* __restrict__ dV, int lddv,
-                                                                  const int* __restrict__ idx, int ldi,
-                                                                  float* __restrict__ dA, int ldda, int C,
-                                                                  const int* __restrict__ tile_row0,
-                                                                  const int* __restrict__ tile_nrows,
-                                                                  const int* __restrict__ tile_group,
-                                                                  const int* __restrict__ grp_row0,
-                                                                  const int* __restrict__ grp_M,
-                                                                  const int* __restrict__ grp_vrow0) {
+__global__ __launch_bounds__(256) void pair_expand_max_bwd_kernel(
+    const float* __restrict__ dV, int lddv, const int* __restrict__ idx, int ldi, float* __restrict__ dA, int ldda, int C,
+    const int* __restrict__ tile_row0, const int* __restrict__ tile_nrows, const int* __restrict__ tile_group,
+    const int* __restrict__ grp_row0, const int* __restrict__ grp_M, const int* __restrict__ grp_vrow0) {
   const int t = blockIdx.x;
   const int row0 = tile_row0[t], nrows = tile_nrows[t], g = tile_group[t];
   const int M = grp_M[g], v0 = grp_vrow0[g], base = row0 - grp_row0[g];
   for (int q = threadIdx.x; q < nrows * (C / 4); q += 256) {
-    const int r = q / (C / 4), c = (q - r * (C / 4)) * 4;
-    const int local = base + r;
-    const int i = local / M, j = local - i * M;
-    const long vn = (long)v0 + j, ve = (long)v0 + M + i;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(&dV[vn * lddv + c]);
-    const f32x4 b = *reinterpret_cast<const f32x4*>(&dV[ve * lddv + c]);
-    const i32x4 ka = *reinterpret_cast<const i32x4*>(&idx[vn * ldi + c]);
-    const i32x4 kb = *reinterpret_cast<const i32x4*>(&idx[ve * ldi + c]);
+    const PairExpandAt p = mm_pair_expand_at(q, C, row0, base, M, v0);
+    const f32x4 a = *reinterpret_cast<const f32x4*>(&dV[p.vn * lddv + p.c]);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(&dV[p.ve * lddv + p.c]);
+    const i32x4 ka = *reinterpret_cast<const i32x4*>(&idx[p.vn * ldi + p.c]);
+    const i32x4 kb = *reinterpret_cast<const i32x4*>(&idx[p.ve * ldi + p.c]);
     f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (ka[e] == i ? a[e] : 0.f) + (kb[e] == j ? b[e] : 0.f);
-    *reinterpret_cast<f32x4*>(&dA[(long)(row0 + r) * ldda + c]) = o;
+    for (int e = 0; e < 4; ++e) o[e] = (ka[e] == p.i ? a[e] : 0.f) + (kb[e] == p.j ? b[e] : 0.f);
+    *reinterpret_cast<f32x4*>(&dA[p.row * ldda + p.c]) = o;
   }
 }
 

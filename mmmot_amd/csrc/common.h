@@ -24,6 +24,9 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 static inline int mm_check(hipError_t e) { return e == hipSuccess ? MMMOT_OK : (int)e; }
 static inline bool mm_al16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// grid of a grid-stride launch of 256-thread workgroups over n items: one item per thread, at most 8192 workgroups
+static inline int mm_grid256(long n) { return (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192); }
+
 // CU count of the current device (one process drives one GPU); 0 when there is none.  A function-local static:
 // initialised once, thread-safe (C++11).
 static inline int mm_num_cu() {

@@ -105,7 +105,6 @@ __global__ __launch_bounds__(256) void cr_u8_normalize_kernel(const unsigned cha
 extern "C" int mmmot_u8_normalize(const unsigned char* u8, int N, int S, const float* mean_std, float* out, void* stream) {
   if (!u8 || !mean_std || !out || N <= 0 || S <= 0) return MMMOT_EINVAL;
   const long npix = (long)N * S * S;
-  const int grid = (int)((npix + 255) / 256 < 8192 ? (npix + 255) / 256 : 8192);
-  hipLaunchKernelGGL(cr_u8_normalize_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, u8, npix, S * S, mean_std, out);
+  hipLaunchKernelGGL(cr_u8_normalize_kernel, dim3(mm_grid256(npix)), dim3(256), 0, (hipStream_t)stream, u8, npix, S * S, mean_std, out);
   return mm_check(hipGetLastError());
 }

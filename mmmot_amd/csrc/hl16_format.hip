@@ -88,9 +88,8 @@ __global__ void hl16_pack_pow2_kernel(const float* __restrict__ x, u32x4* __rest
 extern "C" int mmmot_hl16_pack_pow2(const float* x, void* y, long n, const float* amax, int target, void* stream) {
   if (!x || !y || n <= 0 || n % 8 != 0 || !mm_al16(x) || !mm_al16(y) || target < -60 || target > 15) return MMMOT_EINVAL;
   const long nu = n / 8;
-  const long nb = (nu + 255) / 256;
-  hipLaunchKernelGGL(hl16_pack_pow2_kernel, dim3((unsigned)(nb < 8192 ? nb : 8192)), dim3(256), 0, (hipStream_t)stream, x,
-                     (u32x4*)y, nu, amax, target);
+  hipLaunchKernelGGL(hl16_pack_pow2_kernel, dim3(mm_grid256(nu)), dim3(256), 0, (hipStream_t)stream, x, (u32x4*)y, nu,
+                     amax, target);
   return mm_check(hipGetLastError());
 }
 

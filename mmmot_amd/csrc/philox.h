@@ -34,3 +34,10 @@ __host__ __device__ __forceinline__ u32x4 mm_philox4x32_10(unsigned c0, unsigned
 __host__ __device__ __forceinline__ u32x4 mm_dropout_words(unsigned long long seed, unsigned r, int c) {
   return mm_philox4x32_10(r, (unsigned)c >> 2, 0u, 0u, (unsigned)seed, (unsigned)(seed >> 32));
 }
+
+// keep(r, c + e) ? v[e] * scale : 0, for the words w of mm_dropout_words(seed, r, c)
+__device__ __forceinline__ f32x4 mm_drop4(f32x4 v, u32x4 w, unsigned threshold, float scale) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = w[e] >= threshold ? v[e] * scale : 0.f;
+  return v;
+}

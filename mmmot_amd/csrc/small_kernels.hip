@@ -3,7 +3,7 @@
 // per-row LayerNorm, the K=3 PointNet input layer, normalise+activate, fusion
 // combine and the dual-softmax.  All use 64-lane wave reductions and 16-byte
 // coalesced accesses along the channel axis.
-#include "common.h"
+#include "segpool.h"
 
 // ---------------------------------------------------------------------------
 // GroupNorm statistics -> scale/shift.  One workgroup per (group, norm-group).
@@ -178,99 +178,25 @@ extern "C" int mmmot_gn_finalize(const float* part, const int* grp_tile0, const 
 }
 
 // ---------------------------------------------------------------------------
-// Strided segment mean.  grid = (nseg, ceil(C/256)); 4 waves split the rows of
-// the segment, every lane owns 4 consecutive channels (1 KiB per wave load).
+// Strided segment mean (flag bit 0: ReLU in the row value; bit 1: the maximum over the segment instead of the mean,
+// new_end.py:72-74).  Decomposition, row value and reductions: segpool.h.
 __global__ __launch_bounds__(256) void segment_mean_kernel(
     const float* __restrict__ X, int ldx, int C, const int* __restrict__ seg_start,
     const int* __restrict__ seg_count, const int* __restrict__ seg_stride, const int* __restrict__ seg_group,
     const int* __restrict__ seg_div, const float* __restrict__ sc, const float* __restrict__ sh, int ldsc, int flags,
     float* __restrict__ out, int ldo, int hl16) {
-  const int relu = flags & 1;
-  const bool take_max = (flags & 2) != 0;  // maximum over the segment instead of the mean (new_end.py:72-74)
   __shared__ __attribute__((aligned(16))) float red[4][256];
-  const int s = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c = blockIdx.y * 256 + lane * 4;
-  const bool cv = c < C;
-  const int start = seg_start[s], count = seg_count[s], stride = seg_stride ? seg_stride[s] : 1;
-  const int g = seg_group ? seg_group[s] : 0;
-  f32x4 s4 = {1.f, 1.f, 1.f, 1.f}, h4 = {0.f, 0.f, 0.f, 0.f};
+  const int relu = flags & 1;
   const bool norm = (sc != nullptr);
-  if (norm && cv) {
-    s4 = *reinterpret_cast<const f32x4*>(&sc[(long)g * ldsc + c]);
-    h4 = *reinterpret_cast<const f32x4*>(&sh[(long)g * ldsc + c]);
-  }
-  const float a0 = take_max ? -3.0e38f : 0.f;
-  f32x4 acc0 = {a0, a0, a0, a0}, acc1 = acc0, acc2 = acc0, acc3 = acc0;
-  auto ld = [&](int t) -> f32x4 {
-    f32x4 v;
-    if (hl16 == 2) {
-      // hq8 row: 128-byte record per 32 channels = [32 x fp16 hi | 32 x e4m3 (unused here) | 32 x e4m3(lo * 2^9)]
-      const unsigned char* rec = reinterpret_cast<const unsigned char*>(X + ((long)start + (long)t * stride) * ldx) +
-                                 (c >> 5) * 128;
-      const f16x4 h = *reinterpret_cast<const f16x4*>(rec + 2 * (c & 31));
-      const int l = *reinterpret_cast<const int*>(rec + 96 + (c & 31));
-      const auto p0 = __builtin_amdgcn_cvt_pk_f32_fp8(l, false);
-      const auto p1 = __builtin_amdgcn_cvt_pk_f32_fp8(l, true);
-      v[0] = (float)h[0] + p0[0] * (1.f / 512.f);
-      v[1] = (float)h[1] + p0[1] * (1.f / 512.f);
-      v[2] = (float)h[2] + p1[0] * (1.f / 512.f);
-      v[3] = (float)h[3] + p1[1] * (1.f / 512.f);
-    } else if (hl16) {
-      // hl16 row (same bytes as fp32): unit u = c>>3 holds [hi8 | lo8] halves; this lane's 4 channels
-      const _Float16* rowp = reinterpret_cast<const _Float16*>(X + ((long)start + (long)t * stride) * ldx);
-      const f16x4 h = *reinterpret_cast<const f16x4*>(rowp + (c >> 3) * 16 + (c & 7));
-      const f16x4 l = *reinterpret_cast<const f16x4*>(rowp + (c >> 3) * 16 + 8 + (c & 7));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = mm_hl_join(h[e], l[e]);
-    } else {
-      v = *reinterpret_cast<const f32x4*>(&X[((long)start + (long)t * stride) * ldx + c]);
-    }
-    if (norm) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], s4[e], h4[e]);
-    }
-    if (relu) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-    }
-    return v;
-  };
-  auto mx4 = [](f32x4 a, f32x4 b) -> f32x4 {
-    f32x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = fmaxf(a[e], b[e]);
-    return r;
-  };
-  if (cv) {
-    int t = wave;
-    if (take_max) {
-      for (; t < count; t += 4) acc0 = mx4(acc0, ld(t));
-    } else {
-      for (; t + 12 < count; t += 16) {
-        const f32x4 v0 = ld(t), v1 = ld(t + 4), v2 = ld(t + 8), v3 = ld(t + 12);
-        acc0 += v0; acc1 += v1; acc2 += v2; acc3 += v3;
-      }
-      for (; t < count; t += 4) acc0 += ld(t);
-    }
-  }
-  const f32x4 acc = take_max ? acc0 : (acc0 + acc1) + (acc2 + acc3);
-  *reinterpret_cast<f32x4*>(&red[wave][lane * 4]) = acc;
-  __syncthreads();
-  if (wave == 0 && cv) {
-    f32x4 r = *reinterpret_cast<const f32x4*>(&red[0][lane * 4]);
-    if (take_max) {
-      r = mx4(mx4(r, *reinterpret_cast<const f32x4*>(&red[1][lane * 4])),
-              mx4(*reinterpret_cast<const f32x4*>(&red[2][lane * 4]), *reinterpret_cast<const f32x4*>(&red[3][lane * 4])));
-    } else {
-      r += *reinterpret_cast<const f32x4*>(&red[1][lane * 4]);
-      r += *reinterpret_cast<const f32x4*>(&red[2][lane * 4]);
-      r += *reinterpret_cast<const f32x4*>(&red[3][lane * 4]);
-      const float inv = 1.f / (float)(seg_div ? seg_div[s] : count);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] *= inv;
-    }
-    *reinterpret_cast<f32x4*>(&out[(long)s * ldo + c]) = r;
+  const SegPool k = mm_seg_pool(C, seg_start, seg_count, seg_stride, seg_group, norm, sc, sh, ldsc);
+  auto row = [&](int t) { return mm_seg_row(k, X, ldx, t, hl16, norm, relu); };
+  const bool take_max = (flags & 2) != 0;
+  mm_seg_put(k, red, take_max ? mm_seg_wave_max(k, row) : mm_seg_wave_sum(k, row));
+  if (k.wave == 0 && k.cv) {
+    if (take_max)
+      *reinterpret_cast<f32x4*>(&out[(long)k.s * ldo + k.c]) = mm_seg_max_waves(k, red);
+    else
+      mm_seg_mean_store(k, red, seg_div ? seg_div[k.s] : k.count, out, ldo);
   }
 }
 
@@ -328,13 +254,10 @@ extern "C" int mmmot_segment_mean(const float* X, int ldx, int C, const int* seg
                                   const int* seg_stride, const int* seg_group, const int* seg_div, int nseg,
                                   const float* sc, const float* sh, int ldsc, int relu, float* out, int ldo,
                                   int hl16, void* stream) {
-  if (!X || !seg_start || !seg_count || !out || nseg <= 0 || C <= 0) return MMMOT_EINVAL;
+  if (!mm_seg_args_ok(X, ldx, C, seg_start, seg_count, nseg, sc, sh, ldsc, out, ldo, false)) return MMMOT_EINVAL;
   if (hl16 && (C % 8 != 0 || ldx % 8 != 0)) return MMMOT_EINVAL;
   if (hl16 == 2 && (C % 32 != 0 || ldx % 32 != 0)) return MMMOT_EINVAL;
   if (hl16 < 0 || hl16 > 2 || relu < 0 || relu > 3) return MMMOT_EINVAL;
-  if (C % 4 != 0 || ldx % 4 != 0 || ldo % 4 != 0 || !mm_al16(X) || !mm_al16(out)) return MMMOT_EINVAL;
-  if ((sc == nullptr) != (sh == nullptr)) return MMMOT_EINVAL;
-  if (sc && (ldsc % 4 != 0 || !mm_al16(sc) || !mm_al16(sh))) return MMMOT_EINVAL;
   if (hl16 == 1 && !sc && relu == 0 && (C == 128 || C == 256 || C == 512) && mm_al16(X) && ldx % 8 == 0) {
     hipStream_t st = (hipStream_t)stream;
     if (C == 128)

@@ -1,19 +1,22 @@
 // Training step, second slice: what the backward of the LiDAR encoder and the loss need beyond the
 // kernels of backward.hip (GroupNorm backward, weight-gradient GEMM, row GEMM with the transposed weight):
 //   * mmmot_rows_gather_scale   - backward of the per-detection average pools (reference modules/point_net.py:32-39,
-//                                 139-148): every point row receives its detection's gradient row / point count;
+//                                 139-148): every point row receives its detection's gradient row / point count; and
+//                                 mmmot_rows_gather_scale_dropout, the same kernel template times the dropout mask
+//                                 (csrc/philox.h) of the forward pool in csrc/dropout.hip;
 //   * mmmot_pointnet_layer1_bwd - weight / bias gradient of the first shared-MLP layer (K = 3 | 4 input channels: not
 //                                 matrix-core shaped, like its forward mmmot_pointnet_layer1);
 //   * mmmot_score_loss          - the elementwise terms of TrackingLoss (reference cost.py:97-185: binary cross entropy
 //                                 with logits, masked L2, masked smooth L1) with their gradients in the same pass.
 // Plain fp32, deterministic (per-block partial sums, no atomics).
-#include "common.h"
+#include "philox.h"
 
-// X[r][c] = S[rowidx[r]][c] * (scale ? scale[rowidx[r]] : 1)
-__global__ __launch_bounds__(256) void rows_gather_scale_kernel(const float* __restrict__ S, int lds,
-                                                                const int* __restrict__ rowidx,
-                                                                const float* __restrict__ scale, float* __restrict__ X,
-                                                                int ldx, long R, int C) {
+// X[r][c] = S[rowidx[r]][c] * (scale ? scale[rowidx[r]] : 1); with DROP (mmmot_rows_gather_scale_dropout, the backward of
+// the dropout pool of csrc/dropout.hip) that product goes through mm_drop4: keep(r, c) ? dscale * product : 0
+template <bool DROP>
+__global__ __launch_bounds__(256) void rows_gather_scale_kernel(
+    const float* __restrict__ S, int lds, const int* __restrict__ rowidx, const float* __restrict__ scale,
+    float* __restrict__ X, int ldx, long R, int C, unsigned long long seed, unsigned threshold, float dscale) {
   const int C4 = C >> 2;
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < R * C4; idx += (long)gridDim.x * 256) {
     const long r = idx / C4;
@@ -25,6 +28,7 @@ __global__ __launch_bounds__(256) void rows_gather_scale_kernel(const float* __r
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] *= f;
     }
+    if (DROP) v = mm_drop4(v, mm_dropout_words(seed, (unsigned)r, c), threshold, dscale);
     *reinterpret_cast<f32x4*>(&X[r * ldx + c]) = v;
   }
 }
@@ -33,10 +37,19 @@ extern "C" int mmmot_rows_gather_scale(const float* S, int lds, const int* rowid
                                        long R, int C, void* stream) {
   if (!S || !rowidx || !X || R <= 0 || C <= 0 || C % 4 != 0 || lds % 4 != 0 || ldx % 4 != 0) return MMMOT_EINVAL;
   if (!mm_al16(S) || !mm_al16(X)) return MMMOT_EINVAL;
-  const long n4 = R * (C / 4);
-  const int grid = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
-  hipLaunchKernelGGL(rows_gather_scale_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, S, lds, rowidx, scale, X,
-                     ldx, R, C);
+  hipLaunchKernelGGL(rows_gather_scale_kernel<false>, dim3(mm_grid256(R * (C / 4))), dim3(256), 0, (hipStream_t)stream, S,
+                     lds, rowidx, scale, X, ldx, R, C, 0ull, 0u, 1.f);
+  return mm_check(hipGetLastError());
+}
+
+extern "C" int mmmot_rows_gather_scale_dropout(const float* S, int lds, const int* rowidx, const float* scale, float* X,
+                                               int ldx, long R, int C, unsigned long long seed, unsigned threshold,
+                                               float dscale, void* stream) {
+  if (!S || !rowidx || !X || R <= 0 || R > 0xFFFFFFFFL || C <= 0 || C % 4 != 0 || lds % 4 != 0 || ldx % 4 != 0)
+    return MMMOT_EINVAL;
+  if (lds < C || ldx < C || !mm_al16(S) || !mm_al16(X)) return MMMOT_EINVAL;
+  hipLaunchKernelGGL(rows_gather_scale_kernel<true>, dim3(mm_grid256(R * (C / 4))), dim3(256), 0, (hipStream_t)stream, S,
+                     lds, rowidx, scale, X, ldx, R, C, seed, threshold, dscale);
   return mm_check(hipGetLastError());
 }
 

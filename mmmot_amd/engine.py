@@ -319,13 +319,8 @@ class Engine:
         hl16 = POOL_INPUT[fmt]
         ops, Lt, hd, T = self.ops, plan.Lt, self.P['skippool'][s], plan.det_tiles
         pooled = self.buf('sp_pool', Lt, C)
-        first, second, npart = plan.crop_segments(hw)
-        if second is None:
-            ops.segment_mean(x, C, first, pooled, use_group=False, hl16=hl16)
-        else:  # two-level pool: row chunks of a crop -> partial sums -> mean (few crops: see plan._crop_segments)
-            partial = self.buf('sp_partial', npart, C)
-            ops.segment_mean(x, C, first, partial, use_group=False, hl16=hl16)
-            ops.segment_mean(partial, C, second, pooled, use_group=False)
+        # large maps in two levels: row chunks of a crop -> partial sums -> mean (few crops: see plan._crop_segments)
+        plan.crop_segments(hw).pool(ops, x, C, pooled, partial=lambda n: self.buf('sp_partial', n, C), hl16=hl16)
         if self.sp_fused and hasattr(ops, 'skippool_head'):
             ops.skippool_head(pooled, C, hd, EPS, cat[:, 128 * s:128 * (s + 1)], Lt)  # the whole head in one launch
             return

@@ -137,6 +137,45 @@ class Segments:
             _put(self, device, div=self.h_div)
 
 
+class PoolLevels:
+    """A strided pool (mmmot_segment_mean) as its levels, a Segments each: the first reads the rows, each further one the
+    partial rows of the level before.  One segment is one workgroup per 256 channels, so long segments are summed in
+    chunks first; the chunking fixes the summation order, which is why every user names its own `chunk` and `longer_than`."""
+
+    def __init__(self, levels):
+        self.levels, self.n = list(levels), levels[-1].n
+
+    @classmethod
+    def chunked(cls, start, count, stride, device, chunk, longer_than, div=None, repeat=False):
+        """The pool of `count[i]` rows from `start[i]` with `stride`, divided by `div` (each: one value, or one per segment;
+        div None: the mean).  A segment longer than `longer_than` rows: `chunk`-row chunks of every segment are summed
+        (divisor 1) and a second level pools each segment's chunk sums - chunked in turn, with `repeat`, until it fits."""
+        start, count = np.asarray(start, np.int64).reshape(-1), np.asarray(count, np.int64).reshape(-1)
+        n = len(start)
+        stride = np.broadcast_to(np.asarray(stride, np.int64), (n,))
+        div = None if div is None else np.broadcast_to(np.asarray(div, np.int64), (n,))
+        levels = []
+        while n and count.max() > longer_than and (repeat or not levels):
+            nch = -(-count // chunk)
+            off = np.concatenate([[0], np.cumsum(nch)[:-1]])
+            seg = np.repeat(np.arange(n), nch)
+            k = np.arange(len(seg)) - off[seg]  # chunk k of segment seg
+            levels.append(Segments(start[seg] + stride[seg] * chunk * k, np.minimum(chunk, count[seg] - chunk * k),
+                                   stride[seg], np.zeros(len(seg)), device, div=np.ones(len(seg))))
+            div = count if div is None else div
+            start, count, stride = off, nch, np.ones(n, np.int64)
+        return cls(levels + [Segments(start, count, stride, np.zeros(n), device, div=div)])
+
+    def pool(self, ops, X, C, out, partial=None, **first_level_kw):
+        """X [rows][C] -> out [n][C], one ops.segment_mean per level.  `first_level_kw` (hl16 / sc / sh / relu) describe X:
+        first level only.  `partial(rows)`: the buffer for a level's partial rows (default: a fresh tensor like X)."""
+        for seg in self.levels[:-1]:
+            part = partial(seg.n) if partial else torch.empty(seg.n, C, dtype=X.dtype, device=X.device)
+            ops.segment_mean(X, C, seg, part, use_group=False, **first_level_kw)
+            X, first_level_kw = part, {}
+        ops.segment_mean(X, C, self.levels[-1], out, use_group=False, **first_level_kw)
+
+
 class BatchPlan:
     """samples: list of (frame_counts, points_split) with frame_counts a list of
     per-frame detection counts and points_split the sample-local cumulative point
@@ -226,7 +265,7 @@ class BatchPlan:
         # ---- detection spaces -------------------------------------------
         self.det_tiles = RowTiles(L, device)
         self.F_tiles = RowTiles([nR * Lt], device)
-        self.crop_segs = {}  # (h*w) -> Segments over crops, built lazily
+        self.crop_segs = {}  # (h*w) -> PoolLevels over crops, built lazily
 
         # ---- association pairs ------------------------------------------
         pairs = []  # (sample, a_det0, N, b_det0, M)
@@ -285,20 +324,11 @@ class BatchPlan:
     def _crop_segments(self, hw, device):
         """Global average pool of every crop's hw pixels.  One workgroup reduces one segment, so with few crops (a single
         reference-shaped pair: 22 crops x 3136 pixels at stage 0) a segment per crop leaves 22 workgroups walking 3136
-        rows each - 0.3 ms at B = 1.  Maps of more than 256 pixels are therefore pooled in two levels: 256-row chunks of a crop are summed (divisor 1),
-        a second pass adds a crop's S partial rows and divides by hw.  Returns (first, second | None, rows of partials)."""
+        rows each - 0.3 ms at B = 1.  Maps of more than 256 pixels are therefore pooled in two levels (PoolLevels): fixed
+        256-row chunks of a crop are summed, a second pass adds a crop's partial rows and divides by hw - the summation
+        order of a crop does not depend on the batch it is in."""
         Lt = self.Lt
-        S = -(-hw // 256)  # fixed 256-row chunks: the summation order of a crop does not depend on the batch it is in
-        if S <= 1:
-            self.crop_segs[hw] = (Segments(np.arange(Lt) * hw, np.full(Lt, hw), np.ones(Lt), np.zeros(Lt), device), None, 0)
-            return self.crop_segs[hw]
-        chunk = 256
-        l, c = np.repeat(np.arange(Lt), S), np.tile(np.arange(S), Lt)
-        start = l * hw + c * chunk
-        count = np.minimum(chunk, hw - c * chunk)
-        first = Segments(start, count, np.ones(Lt * S), np.zeros(Lt * S), device, div=np.ones(Lt * S))
-        second = Segments(np.arange(Lt) * S, np.full(Lt, S), np.ones(Lt), np.zeros(Lt), device, div=np.full(Lt, hw))
-        self.crop_segs[hw] = (first, second, Lt * S)
+        self.crop_segs[hw] = PoolLevels.chunked(np.arange(Lt) * hw, np.full(Lt, hw), 1, device, chunk=256, longer_than=256)
         return self.crop_segs[hw]
 
     def crop_segments(self, hw):

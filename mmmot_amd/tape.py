@@ -11,44 +11,25 @@ import collections
 import numpy as np
 import torch
 
-from .plan import Segments
+from .plan import PoolLevels
 
 SEGSUM_CHUNK = 128  # rows per first-level segment of a long strided sum
 
 
 def chunked_segments(start, count, stride, device):
-    """sum (divisor 1) of `count[i]` rows from `start[i]` with `stride`: one Segments, or - any segment longer than
-    4 * SEGSUM_CHUNK rows - (first level: SEGSUM_CHUNK-row chunks of every segment, second level: a segment's chunk sums)"""
-    start, count = np.asarray(start, np.int64), np.asarray(count, np.int64)
-    n = len(start)
-    if n == 0 or count.max() <= 4 * SEGSUM_CHUNK:
-        return Segments(start, count, np.full(n, stride), np.zeros(n), device, div=np.ones(n))
-    nch = -(-count // SEGSUM_CHUNK)
-    s1, c1 = [], []
-    for i in range(n):
-        k = np.arange(nch[i])
-        s1.append(start[i] + stride * SEGSUM_CHUNK * k)
-        c1.append(np.minimum(SEGSUM_CHUNK, count[i] - SEGSUM_CHUNK * k))
-    s1, c1 = np.concatenate(s1), np.concatenate(c1)
-    first = Segments(s1, c1, np.full(len(s1), stride), np.zeros(len(s1)), device, div=np.ones(len(s1)))
-    off = np.concatenate([[0], np.cumsum(nch)[:-1]])
-    second = Segments(off, nch, np.ones(n), np.zeros(n), device, div=np.ones(n))
-    return (first, second)
+    """sum (divisor 1) of `count[i]` rows from `start[i]` with `stride` as PoolLevels: two levels - SEGSUM_CHUNK-row chunks of
+    every segment, then a segment's chunk sums - when any segment is longer than 4 * SEGSUM_CHUNK rows"""
+    return PoolLevels.chunked(start, count, stride, device, chunk=SEGSUM_CHUNK, longer_than=4 * SEGSUM_CHUNK, div=1)
 
 
 def segsum(eng, X, C, segs, out):
-    """segment sums through mmmot_segment_mean (divisor 1); `segs`: a Segments or a two-level pair of chunked_segments"""
-    if isinstance(segs, tuple):
-        part = torch.empty(segs[0].n, C, dtype=X.dtype, device=X.device)
-        eng.ops.segment_mean(X, C, segs[0], part, use_group=False)
-        eng.ops.segment_mean(part, C, segs[1], out, use_group=False)
-    else:
-        eng.ops.segment_mean(X, C, segs, out, use_group=False)
+    """segment sums through mmmot_segment_mean (divisor 1); `segs`: the PoolLevels of chunked_segments"""
+    segs.pool(eng.ops, X, C, out)
 
 
 def tile_sums(plan, tiles, device):
     """(per-group, total) segment tables that sum the [T][2][C] partials of a tiling, viewed as [2T][C] rows; built once
-    per (plan, tiling).  Each is a Segments, or - long segments - a two-level (chunks, chunk sums) pair for segsum: one
+    per (plan, tiling).  Each is a PoolLevels for segsum - long segments in two levels (chunks, chunk sums): one
     segment is one workgroup, and the 8 624 tiles of a full-resolution trunk layer walked by two workgroups were the 0.9 ms
     launches of the training step's kernel table (profiles/r05/rocprofv3_kernel_stats_train.txt)."""
     cache = plan.__dict__.setdefault('_tile_sums', {})
@@ -73,7 +54,7 @@ def colsum(eng, X):
     chunks, level after level, until at most 2 * COLSUM_CHUNK rows are left (1.1 M rows of 64 channels: viewed as 276 k rows
     of 256, 2 156 -> 17 -> 1)."""
     rows, C = int(X.shape[0]), int(X.shape[1])
-    cache = eng.__dict__.setdefault('_colsum_segs', {})  # the segment tables per row count: small uploads saved per call
+    cache = eng.__dict__.setdefault('_colsum_segs', {})  # the PoolLevels per row count: small uploads saved per call
     # narrow rows: a lane of the kernel owns 4 channels, so a 64-channel tensor would keep 16 lanes of a wave busy - k
     # consecutive rows are viewed as one row of k * C channels (the sums of the rows = r mod k classes), folded at the end
     fold, C0 = 1, C
@@ -81,24 +62,16 @@ def colsum(eng, X):
         while C * 2 <= 256 and rows % 2 == 0 and rows > 2 * COLSUM_CHUNK:
             fold, C, rows = fold * 2, C * 2, rows // 2
         X = X.view(rows, C)
-    while True:
-        key = (rows, str(X.device))
-        seg = cache.get(key)
-        if seg is None:
-            if len(cache) > 256:
-                cache.clear()
-            if rows > 2 * COLSUM_CHUNK:
-                n = -(-rows // COLSUM_CHUNK)
-                start = np.arange(n) * COLSUM_CHUNK
-                seg = Segments(start, np.minimum(COLSUM_CHUNK, rows - start), np.ones(n), np.zeros(n), X.device, div=np.ones(n))
-            else:
-                seg = Segments([0], [rows], [1], [0], X.device, div=[1])
-            cache[key] = seg
-        out = torch.empty(seg.n, C, dtype=X.dtype, device=X.device)
-        eng.ops.segment_mean(X, C, seg, out, use_group=False)
-        if seg.n == 1:
-            return out[0] if fold == 1 else out.view(fold, C0).sum(0)
-        X, rows = out, seg.n
+    key = (rows, str(X.device))
+    levels = cache.get(key)
+    if levels is None:
+        if len(cache) > 256:
+            cache.clear()
+        levels = cache[key] = PoolLevels.chunked([0], [rows], 1, X.device, chunk=COLSUM_CHUNK, longer_than=2 * COLSUM_CHUNK,
+                                                 div=1, repeat=True)
+    out = torch.empty(1, C, dtype=X.dtype, device=X.device)
+    levels.pool(eng.ops, X, C, out)
+    return out[0] if fold == 1 else out.view(fold, C0).sum(0)
 
 
 def unit(eng, C, dev, dtype=torch.float32):

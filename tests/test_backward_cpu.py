@@ -204,22 +204,22 @@ def test_two_level_segment_sums_equal_the_direct_sums():
     T, C = 5 * SEGSUM_CHUNK + 37, 8
     X = torch.randn(2 * T + 6, C, generator=g, dtype=torch.float64).float()
     segs = chunked_segments(np.array([0, 1, 2 * T]), np.array([T, T, 3]), 2, 'cpu')
-    assert isinstance(segs, tuple) and segs[0].n == 2 * 6 + 1 and segs[1].n == 3
+    assert len(segs.levels) == 2 and segs.levels[0].n == 2 * 6 + 1 and segs.levels[1].n == 3
     out = torch.zeros(3, C)
     segsum(eng, X, C, segs, out)
     want = torch.stack([X[0:2 * T:2].double().sum(0), X[1:2 * T:2].double().sum(0), X[2 * T:2 * T + 6:2].double().sum(0)])
     assert (out.double() - want).abs().max().item() < 1e-4
     short = chunked_segments(np.array([0, 1]), np.array([40, 40]), 2, 'cpu')
-    assert not isinstance(short, tuple)
+    assert len(short.levels) == 1
     tall = torch.randn(9000, C, generator=g)
     assert (colsum(eng, tall).double() - tall.double().sum(0)).abs().max().item() < 1e-3
     # 9000 x 8 is viewed as 1125 rows of 64 (three halvings, 1125 is odd), summed as 9 chunks of 128 rows, then the 9 chunk
     # sums, then the eight row classes are folded
-    assert eng._colsum_segs[(1125, 'cpu')].n == 9 and eng._colsum_segs[(9, 'cpu')].n == 1
+    assert [lv.n for lv in eng._colsum_segs[(1125, 'cpu')].levels] == [9, 1]
     assert (9000, 'cpu') not in eng._colsum_segs
     odd = torch.randn(1001, 12, generator=g)                      # odd row count: no folding, 8 chunks, then one segment
     assert (colsum(eng, odd).double() - odd.double().sum(0)).abs().max().item() < 1e-3
-    assert eng._colsum_segs[(1001, 'cpu')].n == 8
+    assert [lv.n for lv in eng._colsum_segs[(1001, 'cpu')].levels] == [8, 1]
     wide = torch.randn(4096, 520, generator=g)[:, :512]           # a column slice (not contiguous): summed as it lies
     assert (colsum(eng, wide).double() - wide.double().sum(0)).abs().max().item() < 2e-3
     small = torch.randn(7, 16, generator=g)

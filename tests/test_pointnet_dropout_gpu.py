@@ -74,9 +74,12 @@ def test_rows_gather_scale_dropout_is_the_plain_kernel_times_the_mask(hip, R_, C
 COUNTS = [1, 2, 3, 4, 5, 63, 64, 65, 257, 1000]
 
 
-def ragged(C, dev):
-    """segments of COUNTS rows, alternating between two groups with their own sc / sh"""
-    cnt = np.asarray(COUNTS)
+POOL_COUNTS = [1, 3, 4, 5, 13, 16, 17, 65]  # around the 4-wave split and the 16-row stride (tests/test_segpool_gpu.py)
+
+
+def ragged(C, dev, counts=COUNTS):
+    """segments of `counts` rows, alternating between two groups with their own sc / sh"""
+    cnt = np.asarray(counts)
     start = np.concatenate([[0], np.cumsum(cnt)[:-1]])
     grp = np.arange(len(cnt)) % 2
     X = rnd(int(cnt.sum()), C, seed=11)
@@ -84,9 +87,10 @@ def ragged(C, dev):
     return X, sc, sh, Segments(start, cnt, np.ones(len(cnt)), grp, dev), grp
 
 
-@pytest.mark.parametrize('C', [512, 8])
-def test_segment_mean_dropout_keeping_everything_is_segment_mean(hip, C):
-    X, sc, sh, sg, _ = ragged(C, DEV)
+@pytest.mark.parametrize('C,counts', [pytest.param(512, COUNTS, id='512'), pytest.param(8, COUNTS, id='8'),
+                                      pytest.param(4, POOL_COUNTS, id='4-short'), pytest.param(260, POOL_COUNTS, id='260-short')])
+def test_segment_mean_dropout_keeping_everything_is_segment_mean(hip, C, counts):
+    X, sc, sh, sg, _ = ragged(C, DEV, counts)
     Xg, scg, shg = X.cuda(), sc.cuda(), sh.cuda()
     want = torch.empty(sg.n, C, device=DEV)
     hip.segment_mean(Xg, C, sg, want, sc=scg, sh=shg, relu=True)
