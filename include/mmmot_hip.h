@@ -176,9 +176,20 @@ int mmmot_trunk_range_bind(unsigned int* counters4);
  * problems run several chained tiles per workgroup like production sizes do.  Results do not depend on it. */
 int mmmot_set_patch_grid_limit(int n);
 /* ABI 7.  tests: smallest block edge the trunk dispatcher may choose - 0 / 4 = automatic (maps of at most 4 x 4 pixels,
- * conv5_x at 64-pixel crops /root/reference/modules/vgg.py:67-80, run 16 whole maps per 256-row tile without halo),
+ * conv5_x at 64-pixel crops, reference modules/vgg.py:67-80, run 16 whole maps per 256-row tile without halo),
  * 8 = such maps run as one haloed 8 x 8 block at 25 % fill like before ABI 7.  Results do not depend on it, bit for bit. */
 int mmmot_set_patch_min_block(int bs);
+/* tests (additive, ABI unchanged): output channels per tile of the patch kernels - 0 = automatic (csrc/patch_choice.h: 64-
+ * channel tiles where twice as many tiles fill the CUs better, and wherever Cout % 128 != 0), 64, or 128 = 128-channel
+ * tiles wherever Cout % 128 == 0.  The fused first launches always run 64-channel tiles.  Any other value: MMMOT_EINVAL.
+ * Results do not depend on it, bit for bit (tests/test_trunk_kernels_gpu.py). */
+int mmmot_set_patch_tile_width(int bn);
+/* What the next mmmot_conv3x3_bn_relu_hl16_patch / mmmot_conv3x3_raw_hl16 / mmmot_conv3x3_bn_relu_hq8 launch of this
+ * shape would use under the three knobs above: bn = channels per tile (64 | 128), bs = block edge (16 | 8 | 4), items =
+ * tiles (pixel tiles x channel tiles), grid = persistent workgroups.  Host pointers, any of them may be NULL.  No launch.
+ * L, H, W >= 1, Cout % 64 == 0, else MMMOT_EINVAL.  The choice is one pure host function (csrc/patch_choice.h,
+ * pinned without a GPU by tests/test_patch_choice_cpu.py). */
+int mmmot_patch_choice(int L, int H, int W, int Cout, int* bn, int* bs, int* items, int* grid);
 #ifdef MMMOT_DEBUG
 /* -DMMMOT_DEBUG builds only (tools/, never the product library; csrc/patch_debug.h): phase timers of the patch kernel
  * (0 = the product kernels, 9 = the timed instantiations; results are correct either way) and their read-out. */

@@ -13,7 +13,7 @@
 // is an in-register max and the pooled NHWC store index is simply q.
 #include "common.h"
 
-// OUT16: write the output in the hl16 split-half format consumed by conv3x3_hl16.hip
+// OUT16: write the output in the hl16 split-half format consumed by conv3x3_hl16_patch.hip
 // (unit u of a pixel = [hi of channels 8u..8u+7 | lo of channels 8u..8u+7], 2-byte stores).
 // RAW: bias only - no ReLU, no folded BatchNorm - the pre-BatchNorm tensor of the training-mode trunk (train_vgg.hip) and,
 // with flipped / transposed weights, its input gradient.

@@ -1,9 +1,9 @@
 // hl16 trunk layer with an LDS-resident haloed activation patch ("patch" kernel).
 //
-// Same arithmetic and storage format as conv3x3_hl16.hip (3-term fp16 hi/lo split on
-// v_mfma_f32_32x32x16_f16, fp32 accumulate, hl16 activations and weights).  Different data movement,
-// driven by the measurements of round 1 (profiles/README.md): the tile kernels re-read the activation tile
-// once per tap through L2 (9x) and are bound by the ~3.5 B/clk/wave L2->CU path.  Here
+// Arithmetic and storage format of the hl16 trunk (include/mmmot_hip.h: 3-term fp16 hi/lo split on
+// v_mfma_f32_32x32x16_f16, fp32 accumulate, hl16 activations and weights).  The data movement is
+// driven by the measurements of round 1 (profiles/README.md): a tile kernel that re-reads the activation tile
+// once per tap through L2 (9x, like the fp32 kernel of conv3x3.hip) is bound by the ~3.5 B/clk/wave L2->CU path.  Here
 //   * a workgroup owns 256 output pixels as NB blocks of BS x BS pixels (16x16x1 or 8x8x4) and BN output
 //     channels; per 32-channel slab it holds the (BS+2)^2 haloed activation patch of every block in LDS
 //     (128 B per pixel: 4 hl16 units) and all 9 taps read their shifted A fragments from it: activation
@@ -24,6 +24,7 @@
 
 #include "common.h"
 
+#include "patch_choice.h"
 #include "patch_common.h"
 
 // RAW (training, mmmot_conv3x3_raw_hl16): the output is the plain convolution  acc * oscale + bias  as fp32 rows (8 floats
@@ -100,29 +101,40 @@ extern "C" int mmmot_set_patch_min_block(int bs) {
   return MMMOT_OK;
 }
 
+static std::atomic<int> g_patch_tile_width{0};
+// Test knob: output channels per tile (0 = the heuristic of patch_choice.h; 64; 128 = 128-channel tiles wherever the
+// layer has them, Cout % 128 == 0; the fused first launches stay at 64).  Results do not depend on it, bit for bit.
+extern "C" int mmmot_set_patch_tile_width(int bn) {
+  if (bn != 0 && bn != 64 && bn != 128) return MMMOT_EINVAL;
+  g_patch_tile_width.store(bn);
+  return MMMOT_OK;
+}
+
 static int pt_num_cu() { return mm_num_cu(); }
 
-// block edge of a layer: 16 x 16 blocks unless the whole map fits an 8 x 8 block; maps of at most 4 x 4 pixels
-// (conv5 at 64-pixel crops) take the halo-free whole-map geometry, 16 maps per tile
-static int pt_block_edge(int H, int W) {
-  if (H > 8 || W > 8) return 16;
-  if (H <= 4 && W <= 4 && g_patch_min_block.load() != 8) return 4;
-  return 8;
+// the instantiation and grid of a layer under the current knobs (patch_choice.h)
+static mmmot_patch_plan pt_plan(int L, int H, int W, int Cout) {
+  return mmmot_patch_choose(L, H, W, Cout, pt_num_cu(), g_patch_min_block.load(), g_patch_grid_limit.load(),
+                            g_patch_tile_width.load());
 }
 
-// 128- or 64-channel tiles?  128 halves the LDS traffic per MFMA, but a small problem (one reference-shaped frame pair:
-// 22 crops, 14 x 14 maps at conv5 = 88 tiles of 128 channels on 256 CUs) fills the chip better with twice as many
-// 64-channel tiles.  Same arithmetic per output element either way (bitwise identical results).
-static bool pt_use_bn64(int L, int H, int W, int Cout) {
-  if (Cout % 128 != 0) return true;
-  const int n_cu = pt_num_cu();
-  if (n_cu <= 0) return false;
-  const int bs = pt_block_edge(H, W), nb = 256 / (bs * bs);
-  const long nblk = (long)L * ((H + bs - 1) / bs) * ((W + bs - 1) / bs);
-  const long i128 = ((nblk + nb - 1) / nb) * (Cout / 128), i64 = 2 * i128;
-  auto eff = [&](long items) { return (double)items / (double)(((items + n_cu - 1) / n_cu) * n_cu); };
-  return 0.85 * eff(i64) > eff(i128);  // a 64-channel tile does half the work of a 128-channel one in ~0.59 of the time
+// What the next mmmot_conv3x3_bn_relu_hl16_patch / _raw_hl16 / _bn_relu_hq8 launch of this shape would use: channels per
+// tile, block edge, tiles and workgroups.  Any of the four pointers may be NULL.
+extern "C" int mmmot_patch_choice(int L, int H, int W, int Cout, int* bn, int* bs, int* items, int* grid) {
+  if (L <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cout % 64 != 0) return MMMOT_EINVAL;
+  if (pt_num_cu() <= 0) return MMMOT_EINVAL;
+  const mmmot_patch_plan p = pt_plan(L, H, W, Cout);
+  if (bn) *bn = p.bn;
+  if (bs) *bs = p.bs;
+  if (items) *items = p.items;
+  if (grid) *grid = p.grid;
+  return MMMOT_OK;
 }
+
+// F(BN, BS) for the plan's instantiation
+#define PT_DISPATCH(p, F)                                                              \
+  ((p).bn == 128 ? ((p).bs == 16 ? F(128, 16) : (p).bs == 8 ? F(128, 8) : F(128, 4)) \
+                 : ((p).bs == 16 ? F(64, 16) : (p).bs == 8 ? F(64, 8) : F(64, 4)))
 
 template <int BN, int BS, bool POOL, bool FUSE1 = false, bool Q8 = false, bool RAW = false PT_TIMED_TPARAM>
 static int launch_patch_e(const void* in, const void* wp, const float* bias, void* out, int L, int H, int W, int Cin,
@@ -134,11 +146,7 @@ static int launch_patch_e(const void* in, const void* wp, const float* bias, voi
   const int ntn = Cout / BN;
   const int n_cu = pt_num_cu();
   if (n_cu <= 0) return MMMOT_EINVAL;
-  const int nitems = ntm * ntn;
-  int grid = (n_cu / 8) * 8;                       // one persistent workgroup per CU, whole XCDs
-  const int glimit = g_patch_grid_limit.load();
-  if (glimit > 0 && grid > glimit) grid = glimit;
-  if (grid > ((nitems + 7) / 8) * 8) grid = ((nitems + 7) / 8) * 8;
+  const int grid = mmmot_patch_grid(ntm * ntn, n_cu, g_patch_grid_limit.load());  // persistent workgroups (patch_choice.h)
   unsigned int* rng = pt_range_block();
   if (!rng) return MMMOT_EINVAL;
   hipLaunchKernelGGL((conv3x3_hl16_patch_kernel<BN, BS, POOL, FUSE1, Q8, RAW PT_TIMED_TARG(TIMED)>), dim3(grid), dim3(512), 0, s,
@@ -174,14 +182,10 @@ extern "C" int mmmot_conv3x3_bn_relu_hl16_patch(const void* in, const void* wp, 
   if (Cin % 32 != 0 || Cout % 64 != 0) return MMMOT_EINVAL;  // odd maps: floor pooling (partial windows dropped)
   if (!mm_al16(in) || !mm_al16(wp) || !mm_al16(out)) return MMMOT_EINVAL;
   if ((long)L * H * W * (Cin / 4) >= (1L << 31) - 64) return MMMOT_EINVAL;  // 32-bit piece offsets
-  const int bs = pt_block_edge(H, W);
-  if (!pt_use_bn64(L, H, W, Cout))
-    return bs == 16 ? launch_patch_p<128, 16>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
-           : bs == 8 ? launch_patch_p<128, 8>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
-                     : launch_patch_p<128, 4>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
-  return bs == 16 ? launch_patch_p<64, 16>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
-         : bs == 8 ? launch_patch_p<64, 8>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
-                   : launch_patch_p<64, 4>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
+  const mmmot_patch_plan plan = pt_plan(L, H, W, Cout);
+#define PT_HL16(BNV, BSV) launch_patch_p<BNV, BSV>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
+  return PT_DISPATCH(plan, PT_HL16);
+#undef PT_HL16
 }
 
 // Training (mmmot_amd/train_vgg.py): the plain convolution out[p][n] = oscale[n] * sum in * wp + bias[n] as fp32 rows
@@ -195,10 +199,9 @@ extern "C" int mmmot_conv3x3_raw_hl16(const void* in, const void* wp, const floa
   if (Cin % 32 != 0 || Cout % 64 != 0) return MMMOT_EINVAL;
   if (!mm_al16(in) || !mm_al16(wp) || !mm_al16(out)) return MMMOT_EINVAL;
   if ((long)L * H * W * (Cin / 4) >= (1L << 31) - 64) return MMMOT_EINVAL;
-  const int bs = pt_block_edge(H, W);
+  const mmmot_patch_plan plan = pt_plan(L, H, W, Cout);
 #define PT_RAW(BNV, BSV) launch_patch_e<BNV, BSV, false, false, false, true>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
-  if (!pt_use_bn64(L, H, W, Cout)) return bs == 16 ? PT_RAW(128, 16) : bs == 8 ? PT_RAW(128, 8) : PT_RAW(128, 4);
-  return bs == 16 ? PT_RAW(64, 16) : bs == 8 ? PT_RAW(64, 8) : PT_RAW(64, 4);
+  return PT_DISPATCH(plan, PT_RAW);
 #undef PT_RAW
 }
 
@@ -250,14 +253,10 @@ extern "C" int mmmot_conv3x3_bn_relu_hq8(const void* in, const void* wp, const f
   if (Cin % 32 != 0 || Cout % 64 != 0) return MMMOT_EINVAL;  // odd maps: floor pooling (partial windows dropped)
   if (!mm_al16(in) || !mm_al16(wp) || !mm_al16(out)) return MMMOT_EINVAL;
   if ((long)L * H * W * (Cin / 4) >= (1L << 31) - 64) return MMMOT_EINVAL;
-  const int bs = pt_block_edge(H, W);
-  if (!pt_use_bn64(L, H, W, Cout))
-    return bs == 16 ? launch_q8_p<128, 16>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
-           : bs == 8 ? launch_q8_p<128, 8>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
-                     : launch_q8_p<128, 4>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
-  return bs == 16 ? launch_q8_p<64, 16>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
-         : bs == 8 ? launch_q8_p<64, 8>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
-                   : launch_q8_p<64, 4>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
+  const mmmot_patch_plan plan = pt_plan(L, H, W, Cout);
+#define PT_HQ8(BNV, BSV) launch_q8_p<BNV, BSV>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
+  return PT_DISPATCH(plan, PT_HQ8);
+#undef PT_HQ8
 }
 
 extern "C" int mmmot_conv1_fused_hq8(const float* crops, const void* w1, const float* bias1, float oscale1,

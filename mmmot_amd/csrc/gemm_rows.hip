@@ -11,7 +11,7 @@
 //
 // Two arithmetic paths behind one template:
 //   F16 = false : exact fp32 MFMA (v_mfma_f32_32x32x2_f32), BK = 32;
-//   F16 = true  : fp16 matrix cores with the 3-term hi/lo split of conv3x3_hl16.hip
+//   F16 = true  : fp16 matrix cores with the 3-term hi/lo split of conv3x3_hl16_patch.hip
 //                 (a_hi*w_hi + a_hi*w_lo + a_lo*w_hi on v_mfma_f32_32x32x16_f16, fp32 accumulate),
 //                 BK = 64.  W arrives pre-split (hl16 format, host-scaled by 1/oscale); the fp32
 //                 A operand is produced by the prologue and split while it is staged to LDS.

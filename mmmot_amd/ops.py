@@ -186,6 +186,17 @@ class HipOps:
         _lib.check(self.lib.mmmot_trunk_range_bind(None if counters is None else _ptr(counters, torch.int32)),
                    'mmmot_trunk_range_bind')
 
+    def set_patch_tile_width(self, bn):
+        """Test knob: output channels per tile of the patch kernels (0 = automatic, 64, 128; mmmot_set_patch_tile_width)."""
+        _lib.check(self.lib.mmmot_set_patch_tile_width(int(bn)), 'mmmot_set_patch_tile_width')
+
+    def patch_choice(self, L, H, W, Cout):
+        """(channels per tile, block edge, tiles, workgroups) of the next patch-kernel launch of this shape under the
+        current knobs (mmmot_patch_choice); no launch."""
+        v = [ctypes.c_int(0) for _ in range(4)]
+        _lib.check(self.lib.mmmot_patch_choice(L, H, W, Cout, *[ctypes.byref(x) for x in v]), 'mmmot_patch_choice')
+        return tuple(x.value for x in v)
+
     def hq8_pack(self, x, y):
         _lib.check(self.lib.mmmot_hq8_pack(_ptr(x), _ptr(y), x.numel(), self._stream()), 'mmmot_hq8_pack')
 

@@ -243,7 +243,7 @@ def test_conv1_fused_many_tiles_per_workgroup(hip, small_grid):
 
 def test_tile_width_heuristic_is_bitwise_neutral(hip):
     """Small problems run 64-channel tiles (twice as many items for the 256 CUs), large ones 128-channel tiles: the
-    launcher decides from the problem size alone (pt_use_bn64) and the per-element arithmetic is the same - the first
+    launcher decides from the problem size alone (csrc/patch_choice.h) and the per-element arithmetic is the same - the first
     two crops of a 512-crop launch (128-channel tiles) equal a 2-crop launch (64-channel tiles) bit for bit."""
     H = W = 16
     Cin, Cout = 64, 128
