@@ -273,6 +273,18 @@ int mmmot_gemm_rows(const mmmot_gemm_args* a, void* stream);
  * any size) with one 128-row tile per four-wave workgroup (two workgroups per CU) / two tiles per eight-wave workgroup;
  * 2 (the round-5 form of the wide kernel, removed in round 6) is rejected.  Y and part do not depend on it, bit for bit. */
 int mmmot_set_gemm_rows_variant(int v);
+/* tests (additive, ABI unchanged): cap the persistent grid of the wide kernel - 0 = automatic, n > 0: at most n
+ * workgroups, rounded down to whole groups of 8 * (N / 256) and never below one such group (the launcher's floor, the grid
+ * of an 8-CU part), so that a small problem walks the chains of items a production batch walks; negative: MMMOT_EINVAL.
+ * Y and part do not depend on it, bit for bit (tests/test_wide_kernels_gpu.py). */
+int mmmot_set_gemm_wide_grid_limit(int n);
+/* What the next mmmot_gemm_rows launch of these arguments would use under the variant and the grid limit above: wide =
+ * 1 the wide kernel | 0 the tile kernel, nh = 128-row tiles per workgroup of the wide kernel (1 | 2; 0 on the tile kernel),
+ * items = items of the launch (wide: groups of nh row tiles x 256-column tiles, padded to whole groups of 8 * (N / 256);
+ * tile kernel: T x column tiles), grid = workgroups.  Host pointers, any of them may be NULL.  No launch.  The argument
+ * checks of mmmot_gemm_rows, MMMOT_EINVAL where it would return that.  The choice is one pure host function
+ * (csrc/wide_choice.h, pinned without a GPU by tests/test_wide_choice_cpu.py). */
+int mmmot_gemm_rows_choice(const mmmot_gemm_args* a, int* wide, int* nh, int* items, int* grid);
 
 /* A-resident row GEMM for layers whose output is only ever reduced (PointNet conv5 128->1024 and
  * PointNet_v1.conv1 64->512, reference modules/point_net.py:28-39,138-148): the workgroup keeps its 128

@@ -86,6 +86,9 @@ SIGNATURES = {
     'mmmot_conv3x3_bn_relu': [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
     'mmmot_gemm_rows': [ctypes.POINTER(GemmArgs), c_f],
     'mmmot_set_gemm_rows_variant': [c_i],
+    'mmmot_set_gemm_wide_grid_limit': [c_i],
+    'mmmot_gemm_rows_choice': [ctypes.POINTER(GemmArgs), ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.POINTER(c_i),
+                               ctypes.POINTER(c_i)],
     'mmmot_gemm_ares': [ctypes.POINTER(GemmAresArgs), c_f],
     'mmmot_set_gemm_ares_variant': [c_i],
     'mmmot_gram_rows': [c_f, c_i, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_f],

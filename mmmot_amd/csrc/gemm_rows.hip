@@ -16,6 +16,7 @@
 //                 BK = 64.  W arrives pre-split (hl16 format, host-scaled by 1/oscale); the fp32
 //                 A operand is produced by the prologue and split while it is staged to LDS.
 #include "common.h"
+#include "wide_choice.h"
 
 #define G16_BK 64
 #define G16_LDT 72  // halves per LDS row (144 B): conflict-free ds_read_b128
@@ -389,9 +390,10 @@ static int dispatch_gemm(const mmmot_gemm_args* a, hipStream_t s) {
 
 // gemm_wide.hip: the K >= 256 layers of the pairwise block on a batch that fills the chip
 int mmmot_gemm_wide_try(const mmmot_gemm_args* a, hipStream_t s, int* status);
+mmmot_wide_plan mmmot_gemm_wide_plan(const mmmot_gemm_args* a);
 
-extern "C" int mmmot_gemm_rows(const mmmot_gemm_args* a, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
+// the argument checks of mmmot_gemm_rows and mmmot_gemm_rows_choice
+static int gemm_rows_check(const mmmot_gemm_args* a) {
   if (!a || !a->W || a->T <= 0 || !a->tile_row0 || !a->tile_nrows) return MMMOT_EINVAL;
   const int bk = a->w_hl16 ? G16_BK : MM_BK;
   if (a->K <= 0 || a->K % bk != 0 || a->N <= 0 || a->N % 64 != 0) return MMMOT_EINVAL;
@@ -409,9 +411,25 @@ extern "C" int mmmot_gemm_rows(const mmmot_gemm_args* a, void* stream) {
   if (a->dbias && !a->rowidx) return MMMOT_EINVAL;
   if (a->colsum && (!a->osc || !a->osh)) return MMMOT_EINVAL;
   if (a->w_hl16 && a->Y && (a->ldy % 4 != 0 || !mm_al16(a->Y))) return MMMOT_EINVAL;
+  return MMMOT_OK;
+}
+
+extern "C" int mmmot_gemm_rows(const mmmot_gemm_args* a, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (gemm_rows_check(a) != MMMOT_OK) return MMMOT_EINVAL;
   int status = MMMOT_OK;
   if (mmmot_gemm_wide_try(a, s, &status)) return status;
   return a->w_hl16 ? dispatch_gemm<true>(a, s) : dispatch_gemm<false>(a, s);
+}
+
+extern "C" int mmmot_gemm_rows_choice(const mmmot_gemm_args* a, int* wide, int* nh, int* items, int* grid) {
+  if (gemm_rows_check(a) != MMMOT_OK) return MMMOT_EINVAL;
+  const mmmot_wide_plan p = mmmot_gemm_wide_plan(a);
+  if (wide) *wide = p.wide;
+  if (nh) *nh = p.nh;
+  if (items) *items = p.nitems;
+  if (grid) *grid = p.grid;
+  return MMMOT_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "wide_choice.h"
 
 struct GwRaw {  // source values of one 16-k step of this lane's row: 8 consecutive k of b_j (PAIR) / X (NORM_RELU)
   f32x4 x[2];
@@ -454,49 +455,42 @@ extern "C" int mmmot_set_gemm_rows_variant(int v) {
   return MMMOT_OK;
 }
 
+static std::atomic<int> g_gemm_wide_grid_limit{0};
+// Test knob: 0 = automatic, n > 0 caps the persistent grid (csrc/wide_choice.h) so that a small problem walks the item
+// chains of a production batch.  Results do not depend on it (bit for bit).
+extern "C" int mmmot_set_gemm_wide_grid_limit(int n) {
+  if (n < 0) return MMMOT_EINVAL;
+  g_gemm_wide_grid_limit.store(n);
+  return MMMOT_OK;
+}
+
+// the plan of the next launch of these arguments under the current knobs (csrc/wide_choice.h): mmmot_gemm_wide_try and
+// mmmot_gemm_rows_choice (gemm_rows.hip)
+mmmot_wide_plan mmmot_gemm_wide_plan(const mmmot_gemm_args* a) {
+  return mmmot_wide_choose(a, mm_num_cu(), g_gemm_variant.load(), g_gemm_wide_grid_limit.load());
+}
+
 template <int NH, int AMODE, int PAIROP>
-static int gw_launch(const mmmot_gemm_args* a, hipStream_t s, int n_cu) {
-  const int ntn = a->N / 256;
-  const int nu = (a->T + NH - 1) / NH;               // groups of NH row tiles
-  const int nitems = ((nu + 7) / 8) * 8 * ntn;       // padded to whole groups of 8 x ntn column tiles
-  int grid = ((2 / NH) * n_cu / (8 * ntn)) * (8 * ntn);  // NH = 1: two workgroups per CU; whole groups (column tiles of a row tile on one XCD)
-  if (grid < 8 * ntn) grid = 8 * ntn;
-  if (grid > nitems) grid = nitems;
-  hipLaunchKernelGGL((gemm_wide_kernel<NH, AMODE, PAIROP>), dim3(grid), dim3(256 * NH), 0, s, *a, ntn, nitems);
+static int gw_launch(const mmmot_gemm_args* a, hipStream_t s, const mmmot_wide_plan& p) {
+  hipLaunchKernelGGL((gemm_wide_kernel<NH, AMODE, PAIROP>), dim3(p.grid), dim3(256 * NH), 0, s, *a, p.ntn, p.nitems);
   return mm_check(hipGetLastError());
 }
 
 template <int NH>
-static int gw_dispatch(const mmmot_gemm_args* a, hipStream_t s, int n_cu) {
-  if (a->amode == MMMOT_A_NORM_RELU) return gw_launch<NH, MMMOT_A_NORM_RELU, 0>(a, s, n_cu);
+static int gw_dispatch(const mmmot_gemm_args* a, hipStream_t s, const mmmot_wide_plan& p) {
+  if (a->amode == MMMOT_A_NORM_RELU) return gw_launch<NH, MMMOT_A_NORM_RELU, 0>(a, s, p);
   switch (a->pairop) {
-    case MMMOT_PAIR_MULTIPLY: return gw_launch<NH, MMMOT_A_PAIR, MMMOT_PAIR_MULTIPLY>(a, s, n_cu);
-    case MMMOT_PAIR_MINUS_ABS: return gw_launch<NH, MMMOT_A_PAIR, MMMOT_PAIR_MINUS_ABS>(a, s, n_cu);
-    default: return gw_launch<NH, MMMOT_A_PAIR, MMMOT_PAIR_MINUS>(a, s, n_cu);
+    case MMMOT_PAIR_MULTIPLY: return gw_launch<NH, MMMOT_A_PAIR, MMMOT_PAIR_MULTIPLY>(a, s, p);
+    case MMMOT_PAIR_MINUS_ABS: return gw_launch<NH, MMMOT_A_PAIR, MMMOT_PAIR_MINUS_ABS>(a, s, p);
+    default: return gw_launch<NH, MMMOT_A_PAIR, MMMOT_PAIR_MINUS>(a, s, p);
   }
 }
 
 // Called by mmmot_gemm_rows after its argument checks.  Returns 1 when the wide kernel took the launch (*status = its
-// result), 0 when the layer is left to the tile kernel.
+// result), 0 when the layer is left to the tile kernel.  The choice and the launch geometry are csrc/wide_choice.h's.
 int mmmot_gemm_wide_try(const mmmot_gemm_args* a, hipStream_t s, int* status) {
-  const int variant = g_gemm_variant.load();
-  if (variant == 1) return 0;
-  if (!a->w_hl16 || (a->K != 256 && a->K != 512) || a->N % 128 != 0) return 0;  // (whole 256-value pieces of the uniform rows)
-  if (a->amode != MMMOT_A_PAIR && a->amode != MMMOT_A_NORM_RELU) return 0;
-  if (a->dbias || a->colsum || a->act != MMMOT_ACT_NONE) return 0;
-  if (a->amode == MMMOT_A_PAIR && (a->ldf % 4 != 0 || a->K > a->ldf || !a->pair_uniform32)) return 0;
-  if (a->amode == MMMOT_A_NORM_RELU && a->ldsc < a->K) return 0;
-  if (a->Y && (a->ldy % 4 != 0)) return 0;
-  const int n_cu = mm_num_cu();
-  if (n_cu <= 0) return 0;
-  if (a->N % 256 != 0) return 0;  // 256-column items (the N = 128 layer of the block is HBM-bound on the tile kernel)
-  const long items = (long)((a->T + 1) / 2) * (a->N / 256);
-  // small problems (one reference-shaped frame pair) are latency-bound: more, smaller workgroups finish sooner
-  if (variant == 0 && items < n_cu / 2) return 0;
-  // eight waves sharing the weight stages win once every workgroup walks a long chain of items (cfg4's 32-pair batches:
-  // -4 .. -6 % against the four-wave form, tools/bench_rows_gemm.py); below that the two forms are within the box spread
-  // of each other and the four-wave form fills the chip with half as many rows
-  const bool nh2 = (variant == 4) || (variant == 0 && items >= 24L * n_cu);
-  *status = nh2 ? gw_dispatch<2>(a, s, n_cu) : gw_dispatch<1>(a, s, n_cu);
+  const mmmot_wide_plan p = mmmot_gemm_wide_plan(a);
+  if (!p.wide) return 0;
+  *status = p.nh == 2 ? gw_dispatch<2>(a, s, p) : gw_dispatch<1>(a, s, p);
   return 1;
 }

@@ -238,6 +238,30 @@ class HipOps:
              w_hl16=False, oscale=1.0, osc=None, osh=None, colsum=None):
         """W: [N][K] fp32 weights, or (w_hl16=True) the hl16 split-half copy scaled by 1/oscale.
         colsum [T][N] (+ osc/osh [G][N]): per-tile column sums of relu(v * osc + osh) (fused next-norm consumer)."""
+        a = self._gemm_args(W, tiles, N, K, X, bias, dbias, rowidx, Y, part, sc, sh, FA, FB, pair, amode, pairop, act,
+                            w_hl16, oscale, osc, osh, colsum)
+        _lib.check(self.lib.mmmot_gemm_rows(ctypes.byref(a), self._stream()), 'mmmot_gemm_rows')
+
+    def gemm_choice(self, W, tiles, N, K, **kw):
+        """(wide, nh, items, grid) of the gemm launch of the same arguments under the current variant and grid limit
+        (mmmot_gemm_rows_choice); no launch."""
+        d = dict(X=None, bias=None, dbias=None, rowidx=None, Y=None, part=None, sc=None, sh=None, FA=None, FB=None,
+                 pair=None, amode=A_PLAIN, pairop=0, act=ACT_NONE, w_hl16=False, oscale=1.0, osc=None, osh=None, colsum=None)
+        d.update(kw)
+        a = self._gemm_args(W, tiles, N, K, *[d[k] for k in ('X', 'bias', 'dbias', 'rowidx', 'Y', 'part', 'sc', 'sh', 'FA',
+                                                             'FB', 'pair', 'amode', 'pairop', 'act', 'w_hl16', 'oscale',
+                                                             'osc', 'osh', 'colsum')])
+        v = [ctypes.c_int(0) for _ in range(4)]
+        _lib.check(self.lib.mmmot_gemm_rows_choice(ctypes.byref(a), *[ctypes.byref(x) for x in v]), 'mmmot_gemm_rows_choice')
+        return tuple(x.value for x in v)
+
+    def set_gemm_wide_grid_limit(self, n):
+        """Test knob: cap of the wide kernel's persistent grid (0 = automatic; mmmot_set_gemm_wide_grid_limit)."""
+        _lib.check(self.lib.mmmot_set_gemm_wide_grid_limit(int(n)), 'mmmot_set_gemm_wide_grid_limit')
+
+    @staticmethod
+    def _gemm_args(W, tiles, N, K, X, bias, dbias, rowidx, Y, part, sc, sh, FA, FB, pair, amode, pairop, act, w_hl16,
+                   oscale, osc, osh, colsum):
         a = _lib.GemmArgs()
         a.X, a.ldx = _ptr(X), _ld(X)
         a.W = _ptr(W)
@@ -257,7 +281,7 @@ class HipOps:
         a.w_hl16, a.oscale = int(w_hl16), float(oscale)
         a.osc, a.osh, a.ldosc = _ptr(osc), _ptr(osh), _ld(osc)
         a.colsum = _ptr(colsum)
-        _lib.check(self.lib.mmmot_gemm_rows(ctypes.byref(a), self._stream()), 'mmmot_gemm_rows')
+        return a
 
     def gemm_ares(self, W16, oscale, tiles, N, K, X, sc, sh, bias=None, dbias=None, tile_dbrow=None, part=None,
                   osc=None, osh=None, colsum=None):

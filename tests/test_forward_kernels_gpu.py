@@ -91,7 +91,7 @@ def sentinel(value, *shape):
 # ---- gemm_rows --------------------------------------------------------------------------------------------------------
 @pytest.fixture
 def tile_kernel(hip):
-    """pins mmmot_gemm_rows to the tile kernel (the wide kernel of csrc/gemm_wide.hip has bitwise tests of its own)"""
+    """pins mmmot_gemm_rows to the tile kernel (the wide kernel of csrc/gemm_wide.hip has a pass of its own, tests/test_wide_kernels_gpu.py)"""
     assert hip.lib.mmmot_set_gemm_rows_variant(1) == 0
     yield
     assert hip.lib.mmmot_set_gemm_rows_variant(0) == 0

@@ -1,5 +1,7 @@
 """mmmot_gemm_rows with w_hl16=1: the row GEMM on the fp16 matrix cores (3-term hi/lo split) must agree
 with an fp64 GEMM to fp32-class accuracy in every A-operand mode."""
+import ctypes
+
 import pytest
 import torch
 
@@ -122,8 +124,11 @@ def test_gemm_wide_pair(hip, variants, pairop, N, K, NM):
     for v in (3, 4, 1):
         assert variants(v) == 0
         Yg, pg = torch.full((R + 1, N), float('nan')).cuda(), torch.full((tl.cpu.T, 2, N), float('nan')).cuda()
-        hip.gemm(Wg, tl.gpu, N, K, FA=Fg, FB=Fg, pair=pt, amode=2, pairop=pairop, bias=bg, Y=Yg, part=pg, w_hl16=True,
-                 oscale=osc)
+        kw = dict(FA=Fg, FB=Fg, pair=pt, amode=2, pairop=pairop, bias=bg, Y=Yg, part=pg, w_hl16=True, oscale=osc)
+        # which kernel the launch reaches (mmmot_gemm_rows_choice): N = 128 and M % 32 != 0 are the tile kernel's by design
+        eligible = N % 256 == 0 and all(m % 32 == 0 for _, m in NM)
+        assert hip.gemm_choice(Wg, tl.gpu, N, K, **kw)[:2] == ((1, v - 2) if eligible and v != 1 else (0, 0))
+        hip.gemm(Wg, tl.gpu, N, K, **kw)
         assert torch.isnan(Yg[R]).all(), 'row beyond the last tile written'
         outs[v] = (Yg[:R].cpu(), pg.cpu())
     close(outs[3][0], Y, 3e-6, 'wide gemm pair Y')
@@ -155,8 +160,11 @@ def test_gemm_wide_norm_relu(hip, variants, N, K, ldx, counts):
     for v in (3, 4, 1):
         assert variants(v) == 0
         Yg, pg = torch.full((R, N), float('nan')).cuda(), torch.full((tl.cpu.T, 2, N), float('nan')).cuda()
-        hip.gemm(W16.cuda(), tl.gpu, N, K, X=bufg[:, ldx - K:], bias=bias.cuda(), Y=Yg, part=pg, sc=sc.cuda(), sh=sh.cuda(),
-                 amode=1, w_hl16=True, oscale=osc)
+        kw = dict(X=bufg[:, ldx - K:], bias=bias.cuda(), Y=Yg, part=pg, sc=sc.cuda(), sh=sh.cuda(), amode=1, w_hl16=True,
+                  oscale=osc)
+        # which kernel the launch reaches (mmmot_gemm_rows_choice): N = 128 is the tile kernel's by design
+        assert hip.gemm_choice(W16.cuda(), tl.gpu, N, K, **kw)[:2] == ((1, v - 2) if N % 256 == 0 and v != 1 else (0, 0))
+        hip.gemm(W16.cuda(), tl.gpu, N, K, **kw)
         outs[v] = (Yg.cpu(), pg.cpu())
     close(outs[3][0], Y, 3e-6, 'wide gemm norm_relu Y')
     close(outs[3][1][:, 0], part[:, 0], 1e-5, 'wide gemm norm_relu tile sums')
@@ -175,11 +183,18 @@ def test_gemm_wide_long_chains_are_deterministic(hip, variants):
     W = rnd(N, K, seed=261, scale=K ** -0.5)
     W16, osc = split_w(W)
     pt = _pair_tables(tl, NM, [0], [250], 'cuda')
+    ncu = ctypes.c_int(0)
+    assert hip.lib.mmmot_device_info(torch.cuda.current_device(), ctypes.byref(ncu), None, 0) == 0
+    ncu = ncu.value
     outs = []
     for v in (1, 3, 3, 3, 4, 4, 4, 0):
         assert variants(v) == 0
         Yg, pg = torch.full((40000, N), float('nan')).cuda(), torch.full((tl.cpu.T, 2, N), float('nan')).cuda()
-        hip.gemm(W16.cuda(), tl.gpu, N, K, FA=Fm, FB=Fm, pair=pt, amode=2, pairop=0, Y=Yg, part=pg, w_hl16=True, oscale=osc)
+        kw = dict(FA=Fm, FB=Fm, pair=pt, amode=2, pairop=0, Y=Yg, part=pg, w_hl16=True, oscale=osc)
+        # 313 tiles: 157 * 4 = 628 items - the automatic choice is the wide kernel from 2 * 628 CUs down, NH = 2 below 27
+        auto = (0, 0) if 628 < ncu // 2 else (1, 2) if 628 >= 24 * ncu else (1, 1)
+        assert hip.gemm_choice(W16.cuda(), tl.gpu, N, K, **kw)[:2] == {1: (0, 0), 3: (1, 1), 4: (1, 2), 0: auto}[v]
+        hip.gemm(W16.cuda(), tl.gpu, N, K, **kw)
         outs.append((Yg, pg))
     for Yg, pg in outs[1:]:
         assert torch.equal(Yg, outs[0][0]), 'wide kernel (chained tiles) differs from the tile kernel'
