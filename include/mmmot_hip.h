@@ -539,6 +539,19 @@ int mmmot_u8_normalize(const unsigned char* u8, int N, int S, const float* mean_
 int mmmot_crop_resize_norm(const unsigned char* img, int H, int W, const int* boxes, int N, int S, int kmax,
                            const float* mean_std, int* work, float* out, unsigned char* out_u8, void* stream);
 
+/* The crops of NI images in ONE launch pair (additive in ABI 10): mmmot_crop_resize_norm with the image behind a table.
+ *   images [NI][4] int64, device: per image (device address of its uint8 pixels, H, W, row pitch in bytes >= 3 W);
+ *   img_of [N] int32, device: crop n is cut from image img_of[n];
+ *   boxes / S / mean_std / out / out_u8 as above, crop after crop in the order of `boxes`;
+ *   kmax and work (N*2*S*(2+kmax) ints) sized for the LARGEST box of the launch.
+ * The arithmetic is that of the single form (one coefficient routine, one pixel routine): out and out_u8 are bit-identical
+ * to NI calls of it, concatenated.  The table lives on the device, so its contents are the caller's to validate; a crop
+ * whose img_of lies outside [0, NI) is skipped by the kernel (its output is not written).  N = 0 is a no-op that returns
+ * 0.  MMMOT_EINVAL before any launch: a null pointer (both outputs NULL), NI < 1, N < 0, S outside [1, 256], kmax < 3. */
+int mmmot_crop_resize_norm_multi(const long long* images, int NI, const int* img_of, const int* boxes, int N, int S,
+                                 int kmax, const float* mean_std, int* work, float* out, unsigned char* out_u8,
+                                 void* stream);
+
 /* Training augmentation of those 8-bit crops (reference utils/build_util.py:110-144 train_transform behind
  * dataset/patchwise_dataset.py:161-171): per crop torchvision's resized_crop(img, top, left, h, w, (S, S), BILINEAR) -
  * for a PIL image img.crop((left, top, left + w, top + h)).resize((S, S), BILINEAR) - then hflip when flip is set
@@ -821,6 +834,26 @@ int mmmot_track_ids(const float* blocks, const int* pairs, const int* out_off, c
  * Returns MMMOT_EINVAL on a null pointer, B < 1 or max_n outside [0, 512] before any launch. */
 int mmmot_track_chain_ids(const float* blocks, const int* chains, const int* out_off, const int* frame_idx, int B,
                           int max_n, int* state, int* ids_out, void* stream);
+
+/* The ID step of S sequences in ONE launch (csrc/track_ids.hip: one workgroup per sequence runs the walk of the single
+ * forms), additive in ABI 10.  The arguments are those of mmmot_track_ids / mmmot_track_chain_ids, except:
+ *   states: int32 [S][MMMOT_TRACK_STATE_INTS], row s the state of sequence s;
+ *   seq_start: int32 [S + 1], device: entries [seq_start[s], seq_start[s+1]) of the launch are the CONSECUTIVE pairs
+ *   (windows) of sequence s, in order.
+ * Contract:
+ *   - a sequence with an empty range is neither read nor written;
+ *   - error flags are per sequence (word [2] of its row) and sticky, as in the single forms;
+ *   - a range that is decreasing or leaves [0, B] sets MMMOT_TRACK_ECONTRACT in that sequence's row: nothing of it is
+ *     walked and its ids_out words are not written.  The same holds for a sequence with an entry outside the launch's
+ *     limits in FRONT of its range (its place in ids_out cannot be told);
+ *   - ids_out has the layout of the single forms, entry after entry in launch order; the words of a sequence depend on
+ *     its own entries and state only, never on what the other sequences of the launch hold or do.
+ * The wave count follows max_nm / max_n as in the single forms.  Returns MMMOT_EINVAL before any launch for a null
+ * pointer, S < 1, B < 1 or max_nm / max_n outside [0, 512]. */
+int mmmot_track_ids_multi(const float* blocks, const int* pairs, const int* out_off, const int* frame_idx,
+                          const int* seq_start, int S, int B, int max_nm, int* states, int* ids_out, void* stream);
+int mmmot_track_chain_ids_multi(const float* blocks, const int* chains, const int* out_off, const int* frame_idx,
+                                const int* seq_start, int S, int B, int max_n, int* states, int* ids_out, void* stream);
 
 /* CLEAR-MOT evaluation of tracked sequences (reference kitti_devkit/evaluate_tracking.py:393-792
  * compute3rdPartyMetrics; csrc/clear_mot.hip), additive in ABI 10.  Four launches: one workgroup per frame (Hungarian

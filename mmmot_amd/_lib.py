@@ -134,6 +134,8 @@ SIGNATURES = {
     'mmmot_points_count': [c_f, c_i, c_i, c_f, c_i, c_i, c_f, c_f, c_f],
     'mmmot_points_scatter': [c_f, c_i, c_i, c_f, c_i, c_f, c_f, c_f, c_i, c_f],
     'mmmot_crop_resize_norm': [c_f, c_i, c_i, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f],
+    # images, NI, img_of, boxes, N, S, kmax, mean_std, work, out, out_u8, stream
+    'mmmot_crop_resize_norm_multi': [c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f],
     # crops_u8, params, L, S, mean_std, out, out_u8, stream
     'mmmot_crop_augment': [c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f],
     'mmmot_points_count_batched': [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f],
@@ -178,6 +180,9 @@ SIGNATURES = {
     'mmmot_track_ids': [c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f],
     # blocks, chains, out_off, frame_idx, B, max_n, state, ids_out, stream
     'mmmot_track_chain_ids': [c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f],
+    # blocks, pairs | chains, out_off, frame_idx, seq_start, S, B, max_n, states, ids_out, stream
+    'mmmot_track_ids_multi': [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f],
+    'mmmot_track_chain_ids_multi': [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f],
     'mmmot_clear_mot': [c_f, c_i, c_i, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_f, c_i, ctypes.c_double, ctypes.c_double,
                         ctypes.c_double, ctypes.c_double, c_f, c_f, c_f, c_f, c_f, c_f, c_f],
     # ids, cls, chains, B, max_n, max_L, out, out_off, stream

@@ -7,7 +7,8 @@ dataset/test_seq_dataset.py:212-218) with the valid-transform of utils/build_uti
     transform(img.crop((x1, y1, x2, y2)).resize((224, 224), Image.BILINEAR))
 
 One launch pair for all detections of a frame (csrc/crop_resize.hip); the result is bit-identical to the
-Pillow / torchvision pipeline and stays on the device.  No CPU fallback.
+Pillow / torchvision pipeline and stays on the device.  No CPU fallback.  ``crop_resize_u8_multi`` does the same for the
+frames of several sequences, of different sizes, in one launch pair (``mmmot_crop_resize_norm_multi``).
 
 Training (dataset/patchwise_dataset.py:161-171 with the train-transform of utils/build_util.py:113-131): the same 8-bit
 crop, then ``augment_crops`` - RandomResizedCrop + RandomHorizontalFlip + ToTensor + Normalize for given parameters, one
@@ -63,6 +64,83 @@ def crop_resize_normalize(frame, bboxes, size=224, mean=MEAN, std=STD, return_u8
                                     torch.cuda.current_stream().cuda_stream)
     _lib.check(st, 'mmmot_crop_resize_norm')
     return u8 if only_u8 else ((out, u8) if return_u8 else out)
+
+
+def image_table(frames):
+    """host int64 [S, 4] of (device address, H, W, row pitch in bytes) for device uint8 frames [H, W, 3]; a frame may be
+    a view with a row pitch above 3 W (unit strides inside a row).  Everything the kernel cannot check is checked here."""
+    rows = []
+    for i, f in enumerate(frames):
+        if not torch.is_tensor(f) or not f.is_cuda:
+            raise RuntimeError('crop_resize_u8_multi needs device frames; there is no CPU fallback')
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or f.shape[0] < 1 or f.shape[1] < 1:
+            raise TypeError('frame %d must be uint8 [H, W, 3]' % i)
+        if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.shape[1]:
+            raise ValueError('frame %d: pixels must be packed within a row and rows at least 3 W bytes apart' % i)
+        rows.append((f.data_ptr(), int(f.shape[0]), int(f.shape[1]), int(f.stride(0))))
+    return np.asarray(rows, dtype=np.int64).reshape(-1, 4)
+
+
+def check_image_index(img_of, n_images):
+    """int32 [N] per-crop image indices, refused unless every one lies in [0, n_images)"""
+    img_of = np.asarray(img_of, dtype=np.int64).reshape(-1)
+    if img_of.size and (img_of.min() < 0 or img_of.max() >= n_images):
+        raise ValueError('crop_resize_multi: image index %d outside [0, %d)'
+                         % (int(img_of.max() if img_of.max() >= n_images else img_of.min()), n_images))
+    return img_of.astype(np.int32)
+
+
+def crop_resize_multi(frames, boxes, img_of, size=224, mean=MEAN, std=STD, want_out=True, want_u8=True):
+    """ONE launch pair for the crops of several frames (``mmmot_crop_resize_norm_multi``): ``boxes`` int32 [N, 4] crop
+    boxes and ``img_of`` [N] the frame each is cut from.  Returns (fp32 [N, 3, size, size] or None, uint8
+    [N, size, size, 3] or None), bit for bit what ``crop_resize_normalize`` gives per frame."""
+    if not 1 <= int(size) <= 256:
+        raise ValueError('crop_resize_multi: crops of side 1 .. 256, got %s' % (size,))
+    table = image_table(frames)
+    img_of = check_image_index(img_of, len(frames))
+    boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
+    N = boxes.shape[0]
+    if img_of.shape[0] != N:
+        raise ValueError('crop_resize_multi: %d image indices for %d boxes' % (img_of.shape[0], N))
+    if not len(frames):
+        raise ValueError('crop_resize_multi: no frames')
+    dev = frames[0].device
+    out = torch.empty(N, 3, size, size, dtype=torch.float32, device=dev) if want_out else None
+    u8 = torch.empty(N, size, size, 3, dtype=torch.uint8, device=dev) if want_u8 else None
+    if N == 0:
+        return out, u8
+    ext = int(max((boxes[:, 2] - boxes[:, 0]).max(), (boxes[:, 3] - boxes[:, 1]).max(), 1))
+    kmax = 2 * int(math.ceil(max(1.0, ext / float(size)))) + 1  # for the largest box of the launch
+    # ONE upload: [image table as int32 pairs | boxes | image indices | mean, std bits]
+    S = len(frames)
+    a, b, c = 8 * S, 8 * S + 4 * N, 8 * S + 5 * N
+    stage = torch.empty(c + 6, dtype=torch.int32, pin_memory=True)
+    stage[:a] = torch.from_numpy(table).view(torch.int32).reshape(-1)
+    stage[a:b] = torch.from_numpy(boxes).reshape(-1)
+    stage[b:c] = torch.from_numpy(img_of)
+    stage[c:].view(torch.float32).copy_(torch.tensor(list(mean) + list(std), dtype=torch.float32))
+    dbuf = stage.to(dev, non_blocking=True)
+    work = torch.empty(N * 2 * size * (2 + kmax), dtype=torch.int32, device=dev)
+    st = _lib.load().mmmot_crop_resize_norm_multi(
+        dbuf.data_ptr(), S, _iptr(dbuf[b:c]), _iptr(dbuf[a:b]), N, int(size), kmax, _ptr(dbuf[c:].view(torch.float32)),
+        _iptr(work), None if out is None else _ptr(out), None if u8 is None else u8.data_ptr(),
+        torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, 'mmmot_crop_resize_norm_multi')
+    return out, u8
+
+
+def crop_resize_u8_multi(frames, bboxes_per_frame, size=224):
+    """The 8-bit crops of several frames, whose sizes may differ, in one launch pair: ``frames`` device uint8 [H, W, 3]
+    each, ``bboxes_per_frame`` per frame its [n, 4] float detections.  Returns (device uint8 [sum n, size, size, 3],
+    the frames' crops one after the other, and the per-frame counts)."""
+    if len(frames) != len(bboxes_per_frame):
+        raise ValueError('crop_resize_u8_multi: %d frames, %d box lists' % (len(frames), len(bboxes_per_frame)))
+    boxes = [boxes_of_bboxes(b) for b in bboxes_per_frame]
+    counts = [int(b.shape[0]) for b in boxes]
+    img_of = np.repeat(np.arange(len(frames)), counts)
+    _, u8 = crop_resize_multi(frames, np.concatenate(boxes + [np.zeros((0, 4), np.int32)]), img_of, size,
+                              want_out=False)
+    return u8, counts
 
 
 def u8_normalize(crops_u8, mean=MEAN, std=STD):

@@ -30,13 +30,12 @@ __global__ void cr_coeff_kernel(const int* __restrict__ boxes, int S, int kmax, 
   cr_coeffs(in_size, S, xx, kmax, bounds, kk);
 }
 
-// grid (N, S): one output row per workgroup, one output column per thread.
-__global__ __launch_bounds__(256) void cr_resize_kernel(const unsigned char* __restrict__ img, int H, int W,
-                                                        const int* __restrict__ boxes, int S, int kmax,
-                                                        const int* __restrict__ work, const float* __restrict__ ms,
-                                                        float* __restrict__ out, unsigned char* __restrict__ out_u8) {
-  const int n = blockIdx.x, oy = blockIdx.y, ox = threadIdx.x;
-  if (ox >= S) return;
+// output pixel (oy, ox) of crop n from the image img [H][W][3] whose rows lie `pitch` bytes apart: the body of both
+// resize kernels
+__device__ __forceinline__ void cr_resize_pixel(const unsigned char* __restrict__ img, int H, int W, long pitch,
+                                                const int* __restrict__ boxes, int n, int oy, int ox, int S, int kmax,
+                                                const int* __restrict__ work, const float* __restrict__ ms,
+                                                float* __restrict__ out, unsigned char* __restrict__ out_u8) {
   const int* b = boxes + n * 4;
   const int x1 = b[0], y1 = b[1];
   const int* hb = work + ((long)n * 2 + 0) * S * (2 + kmax);
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(256) void cr_resize_kernel(const unsigned char* __r
     const int gy = y1 + ymin + j;
     int h[3] = {1 << (CR_PREC - 1), 1 << (CR_PREC - 1), 1 << (CR_PREC - 1)};
     if (gy >= 0 && gy < H) {
-      const unsigned char* row = img + (long)gy * W * 3;
+      const unsigned char* row = img + (long)gy * pitch;
       for (int i = 0; i < xcnt; ++i) {
         const int gx = x1 + xmin + i;
         if (gx >= 0 && gx < W) {
@@ -74,6 +73,45 @@ __global__ __launch_bounds__(256) void cr_resize_kernel(const unsigned char* __r
       out[(((long)n * 3 + c) * S + oy) * S + ox] = cr_norm(v8, ms[c], ms[3 + c]);  // to_tensor, normalize
     }
   }
+}
+
+// grid (N, S): one output row per workgroup, one output column per thread.
+__global__ __launch_bounds__(256) void cr_resize_kernel(const unsigned char* __restrict__ img, int H, int W,
+                                                        const int* __restrict__ boxes, int S, int kmax,
+                                                        const int* __restrict__ work, const float* __restrict__ ms,
+                                                        float* __restrict__ out, unsigned char* __restrict__ out_u8) {
+  const int n = blockIdx.x, oy = blockIdx.y, ox = threadIdx.x;
+  if (ox >= S) return;
+  cr_resize_pixel(img, H, W, (long)W * 3, boxes, n, oy, ox, S, kmax, work, ms, out, out_u8);
+}
+
+// the same grid over the crops of NI images: crop n reads row img_of[n] of the image table [NI][4] = (address, H, W,
+// row pitch in bytes); a crop whose index lies outside [0, NI) is skipped (nothing of it is written)
+__global__ __launch_bounds__(256) void cr_resize_multi_kernel(const long long* __restrict__ images, int NI,
+                                                              const int* __restrict__ img_of,
+                                                              const int* __restrict__ boxes, int S, int kmax,
+                                                              const int* __restrict__ work,
+                                                              const float* __restrict__ ms, float* __restrict__ out,
+                                                              unsigned char* __restrict__ out_u8) {
+  const int n = blockIdx.x, oy = blockIdx.y, ox = threadIdx.x;
+  const int im = img_of[n];
+  if (ox >= S || im < 0 || im >= NI) return;
+  const long long* e = images + 4 * (long)im;
+  cr_resize_pixel((const unsigned char*)e[0], (int)e[1], (int)e[2], (long)e[3], boxes, n, oy, ox, S, kmax, work, ms, out,
+                  out_u8);
+}
+
+extern "C" int mmmot_crop_resize_norm_multi(const long long* images, int NI, const int* img_of, const int* boxes, int N,
+                                            int S, int kmax, const float* mean_std, int* work, float* out,
+                                            unsigned char* out_u8, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (N == 0) return 0;
+  if (!images || !img_of || !boxes || !mean_std || !work || (!out && !out_u8) || NI < 1 || N < 0) return MMMOT_EINVAL;
+  if (S <= 0 || S > 256 || kmax < 3) return MMMOT_EINVAL;
+  hipLaunchKernelGGL(cr_coeff_kernel, dim3(N, 2, (S + 63) / 64), dim3(64), 0, s, boxes, S, kmax, work);
+  hipLaunchKernelGGL(cr_resize_multi_kernel, dim3(N, S), dim3(256), 0, s, images, NI, img_of, boxes, S, kmax, work,
+                     mean_std, out, out_u8);
+  return mm_check(hipGetLastError());
 }
 
 extern "C" int mmmot_crop_resize_norm(const unsigned char* img, int H, int W, const int* boxes, int N, int S, int kmax,

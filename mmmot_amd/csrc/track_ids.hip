@@ -15,6 +15,10 @@
 //   the entry's LAST frame is stored when !same or frame 1 keeps a detection; otherwise nothing is stored (the
 //   reference's "only support check for 2 frame case" quirk: the next entry then runs as a discontinuity).
 // Behind the L IDs an entry writes frame_start (= same) and last_id; a window also `stored` (TAIL = 3).
+//
+// The walk is a device function (track_ids_walk).  The single entry points launch one workgroup on one state; the multi
+// ones (mmmot_track_ids_multi, mmmot_track_chain_ids_multi) launch one workgroup per sequence on a table of states, each
+// walking its own range of the launch's entries.
 #include "common.h"
 
 #define TK_MAXN 512
@@ -68,12 +72,12 @@ struct ChainTab {
   __device__ int frame(int t) const { return fi[t]; }
 };
 
+// the walk of one workgroup: entries [c0, c1) of the launch on ONE state, writing ids_out from word oo on
 template <int NW, class Tab>
-__global__ __launch_bounds__(64 * NW) void track_ids_kernel(const float* __restrict__ blocks,
-                                                            const int* __restrict__ table,
-                                                            const int* __restrict__ out_off,
-                                                            const int* __restrict__ frame_idx, int B, int cap,
-                                                            int* __restrict__ state, int* __restrict__ ids_out) {
+__device__ __forceinline__ void track_ids_walk(const float* __restrict__ blocks, const int* __restrict__ table,
+                                               const int* __restrict__ out_off, const int* __restrict__ frame_idx,
+                                               int c0, int c1, int oo, int cap, int* __restrict__ state,
+                                               int* __restrict__ ids_out) {
   constexpr int NT = 64 * NW;
   __shared__ int st[TK_MAXN], ids[2][TK_MAXN], red[8], bad;
   const int tid = threadIdx.x;
@@ -83,8 +87,7 @@ __global__ __launch_bounds__(64 * NW) void track_ids_kernel(const float* __restr
   int last_id = state[0], stored = state[1], flag = state[2], stored_n = state[3];
   __syncthreads();
 
-  int oo = 0;  // this entry's place in ids_out
-  for (int c = 0; c < B; ++c) {
+  for (int c = c0; c < c1; ++c) {  // oo: this entry's place in ids_out
     const Tab tab(table, frame_idx, c);
     const int T = tab.frames();
     bool ok = T >= 2 && T <= TK_MAX_T;
@@ -195,6 +198,55 @@ __global__ __launch_bounds__(64 * NW) void track_ids_kernel(const float* __restr
   }
 }
 
+template <int NW, class Tab>
+__global__ __launch_bounds__(64 * NW) void track_ids_kernel(const float* __restrict__ blocks,
+                                                            const int* __restrict__ table,
+                                                            const int* __restrict__ out_off,
+                                                            const int* __restrict__ frame_idx, int B, int cap,
+                                                            int* __restrict__ state, int* __restrict__ ids_out) {
+  track_ids_walk<NW, Tab>(blocks, table, out_off, frame_idx, 0, B, 0, cap, state, ids_out);
+}
+
+// S states in one launch: workgroup s walks entries [seq_start[s], seq_start[s + 1]) on row s of the state table.  Its
+// place in ids_out is the sum of the entries before its range, read from the table - it does not depend on what the
+// other workgroups do.  An entry outside the launch's limits in front of the range leaves that place unknown: the
+// stream gets MMMOT_TRACK_ECONTRACT and is not walked.
+template <int NW, class Tab>
+__global__ __launch_bounds__(64 * NW) void track_ids_multi_kernel(const float* __restrict__ blocks,
+                                                                  const int* __restrict__ table,
+                                                                  const int* __restrict__ out_off,
+                                                                  const int* __restrict__ frame_idx,
+                                                                  const int* __restrict__ seq_start, int B, int cap,
+                                                                  int* __restrict__ states, int* __restrict__ ids_out) {
+  const int s = blockIdx.x;
+  const int c0 = seq_start[s], c1 = seq_start[s + 1];
+  if (c0 == c1) return;  // an empty range: the stream is neither read nor written
+  int* state = states + (long)s * MMMOT_TRACK_STATE_INTS;
+  if (c0 < 0 || c1 > B || c0 > c1) {  // uniform over the workgroup
+    if (threadIdx.x == 0) state[2] |= MMMOT_TRACK_ECONTRACT;
+    return;
+  }
+  // every thread sums the same words (c0 is small: the entries of the streams in front)
+  int oo = 0;
+  bool ok = true;
+  for (int c = 0; c < c0 && ok; ++c) {
+    const Tab tab(table, frame_idx, c);
+    const int T = tab.frames();
+    ok = T >= 2 && T <= TK_MAX_T;
+    for (int t = 0; ok && t < T; ++t) {
+      const int n = tab.count(t);
+      ok = n >= 0 && n <= cap;
+      oo += n;
+    }
+    oo += Tab::TAIL;
+  }
+  if (!ok) {  // no place in ids_out can be told: nothing of this stream is walked
+    if (threadIdx.x == 0) state[2] |= MMMOT_TRACK_ECONTRACT;
+    return;
+  }
+  track_ids_walk<NW, Tab>(blocks, table, out_off, frame_idx, c0, c1, oo, cap, state, ids_out);
+}
+
 // one wave up to 128 detections a frame, as the solve; four above (max_n picks the kernel)
 template <class Tab>
 int launch_track_ids(const float* blocks, const int* table, const int* out_off, const int* frame_idx, int B, int max_n,
@@ -211,6 +263,21 @@ int launch_track_ids(const float* blocks, const int* table, const int* out_off, 
   return mm_check(hipGetLastError());
 }
 
+template <class Tab>
+int launch_track_ids_multi(const float* blocks, const int* table, const int* out_off, const int* frame_idx,
+                           const int* seq_start, int S, int B, int max_n, int* states, int* ids_out, void* stream) {
+  if (!blocks || !table || !out_off || !frame_idx || !seq_start || !states || !ids_out) return MMMOT_EINVAL;
+  if (S < 1 || B < 1 || max_n < 0 || max_n > TK_MAXN) return MMMOT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (max_n <= 128)
+    hipLaunchKernelGGL((track_ids_multi_kernel<1, Tab>), dim3(S), dim3(64), 0, st, blocks, table, out_off, frame_idx,
+                       seq_start, B, max_n, states, ids_out);
+  else
+    hipLaunchKernelGGL((track_ids_multi_kernel<4, Tab>), dim3(S), dim3(256), 0, st, blocks, table, out_off, frame_idx,
+                       seq_start, B, max_n, states, ids_out);
+  return mm_check(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" int mmmot_track_ids(const float* blocks, const int* pairs, const int* out_off, const int* frame_idx, int B,
@@ -221,4 +288,18 @@ extern "C" int mmmot_track_ids(const float* blocks, const int* pairs, const int*
 extern "C" int mmmot_track_chain_ids(const float* blocks, const int* chains, const int* out_off, const int* frame_idx,
                                      int B, int max_n, int* state, int* ids_out, void* stream) {
   return launch_track_ids<ChainTab>(blocks, chains, out_off, frame_idx, B, max_n, state, ids_out, stream);
+}
+
+extern "C" int mmmot_track_ids_multi(const float* blocks, const int* pairs, const int* out_off, const int* frame_idx,
+                                     const int* seq_start, int S, int B, int max_nm, int* states, int* ids_out,
+                                     void* stream) {
+  return launch_track_ids_multi<PairTab>(blocks, pairs, out_off, frame_idx, seq_start, S, B, max_nm, states, ids_out,
+                                         stream);
+}
+
+extern "C" int mmmot_track_chain_ids_multi(const float* blocks, const int* chains, const int* out_off,
+                                           const int* frame_idx, const int* seq_start, int S, int B, int max_n,
+                                           int* states, int* ids_out, void* stream) {
+  return launch_track_ids_multi<ChainTab>(blocks, chains, out_off, frame_idx, seq_start, S, B, max_n, states, ids_out,
+                                          stream);
 }

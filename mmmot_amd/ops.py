@@ -428,6 +428,14 @@ class HipOps:
                                             int(max_n), _iptr(state), _iptr(ids_out), self._stream())
         _lib.check(st, 'mmmot_track_chain_ids')
 
+    def track_ids_multi(self, blocks, table, out_off, frame_idx, seq_start, S, B, max_n, states, ids_out, chains=False):
+        """The ID step of S sequences in one launch; see mmmot_track_ids_multi / mmmot_track_chain_ids_multi
+        (``chains``).  seq_start [S + 1] and the state table [S, TRACK_STATE_INTS] are int32 device tensors."""
+        name = 'mmmot_track_chain_ids_multi' if chains else 'mmmot_track_ids_multi'
+        st = getattr(self.lib, name)(_ptr(blocks), _iptr(table), _iptr(out_off), _iptr(frame_idx), _iptr(seq_start),
+                                     int(S), int(B), int(max_n), _iptr(states), _iptr(ids_out), self._stream())
+        _lib.check(st, name)
+
     def clear_mot(self, boxes, nG, nT, nD, frames, NF, g_attr, t_attr, traj_off, traj_obj, NTr, seq_off, S, params,
                   frame_d, frame_i, gt_out, traj_i, seq_d, seq_i):
         """CLEAR-MOT evaluation of S sequences in four launches; see mmmot_clear_mot.  boxes / frame_d / seq_d: fp64

@@ -67,18 +67,27 @@ last frame, and ``pipe.tracks`` is filled through ``tracks.merge_chain_tracks``:
 frame 0 continues the stored frame and whose frame 1 keeps no detection is not stored at all - its frames keep the IDs
 they had (-1 if none) and the next window starts a new stretch of IDs.  ``window=2`` is the pair path above: the pair
 solver, the pair ID entry point, a pair's ``ids`` tuple.
+
+Frames without detections: the reference's dataset skips them (dataset/test_seq_dataset.py:82-102: a sample's second
+frame is the next NON-EMPTY one) and the network is not defined on one, so the pair path (``run``, ``run_offline``, the
+lockstep order) goes over the frames that hold a detection; callbacks and ``tracks`` keep the sequence's own frame
+indices, an empty frame's ``tracks`` entry is the empty array, and ``stats['empty_frames']`` counts them.
+
+Many sequences (``LockstepPipeline``): S live sequences step together in the ``reuse_appearance``
+order - per step one stage A, one trunk launch sequence, one ``forward_batch``, one solve, one multi-state ID launch and
+one hand-off copy for the pairs of all of them - and every sequence gets what ``SequencePipeline.run`` gives it alone.
 """
 import time
 
 import numpy as np
 import torch
 
-from .crops import crop_resize_u8
+from .crops import crop_resize_u8, crop_resize_u8_multi
 from . import ego
 from .points import align_points_batched, prep_points_batched
 from .association import select, select_chain
 from .tracker_glue import queue_scores, queue_solve, queue_solve_chains
-from .tracks import TrackState, merge_chain_tracks, merge_tracks, window_starts
+from .tracks import TrackState, TrackStates, merge_chain_tracks, merge_tracks, window_starts
 
 
 class FrameFeed:
@@ -113,6 +122,27 @@ def _check_poses(feeds):
         raise ValueError('SequencePipeline: %d of %d frames carry a pose; the ego-motion alignment needs the pose of '
                          'every frame (or of none)' % (n, len(feeds)))
     return n > 0
+
+
+def _skip_empty(feeds, callbacks):
+    """The pair path over the frames that hold a detection.  The reference's dataset never hands the tracker a frame
+    without detections (dataset/test_seq_dataset.py:82-102, "skip the empty frame"): a sample starts at a non-empty
+    frame and takes the NEXT NON-EMPTY frame as its second one, so the tracker sees the consecutive pairs of the
+    sequence with its empty frames left out (the network is not defined on an empty frame).  Returns (the kept feeds,
+    their indices in ``feeds``, the callbacks taking an index into the kept feeds and passing on the frame's own)."""
+    idx = [t for t, f in enumerate(feeds) if len(f.dets['bbox']) > 0]
+    if len(idx) == len(feeds):
+        return feeds, idx, callbacks
+    own = lambda f: None if f is None else (lambda t, x: f(idx[t], x))
+    return [feeds[t] for t in idx], idx, tuple(own(f) for f in callbacks)
+
+
+def _spread_tracks(tracks, idx, n_frames):
+    """the tracks of the kept frames at their own indices; a frame without detections has the empty array"""
+    out = [np.zeros(0, np.int64) for _ in range(n_frames)]
+    for t, ids in zip(idx, tracks):
+        out[t] = ids
+    return out
 
 
 def _pair_record(prev_feed, feed):
@@ -250,16 +280,19 @@ class SequencePipeline:
             ev.append(('forward', [e0, e1]))
         return out
 
-    def queue_hand_off(self, outs, groups):
+    def queue_hand_off(self, outs, groups, stream_of=None):
         """Queue the hand-off of ``groups`` = [(first frame, frames)], pairs or windows, behind their forward outputs
         ``outs``; returns the pending HandOff.  associate=True: with the groups' solve in one launch (the pair solver for
-        window = 2, the chain solver above); track=True: and the ID launch of these consecutive groups behind it."""
+        window = 2, the chain solver above); track=True: and the ID launch of these consecutive groups behind it.
+        ``stream_of`` (LockstepPipeline): the pairs belong to several sequences, pair g to ``stream_of[g]``, and
+        ``self.track_state`` is the table of their states."""
         tm = self.model.test_mode
         if not self.associate:
             return queue_scores(outs, tm)
         if self.window == 2:
             sel = [select(o[0], o[1], o[2], o[3], tm) for o in outs]
-            return queue_solve(sel, [(a['n'], b['n']) for _, (a, b) in groups], track=self.track_state,
+            track = self.track_state if stream_of is None else (self.track_state, list(stream_of))
+            return queue_solve(sel, [(a['n'], b['n']) for _, (a, b) in groups], track=track,
                                frame_idx=[(s, s + 1) for s, _ in groups])
         sel = [select_chain(o[0], o[1], o[2], o[3], tm) for o in outs]
         return queue_solve_chains(sel, [[f['n'] for f in fr] for _, fr in groups], track=self.track_state,
@@ -274,19 +307,20 @@ class SequencePipeline:
             self.track_state.reset()
             self.tracks = [np.full(len(f.dets['bbox']), -1, np.int64) for f in feeds]
 
-    def _deliver(self, s, k, r, on_scores, on_assign, on_tracks):
+    def _deliver(self, s, k, r, on_scores, on_assign, on_tracks, tracks=None):
         """the callbacks and the bookkeeping of the pair or window of k frames from frame s, a hand-off result; returns
-        what the run returns for it"""
+        what the run returns for it.  ``tracks``: the per-frame list to fill (default ``self.tracks``)"""
         t = s + k - 1
+        tracks = self.tracks if tracks is None else tracks
         if on_scores is not None:
             on_scores(t, r.scores)
         if on_assign is not None and r.assignment is not None:
             on_assign(t, r.assignment)
         if r.ids is not None:
             if self.window == 2:
-                merge_tracks(self.tracks, t, r.ids[0], r.ids[1], r.ids[2], on_tracks)
+                merge_tracks(tracks, t, r.ids[0], r.ids[1], r.ids[2], on_tracks)
             else:
-                merge_chain_tracks(self.tracks, range(s, s + k), r.ids[0], r.ids[1], r.ids[3], on_tracks)
+                merge_chain_tracks(tracks, range(s, s + k), r.ids[0], r.ids[1], r.ids[3], on_tracks)
         key = 'pairs' if self.window == 2 else 'windows'
         self.stats[key] = self.stats.get(key, 0) + 1
         return (r.scores, r.assignment) if self.associate else r.scores
@@ -337,8 +371,24 @@ class SequencePipeline:
                 raise ValueError('SequencePipeline.run: reuse_appearance=True runs the pair-shaped cached-rows forward; '
                                  'with window > 2 use run_offline, which encodes every frame once')
             self._check_window_poses(moving)
+        n_frames, idx = len(feeds), None
+        if self.window == 2:  # pairs: frames without detections are left out, as the reference's dataset leaves them out
+            feeds, idx, (on_scores, on_assign, on_tracks) = _skip_empty(feeds, (on_scores, on_assign, on_tracks))
         self._start_tracks(feeds)
-        return self._run_online(feeds, moving, on_scores, on_assign, on_tracks)
+        res = self._run_online(feeds, moving, on_scores, on_assign, on_tracks)
+        self.tracks = self._account_empty(self.tracks, idx, n_frames, self.reuse_appearance and len(feeds) >= 2)
+        return res
+
+    def _account_empty(self, tracks, idx, n_frames, once):
+        """after a pair run over the kept frames ``idx``: returns ``tracks`` at the sequence's own frame indices, and the
+        frames left out are counted.  ``once`` (the orders that encode every frame once): they count as encoded too, so that
+        ``encoded_frames`` stays the sequence's frame count - a frame without crops has nothing left to encode"""
+        if idx is None or len(idx) == n_frames:
+            return tracks
+        self.stats['empty_frames'] = self.stats.get('empty_frames', 0) + n_frames - len(idx)
+        if once:
+            self.stats['encoded_frames'] += n_frames - len(idx)
+        return _spread_tracks(tracks, idx, n_frames) if self.track else tracks
 
     # ---- the forward of a window of 3 .. 8 frames --------------------------------------------------------------------
     def _check_window_poses(self, moving):
@@ -459,9 +509,13 @@ class SequencePipeline:
         moving = _check_poses(feeds)
         if self.window > 2:
             self._check_window_poses(moving)
+        n_frames, idx = len(feeds), None
+        if self.window == 2:  # as in ``run``: the pairs of the frames that hold a detection
+            feeds, idx, (on_scores, on_assign, on_tracks) = _skip_empty(feeds, (on_scores, on_assign, on_tracks))
         self._start_tracks(feeds)
         frames = [self.prepare(f) for f in feeds]
         if len(frames) < 2:
+            self.tracks = self._account_empty(self.tracks, idx, n_frames, False)
             return []
         if moving and self.window == 2:  # one align launch per K frames, queued in front of their trunk launches
             for t0 in range(1, len(frames), K):
@@ -482,7 +536,175 @@ class SequencePipeline:
             done = self.finish_hand_off(self.queue_hand_off(outs, grp))
             for (s, fr), r in zip(grp, done):
                 res.append(self._deliver(s, len(fr), r, on_scores, on_assign, on_tracks))
+        self.tracks = self._account_empty(self.tracks, idx, n_frames, True)
         return res
+
+
+def lockstep_steps(lens):
+    """The lockstep schedule as a pure function: per step k the sequences (indices into ``lens``, their frame counts)
+    that have a pair (k, k + 1).  A sequence of fewer than two frames is in no step; the steps end with the longest."""
+    lens = [int(n) for n in lens]
+    return [[s for s, n in enumerate(lens) if n >= k + 2] for k in range(max([n - 1 for n in lens if n >= 2], default=0))]
+
+
+def lockstep_stage(lens, t):
+    """the sequences whose frame t goes through stage A: those with a frame t that have a pair at all"""
+    return [s for s, n in enumerate(lens) if int(n) >= 2 and int(n) > t]
+
+
+class LockstepPipeline(SequencePipeline):
+    """S live sequences frame by frame in lockstep: step k scores, solves and numbers pair (k, k+1) of EVERY sequence
+    that still has one, in one batched launch sequence ("Many sequences").
+
+    Per step: stage A of the live sequences' frames k+2 on the side stream (uploads, ONE ``prep_points_batched``, ONE
+    alignment launch for the sequences that carry poses, ONE multi-image crop launch) -> ONE ``encode_appearance`` over
+    the crops of the frames k+1 -> ONE ``forward_batch`` on the cached rows -> ONE solve, ONE multi-state ID launch
+    (tracks.TrackStates) and ONE hand-off copy.  This is the ``reuse_appearance`` order of SequencePipeline - every
+    frame goes through the trunk once - and its results are that pipeline's, sequence by sequence, bit for bit.
+
+    Sequences end independently; one shorter than two frames contributes nothing.  A frame without detections is
+    left out as SequencePipeline leaves it out (``_skip_empty``: step k scores a sequence's k-th pair of the frames that
+    hold a detection; callbacks and ``tracks`` keep the sequence's own frame indices); the hand-off
+    itself (tracker_glue.queue_solve with track=(states, stream_of)) answers a pair with an empty frame on the host
+    without taking the step's other pairs there, and its IDs come from the same ID launch.  After the hand-off the rows of every sequence's two frames are checked
+    (``appearance_is_current``): the sequences whose rows are stale get their states back from the step's snapshot,
+    are encoded again and redo their pair - three rounds at most.  Per sequence either every frame carries a pose or
+    none does; sequences may differ.  Pairs only: windows of 3 .. 8 frames run through SequencePipeline."""
+
+    def __init__(self, model, size=224, overlap=True, without_reflectivity=True, associate=False, track=False, window=2):
+        if int(window) != 2:
+            raise ValueError('LockstepPipeline steps through pairs (window=2), got window=%s; windows of 3 .. 8 frames '
+                             'run one sequence at a time: SequencePipeline(window=...)' % (window,))
+        if track and not associate:
+            raise ValueError('LockstepPipeline: track=True needs associate=True (the IDs come from the assignments)')
+        super().__init__(model, size, overlap, without_reflectivity, reuse_appearance=True, associate=associate,
+                         track=track)
+        self.track_state = None    # track=True: the TrackStates table of the running sequences
+        self.frames = None         # during a run: per sequence the prepared frames still in use
+        self.stats['steps'] = 0
+
+    # ---- stage A of one frame of each of several sequences ------------------------------------------------------------
+    def _prepare_many(self, feeds, prevs):
+        imgs = [f.img.to(self.dev, non_blocking=True) for f in feeds]
+        sweeps = [f.sweep.to(self.dev, non_blocking=True) for f in feeds]
+        pcs = prep_points_batched(sweeps, [f.info for f in feeds], [f.dets for f in feeds],
+                                  without_reflectivity=self.wo_refl)
+        pts = [pc['points'] if f.point_transform is None else f.point_transform(pc['points']).contiguous()
+               for f, pc in zip(feeds, pcs)]
+        aligned = [None] * len(feeds)
+        mv = [i for i, (f, p) in enumerate(zip(feeds, prevs)) if p is not None and f.pose is not None]
+        if mv:  # each aligned to the frame before it in its own sequence, all in one launch
+            rows = np.concatenate([[0], np.cumsum([int(pts[i].shape[0]) for i in mv])])
+            rec = np.stack([_pair_record(prevs[i], feeds[i]) for i in mv])
+            out = align_points_batched(torch.cat([pts[i] for i in mv]), rows, rec, 1)
+            for j, i in enumerate(mv):
+                aligned[i] = out[int(rows[j]):int(rows[j + 1])]
+        crops, counts = crop_resize_u8_multi(imgs, [f.dets['bbox'] for f in feeds], self.size)
+        frames, o = [], 0
+        for i, n in enumerate(counts):
+            frames.append({'crops': crops[o:o + n], 'points': pts[i], 'points_aligned': aligned[i],
+                           'split': np.asarray(pcs[i]['points_split'], dtype=np.int64), 'n': n, 'ready': None})
+            o += n
+        return frames
+
+    def prepare_many(self, feeds, prevs):
+        """stage A of ``feeds``, one frame of each of several sequences; ``prevs[i]``: the frame before ``feeds[i]`` in
+        its sequence (None for a first frame)"""
+        if not self.overlap:
+            return self._prepare_many(feeds, prevs)
+        cur = torch.cuda.current_stream(self.dev)
+        with torch.cuda.stream(self.side):
+            frames = self._prepare_many(feeds, prevs)
+            ready = torch.cuda.Event()
+            ready.record(self.side)
+        for a in frames:
+            a['ready'] = ready
+            for t in (a['crops'], a['points'], a['points_aligned']):
+                if t is not None:
+                    t.record_stream(cur)   # allocated on the side stream, consumed on the main one
+        return frames
+
+    # ---- one step: pair (k, k + 1) of the sequences ``live`` -----------------------------------------------------------
+    def _launch_step(self, frames, live, k):
+        """queue the encode of the frames that have no current rows, the forward of the pairs on the rows, and their
+        hand-off; returns the pending HandOff"""
+        prs = [(frames[s][k], frames[s][k + 1]) for s in live]
+        if len(prs) == 1:  # one sequence left in the step: the pair forward of SequencePipeline, trunk and head in one op
+            return self.queue_hand_off([self.launch_pair_cached(*prs[0])], [(k, list(prs[0]))], stream_of=live)
+        both = [f for pr in prs for f in pr]
+        self._wait(*both)
+        new = [f for f in both if not self._current(f)]
+        if new:
+            self.encode(new)
+        plan = self.model.make_plan([([a['n'], b['n']], self._window_split([a, b])) for a, b in prs], self.size)
+        with torch.no_grad():
+            outs = self.model.forward_batch(plan, None, torch.cat([p for a, b in prs for p in (a['points'], self._second(b))]),
+                                            appearance=torch.cat([f['rows'].rows for f in both]))
+        return self.queue_hand_off(outs, [(k, list(pr)) for pr in prs], stream_of=live)
+
+    def _checked_step(self, frames, live, k, done, snap):
+        """``_checked_scores`` for a step: the sequences whose rows the range guard rejected (or that went stale
+        otherwise) get their ID states back from ``snap``, and their pairs are computed again - theirs only"""
+        for _ in range(3):
+            stale = [i for i, s in enumerate(live)
+                     if not (self._current(frames[s][k]) and self._current(frames[s][k + 1]))]
+            if not stale:
+                return done
+            self.stats['recomputed_pairs'] += len(stale)
+            sub = [live[i] for i in stale]
+            if snap is not None:
+                self.track_state.restore(snap, sub)
+            for i, r in zip(stale, self.finish_hand_off(self._launch_step(frames, sub, k))):
+                done[i] = r
+        raise RuntimeError('mmmot_amd: the appearance rows of a step stayed stale after recomputing it three times')
+
+    def run(self, streams, on_scores=None, on_assign=None, on_tracks=None):
+        """``streams``: S lists of FrameFeed, of any lengths.  Returns per sequence the list ``SequencePipeline.run``
+        returns for it; the callbacks get (s, t, ..) with s the sequence; track=True: ``self.tracks[s]`` is that
+        pipeline's ``tracks``.  Every call starts every sequence anew."""
+        S = len(streams)
+        if S < 1:
+            raise ValueError('LockstepPipeline.run: no sequences')
+        for feeds in streams:
+            _check_poses(feeds)
+        # per sequence the frames that hold a detection (``_skip_empty``): step k scores its k-th pair of THOSE, and a
+        # frame index below is an index into them; the callbacks and ``tracks`` speak of the sequence's own indices
+        n_frames, bind = [len(f) for f in streams], lambda f, s: None if f is None else (lambda t, x: f(s, t, x))
+        kept = [_skip_empty(feeds, (bind(on_scores, s), bind(on_assign, s), bind(on_tracks, s)))
+                for s, feeds in enumerate(streams)]
+        streams, lens = [k[0] for k in kept], [len(k[0]) for k in kept]
+        if self.track:
+            self.track_state = TrackStates(S, self.dev)
+            self.tracks = [[np.full(len(f.dets['bbox']), -1, np.int64) for f in feeds] for feeds in streams]
+        res, frames = [[] for _ in range(S)], [{} for _ in range(S)]
+        self.frames = frames   # per sequence {frame index: its prepared frame}, the frames still in use
+
+        def stage_a(t):
+            live = lockstep_stage(lens, t)
+            if live:
+                feeds = [streams[s][t] for s in live]
+                for s, a in zip(live, self.prepare_many(feeds, [streams[s][t - 1] if t else None for s in live])):
+                    frames[s][t] = a
+        stage_a(0)
+        stage_a(1)
+        for k, live in enumerate(lockstep_steps(lens)):
+            snap = self.track_state.snapshot() if self.track else None   # recomputed pairs start from it again
+            pending = self._launch_step(frames, live, k)
+            stage_a(k + 2)   # queued before the host blocks on this step's results
+            done = self._checked_step(frames, live, k, self.finish_hand_off(pending), snap)
+            for s, r in zip(live, done):
+                res[s].append(self._deliver(k, 2, r, *kept[s][2], tracks=self.tracks[s] if self.track else None))
+                del frames[s][k]
+            self.stats['steps'] += 1
+        for s, (_, idx, _) in enumerate(kept):   # the frames left out, per sequence
+            tr = self._account_empty(self.tracks[s] if self.track else None, idx, n_frames[s], len(idx) >= 2)
+            if self.track:
+                self.tracks[s] = tr
+        return res
+
+    def run_offline(self, *args, **kwargs):
+        raise NotImplementedError('LockstepPipeline steps through live sequences; a sequence known in full runs through '
+                                  'SequencePipeline.run_offline')
 
 
 def time_sequence(model, feeds, size=224, overlap=True, warm=3, associate=False, track=False):

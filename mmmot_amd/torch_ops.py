@@ -411,6 +411,81 @@ _LIB.impl('track_chain_ids', _track_chain_ids, 'CUDA')
 _LIB.impl('track_chain_ids', _track_chain_ids_meta, 'Meta')
 
 
+#   mmmot::track_ids_multi(Tensor blocks, Tensor pairs, Tensor frame_idx, Tensor seq_start, Tensor(a!) states,
+#                          int max_nm) -> Tensor
+#   mmmot::track_chain_ids_multi(Tensor blocks, Tensor chains, Tensor frame_idx, Tensor seq_start, Tensor(a!) states,
+#                                int max_n) -> Tensor
+#       The ID step of S sequences in ONE launch (mmmot_track_ids_multi / mmmot_track_chain_ids_multi): states = the
+#       device int32 [S, TRACK_STATE_INTS] table; seq_start = CPU int32 [S + 1], entries [seq_start[s], seq_start[s+1])
+#       of the table are the consecutive pairs (windows) of sequence s.  seq_start is NOT checked here - a range that is
+#       decreasing or leaves [0, B] is answered by the kernel with ECONTRACT in that sequence's state.  The words of
+#       such a sequence in the returned buffer (and only those) are unwritten memory.  Same layout as the single forms.
+def _seq_start_checked(op, seq_start, states):
+    if states.dtype != torch.int32 or states.dim() != 2 or states.shape[1] != TRACK_STATE_INTS or states.shape[0] < 1 \
+            or not states.is_contiguous():
+        raise ValueError('mmmot::%s: states must be a contiguous int32 [S, %d] table' % (op, TRACK_STATE_INTS))
+    if seq_start.device.type != 'cpu' or seq_start.dtype != torch.int32 or \
+            tuple(seq_start.shape) != (states.shape[0] + 1,):
+        raise ValueError('mmmot::%s: seq_start must be a CPU int32 [S + 1] table' % op)
+
+
+def _track_launch_multi(op, layout, blocks, table, frame_idx, seq_start, states, max_n, chains):
+    """``_track_launch`` with the state table and seq_start behind the same pinned block"""
+    total, off, need = layout(table, frame_idx, int(blocks.numel()))
+    _seq_start_checked(op, seq_start, states)
+    if blocks.dtype != torch.float32 or not blocks.is_contiguous() or states.device != blocks.device:
+        raise ValueError('mmmot::%s: blocks must be a contiguous fp32 tensor on the states\' device' % op)
+    if max_n and (max_n < need or max_n > MAX_ASSOC):
+        raise ValueError('mmmot::%s: max_n %d does not cover the table (%d)' % (op, max_n, need))
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    B, S = int(table.shape[0]), int(states.shape[0])
+    a, b = table.numel(), table.numel() + B
+    c = b + frame_idx.numel()
+    host = torch.empty(c + S + 1, dtype=torch.int32, pin_memory=True)
+    host[:a] = table.reshape(-1)
+    host[a:b] = off
+    host[b:c] = frame_idx.reshape(-1)
+    host[c:] = seq_start
+    dev = host.to(blocks.device, non_blocking=True)
+    ids = torch.empty(total, dtype=torch.int32, device=blocks.device)
+    if blocks.numel() == 0:  # entries without a detection: never read, but not a null pointer
+        blocks = dev.view(torch.float32)
+    _ASSOC_OPS[0].track_ids_multi(blocks, dev[:a], dev[a:b], dev[b:c], dev[c:], S, B, max_n or need, states, ids,
+                                  chains=chains)
+    return ids
+
+
+def _track_ids_multi(blocks, pairs, frame_idx, seq_start, states, max_nm):
+    return _track_launch_multi('track_ids_multi', track_layout, blocks, pairs, frame_idx, seq_start, states, max_nm, False)
+
+
+def _track_ids_multi_meta(blocks, pairs, frame_idx, seq_start, states, max_nm):
+    total, _, _ = track_layout(pairs, frame_idx)
+    return blocks.new_empty((total,), dtype=torch.int32)
+
+
+def _track_chain_ids_multi(blocks, chains, frame_idx, seq_start, states, max_n):
+    return _track_launch_multi('track_chain_ids_multi', track_chain_layout, blocks, chains, frame_idx, seq_start, states,
+                               max_n, True)
+
+
+def _track_chain_ids_multi_meta(blocks, chains, frame_idx, seq_start, states, max_n):
+    total, _, _ = track_chain_layout(chains, frame_idx)
+    return blocks.new_empty((total,), dtype=torch.int32)
+
+
+_LIB.define('track_ids_multi(Tensor blocks, Tensor pairs, Tensor frame_idx, Tensor seq_start, Tensor(a!) states, '
+            'int max_nm) -> Tensor')
+_LIB.impl('track_ids_multi', _track_ids_multi, 'CUDA')
+_LIB.impl('track_ids_multi', _track_ids_multi_meta, 'Meta')
+_LIB.define('track_chain_ids_multi(Tensor blocks, Tensor chains, Tensor frame_idx, Tensor seq_start, Tensor(a!) states, '
+            'int max_n) -> Tensor')
+_LIB.impl('track_chain_ids_multi', _track_chain_ids_multi, 'CUDA')
+_LIB.impl('track_chain_ids_multi', _track_chain_ids_multi_meta, 'Meta')
+
+
 # ---- CLEAR-MOT evaluation (mmmot_amd/evaluate.py; csrc/clear_mot.hip) ----------------------------------------------
 #   mmmot::clear_mot(Tensor packed, int[] sizes, float[] params) -> Tensor
 #       Evaluates S sequences (mmmot_clear_mot: frame, trajectory, sequence and total launches).  packed: ONE device

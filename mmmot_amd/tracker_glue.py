@@ -20,7 +20,8 @@ import torch
 
 from .association import (associate, chain_block_size, chain_of, chains_table, pairs_table, select, select_chain,
                           split_of, unpack_chain)
-from .tracks import queue_chain_ids, queue_ids, split_chain_ids, split_ids
+from .tracks import (queue_chain_ids, queue_chain_ids_multi, queue_ids, queue_ids_multi, split_chain_ids, split_ids,
+                     split_ids_multi)
 
 # one pair or window on the host: scores (det L, [link 1 x n_t x n_{t+1} ...], new L, end L) as ``scores_for_solver``
 # returns them, assignment as ``ortools_solve`` does, ids = (ids0, ids1, frame_start, last_id) of ``tracks.split_ids``
@@ -59,11 +60,13 @@ class HandOff:
     still to be copied (None: nothing is left on the device), read by ``unpack_chain_hand_off`` with ``layout`` =
     (splits, S, K, n_ids); ``pairs``: the entries are pairs, whose ``ids`` come back as ``tracks.split_ids`` gives them.
     ``done``: per pair the (scores, assignment) a pair with an empty frame was given on the host at queue time; ``flat``
-    then holds the IDs alone.  ``outs`` (``queue_scores``): per entry the device outputs of a score-only hand-off."""
+    then holds the IDs alone.  In a hand-off over several sequences (``queue_solve`` with ``track=(states, stream_of)``)
+    ``done`` holds None for the pairs the device solved, which ``flat`` then carries as usual.  ``outs`` (``queue_scores``): per entry the device outputs of a score-only hand-off."""
 
-    def __init__(self, layout=None, flat=None, done=None, outs=None, test_mode=0, pairs=True):
+    def __init__(self, layout=None, flat=None, done=None, outs=None, test_mode=0, pairs=True, ids_reader=None):
         self.layout, self.flat, self.done, self.outs, self.test_mode = layout, flat, done, outs, test_mode
-        self.split_ids = split_ids if pairs else split_chain_ids
+        # ``ids_reader``: the reading of a multi-state ID launch (``_hand_off``), in place of the single-state ones
+        self.split_ids = ids_reader or (split_ids if pairs else split_chain_ids)
 
     def fetch(self):
         """the host copy -> per entry a result: ONE device-to-host copy of ``flat``; score-only: one per entry"""
@@ -72,8 +75,11 @@ class HandOff:
         flat = torch.zeros(0) if self.flat is None else self.flat.to('cpu')
         if self.done is None:
             return unpack_chain_hand_off(flat, *self.layout, split_ids=self.split_ids)
-        splits, _, _, n_ids = self.layout
-        return [PairResult(sc, asg, i) for (sc, asg), i in zip(self.done, unpack_ids(flat, splits, n_ids, self.split_ids))]
+        # entries answered on the host stand in ``done``; the others (None there) are read from the buffer, in order
+        splits, S, K, n_ids = self.layout
+        solved = iter(unpack_chain_hand_off(flat, [s for s, d in zip(splits, self.done) if d is None], S, K))
+        ids = unpack_ids(flat, splits, n_ids, self.split_ids)
+        return [PairResult(*(next(solved)[:2] if d is None else d), i) for d, i in zip(self.done, ids)]
 
 
 def unpack_ids(flat, splits, n_ids, split_ids=split_ids):
@@ -116,15 +122,35 @@ def queue_scores(outs, test_mode):
     return HandOff(outs=outs, test_mode=test_mode)
 
 
-def _hand_off(parts, out, splits, S, K, track, frame_idx, pairs, done=None):
+def _hand_off(parts, out, splits, S, K, track, frame_idx, pairs, done=None, block_order=None):
     """the common tail of ``queue_solve`` and ``queue_solve_chains``: with ``track`` the ID launch behind the solver
     blocks ``out``, its int32 result appended to ``parts`` (bits, not values), and the pending ``HandOff``"""
-    n_ids = 0
-    if track is not None:
+    n_ids, reader = 0, None
+    if isinstance(track, tuple):
+        # (tracks.TrackStates, stream_of): ONE launch for the entries of several sequences.  ``block_order``: the
+        # entries in the order their blocks lie in ``out``
+        states, stream_of = track
+        order = list(range(len(splits))) if block_order is None else list(block_order)
+        o_splits, o_streams = [splits[i] for i in order], [int(stream_of[i]) for i in order]
+        ids = (queue_ids_multi if pairs else queue_chain_ids_multi)(states, out, o_splits, [frame_idx[i] for i in order],
+                                                                    o_streams)
+        parts, n_ids = parts + [ids.view(torch.float32)], ids.numel()
+        reader = lambda flat, _: multi_ids_reader(flat, o_splits, o_streams, order, 2 if pairs else 3)
+    elif track is not None:
         ids = (queue_ids if pairs else queue_chain_ids)(track, out, splits, frame_idx)
         parts, n_ids = parts + [ids.view(torch.float32)], ids.numel()
     flat = None if not parts else parts[0] if len(parts) == 1 else torch.cat(parts)
-    return HandOff((splits, S, K, n_ids), flat, done, pairs=pairs)
+    return HandOff((splits, S, K, n_ids), flat, done, pairs=pairs, ids_reader=reader)
+
+
+def multi_ids_reader(flat, o_splits, o_streams, order, tail=2):
+    """host int32 buffer of a multi-state ID launch whose entries were queued in the order ``order`` (entry order[k] of
+    the hand-off at place k, of stream o_streams[k]) -> per entry of the hand-off, in ITS order, what
+    ``tracks.split_ids_multi`` gives"""
+    res = [None] * len(order)
+    for i, r in zip(order, split_ids_multi(flat, o_splits, o_streams, tail=tail)):
+        res[i] = r
+    return res
 
 
 def queue_solve(selected, splits, track=None, frame_idx=None):
@@ -132,11 +158,15 @@ def queue_solve(selected, splits, track=None, frame_idx=None):
     rows (det L, [link 1 x N x M], new L, end L) of ``association.select``; ``splits``: per pair (N, M).  Returns the
     pending ``HandOff``: one device buffer [det | new | end | link of every pair | solver output].
     ``track`` (a tracks.TrackState; the pairs are then CONSECUTIVE pairs of its sequence, ``frame_idx`` their frame
-    index pairs): the ID launch is queued behind the solve and its int32 result rides at the end of the same buffer."""
+    index pairs): the ID launch is queued behind the solve and its int32 result rides at the end of the same buffer.
+    ``track`` = (tracks.TrackStates, stream_of): the pairs belong to several sequences, pair p to ``stream_of[p]``
+    (``states`` may be None: no IDs); one multi-state ID launch serves all of them, and a pair with an empty frame is
+    split off - answered on the host as above, while the others are solved in the one launch."""
     splits = [(int(N), int(M)) for N, M in splits]
+    if isinstance(track, tuple):
+        return _queue_solve_streams(selected, splits, track, frame_idx)
     if any(N == 0 or M == 0 for N, M in splits):  # an empty frame: nothing to link, answered on the host
-        host = [scores_for_solver(d.unsqueeze(0), l, n.unsqueeze(0), e.unsqueeze(0), 0) for d, l, n, e in selected]
-        done = [(sc, associate(sc[0], sc[1], sc[2], sc[3], split)) for sc, split in zip(host, splits)]
+        done = _host_pairs(selected, splits)
         blocks = None
         if track is not None:
             # the IDs still come from the kernel, so that the state stays on the device: the assignments are uploaded
@@ -149,6 +179,43 @@ def queue_solve(selected, splits, track=None, frame_idx=None):
     buf = torch.cat([det, new, end, link])
     out, _ = torch.ops.mmmot.associate(buf[0:S], buf[S:2 * S], buf[2 * S:3 * S], buf[3 * S:], pairs_table(splits)[0])
     return _hand_off([buf, out], out, splits, S, K, track, frame_idx, True)
+
+
+def _host_pairs(selected, splits):
+    """pairs with an empty frame: their scores to the host and the assignment ``associate`` gives there"""
+    host = [scores_for_solver(d.unsqueeze(0), l, n.unsqueeze(0), e.unsqueeze(0), 0) for d, l, n, e in selected]
+    return [(sc, associate(sc[0], sc[1], sc[2], sc[3], split)) for sc, split in zip(host, splits)]
+
+
+def _queue_solve_streams(selected, splits, track, frame_idx):
+    """``queue_solve`` over the pairs of several sequences (``track`` = (TrackStates or None, stream_of)): the pairs
+    with two non-empty frames in ONE solver launch, the others on the host; the IDs of all of them from ONE multi-state
+    launch over [solver output | the uploaded assignments of the host pairs]"""
+    states, stream_of = track
+    if len(stream_of) != len(splits):
+        raise ValueError('queue_solve: %d stream names for %d pairs' % (len(stream_of), len(splits)))
+    full = [p for p, (N, M) in enumerate(splits) if N and M]
+    host = [p for p, (N, M) in enumerate(splits) if not (N and M)]
+    parts, out, S, K = [], None, 0, 0
+    if full:
+        cat = lambda k: torch.cat([(selected[p][k][0] if k == 1 else selected[p][k]).reshape(-1) for p in full])
+        det, new, end, link = cat(0), cat(2), cat(3), cat(1)
+        S, K = det.numel(), link.numel()
+        buf = torch.cat([det, new, end, link])
+        out, _ = torch.ops.mmmot.associate(buf[0:S], buf[S:2 * S], buf[2 * S:3 * S], buf[3 * S:],
+                                           pairs_table([splits[p] for p in full])[0])
+        parts = [buf, out]
+    done = None
+    if host:
+        done = [None] * len(splits)
+        for p, d in zip(host, _host_pairs([selected[p] for p in host], [splits[p] for p in host])):
+            done[p] = d
+        if states is not None:
+            up = torch.cat([t.reshape(-1).to(torch.float32) for p in host for a in (done[p][1],)
+                            for t in (a[0], a[2], a[3], a[1][0])]).to(states.buf.device)
+            out = up if out is None else torch.cat([out, up])
+    return _hand_off(parts, out, splits, S, K, None if states is None else (states, stream_of), frame_idx, True, done,
+                     block_order=full + host)
 
 
 def queue_solve_chains(selected, splits, track=None, frame_idx=None):

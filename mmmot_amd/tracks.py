@@ -27,6 +27,10 @@ behaviour of the reference is kept: a window whose frame 0 continues the stored 
 is not stored (``stored`` = 0) - only ``last_id`` moves, and its frames are not part of the tracks.  The pair forms are
 the two-frame readings of the window forms: ``split_ids`` of ``split_chain_ids``, ``merge_tracks`` of
 ``merge_chain_tracks`` (a pair has no ``stored`` word and is always written).
+
+Many sequences: ``TrackStates(S)`` is a table of S states, ``queue_ids_multi`` / ``queue_chain_ids_multi`` number the
+pairs / windows of several sequences in ONE launch (one workgroup per sequence, ``mmmot_track_ids_multi``), each group
+named by ``stream_of``, and ``split_ids_multi`` reads the buffer back per group and names the sequence in its error.
 """
 import numpy as np
 import torch
@@ -205,6 +209,131 @@ def track_chain_ids(state, assign_det, assign_links, assign_new, assign_end, det
                        for t in (assign_det, assign_new, assign_end, *assign_links)])
     ids, start, _, _ = assign_chain_ids(state, block.to(state.buf.device), [split], [frame_idx])[0]
     return [torch.from_numpy(i) for i in ids[start:]], start
+
+
+# ---- many sequences in one launch (mmmot_track_ids_multi / mmmot_track_chain_ids_multi) -----------------------------
+class TrackStates:
+    """The ID states of S sequences as ONE device table int32 [S, TRACK_STATE_INTS]; ``states[s]`` is the view of row s,
+    usable wherever a ``TrackState.buf`` is (the single-state ops included)."""
+
+    def __init__(self, S, device='cuda'):
+        if int(S) < 1:
+            raise ValueError('TrackStates: S >= 1 sequences, got %s' % (S,))
+        init = torch.full((int(S), TRACK_STATE_INTS), -1, dtype=torch.int32)
+        init[:, 0] = init[:, 2] = init[:, 3] = 0
+        self._init = init.to(device)
+        self.buf = self._init.clone()
+
+    def __len__(self):
+        return int(self.buf.shape[0])
+
+    def __getitem__(self, s):
+        return self.buf[int(s)]
+
+    def _rows(self, streams):
+        return torch.as_tensor(sorted(int(s) for s in streams), dtype=torch.long, device=self.buf.device)
+
+    def reset(self, streams=None):
+        """start new sequences: all of them, or the listed ones; queued on the current stream"""
+        if streams is None:
+            self.buf.copy_(self._init)
+        elif len(streams):
+            r = self._rows(streams)
+            self.buf[r] = self._init[r]
+
+    def snapshot(self):
+        return self.buf.clone()
+
+    def restore(self, snap, streams=None):
+        """the whole table from ``snapshot()``, or the listed sequences' rows of it"""
+        if streams is None:
+            self.buf.copy_(snap)
+        elif len(streams):
+            r = self._rows(streams)
+            self.buf[r] = snap[r]
+
+    def read(self, s):
+        """host view of sequence s (waits for the stream), as ``TrackState.read``"""
+        h = self.buf[int(s)].cpu().numpy()
+        n = int(h[3])
+        return {'last_id': int(h[0]), 'frame': None if h[1] < 0 else int(h[1]), 'flags': int(h[2]),
+                'ids': h[TRACK_STATE_HEAD:TRACK_STATE_HEAD + n].astype(np.int64)}
+
+
+def stream_major(stream_of, S):
+    """The host tables of a multi-state launch: (order, seq_start).  ``order``: int64 [B], the groups' indices sorted by
+    stream, groups of one stream in the order given (stable); ``seq_start``: int32 [S + 1] with the groups of stream s
+    at [seq_start[s], seq_start[s+1]) of that order - an empty range for a stream without groups."""
+    so = np.asarray(stream_of, dtype=np.int64).reshape(-1)
+    if so.size and (so.min() < 0 or so.max() >= int(S)):
+        raise ValueError('stream_of names a stream outside [0, %d)' % int(S))
+    order = np.argsort(so, kind='stable')
+    seq_start = np.zeros(int(S) + 1, np.int32)
+    np.cumsum(np.bincount(so, minlength=int(S)), out=seq_start[1:])
+    return order, seq_start
+
+
+def _reorder_blocks(blocks, sizes, order):
+    """the solver blocks (``sizes`` fp32 each, one after the other) in the order ``order``: one gather on the device"""
+    if np.array_equal(order, np.arange(len(order))):
+        return blocks
+    off = np.cumsum(sizes) - sizes
+    idx = np.concatenate([np.arange(off[g], off[g] + sizes[g]) for g in order] + [np.zeros(0, np.int64)])
+    return blocks[torch.from_numpy(idx.astype(np.int64)).to(blocks.device, non_blocking=True)]
+
+
+def _queue_multi(op, table_of, frames_of, states, blocks, splits, frame_idx, stream_of, max_n):
+    if len(stream_of) != len(splits):
+        raise ValueError('%s: %d stream names for %d groups' % (op, len(stream_of), len(splits)))
+    order, seq_start = stream_major(stream_of, len(states))
+    splits = [splits[g] for g in order]
+    sizes = np.asarray([3 * sum(s) + sum(a * b for a, b in zip(s[:-1], s[1:])) for s in splits], dtype=np.int64)
+    inv = np.argsort(order)  # the blocks lie in the order given: block g goes to place inv[g]
+    blocks = _reorder_blocks(blocks, sizes[inv], order)
+    ids = getattr(torch.ops.mmmot, op)(blocks, table_of(splits)[0], frames_of([frame_idx[g] for g in order], splits),
+                                       torch.from_numpy(seq_start), states.buf, int(max_n))
+    return torch.cat([ids, states.buf[:, 2]])
+
+
+def queue_ids_multi(states, blocks, splits, frame_idx, stream_of, max_nm=0):
+    """Queue ONE ID launch for the pairs of several sequences; nothing waits.  ``states``: a TrackStates; ``blocks``,
+    ``splits``, ``frame_idx`` as ``queue_ids`` takes them, in any order of the groups; ``stream_of[g]`` names the
+    sequence of group g, whose groups must follow each other in the order of that sequence.  The groups are reordered
+    to stream-major on the host (``stream_major``; the blocks follow in one device gather when the order changes).
+    Returns the device int32 buffer [per pair in STREAM-MAJOR order: ids N | ids M | frame_start | last_id] with the
+    error flags of all S sequences appended; ``split_ids_multi`` reads it back in the order given."""
+    splits = [(int(N), int(M)) for N, M in splits]
+    return _queue_multi('track_ids_multi', pairs_table, lambda f, s: frame_table(f, len(s)), states, blocks, splits,
+                        frame_idx, stream_of, max_nm)
+
+
+def queue_chain_ids_multi(states, blocks, splits, frame_idx, stream_of, max_n=0):
+    """``queue_ids_multi`` for WINDOWS of 2 .. 8 frames (per window ids L | frame_start | last_id | stored)"""
+    splits = [[int(n) for n in s] for s in splits]
+    return _queue_multi('track_chain_ids_multi', chains_table, chain_frame_table, states, blocks, splits, frame_idx,
+                        stream_of, max_n)
+
+
+def split_ids_multi(flat, splits, stream_of, tail=2):
+    """host int32 buffer of ``queue_ids_multi`` (``tail`` = 3: of ``queue_chain_ids_multi``) -> per group, in the order
+    of ``splits`` / ``stream_of``, what ``split_ids`` (``split_chain_ids``) gives; raises ``TrackingError`` naming the
+    sequence whose error flags are set"""
+    flat = np.asarray(flat)
+    splits = [[int(n) for n in s] for s in splits]
+    n_ids = sum(sum(s) + tail for s in splits)
+    S = flat.size - n_ids
+    order, _ = stream_major(stream_of, S)
+    for s in range(S):
+        try:
+            check_flags(int(flat[n_ids + s]))
+        except TrackingError as e:
+            raise TrackingError('stream %d: %s' % (s, e)) from None
+    body = np.concatenate([flat[:n_ids], np.zeros(1, flat.dtype)])  # the flag word split_chain_ids checks: clean here
+    major = split_chain_ids(body, [splits[g] for g in order], tail=tail)
+    res = [None] * len(splits)
+    for g, r in zip(order, major):
+        res[g] = (r[0][0], r[0][1], r[1], r[2]) if tail == 2 else r
+    return res
 
 
 def merge_chain_tracks(tracks, frames, ids, frame_start, stored, on_tracks=None):

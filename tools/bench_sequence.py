@@ -13,9 +13,14 @@ of a synthetic drive (mmmot_amd.synth.ego_poses), so each frame's points are ali
 association and track IDs): frames/s of ``run`` and ``run_offline`` for the pair path (window 2) and for every T given,
 each repeat running all of them in turn; the two orders of a window must give bitwise equal scores and equal tracks.
 Writes <out>/bench_sequence_windows.json.
+--streams S [S ..] measures the lockstep order (LockstepPipeline, DESIGN section 12 "Many sequences"): aggregate frames/s
+over S sequences of the workload's shape (different seeds) stepped together, beside SequencePipeline(reuse_appearance=True,
+associate=True, track=True) on one of them in the same run; sequence 0 of every lockstep run must equal that run bit for
+bit.  Writes <out>/bench_sequence_streams.json.
 
     python tools/bench_sequence.py --out <dir> [--repeats 3] [--trunk f16x3] [-K 16] [-B 8] [--associate | --track] [--ego]
     python tools/bench_sequence.py --out <dir> --window 3 5 [--repeats 3] [-K 16] [-B 8] [-W 4] [--ego]
+    python tools/bench_sequence.py --out <dir> --streams 1 2 4 8 16 [--frames 40] [--repeats 3]
 """
 import argparse
 import json
@@ -94,6 +99,51 @@ def bench_windows(args, model, dev):
     print(json.dumps(rec))
 
 
+def bench_streams(args, model, dev):
+    """aggregate frames/s of LockstepPipeline over S copies of the workload (different seeds) beside the single-sequence
+    online order on one of them, association and track IDs on, all in one process"""
+    from mmmot_amd.pipeline import LockstepPipeline
+    n, counts = args.frames, sorted(set(args.streams))
+    if counts[0] < 1:
+        raise SystemExit('--streams takes counts >= 1')
+    streams = [sequence_feeds(n, seed=s) for s in range(counts[-1])]
+    kw = dict(associate=True, track=True)
+    modes = {'single': lambda: SequencePipeline(model, 224, reuse_appearance=True, **kw).run(streams[0])}
+    for S in counts:
+        modes['lockstep%d' % S] = lambda S=S: LockstepPipeline(model, 224, **kw).run(streams[:S])
+    frames = dict({'lockstep%d' % S: S * (n - 1) for S in counts}, single=n - 1)
+    want = flat(modes['single']())   # untimed, and the check: sequence 0 of every lockstep run equals the single run
+    for name in list(modes)[1:]:
+        got = flat(modes[name]()[0])
+        if len(got) != len(want) or not all(torch.equal(x, y) for x, y in zip(got, want)):
+            raise SystemExit('%s: sequence 0 differs from the single-sequence run' % name)
+    fps = {k: [] for k in modes}
+    for _ in range(args.repeats):
+        for name, run in modes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run()
+            torch.cuda.synchronize()
+            fps[name].append(frames[name] / (time.perf_counter() - t0))
+    med = {k: float(np.median(v)) for k, v in fps.items()}
+    rec = {
+        'frames_per_s': {k: round(v, 1) for k, v in med.items()},
+        'frames_per_s_runs': {k: [round(x, 1) for x in v] for k, v in fps.items()},
+        'spread': {k: round((max(v) - min(v)) / med[k], 4) for k, v in fps.items()},
+        'vs_single': {k: round(med[k] / med['single'], 3) for k in modes},
+        'sequence0_bitwise_equal': True, 'trunk': model.engine().trunk, 'range_events': len(model.engine().range_events),
+        'frames': n, 'repeats': args.repeats, 'streams': counts, 'device': torch.cuda.get_device_name(dev),
+        'workload': 'S sequences of %d synthetic KITTI-shaped frames each (make_frame(7000 + 100000 s + t, 120000, n_det), '
+                    '10-12 detections), 224x224 8-bit crops, Fusion A, overlapped stage A, association and track IDs on; '
+                    'single = SequencePipeline(reuse_appearance=True) on sequence 0; frames/s = S (frames - 1) pairs per wall '
+                    'second, median of the repeats' % n,
+    }
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_sequence_streams.json'), 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', required=True)
@@ -108,6 +158,8 @@ def main():
     ap.add_argument('--window', type=int, nargs='+', default=None,
                     help='measure the windowed path for these window lengths (3 .. 8) beside the pair path')
     ap.add_argument('-W', '--windows-per-forward', type=int, default=4)
+    ap.add_argument('--streams', type=int, nargs='+', default=None,
+                    help='measure LockstepPipeline over these numbers of sequences (e.g. 1 2 4 8 16) beside one sequence alone')
     args = ap.parse_args()
     assoc = args.associate or args.track
     kw = dict(associate=assoc, track=True) if args.track else dict(associate=assoc)
@@ -120,6 +172,8 @@ def main():
     model.set_trunk(args.trunk)
     if args.window:
         return bench_windows(args, model, dev)
+    if args.streams:
+        return bench_streams(args, model, dev)
     n = args.frames
     ndet, feeds = detections(n), sequence_feeds(n, ego=0 if args.ego else None)
     K, B = args.frames_per_encode, args.pairs_per_forward

@@ -17,15 +17,16 @@ def detections(frames):
     return np.random.default_rng(5).integers(10, 13, frames)
 
 
-def sequence_feeds(frames, ego=None):
+def sequence_feeds(frames, ego=None, seed=0):
     """``frames`` FrameFeeds (pinned host copies), generated on up to 16 threads.  ``ego=seed``: the same frames seen from
     a moving camera - every feed carries a pose of mmmot_amd.synth.ego_poses(frames, seed) and a KITTI-like
-    Tr_imu_to_velo, so the pipeline aligns each frame's points to the frame before it."""
+    Tr_imu_to_velo, so the pipeline aligns each frame's points to the frame before it.  ``seed``: another sequence of
+    the same shape (0: the one every tool has measured)."""
     from mmmot_amd.pipeline import FrameFeed
     from mmmot_amd.synth import make_frame
     ndet = detections(frames)
     with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as pool:
-        made = list(pool.map(lambda t: make_frame(7000 + t, 120000, int(ndet[t])), range(frames)))
+        made = list(pool.map(lambda t: make_frame(7000 + 100000 * int(seed) + t, 120000, int(ndet[t])), range(frames)))
     if ego is None:
         return [FrameFeed(*f) for f in made]
     from mmmot_amd.synth import KITTI_IMU2VELO, ego_poses
