@@ -880,6 +880,36 @@ int mmmot_clear_mot(const double* boxes, int nG, int nT, int nD, const int* fram
                     double min_overlap, double min_height, double max_truncation, double max_occlusion,
                     double* frame_d, int* frame_i, int* gt_out, int* traj_i, double* seq_d, int* seq_i, void* stream);
 
+/* HOTA and IDF1 evaluation of tracked sequences (csrc/hota.hip, DESIGN.md section 13 "HOTA / IDF1"; the rules are
+ * restated in tests/hota_ref.py), additive in ABI 10.  A fixed number of launches whatever NF and S: one clear of the
+ * work tables, the preparation of every frame (one wave per frame), pass 1 (one workgroup per sequence walks its frames
+ * in order), pass 2 (one wave per frame), the per-sequence sums, the IDF1 matching (one wave per sequence), the totals.
+ *   boxes, frames: as in mmmot_clear_mot (ground truth = every non-DontCare row); frame_seq: int32 [NF] = the frame's
+ *   sequence;
+ *   g_attr: int32 [nG][4] = truncation, occlusion, class code (0 main, 1 neighbouring), dense ID in [0, G_s) (not read
+ *   for the neighbouring class);  t_id: int32 [nT] = dense ID in [0, T_s).  IDs are unique within a frame;
+ *   seq_tab: int32 [S + 1][6] = first frame, G_s, T_s, first cell, first gt ID slot, first tracker ID slot (row S: NF, 0,
+ *   0, cells, sumG, sumT), G_s, T_s <= 2048, G_s T_s <= 2^18;  cells = sum G_s T_s, sumG = sum G_s, sumT = sum T_s;
+ *   max_boxes / max_dontcare: the caller's largest frame (per side / DontCare areas), at most 128 / 64;
+ *   prepare: 1 = the KITTI preparation (min_height, max_truncation, max_occlusion), 0 = keep every main-class ground
+ *   truth row and every tracker row;
+ *   work: 8-byte aligned, work_bytes >= 8 cells + 4 (20 cells + sumG + sumT + nG + nT); cleared by the call.
+ * Outputs, every element written: frame_d fp64 [NF][21] = value of the preparation assignment, value of the pass-2
+ * assignment, LocSum of the 19 alpha;  frame_i int32 [NF][21] = TP of the 19 alpha, kept ground truth, kept tracker
+ * boxes;  seq_d fp64 [S + 1][76] = LocSum[19], sum mc A [19], sum mc mc / max(1, gt_count) [19], sum mc mc / max(1,
+ * tr_count) [19] - in row S the last three are the TP-weighted sums  sum_s (x_s / max(1, TP_s)) TP_s;  seq_i int32
+ * [S + 1][24] = TP[19], kept ground truth, kept tracker boxes, IDTP, status (0, or -1 when a frame or the sequence lay
+ * outside the limits: such a frame gets -1 / NaN rows and nothing of it is read), pad; row S holds the totals.  No
+ * floating-point atomics: two calls on the same input return the same bits, and a sequence's values do not depend on
+ * what else the call holds.  Returns MMMOT_EINVAL before any launch on a missing or misaligned pointer, a negative
+ * count, S < 1, max_boxes > 128, max_dontcare > 64, cells > 2^18 S, sumG or sumT > 2048 S, prepare outside {0, 1} or a
+ * work block that is too small. */
+int mmmot_hota(const double* boxes, int nG, int nT, int nD, const int* frames, int NF, const int* frame_seq,
+               const int* g_attr, const int* t_id, const int* seq_tab, int S, int cells, int sumG, int sumT,
+               int max_boxes, int max_dontcare, double min_height, double max_truncation, double max_occlusion,
+               int prepare, void* work, long long work_bytes, double* frame_d, int* frame_i, double* seq_d, int* seq_i,
+               void* stream);
+
 /* Training targets of chains (reference tracking_model.py:294-351, TrackingModule.generate_gt, restated literally;
  * csrc/labels.hip), additive in ABI 10.  One workgroup per chain, ids and classes staged in LDS, every output element
  * written once by a plain store: results are deterministic and do not depend on the chain's place in the batch.

@@ -20,6 +20,14 @@ non-DontCare rows with track ID -1 are dropped; tracker frames past the ground t
 tracker's trajectories) but not evaluated; FAR and MODP divide by the seqmap's frame counts.  Different: a tracker
 file that repeats a (frame, ID) raises ``ValueError`` (there: ``return False``), and so does a frame with more than 128
 boxes on a side or 64 DontCare areas.  Equal-cost matchings are broken by column index, not munkres's way.
+
+HOTA and IDF1 (``hota_sequences`` / ``evaluate_hota`` -> ``Hota``; csrc/hota.hip) are built from the rules written down
+in DESIGN.md section 13 and restated in tests/hota_ref.py, on the same packed tables:
+
+    h = hota_sequences(gt, tr)                         # h.HOTA, h.AssA, h.IDF1, h.summary()
+    h = evaluate_hota(step, result_path, part, gt_path='./data/tracking', cls='car')
+
+No agreement with any published implementation of these metrics is claimed.
 """
 import math
 import os
@@ -28,6 +36,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .torch_ops import CLEAR_MOT_MAX_BOXES, CLEAR_MOT_MAX_DONTCARE, CLEAR_MOT_SEQ_INTS, clear_mot_layout
+from .torch_ops import (HOTA_ALPHAS, HOTA_FRAME_D, HOTA_FRAME_I, HOTA_MAX_CELLS, HOTA_MAX_IDS, HOTA_SEQ_D, HOTA_SEQ_I,
+                        hota_layout)
 
 TRAIN_SEQ_ID = ['0003', '0001', '0013', '0009', '0004', '0020', '0006', '0015', '0008', '0012']
 VALID_SEQ_ID = ['0005', '0007', '0017', '0011', '0002', '0014', '0000', '0010', '0016', '0019', '0018']
@@ -392,3 +402,211 @@ def evaluate(result_sha, root, part='all', gt_path='./data/tracking', cls=None, 
             f.write(m.stats_line() + '\n')
         last = m
     return False if last is None else last.summary()
+
+
+# ---- HOTA / IDF1 (csrc/hota.hip) -----------------------------------------------------------------------------------
+HOTA_ALPHA = 0.05 * np.arange(1, HOTA_ALPHAS + 1)  # alpha_a = 0.05 (a + 1)
+_PER_ALPHA = ('HOTA', 'DetA', 'AssA', 'DetRe', 'DetPr', 'AssRe', 'AssPr', 'LocA')
+
+
+@dataclass
+class Hota:
+    """HOTA and IDF1 of a set of sequences.  ``<name>_alpha``: the values at the 19 thresholds 0.05 .. 0.95; ``<name>``:
+    their mean.  TP / FN / FP: int64 [19].  seq_*: one entry per sequence."""
+    cls: str = 'car'
+    alphas: np.ndarray = None
+    TP: np.ndarray = None
+    FN: np.ndarray = None
+    FP: np.ndarray = None
+    LocSum: np.ndarray = None
+    HOTA_alpha: np.ndarray = None
+    DetA_alpha: np.ndarray = None
+    AssA_alpha: np.ndarray = None
+    DetRe_alpha: np.ndarray = None
+    DetPr_alpha: np.ndarray = None
+    AssRe_alpha: np.ndarray = None
+    AssPr_alpha: np.ndarray = None
+    LocA_alpha: np.ndarray = None
+    HOTA: float = 0.0
+    DetA: float = 0.0
+    AssA: float = 0.0
+    DetRe: float = 0.0
+    DetPr: float = 0.0
+    AssRe: float = 0.0
+    AssPr: float = 0.0
+    LocA: float = 0.0
+    IDTP: int = 0
+    IDFN: int = 0
+    IDFP: int = 0
+    IDF1: float = 0.0
+    IDR: float = 0.0
+    IDP: float = 0.0
+    n_gt: int = 0                                        # ground-truth boxes after the preparation
+    n_tr: int = 0                                        # tracker boxes after the preparation
+    seq_TP: list = field(default_factory=list)           # per sequence: int64 [19]
+    seq_FN: list = field(default_factory=list)
+    seq_FP: list = field(default_factory=list)
+    seq_IDTP: list = field(default_factory=list)
+    seq_IDFN: list = field(default_factory=list)
+    seq_IDFP: list = field(default_factory=list)
+    seq_n_gt: list = field(default_factory=list)
+    seq_n_tr: list = field(default_factory=list)
+    seq_AssA: list = field(default_factory=list)         # per sequence: float64 [19]
+    seq_LocSum: list = field(default_factory=list)
+    frame_values: np.ndarray = None   # debug, [frames, 2]: value of the preparation assignment, of the pass-2 assignment
+
+    def summary(self):
+        """(HOTA, DetA, AssA, DetRe, DetPr, AssRe, AssPr, LocA, IDF1, IDR, IDP, IDTP, IDFN, IDFP)"""
+        return (self.HOTA, self.DetA, self.AssA, self.DetRe, self.DetPr, self.AssRe, self.AssPr, self.LocA, self.IDF1,
+                self.IDR, self.IDP, self.IDTP, self.IDFN, self.IDFP)
+
+    def summary_line(self):
+        return '%.6f ' * 11 % self.summary()[:11] + '%d %d %d' % self.summary()[11:]
+
+
+def pack_hota(gt, tracker):
+    """Labels of the ground truth and the tracker -> the tables of mmmot_hota: ``pack``'s frame tables plus the dense
+    per-sequence IDs (ground truth: main class only) and the sequence table.  Raises ValueError on what the kernels do not
+    take - frames beyond CLEAR-MOT's limits, an ID twice in a frame, more than HOTA_MAX_IDS IDs on a side or more than
+    HOTA_MAX_CELLS (G * T) cells in a sequence - before anything reaches the device."""
+    p = pack(gt, tracker)
+    nG, nT, nD, NF, NTr, S = p['sizes']
+    foff, g_cnt, t_cnt = p['foff'], p['g_cnt'], p['t_cnt']
+    frame_seq = np.repeat(np.arange(S), np.diff(foff))
+    g_fr, t_fr = np.repeat(np.arange(NF), g_cnt), np.repeat(np.arange(NF), t_cnt)
+    g_tid = np.zeros(nG, np.int64)
+    g_tid[p['traj_obj']] = np.repeat(p['traj_key'][:, 1], p['traj_key'][:, 2]) if NTr else 0
+    t_tid = p['t_attr'][:, 0].astype(np.int64)
+    main = p['g_attr'][:, 2] == MAIN
+
+    def dense(fr, tid, use, what):
+        """dense per-sequence IDs of the rows ``use`` (-1 elsewhere) and the ID count of every sequence"""
+        out, n = np.full(len(tid), -1, np.int64), np.zeros(S, np.int64)
+        seq = frame_seq[fr] if len(fr) else np.zeros(0, np.int64)
+        for s in range(S):
+            m = use & (seq == s)
+            if len(np.unique(np.stack([fr[m], tid[m]], axis=1), axis=0)) != m.sum():
+                raise ValueError('hota: %s track ids are not unique within a frame of sequence %d' % (what, s))
+            ids, inv = np.unique(tid[m], return_inverse=True)
+            out[m], n[s] = inv.reshape(-1), len(ids)
+        return out, n
+
+    g_id, Gs = dense(g_fr, g_tid, main, 'ground-truth')
+    t_id, Ts = dense(t_fr, t_tid, np.ones(nT, bool), 'tracker')
+    if S and (max(Gs.max(), Ts.max()) > HOTA_MAX_IDS or (Gs * Ts).max() > HOTA_MAX_CELLS):
+        raise ValueError('hota: a sequence holds more than %d track ids on a side or more than %d (ground truth x '
+                         'tracker) id pairs' % (HOTA_MAX_IDS, HOTA_MAX_CELLS))
+    cum = lambda v: np.concatenate([[0], np.cumsum(v)]).astype(np.int64)
+    cells, goff, toff = cum(Gs * Ts), cum(Gs), cum(Ts)
+    seq_tab = np.stack([foff, np.r_[Gs, 0], np.r_[Ts, 0], cells, goff, toff], axis=1)
+    d_cnt = p['frames'][:, 5] if NF else np.zeros(0, np.int64)
+    big = lambda v: int(v.max()) if len(v) else 0
+    return {
+        'sizes': [nG, nT, nD, NF, S, int(cells[-1]), int(goff[-1]), int(toff[-1]), max(big(g_cnt), big(t_cnt)), big(d_cnt)],
+        'boxes': p['boxes'], 'frames': p['frames'], 'frame_seq': frame_seq,
+        'g_attr': np.concatenate([p['g_attr'], g_id[:, None]], axis=1), 't_id': t_id, 'seq_tab': seq_tab,
+        'foff': foff, 'Gs': Gs, 'Ts': Ts, 'cls': p['cls'],
+    }
+
+
+def _hota_ratios(h, TP, FN, FP, LocSum, AssA, AssRe, AssPr):
+    """steps 3 and 4: the ratios of every alpha from the counts, LocSum and the association values, and their means"""
+    tp = TP.astype(np.float64)
+    h.TP, h.FN, h.FP, h.LocSum = TP, FN, FP, LocSum
+    h.AssA_alpha, h.AssRe_alpha, h.AssPr_alpha = AssA, AssRe, AssPr
+    h.LocA_alpha = np.where(TP == 0, 1.0, LocSum / np.maximum(1e-10, tp))
+    h.DetRe_alpha = tp / np.maximum(1, TP + FN)
+    h.DetPr_alpha = tp / np.maximum(1, TP + FP)
+    h.DetA_alpha = tp / np.maximum(1, TP + FN + FP)
+    h.HOTA_alpha = np.sqrt(h.DetA_alpha * h.AssA_alpha)
+    for k in _PER_ALPHA:
+        setattr(h, k, float(np.mean(getattr(h, k + '_alpha'))))
+
+
+def finish_hota(p, out):
+    """the packed tables and the device's output sections (numpy) -> Hota"""
+    NF, S = p['sizes'][3], p['sizes'][4]
+    A = HOTA_ALPHAS
+    seq_i = out['seq_i'].reshape(S + 1, HOTA_SEQ_I).astype(np.int64)
+    seq_d = out['seq_d'].reshape(S + 1, HOTA_SEQ_D)
+    if seq_i[:, A + 3].min() < 0:
+        raise RuntimeError('mmmot_hota: a frame or a sequence outside the launch limits reached the kernel')
+    h = Hota(cls=p['cls'], alphas=HOTA_ALPHA.copy())
+    for s in range(S):
+        tp, ng, nt, idtp = seq_i[s, :A], int(seq_i[s, A]), int(seq_i[s, A + 1]), int(seq_i[s, A + 2])
+        h.seq_TP.append(tp.copy())
+        h.seq_FN.append(ng - tp)
+        h.seq_FP.append(nt - tp)
+        h.seq_n_gt.append(ng)
+        h.seq_n_tr.append(nt)
+        h.seq_IDTP.append(idtp)
+        h.seq_IDFN.append(ng - idtp)
+        h.seq_IDFP.append(nt - idtp)
+        h.seq_AssA.append(seq_d[s, A:2 * A] / np.maximum(1, tp))
+        h.seq_LocSum.append(seq_d[s, :A].copy())
+    TP, h.n_gt, h.n_tr, h.IDTP = seq_i[S, :A].copy(), int(seq_i[S, A]), int(seq_i[S, A + 1]), int(seq_i[S, A + 2])
+    den = np.maximum(1, TP)
+    _hota_ratios(h, TP, h.n_gt - TP, h.n_tr - TP, seq_d[S, :A].copy(), seq_d[S, A:2 * A] / den,
+                 seq_d[S, 2 * A:3 * A] / den, seq_d[S, 3 * A:4 * A] / den)
+    h.IDFN, h.IDFP = h.n_gt - h.IDTP, h.n_tr - h.IDTP
+    h.IDF1 = h.IDTP / max(1.0, h.IDTP + 0.5 * h.IDFP + 0.5 * h.IDFN)
+    h.IDR = h.IDTP / max(1.0, float(h.IDTP + h.IDFN))
+    h.IDP = h.IDTP / max(1.0, float(h.IDTP + h.IDFP))
+    h.frame_values = out['frame_d'].reshape(NF, HOTA_FRAME_D)[:, :2].copy()
+    return h
+
+
+def hota_sequences(gt, tracker, cls='car', prepare='kitti', max_truncation=0, min_height=25, max_occlusion=2,
+                   device='cuda'):
+    """HOTA and IDF1 of tracker Labels against ground-truth Labels (one Labels of S sequences, or a list with one per
+    sequence) on the device: one upload, the launches of mmmot_hota, one read-back.  ``prepare``: 'kitti' (the
+    preparation of DESIGN.md section 13 with the knobs of ``evaluate_sequences``) or None (every main-class ground-truth
+    row and every tracker row)."""
+    if prepare not in ('kitti', None):
+        raise ValueError("hota: prepare must be 'kitti' or None, got %r" % (prepare,))
+    p = pack_hota(gt, tracker)
+    p['cls'] = cls
+    return finish_hota(p, run_hota(p, [float(min_height), float(max_truncation), float(max_occlusion),
+                                       1. if prepare == 'kitti' else 0.], device))
+
+
+def run_hota(p, params, device='cuda'):
+    """the tables of ``pack_hota`` through torch.ops.mmmot.hota -> the output sections as numpy arrays"""
+    import torch
+    inp, outl, n_in, n_out, _ = hota_layout(p['sizes'])
+    host = torch.empty(n_in, dtype=torch.int32, pin_memory=True)
+    h = host.numpy()
+    for name, (o, n) in inp.items():
+        if name == 'boxes':
+            h[o:o + n].view(np.float64)[:] = p['boxes'].reshape(-1)
+        else:
+            h[o:o + n] = np.asarray(p[name]).reshape(-1)
+    dev = host.to(device, non_blocking=True)
+    r = torch.ops.mmmot.hota(dev, p['sizes'], params).cpu().numpy()
+    return {name: (r[o:o + n].view(np.float64) if name.endswith('_d') else r[o:o + n]) for name, (o, n) in outl.items()}
+
+
+def evaluate_hota(result_sha, root, part='all', gt_path='./data/tracking', cls=None, device='cuda'):
+    """The file loading of ``evaluate`` with ``hota_sequences`` behind it: evaluates ``root/result_sha/part/<sequence>.txt``
+    against ``gt_path/label_02`` for car, then pedestrian (``cls``: one class only) and returns the Hota record of the
+    last class evaluated, or False when the tracker holds neither class.  No file is written."""
+    names, n_frames = sequences_of(part, gt_path)
+    if not names:
+        raise ValueError('evaluate_hota: the seqmap under %s holds no sequence of part %r' % (gt_path, part))
+    t_path = os.path.join(root, str(result_sha), part)
+    last = None
+    for c in (('car', 'pedestrian') if cls is None else (cls,)):
+        try:
+            tracker = concat([load_kitti(os.path.join(t_path, '%s.txt' % s), c, n, False)
+                              for s, n in zip(names, n_frames)])
+        except IOError:
+            continue
+        if tracker.n_traj.sum() == 0:
+            continue
+        try:
+            gt = concat([load_kitti(os.path.join(gt_path, 'label_02', '%s.txt' % s), c, n, True)
+                         for s, n in zip(names, n_frames)])
+        except IOError:
+            raise ValueError('Ground truth not found.')
+        last = hota_sequences(gt, tracker, cls=c, device=device)
+    return False if last is None else last

@@ -448,6 +448,19 @@ class HipOps:
                                       _iptr(seq_i), self._stream())
         _lib.check(st, 'mmmot_clear_mot')
 
+    def hota(self, boxes, nG, nT, nD, frames, NF, frame_seq, g_attr, t_id, seq_tab, S, cells, sumG, sumT, max_boxes,
+             max_dontcare, params, prepare, work, frame_d, frame_i, seq_d, seq_i):
+        """HOTA / IDF1 evaluation of S sequences in a fixed number of launches; see mmmot_hota.  boxes / frame_d /
+        seq_d: fp64 device tensors, work: an int32 device tensor (8-byte aligned), the rest int32; params: (min_height,
+        max_truncation, max_occlusion)."""
+        d = torch.float64
+        st = self.lib.mmmot_hota(_ptr(boxes, d), int(nG), int(nT), int(nD), _iptr(frames), int(NF), _iptr(frame_seq),
+                                 _iptr(g_attr), _iptr(t_id), _iptr(seq_tab), int(S), int(cells), int(sumG), int(sumT),
+                                 int(max_boxes), int(max_dontcare), float(params[0]), float(params[1]),
+                                 float(params[2]), int(prepare), _iptr(work), 4 * int(work.numel()), _ptr(frame_d, d),
+                                 _iptr(frame_i), _ptr(seq_d, d), _iptr(seq_i), self._stream())
+        _lib.check(st, 'mmmot_hota')
+
     def generate_gt(self, ids, cls, chains, B, max_n, max_L, out, out_off):
         """Training targets of B chains in one launch; see mmmot_generate_gt.  ids / cls / chains / out_off: int32 device
         tensors; out: fp32."""

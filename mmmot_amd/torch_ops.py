@@ -551,6 +551,81 @@ _LIB.impl('clear_mot', _clear_mot, 'CUDA')
 _LIB.impl('clear_mot', _clear_mot_meta, 'Meta')
 
 
+# ---- HOTA / IDF1 evaluation (mmmot_amd/evaluate.py; csrc/hota.hip) -------------------------------------------------
+#   mmmot::hota(Tensor packed, int[] sizes, float[] params) -> Tensor
+#       Evaluates S sequences (mmmot_hota: a fixed number of launches).  packed: ONE device int32 block holding the
+#       call's tables in the order of hota_layout()[0] (the fp64 boxes first, as their bit patterns); sizes = [nG, nT,
+#       nD, NF, S, cells, sumG, sumT, max_boxes, max_dontcare]; params = [min_height, max_truncation, max_occlusion,
+#       prepare (1 = KITTI preparation, 0 = none)].  Returns ONE int32 block in the order of hota_layout()[1] (the fp64
+#       sections first).  The work tables (pot, mc, pm, counts, keep flags) are allocated here and never read back.  The
+#       frame and table limits are the caller's to check on the host (evaluate.pack_hota): beyond them this raises.
+HOTA_ALPHAS = 19
+HOTA_FRAME_D, HOTA_FRAME_I, HOTA_SEQ_D, HOTA_SEQ_I, HOTA_SEQ_TAB = 21, 21, 76, 24, 6
+HOTA_MAX_CELLS, HOTA_MAX_IDS = 1 << 18, 2048  # per sequence: G * T, and G or T
+
+
+def hota_layout(sizes):
+    """({input section: (offset, int32 count)}, {output section: (offset, int32 count)}, input ints, output ints, work
+    ints) of a call with sizes = [nG, nT, nD, NF, S, cells, sumG, sumT, max_boxes, max_dontcare]; fp64 sections come
+    first in every block (8-byte aligned).  Raises ValueError beyond the limits of mmmot_hota."""
+    if len(sizes) != 10 or min(sizes) < 0 or sizes[4] < 1:
+        raise ValueError('mmmot::hota: sizes must be [nG, nT, nD, NF, S, cells, sumG, sumT, max_boxes, max_dontcare] '
+                         'with S >= 1, got %s' % (list(sizes),))
+    nG, nT, nD, NF, S, cells, sumG, sumT, max_boxes, max_dontcare = (int(v) for v in sizes)
+    if max_boxes > CLEAR_MOT_MAX_BOXES or max_dontcare > CLEAR_MOT_MAX_DONTCARE:
+        raise ValueError('mmmot::hota: a frame holds more than %d boxes on a side or more than %d DontCare areas'
+                         % (CLEAR_MOT_MAX_BOXES, CLEAR_MOT_MAX_DONTCARE))
+    if cells > S * HOTA_MAX_CELLS or max(sumG, sumT) > S * HOTA_MAX_IDS:
+        raise ValueError('mmmot::hota: the ID tables exceed %d cells or %d IDs per sequence' % (HOTA_MAX_CELLS, HOTA_MAX_IDS))
+
+    def lay(parts):
+        out, o = {}, 0
+        for name, n in parts:
+            out[name] = (o, n)
+            o += n
+        if o >= 2 ** 31:
+            raise ValueError('mmmot::hota: block exceeds 32-bit offsets')
+        return out, o
+
+    inp, n_in = lay([('boxes', 8 * (nG + nT + nD)), ('frames', 6 * NF), ('frame_seq', NF), ('g_attr', 4 * nG),
+                     ('t_id', nT), ('seq_tab', HOTA_SEQ_TAB * (S + 1))])
+    out, n_out = lay([('frame_d', 2 * HOTA_FRAME_D * NF), ('seq_d', 2 * HOTA_SEQ_D * (S + 1)),
+                      ('frame_i', HOTA_FRAME_I * NF), ('seq_i', HOTA_SEQ_I * (S + 1))])
+    _, n_work = lay([('work', max(2, 2 * cells + (HOTA_ALPHAS + 1) * cells + sumG + sumT + nG + nT))])
+    return inp, out, n_in, n_out, n_work
+
+
+def _hota(packed, sizes, params):
+    inp, outl, n_in, n_out, n_work = hota_layout(sizes)
+    if packed.dtype != torch.int32 or packed.dim() != 1 or packed.numel() != n_in or not packed.is_contiguous():
+        raise ValueError('mmmot::hota: packed must be a contiguous int32 [%d] block for sizes %s' % (n_in, list(sizes)))
+    if len(params) != 4 or params[3] not in (0., 1.):
+        raise ValueError('mmmot::hota: params = [min_height, max_truncation, max_occlusion, prepare (0 or 1)]')
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    nG, nT, nD, NF, S, cells, sumG, sumT, max_boxes, max_dontcare = (int(v) for v in sizes)
+    res = torch.empty(n_out, dtype=torch.int32, device=packed.device)
+    work = torch.empty(n_work, dtype=torch.int32, device=packed.device)
+    sec = lambda buf, lay, name: buf[lay[name][0]:lay[name][0] + lay[name][1]]
+    i = lambda name: sec(packed, inp, name)
+    o = lambda name: sec(res, outl, name)
+    _ASSOC_OPS[0].hota(i('boxes').view(torch.float64), nG, nT, nD, i('frames'), NF, i('frame_seq'), i('g_attr'),
+                       i('t_id'), i('seq_tab'), S, cells, sumG, sumT, max_boxes, max_dontcare, params[:3],
+                       int(params[3]), work, o('frame_d').view(torch.float64), o('frame_i'),
+                       o('seq_d').view(torch.float64), o('seq_i'))
+    return res
+
+
+def _hota_meta(packed, sizes, params):
+    return packed.new_empty((hota_layout(sizes)[3],), dtype=torch.int32)
+
+
+_LIB.define('hota(Tensor packed, int[] sizes, float[] params) -> Tensor')
+_LIB.impl('hota', _hota, 'CUDA')
+_LIB.impl('hota', _hota_meta, 'Meta')
+
+
 # ---- training labels (mmmot_amd/labels.py; csrc/labels.hip) ---------------------------------------------------------
 #   mmmot::generate_gt(Tensor ids, Tensor cls, Tensor chains) -> Tensor
 #       The targets of B chains in one launch (mmmot_generate_gt).  ids / cls: flat int32 device tensors, chain c's L
