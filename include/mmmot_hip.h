@@ -81,7 +81,8 @@ extern "C" {
  * 6 = mmmot_trunk_range_bind (per-caller range-guard counter blocks); 7 - 9: see the entry points marked so below;
  * 10 = mmmot_gram_rows at K = 128 writes the 32 x 32 blocks on and above the block diagonal of Gout only (the finalize
  * entry point mirrors), mmmot_set_gemm_rows_variant: 2 rejected, 3 / 4 = the two forms of the wide kernel;
- * mmmot_segment_argmax, mmmot_pair_expand_max_bwd added (backward of end_mode 'max'; additive, still 10). */
+ * mmmot_segment_argmax, mmmot_pair_expand_max_bwd added (backward of end_mode 'max'; additive, still 10);
+ * mmmot_mot3d added (3D MOT evaluation; additive, still 10). */
 int mmmot_abi_version(void);
 /* returns 0 and fills cu_count / gcn arch string (<=32 bytes) of device 0..; */
 int mmmot_device_info(int device, int* cu_count, char* arch, int arch_len);
@@ -909,6 +910,34 @@ int mmmot_hota(const double* boxes, int nG, int nT, int nD, const int* frames, i
                int max_boxes, int max_dontcare, double min_height, double max_truncation, double max_occlusion,
                int prepare, void* work, long long work_bytes, double* frame_d, int* frame_i, double* seq_d, int* seq_i,
                void* stream);
+
+/* 3D MOT evaluation of tracked sequences: CLEAR-MOT on a rotated-box overlap, and the AMOTA sweep over `levels` score
+ * thresholds (csrc/mot3d.hip, DESIGN.md section 13 "3D / AMOTA"; the rules are restated in tests/mot3d_ref.py), additive
+ * in ABI 10.  The frame evaluation is the one of mmmot_clear_mot (csrc/cm_search.h) with c = 1 - overlap read from a
+ * per-frame table; level l < levels keeps the tracker objects whose track score is >= thr[l], level `levels` keeps all
+ * (pass A).  Two phases, because the caller sorts between them:
+ *   phase 0: the overlap table, then pass A (frame, trajectory, sequence, total launches) into level `levels` of every
+ *   output, and msig fp64 [nG] = the track score of the partner of every ground-truth object that is a true positive and
+ *   not ignored, -inf elsewhere (the caller pre-fills it with -inf);
+ *   phase 1: msig holds the same values SORTED DESCENDING; one launch writes thr fp64 [levels] (+inf where the level is
+ *   unreachable) and reach int32 [levels], then the four launches run with a level dimension into levels 0 .. levels - 1.
+ * The launch count depends on neither NF nor S nor levels.
+ *   boxes, frames, g_attr, t_attr, traj_off, traj_obj, seq_off and the limits: as in mmmot_clear_mot;
+ *   box3d: fp64 [nG + nT][12] = the four footprint corners (x, z), y - h, y, w l, h w l, formed by the caller (not read
+ *   in mode 2);  sigma: fp64 [nT] = track score of every tracker object;
+ *   cell_off: int32 [NF] = first cell of the frame's [G][T] table, cells = their total < 2^31;  table: fp64 [cells] (work);
+ *   mode: 0 = IoU3D, 1 = IoUbev, 2 = the 2D IoU of mmmot_clear_mot;  gate: a cell is valid where c <= gate.
+ * Outputs as in mmmot_clear_mot with a leading level axis [levels + 1]: frame_d [..][NF][2], frame_i [..][NF][6], gt_out
+ * [..][nG][2], traj_i [..][NTr][4], seq_d [..][S + 1][2], seq_i [..][S + 1][12]; phase 0 writes level `levels` only.  A
+ * frame outside the limits, the sections or the table is marked and nothing of it is read.  No floating-point atomics: two
+ * calls return the same bits.  Returns MMMOT_EINVAL before any launch on a missing or misaligned pointer, a negative
+ * count, S < 1, cells >= 2^31, mode outside 0..2, levels outside 0..1024, phase outside {0, 1} or phase 1 at levels 0. */
+int mmmot_mot3d(const double* boxes, const double* box3d, const double* sigma, int nG, int nT, int nD,
+                const int* frames, const int* cell_off, int NF, const int* g_attr, const int* t_attr,
+                const int* traj_off, const int* traj_obj, int NTr, const int* seq_off, int S, int mode, int levels,
+                int phase, double gate, double min_height, double max_truncation, double max_occlusion, double* table,
+                long long cells, double* msig, double* frame_d, int* frame_i, int* gt_out, int* traj_i, double* seq_d,
+                int* seq_i, double* thr, int* reach, void* stream);
 
 /* Training targets of chains (reference tracking_model.py:294-351, TrackingModule.generate_gt, restated literally;
  * csrc/labels.hip), additive in ABI 10.  One workgroup per chain, ids and classes staged in LDS, every output element

@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('MMMOT_LIB_PATH', os.path.join(_HERE, 'libmmmot_hip.so'))  # override: tools' timing-experiment builds
 SOURCES = ['conv3x3.hip', 'hl16_format.hip', 'conv3x3_hl16_patch.hip', 'gemm_rows.hip', 'gemm_wide.hip',
            'gemm_ares.hip', 'gemm_wres.hip', 'gemm_wreg.hip', 'pn_mlp64.hip', 'gram.hip', 'points_gather.hip', 'crop_resize.hip', 'crop_augment.hip','small_kernels.hip', 'backward.hip', 'train.hip', 'train_vgg.hip', 'gemm_tn_f16.hip',
-           'assign.hip', 'assign_chain.hip', 'track_ids.hip', 'clear_mot.hip', 'hota.hip', 'align_points.hip', 'labels.hip', 'adam_step.hip', 'dropout.hip']
+           'assign.hip', 'assign_chain.hip', 'track_ids.hip', 'clear_mot.hip', 'hota.hip', 'mot3d.hip','align_points.hip', 'labels.hip', 'adam_step.hip', 'dropout.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 HIPFLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 
@@ -189,6 +189,12 @@ SIGNATURES = {
     # min_height, max_truncation, max_occlusion, prepare, work, work_bytes, frame_d, frame_i, seq_d, seq_i, stream
     'mmmot_hota': [c_f, c_i, c_i, c_i, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_double,
                    ctypes.c_double, ctypes.c_double, c_i, c_f, ctypes.c_longlong, c_f, c_f, c_f, c_f, c_f],
+    # boxes, box3d, sigma, nG, nT, nD, frames, cell_off, NF, g_attr, t_attr, traj_off, traj_obj, NTr, seq_off, S, mode,
+    # levels, phase, gate, min_height, max_truncation, max_occlusion, table, cells, msig, frame_d, frame_i, gt_out,
+    # traj_i, seq_d, seq_i, thr, reach, stream
+    'mmmot_mot3d': [c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_i,
+                    ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_f, ctypes.c_longlong, c_f, c_f,
+                    c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f],
     # ids, cls, chains, B, max_n, max_L, out, out_off, stream
     'mmmot_generate_gt': [c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f],
     # det_xywh, gt_xywh, gt_id, gt_name, frames, NF, car_code, dontcare_code, max_iou, max_n, det_id, det_cls, stream

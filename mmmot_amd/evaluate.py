@@ -28,6 +28,18 @@ in DESIGN.md section 13 and restated in tests/hota_ref.py, on the same packed ta
     h = evaluate_hota(step, result_path, part, gt_path='./data/tracking', cls='car')
 
 No agreement with any published implementation of these metrics is claimed.
+
+3D evaluation (``evaluate_3d_sequences`` / ``evaluate_3d`` -> ``Mot3D``; csrc/mot3d.hip): the CLEAR-MOT evaluation above
+with the cost 1 - IoU of the rotated 3D boxes (or of their bird's-eye-view footprints) in place of the image-plane IoU,
+and its sweep over 40 recall levels, thresholding the tracks by their mean score (AMOTA, sAMOTA, AMOTP).  The labels
+carry the 3D boxes and scores in ``Labels.box3d``:
+
+    gt = load_kitti(label_file, 'car', n_frames, True, box3d=True)
+    tr = labels_from_tracks(feed_dets, pipe.tracks, box3d=True, scores=scores)
+    m = evaluate_3d_sequences(gt, tr)                  # m.AMOTA, m.sAMOTA, m.AMOTP, m.all.MOTA, m.best, m.summary()
+
+The rules are written down in DESIGN.md section 13 "3D / AMOTA" and restated in tests/mot3d_ref.py.  No agreement with
+any published 3D evaluator is claimed.
 """
 import math
 import os
@@ -38,6 +50,7 @@ import numpy as np
 from .torch_ops import CLEAR_MOT_MAX_BOXES, CLEAR_MOT_MAX_DONTCARE, CLEAR_MOT_SEQ_INTS, clear_mot_layout
 from .torch_ops import (HOTA_ALPHAS, HOTA_FRAME_D, HOTA_FRAME_I, HOTA_MAX_CELLS, HOTA_MAX_IDS, HOTA_SEQ_D, HOTA_SEQ_I,
                         hota_layout)
+from .torch_ops import MOT3D_BOX, MOT3D_MAX_LEVELS, MOT3D_MODES, mot3d_layout
 
 TRAIN_SEQ_ID = ['0003', '0001', '0013', '0009', '0004', '0020', '0006', '0015', '0008', '0012']
 VALID_SEQ_ID = ['0005', '0007', '0017', '0011', '0002', '0014', '0000', '0010', '0016', '0019', '0018']
@@ -69,13 +82,15 @@ def class_code(name, cls):
 class Labels:
     """Packed label tables of S sequences.  rows: float64 [n, 10] = sequence, frame, track ID, class code, truncation,
     occlusion, x1, y1, x2, y2 in file order; n_frames: the seqmap's frame counts; length: frames held (n_frames, or more
-    where a row lies beyond); n_traj: distinct non-DontCare track IDs per sequence."""
+    where a row lies beyond); n_traj: distinct non-DontCare track IDs per sequence; box3d: None, or float64 [n, 8] = h, w,
+    l, x, y, z, rotation_y, score, row for row beside ``rows`` (KITTI camera coordinates; the score of ground truth is 0)."""
     rows: np.ndarray
     n_frames: np.ndarray
     length: np.ndarray
     n_traj: np.ndarray
     cls: str = 'car'
     ground_truth: bool = False
+    box3d: np.ndarray = None
 
     @property
     def n_sequences(self):
@@ -92,16 +107,22 @@ def concat(labels):
         o += lb.n_sequences
         rows.append(r)
     cat = lambda k: np.concatenate([getattr(lb, k) for lb in labels])
+    has3d = [lb.box3d is not None for lb in labels]
+    if any(has3d) and not all(has3d):
+        raise ValueError('concat: some Labels hold box3d and some do not')
     return Labels(np.concatenate(rows).reshape(-1, 10), cat('n_frames'), cat('length'), cat('n_traj'), labels[0].cls,
-                  labels[0].ground_truth)
+                  labels[0].ground_truth, cat('box3d').reshape(-1, 8) if all(has3d) and labels else None)
 
 
-def _finish(parsed, cls, n_frames, ground_truth, what):
-    """rows (frame, id, code, trunc, occ, box) of ONE sequence -> Labels: the bookkeeping of _loadData :293-328"""
-    length, seen, ids, rows = int(n_frames), set(), set(), []
-    for frame, tid, code, trunc, occ, box in parsed:
+def _finish(parsed, cls, n_frames, ground_truth, what, b3=None):
+    """rows (frame, id, code, trunc, occ, box) of ONE sequence -> Labels: the bookkeeping of _loadData :293-328.  b3: None,
+    or per parsed row its eight box3d values."""
+    length, seen, ids, rows, kept3 = int(n_frames), set(), set(), [], []
+    for k, (frame, tid, code, trunc, occ, box) in enumerate(parsed):
         if tid == -1 and code != DONTCARE:
             continue
+        if b3 is not None:
+            kept3.append(b3[k])
         if frame < 0:
             raise ValueError('%s: negative frame index %d' % (what, frame))
         if frame >= length:
@@ -116,12 +137,15 @@ def _finish(parsed, cls, n_frames, ground_truth, what):
             ids.add(tid)
         rows.append([0, frame, tid, code, trunc, occ] + list(box))
     return Labels(np.asarray(rows, np.float64).reshape(-1, 10), np.asarray([n_frames], np.int64),
-                  np.asarray([length], np.int64), np.asarray([len(ids)], np.int64), cls, bool(ground_truth))
+                  np.asarray([length], np.int64), np.asarray([len(ids)], np.int64), cls, bool(ground_truth),
+                  None if b3 is None else np.asarray(kept3, np.float64).reshape(-1, 8))
 
 
-def load_kitti(path, cls, n_frames, ground_truth):
-    """One KITTI tracking label / result file as Labels (evaluate_tracking.py:227-361 _loadData for one sequence)."""
-    parsed = []
+def load_kitti(path, cls, n_frames, ground_truth, box3d=False):
+    """One KITTI tracking label / result file as Labels (evaluate_tracking.py:227-361 _loadData for one sequence).
+    ``box3d``: also read columns 10..16 (h, w, l, x, y, z, rotation_y) and, of a result file, column 17 as the score (0
+    for ground truth or where the column is absent) into ``Labels.box3d``."""
+    parsed, b3 = [], [] if box3d else None
     with open(path, 'r') as f:
         for line in f:
             fields = line.strip().split(' ')
@@ -134,16 +158,22 @@ def load_kitti(path, cls, n_frames, ground_truth):
                 raise ValueError('%s: file is not in KITTI format' % path)
             parsed.append((int(float(fields[0])), int(float(fields[1])), code, int(float(fields[3])),
                            int(float(fields[4])), [float(v) for v in fields[6:10]]))
-    return _finish(parsed, cls, n_frames, ground_truth, path)
+            if box3d:
+                score = float(fields[17]) if not ground_truth and len(fields) > 17 else 0.
+                b3.append([float(v) for v in fields[10:17]] + [score])
+    return _finish(parsed, cls, n_frames, ground_truth, path, b3)
 
 
-def labels_from_tracks(frames, ids, frame_idx=None, cls='car', n_frames=None, ground_truth=False):
+def labels_from_tracks(frames, ids, frame_idx=None, cls='car', n_frames=None, ground_truth=False, box3d=False,
+                       scores=None):
     """The Labels that ``load_kitti`` reads from the file ``tracks.write_kitti_tracks(path, frames, ids, frame_idx)``
     writes, without the file: kept detections only, values through the same '{:.4f}' of the fp32 value.  ``n_frames``:
-    the sequence's frame count (default: one past the last frame)."""
+    the sequence's frame count (default: one past the last frame).  ``box3d``: also fill ``Labels.box3d`` from
+    ``dimensions`` (lhw -> hwl), ``location``, ``rotation_y`` and ``scores[t][j]`` (default 0.9; 0 for ground truth), as
+    ``load_kitti(box3d=True)`` reads them from the file ``write_kitti_tracks(..., scores=scores)`` writes."""
     from .tracks import KITTI_NAMES
     f4 = lambda v: float('{:.4f}'.format(float(np.float32(v))))
-    parsed, last = [], -1
+    parsed, last, b3 = [], -1, [] if box3d else None
     for t, (d, fid) in enumerate(zip(frames, ids)):
         frame = t if frame_idx is None else int(frame_idx[t])
         last = max(last, frame)
@@ -157,7 +187,11 @@ def labels_from_tracks(frames, ids, frame_idx=None, cls='car', n_frames=None, gr
             trunc = int(f4(d['truncated'][j])) if 'truncated' in d else -1
             occ = int(d['occluded'][j]) if 'occluded' in d else -1
             parsed.append((frame, int(fid[j]), code, trunc, occ, [f4(v) for v in np.asarray(d['bbox'][j]).reshape(-1)]))
-    return _finish(parsed, cls, last + 1 if n_frames is None else n_frames, ground_truth, 'labels_from_tracks')
+            if box3d:
+                score = 0. if ground_truth else f4(0.9 if scores is None else scores[t][j])
+                b3.append([f4(v) for v in np.asarray(d['dimensions'][j])[[1, 2, 0]]] +
+                          [f4(v) for v in np.asarray(d['location'][j]).reshape(-1)] + [f4(d['rotation_y'][j]), score])
+    return _finish(parsed, cls, last + 1 if n_frames is None else n_frames, ground_truth, 'labels_from_tracks', b3)
 
 
 @dataclass
@@ -240,18 +274,20 @@ def pack(gt, tracker):
     foff = np.concatenate([[0], np.cumsum(F)])
     NF = int(foff[-1])
 
-    def by_frame(rows):
-        """rows in frame order (stable: file order within a frame), their global frame index, per-frame offset / count"""
-        fr = foff[rows[:, SEQ].astype(np.int64)] + rows[:, FRAME].astype(np.int64)
+    def by_frame(rows, sel):
+        """the rows ``sel`` (a mask) in frame order (stable: file order within a frame), their index in ``rows``,
+        per-frame offset / count"""
+        idx = np.flatnonzero(sel)
+        fr = foff[rows[idx, SEQ].astype(np.int64)] + rows[idx, FRAME].astype(np.int64)
         order = np.argsort(fr, kind='stable')
-        rows, fr = rows[order], fr[order]
+        idx, fr = idx[order], fr[order]
         cnt = np.bincount(fr, minlength=NF).astype(np.int64)
-        return rows, fr, np.cumsum(cnt) - cnt, cnt
+        return rows[idx], idx, np.cumsum(cnt) - cnt, cnt
 
-    g_rows, g_fr, g_off, g_cnt = by_frame(gt.rows[gt.rows[:, CLS] != DONTCARE])
-    d_rows, _, d_off, d_cnt = by_frame(gt.rows[gt.rows[:, CLS] == DONTCARE])
+    g_rows, g_idx, g_off, g_cnt = by_frame(gt.rows, gt.rows[:, CLS] != DONTCARE)
+    d_rows, _, d_off, d_cnt = by_frame(gt.rows, gt.rows[:, CLS] == DONTCARE)
     tr = tracker.rows
-    t_rows, _, t_off, t_cnt = by_frame(tr[tr[:, FRAME] < F[tr[:, SEQ].astype(np.int64)]])
+    t_rows, t_idx, t_off, t_cnt = by_frame(tr, tr[:, FRAME] < F[tr[:, SEQ].astype(np.int64)])
     if NF and (max(g_cnt.max(), t_cnt.max()) > CLEAR_MOT_MAX_BOXES or d_cnt.max() > CLEAR_MOT_MAX_DONTCARE):
         raise ValueError('evaluate: a frame holds more than %d boxes on a side or more than %d DontCare areas'
                          % (CLEAR_MOT_MAX_BOXES, CLEAR_MOT_MAX_DONTCARE))
@@ -270,7 +306,7 @@ def pack(gt, tracker):
         'boxes': np.concatenate([g_rows[:, X1:], t_rows[:, X1:], d_rows[:, X1:]]).astype(np.float64),
         'frames': frames, 'g_attr': g_rows[:, [TRUNC, OCC, CLS]], 't_attr': t_rows[:, [TID, CLS]],
         'traj_off': traj_off, 'traj_obj': traj_obj, 'seq_off': np.stack([foff, toff], axis=1),
-        'g_cnt': g_cnt, 't_cnt': t_cnt, 'foff': foff,
+        'g_cnt': g_cnt, 't_cnt': t_cnt, 'foff': foff, 'g_idx': g_idx, 't_idx': t_idx,
         'traj_key': np.stack([traj_seq, key[first, 1] if NTr else traj_seq, np.diff(traj_off)], axis=1),
         'n_frames': gt.n_frames, 'n_gt_trajectories': int(gt.n_traj.sum()),
         'n_tr_trajectories': int(tracker.n_traj.sum()), 'cls': gt.cls,
@@ -609,4 +645,246 @@ def evaluate_hota(result_sha, root, part='all', gt_path='./data/tracking', cls=N
         except IOError:
             raise ValueError('Ground truth not found.')
         last = hota_sequences(gt, tracker, cls=c, device=device)
+    return False if last is None else last
+
+
+# ---- 3D / AMOTA (csrc/mot3d.hip) -------------------------------------------------------------------------------------
+# columns of Labels.box3d
+B3_H, B3_W, B3_L, B3_X, B3_Y, B3_Z, B3_RY, B3_SCORE = range(8)
+
+
+def footprints(b3):
+    """Labels.box3d rows -> float64 [n, 12]: the four footprint corners (x, z), y - h, y, w l, h w l (DESIGN.md section
+    13 "3D / AMOTA"), in NumPy float64 - what the device and tests/mot3d_ref.py both start from."""
+    b3 = np.asarray(b3, np.float64).reshape(-1, 8)
+    h, w, l, x, y, z, ry = (b3[:, k] for k in range(7))
+    c, s = np.cos(ry), np.sin(ry)
+    out = np.empty((len(b3), MOT3D_BOX), np.float64)
+    for k, (sx, sz) in enumerate(((1., 1.), (1., -1.), (-1., -1.), (-1., 1.))):
+        dx, dz = sx * (l / 2), sz * (w / 2)
+        out[:, 2 * k] = x + c * dx + s * dz
+        out[:, 2 * k + 1] = z - s * dx + c * dz
+    out[:, 8], out[:, 9], out[:, 10], out[:, 11] = y - h, y, w * l, h * w * l
+    return out
+
+
+def track_scores(rows, scores):
+    """per row the score of its track: the mean, in fp64 and in row order, of the scores of the rows with the same
+    (sequence, track ID)"""
+    if not len(rows):
+        return np.zeros(0, np.float64)
+    _, inv = np.unique(rows[:, [SEQ, TID]].astype(np.int64), axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    tot, cnt = np.zeros(inv.max() + 1, np.float64), np.bincount(inv)
+    np.add.at(tot, inv, np.asarray(scores, np.float64))  # one element after the other, in row order
+    return (tot / cnt)[inv]
+
+
+def pack_3d(gt, tracker, need_3d=True):
+    """``pack`` plus the tables of mmmot_mot3d: the packed 3D boxes (``footprints``), the track score of every evaluated
+    tracker row (``track_scores`` over the evaluated rows, in file order) and the offsets of the per-frame overlap
+    tables.  ``need_3d=False`` (the '2d' mode) takes Labels without box3d: zero boxes, zero scores.  Raises ValueError
+    on what ``pack`` refuses, on Labels without box3d, on a non-positive or non-finite dimension and on an overlap table
+    beyond 32-bit offsets - before anything reaches the device."""
+    gt = concat(gt) if isinstance(gt, (list, tuple)) else gt
+    tracker = concat(tracker) if isinstance(tracker, (list, tuple)) else tracker
+    p = pack(gt, tracker)
+    nG, nT = p['sizes'][0], p['sizes'][1]
+    if gt.box3d is None or tracker.box3d is None:
+        if need_3d:
+            raise ValueError('evaluate_3d: the Labels hold no box3d (load_kitti / labels_from_tracks with box3d=True)')
+        p['box3d'], p['sigma'] = np.zeros((nG + nT, MOT3D_BOX)), np.zeros(nT)
+    else:
+        if len(gt.box3d) != len(gt.rows) or len(tracker.box3d) != len(tracker.rows):
+            raise ValueError('evaluate_3d: box3d and rows differ in length')
+        b3 = np.concatenate([gt.box3d[p['g_idx']], tracker.box3d[p['t_idx']]]).reshape(-1, 8)
+        if need_3d and not (np.all(np.isfinite(b3)) and np.all(b3[:, :3] > 0)):
+            raise ValueError('evaluate_3d: a box has a non-positive or non-finite dimension')
+        p['box3d'] = footprints(b3)
+        file_order = np.sort(p['t_idx'])
+        sig = np.zeros(len(tracker.rows))
+        sig[file_order] = track_scores(tracker.rows[file_order], tracker.box3d[file_order, B3_SCORE])
+        p['sigma'] = sig[p['t_idx']]
+    cnt = p['g_cnt'] * p['t_cnt']
+    p['cell_off'] = np.cumsum(cnt) - cnt
+    p['cells'] = int(cnt.sum())
+    if p['cells'] >= 2 ** 31:
+        raise ValueError('evaluate_3d: the overlap tables hold %d cells, beyond 32-bit offsets' % p['cells'])
+    return p
+
+
+@dataclass
+class Mot3D:
+    """3D MOT evaluation.  Per-level arrays have one entry per level k = 1 .. levels (recall r_k = k / levels); an
+    unreachable level holds 0 in the three metric arrays and +inf in ``thr``.  ``all``: the ClearMot of every track (pass
+    A); ``best``: the ClearMot of the reachable level with the highest sMOTA (lowest k on ties), None when there is none."""
+    cls: str = 'car'
+    overlap: str = '3d'
+    AMOTA: float = 0.0
+    sAMOTA: float = 0.0
+    AMOTP: float = 0.0
+    levels: int = 0
+    recall: np.ndarray = None         # r_k
+    thr: np.ndarray = None
+    reachable: np.ndarray = None      # bool
+    MOTA_k: np.ndarray = None
+    sMOTA_k: np.ndarray = None
+    MOTP_k: np.ndarray = None
+    counters: np.ndarray = None       # int64 [levels, 12]: the totals row of mmmot_clear_mot per level
+    cost_k: np.ndarray = None         # sum of the overlaps of the matches
+    n_gt_k: np.ndarray = None
+    best_level: int = -1              # index into the per-level arrays
+    all: ClearMot = None
+    best: ClearMot = None
+
+    def summary(self):
+        """(AMOTA, sAMOTA, AMOTP, then MOTA, MOTP, recall, precision, fp, fn, id_switches of every track)"""
+        a = self.all
+        return (self.AMOTA, self.sAMOTA, self.AMOTP, a.MOTA, a.MOTP, a.recall, a.precision, a.fp, a.fn, a.id_switches)
+
+    def summary_line(self):
+        return '%.6f ' * 7 % self.summary()[:7] + '%d %d %d' % self.summary()[7:]
+
+
+def sweep_metrics(tot_i, tot_d, n_obj, reach):
+    """step 4 and 5 of the sweep from the levels' totals: tot_i int [L, 12] (the totals row of mmmot_clear_mot), tot_d
+    float [L] (sum of the overlaps), n_obj = ground-truth objects, reach bool [L] ->
+    (AMOTA, sAMOTA, AMOTP, MOTA_k, sMOTA_k, MOTP_k, n_gt_k)"""
+    L = len(reach)
+    mota, smota, motp, n_gts = np.zeros(L), np.zeros(L), np.zeros(L), np.zeros(L, np.int64)
+    for k in range(L):
+        tp, itp, fn, ifn, fp, _, ids = (int(v) for v in tot_i[k][:7])
+        n_gt = n_obj - ifn - itp
+        n_gts[k] = n_gt
+        if not reach[k] or n_gt <= 0:
+            continue
+        r = (k + 1) / float(L)
+        mota[k] = 1 - (fn + fp + ids) / float(n_gt)
+        smota[k] = max(0., 1 - (fp + fn + ids - (1 - r) * n_gt) / (r * n_gt))
+        motp[k] = float(tot_d[k]) / float(tp) if tp else 0.
+    mean = lambda v: sum(float(x) for x in v) / float(L) if L else 0.
+    return mean(mota), mean(smota), mean(motp), mota, smota, motp, n_gts
+
+
+def finish_3d(p, out, levels, overlap):
+    """the packed tables and the device's output sections (numpy) -> Mot3D"""
+    nG, nT, nD, NF, NTr, S = p['sizes']
+    Lv = levels + 1
+    lev = {'frame_d': out['frame_d'].reshape(Lv, -1), 'seq_d': out['seq_d'].reshape(Lv, -1),
+           'frame_i': out['frame_i'].reshape(Lv, -1), 'gt_out': out['gt_out'].reshape(Lv, -1),
+           'traj_i': out['traj_i'].reshape(Lv, -1), 'seq_i': out['seq_i'].reshape(Lv, -1)}
+    thr = out['thr'].copy()
+    reach = out['reach'].astype(bool)
+    fseq = np.repeat(np.arange(S), np.diff(p['foff']))
+    t_seq = np.repeat(fseq, p['t_cnt']) if nT else np.zeros(0, np.int64)
+    t_frame = np.repeat(np.arange(NF), p['t_cnt'])
+    t_key = np.stack([t_seq, p['t_attr'][:, 0].astype(np.int64)], axis=1) if nT else np.zeros((0, 2), np.int64)
+
+    def one(k):
+        """the ClearMot of level k (``levels``: pass A) over the tracker rows that level keeps"""
+        q = dict(p)
+        if k < levels:
+            keep = p['sigma'] >= thr[k]
+            q['sizes'] = [nG, int(keep.sum()), nD, NF, NTr, S]
+            q['t_cnt'] = np.bincount(t_frame[keep], minlength=NF).astype(np.int64)
+            q['n_tr_trajectories'] = len(np.unique(t_key[keep], axis=0))
+        return finish(q, {name: v[k] for name, v in lev.items()})
+
+    m = Mot3D(cls=p['cls'], overlap=overlap, levels=levels, all=one(levels))
+    seq_i = lev['seq_i'].reshape(Lv, S + 1, CLEAR_MOT_SEQ_INTS).astype(np.int64)
+    seq_d = lev['seq_d'].reshape(Lv, S + 1, 2)
+    if levels and seq_i[:levels, S].min() < 0:
+        raise RuntimeError('mmmot_mot3d: a frame or a trajectory outside the launch limits reached the kernel')
+    m.recall = np.arange(1, levels + 1) / float(levels) if levels else np.zeros(0)
+    m.thr, m.reachable = thr, reach
+    m.counters, m.cost_k = seq_i[:levels, S].copy(), seq_d[:levels, S, 0].copy()
+    m.AMOTA, m.sAMOTA, m.AMOTP, m.MOTA_k, m.sMOTA_k, m.MOTP_k, m.n_gt_k = sweep_metrics(m.counters, m.cost_k, nG, reach)
+    if reach.any():
+        m.best_level = int(np.argmax(np.where(reach, m.sMOTA_k, -1.)))  # the first of equal maxima
+        m.best = one(m.best_level)
+    return m
+
+
+def upload_3d(p, sizes, device):
+    """the tables of ``pack_3d`` as the one int32 block of mmmot::mot3d on ``device``"""
+    import torch
+    inp, _, n_in, _ = mot3d_layout(sizes)
+    host = torch.empty(n_in, dtype=torch.int32, pin_memory=device != 'meta')
+    h = host.numpy()
+    for name, (o, n) in inp.items():
+        if name in ('boxes', 'box3d', 'sigma'):
+            h[o:o + n].view(np.float64)[:] = np.asarray(p[name], np.float64).reshape(-1)
+        else:
+            h[o:o + n] = np.asarray(p[name]).reshape(-1)
+    return host.to(device, non_blocking=True)
+
+
+def overlap_tables(gt, tracker, overlap='3d', device='cuda'):
+    """c = 1 - overlap of every (ground truth, tracker) cell as the device forms it: per frame a float64 [G, T] array
+    (the table the association reads; never read back by ``evaluate_3d_sequences``)"""
+    from .torch_ops import mot3d_run
+    if overlap not in MOT3D_MODES:
+        raise ValueError("evaluate_3d: overlap must be '3d', 'bev' or '2d', got %r" % (overlap,))
+    p = pack_3d(gt, tracker, need_3d=overlap != '2d')
+    sizes = list(p['sizes']) + [p['cells'], 0, MOT3D_MODES[overlap]]
+    tab = mot3d_run(upload_3d(p, sizes, device), sizes, [1.0, 25., 0., 2.])[1].cpu().numpy()
+    return [tab[o:o + g * t].reshape(g, t) for o, g, t in zip(p['cell_off'], p['g_cnt'], p['t_cnt'])]
+
+
+def evaluate_3d_sequences(gt, tracker, cls='car', overlap='3d', min_iou=0.25, levels=40, min_overlap=0.5,
+                          max_truncation=0, min_height=25, max_occlusion=2, device='cuda'):
+    """3D MOT statistics of tracker Labels against ground-truth Labels (one Labels of S sequences, or a list with one
+    per sequence; both with ``box3d``) on the device: one upload, the launches of mmmot_mot3d, one read-back.
+    ``overlap``: '3d' (IoU of the rotated boxes) or 'bev' (IoU of their footprints), both gated at ``min_iou``, or '2d'
+    (the image-plane IoU of ``evaluate_sequences`` gated at ``min_overlap``; takes Labels without box3d).  ``levels``:
+    the recall levels of the AMOTA sweep; 0 evaluates the one operating point with every track.  The rules are those
+    of DESIGN.md section 13 "3D / AMOTA"; no agreement with any published 3D evaluator is claimed."""
+    import torch
+    if overlap not in MOT3D_MODES:
+        raise ValueError("evaluate_3d: overlap must be '3d', 'bev' or '2d', got %r" % (overlap,))
+    levels = int(levels)
+    if levels < 0 or levels > MOT3D_MAX_LEVELS:
+        raise ValueError('evaluate_3d: levels must lie in [0, %d], got %d' % (MOT3D_MAX_LEVELS, levels))
+    p = pack_3d(gt, tracker, need_3d=overlap != '2d')
+    p['cls'] = cls
+    gate = float(min_overlap) if overlap == '2d' else 1.0 - float(min_iou)
+    sizes = list(p['sizes']) + [p['cells'], levels, MOT3D_MODES[overlap]]
+    outl = mot3d_layout(sizes)[1]
+    r = torch.ops.mmmot.mot3d(upload_3d(p, sizes, device), sizes, [gate, float(min_height), float(max_truncation),
+                                                                   float(max_occlusion)]).cpu().numpy()
+    out = {name: (r[o:o + n].view(np.float64) if name in ('frame_d', 'seq_d', 'thr') else r[o:o + n])
+           for name, (o, n) in outl.items()}
+    return finish_3d(p, out, levels, overlap)
+
+
+def evaluate_3d(result_sha, root, part='all', gt_path='./data/tracking', cls=None, overlap='3d', min_iou=0.25,
+                levels=40, device='cuda'):
+    """The file loading of ``evaluate`` with ``evaluate_3d_sequences`` behind it: evaluates
+    ``root/result_sha/part/<sequence>.txt`` (columns 10..17 included) against ``gt_path/label_02`` for car, then
+    pedestrian (``cls``: one class only), writes ``eval/<cls>/stats3d_<cls>.txt`` (``Mot3D.summary_line``) beside the
+    results and returns the Mot3D of the last class evaluated, or False when the tracker holds neither class."""
+    names, n_frames = sequences_of(part, gt_path)
+    if not names:
+        raise ValueError('evaluate_3d: the seqmap under %s holds no sequence of part %r' % (gt_path, part))
+    t_path = os.path.join(root, str(result_sha), part)
+    last = None
+    for c in (('car', 'pedestrian') if cls is None else (cls,)):
+        try:
+            tracker = concat([load_kitti(os.path.join(t_path, '%s.txt' % s), c, n, False, box3d=True)
+                              for s, n in zip(names, n_frames)])
+        except IOError:
+            continue
+        if tracker.n_traj.sum() == 0:
+            continue
+        try:
+            gt = concat([load_kitti(os.path.join(gt_path, 'label_02', '%s.txt' % s), c, n, True, box3d=True)
+                         for s, n in zip(names, n_frames)])
+        except IOError:
+            raise ValueError('Ground truth not found.')
+        m = evaluate_3d_sequences(gt, tracker, cls=c, overlap=overlap, min_iou=min_iou, levels=levels, device=device)
+        eval_dir = os.path.join(t_path, 'eval', c)
+        os.makedirs(eval_dir, exist_ok=True)
+        with open(os.path.join(eval_dir, 'stats3d_%s.txt' % c), 'w') as f:
+            f.write(m.summary_line() + '\n')
+        last = m
     return False if last is None else last

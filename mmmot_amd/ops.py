@@ -461,6 +461,22 @@ class HipOps:
                                  _iptr(frame_i), _ptr(seq_d, d), _iptr(seq_i), self._stream())
         _lib.check(st, 'mmmot_hota')
 
+    def mot3d(self, boxes, box3d, sigma, nG, nT, nD, frames, cell_off, NF, g_attr, t_attr, traj_off, traj_obj, NTr,
+              seq_off, S, mode, levels, phase, params, table, cells, msig, frame_d, frame_i, gt_out, traj_i, seq_d, seq_i,
+              thr, reach):
+        """One phase of the 3D MOT evaluation of S sequences; see mmmot_mot3d.  boxes / box3d / sigma / table / msig /
+        frame_d / seq_d / thr: fp64 device tensors, the rest int32; params: (gate, min_height, max_truncation,
+        max_occlusion)."""
+        d = torch.float64
+        st = self.lib.mmmot_mot3d(_ptr(boxes, d), _ptr(box3d, d), _ptr(sigma, d), int(nG), int(nT), int(nD),
+                                  _iptr(frames), _iptr(cell_off), int(NF), _iptr(g_attr), _iptr(t_attr), _iptr(traj_off),
+                                  _iptr(traj_obj), int(NTr), _iptr(seq_off), int(S), int(mode), int(levels), int(phase),
+                                  float(params[0]), float(params[1]), float(params[2]), float(params[3]),
+                                  _ptr(table, d), int(cells), _ptr(msig, d), _ptr(frame_d, d), _iptr(frame_i),
+                                  _iptr(gt_out), _iptr(traj_i), _ptr(seq_d, d), _iptr(seq_i), _ptr(thr, d), _iptr(reach),
+                                  self._stream())
+        _lib.check(st, 'mmmot_mot3d')
+
     def generate_gt(self, ids, cls, chains, B, max_n, max_L, out, out_off):
         """Training targets of B chains in one launch; see mmmot_generate_gt.  ids / cls / chains / out_off: int32 device
         tensors; out: fp32."""

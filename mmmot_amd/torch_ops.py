@@ -626,6 +626,96 @@ _LIB.impl('hota', _hota, 'CUDA')
 _LIB.impl('hota', _hota_meta, 'Meta')
 
 
+# ---- 3D MOT evaluation (mmmot_amd/evaluate.py; csrc/mot3d.hip) ------------------------------------------------------
+#   mmmot::mot3d(Tensor packed, int[] sizes, float[] params) -> Tensor
+#       Evaluates S sequences at levels + 1 operating points (mmmot_mot3d: the overlap table and pass A, a sort of the
+#       matched track scores, the thresholds and the sweep - a launch count that depends on neither NF nor S nor levels).
+#       packed: ONE device int32 block in the order of mot3d_layout()[0] (the fp64 sections first, as their bit patterns);
+#       sizes = [nG, nT, nD, NF, NTr, S, cells, levels, mode (0 '3d', 1 'bev', 2 '2d')]; params = [gate, min_height,
+#       max_truncation, max_occlusion].  Returns ONE int32 block in the order of mot3d_layout()[1]: the sections of
+#       mmmot::clear_mot with a leading level axis [levels + 1] (the last level is pass A), thr and reach.  The overlap
+#       table and the matched scores are allocated here and never read back.  The frame limits are the caller's to check
+#       on the host (evaluate.pack_3d); the kernel marks a frame outside them instead of reading it.
+MOT3D_BOX = 12          # doubles per packed 3D box: four footprint corners (x, z), y - h, y, w l, h w l
+MOT3D_MAX_LEVELS = 1024
+MOT3D_MODES = {'3d': 0, 'bev': 1, '2d': 2}
+
+
+def mot3d_layout(sizes):
+    """({input section: (offset, int32 count)}, {output section: (offset, int32 count)}, input ints, output ints) of a
+    call with sizes = [nG, nT, nD, NF, NTr, S, cells, levels, mode]; fp64 sections come first in both blocks (8-byte
+    aligned).  Raises ValueError beyond the limits of mmmot_mot3d."""
+    if len(sizes) != 9 or min(sizes) < 0 or sizes[5] < 1 or sizes[7] > MOT3D_MAX_LEVELS or sizes[8] > 2:
+        raise ValueError('mmmot::mot3d: sizes must be [nG, nT, nD, NF, NTr, S, cells, levels, mode] with S >= 1, levels '
+                         '<= %d and mode in 0..2, got %s' % (MOT3D_MAX_LEVELS, list(sizes)))
+    nG, nT, nD, NF, NTr, S, cells, levels, mode = (int(v) for v in sizes)
+    if cells >= 2 ** 31:
+        raise ValueError('mmmot::mot3d: the overlap table exceeds 32-bit offsets')
+    Lv = levels + 1
+
+    def lay(parts):
+        out, o = {}, 0
+        for name, n in parts:
+            out[name] = (o, n)
+            o += n
+        if o >= 2 ** 31:
+            raise ValueError('mmmot::mot3d: block exceeds 32-bit offsets')
+        return out, o
+
+    inp, n_in = lay([('boxes', 8 * (nG + nT + nD)), ('box3d', 2 * MOT3D_BOX * (nG + nT)), ('sigma', 2 * nT),
+                     ('frames', 6 * NF), ('cell_off', NF), ('g_attr', 3 * nG), ('t_attr', 2 * nT),
+                     ('traj_off', NTr + 1), ('traj_obj', nG), ('seq_off', 2 * (S + 1))])
+    out, n_out = lay([('frame_d', 4 * NF * Lv), ('seq_d', 4 * (S + 1) * Lv), ('thr', 2 * levels),
+                      ('frame_i', 6 * NF * Lv), ('gt_out', 2 * nG * Lv), ('traj_i', 4 * NTr * Lv),
+                      ('seq_i', CLEAR_MOT_SEQ_INTS * (S + 1) * Lv), ('reach', levels)])
+    return inp, out, n_in, n_out
+
+
+def mot3d_run(packed, sizes, params):
+    """mmmot::mot3d's launches -> (the result block, the overlap table fp64 [cells]); the table is what
+    evaluate.overlap_tables shows, the operator returns the block alone"""
+    inp, outl, n_in, n_out = mot3d_layout(sizes)
+    if packed.dtype != torch.int32 or packed.dim() != 1 or packed.numel() != n_in or not packed.is_contiguous():
+        raise ValueError('mmmot::mot3d: packed must be a contiguous int32 [%d] block for sizes %s' % (n_in, list(sizes)))
+    if len(params) != 4:
+        raise ValueError('mmmot::mot3d: params = [gate, min_height, max_truncation, max_occlusion]')
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    nG, nT, nD, NF, NTr, S, cells, levels, mode = (int(v) for v in sizes)
+    res = torch.empty(n_out, dtype=torch.int32, device=packed.device)
+    table = torch.empty(cells, dtype=torch.float64, device=packed.device)
+    msig = torch.full((nG,), float('-inf'), dtype=torch.float64, device=packed.device)
+    sec = lambda buf, lay, name: buf[lay[name][0]:lay[name][0] + lay[name][1]]
+    i = lambda name: sec(packed, inp, name)
+    o = lambda name: sec(res, outl, name)
+    d = lambda t: t.view(torch.float64)
+
+    def phase(k, m):
+        _ASSOC_OPS[0].mot3d(d(i('boxes')), d(i('box3d')), d(i('sigma')), nG, nT, nD, i('frames'), i('cell_off'), NF,
+                            i('g_attr'), i('t_attr'), i('traj_off'), i('traj_obj'), NTr, i('seq_off'), S, mode, levels,
+                            k, params, table, cells, m, d(o('frame_d')), o('frame_i'), o('gt_out'), o('traj_i'),
+                            d(o('seq_d')), o('seq_i'), d(o('thr')), o('reach'))
+
+    phase(0, msig)
+    if levels:
+        phase(1, torch.sort(msig, descending=True).values)
+    return res, table
+
+
+def _mot3d(packed, sizes, params):
+    return mot3d_run(packed, sizes, params)[0]
+
+
+def _mot3d_meta(packed, sizes, params):
+    return packed.new_empty((mot3d_layout(sizes)[3],), dtype=torch.int32)
+
+
+_LIB.define('mot3d(Tensor packed, int[] sizes, float[] params) -> Tensor')
+_LIB.impl('mot3d', _mot3d, 'CUDA')
+_LIB.impl('mot3d', _mot3d_meta, 'Meta')
+
+
 # ---- training labels (mmmot_amd/labels.py; csrc/labels.hip) ---------------------------------------------------------
 #   mmmot::generate_gt(Tensor ids, Tensor cls, Tensor chains) -> Tensor
 #       The targets of B chains in one launch (mmmot_generate_gt).  ids / cls: flat int32 device tensors, chain c's L

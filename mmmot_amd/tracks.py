@@ -347,13 +347,13 @@ def merge_chain_tracks(tracks, frames, ids, frame_start, stored, on_tracks=None)
             on_tracks(t, i)
 
 
-def write_kitti_tracks(path, frames, ids, frame_idx=None):
+def write_kitti_tracks(path, frames, ids, frame_idx=None, scores=None):
     """The reference's result file (utils/data_util.py:80-128 write_kitti_result + kitti_result_line) on the host:
     ``frames``: per frame the detection dict the pipeline holds (FrameFeed.dets: bbox [n, 4], dimensions [n, 3] lhw,
     location [n, 3], rotation_y [n]; optional name (KITTI class index or string), truncated, occluded, alpha, else the
     format's "unknown" values); ``ids``: per frame the per-detection IDs (pipe.tracks).  Kept detections only,
     dimensions lhw -> hwl, score 0.9, values at fp32 as the reference's tensors; ``frame_idx``: the frames' numbers
-    (default 0, 1, ..)."""
+    (default 0, 1, ..); ``scores``: per frame the per-detection scores, written in place of the constant 0.9."""
     f4 = lambda v: '{:.4f}'.format(float(np.float32(v)))
     lines = []
     for t, (d, fid) in enumerate(zip(frames, ids)):
@@ -368,7 +368,8 @@ def write_kitti_tracks(path, frames, ids, frame_idx=None):
                    str(int(d['occluded'][j])) if 'occluded' in d else '-1',
                    f4(d['alpha'][j]) if 'alpha' in d else '-10']
             row += [f4(v) for v in np.asarray(d['bbox'][j]).reshape(-1)] + [f4(v) for v in dims]
-            row += [f4(v) for v in np.asarray(d['location'][j]).reshape(-1)] + [f4(d['rotation_y'][j]), f4(0.9)]
+            row += [f4(v) for v in np.asarray(d['location'][j]).reshape(-1)] + [f4(d['rotation_y'][j]),
+                                                                                f4(0.9 if scores is None else scores[t][j])]
             lines.append(' '.join(row))
     with open(path, 'w') as f:
         f.write('\n'.join(lines))

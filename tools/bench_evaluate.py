@@ -7,7 +7,13 @@ beside the NumPy + scipy restatement tests/hota_ref.py on the same tables, and t
 ``run_hota`` (upload, launches, read-back).  Every timed run ends in a synchronise; one untimed run first; each repeat
 runs all of them in turn.  Whether the two records agree in their integer fields is reported.  Writes <out>/bench_hota.json.
 
+--mot3d times ``evaluate_3d_sequences`` (3D IoU, 40 levels: packing, one upload, the launches of mmmot_mot3d, one
+read-back, the ratios) and its single operating point (levels = 0) on 3D scenes of the same shape
+(tests/mot3d_cases.random_sequence), beside the NumPy restatement tests/mot3d_ref.py, which is run once.  Whether the
+two agree in the thresholds and the per-level counters is reported.  Writes <out>/bench_mot3d.json.
+
     python tools/bench_evaluate.py --hota --out <dir> [--repeats 3]
+    python tools/bench_evaluate.py --mot3d --out <dir> [--repeats 3]
 """
 import argparse
 import json
@@ -71,12 +77,58 @@ def bench_hota(args):
     print(json.dumps(res))
 
 
+def bench_mot3d(args):
+    import mot3d_cases
+    import mot3d_ref
+    rng = np.random.default_rng(2024)
+    gts, trs = [], []
+    for s, n in enumerate(FRAMES):
+        counts = [tuple(int(v) for v in rng.integers(5, 13, 2)) for _ in range(n)]
+        g, t = mot3d_cases.random_sequence(np.random.default_rng(9000 + s), counts, n_gid=40)
+        gts.append(g)
+        trs.append(t)
+    p = E.pack_3d(gts, trs)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, r
+
+    modes = {'evaluate_3d_sequences': lambda: E.evaluate_3d_sequences(gts, trs),
+             'evaluate_3d_sequences_levels0': lambda: E.evaluate_3d_sequences(gts, trs, levels=0)}
+    m = modes['evaluate_3d_sequences']()  # untimed
+    modes['evaluate_3d_sequences_levels0']()
+    times = {k: [] for k in modes}
+    for _ in range(args.repeats):
+        for k, fn in modes.items():
+            times[k].append(timed(fn)[0])
+    t_ref, want = timed(lambda: mot3d_ref.sweep(E.concat(gts), E.concat(trs), '3d'))
+    keys = ('tp', 'itp', 'fn', 'ifn', 'fp', 'n_itr', 'id_switches', 'fragments')
+    equal = bool(np.array_equal(m.thr, want['thr'])) and all(
+        m.counters[k][:8].tolist() == [want['levels'][k][q] for q in keys] for k in range(40) if want['reachable'][k])
+    res = {'sequences': len(FRAMES), 'frames': int(sum(FRAMES)), 'gt_boxes': p['sizes'][0], 'tracker_boxes': p['sizes'][1],
+           'cells': p['cells'], 'levels': 40, 'reachable': int(m.reachable.sum()), 'repeats': args.repeats, 'AMOTA': m.AMOTA,
+           'sAMOTA': m.sAMOTA, 'AMOTP': m.AMOTP, 'thresholds_and_counters_equal': equal,
+           'seconds': dict({k: {'min': min(v), 'median': float(np.median(v)), 'max': max(v)} for k, v in times.items()},
+                           numpy_restatement={'once': t_ref})}
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_mot3d.json'), 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--hota', action='store_true', help='time hota_sequences beside the NumPy restatement')
+    ap.add_argument('--mot3d', action='store_true', help='time evaluate_3d_sequences beside the NumPy restatement')
     ap.add_argument('--out', required=True)
     ap.add_argument('--repeats', type=int, default=3)
     args = ap.parse_args()
-    if not args.hota:
-        ap.error('nothing to measure: give --hota')
-    bench_hota(args)
+    if not (args.hota or args.mot3d):
+        ap.error('nothing to measure: give --hota or --mot3d')
+    if args.hota:
+        bench_hota(args)
+    if args.mot3d:
+        bench_mot3d(args)
