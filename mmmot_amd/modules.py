@@ -331,6 +331,42 @@ class PackSnapshot:
             self.versions[i] = self.tensors[i]._version
 
 
+def graph_stale_reason(engine_then, engine_now, pack_version_then, pack_version_now, trained_since_pack, packed_is_current):
+    """Why a captured forward may not be replayed any more (None: it may).  A replay launches exactly what was captured,
+    on the packed weights of capture time, and runs none of the eval entry points' checks - so everything they guard
+    against (``TrackingNet._repack_if_trained``) has to be refused here:
+      - the engine was replaced or its packed tensors were (load_state_dict / invalidate / set_trunk / .to(), a head
+        refresh that could not be done in place, refresh_head_device): the graph computes with tensors the model dropped;
+      - ``trained_since_pack``: a training step refreshed the fp32 head on the device, the fp16-split copies are stale;
+      - not ``packed_is_current``: a parameter or buffer was modified in place (optimizer.step(), a training-mode
+        BatchNorm update, by hand) and nothing was re-packed yet - the replay would return the OLD weights' scores."""
+    if engine_now is not engine_then or pack_version_now != pack_version_then:
+        return ('the model was re-packed (load_state_dict / invalidate / set_trunk / .to() / a training step) after '
+                'capture(); capture again')
+    if trained_since_pack:
+        return ('a training step left the packed fp16-split copies of the head stale (refresh_head() does not clear '
+                'that); the next eval forward re-packs the model - capture again after it')
+    if not packed_is_current:
+        return ('a parameter or buffer was modified in place after it was packed; call refresh_head() if only the head '
+                '(fusion_module, w_det, w_link) changed, else run an eval forward (which re-packs) and capture again')
+    return None
+
+
+def check_graph_inputs(crops_buf, points_buf, crops, points):
+    """Host check of the inputs of a replay against the captured buffers, BEFORE anything is copied: ``copy_`` would
+    broadcast a [1,3,S,S] tensor over [Lt,3,S,S] and convert fp32 crops into a uint8 buffer (and back) without a word,
+    where the eager forward refuses both (Engine._check_crops).  None = keep what the buffer holds."""
+    for name, buf, t in (('crops', crops_buf, crops), ('points', points_buf, points)):
+        if t is None:
+            continue
+        if buf is None:
+            raise ValueError('%s given to a captured forward that was captured without %s' % (name, name))
+        if not torch.is_tensor(t) or t.shape != buf.shape or t.dtype != buf.dtype:
+            raise ValueError('%s of a captured forward must be a %s %s tensor (the shape and type it was captured with), '
+                             'got %s' % (name, buf.dtype, list(buf.shape),
+                                         '%s %s' % (t.dtype, list(t.shape)) if torch.is_tensor(t) else type(t).__name__))
+
+
 class GraphedForward:
     """See ``TrackingNet.capture``."""
 
@@ -338,6 +374,7 @@ class GraphedForward:
         self.plan = plan
         self.crops = None if crops is None else crops.clone()
         self.points = None if points is None else points.clone()
+        model._repack_if_trained()  # here, not inside the warm-up: the engine taken below is the one that gets captured
         eng = model.engine()
         with torch.no_grad():
             model.forward_batch(plan, self.crops, self.points)   # warm-up: workspace allocation, range-guard check
@@ -351,15 +388,20 @@ class GraphedForward:
         # re-allocates workspace buffers - a replay then reads valid memory.  It would still compute with the weights
         # of capture time, so a re-pack that could not be done in place (invalidate / load_state_dict / set_trunk / a
         # head refresh that changed shapes) marks the graph stale: __call__ raises instead of silently replaying it.
-        # refresh_head() itself copies into the packed tensors IN PLACE, so a graph follows an optimizer step.
+        # refresh_head() itself copies into the packed tensors IN PLACE, so a graph follows an optimizer step once
+        # refresh_head() was called; until then (parameters edited, nothing re-packed) the graph is stale as well.
         self._engine = eng
         self._model = model
         self._pack_version = model._pack_version
         self._keep = list(eng.ws.values()) + _collect_tensors(eng.P) + [eng.guard.block]
 
-    def stale(self):
+    def stale_reason(self):
         m = self._model
-        return m._engine is not self._engine or m._pack_version != self._pack_version
+        return graph_stale_reason(self._engine, m._engine, self._pack_version, m._pack_version,
+                                  m._trained_since_pack, m._packed_is_current())
+
+    def stale(self):
+        return self.stale_reason() is not None
 
     def check_range(self):
         """The trunk's range guard never runs inside a replay (its counter read synchronises): call this now and then
@@ -375,9 +417,10 @@ class GraphedForward:
         return sat, clamp, c11
 
     def __call__(self, crops=None, points=None):
-        if self.stale():
-            raise RuntimeError('mmmot_amd: this captured forward is stale - the model was re-packed (load_state_dict / '
-                               'invalidate / set_trunk / .to()) after capture(); capture again')
+        why = self.stale_reason()
+        if why is not None:
+            raise RuntimeError('mmmot_amd: this captured forward is stale - ' + why)
+        check_graph_inputs(self.crops, self.points, crops, points)
         if crops is not None and crops.data_ptr() != self.crops.data_ptr():
             self.crops.copy_(crops, non_blocking=True)
         if points is not None and points.data_ptr() != self.points.data_ptr():
@@ -697,9 +740,13 @@ class TrackingNet(nn.Module):
         """hipGraph of one ``forward_batch`` for a FIXED plan (the C-ABI entry points only launch: no allocation, no
         synchronisation, so the whole step is capturable).  Returns a ``GraphedForward``; its ``__call__(crops,
         points)`` copies the inputs into the captured buffers, replays the graph and returns the same per-sample
-        tuples as ``forward_batch`` (views of static output buffers, overwritten by the next replay).  Use it when
-        consecutive calls share the batch shape (throughput serving of fixed-size batches, the benchmark); a tracker
-        whose detections change every frame calls ``forward`` / ``forward_batch`` instead."""
+        tuples as ``forward_batch`` (views of static output buffers, overwritten by the next replay or forward of this
+        engine).  Use it when consecutive calls share the batch shape (throughput serving of fixed-size batches, the
+        benchmark); a tracker whose detections change every frame calls ``forward`` / ``forward_batch`` instead.
+        ``__call__`` refuses inputs of another shape or type than the captured ones (ValueError; None keeps a buffer)
+        and raises once the graph is stale: the model was re-packed, or a parameter / buffer was modified in place
+        and not packed again (``refresh_head()`` after a head-only edit lets the graph follow).  A replay cannot lower
+        its arithmetic: ``check_range()`` is its only range protection ("Captured forward")."""
         return GraphedForward(self, plan, crops, points)
 
     def trans(self):

@@ -255,3 +255,22 @@ def check_over_poison(m, call, what):
             poison_workspace(m.engine(), byte)
             assert_same_scores(scores(call()), want, '%s, workspace filled with 0x%02X' % (what, byte))
     return want
+
+
+# ---- in-place head edits a captured forward can follow (tests/test_graph_gpu.py, tests/test_batch_sizes_gpu.py) ----
+def edit_below_half_max(w, factor, gain=None):
+    """Scale, in place, the entries of the weight `w` ([N][K] after flattening) whose magnitude - times the per-row
+    `gain` the packing folds in, if any - is below HALF the largest one.  The largest folded magnitude stays what it
+    was, and with it the power-of-two scale of the weight's fp16-split copy (pack.hl16_weight_shift reads max |w| only):
+    the one python scalar a packed matrix carries."""
+    f = w.detach().flatten(1).double()
+    if gain is not None:
+        f = f * gain.double().view(-1, 1)
+    mask = (f.abs() < 0.5 * f.abs().max()).view_as(w)
+    assert 0 < int(mask.sum()) < mask.numel()
+    with torch.no_grad():
+        w.mul_(torch.where(mask, torch.full_like(w, factor), torch.ones_like(w)))
+
+
+def packed_scalars(P):
+    return {(s, k): v for s in ('fusion', 'w_det', 'w_link') for k, v in P[s].items() if not torch.is_tensor(v)}

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from common import TOL, build_model, get_case, golden
+from common import TOL, build_model, edit_below_half_max, get_case, golden, packed_scalars
 from mmmot_amd.synth import make_pair
 
 pytestmark = pytest.mark.gpu
@@ -66,16 +66,24 @@ def test_captured_forward_follows_refresh_head_and_goes_stale_on_repack():
     crops, points = x[0].to(DEV), x[1]['points'].reshape(-1, 3).to(DEV)
     g = m.capture(plan, crops, points)
     a = [t.clone() for t in (g(crops, points)[0][0], g(crops, points)[0][1][0])]
-    with torch.no_grad():
-        m.w_link.conv1[3].weight.mul_(1.01)
-        m.w_det[0].weight.mul_(0.99)
+    eng = m.engine()
+    scalars = packed_scalars(eng.P)
+    # edits that keep every by-value scalar of the packed head (final biases, power-of-two scales of the fp16-split
+    # copies): refresh_head() can copy everything in place and the graph must follow, unconditionally
+    edit_below_half_max(m.w_link.conv1[3].weight, 1.01)
+    bn = m.w_det[1]
+    edit_below_half_max(m.w_det[0].weight, 0.99, gain=bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps))
     assert not m.head_is_current()
+    with pytest.raises(RuntimeError, match='stale'):  # edited, not re-packed: a replay would return the old weights' scores
+        g(crops, points)
     m.refresh_head()
-    if not g.stale():   # scalars (final biases, hl16 scales) unchanged: the in-place path
-        b = g(crops, points)[0]
-        eager = m.forward_batch(plan, crops, points)[0]
-        assert torch.equal(b[0], eager[0]) and torch.equal(b[1][0], eager[1][0])
-        assert not torch.equal(b[1][0], a[1])
+    assert packed_scalars(eng.P) == scalars
+    assert not g.stale()
+    b = [(t[0].clone(), [t[1][0].clone()]) for t in g(crops, points)][0]
+    eager = m.forward_batch(plan, crops, points)[0]
+    assert m.engine() is eng
+    assert torch.equal(b[0], eager[0]) and torch.equal(b[1][0], eager[1][0])
+    assert not torch.equal(b[1][0], a[1]) and not torch.equal(b[0], a[0])
     assert g.check_range() == (0, 0, 0)
     m.invalidate()
     with pytest.raises(RuntimeError, match='stale'):
