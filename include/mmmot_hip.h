@@ -791,6 +791,49 @@ int mmmot_associate_chains(const float* det, const float* new_score, const float
  * four waves), 1 / 2 = one / four waves.  Results do not depend on it, bit for bit. */
 int mmmot_set_chain_variant(int variant);
 
+/* Association of WHOLE sequences (ortools_solve at len(det_split) = the sequence's length; csrc/assign_sequence.hip),
+ * exact, additive in ABI 10.  The program and its network are those of mmmot_associate_chains; one workgroup per
+ * sequence augments along successive shortest paths, each found by a label-correcting search that alternates a forward
+ * sweep over the frames with a backward sweep along the trajectories until a pass lowers no label (true costs, no
+ * potentials; ties to the smallest node index, the source first).  Results are deterministic and do not depend on the
+ * sequence's place in the batch, on the batch, or on the kernel variant.
+ *   det / new_score / end_score: fp32 [n_scores], sequence s's L = sum n_t scores at [score offset, + L);
+ *   link: fp32 [n_link], its row-major blocks link_0 (n_0 x n_1) .. link_{T-2} one after the other from its link offset;
+ *   seqs: int32 [B][MMMOT_SEQ_ROW] = (T, score offset, link offset, offset of n_0 in nts, output offset, workspace
+ *   offset in 8-byte units);  nts: int32 [n_nts], the n_t of every sequence;
+ *   limits: 2 <= T <= 4096, 0 <= n_t <= max_n <= 512 (an empty frame carries no trajectory across it), 1 <= L <= max_L
+ *   <= 65536, the link scores of a sequence < 2^31 - 1;
+ *   out: fp32 [n_out], sequence s's block [det L | new L | end L | link_0 | .. | link_{T-2}] at its output offset, the
+ *   0 / 1 values of ortools_solve, every element written;
+ *   ids: int32 [n_scores], at the score offset, every element of the sequence written: -1 where det = 0, else the trajectory's number - trajectories are numbered
+ *   0, 1, .. in the order of (first frame, detection index);
+ *   objective: fp64 [B];  info: int32 [B][4] = (status, trajectories, augmentations, passes);
+ *   max_T: the largest T of the launch (the frame starts and link offsets of a sequence are kept in LDS);
+ *   ws: workspace of ws_units 8-byte units, 8-byte aligned: per sequence (53 L + 7) / 8 units of search state (labels,
+ *   parents, used / pred / succ, a copy of the scores) from its workspace offset - read and written only when the state does not fit LDS.
+ * Every loop is bounded by the sizes: augmentations <= L, passes per augmentation <= 2L + 2, path walk <= 2L + 2.  A
+ * bound that is hit gives a NaN objective and status MMMOT_SEQ_EAUG / EPASS / EWALK (the block is still written in
+ * full, its content is then unspecified); a sequence outside the limits or the buffers gets a NaN objective and
+ * MMMOT_SEQ_ECONTRACT, and nothing else of it is read or written.  A NaN score means "variable absent"; infinite scores
+ * are clamped to +-1e30.  Returns MMMOT_EINVAL on a null pointer, B < 1, max_T outside [2, 4096], max_n outside [1, 512], max_L
+ * outside [1, 65536], a negative size or a misaligned workspace before any launch. */
+#define MMMOT_SEQ_ROW 6
+#define MMMOT_SEQ_MAXT 4096
+#define MMMOT_SEQ_MAXL 65536
+#define MMMOT_SEQ_OK 0
+#define MMMOT_SEQ_ECONTRACT 1
+#define MMMOT_SEQ_EAUG 2
+#define MMMOT_SEQ_EPASS 3
+#define MMMOT_SEQ_EWALK 4
+int mmmot_associate_sequences(const float* det, const float* new_score, const float* end_score, const float* link,
+                              const int* seqs, const int* nts, int B, int n_nts, int max_T, int max_n, int max_L,
+                              int n_scores, long long n_link, float* out, long long n_out, int* ids, double* objective,
+                              int* info, double* ws, long long ws_units, void* stream);
+/* tests / A-B: which kernel serves mmmot_associate_sequences - 0 = automatic (state in LDS when max_L <= 2304, one wave
+ * when max_n <= 16, else four), 1 / 2 = one / four waves with the state in the workspace, 3 / 4 = one / four waves with
+ * the state in LDS (max_L <= 2304, else MMMOT_EINVAL).  Results do not depend on it, bit for bit. */
+int mmmot_set_sequence_variant(int variant);
+
 /* Track IDs from pair assignments (reference tracking_model.py:218-292 assign_det_id, then :109-216 align_id, restated
  * by detection index; csrc/track_ids.hip), additive in ABI 10.  One workgroup walks the B CONSECUTIVE pairs of ONE
  * sequence in order; queued behind mmmot_associate_pairs it reads that call's `out` / `pairs` / `out_off` as they are.

@@ -23,11 +23,21 @@ chain), with ``gt=`` the loss-augmented objective of training-time inference:
 
 ``associate_chain_batch`` solves B chains in one launch and ``select_chain`` picks the ``test_mode`` rows of every link
 block of a ``TrackingNet(seq_len > 2)`` forward.
+
+``associate_sequence`` is the same program at the length of a whole sequence (T up to 4096 frames, L up to 65536
+detections; DESIGN.md, "Sequences"; csrc/assign_sequence.hip, one workgroup per sequence), and it can return the
+trajectory number of every detection: a unit of flow is a trajectory and therefore an ID.
+
+    from mmmot_amd.association import associate_sequence
+    assign_det, assign_links, assign_new, assign_end, ids, n_tracks = associate_sequence(
+        det, links, new, end, det_split, return_ids=True)
+
+``associate_sequence_batch`` solves B sequences in one launch.
 """
 import numpy as np
 import torch
 
-from . import torch_ops  # noqa: F401  (registers mmmot::associate and mmmot::associate_chains)
+from . import torch_ops  # noqa: F401  (registers mmmot::associate, mmmot::associate_chains and mmmot::associate_sequences)
 
 
 def split_of(det_split):
@@ -232,4 +242,125 @@ def associate_chain_batch(det_scores, link_scores, new_scores, end_scores, det_s
     out, obj = torch.ops.mmmot.associate_chains(cat(0), cat(1), cat(2), link, chains)
     res = [unpack_chain(out[o:o + chain_block_size(s)], s, d, [x.size() for x in l])
            for s, o, d, l in zip(splits, offs, det_scores, link_scores)]
+    return (res, obj) if return_objective else res
+
+
+# ---- whole sequences: one min-cost flow each ---------------------------------------------------------------------------
+class AssociationError(RuntimeError):
+    """The sequence solver ended a sequence at one of its loop bounds, or found it outside the launch contract: its
+    status word is in ``.status`` (include/mmmot_hip.h, MMMOT_SEQ_*), the sequence's place in the batch in ``.index``."""
+
+    def __init__(self, index, status):
+        names = {1: 'outside the launch contract', 2: 'augmentation bound hit', 3: 'pass bound hit',
+                 4: 'path walk bound hit'}
+        super().__init__('associate_sequence: sequence %d not solved: %s (status %d)'
+                         % (index, names.get(status, 'unknown status'), status))
+        self.index, self.status = index, status
+
+
+SEQ_MAX_N = torch_ops.MAX_ASSOC
+
+
+def sequence_of(det_split):
+    """[n_0 .. n_{T-1}] of a ``det_split`` of 2 <= T <= 4096 frames of at most 512 detections, L <= 65536."""
+    split = [int(n) for n in det_split]
+    if len(split) < 2:
+        raise ValueError('associate_sequence: det_split must have at least 2 entries, got %d' % len(split))
+    if len(split) > torch_ops.SEQ_MAX_T:
+        raise ValueError('associate_sequence: at most %d frames, got %d' % (torch_ops.SEQ_MAX_T, len(split)))
+    if min(split) < 0 or max(split) > SEQ_MAX_N:
+        raise ValueError('associate_sequence: every frame needs 0 <= n_t <= %d detections' % SEQ_MAX_N)
+    if sum(split) > torch_ops.SEQ_MAX_L:
+        raise ValueError('associate_sequence: at most %d detections, got %d' % (torch_ops.SEQ_MAX_L, sum(split)))
+    return split
+
+
+def sequences_table(splits):
+    """(seqs CPU int32 [B, 4] = (T, score offset, link offset, offset of n_0 in nts), nts CPU int32 flat, output
+    offsets, score offsets) of sequences packed one after the other."""
+    rows, nts, so, lo, oo, offs, sos = [], [], 0, 0, 0, [], []
+    for split in splits:
+        K = sum(a * b for a, b in zip(split[:-1], split[1:]))
+        rows.append([len(split), so, lo, len(nts)])
+        nts.extend(split)
+        offs.append(oo)
+        sos.append(so)
+        so += sum(split)
+        lo += K
+        oo += 3 * sum(split) + K
+    if lo >= 2 ** 31 - 1 or oo >= 2 ** 31 - 1:
+        raise ValueError('associate_sequence: the link scores of one launch must number fewer than 2^31')
+    return torch.tensor(rows, dtype=torch.int32), torch.tensor(nts, dtype=torch.int32), offs, sos
+
+
+def _raise_status(info):
+    """``info``: host int32 [B, 4]; raises AssociationError for the first sequence whose status word is set"""
+    bad = np.nonzero(info[:, 0])[0]
+    if bad.size:
+        raise AssociationError(int(bad[0]), int(info[bad[0], 0]))
+
+
+def split_ids(ids, split):
+    """flat per-detection IDs -> per frame an int64 array (views of one int64 copy)"""
+    ids = ids.to(torch.int64)
+    return list(ids.split(split))
+
+
+def associate_sequence(det_score, link_scores, new_score, end_score, det_split, gt=None, return_ids=False):
+    """``ortools_solve(det_score, link_score, new_score, end_score, det_split, gt)`` at the length of a whole sequence
+    (2 <= T <= 4096 frames of at most 512 detections, L <= 65536): the arguments, the results, the shapes, dtypes and the
+    host / device rules of ``associate_chain``.  With ``return_ids`` also the per-frame int64 trajectory numbers (-1: not
+    kept; trajectories numbered in the order of first frame, then detection index) and the trajectory count.  Raises
+    AssociationError when the solver reports a status (one host read of four words per call)."""
+    split = sequence_of(det_split)
+    _check_chain(det_score, link_scores, new_score, end_score, split)
+    L = sum(split)
+    if L == 0:
+        z = det_score.new_zeros(det_score.size())
+        res = (z, [det_score.new_zeros(l.size()) for l in link_scores], z.clone(), z.clone())
+        empty = [torch.zeros(0, dtype=torch.int64, device=det_score.device) for _ in split]
+        return res + (empty, 0) if return_ids else res
+    flat = _flat_scores(det_score, link_scores, new_score, end_score, gt)
+    on_host = not det_score.is_cuda
+    if on_host:
+        flat = flat.to('cuda')  # one host-to-device copy
+    seqs, nts, _, _ = sequences_table([split])
+    out, ids, _, info = torch.ops.mmmot.associate_sequences(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:],
+                                                            seqs, nts)
+    info = info.cpu().numpy()
+    _raise_status(info)
+    if on_host:
+        out, ids = out.cpu(), ids.cpu()
+    res = unpack_chain(out, split, det_score, [l.size() for l in link_scores])
+    return res + (split_ids(ids, split), int(info[0, 1])) if return_ids else res
+
+
+def associate_sequence_batch(det_scores, link_scores, new_scores, end_scores, det_splits, gts=None,
+                             return_objective=False, return_ids=False):
+    """B sequences in one launch, one workgroup each.  Per sequence s: det_scores[s] / new_scores[s] / end_scores[s]
+    [L_s], link_scores[s] = [link 1 x n_t x n_{t+1} ...], all on one device; ``gts``: None or per sequence a ``gt`` tuple
+    (or None).  Returns the list of ortools_solve tuples (on that device) - each followed by its per-frame IDs and its
+    trajectory count with ``return_ids`` - and the fp64 optima [B] when ``return_objective``."""
+    splits = [sequence_of(s) for s in det_splits]
+    if not splits:
+        raise ValueError('associate_sequence_batch: no sequences')
+    if any(sum(s) == 0 for s in splits):
+        raise ValueError('associate_sequence_batch: every sequence needs a detection (use associate_sequence for empty '
+                         'sequences)')
+    gts = gts if gts is not None else [None] * len(splits)
+    flats = []
+    for d, l, n, e, s, g in zip(det_scores, link_scores, new_scores, end_scores, splits, gts):
+        _check_chain(d, l, n, e, s)
+        flats.append(_flat_scores(d, l, n, e, g))
+    Ls = [sum(s) for s in splits]
+    seqs, nts, offs, sos = sequences_table(splits)
+    cat = lambda k: torch.cat([f[k * L:(k + 1) * L] for f, L in zip(flats, Ls)])
+    link = torch.cat([f[3 * L:] for f, L in zip(flats, Ls)])
+    out, ids, obj, info = torch.ops.mmmot.associate_sequences(cat(0), cat(1), cat(2), link, seqs, nts)
+    info = info.cpu().numpy()
+    _raise_status(info)
+    res = []
+    for i, (s, o, so, d, l) in enumerate(zip(splits, offs, sos, det_scores, link_scores)):
+        r = unpack_chain(out[o:o + chain_block_size(s)], s, d, [x.size() for x in l])
+        res.append(r + (split_ids(ids[so:so + sum(s)], s), int(info[i, 1])) if return_ids else r)
     return (res, obj) if return_objective else res

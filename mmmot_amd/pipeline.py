@@ -49,7 +49,9 @@ All orders and modes, pairs and windows, share their steps.  ``queue_hand_off`` 
 forward of one pair or window, or a batch of them, and returns a tracker_glue.HandOff; ``finish_hand_off`` is its host
 copy - the one place the host waits - with one result (scores, assignment, ids) each, and ``_deliver`` turns a result
 into the callbacks, ``stats`` and the returned shape.  ``run`` is one loop (``_run_online``) over
-``tracks.window_starts`` - for ``window=2`` the list of pairs - and ``run_offline`` one loop over batches of them.  A pair
+``tracks.window_starts`` - for ``window=2`` the list of pairs - and ``run_offline`` one loop over batches of them
+(``_offline_frames`` and ``_offline_forwards``, which ``run_global`` shares: it keeps the batches' selected rows on the
+device and decides the whole sequence with one min-cost flow, association.associate_sequence).  A pair
 differs from a window in three places: stage A aligns a frame to the one before it (a window aligns at launch;
 ``run_offline`` aligns K frames per launch in front of the trunk), the forward (``launch_pair`` with the stage events,
 ``launch_pair_cached`` on cached rows; ``launch_window`` otherwise), and the recompute check of ``reuse_appearance``.
@@ -85,7 +87,7 @@ import torch
 from .crops import crop_resize_u8, crop_resize_u8_multi
 from . import ego
 from .points import align_points_batched, prep_points_batched
-from .association import select, select_chain
+from .association import _raise_status, select, select_chain, sequences_table, unpack_chain
 from .tracker_glue import queue_scores, queue_solve, queue_solve_chains
 from .tracks import TrackState, TrackStates, merge_chain_tracks, merge_tracks, window_starts
 
@@ -513,16 +515,35 @@ class SequencePipeline:
         if self.window == 2:  # as in ``run``: the pairs of the frames that hold a detection
             feeds, idx, (on_scores, on_assign, on_tracks) = _skip_empty(feeds, (on_scores, on_assign, on_tracks))
         self._start_tracks(feeds)
-        frames = [self.prepare(f) for f in feeds]
+        frames = self._offline_frames(feeds, K, moving)
         if len(frames) < 2:
             self.tracks = self._account_empty(self.tracks, idx, n_frames, False)
             return []
-        if moving and self.window == 2:  # one align launch per K frames, queued in front of their trunk launches
+        res = []
+        for grp, outs in self._offline_forwards(frames, feeds, moving, B):
+            done = self.finish_hand_off(self.queue_hand_off(outs, grp))
+            for (s, fr), r in zip(grp, done):
+                res.append(self._deliver(s, len(fr), r, on_scores, on_assign, on_tracks))
+        self.tracks = self._account_empty(self.tracks, idx, n_frames, True)
+        return res
+
+    def _offline_frames(self, feeds, K, moving):
+        """the offline orders up to the rows: stage A of every frame, for pairs of a moving sequence one align launch per
+        K frames in front of their trunk launches, then the trunk over K frames per launch sequence (with fewer than two
+        frames: stage A only, nothing is scored)"""
+        frames = [self.prepare(f) for f in feeds]
+        if len(frames) < 2:
+            return frames
+        if moving and self.window == 2:
             for t0 in range(1, len(frames), K):
                 self._align_group(frames, feeds, t0, min(t0 + K, len(frames)))
         self._encode_all(frames, K)  # waits for stage A of every frame
+        return frames
+
+    def _offline_forwards(self, frames, feeds, moving, B):
+        """the offline orders' forwards: per batch of B pairs or windows (its groups [(first frame, frames)], the device
+        outputs of one ``forward_batch`` on the rows)"""
         wins = window_starts(len(frames), self.window)
-        res = []
         for g0 in range(0, len(wins), B):
             grp = [(s, frames[s:s + k]) for s, k in wins[g0:g0 + B]]
             plan = self.model.make_plan([([f['n'] for f in fr], self._window_split(fr)) for _, fr in grp], self.size)
@@ -533,11 +554,92 @@ class SequencePipeline:
             with torch.no_grad():
                 outs = self.model.forward_batch(plan, None, torch.cat(points),
                                                 appearance=torch.cat([f['rows'].rows for _, fr in grp for f in fr]))
-            done = self.finish_hand_off(self.queue_hand_off(outs, grp))
-            for (s, fr), r in zip(grp, done):
-                res.append(self._deliver(s, len(fr), r, on_scores, on_assign, on_tracks))
-        self.tracks = self._account_empty(self.tracks, idx, n_frames, True)
+            yield grp, outs
+
+    def run_global(self, feeds, frames_per_encode=16, pairs_per_forward=8):
+        """The whole sequence decided at once: ``run_offline``'s stage A, alignment, trunk and batched pair forwards, then
+        ONE min-cost flow over all frames (association.associate_sequence; DESIGN section 11, "Sequences") in place of a
+        solve per pair and the ID walk - a unit of flow is a trajectory, its number the track ID.  Needs ``window == 2``.
+        Per batch only the ``test_mode`` rows stay on the device; after the last batch the sequence's scores are
+        assembled there - for the kept frames f_0 .. f_{K-1} and pair p = (f_p, f_{p+1}): det and new of frame 0 from
+        pair 0's first half, of frame t >= 1 from pair t-1's second half; end of frame t <= K-2 from pair t's first half,
+        of frame K-1 from pair K-2's second half; link_t = pair t's block (the layout a K-frame eval forward returns) -
+        then one launch solves them and one copy brings everything back.  Returns a ``GlobalResult`` (``.scores`` and
+        ``.assignment`` in ``ortools_solve`` order, ``.ids`` per kept frame, ``.n_tracks``, ``.objective``) and fills
+        ``self.tracks`` at the sequence's own frame indices, whatever ``track`` is (``_account_empty`` spreads them only
+        for ``track=True``, so the frames left out are counted here).  With fewer than two frames that
+        hold a detection nothing is solved, as in ``run_offline``: returns None and the tracks stay -1."""
+        if self.window != 2:
+            raise ValueError('SequencePipeline.run_global assembles the scores of frame pairs: window must be 2, got %d'
+                             % self.window)
+        K, B = int(frames_per_encode), int(pairs_per_forward)
+        if K < 1 or B < 1:
+            raise ValueError('frames_per_encode and pairs_per_forward must be >= 1')
+        moving = _check_poses(feeds)
+        n_frames = len(feeds)
+        feeds, idx, _ = _skip_empty(feeds, (None, None, None))
+        tracks = [np.full(len(f.dets['bbox']), -1, np.int64) for f in feeds]
+        frames = self._offline_frames(feeds, K, moving)
+        res = None
+        if len(frames) >= 2:
+            tm, rows = self.model.test_mode, []
+            for grp, outs in self._offline_forwards(frames, feeds, moving, B):
+                # the selected rows only: the batch's other rows go back to the allocator
+                rows += [tuple(x.reshape(-1).clone() for x in (d, l[0], n, e))
+                         for d, l, n, e in (select(o[0], o[1], o[2], o[3], tm) for o in outs)]
+                self.stats['pairs'] += len(grp)
+            res = solve_global(rows, [f['n'] for f in frames])
+            tracks = res.ids
+        if len(idx) < n_frames:  # the frames left out: counted, and as encoded too once the trunk has run (``_account_empty``)
+            self.stats['empty_frames'] = self.stats.get('empty_frames', 0) + n_frames - len(idx)
+            if len(frames) >= 2:
+                self.stats['encoded_frames'] += n_frames - len(idx)
+        self.tracks = _spread_tracks(tracks, idx, n_frames)
         return res
+
+
+class GlobalResult:
+    """What ``SequencePipeline.run_global`` returns, on the host: ``scores`` = (det L, [link 1 x n_t x n_{t+1} ...],
+    new L, end L) of the kept frames, ``assignment`` the 0 / 1 tensors of the same shapes (both in ``ortools_solve``
+    order), ``ids`` per kept frame the int64 track IDs (-1: rejected), ``n_tracks``, ``objective`` (fp64), ``split``."""
+
+    def __init__(self, scores, assignment, ids, n_tracks, objective, split):
+        self.scores, self.assignment, self.ids = scores, assignment, ids
+        self.n_tracks, self.objective, self.split = n_tracks, objective, split
+
+
+def assemble_rows(rows, counts):
+    """The sequence's flat scores [det L | new L | end L | link_0 | ..] on the device from the selected rows of its
+    consecutive pairs, ``rows[p]`` = (det, link, new, end) of pair (p, p + 1), flat; the convention of ``run_global``."""
+    n = [int(c) for c in counts]
+    last = len(n) - 2
+    det = [rows[0][0][:n[0]]] + [r[0][n[p]:] for p, r in enumerate(rows)]
+    new = [rows[0][2][:n[0]]] + [r[2][n[p]:] for p, r in enumerate(rows)]
+    end = [r[3][:n[p]] for p, r in enumerate(rows)] + [rows[last][3][n[last]:]]
+    return torch.cat(det + new + end + [r[1] for r in rows])
+
+
+def solve_global(rows, counts):
+    """assemble, one ``associate_sequences`` launch, one copy; raises association.AssociationError on a status word"""
+    split = [int(c) for c in counts]
+    L = sum(split)
+    flat = assemble_rows(rows, split).to(torch.float32)
+    seqs, nts, _, _ = sequences_table([split])
+    out, ids, obj, info = torch.ops.mmmot.associate_sequences(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:],
+                                                              seqs, nts)
+    # the fp64 objective first: every part then starts at a multiple of its element size, whatever L and the link count
+    parts = [obj, flat, out, ids, info.reshape(-1)]
+    host = torch.cat([x.view(torch.uint8) for x in parts]).cpu()  # the one copy
+    o, got = 0, []
+    for x in parts:
+        got.append(host[o:o + x.numel() * x.element_size()].view(x.dtype))
+        o += x.numel() * x.element_size()
+    got = got[1:] + got[:1]  # flat, out, ids, info, objective
+    _raise_status(got[3].view(1, 4).numpy())
+    sizes = [(1, a, b) for a, b in zip(split[:-1], split[1:])]
+    like = got[0][0:L]
+    return GlobalResult(unpack_chain(got[0], split, like, sizes), unpack_chain(got[1], split, like, sizes),
+                        [i.numpy() for i in got[2].to(torch.int64).split(split)], int(got[3][1]), float(got[4][0]), split)
 
 
 def lockstep_steps(lens):

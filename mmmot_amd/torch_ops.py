@@ -294,6 +294,104 @@ _LIB.impl('associate_chains', _associate_chains, 'CUDA')
 _LIB.impl('associate_chains', _associate_chains_meta, 'Meta')
 
 
+# ---- whole-sequence association (mmmot_amd/association.py; csrc/assign_sequence.hip) --------------------------------
+#   mmmot::associate_sequences(Tensor det, Tensor new, Tensor end, Tensor link, Tensor seqs, Tensor nts) -> Tensor[]
+#       B sequences of 2 .. 4096 frames solved exactly in one launch (mmmot_associate_sequences).  det / new / end /
+#       link: flat fp32 device tensors; seqs: a CPU int32 [B, 4] table (T, score offset, link offset, offset of n_0 in
+#       nts); nts: a CPU int32 flat array of the n_t - host data, like the chain table.  Returns [out, ids, objective,
+#       info]: out fp32, sequence s's [det L | new L | end L | link_0 | .. | link_{T-2}] one after the other; ids int32
+#       with the layout of det (-1: not kept, else the trajectory's number); objective fp64 [B]; info int32 [B, 4]
+#       (status, trajectories, augmentations, passes).  The search state lives in a workspace allocated here.
+SEQ_MAX_T = 4096
+SEQ_MAX_L = 65536
+SEQ_ROW = 6
+SEQ_STATE_BYTES = 53
+
+
+def sequence_layout(seqs, nts, n_scores=None, n_link=None):
+    """(total output floats, int64 [B] output offsets, int64 [B] workspace offsets in 8-byte units, workspace units,
+    max n_t, max L, max T) of a sequence table; checks the table, and against the sizes of the score / link buffers when given
+    (the kernel reads what the table says)."""
+    if seqs.device.type != 'cpu' or seqs.dtype != torch.int32 or seqs.dim() != 2 or seqs.shape[1] != 4:
+        raise ValueError('mmmot::associate_sequences: seqs must be a CPU int32 [B, 4] table (T, score offset, link '
+                         'offset, offset of n_0 in nts)')
+    if nts.device.type != 'cpu' or nts.dtype != torch.int32 or nts.dim() != 1:
+        raise ValueError('mmmot::associate_sequences: nts must be a CPU int32 flat array of the n_t')
+    if seqs.shape[0] < 1:
+        raise ValueError('mmmot::associate_sequences: no sequences')
+    t = seqs.numpy().astype(np.int64)
+    n = nts.numpy().astype(np.int64)
+    T, so, lo, no = t[:, 0], t[:, 1], t[:, 2], t[:, 3]
+    if T.min() < 2 or T.max() > SEQ_MAX_T:
+        raise ValueError('mmmot::associate_sequences: every sequence needs 2 <= T <= %d frames' % SEQ_MAX_T)
+    if min(so.min(), lo.min(), no.min()) < 0:
+        raise ValueError('mmmot::associate_sequences: negative offset in the sequence table')
+    if (no + T).max() > n.size:
+        raise ValueError('mmmot::associate_sequences: a sequence reads past the end of nts')
+    if n.size and (n.min() < 0 or n.max() > MAX_ASSOC):
+        raise ValueError('mmmot::associate_sequences: every frame needs 0 <= n_t <= %d' % MAX_ASSOC)
+    L = np.empty(len(T), np.int64)
+    K = np.empty(len(T), np.int64)
+    max_n = 0
+    for s in range(len(T)):
+        ns = n[no[s]:no[s] + T[s]]
+        L[s], K[s], max_n = ns.sum(), (ns[:-1] * ns[1:]).sum(), max(max_n, int(ns.max()))
+    if L.min() < 1 or L.max() > SEQ_MAX_L:
+        raise ValueError('mmmot::associate_sequences: every sequence needs 1 <= L <= %d detections' % SEQ_MAX_L)
+    if n_scores is not None and (so + L).max() > n_scores:
+        raise ValueError('mmmot::associate_sequences: a sequence reads past the end of the score buffers')
+    if n_link is not None and (lo + K).max() > n_link:
+        raise ValueError('mmmot::associate_sequences: a sequence reads past the end of the link buffer')
+    sizes = 3 * L + K
+    total = int(sizes.sum())
+    if total >= 2 ** 31 - 1 or int((lo + K).max()) >= 2 ** 31 - 1:
+        raise ValueError('mmmot::associate_sequences: link scores or output block exceed 32-bit offsets')
+    units = (SEQ_STATE_BYTES * L + 7) // 8
+    return (total, torch.from_numpy(np.cumsum(sizes) - sizes), torch.from_numpy(np.cumsum(units) - units),
+            int(units.sum()), max_n, int(L.max()), int(T.max()))
+
+
+def _associate_sequences(det, new, end, link, seqs, nts):
+    n_scores = min(int(det.numel()), int(new.numel()), int(end.numel()))
+    total, off, woff, units, max_n, max_L, max_T = sequence_layout(seqs, nts, n_scores, int(link.numel()))
+    if not _ASSOC_OPS:
+        from .ops import HipOps
+        _ASSOC_OPS.append(HipOps())
+    B, NT = int(seqs.shape[0]), int(nts.numel())
+    if link.numel() == 0:  # no sequence has a link: never read, but not a null pointer
+        link = det
+    # sequence table + the n_t in one pinned block: an asynchronous copy (a pageable one would wait for the stream)
+    host = torch.empty(SEQ_ROW * B + NT, dtype=torch.int32, pin_memory=True)
+    rows = host[:SEQ_ROW * B].view(B, SEQ_ROW)
+    rows[:, :4] = seqs
+    rows[:, 4] = off
+    rows[:, 5] = woff
+    host[SEQ_ROW * B:] = nts
+    table = host.to(det.device, non_blocking=True)
+    out = torch.empty(total, dtype=torch.float32, device=det.device)
+    ids = torch.empty(n_scores, dtype=torch.int32, device=det.device)
+    obj = torch.empty(B, dtype=torch.float64, device=det.device)
+    info = torch.empty((B, 4), dtype=torch.int32, device=det.device)
+    ws = torch.empty(units, dtype=torch.float64, device=det.device)
+    _ASSOC_OPS[0].associate_sequences(det.contiguous(), new.contiguous(), end.contiguous(), link.contiguous(),
+                                      table[:SEQ_ROW * B], table[SEQ_ROW * B:], B, max_T, max_n, max_L, out, ids, obj, info,
+                                      ws)
+    return [out, ids, obj, info]
+
+
+def _associate_sequences_meta(det, new, end, link, seqs, nts):
+    total = sequence_layout(seqs, nts)[0]
+    B = int(seqs.shape[0])
+    n_scores = min(int(det.numel()), int(new.numel()), int(end.numel()))
+    return [det.new_empty((total,), dtype=torch.float32), det.new_empty((n_scores,), dtype=torch.int32),
+            det.new_empty((B,), dtype=torch.float64), det.new_empty((B, 4), dtype=torch.int32)]
+
+
+_LIB.define('associate_sequences(Tensor det, Tensor new, Tensor end, Tensor link, Tensor seqs, Tensor nts) -> Tensor[]')
+_LIB.impl('associate_sequences', _associate_sequences, 'CUDA')
+_LIB.impl('associate_sequences', _associate_sequences_meta, 'Meta')
+
+
 # ---- track IDs (mmmot_amd/tracks.py; csrc/track_ids.hip) -------------------------------------------------------------
 #   mmmot::track_ids(Tensor blocks, Tensor pairs, Tensor frame_idx, Tensor(a!) state, int max_nm) -> Tensor
 #       Track IDs of B consecutive pairs of ONE sequence (mmmot_track_ids) from the solver's output blocks: blocks = the

@@ -18,6 +18,17 @@ host stand-ins for CBC, scipy's linprog and milp on the literal program (tests/a
 <out>/bench_assign_chain.json.
 
     python tools/bench_assign.py --chain --out <dir> [--iters 200]
+
+``--sequence`` measures the whole-sequence association (csrc/assign_sequence.hip): HIP-event time per launch (median
+of --iters) of mmmot_associate_sequences at B = 1 and B = 21 on two shapes of T = 1000 frames - "planted": n_t uniform in
+5 .. 15, hidden tracks that die with probability 1 / 40 per frame, kind eval (det ~ N(1, 1), new / end ~ N(-1, 1) with the
+eval zeros, planted links ~ N(2, 1), all others ~ N(-2, 1)); "random": n_t in 0 .. 4, standard normal scores, kind eval,
+the long case of tests/test_association_sequence_gpu.py - with the augmentations and passes of sequence 0.  Beside them,
+on the same box: the host's linprog on the literal program (tests/association_chain_ref.lp_route) with and without the
+construction of the program, and mmmot_associate_pairs over the sequence's T - 1 pairs in one launch (empty frames left
+out).  Writes <out>/bench_assign_sequence.json.
+
+    python tools/bench_assign.py --sequence --out <dir> [--iters 50] [--shapes planted,random] [--batches 1,21]
 """
 import argparse
 import json
@@ -162,6 +173,108 @@ def chain_main(args):
     print(json.dumps(res))
 
 
+def planted_sequence(rng, T=1000, lo=5, hi=15, mean_len=40):
+    """the "planted" shape of --sequence: (split, (det, new, end, links))"""
+    live, nxt, frames = [], 0, []
+    for t in range(T):
+        live = [h for h in live if rng.random() > 1.0 / mean_len]
+        target = int(rng.integers(lo, hi + 1))
+        live = [live[i] for i in sorted(rng.permutation(len(live))[:target])]
+        while len(live) < target:
+            live.append(nxt)
+            nxt += 1
+        frames.append([live[i] for i in rng.permutation(len(live))])
+    split = [len(f) for f in frames]
+    L = sum(split)
+    g = lambda mu, *s: (mu + rng.standard_normal(s)).astype(np.float32)
+    det, new, end = g(1, L), g(-1, L), g(-1, L)
+    new[:split[0]] = 0
+    end[L - split[-1]:] = 0
+    links = []
+    for t in range(T - 1):
+        l = g(-2, split[t], split[t + 1])
+        pos = {h: k for k, h in enumerate(frames[t + 1])}
+        for j, h in enumerate(frames[t]):
+            if h in pos:
+                l[j, pos[h]] = g(2)
+        links.append(l)
+    return split, (det, new, end, links)
+
+
+def random_sequence(rng, T=1000, hi=5):
+    from association_chain_ref import random_chain
+    split = [int(n) for n in rng.integers(0, hi, T)]
+    return split, random_chain(rng, split, 1.0, 'eval')
+
+
+def sequence_device_ms(ops, insts, iters):
+    """(median ms per launch, info of sequence 0)"""
+    from mmmot_amd.association import sequences_table
+    from mmmot_amd.torch_ops import SEQ_ROW, sequence_layout
+    seqs, nts, _, _ = sequences_table([s for s, _ in insts])
+    cat = lambda k: torch.from_numpy(np.concatenate([sc[k].reshape(-1) for _, sc in insts])).cuda()
+    det, new, end = cat(0), cat(1), cat(2)
+    link = torch.from_numpy(np.concatenate([l.reshape(-1) for _, sc in insts for l in sc[3]])).cuda()
+    total, off, woff, units, max_n, max_L, max_T = sequence_layout(seqs, nts, det.numel(), link.numel())
+    B = len(insts)
+    rows = torch.cat([seqs, off.to(torch.int32)[:, None], woff.to(torch.int32)[:, None]], 1)
+    table = torch.cat([rows.reshape(-1), nts]).cuda()
+    out = torch.empty(total, dtype=torch.float32, device='cuda')
+    ids = torch.empty(det.numel(), dtype=torch.int32, device='cuda')
+    obj = torch.empty(B, dtype=torch.float64, device='cuda')
+    info = torch.empty((B, 4), dtype=torch.int32, device='cuda')
+    ws = torch.empty(units, dtype=torch.float64, device='cuda')
+    run = lambda: ops.associate_sequences(det, new, end, link, table[:SEQ_ROW * B], table[SEQ_ROW * B:], B, max_T, max_n,
+                                          max_L, out, ids, obj, info, ws)
+    run()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return statistics.median(ts), [int(x) for x in info[0].cpu()], float(obj[0].cpu())
+
+
+def sequence_main(args):
+    from association_chain_ref import _program, lp_route
+    ops = HipOps()
+    res = {'iters': args.iters, 'rows': []}
+    makers = {'planted': planted_sequence, 'random': random_sequence}
+    for name in args.shapes.split(','):
+        first = makers[name](np.random.default_rng(1000))
+        split, sc = first
+        row = {'shape': name, 'T': len(split), 'L': sum(split)}
+        for B in [int(b) for b in args.batches.split(',')]:
+            insts = [first] + [makers[name](np.random.default_rng(1000 + b)) for b in range(1, B)]
+            ms, info, obj = sequence_device_ms(ops, insts, args.iters)
+            row['B%d_ms_per_launch' % B] = round(ms, 3)
+            row['status'], row['tracks'], row['augmentations'], row['passes'] = info
+            print(json.dumps(row), flush=True)
+        t0 = time.perf_counter()
+        _program(sc[0], sc[1], sc[2], sc[3], split)
+        t1 = time.perf_counter()
+        _, wobj = lp_route(sc[0], sc[1], sc[2], sc[3], split)
+        t2 = time.perf_counter()
+        row['host_program_ms'], row['host_lp_route_ms'] = round((t1 - t0) * 1e3, 1), round((t2 - t1) * 1e3, 1)
+        row['host_solve_only_ms'] = round((t2 - t1 - (t1 - t0)) * 1e3, 1)
+        row['objective_matches_host'] = bool(abs(obj - wobj) <= 1e-9 * max(1.0, abs(wobj)))
+        st = np.concatenate([[0], np.cumsum(split)])
+        pair_insts = [(split[t], split[t + 1], (sc[0][st[t]:st[t + 2]], sc[1][st[t]:st[t + 2]], sc[2][st[t]:st[t + 2]],
+                                                  sc[3][t])) for t in range(len(split) - 1) if split[t] and split[t + 1]]
+        row['pairs'] = len(pair_insts)
+        row['pair_solver_ms_per_launch'] = round(device_ms(ops, pair_insts, 0, max(args.iters, 50)), 4)
+        res['rows'].append(row)
+        print(json.dumps(row), flush=True)
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_assign_sequence.json'), 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def host_ms(fn, inst, reps):
     N, M, (det, new, end, link) = inst
     ts = []
@@ -201,9 +314,14 @@ def main():
     ap.add_argument('--host-reps', type=int, default=3)
     ap.add_argument('--no-pipeline', action='store_true')
     ap.add_argument('--chain', action='store_true', help='measure the chain association instead')
+    ap.add_argument('--sequence', action='store_true', help='measure the whole-sequence association instead')
+    ap.add_argument('--shapes', default='planted,random', help='--sequence: which of its shapes')
+    ap.add_argument('--batches', default='1,21', help='--sequence: sequences per launch')
     args = ap.parse_args()
     if args.chain:
         return chain_main(args)
+    if args.sequence:
+        return sequence_main(args)
     from association_ref import lsa_route, milp_route
     ops = HipOps()
     res = {'device_ms_per_launch': [], 'host_ms_per_pair': []}
