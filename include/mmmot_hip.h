@@ -834,6 +834,41 @@ int mmmot_associate_sequences(const float* det, const float* new_score, const fl
  * the state in LDS (max_L <= 2304, else MMMOT_EINVAL).  Results do not depend on it, bit for bit. */
 int mmmot_set_sequence_variant(int variant);
 
+/* Association of whole sequences with SKIP LINKS (csrc/assign_sequence_gap.hip), exact, additive in ABI 10: the program
+ * of mmmot_associate_sequences with link blocks link^g_t (n_t x n_{t+g}) for every gap g = 1 .. max_gap, t = 0 ..
+ * T-1-g, so that a trajectory may miss up to max_gap - 1 frames (and may cross an empty frame).  For every detection v
+ * of frame t: det_v = new_v + sum_g sum_j link^g_{t-g}[j][v] = end_v + sum_g sum_k link^g_t[v][k], all variables 0 / 1,
+ * maximise sum score * variable.  The network gains the arcs out(t, j) -> in(t + g, k); the search is that of
+ * mmmot_associate_sequences - a forward sweep relaxes in(k) of frame t over the source and over out(j) of the frames
+ * t-1 .. t-max_gap, a backward sweep follows pred, which may lie up to max_gap frames back - with its tie rule (the
+ * smallest node index, the source first: the earlier frame wins), its bounds and its status words.  With max_gap = 1 the
+ * results are those of mmmot_associate_sequences, bit for bit.  Results are deterministic and do not depend on the
+ * sequence's place in the batch, on the batch, or on the kernel variant.
+ *   det / new_score / end_score / seqs / nts / ids / objective / info: as mmmot_associate_sequences;
+ *   link: fp32 [n_link], from the sequence's link offset its row-major blocks gap by gap: link^1_0 .. link^1_{T-2}, then
+ *   link^2_0 .. link^2_{T-3}, .. link^G_0 .. link^G_{T-1-G}; a block with n_t = 0 or n_{t+g} = 0 has no elements;
+ *   out: fp32 [n_out], sequence s's block [det L | new L | end L | the link blocks in the order of `link`] at its output
+ *   offset, 0 / 1 values, every element written;
+ *   limits: those of mmmot_associate_sequences, 1 <= max_gap <= MMMOT_SEQ_MAXGAP, max_gap < T for every sequence, the
+ *   link scores of a sequence (all gaps) < 2^31 - 1;
+ *   ws: workspace of ws_units 8-byte units, 8-byte aligned: per sequence, from its workspace offset, (max_gap T + 1) / 2
+ *   units for the max_gap x T table of block offsets, then (53 L + 7) / 8 units of search state.  The table is read and
+ *   written there only when it does not fit LDS beside the frame starts and the state (the dynamic LDS request never
+ *   exceeds that of mmmot_associate_sequences), the state only when L > 2304 or the variant says so.
+ * A bound that is hit gives a NaN objective and MMMOT_SEQ_EAUG / EPASS / EWALK; a sequence outside the limits or the
+ * buffers - max_gap >= T included - gets a NaN objective and MMMOT_SEQ_ECONTRACT, and nothing else of it is read or
+ * written.  A NaN score means "variable absent"; infinite scores are clamped to +-1e30.  Returns MMMOT_EINVAL on a null
+ * pointer, B < 1, max_T outside [2, 4096], max_n outside [1, 512], max_L outside [1, 65536], max_gap outside [1, 8] or
+ * >= max_T, a negative size or a misaligned workspace before any launch. */
+#define MMMOT_SEQ_MAXGAP 8
+int mmmot_associate_sequences_gap(const float* det, const float* new_score, const float* end_score, const float* link,
+                                  const int* seqs, const int* nts, int B, int n_nts, int max_T, int max_n, int max_L,
+                                  int max_gap, int n_scores, long long n_link, float* out, long long n_out, int* ids,
+                                  double* objective, int* info, double* ws, long long ws_units, void* stream);
+/* tests / A-B: which kernel serves mmmot_associate_sequences_gap - the variants of mmmot_set_sequence_variant.  Results
+ * do not depend on it, bit for bit. */
+int mmmot_set_sequence_gap_variant(int variant);
+
 /* Track IDs from pair assignments (reference tracking_model.py:218-292 assign_det_id, then :109-216 align_id, restated
  * by detection index; csrc/track_ids.hip), additive in ABI 10.  One workgroup walks the B CONSECUTIVE pairs of ONE
  * sequence in order; queued behind mmmot_associate_pairs it reads that call's `out` / `pairs` / `out_off` as they are.

@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('MMMOT_LIB_PATH', os.path.join(_HERE, 'libmmmot_hip.so'))  # override: tools' timing-experiment builds
 SOURCES = ['conv3x3.hip', 'hl16_format.hip', 'conv3x3_hl16_patch.hip', 'gemm_rows.hip', 'gemm_wide.hip',
            'gemm_ares.hip', 'gemm_wres.hip', 'gemm_wreg.hip', 'pn_mlp64.hip', 'gram.hip', 'points_gather.hip', 'crop_resize.hip', 'crop_augment.hip','small_kernels.hip', 'backward.hip', 'train.hip', 'train_vgg.hip', 'gemm_tn_f16.hip',
-           'assign.hip', 'assign_chain.hip', 'assign_sequence.hip', 'track_ids.hip', 'clear_mot.hip', 'hota.hip', 'mot3d.hip','align_points.hip', 'labels.hip', 'adam_step.hip', 'dropout.hip']
+           'assign.hip', 'assign_chain.hip', 'assign_sequence.hip', 'assign_sequence_gap.hip', 'track_ids.hip', 'clear_mot.hip', 'hota.hip', 'mot3d.hip','align_points.hip', 'labels.hip', 'adam_step.hip', 'dropout.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 HIPFLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 
@@ -182,6 +182,11 @@ SIGNATURES = {
     'mmmot_associate_sequences': [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_longlong, c_f,
                                   ctypes.c_longlong, c_f, c_f, c_f, c_f, ctypes.c_longlong, c_f],
     'mmmot_set_sequence_variant': [c_i],
+    # det, new, end, link, seqs, nts, B, n_nts, max_T, max_n, max_L, max_gap, n_scores, n_link, out, n_out, ids, objective,
+    # info, ws, ws_units, stream
+    'mmmot_associate_sequences_gap': [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_longlong,
+                                      c_f, ctypes.c_longlong, c_f, c_f, c_f, c_f, ctypes.c_longlong, c_f],
+    'mmmot_set_sequence_gap_variant': [c_i],
     'mmmot_track_ids': [c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f],
     # blocks, chains, out_off, frame_idx, B, max_n, state, ids_out, stream
     'mmmot_track_chain_ids': [c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f],

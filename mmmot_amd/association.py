@@ -33,11 +33,21 @@ trajectory number of every detection: a unit of flow is a trajectory and therefo
         det, links, new, end, det_split, return_ids=True)
 
 ``associate_sequence_batch`` solves B sequences in one launch.
+
+``associate_sequence_gaps`` adds skip links ("Sequences: skip links"; csrc/assign_sequence_gap.hip):
+``link_scores[g - 1][t]`` scores the links from frame t to frame t + g for every gap g = 1 .. G <= 8, so a trajectory
+may miss up to G - 1 frames instead of ending at the first missed detection:
+
+    from mmmot_amd.association import associate_sequence_gaps
+    assign_det, assign_links, assign_new, assign_end, ids, n_tracks = associate_sequence_gaps(
+        det, [links_gap1, links_gap2, links_gap3], new, end, det_split, return_ids=True)
+
+``associate_sequence_gaps_batch`` solves B sequences with the same number of gaps in one launch.
 """
 import numpy as np
 import torch
 
-from . import torch_ops  # noqa: F401  (registers mmmot::associate, mmmot::associate_chains and mmmot::associate_sequences)
+from . import torch_ops  # noqa: F401  (registers mmmot::associate, mmmot::associate_chains, mmmot::associate_sequences[_gap])
 
 
 def split_of(det_split):
@@ -362,5 +372,146 @@ def associate_sequence_batch(det_scores, link_scores, new_scores, end_scores, de
     res = []
     for i, (s, o, so, d, l) in enumerate(zip(splits, offs, sos, det_scores, link_scores)):
         r = unpack_chain(out[o:o + chain_block_size(s)], s, d, [x.size() for x in l])
+        res.append(r + (split_ids(ids[so:so + sum(s)], s), int(info[i, 1])) if return_ids else r)
+    return (res, obj) if return_objective else res
+
+
+# ---- whole sequences with skip links: a trajectory may miss up to max_gap - 1 frames ---------------------------------------
+SEQ_MAX_GAP = torch_ops.SEQ_MAX_GAP
+
+
+def gap_link_sizes(split, max_gap):
+    """The (n_t, n_{t+g}) of every link block in layout order: all g = 1 blocks in frame order, then all g = 2 blocks,
+    .. up to g = ``max_gap``."""
+    return [(split[t], split[t + g]) for g in range(1, int(max_gap) + 1) for t in range(len(split) - g)]
+
+
+def gap_block_size(split, max_gap):
+    return 3 * sum(split) + sum(a * b for a, b in gap_link_sizes(split, max_gap))
+
+
+def gap_sequences_table(splits, max_gap):
+    """``sequences_table`` for link blocks of every gap 1 .. ``max_gap``."""
+    rows, nts, so, lo, oo, offs, sos = [], [], 0, 0, 0, [], []
+    for split in splits:
+        K = sum(a * b for a, b in gap_link_sizes(split, max_gap))
+        rows.append([len(split), so, lo, len(nts)])
+        nts.extend(split)
+        offs.append(oo)
+        sos.append(so)
+        so += sum(split)
+        lo += K
+        oo += 3 * sum(split) + K
+    if lo >= 2 ** 31 - 1 or oo >= 2 ** 31 - 1:
+        raise ValueError('associate_sequence_gaps: the link scores of one launch must number fewer than 2^31')
+    return torch.tensor(rows, dtype=torch.int32), torch.tensor(nts, dtype=torch.int32), offs, sos
+
+
+def unpack_gaps(block, split, max_gap, like=None, link_sizes=None):
+    """One sequence's output block [det L | new L | end L | g = 1 blocks | .. | g = max_gap blocks] -> (det, [[links of
+    gap 1], [links of gap 2], ..], new, end), views of ``block``; ``link_sizes``: the nested sizes the links take."""
+    L, T = sum(split), len(split)
+    det, new, end = block[0:L], block[L:2 * L], block[2 * L:3 * L]
+    links, o = [], 3 * L
+    for g in range(1, int(max_gap) + 1):
+        row = []
+        for t in range(T - g):
+            a, b = split[t], split[t + g]
+            row.append(block[o:o + a * b].view(1, a, b))
+            o += a * b
+        links.append(row)
+    if like is not None:
+        det, new, end = (t.view(like.size()).to(like.dtype) for t in (det, new, end))
+        links = [[l.view(sz).to(like.dtype) for l, sz in zip(row, szs)] for row, szs in zip(links, link_sizes)]
+    return det, links, new, end
+
+
+def _check_gaps(det_score, link_scores, new_score, end_score, split):
+    """refuses, naming the fault, what ``associate_sequence_gaps`` cannot solve; returns max_gap"""
+    G, T, L = len(link_scores), len(split), sum(split)
+    if G < 1 or G > SEQ_MAX_GAP:
+        raise ValueError('associate_sequence_gaps: link_scores must hold the blocks of 1 .. %d gaps, got %d' % (SEQ_MAX_GAP, G))
+    if G >= T:
+        raise ValueError('associate_sequence_gaps: max_gap = %d needs more than %d frames, got %d' % (G, G, T))
+    if any(t.numel() != L for t in (det_score, new_score, end_score)):
+        raise ValueError('associate_sequence_gaps: det / new / end scores do not match det_split %s' % (split,))
+    for g, row in enumerate(link_scores, 1):
+        if len(row) != T - g:
+            raise ValueError('associate_sequence_gaps: gap %d needs %d link blocks, got %d' % (g, T - g, len(row)))
+        for t, l in enumerate(row):
+            if tuple(l.shape) not in ((split[t], split[t + g]), (1, split[t], split[t + g])):
+                raise ValueError('associate_sequence_gaps: link block (gap %d, frame %d) must be %d x %d, got %s'
+                                 % (g, t, split[t], split[t + g], tuple(l.shape)))
+    return G
+
+
+def _flat_gaps(det_score, link_scores, new_score, end_score, gt):
+    if gt is not None:
+        if len(gt) != 4 or len(gt[3]) != len(link_scores) or any(len(a) != len(b) for a, b in zip(gt[3], link_scores)):
+            raise ValueError('associate_sequence_gaps: gt does not match the scores')
+        gt = (gt[0], gt[1], gt[2], [g for row in gt[3] for g in row])
+    return _flat_scores(det_score, [l for row in link_scores for l in row], new_score, end_score, gt)
+
+
+def associate_sequence_gaps(det_score, link_scores, new_score, end_score, det_split, gt=None, return_ids=False):
+    """``associate_sequence`` with skip links: ``link_scores[g - 1][t]`` is the n_t x n_{t+g} (or 1 x n_t x n_{t+g})
+    block of the links from frame t to frame t + g, ``G = len(link_scores)`` <= 8 the largest gap, G < T.  A kept
+    detection continues into one detection of the next G frames or ends; a trajectory may miss up to G - 1 frames and may
+    cross an empty frame.  Returns (det, [[links of gap 1], [links of gap 2], ..], new, end) with the dtype, device and
+    shapes of the scores, and with ``return_ids`` the per-frame int64 trajectory numbers and the trajectory count.  ``gt``
+    = (gt_det, gt_new, gt_end, [[gt_link of gap 1 ..], ..]) selects the loss-augmented objective.  Host or device inputs,
+    as ``associate_sequence``; with one gap the results are those of ``associate_sequence``.  Refuses before any launch,
+    with a ValueError, scores that do not match; raises AssociationError when the solver reports a status."""
+    split = sequence_of(det_split)
+    G = _check_gaps(det_score, link_scores, new_score, end_score, split)
+    L = sum(split)
+    sizes = [[l.size() for l in row] for row in link_scores]
+    if L == 0:
+        z = det_score.new_zeros(det_score.size())
+        res = (z, [[det_score.new_zeros(sz) for sz in row] for row in sizes], z.clone(), z.clone())
+        empty = [torch.zeros(0, dtype=torch.int64, device=det_score.device) for _ in split]
+        return res + (empty, 0) if return_ids else res
+    flat = _flat_gaps(det_score, link_scores, new_score, end_score, gt)
+    on_host = not det_score.is_cuda
+    if on_host:
+        flat = flat.to('cuda')  # one host-to-device copy
+    seqs, nts, _, _ = gap_sequences_table([split], G)
+    out, ids, _, info = torch.ops.mmmot.associate_sequences_gap(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L],
+                                                                flat[3 * L:], seqs, nts, G)
+    info = info.cpu().numpy()
+    _raise_status(info)
+    if on_host:
+        out, ids = out.cpu(), ids.cpu()
+    res = unpack_gaps(out, split, G, det_score, sizes)
+    return res + (split_ids(ids, split), int(info[0, 1])) if return_ids else res
+
+
+def associate_sequence_gaps_batch(det_scores, link_scores, new_scores, end_scores, det_splits, gts=None,
+                                  return_objective=False, return_ids=False):
+    """B sequences with skip links in one launch, all with the same number of gaps; per sequence the arguments of
+    ``associate_sequence_gaps``, all on one device.  Returns what ``associate_sequence_batch`` returns, the links nested
+    by gap."""
+    splits = [sequence_of(s) for s in det_splits]
+    if not splits:
+        raise ValueError('associate_sequence_gaps_batch: no sequences')
+    if any(sum(s) == 0 for s in splits):
+        raise ValueError('associate_sequence_gaps_batch: every sequence needs a detection (use associate_sequence_gaps '
+                         'for empty sequences)')
+    gts = gts if gts is not None else [None] * len(splits)
+    flats, G = [], len(link_scores[0])
+    for d, l, n, e, s, g in zip(det_scores, link_scores, new_scores, end_scores, splits, gts):
+        if _check_gaps(d, l, n, e, s) != G:
+            raise ValueError('associate_sequence_gaps_batch: every sequence needs the blocks of the same %d gaps' % G)
+        flats.append(_flat_gaps(d, l, n, e, g))
+    Ls = [sum(s) for s in splits]
+    seqs, nts, offs, sos = gap_sequences_table(splits, G)
+    cat = lambda k: torch.cat([f[k * L:(k + 1) * L] for f, L in zip(flats, Ls)])
+    link = torch.cat([f[3 * L:] for f, L in zip(flats, Ls)])
+    out, ids, obj, info = torch.ops.mmmot.associate_sequences_gap(cat(0), cat(1), cat(2), link, seqs, nts, G)
+    info = info.cpu().numpy()
+    _raise_status(info)
+    res = []
+    for i, (s, o, so, d, l) in enumerate(zip(splits, offs, sos, det_scores, link_scores)):
+        r = unpack_gaps(out[o:o + gap_block_size(s, G)], s, G, d, [[x.size() for x in row] for row in l])
         res.append(r + (split_ids(ids[so:so + sum(s)], s), int(info[i, 1])) if return_ids else r)
     return (res, obj) if return_objective else res

@@ -51,7 +51,8 @@ copy - the one place the host waits - with one result (scores, assignment, ids) 
 into the callbacks, ``stats`` and the returned shape.  ``run`` is one loop (``_run_online``) over
 ``tracks.window_starts`` - for ``window=2`` the list of pairs - and ``run_offline`` one loop over batches of them
 (``_offline_frames`` and ``_offline_forwards``, which ``run_global`` shares: it keeps the batches' selected rows on the
-device and decides the whole sequence with one min-cost flow, association.associate_sequence).  A pair
+device and decides the whole sequence with one min-cost flow, association.associate_sequence - with ``max_gap`` > 1
+one with skip links, association.associate_sequence_gaps, over the pairs (f_t, f_{t+g}) as well).  A pair
 differs from a window in three places: stage A aligns a frame to the one before it (a window aligns at launch;
 ``run_offline`` aligns K frames per launch in front of the trunk), the forward (``launch_pair`` with the stage events,
 ``launch_pair_cached`` on cached rows; ``launch_window`` otherwise), and the recompute check of ``reuse_appearance``.
@@ -87,8 +88,10 @@ import torch
 from .crops import crop_resize_u8, crop_resize_u8_multi
 from . import ego
 from .points import align_points_batched, prep_points_batched
-from .association import _raise_status, select, select_chain, sequences_table, unpack_chain
+from .association import (_raise_status, gap_sequences_table, select, select_chain, sequences_table, unpack_chain,
+                          unpack_gaps)
 from .tracker_glue import queue_scores, queue_solve, queue_solve_chains
+from .torch_ops import SEQ_MAX_GAP
 from .tracks import TrackState, TrackStates, merge_chain_tracks, merge_tracks, window_starts
 
 
@@ -234,15 +237,19 @@ class SequencePipeline:
                 t.record_stream(cur)   # allocated on the side stream, consumed on the main one
         return a
 
+    def _aligned_group(self, frames, feeds, t0, t1, gap=1):
+        """the points of frames [t0, t1) (t0 >= gap), each aligned to the frame ``gap`` before it, in ONE launch"""
+        self._wait(*frames[t0:t1])
+        rows = np.concatenate([[0], np.cumsum([int(frames[t]['points'].shape[0]) for t in range(t0, t1)])])
+        rec = np.stack([_pair_record(feeds[t - gap], feeds[t]) for t in range(t0, t1)])
+        out = align_points_batched(torch.cat([frames[t]['points'] for t in range(t0, t1)]), rows, rec, 1)
+        return [out[int(rows[i]):int(rows[i + 1])] for i in range(t1 - t0)]
+
     def _align_group(self, frames, feeds, t0, t1):
         """run_offline with poses: ``points_aligned`` of frames [t0, t1) (t0 >= 1) in ONE launch, each aligned to the
         frame before it"""
-        self._wait(*frames[t0:t1])
-        rows = np.concatenate([[0], np.cumsum([int(frames[t]['points'].shape[0]) for t in range(t0, t1)])])
-        rec = np.stack([_pair_record(feeds[t - 1], feeds[t]) for t in range(t0, t1)])
-        out = align_points_batched(torch.cat([frames[t]['points'] for t in range(t0, t1)]), rows, rec, 1)
-        for i, t in enumerate(range(t0, t1)):
-            frames[t]['points_aligned'] = out[int(rows[i]):int(rows[i + 1])]
+        for t, pts in zip(range(t0, t1), self._aligned_group(frames, feeds, t0, t1)):
+            frames[t]['points_aligned'] = pts
 
     # ---- stage B: the pair forward + the packed hand-off -------------------------------------------------------
     def _wait(self, *frames):
@@ -556,7 +563,36 @@ class SequencePipeline:
                                                 appearance=torch.cat([f['rows'].rows for _, fr in grp for f in fr]))
             yield grp, outs
 
-    def run_global(self, feeds, frames_per_encode=16, pairs_per_forward=8):
+    def _gap_links(self, frames, feeds, moving, K, B, G, gap_penalty):
+        """run_global with skip links: the selected link block of every pair (f_t, f_{t+g}), g = 2 .. G, in layout order
+        (gap by gap, each in frame order), flat, less ``gap_penalty * (g - 1)``.  The pairs run ``B`` at a time through
+        ``forward_batch`` on the cached appearance rows; with poses the second frame of a pair is aligned to the pair's
+        first frame, one launch per gap and group of ``K`` frames, and the copy is kept per gap (``points_aligned`` stays
+        the alignment to the frame before)."""
+        tm, n = self.model.test_mode, len(frames)
+        pairs = [(t, g) for g in range(2, G + 1) for t in range(n - g)]
+        second = {}
+        if moving:
+            for g in range(2, G + 1):
+                for t0 in range(g, n, K):
+                    t1 = min(t0 + K, n)
+                    second.update(zip(((t, g) for t in range(t0, t1)), self._aligned_group(frames, feeds, t0, t1, g)))
+        links = []
+        for p0 in range(0, len(pairs), B):
+            grp = [(frames[t], frames[t + g], second.get((t + g, g)), g) for t, g in pairs[p0:p0 + B]]
+            plan = self.model.make_plan([([a['n'], b['n']], self._window_split([a, b])) for a, b, _, _ in grp], self.size)
+            points = [p for a, b, sec, _ in grp for p in (a['points'], b['points'] if sec is None else sec)]
+            with torch.no_grad():
+                outs = self.model.forward_batch(plan, None, torch.cat(points),
+                                                appearance=torch.cat([f['rows'].rows for a, b, _, _ in grp for f in (a, b)]))
+            for o, (_, _, _, g) in zip(outs, grp):
+                blk = select(o[0], o[1], o[2], o[3], tm)[1][0].reshape(-1)
+                links.append(blk - gap_penalty * (g - 1) if gap_penalty != 0.0 else blk.clone())
+        self.stats['pairs'] += len(pairs)
+        self.stats['gap_pairs'] = self.stats.get('gap_pairs', 0) + len(pairs)
+        return links
+
+    def run_global(self, feeds, frames_per_encode=16, pairs_per_forward=8, max_gap=1, gap_penalty=0.0):
         """The whole sequence decided at once: ``run_offline``'s stage A, alignment, trunk and batched pair forwards, then
         ONE min-cost flow over all frames (association.associate_sequence; DESIGN section 11, "Sequences") in place of a
         solve per pair and the ID walk - a unit of flow is a trajectory, its number the track ID.  Needs ``window == 2``.
@@ -568,13 +604,23 @@ class SequencePipeline:
         ``.assignment`` in ``ortools_solve`` order, ``.ids`` per kept frame, ``.n_tracks``, ``.objective``) and fills
         ``self.tracks`` at the sequence's own frame indices, whatever ``track`` is (``_account_empty`` spreads them only
         for ``track=True``, so the frames left out are counted here).  With fewer than two frames that
-        hold a detection nothing is solved, as in ``run_offline``: returns None and the tracks stay -1."""
+        hold a detection nothing is solved, as in ``run_offline``: returns None and the tracks stay -1.
+
+        ``max_gap = G > 1`` ("skip links"): a trajectory may miss up to G - 1 of the kept frames.
+        After the adjacent pairs the pairs (f_t, f_{t+g}), g = 2 .. G, are scored on the cached appearance rows - no crop
+        is encoded again - and only their link blocks are kept, less ``gap_penalty * (g - 1)``; det / new / end stay those
+        of the adjacent pairs.  One association.associate_sequence_gaps launch solves the program, one copy brings it
+        back; the result carries the blocks of the gaps 2 .. G in ``.gap_scores`` / ``.gap_assignment``.  With fewer
+        than G + 1 kept frames the largest gap that fits is used (``.max_gap``).  ``stats['gap_pairs']`` counts the pairs
+        of the gaps above 1, ``stats['pairs']`` all pairs.  ``max_gap = 1`` is the path above, launch for launch."""
         if self.window != 2:
             raise ValueError('SequencePipeline.run_global assembles the scores of frame pairs: window must be 2, got %d'
                              % self.window)
         K, B = int(frames_per_encode), int(pairs_per_forward)
         if K < 1 or B < 1:
             raise ValueError('frames_per_encode and pairs_per_forward must be >= 1')
+        if not 1 <= int(max_gap) <= SEQ_MAX_GAP:
+            raise ValueError('SequencePipeline.run_global: max_gap must lie in 1 .. %d, got %s' % (SEQ_MAX_GAP, max_gap))
         moving = _check_poses(feeds)
         n_frames = len(feeds)
         feeds, idx, _ = _skip_empty(feeds, (None, None, None))
@@ -588,7 +634,12 @@ class SequencePipeline:
                 rows += [tuple(x.reshape(-1).clone() for x in (d, l[0], n, e))
                          for d, l, n, e in (select(o[0], o[1], o[2], o[3], tm) for o in outs)]
                 self.stats['pairs'] += len(grp)
-            res = solve_global(rows, [f['n'] for f in frames])
+            G = min(int(max_gap), len(frames) - 1)  # the largest gap that fits
+            if G > 1:
+                res = solve_global(rows, [f['n'] for f in frames],
+                                   self._gap_links(frames, feeds, moving, K, B, G, float(gap_penalty)), G)
+            else:
+                res = solve_global(rows, [f['n'] for f in frames])
             tracks = res.ids
         if len(idx) < n_frames:  # the frames left out: counted, and as encoded too once the trunk has run (``_account_empty``)
             self.stats['empty_frames'] = self.stats.get('empty_frames', 0) + n_frames - len(idx)
@@ -601,11 +652,14 @@ class SequencePipeline:
 class GlobalResult:
     """What ``SequencePipeline.run_global`` returns, on the host: ``scores`` = (det L, [link 1 x n_t x n_{t+1} ...],
     new L, end L) of the kept frames, ``assignment`` the 0 / 1 tensors of the same shapes (both in ``ortools_solve``
-    order), ``ids`` per kept frame the int64 track IDs (-1: rejected), ``n_tracks``, ``objective`` (fp64), ``split``."""
+    order), ``ids`` per kept frame the int64 track IDs (-1: rejected), ``n_tracks``, ``objective`` (fp64), ``split``.
+    With skip links (``max_gap`` > 1) ``gap_scores`` / ``gap_assignment`` hold, for g = 2 .. max_gap, the list of the
+    blocks 1 x n_t x n_{t+g}; they are empty at ``max_gap`` = 1."""
 
-    def __init__(self, scores, assignment, ids, n_tracks, objective, split):
+    def __init__(self, scores, assignment, ids, n_tracks, objective, split, gap_scores=(), gap_assignment=(), max_gap=1):
         self.scores, self.assignment, self.ids = scores, assignment, ids
         self.n_tracks, self.objective, self.split = n_tracks, objective, split
+        self.gap_scores, self.gap_assignment, self.max_gap = list(gap_scores), list(gap_assignment), max_gap
 
 
 def assemble_rows(rows, counts):
@@ -619,14 +673,22 @@ def assemble_rows(rows, counts):
     return torch.cat(det + new + end + [r[1] for r in rows])
 
 
-def solve_global(rows, counts):
-    """assemble, one ``associate_sequences`` launch, one copy; raises association.AssociationError on a status word"""
+def solve_global(rows, counts, gap_links=None, max_gap=1):
+    """assemble, one ``associate_sequences`` launch, one copy; raises association.AssociationError on a status word.
+    ``max_gap`` > 1: ``gap_links`` = the flat link blocks of the gaps 2 .. max_gap in layout order, joined behind the
+    adjacent pairs' blocks, and the launch is ``associate_sequences_gap``."""
     split = [int(c) for c in counts]
     L = sum(split)
-    flat = assemble_rows(rows, split).to(torch.float32)
-    seqs, nts, _, _ = sequences_table([split])
-    out, ids, obj, info = torch.ops.mmmot.associate_sequences(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:],
-                                                              seqs, nts)
+    if max_gap == 1:
+        flat = assemble_rows(rows, split).to(torch.float32)
+        seqs, nts, _, _ = sequences_table([split])
+        out, ids, obj, info = torch.ops.mmmot.associate_sequences(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:],
+                                                                  seqs, nts)
+    else:
+        flat = torch.cat([assemble_rows(rows, split)] + list(gap_links)).to(torch.float32)
+        seqs, nts, _, _ = gap_sequences_table([split], max_gap)
+        out, ids, obj, info = torch.ops.mmmot.associate_sequences_gap(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L],
+                                                                      flat[3 * L:], seqs, nts, max_gap)
     # the fp64 objective first: every part then starts at a multiple of its element size, whatever L and the link count
     parts = [obj, flat, out, ids, info.reshape(-1)]
     host = torch.cat([x.view(torch.uint8) for x in parts]).cpu()  # the one copy
@@ -636,10 +698,15 @@ def solve_global(rows, counts):
         o += x.numel() * x.element_size()
     got = got[1:] + got[:1]  # flat, out, ids, info, objective
     _raise_status(got[3].view(1, 4).numpy())
-    sizes = [(1, a, b) for a, b in zip(split[:-1], split[1:])]
     like = got[0][0:L]
-    return GlobalResult(unpack_chain(got[0], split, like, sizes), unpack_chain(got[1], split, like, sizes),
-                        [i.numpy() for i in got[2].to(torch.int64).split(split)], int(got[3][1]), float(got[4][0]), split)
+    tail = ([i.numpy() for i in got[2].to(torch.int64).split(split)], int(got[3][1]), float(got[4][0]), split)
+    if max_gap == 1:
+        sizes = [(1, a, b) for a, b in zip(split[:-1], split[1:])]
+        return GlobalResult(unpack_chain(got[0], split, like, sizes), unpack_chain(got[1], split, like, sizes), *tail)
+    sizes = [[(1, split[t], split[t + g]) for t in range(len(split) - g)] for g in range(1, max_gap + 1)]
+    sc, asg = (unpack_gaps(x, split, max_gap, like, sizes) for x in (got[0], got[1]))
+    return GlobalResult((sc[0], sc[1][0], sc[2], sc[3]), (asg[0], asg[1][0], asg[2], asg[3]), *tail,
+                        gap_scores=sc[1][1:], gap_assignment=asg[1][1:], max_gap=max_gap)
 
 
 def lockstep_steps(lens):

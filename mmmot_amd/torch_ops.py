@@ -308,52 +308,69 @@ SEQ_ROW = 6
 SEQ_STATE_BYTES = 53
 
 
-def sequence_layout(seqs, nts, n_scores=None, n_link=None):
-    """(total output floats, int64 [B] output offsets, int64 [B] workspace offsets in 8-byte units, workspace units,
-    max n_t, max L, max T) of a sequence table; checks the table, and against the sizes of the score / link buffers when given
-    (the kernel reads what the table says)."""
+def _sequence_layout(op, seqs, nts, max_gap, n_scores, n_link):
+    """``sequence_layout`` (max_gap = 0: links to the next frame only, no offset table in the workspace) and
+    ``sequence_gap_layout`` (link blocks of every gap 1 .. max_gap)"""
     if seqs.device.type != 'cpu' or seqs.dtype != torch.int32 or seqs.dim() != 2 or seqs.shape[1] != 4:
-        raise ValueError('mmmot::associate_sequences: seqs must be a CPU int32 [B, 4] table (T, score offset, link '
-                         'offset, offset of n_0 in nts)')
+        raise ValueError('%s: seqs must be a CPU int32 [B, 4] table (T, score offset, link '
+                         'offset, offset of n_0 in nts)' % op)
     if nts.device.type != 'cpu' or nts.dtype != torch.int32 or nts.dim() != 1:
-        raise ValueError('mmmot::associate_sequences: nts must be a CPU int32 flat array of the n_t')
+        raise ValueError('%s: nts must be a CPU int32 flat array of the n_t' % op)
     if seqs.shape[0] < 1:
-        raise ValueError('mmmot::associate_sequences: no sequences')
+        raise ValueError('%s: no sequences' % op)
+    G = max(int(max_gap), 1)
     t = seqs.numpy().astype(np.int64)
     n = nts.numpy().astype(np.int64)
     T, so, lo, no = t[:, 0], t[:, 1], t[:, 2], t[:, 3]
     if T.min() < 2 or T.max() > SEQ_MAX_T:
-        raise ValueError('mmmot::associate_sequences: every sequence needs 2 <= T <= %d frames' % SEQ_MAX_T)
+        raise ValueError('%s: every sequence needs 2 <= T <= %d frames' % (op, SEQ_MAX_T))
+    if T.min() <= G:
+        raise ValueError('%s: every sequence needs more than max_gap = %d frames' % (op, G))
     if min(so.min(), lo.min(), no.min()) < 0:
-        raise ValueError('mmmot::associate_sequences: negative offset in the sequence table')
+        raise ValueError('%s: negative offset in the sequence table' % op)
     if (no + T).max() > n.size:
-        raise ValueError('mmmot::associate_sequences: a sequence reads past the end of nts')
+        raise ValueError('%s: a sequence reads past the end of nts' % op)
     if n.size and (n.min() < 0 or n.max() > MAX_ASSOC):
-        raise ValueError('mmmot::associate_sequences: every frame needs 0 <= n_t <= %d' % MAX_ASSOC)
+        raise ValueError('%s: every frame needs 0 <= n_t <= %d' % (op, MAX_ASSOC))
     L = np.empty(len(T), np.int64)
     K = np.empty(len(T), np.int64)
     max_n = 0
     for s in range(len(T)):
         ns = n[no[s]:no[s] + T[s]]
-        L[s], K[s], max_n = ns.sum(), (ns[:-1] * ns[1:]).sum(), max(max_n, int(ns.max()))
+        L[s], max_n = ns.sum(), max(max_n, int(ns.max()))
+        K[s] = sum(int((ns[:-g] * ns[g:]).sum()) for g in range(1, G + 1))
     if L.min() < 1 or L.max() > SEQ_MAX_L:
-        raise ValueError('mmmot::associate_sequences: every sequence needs 1 <= L <= %d detections' % SEQ_MAX_L)
+        raise ValueError('%s: every sequence needs 1 <= L <= %d detections' % (op, SEQ_MAX_L))
     if n_scores is not None and (so + L).max() > n_scores:
-        raise ValueError('mmmot::associate_sequences: a sequence reads past the end of the score buffers')
+        raise ValueError('%s: a sequence reads past the end of the score buffers' % op)
     if n_link is not None and (lo + K).max() > n_link:
-        raise ValueError('mmmot::associate_sequences: a sequence reads past the end of the link buffer')
+        raise ValueError('%s: a sequence reads past the end of the link buffer' % op)
     sizes = 3 * L + K
     total = int(sizes.sum())
     if total >= 2 ** 31 - 1 or int((lo + K).max()) >= 2 ** 31 - 1:
-        raise ValueError('mmmot::associate_sequences: link scores or output block exceed 32-bit offsets')
+        raise ValueError('%s: link scores or output block exceed 32-bit offsets' % op)
     units = (SEQ_STATE_BYTES * L + 7) // 8
+    if max_gap:  # the G x T table of block offsets in front of the state
+        units = units + (G * T + 1) // 2
     return (total, torch.from_numpy(np.cumsum(sizes) - sizes), torch.from_numpy(np.cumsum(units) - units),
             int(units.sum()), max_n, int(L.max()), int(T.max()))
 
 
-def _associate_sequences(det, new, end, link, seqs, nts):
+def sequence_layout(seqs, nts, n_scores=None, n_link=None):
+    """(total output floats, int64 [B] output offsets, int64 [B] workspace offsets in 8-byte units, workspace units,
+    max n_t, max L, max T) of a sequence table; checks the table, and against the sizes of the score / link buffers when given
+    (the kernel reads what the table says)."""
+    return _sequence_layout('mmmot::associate_sequences', seqs, nts, 0, n_scores, n_link)
+
+
+def _launch_sequences(det, new, end, link, seqs, nts, max_gap):
+    """the launch of mmmot::associate_sequences (max_gap = 0) and mmmot::associate_sequences_gap"""
     n_scores = min(int(det.numel()), int(new.numel()), int(end.numel()))
-    total, off, woff, units, max_n, max_L, max_T = sequence_layout(seqs, nts, n_scores, int(link.numel()))
+    if max_gap:
+        lay = sequence_gap_layout(seqs, nts, max_gap, n_scores, int(link.numel()))
+    else:
+        lay = sequence_layout(seqs, nts, n_scores, int(link.numel()))
+    total, off, woff, units, max_n, max_L, max_T = lay
     if not _ASSOC_OPS:
         from .ops import HipOps
         _ASSOC_OPS.append(HipOps())
@@ -373,23 +390,66 @@ def _associate_sequences(det, new, end, link, seqs, nts):
     obj = torch.empty(B, dtype=torch.float64, device=det.device)
     info = torch.empty((B, 4), dtype=torch.int32, device=det.device)
     ws = torch.empty(units, dtype=torch.float64, device=det.device)
-    _ASSOC_OPS[0].associate_sequences(det.contiguous(), new.contiguous(), end.contiguous(), link.contiguous(),
-                                      table[:SEQ_ROW * B], table[SEQ_ROW * B:], B, max_T, max_n, max_L, out, ids, obj, info,
-                                      ws)
+    args = (det.contiguous(), new.contiguous(), end.contiguous(), link.contiguous(), table[:SEQ_ROW * B],
+            table[SEQ_ROW * B:], B, max_T, max_n, max_L)
+    if max_gap:
+        _ASSOC_OPS[0].associate_sequences_gap(*args, int(max_gap), out, ids, obj, info, ws)
+    else:
+        _ASSOC_OPS[0].associate_sequences(*args, out, ids, obj, info, ws)
     return [out, ids, obj, info]
 
 
-def _associate_sequences_meta(det, new, end, link, seqs, nts):
-    total = sequence_layout(seqs, nts)[0]
-    B = int(seqs.shape[0])
-    n_scores = min(int(det.numel()), int(new.numel()), int(end.numel()))
+def _sequences_meta(det, total, B):
+    n_scores = int(det.numel())
     return [det.new_empty((total,), dtype=torch.float32), det.new_empty((n_scores,), dtype=torch.int32),
             det.new_empty((B,), dtype=torch.float64), det.new_empty((B, 4), dtype=torch.int32)]
+
+
+def _associate_sequences(det, new, end, link, seqs, nts):
+    return _launch_sequences(det, new, end, link, seqs, nts, 0)
+
+
+def _associate_sequences_meta(det, new, end, link, seqs, nts):
+    n = min((det, new, end), key=lambda t: int(t.numel()))
+    return _sequences_meta(n, sequence_layout(seqs, nts)[0], int(seqs.shape[0]))
 
 
 _LIB.define('associate_sequences(Tensor det, Tensor new, Tensor end, Tensor link, Tensor seqs, Tensor nts) -> Tensor[]')
 _LIB.impl('associate_sequences', _associate_sequences, 'CUDA')
 _LIB.impl('associate_sequences', _associate_sequences_meta, 'Meta')
+
+
+# ---- whole-sequence association with skip links (mmmot_amd/association.py; csrc/assign_sequence_gap.hip) ------------
+#   mmmot::associate_sequences_gap(Tensor det, Tensor new, Tensor end, Tensor link, Tensor seqs, Tensor nts,
+#                                  int max_gap) -> Tensor[]
+#       mmmot::associate_sequences with link blocks for every gap g = 1 .. max_gap <= 8 (mmmot_associate_sequences_gap):
+#       a trajectory may miss up to max_gap - 1 frames.  link, and the link part of every output block: the blocks gap
+#       by gap - all g = 1 blocks in frame order, then all g = 2 blocks, ..  Every sequence needs T > max_gap.  The same
+#       tables and the same four results; the workspace also holds each sequence's max_gap x T table of block offsets.
+SEQ_MAX_GAP = 8
+
+
+def sequence_gap_layout(seqs, nts, max_gap, n_scores=None, n_link=None):
+    """``sequence_layout`` for link blocks of every gap 1 .. ``max_gap``: the same tuple, the workspace of a sequence
+    being its offset table ((max_gap T + 1) // 2 units) followed by its search state."""
+    if not 1 <= int(max_gap) <= SEQ_MAX_GAP:
+        raise ValueError('mmmot::associate_sequences_gap: max_gap must be in 1 .. %d, got %d' % (SEQ_MAX_GAP, max_gap))
+    return _sequence_layout('mmmot::associate_sequences_gap', seqs, nts, int(max_gap), n_scores, n_link)
+
+
+def _associate_sequences_gap(det, new, end, link, seqs, nts, max_gap):
+    return _launch_sequences(det, new, end, link, seqs, nts, int(max_gap))
+
+
+def _associate_sequences_gap_meta(det, new, end, link, seqs, nts, max_gap):
+    n = min((det, new, end), key=lambda t: int(t.numel()))
+    return _sequences_meta(n, sequence_gap_layout(seqs, nts, max_gap)[0], int(seqs.shape[0]))
+
+
+_LIB.define('associate_sequences_gap(Tensor det, Tensor new, Tensor end, Tensor link, Tensor seqs, Tensor nts, '
+            'int max_gap) -> Tensor[]')
+_LIB.impl('associate_sequences_gap', _associate_sequences_gap, 'CUDA')
+_LIB.impl('associate_sequences_gap', _associate_sequences_gap_meta, 'Meta')
 
 
 # ---- track IDs (mmmot_amd/tracks.py; csrc/track_ids.hip) -------------------------------------------------------------

@@ -17,10 +17,17 @@ Writes <out>/bench_sequence_windows.json.
 over S sequences of the workload's shape (different seeds) stepped together, beside SequencePipeline(reuse_appearance=True,
 associate=True, track=True) on one of them in the same run; sequence 0 of every lockstep run must equal that run bit for
 bit.  Writes <out>/bench_sequence_streams.json.
+--global-gap G [G ..] measures the whole-sequence order with skip links (run_global(max_gap=G), DESIGN section 11 "skip
+links"): wall time of ``run_global`` per gap on the workload, every gap once per repeat, with the number of trajectories
+each gap leaves; and the solver alone on a planted instance (T = 400 frames, 8 hidden tracks whose detections are missed
+with probability 0.1): mmmot_associate_sequences beside mmmot_associate_sequences_gap at G = 1 and at the gaps given, in
+one process, interleaved, HIP-event time of the operator call, median of --solver-calls calls.  Writes
+<out>/bench_sequence_gaps.json.
 
     python tools/bench_sequence.py --out <dir> [--repeats 3] [--trunk f16x3] [-K 16] [-B 8] [--associate | --track] [--ego]
     python tools/bench_sequence.py --out <dir> --window 3 5 [--repeats 3] [-K 16] [-B 8] [-W 4] [--ego]
     python tools/bench_sequence.py --out <dir> --streams 1 2 4 8 16 [--frames 40] [--repeats 3]
+    python tools/bench_sequence.py --out <dir> --global-gap 1 2 3 4 [--frames 100] [--repeats 3] [--solver-calls 20]
 """
 import argparse
 import json
@@ -144,6 +151,86 @@ def bench_streams(args, model, dev):
     print(json.dumps(rec))
 
 
+def planted_gaps(T, tracks, p_miss, G, seed=0):
+    """(split, flat device scores [det | new | end | links gap by gap]) of ``tracks`` hidden tracks over T frames, each
+    detection missed with probability p_miss (never in the first or the last frame): det in [5, 6], the links of one
+    track in [5, 6], all others in [-6, -5], new / end in [-1, 0] with the eval zeros"""
+    rng = np.random.default_rng(seed)
+    frames = [[h for h in rng.permutation(tracks) if t in (0, T - 1) or rng.random() >= p_miss] for t in range(T)]
+    split = [len(f) for f in frames]
+    L = sum(split)
+    u = lambda lo, hi, *s: rng.uniform(lo, hi, s).astype(np.float32)
+    det, new, end = u(5, 6, L), u(-1, 0, L), u(-1, 0, L)
+    new[:split[0]] = 0
+    end[L - split[-1]:] = 0
+    links = []
+    for g in range(1, G + 1):
+        for t in range(T - g):
+            same_track = np.equal.outer(np.asarray(frames[t]), np.asarray(frames[t + g]))
+            links.append(np.where(same_track, u(5, 6, *same_track.shape), u(-6, -5, *same_track.shape)).reshape(-1))
+    return split, torch.from_numpy(np.concatenate([det, new, end] + links)).cuda()
+
+
+def bench_gaps(args, model, dev):
+    """wall time of run_global per gap, and the solver alone: the old entry beside the new one, interleaved"""
+    from mmmot_amd.association import gap_sequences_table, sequences_table
+    n, gaps = args.frames, sorted(set(args.global_gap))
+    if gaps[0] < 1 or gaps[-1] > 8:
+        raise SystemExit('--global-gap takes gaps in 1 .. 8')
+    feeds = sequence_feeds(n, ego=0 if args.ego else None)
+    K, B = args.frames_per_encode, args.pairs_per_forward
+    run = lambda G: SequencePipeline(model, 224).run_global(feeds, frames_per_encode=K, pairs_per_forward=B, max_gap=G)
+    tracks = {G: run(G).n_tracks for G in gaps}  # untimed
+    wall = {G: [] for G in gaps}
+    for _ in range(args.repeats):
+        for G in gaps:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(G)
+            torch.cuda.synchronize()
+            wall[G].append(1e3 * (time.perf_counter() - t0))
+    # the solver alone
+    T, Gmax = 400, gaps[-1]
+    split, flat = planted_gaps(T, 8, 0.1, Gmax)
+    L, K1 = sum(split), sum(a * b for a, b in zip(split[:-1], split[1:]))
+    parts = flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:]
+    old_tab = sequences_table([split])[:2]
+    calls = {'sequences': lambda: torch.ops.mmmot.associate_sequences(*parts[:3], parts[3][:K1], *old_tab)}
+    for G in sorted(set([1] + gaps)):
+        tab = gap_sequences_table([split], G)[:2]
+        calls['gap%d' % G] = lambda G=G, tab=tab: torch.ops.mmmot.associate_sequences_gap(*parts, *tab, G)
+    ms, found = {k: [] for k in calls}, {}
+    for i in range(args.solver_calls + 1):  # the first round untimed
+        for name, call in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = call()
+            e1.record()
+            torch.cuda.synchronize()
+            if i:
+                ms[name].append(e0.elapsed_time(e1))
+            found[name] = [int(x) for x in out[3][0].cpu()]
+    if found['sequences'] != found['gap1']:
+        raise SystemExit('the two entries differ at one gap: %s, %s' % (found['sequences'], found['gap1']))
+    rec = {
+        'run_global_ms': {str(G): round(float(np.median(v)), 2) for G, v in wall.items()},
+        'run_global_ms_runs': {str(G): [round(x, 2) for x in v] for G, v in wall.items()},
+        'run_global_trajectories': {str(G): t for G, t in tracks.items()},
+        'solver_ms': {k: round(float(np.median(v)), 3) for k, v in ms.items()},
+        'solver_ms_min_max': {k: [round(min(v), 3), round(max(v), 3)] for k, v in ms.items()},
+        'solver_info': {k: dict(zip(('status', 'trajectories', 'augmentations', 'passes'), v)) for k, v in found.items()},
+        'solver_instance': 'T = %d frames, 8 hidden tracks, p_miss = 0.1: L = %d detections, n_t = %d .. %d (mean %.1f)'
+                           % (T, L, min(split), max(split), L / T),
+        'solver_calls': args.solver_calls, 'frames': n, 'repeats': args.repeats, 'frames_per_encode': K,
+        'pairs_per_forward': B, 'ego': bool(args.ego), 'trunk': model.engine().trunk,
+        'device': torch.cuda.get_device_name(dev),
+    }
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_sequence_gaps.json'), 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', required=True)
@@ -160,6 +247,9 @@ def main():
     ap.add_argument('-W', '--windows-per-forward', type=int, default=4)
     ap.add_argument('--streams', type=int, nargs='+', default=None,
                     help='measure LockstepPipeline over these numbers of sequences (e.g. 1 2 4 8 16) beside one sequence alone')
+    ap.add_argument('--global-gap', type=int, nargs='+', default=None,
+                    help='time run_global(max_gap=G) for these gaps (1 .. 8) and the sequence solvers alone')
+    ap.add_argument('--solver-calls', type=int, default=20)
     args = ap.parse_args()
     assoc = args.associate or args.track
     kw = dict(associate=assoc, track=True) if args.track else dict(associate=assoc)
@@ -174,6 +264,8 @@ def main():
         return bench_windows(args, model, dev)
     if args.streams:
         return bench_streams(args, model, dev)
+    if args.global_gap:
+        return bench_gaps(args, model, dev)
     n = args.frames
     ndet, feeds = detections(n), sequence_feeds(n, ego=0 if args.ego else None)
     K, B = args.frames_per_encode, args.pairs_per_forward
