@@ -834,7 +834,7 @@ int mmmot_associate_sequences(const float* det, const float* new_score, const fl
  * the state in LDS (max_L <= 2304, else MMMOT_EINVAL).  Results do not depend on it, bit for bit. */
 int mmmot_set_sequence_variant(int variant);
 
-/* Association of whole sequences with SKIP LINKS (csrc/assign_sequence_gap.hip), exact, additive in ABI 10: the program
+/* Association of whole sequences with SKIP LINKS (csrc/assign_sequence.hip too), exact, additive in ABI 10: the program
  * of mmmot_associate_sequences with link blocks link^g_t (n_t x n_{t+g}) for every gap g = 1 .. max_gap, t = 0 ..
  * T-1-g, so that a trajectory may miss up to max_gap - 1 frames (and may cross an empty frame).  For every detection v
  * of frame t: det_v = new_v + sum_g sum_j link^g_{t-g}[j][v] = end_v + sum_g sum_k link^g_t[v][k], all variables 0 / 1,

@@ -34,7 +34,7 @@ trajectory number of every detection: a unit of flow is a trajectory and therefo
 
 ``associate_sequence_batch`` solves B sequences in one launch.
 
-``associate_sequence_gaps`` adds skip links ("Sequences: skip links"; csrc/assign_sequence_gap.hip):
+``associate_sequence_gaps`` adds skip links ("Sequences: skip links"; the same csrc/assign_sequence.hip):
 ``link_scores[g - 1][t]`` scores the links from frame t to frame t + g for every gap g = 1 .. G <= 8, so a trajectory
 may miss up to G - 1 frames instead of ending at the first missed detection:
 
@@ -286,21 +286,8 @@ def sequence_of(det_split):
 
 
 def sequences_table(splits):
-    """(seqs CPU int32 [B, 4] = (T, score offset, link offset, offset of n_0 in nts), nts CPU int32 flat, output
-    offsets, score offsets) of sequences packed one after the other."""
-    rows, nts, so, lo, oo, offs, sos = [], [], 0, 0, 0, [], []
-    for split in splits:
-        K = sum(a * b for a, b in zip(split[:-1], split[1:]))
-        rows.append([len(split), so, lo, len(nts)])
-        nts.extend(split)
-        offs.append(oo)
-        sos.append(so)
-        so += sum(split)
-        lo += K
-        oo += 3 * sum(split) + K
-    if lo >= 2 ** 31 - 1 or oo >= 2 ** 31 - 1:
-        raise ValueError('associate_sequence: the link scores of one launch must number fewer than 2^31')
-    return torch.tensor(rows, dtype=torch.int32), torch.tensor(nts, dtype=torch.int32), offs, sos
+    """``gap_sequences_table`` of next-frame links alone."""
+    return gap_sequences_table(splits, 1)
 
 
 def _raise_status(info):
@@ -314,6 +301,23 @@ def split_ids(ids, split):
     """flat per-detection IDs -> per frame an int64 array (views of one int64 copy)"""
     ids = ids.to(torch.int64)
     return list(ids.split(split))
+
+
+def _solve_sequences(flats, splits, max_gap):
+    """One launch over the sequences' flat device scores ([det | new | end | links] each, ``_flat_scores``): ``max_gap``
+    = 0 is mmmot::associate_sequences (next-frame links), else mmmot::associate_sequences_gap.  Returns (out, ids,
+    objective, host info [B, 4], output offsets, score offsets); raises AssociationError for a status word."""
+    seqs, nts, offs, sos = gap_sequences_table(splits, max(max_gap, 1))
+    cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts)
+    det, new, end = (cat([f[k * sum(s):(k + 1) * sum(s)] for f, s in zip(flats, splits)]) for k in range(3))
+    link = cat([f[3 * sum(s):] for f, s in zip(flats, splits)])
+    if max_gap:
+        out, ids, obj, info = torch.ops.mmmot.associate_sequences_gap(det, new, end, link, seqs, nts, max_gap)
+    else:
+        out, ids, obj, info = torch.ops.mmmot.associate_sequences(det, new, end, link, seqs, nts)
+    info = info.cpu().numpy()
+    _raise_status(info)
+    return out, ids, obj, info, offs, sos
 
 
 def associate_sequence(det_score, link_scores, new_score, end_score, det_split, gt=None, return_ids=False):
@@ -334,11 +338,7 @@ def associate_sequence(det_score, link_scores, new_score, end_score, det_split, 
     on_host = not det_score.is_cuda
     if on_host:
         flat = flat.to('cuda')  # one host-to-device copy
-    seqs, nts, _, _ = sequences_table([split])
-    out, ids, _, info = torch.ops.mmmot.associate_sequences(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:],
-                                                            seqs, nts)
-    info = info.cpu().numpy()
-    _raise_status(info)
+    out, ids, _, info, _, _ = _solve_sequences([flat], [split], 0)
     if on_host:
         out, ids = out.cpu(), ids.cpu()
     res = unpack_chain(out, split, det_score, [l.size() for l in link_scores])
@@ -362,13 +362,7 @@ def associate_sequence_batch(det_scores, link_scores, new_scores, end_scores, de
     for d, l, n, e, s, g in zip(det_scores, link_scores, new_scores, end_scores, splits, gts):
         _check_chain(d, l, n, e, s)
         flats.append(_flat_scores(d, l, n, e, g))
-    Ls = [sum(s) for s in splits]
-    seqs, nts, offs, sos = sequences_table(splits)
-    cat = lambda k: torch.cat([f[k * L:(k + 1) * L] for f, L in zip(flats, Ls)])
-    link = torch.cat([f[3 * L:] for f, L in zip(flats, Ls)])
-    out, ids, obj, info = torch.ops.mmmot.associate_sequences(cat(0), cat(1), cat(2), link, seqs, nts)
-    info = info.cpu().numpy()
-    _raise_status(info)
+    out, ids, obj, info, offs, sos = _solve_sequences(flats, splits, 0)
     res = []
     for i, (s, o, so, d, l) in enumerate(zip(splits, offs, sos, det_scores, link_scores)):
         r = unpack_chain(out[o:o + chain_block_size(s)], s, d, [x.size() for x in l])
@@ -391,7 +385,8 @@ def gap_block_size(split, max_gap):
 
 
 def gap_sequences_table(splits, max_gap):
-    """``sequences_table`` for link blocks of every gap 1 .. ``max_gap``."""
+    """(seqs CPU int32 [B, 4] = (T, score offset, link offset, offset of n_0 in nts), nts CPU int32 flat, output
+    offsets, score offsets) of sequences packed one after the other, with link blocks of every gap 1 .. ``max_gap``."""
     rows, nts, so, lo, oo, offs, sos = [], [], 0, 0, 0, [], []
     for split in splits:
         K = sum(a * b for a, b in gap_link_sizes(split, max_gap))
@@ -475,11 +470,7 @@ def associate_sequence_gaps(det_score, link_scores, new_score, end_score, det_sp
     on_host = not det_score.is_cuda
     if on_host:
         flat = flat.to('cuda')  # one host-to-device copy
-    seqs, nts, _, _ = gap_sequences_table([split], G)
-    out, ids, _, info = torch.ops.mmmot.associate_sequences_gap(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L],
-                                                                flat[3 * L:], seqs, nts, G)
-    info = info.cpu().numpy()
-    _raise_status(info)
+    out, ids, _, info, _, _ = _solve_sequences([flat], [split], G)
     if on_host:
         out, ids = out.cpu(), ids.cpu()
     res = unpack_gaps(out, split, G, det_score, sizes)
@@ -503,13 +494,7 @@ def associate_sequence_gaps_batch(det_scores, link_scores, new_scores, end_score
         if _check_gaps(d, l, n, e, s) != G:
             raise ValueError('associate_sequence_gaps_batch: every sequence needs the blocks of the same %d gaps' % G)
         flats.append(_flat_gaps(d, l, n, e, g))
-    Ls = [sum(s) for s in splits]
-    seqs, nts, offs, sos = gap_sequences_table(splits, G)
-    cat = lambda k: torch.cat([f[k * L:(k + 1) * L] for f, L in zip(flats, Ls)])
-    link = torch.cat([f[3 * L:] for f, L in zip(flats, Ls)])
-    out, ids, obj, info = torch.ops.mmmot.associate_sequences_gap(cat(0), cat(1), cat(2), link, seqs, nts, G)
-    info = info.cpu().numpy()
-    _raise_status(info)
+    out, ids, obj, info, offs, sos = _solve_sequences(flats, splits, G)
     res = []
     for i, (s, o, so, d, l) in enumerate(zip(splits, offs, sos, det_scores, link_scores)):
         r = unpack_gaps(out[o:o + gap_block_size(s, G)], s, G, d, [[x.size() for x in row] for row in l])

@@ -416,24 +416,25 @@ class HipOps:
     def associate_sequences(self, det, new, end, link, seqs, nts, B, max_T, max_n, max_L, out, ids, objective, info, ws):
         """B whole sequences solved exactly in one launch; see mmmot_associate_sequences.  seqs / nts / ids / info: int32
         device tensors; ws: the fp64 workspace."""
-        st = self.lib.mmmot_associate_sequences(_ptr(det), _ptr(new), _ptr(end), _ptr(link), _iptr(seqs), _iptr(nts),
-                                                int(B), int(nts.numel()), int(max_T), int(max_n), int(max_L),
-                                                int(min(det.numel(), new.numel(), end.numel())), int(link.numel()),
-                                                _ptr(out), int(out.numel()), _iptr(ids), _ptr(objective, torch.float64),
-                                                _iptr(info), _ptr(ws, torch.float64), int(ws.numel()), self._stream())
-        _lib.check(st, 'mmmot_associate_sequences')
+        self._associate_sequences('mmmot_associate_sequences', (), det, new, end, link, seqs, nts, B, max_T, max_n, max_L,
+                                  out, ids, objective, info, ws)
 
     def associate_sequences_gap(self, det, new, end, link, seqs, nts, B, max_T, max_n, max_L, max_gap, out, ids, objective,
                                 info, ws):
         """B whole sequences with skip links of up to ``max_gap`` frames solved exactly in one launch; see
         mmmot_associate_sequences_gap.  seqs / nts / ids / info: int32 device tensors; ws: the fp64 workspace."""
-        st = self.lib.mmmot_associate_sequences_gap(_ptr(det), _ptr(new), _ptr(end), _ptr(link), _iptr(seqs), _iptr(nts),
-                                                    int(B), int(nts.numel()), int(max_T), int(max_n), int(max_L),
-                                                    int(max_gap), int(min(det.numel(), new.numel(), end.numel())),
-                                                    int(link.numel()), _ptr(out), int(out.numel()), _iptr(ids),
-                                                    _ptr(objective, torch.float64), _iptr(info),
-                                                    _ptr(ws, torch.float64), int(ws.numel()), self._stream())
-        _lib.check(st, 'mmmot_associate_sequences_gap')
+        self._associate_sequences('mmmot_associate_sequences_gap', (int(max_gap),), det, new, end, link, seqs, nts, B,
+                                  max_T, max_n, max_L, out, ids, objective, info, ws)
+
+    def _associate_sequences(self, name, gap, det, new, end, link, seqs, nts, B, max_T, max_n, max_L, out, ids, objective,
+                             info, ws):
+        """the two entries' one argument list; ``gap``: () or (max_gap,), which the gap entry takes after max_L"""
+        st = getattr(self.lib, name)(_ptr(det), _ptr(new), _ptr(end), _ptr(link), _iptr(seqs), _iptr(nts), int(B),
+                                     int(nts.numel()), int(max_T), int(max_n), int(max_L), *gap,
+                                     int(min(det.numel(), new.numel(), end.numel())), int(link.numel()), _ptr(out),
+                                     int(out.numel()), _iptr(ids), _ptr(objective, torch.float64), _iptr(info),
+                                     _ptr(ws, torch.float64), int(ws.numel()), self._stream())
+        _lib.check(st, name)
 
     def track_ids(self, blocks, pairs, out_off, frame_idx, B, max_nm, state, ids_out):
         """Track IDs of B consecutive pairs of one sequence from their solver blocks; see mmmot_track_ids.  pairs /

@@ -88,8 +88,7 @@ import torch
 from .crops import crop_resize_u8, crop_resize_u8_multi
 from . import ego
 from .points import align_points_batched, prep_points_batched
-from .association import (_raise_status, gap_sequences_table, select, select_chain, sequences_table, unpack_chain,
-                          unpack_gaps)
+from .association import _raise_status, gap_sequences_table, select, select_chain, unpack_gaps
 from .tracker_glue import queue_scores, queue_solve, queue_solve_chains
 from .torch_ops import SEQ_MAX_GAP
 from .tracks import TrackState, TrackStates, merge_chain_tracks, merge_tracks, window_starts
@@ -635,11 +634,8 @@ class SequencePipeline:
                          for d, l, n, e in (select(o[0], o[1], o[2], o[3], tm) for o in outs)]
                 self.stats['pairs'] += len(grp)
             G = min(int(max_gap), len(frames) - 1)  # the largest gap that fits
-            if G > 1:
-                res = solve_global(rows, [f['n'] for f in frames],
-                                   self._gap_links(frames, feeds, moving, K, B, G, float(gap_penalty)), G)
-            else:
-                res = solve_global(rows, [f['n'] for f in frames])
+            gap_links = self._gap_links(frames, feeds, moving, K, B, G, float(gap_penalty)) if G > 1 else ()
+            res = solve_global(rows, [f['n'] for f in frames], gap_links, G)
             tracks = res.ids
         if len(idx) < n_frames:  # the frames left out: counted, and as encoded too once the trunk has run (``_account_empty``)
             self.stats['empty_frames'] = self.stats.get('empty_frames', 0) + n_frames - len(idx)
@@ -673,22 +669,22 @@ def assemble_rows(rows, counts):
     return torch.cat(det + new + end + [r[1] for r in rows])
 
 
-def solve_global(rows, counts, gap_links=None, max_gap=1):
+def solve_global(rows, counts, gap_links=(), max_gap=1):
     """assemble, one ``associate_sequences`` launch, one copy; raises association.AssociationError on a status word.
     ``max_gap`` > 1: ``gap_links`` = the flat link blocks of the gaps 2 .. max_gap in layout order, joined behind the
     adjacent pairs' blocks, and the launch is ``associate_sequences_gap``."""
     split = [int(c) for c in counts]
     L = sum(split)
+    flat = assemble_rows(rows, split)
+    if max_gap > 1:
+        flat = torch.cat([flat] + list(gap_links))
+    flat = flat.to(torch.float32)
+    scores = (flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:])
+    seqs, nts, _, _ = gap_sequences_table([split], max_gap)
     if max_gap == 1:
-        flat = assemble_rows(rows, split).to(torch.float32)
-        seqs, nts, _, _ = sequences_table([split])
-        out, ids, obj, info = torch.ops.mmmot.associate_sequences(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:],
-                                                                  seqs, nts)
+        out, ids, obj, info = torch.ops.mmmot.associate_sequences(*scores, seqs, nts)
     else:
-        flat = torch.cat([assemble_rows(rows, split)] + list(gap_links)).to(torch.float32)
-        seqs, nts, _, _ = gap_sequences_table([split], max_gap)
-        out, ids, obj, info = torch.ops.mmmot.associate_sequences_gap(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L],
-                                                                      flat[3 * L:], seqs, nts, max_gap)
+        out, ids, obj, info = torch.ops.mmmot.associate_sequences_gap(*scores, seqs, nts, max_gap)
     # the fp64 objective first: every part then starts at a multiple of its element size, whatever L and the link count
     parts = [obj, flat, out, ids, info.reshape(-1)]
     host = torch.cat([x.view(torch.uint8) for x in parts]).cpu()  # the one copy
@@ -700,9 +696,6 @@ def solve_global(rows, counts, gap_links=None, max_gap=1):
     _raise_status(got[3].view(1, 4).numpy())
     like = got[0][0:L]
     tail = ([i.numpy() for i in got[2].to(torch.int64).split(split)], int(got[3][1]), float(got[4][0]), split)
-    if max_gap == 1:
-        sizes = [(1, a, b) for a, b in zip(split[:-1], split[1:])]
-        return GlobalResult(unpack_chain(got[0], split, like, sizes), unpack_chain(got[1], split, like, sizes), *tail)
     sizes = [[(1, split[t], split[t + g]) for t in range(len(split) - g)] for g in range(1, max_gap + 1)]
     sc, asg = (unpack_gaps(x, split, max_gap, like, sizes) for x in (got[0], got[1]))
     return GlobalResult((sc[0], sc[1][0], sc[2], sc[3]), (asg[0], asg[1][0], asg[2], asg[3]), *tail,

@@ -419,7 +419,7 @@ _LIB.impl('associate_sequences', _associate_sequences, 'CUDA')
 _LIB.impl('associate_sequences', _associate_sequences_meta, 'Meta')
 
 
-# ---- whole-sequence association with skip links (mmmot_amd/association.py; csrc/assign_sequence_gap.hip) ------------
+# ---- whole-sequence association with skip links (mmmot_amd/association.py; csrc/assign_sequence.hip, GAPS) ----------
 #   mmmot::associate_sequences_gap(Tensor det, Tensor new, Tensor end, Tensor link, Tensor seqs, Tensor nts,
 #                                  int max_gap) -> Tensor[]
 #       mmmot::associate_sequences with link blocks for every gap g = 1 .. max_gap <= 8 (mmmot_associate_sequences_gap):

@@ -1,5 +1,5 @@
 """Host statements of the whole-sequence association WITH SKIP LINKS (mmmot_amd.association.associate_sequence_gaps,
-csrc/assign_sequence_gap.hip), shared by the CPU and the GPU suite.  ``links[g - 1][t]`` is the n_t x n_{t+g} block of
+csrc/assign_sequence.hip), shared by the CPU and the GPU suite.  ``links[g - 1][t]`` is the n_t x n_{t+g} block of
 gap g, g = 1 .. G; the flat order is [det | new | end | all g = 1 blocks in frame order | all g = 2 blocks | ..].
 
 * ``milp_gap_route`` / ``lp_gap_route``: the literal program - for every detection v of frame t

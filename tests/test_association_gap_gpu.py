@@ -1,5 +1,5 @@
 """Whole-sequence association with skip links on the device (mmmot_amd.association.associate_sequence_gaps,
-csrc/assign_sequence_gap.hip): planted tracks recovered across missed detections, against the literal program (scipy's
+csrc/assign_sequence.hip): planted tracks recovered across missed detections, against the literal program (scipy's
 milp) and the serial restatement of the search (tests/sequence_gap_ref.py), at one gap against mmmot_associate_sequences
 bit for bit, over kernel variant, batch position, poisoned outputs and tampered table rows, with ``gt=``, with host and
 device inputs, and what the C entry refuses."""

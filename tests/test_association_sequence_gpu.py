@@ -32,17 +32,19 @@ def ops():
     return _OPS[0]
 
 
-def solve(insts, variant=0, fill=None, tamper=None):
+def solve(insts, variant=0, fill=None, tamper=None, max_T=None, max_L=None):
     """one launch over [(split, (det, new, end, links)) ...] -> [(det, [link ...], new, end) numpy], objective [B],
     per sequence its flat ids, info [B, 4]; ``fill``: the outputs are pre-filled with this byte (or NaN for 'nan');
-    ``tamper(rows, max_T)``: changes the [B, 6] device table in place before it is uploaded"""
+    ``tamper(rows, max_T)``: changes the [B, 6] device table in place before it is uploaded; ``max_T`` / ``max_L``: what
+    the launch is sized for when not what the sequences need"""
     splits = [list(s) for s, _ in insts]
     seqs, nts, offs, sos = sequences_table(splits)
     f32 = lambda x: np.asarray(x, np.float32).reshape(-1)
     cat = lambda k: torch.from_numpy(np.concatenate([f32(sc[k]) for _, sc in insts])).cuda()
     det, new, end = cat(0), cat(1), cat(2)
     link = torch.from_numpy(np.concatenate([f32(l) for _, sc in insts for l in sc[3]] + [np.zeros(1, np.float32)])).cuda()
-    total, off, woff, units, max_n, max_L, max_T = sequence_layout(seqs, nts, det.numel(), link.numel())
+    total, off, woff, units, max_n, mL, mT = sequence_layout(seqs, nts, det.numel(), link.numel())
+    max_T, max_L = max_T or mT, max_L or mL
     B = len(insts)
     rows = torch.cat([seqs, off.to(torch.int32)[:, None], woff.to(torch.int32)[:, None]], 1)
     assert rows.shape == (B, SEQ_ROW)
@@ -134,6 +136,17 @@ def test_every_kernel_variant_returns_the_same_bits(variant):
     insts = [c[0] for c in oracle_cases()]
     auto = solve(insts)
     got = solve(insts, variant)
+    assert same(got[0], auto[0]) and np.array_equal(got[1], auto[1])
+    assert all(np.array_equal(x, y) for x, y in zip(got[2], auto[2])) and np.array_equal(got[3], auto[3])
+
+
+@pytest.mark.parametrize('variant', (3, 4))
+def test_the_largest_lds_request_returns_the_same_bits(variant):
+    """a launch sized for T = 4096 and L = 2304 asks for the most dynamic LDS the kernel may (154 896 bytes)"""
+    rng = np.random.default_rng(93)
+    insts = [(s, random_chain(rng, s, 1.0, 'normal')) for s in ([5] * 12, [18, 2, 0, 7, 3, 20, 1, 4, 9])]
+    auto = solve(insts)
+    got = solve(insts, variant, 'nan', max_T=4096, max_L=2304)
     assert same(got[0], auto[0]) and np.array_equal(got[1], auto[1])
     assert all(np.array_equal(x, y) for x, y in zip(got[2], auto[2])) and np.array_equal(got[3], auto[3])
 
