@@ -21,15 +21,19 @@
 // stays an in-register/LDS-local max in the epilogue.
 #include <atomic>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 
 #include "patch_choice.h"
+#include "patch_m16.h"
 #include "patch_common.h"
 
 // RAW (training, mmmot_conv3x3_raw_hl16): the output is the plain convolution  acc * oscale + bias  as fp32 rows (8 floats
 // where an inference launch writes one [hi8 | lo8] unit: the same bytes at the same place) - no ReLU, no clamp, no split.
-template <int BN, int BS, bool POOL, bool FUSE1 = false, bool Q8 = false, bool RAW = false PT_TIMED_TPARAM>
+// M16 (plain f16x3 layers only, chosen per LAYER by mmmot_patch_m16): the same fragments, read from the same LDS
+// addresses, become operands of v_mfma_f32_16x16x32_f16 by four v_permlane16_swap per fragment pair (patch_fragments.inc).
+template <int BN, int BS, bool POOL, bool FUSE1 = false, bool Q8 = false, bool RAW = false, bool M16 = false PT_TIMED_TPARAM>
 __global__ __launch_bounds__(512) void conv3x3_hl16_patch_kernel(
     const u32x4* __restrict__ in, const u32x4* __restrict__ wp, const float* __restrict__ bias,
     u32x4* __restrict__ out, int L, int H, int W, int Cin, int Cout, int nby, int nbx, int nblk, int ntm, int ntn,
@@ -136,7 +140,7 @@ extern "C" int mmmot_patch_choice(int L, int H, int W, int Cout, int* bn, int* b
   ((p).bn == 128 ? ((p).bs == 16 ? F(128, 16) : (p).bs == 8 ? F(128, 8) : F(128, 4)) \
                  : ((p).bs == 16 ? F(64, 16) : (p).bs == 8 ? F(64, 8) : F(64, 4)))
 
-template <int BN, int BS, bool POOL, bool FUSE1 = false, bool Q8 = false, bool RAW = false PT_TIMED_TPARAM>
+template <int BN, int BS, bool POOL, bool FUSE1 = false, bool Q8 = false, bool RAW = false, bool M16 = false PT_TIMED_TPARAM>
 static int launch_patch_e(const void* in, const void* wp, const float* bias, void* out, int L, int H, int W, int Cin,
                         int Cout, const float* oscale, hipStream_t s, Fuse1Args fz = Fuse1Args{nullptr, nullptr, nullptr, 1.f, nullptr, {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}}) {
   const int nby = (H + BS - 1) / BS, nbx = (W + BS - 1) / BS;
@@ -149,27 +153,27 @@ static int launch_patch_e(const void* in, const void* wp, const float* bias, voi
   const int grid = mmmot_patch_grid(ntm * ntn, n_cu, g_patch_grid_limit.load());  // persistent workgroups (patch_choice.h)
   unsigned int* rng = pt_range_block();
   if (!rng) return MMMOT_EINVAL;
-  hipLaunchKernelGGL((conv3x3_hl16_patch_kernel<BN, BS, POOL, FUSE1, Q8, RAW PT_TIMED_TARG(TIMED)>), dim3(grid), dim3(512), 0, s,
+  hipLaunchKernelGGL((conv3x3_hl16_patch_kernel<BN, BS, POOL, FUSE1, Q8, RAW, M16 PT_TIMED_TARG(TIMED)>), dim3(grid), dim3(512), 0, s,
                      (const u32x4*)in, (const u32x4*)wp, bias, (u32x4*)out, L, H, W, Cin, Cout, nby, nbx, nblk, ntm, ntn,
                      oscale, fz, rng);
   return mm_check(hipGetLastError());
 }
 
-template <int BN, int BS, bool POOL>
+template <int BN, int BS, bool POOL, bool M16>
 static int launch_patch(const void* in, const void* wp, const float* bias, void* out, int L, int H, int W, int Cin,
                         int Cout, const float* oscale, hipStream_t s) {
 #ifdef MMMOT_DEBUG
   if constexpr (BN == 128 && BS == 16)  // phase timers: pooled and unpooled (tools/patch_phase_timers_f16x3.py)
-    if (g_patch_timed) return launch_patch_e<BN, BS, POOL, false, false, false, true>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
+    if (g_patch_timed) return launch_patch_e<BN, BS, POOL, false, false, false, M16, true>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
 #endif
-  return launch_patch_e<BN, BS, POOL>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
+  return launch_patch_e<BN, BS, POOL, false, false, false, M16>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
 }
 
-template <int BN, int BS>
+template <int BN, int BS, bool M16>
 static int launch_patch_p(int pool, const void* in, const void* wp, const float* bias, void* out, int L, int H, int W,
                           int Cin, int Cout, const float* oscale, hipStream_t s) {
-  return pool ? launch_patch<BN, BS, true>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
-              : launch_patch<BN, BS, false>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
+  return pool ? launch_patch<BN, BS, true, M16>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
+              : launch_patch<BN, BS, false, M16>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
 }
 
 // Same contract as mmmot_conv3x3_bn_relu_hl16 (Cin % 32 == 0, Cout % 64 == 0); any H, W >= 1: pool = 1 on an odd map
@@ -183,7 +187,10 @@ extern "C" int mmmot_conv3x3_bn_relu_hl16_patch(const void* in, const void* wp, 
   if (!mm_al16(in) || !mm_al16(wp) || !mm_al16(out)) return MMMOT_EINVAL;
   if ((long)L * H * W * (Cin / 4) >= (1L << 31) - 64) return MMMOT_EINVAL;  // 32-bit piece offsets
   const mmmot_patch_plan plan = pt_plan(L, H, W, Cout);
-#define PT_HL16(BNV, BSV) launch_patch_p<BNV, BSV>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
+  const bool m16 = mmmot_patch_m16(Cin, Cout, 0, 0);  // per layer: every instantiation of it, or none
+#define PT_HL16(BNV, BSV)                                                                          \
+  (m16 ? launch_patch_p<BNV, BSV, true>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s) \
+       : launch_patch_p<BNV, BSV, false>(pool, in, wp, bias, out, L, H, W, Cin, Cout, oscale, s))
   return PT_DISPATCH(plan, PT_HL16);
 #undef PT_HL16
 }
@@ -200,7 +207,10 @@ extern "C" int mmmot_conv3x3_raw_hl16(const void* in, const void* wp, const floa
   if (!mm_al16(in) || !mm_al16(wp) || !mm_al16(out)) return MMMOT_EINVAL;
   if ((long)L * H * W * (Cin / 4) >= (1L << 31) - 64) return MMMOT_EINVAL;
   const mmmot_patch_plan plan = pt_plan(L, H, W, Cout);
-#define PT_RAW(BNV, BSV) launch_patch_e<BNV, BSV, false, false, false, true>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
+  const bool m16 = mmmot_patch_m16(Cin, Cout, 0, 0);  // the same form as the layer's inference launches
+#define PT_RAW(BNV, BSV)                                                                                        \
+  (m16 ? launch_patch_e<BNV, BSV, false, false, false, true, true>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s) \
+       : launch_patch_e<BNV, BSV, false, false, false, true>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s))
   return PT_DISPATCH(plan, PT_RAW);
 #undef PT_RAW
 }
@@ -214,7 +224,7 @@ extern "C" int mmmot_conv1_fused_hl16(const float* crops, const void* w1, const 
   if ((H & 1) || (W & 1) || !mm_al16(w1) || !mm_al16(w2) || !mm_al16(out)) return MMMOT_EINVAL;
   Fuse1Args fz{crops, (const u32x4*)w1, bias1, oscale1, nullptr, {0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}};
 #ifdef MMMOT_DEBUG
-  if (g_patch_timed) return launch_patch_e<64, 16, true, true, false, false, true>(nullptr, w2, bias2, out, L, H, W, 64, 64, oscale2, s, fz);
+  if (g_patch_timed) return launch_patch_e<64, 16, true, true, false, false, false, true>(nullptr, w2, bias2, out, L, H, W, 64, 64, oscale2, s, fz);
 #endif
   return launch_patch_e<64, 16, true, true>(nullptr, w2, bias2, out, L, H, W, 64, 64, oscale2, s, fz);
 }
@@ -240,7 +250,7 @@ static int launch_q8_p(int pool, const void* in, const void* wp, const float* bi
                        int Cin, int Cout, const float* oscale, hipStream_t s) {
 #ifdef MMMOT_DEBUG
   if constexpr (BN == 128 && BS == 16)  // phase timers (tools/patch_phase_timers.py)
-    if (!pool && g_patch_timed) return launch_patch_e<BN, BS, false, false, true, false, true>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
+    if (!pool && g_patch_timed) return launch_patch_e<BN, BS, false, false, true, false, false, true>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);
 #endif
   return pool ? launch_patch_e<BN, BS, true, false, true>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s)
               : launch_patch_e<BN, BS, false, false, true>(in, wp, bias, out, L, H, W, Cin, Cout, oscale, s);

@@ -64,6 +64,23 @@ static inline mmmot_patch_plan mmmot_patch_choose(int L, int H, int W, int Cout,
   return p;
 }
 
+// Does the layer run in the M16 form (v_mfma_f32_16x16x32_f16 on fragment pairs exchanged in registers, see
+// patch_fragments.inc)?  A property of the LAYER - its channel counts and its arithmetic - and of nothing else: never of
+// L, the map size, the grid or a knob.  The two MFMA shapes round differently (one 32-deep sum against two 16-deep
+// ones), so every instantiation a layer can get (64- / 128-channel tiles, 16 x 16 / 8 x 8 / whole-map blocks, pooled,
+// unpooled, raw) must be of one form, or batched == alone and the other bitwise guarantees would break.
+// The M16 K loop alternates two register assignments from stage to stage and starts every tile with the first one, so it
+// needs an even number of stages per tile: Cin % 64 == 0.  The hq8 arithmetic and the fused first launch have no M16 form.
+// Which layers: the ones measured faster by more than twice the run-to-run spread of the 32x32x16 form (DESIGN.md, section 7;
+// profiles/m16) AND inside the 2e-6 bound the project holds a layer's output to: Cin = 128 .. 256 except 128 -> 128, whose
+// gain stayed inside that spread.  The Cin = 64 launches are not power-limited and gain nothing; at Cin = 512 (K = 4608) the
+// form is the fastest of all but its worst element measured 2.05e-6 of the output's maximum (tests/test_conv_patch_gpu.py).
+static inline bool mmmot_patch_m16(int Cin, int Cout, int q8, int fused) {
+  if (q8 || fused) return false;
+  if (Cin == 128 && Cout == 128) return false;
+  return Cin >= 128 && Cin <= 256 && Cin % 64 == 0;
+}
+
 // the fused first launches (conv1_1 + conv1_2 + pool): 64 channels, 16 x 16 blocks - no choice but the grid
 static inline mmmot_patch_plan mmmot_patch_choose_fused(int L, int H, int W, int n_cu, int grid_limit) {
   mmmot_patch_plan p;

@@ -90,6 +90,12 @@ __device__ __forceinline__ void pt_range_guard(const float* v, bool q8, unsigned
 #define PT_COUNT_ITEM()
 #endif
 
+// f(integral_constant<int, 0>{}), f(<1>{}), ...: the slots of a half stage written out (M16: 24 of them)
+template <int... I, class F>
+__device__ __forceinline__ void pt_unroll(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+
 __device__ __forceinline__ int pt_swz_b(int r) { return (r >> 1) & 7; }
 __device__ __forceinline__ int pt_swz_a(int py, int px) { return ((px >> 1) + 4 * (py & 1)) & 7; }
 

@@ -81,7 +81,29 @@
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
     const int rb = wm * TM + tm;  // 32-row block of the tile (wave-uniform)
-    if constexpr (POOL) {
+    if constexpr (M16 && POOL) {
+      // the four registers of a lane are rows 4 (l / 16) .. + 3 of its sub-tile = quad mm_m16_quad; the quads are staged in
+      // the slot order of patch_m16.h (conflict-free writes), which the store loop below undoes
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const f32x4 c = acc16[tm][tn][s >> 1][s & 1];
+          const float m = fmaxf(fmaxf(c[0], c[1]), fmaxf(c[2], c[3]));
+          Cs[(rb * 8 + mm_m16_pool_slot(mm_m16_quad(s >> 1, lane))) * CLD + wn * TN * 32 + tn * 32 + mm_m16_col(s & 1, lane)] = m;
+        }
+    } else if constexpr (M16) {
+      if (rb / (8 / NCH) == ch) {
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              Cs[((rb % (8 / NCH)) * 32 + mm_m16_row(s >> 1, lane, r)) * CLD + wn * TN * 32 + tn * 32 + mm_m16_col(s & 1, lane)] =
+                  acc16[tm][tn][s >> 1][s & 1][r];
+      }
+    } else if constexpr (POOL) {
       // quad q = 2j + h of the 32-row block holds rows 8j + 4h .. + 3 = accumulator registers 4j .. 4j + 3
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
@@ -181,7 +203,7 @@
       const int qd = ch * NQ + qdl;
       if (qdl >= NQ) continue;
       int blk, y, x;
-      pt_row_to_pixel<BS>(qd >> 3, (qd & 7) * 4, blk, y, x);
+      pt_row_to_pixel<BS>(qd >> 3, (M16 ? mm_m16_pool_quad(qd & 7) : (qd & 7)) * 4, blk, y, x);  // M16: staged slot -> quad
       PT_BLK_PIXEL(blk, y, x)
       if (crop >= 0 && gy < H && gx < W && (gy >> 1) < Hq && (gx >> 1) < Wq) {  // floor pooling: see the hq8 branch
         f32x8 v = {va[i][0], va[i][1], va[i][2], va[i][3], vb[i][0], vb[i][1], vb[i][2], vb[i][3]};

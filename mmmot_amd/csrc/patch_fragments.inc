@@ -146,6 +146,101 @@
     else
       acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[tm], f.bh[tn], acc[tm][tn], 0, 0, 0);
   };
+  // ---------------- M16: the same fragments as operands of v_mfma_f32_16x16x32_f16 -------------------------
+  // A 32x32x16 fragment is 4 VGPRs: lane l = row l % 32, the 8 channels of lane half l / 32 of its k-step.  In 16-lane
+  // rows the pair (k-step 0, k-step 1) of one 32-row block is
+  //     R0 = [rows 0-15, (j0,h0) | rows 16-31, (j0,h0) | rows 0-15, (j0,h1) | rows 16-31, (j0,h1)]      R1 = the same for j1.
+  // v_permlane16_swap_b32 exchanges the odd 16-lane rows of its first register with the even ones of its second:
+  //     R0 = [rows 0-15: (j0,h0) | (j1,h0) | (j0,h1) | (j1,h1)]                                         R1 = the same for rows 16-31
+  // - each a 16x16x32 operand (lane l = row l % 16, k-group l / 16) whose four k-groups cover the 32 channels of the slab.
+  // Activations and weights are paired the same way, so both operands agree on the order of the k-groups (which a dot
+  // product does not care about).  Reads, addresses and swizzles are those of read_one; four swaps per pair follow.
+  // An operand = the hi and lo fragments of both k-steps of ONE 32-row block (16 VGPRs): x[j] as read, x[si] (16-row
+  // half) once swapped.
+  struct Opnd {
+    u32x4 h[2], l[2];
+  };
+  // read k of an operand: 0 = hi j0, 1 = hi j1, 2 = lo j0, 3 = lo j1 (a swap pair completes with every second read)
+  auto m16_read = [&](Opnd& o, auto ISAC, auto TILEC, auto KC, auto TAPC, int pb) {
+    constexpr bool isa = decltype(ISAC)::value != 0;
+    constexpr int tile = decltype(TILEC)::value;
+    constexpr int k = decltype(KC)::value;
+    constexpr int tap = decltype(TAPC)::value;
+    constexpr int j = k & 1, lo = k >> 1;
+    int ad;
+    if constexpr (isa) {
+      int rec, sxo;
+      a_addr(std::integral_constant<int, tile>{}, TAPC, pb, rec, sxo);
+      sxo ^= 64 * j;
+      ad = (rec + (sxo ^ (16 * lo))) + a_imm(tap);
+    } else {
+      constexpr int sb = RING0 + (tap % 3) * B_BYTES;
+      ad = ((b_off[tile] ^ (64 * j)) ^ (16 * lo)) + sb;
+    }
+    const u32x4 v = *reinterpret_cast<const u32x4*>(smem + ad);
+    if constexpr (lo == 0) o.h[j] = v; else o.l[j] = v;
+  };
+  // swap k of an operand: register k & 3 of the hi (k < 4) or lo pair
+  auto m16_swap = [&](Opnd& o, auto KC) {
+    constexpr int k = decltype(KC)::value;
+    constexpr int w = k & 3;
+    if constexpr (k < 4) {
+      const auto s = __builtin_amdgcn_permlane16_swap(o.h[0][w], o.h[1][w], false, false);
+      o.h[0][w] = s[0];
+      o.h[1][w] = s[1];
+    } else {
+      const auto s = __builtin_amdgcn_permlane16_swap(o.l[0][w], o.l[1][w], false, false);
+      o.l[0][w] = s[0];
+      o.l[1][w] = s[1];
+    }
+  };
+  // MFMA i (0..11) of the product (tm, tn): term-major like mma_one (lo*hi, hi*lo, hi*hi), sub-tile i % 4 = 2 si + sj
+  auto m16_mma = [&](const Opnd& a, const Opnd& b, auto TMC, auto TNC, auto IC) {
+    constexpr int tm = decltype(TMC)::value, tn = decltype(TNC)::value;
+    constexpr int i = decltype(IC)::value;
+    constexpr int term = i / 4, si = (i >> 1) & 1, sj = i & 1;
+    const f16x8 ah = __builtin_bit_cast(f16x8, a.h[si]), al = __builtin_bit_cast(f16x8, a.l[si]);
+    const f16x8 bh = __builtin_bit_cast(f16x8, b.h[sj]), bl = __builtin_bit_cast(f16x8, b.l[sj]);
+    f32x4& c = acc16[tm][tn][si][sj];
+    if constexpr (term == 0) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);
+    else if constexpr (term == 1) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
+    else c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
+  };
+  // slot i of a half stage's load schedule for one operand: its four reads from slot R0 on (one per slot), its eight
+  // swaps from slot S0 on (SPS per slot); each non-MFMA instruction pinned behind an MFMA like everything in the K loop
+  auto m16_load_slot = [&](Opnd& o, auto ISAC, auto TILEC, auto TAPC, int pb, auto IC, auto R0C, auto S0C, auto SPSC) {
+    constexpr int i = decltype(IC)::value, r0 = decltype(R0C)::value, s0 = decltype(S0C)::value;
+    constexpr int sps = decltype(SPSC)::value;
+    if constexpr (i >= r0 && i < r0 + 4) {
+      m16_read(o, ISAC, TILEC, std::integral_constant<int, (i - r0) & 3>{}, TAPC, pb);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (i >= s0 && i < s0 + 8 / sps) {
+      constexpr int k0 = ((i - s0) * sps) & 7;
+      m16_swap(o, std::integral_constant<int, k0>{});
+      if constexpr (sps > 1) m16_swap(o, std::integral_constant<int, (k0 + 1) & 7>{});
+      if constexpr (sps > 2) {
+        m16_swap(o, std::integral_constant<int, (k0 + 2) & 7>{});
+        m16_swap(o, std::integral_constant<int, (k0 + 3) & 7>{});
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // all of an operand at once (prologue)
+  auto m16_load = [&](Opnd& o, auto ISAC, auto TILEC, auto TAPC, int pb) {
+    m16_read(o, ISAC, TILEC, std::integral_constant<int, 0>{}, TAPC, pb);
+    m16_read(o, ISAC, TILEC, std::integral_constant<int, 1>{}, TAPC, pb);
+    m16_read(o, ISAC, TILEC, std::integral_constant<int, 2>{}, TAPC, pb);
+    m16_read(o, ISAC, TILEC, std::integral_constant<int, 3>{}, TAPC, pb);
+    m16_swap(o, std::integral_constant<int, 0>{});
+    m16_swap(o, std::integral_constant<int, 1>{});
+    m16_swap(o, std::integral_constant<int, 2>{});
+    m16_swap(o, std::integral_constant<int, 3>{});
+    m16_swap(o, std::integral_constant<int, 4>{});
+    m16_swap(o, std::integral_constant<int, 5>{});
+    m16_swap(o, std::integral_constant<int, 6>{});
+    m16_swap(o, std::integral_constant<int, 7>{});
+  };
   auto read_frags = [&](Frags& f, auto TAPC, auto JC, int pb) {  // all reads of a half stage (prologue)
     read_one(f, std::integral_constant<int, 0>{}, TAPC, JC, pb);
     read_one(f, std::integral_constant<int, 1>{}, TAPC, JC, pb);

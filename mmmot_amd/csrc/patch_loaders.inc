@@ -16,6 +16,16 @@
     for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[tm][tn][e] = 0.f;
+  // M16: the same 32 x 32 products as four 16 x 16 sub-tiles [si][sj] each (patch_m16.h), `acc` stays unused
+  f32x4 acc16[TM][TN][2][2];
+  if constexpr (M16) {
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc16[tm][tn][s >> 1][s & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   const int wm = wave / WN, wn = wave % WN;
   const int lr = lane & 31;
   const int h = lane >> 5;

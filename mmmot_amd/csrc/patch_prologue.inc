@@ -199,7 +199,15 @@
     PT_STAMP(1)
   }
   Frags f0, f1;
-  read_frags(f0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, pcur);
+  // M16: the operands of a stage (see the K loop): oA[tm] (BN = 128) or the two alternating sets of the single
+  // activation block (BN = 64), oB[tn]; every tile starts with the first stage's first product, (oA[0], oB[0])
+  Opnd oA[2], oB[2];
+  if constexpr (M16) {
+    m16_load(oA[0], std::integral_constant<int, 1>{}, I0{}, I0{}, pcur);
+    m16_load(oB[0], I0{}, I0{}, I0{}, pcur);
+  } else {
+    read_frags(f0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, pcur);
+  }
 
   // One stage = one (slab, tap): 2 k-steps of 16 channels.  Weight stage t+3 is issued after the
   // barrier of stage t (its ring slot was last read by stage t); the patch of the next slab is issued

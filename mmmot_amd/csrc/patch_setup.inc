@@ -5,6 +5,7 @@
 // of a tile and its per-thread patch source offsets (tile_blocks / poff_round / compute_poff), stream state.
   static_assert(!FUSE1 || (BN == 64 && BS == 16), "the fused first layer exists for 64-channel 16x16 tiles");
   static_assert(!RAW || (!POOL && !FUSE1 && !Q8), "raw fp32 output: plain unpooled f16x3 layers");
+  static_assert(!M16 || (!FUSE1 && !Q8), "16x16x32 form: plain f16x3 layers");
   using G = PatchGeom<BS>;
   constexpr int WN = (BN == 128) ? 2 : 1;  // waves along channels
   constexpr int WM = 8 / WN;               // waves along pixels

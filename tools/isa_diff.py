@@ -7,7 +7,9 @@
 Compares, kernel by kernel, every instruction line (labels, directives and comments dropped, symbol names masked).
 Used in round 5 to show that taking the timing experiments out of the trunk kernel and cutting its body into
 csrc/patch_*.inc changed nothing the device executes (32 of 32 instantiations identical).  ``--drop-targ n`` removes the
-n-th template argument (1-based) from the OLD listing's mangled names - the argument the refactor removed."""
+n-th template argument (1-based) from the OLD listing's mangled names - the argument the refactor removed;
+``--drop-false-targ-new n`` removes the n-th template argument from the NEW listing's names where it is `false` - a flag the
+new tree added whose `false` instantiations must be the old kernels (the `true` ones are listed as NEW)."""
 import argparse
 import re
 
@@ -29,15 +31,18 @@ def kernels(path, match):
             continue
         if not t or t[0] in ';.' or t.endswith(':'):
             continue
-        ks[cur].append(re.sub(r';.*$', '', re.sub(r'_Z\S+', 'SYM', t)).strip())
+        # (branch targets: the function's number in the listing is masked, the block number stays)
+        ks[cur].append(re.sub(r'\.LBB\d+_', '.LBB_', re.sub(r';.*$', '', re.sub(r'_Z\S+', 'SYM', t))).strip())
     return ks
 
 
-def drop_targ(name, n):
+def drop_targ(name, n, only=None):
     m = re.match(r'^(_Z\d+\w+?I)((?:L[ib]\d+E)+)(E.*)$', name)
     if not m:
         return name
     args = re.findall(r'L[ib]\d+E', m.group(2))
+    if n > len(args) or (only is not None and args[n - 1] != only):
+        return name
     del args[n - 1]
     return m.group(1) + ''.join(args) + m.group(3)
 
@@ -48,10 +53,13 @@ def main():
     ap.add_argument('new')
     ap.add_argument('--match', default='')
     ap.add_argument('--drop-targ', type=int, default=0)
+    ap.add_argument('--drop-false-targ-new', type=int, default=0)
     a = ap.parse_args()
     old, new = kernels(a.old, a.match), kernels(a.new, a.match)
     if a.drop_targ:
         old = {drop_targ(k, a.drop_targ): v for k, v in old.items()}
+    if a.drop_false_targ_new:
+        new = {drop_targ(k, a.drop_false_targ_new, only='Lb0E'): v for k, v in new.items()}
     same = 0
     for k, v in new.items():
         if old.get(k) == v:
