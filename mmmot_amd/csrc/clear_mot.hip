@@ -6,10 +6,10 @@
 //
 // Frame: with c = 1 - IoU (boxoverlap :364-391 in its operation order, fp64, no contraction) a cell is valid where
 // c <= min_overlap.  Munkres on the reference's zero-padded matrix (1e9 in the invalid cells) assigns min(G, T) rows
-// and thereby takes as many valid cells as a matching can hold and among those the smallest sum of c.  Here the same
-// shortest-augmenting-path search as csrc/assign.hip assigns every row of the smaller side at cost c - CM_K (valid) or 0
-// (invalid): CM_K = 128 outweighs any sum of c a frame can hold (<= 64), so one more valid cell always wins; rows that
-// end on an invalid cell are dropped afterwards, which is what `c < max_cost` does there.  The gains are formed from the
+// and thereby takes as many valid cells as a matching can hold and among those the smallest sum of c.  Here the
+// shortest-augmenting-path search of csrc/frame_match.h assigns every row of the smaller side at cost c - CM_K (valid)
+// or 0 (invalid): CM_K = 128 outweighs any sum of c a frame can hold (<= 64), so one more valid cell always wins; rows
+// that end on an invalid cell are dropped afterwards, which is what `c < max_cost` does there.  The gains are formed from the
 // boxes in LDS at every step.  Ties between equal-cost matchings go to the smallest column index, which need not be
 // munkres's choice.
 //
@@ -17,7 +17,7 @@
 // tracker's ID instead of at "is matched" (a GT whose partner has a negative ID takes the false-negative branch) and
 // nignoredpairs, which is always 0 because a matched tracker is never ignored (tracker IDs are unique per frame: the
 // loader refuses a file where they are not).
-#include "cm_search.h"  // the search, the ignore logic, the counters and the trajectory / sequence / total kernels
+#include "cm_search.h"  // the frame body (association, ignore logic, counters), trajectory / sequence / total kernels
 
 namespace {
 
@@ -28,14 +28,14 @@ __global__ __launch_bounds__(64) void cm_frame_kernel(const double* __restrict__
                                                       double* __restrict__ frame_d, int* __restrict__ frame_i,
                                                       int* __restrict__ gt_out) {
   const int f = blockIdx.x;
-  const int* fr = frames + 6 * f;
-  if (!cm_frame_ok(fr, nG, nT, nD)) {
+  const FmFrame fr = fm_frame(frames + 6 * f, nG, nT, nD);
+  if (!fr.ok) {
     cm_frame_mark(frame_d + 2 * f, frame_i + 6 * f);
     return;
   }
-  const int go = fr[0], G = fr[1], to = fr[2], T = fr[3], dof = fr[4], D = fr[5];
+  const int go = fr.go, G = fr.G, to = fr.to, T = fr.T, dof = fr.dof, D = fr.D;
   CmBoxCost cf;
-  cm_frame_body(cf, (const CmBox*)boxes + go, (const CmBox*)boxes + nG + to, (const CmBox*)boxes + nG + nT + dof, G, T,
+  cm_frame_body(cf, (const FmBox*)boxes + go, (const FmBox*)boxes + nG + to, (const FmBox*)boxes + nG + nT + dof, G, T,
                 D, go, to, g_attr, t_attr, min_overlap, min_height, max_truncation, max_occlusion, frame_d + 2 * f,
                 frame_i + 6 * f, gt_out);
 }

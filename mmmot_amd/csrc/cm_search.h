@@ -1,7 +1,8 @@
-// The CLEAR-MOT frame evaluation, once, for both cost sources: the shortest-augmenting-path association, the gate, the
-// ignore logic and the counters of csrc/clear_mot.hip, parametrised by a cost functor - the 2D boxes in LDS
-// (clear_mot.hip) or a per-frame table of c (mot3d.hip) - and the trajectory / sequence / total kernels with a level
-// dimension (blockIdx.y; the 2D evaluator launches one level).  Included by one .hip file each; everything is file-local.
+// The CLEAR-MOT frame evaluation, once, for both cost sources: the association (the search of csrc/frame_match.h over the
+// gated cost), the gate, the ignore logic and the counters of csrc/clear_mot.hip, parametrised by a cost functor - the 2D
+// boxes in LDS (clear_mot.hip) or a per-frame table of c (mot3d.hip) - and the trajectory / sequence / total kernels with
+// a level dimension (blockIdx.y; the 2D evaluator launches one level).  Included by one .hip file each; everything is
+// file-local.
 //
 // A cost functor F provides
 //   void bind(gb, tb)           receives the frame's 2D boxes in LDS (ground truth, tracker columns)
@@ -14,55 +15,20 @@
 //                               positive that is not ignored
 // and the arithmetic never depends on F beyond the value of c.
 #pragma once
-#include "common.h"
+#include "frame_match.h"  // the box, the overlap, the limits, the frame-row check and the search
 
-#define CM_MAXN 128  // ground-truth or tracker boxes per frame
-#define CM_MAXD 64   // DontCare boxes per frame
 #define CM_K 128.0
 #define CM_SEQ_INTS 12  // tp, itp, fn, ifn, fp, n_itr, id switches, fragments, MT, PT, ML, ignored trajectories
 
 namespace {
 
-struct CmBox {
-  double x1, y1, x2, y2;
-};
-
-// boxoverlap(a, b, "union") / (a, b, "a"): every product, sum and quotient rounded on its own
-__device__ __forceinline__ double cm_overlap(const CmBox& a, const CmBox& b, bool over_a) {
-#pragma clang fp contract(off)
-  const double x1 = fmax(a.x1, b.x1), y1 = fmax(a.y1, b.y1), x2 = fmin(a.x2, b.x2), y2 = fmin(a.y2, b.y2);
-  const double w = x2 - x1, h = y2 - y1;
-  if (w <= 0.0 || h <= 0.0) return 0.0;
-  const double inter = w * h;
-  const double aarea = (a.x2 - a.x1) * (a.y2 - a.y1);
-  if (over_a) return inter / aarea;
-  const double barea = (b.x2 - b.x1) * (b.y2 - b.y1);
-  return inter / (aarea + barea - inter);
-}
-
 // c = 1 - IoU of ground truth g and tracker t
-__device__ __forceinline__ double cm_c(const CmBox& g, const CmBox& t) {
+__device__ __forceinline__ double cm_c(const FmBox& g, const FmBox& t) {
 #pragma clang fp contract(off)
-  return 1.0 - cm_overlap(g, t, false);
+  return 1.0 - fm_overlap(g, t, false);
 }
 
 __device__ __forceinline__ double cm_cost(double c, double min_overlap) { return c <= min_overlap ? c - CM_K : 0.0; }
-
-__device__ __forceinline__ void cm_better(double& bv, int& bj, double ov, int oj) {
-  if (ov < bv || (ov == bv && oj < bj)) {
-    bv = ov;
-    bj = oj;
-  }
-}
-
-__device__ __forceinline__ int cm_count(bool p) { return __popcll(__ballot(p)); }
-
-// the frame's row of the frame table inside the contract and the sections?
-__device__ __forceinline__ bool cm_frame_ok(const int* fr, int nG, int nT, int nD) {
-  const int go = fr[0], G = fr[1], to = fr[2], T = fr[3], dof = fr[4], D = fr[5];
-  return !(G < 0 || T < 0 || D < 0 || G > CM_MAXN || T > CM_MAXN || D > CM_MAXD || go < 0 || to < 0 || dof < 0 ||
-           go > nG - G || to > nT - T || dof > nD - D);
-}
 
 // a frame outside the contract: a marked frame, nothing is read
 __device__ __forceinline__ void cm_frame_mark(double* fd, int* fi) {
@@ -73,10 +39,10 @@ __device__ __forceinline__ void cm_frame_mark(double* fd, int* fi) {
 
 // the cost from the 2D boxes in LDS, formed at every step
 struct CmBoxCost {
-  const CmBox* gb;
-  const CmBox* tb;
-  typedef CmBox Row;
-  __device__ __forceinline__ void bind(const CmBox* g, const CmBox* t) {
+  const FmBox* gb;
+  const FmBox* tb;
+  typedef FmBox Row;
+  __device__ __forceinline__ void bind(const FmBox* g, const FmBox* t) {
     gb = g;
     tb = t;
   }
@@ -89,19 +55,32 @@ struct CmBoxCost {
   __device__ __forceinline__ void matched(int, int, bool) const {}
 };
 
-// One wave evaluates one frame of G ground-truth objects (from gsrc, attributes g_attr + 3 go) against T tracker
-// columns (object cf.col(j) of tsrc / t_attr + 2 to) and D DontCare areas.  G, T <= CM_MAXN, D <= CM_MAXD.
+// what fm_assign searches: the gated cost of the functor's c, the rows being the smaller side (tr: the tracker side)
 template <class F>
-__device__ __forceinline__ void cm_frame_body(F& cf, const CmBox* __restrict__ gsrc, const CmBox* __restrict__ tsrc,
-                                              const CmBox* __restrict__ dsrc, int G, int T, int D, int go, int to,
+struct CmSearchCost {
+  const F& cf;
+  bool tr;
+  double min_overlap;
+  typedef typename F::Row Row;
+  __device__ __forceinline__ Row row(int i) const { return cf.row(tr, i); }
+  __device__ __forceinline__ double cell(const Row& rb, int j) const {
+    return cm_cost(cf.cell(rb, tr, j), min_overlap);
+  }
+};
+
+// One wave evaluates one frame of G ground-truth objects (from gsrc, attributes g_attr + 3 go) against T tracker
+// columns (object cf.col(j) of tsrc / t_attr + 2 to) and D DontCare areas.  G, T <= FM_MAXN, D <= FM_MAXD.
+template <class F>
+__device__ __forceinline__ void cm_frame_body(F& cf, const FmBox* __restrict__ gsrc, const FmBox* __restrict__ tsrc,
+                                              const FmBox* __restrict__ dsrc, int G, int T, int D, int go, int to,
                                               const int* __restrict__ g_attr, const int* __restrict__ t_attr,
                                               double min_overlap, double min_height, double max_truncation,
                                               double max_occlusion, double* __restrict__ fd, int* __restrict__ fi,
                                               int* __restrict__ gt_out) {
-  constexpr int K = CM_MAXN / 64;
-  __shared__ CmBox gb[CM_MAXN], tb[CM_MAXN], db[CM_MAXD];
-  __shared__ double u[CM_MAXN], ov[CM_MAXN];
-  __shared__ int row4col[CM_MAXN], col4row[CM_MAXN], path[CM_MAXN], mg[CM_MAXN], tval[CM_MAXN], tign[CM_MAXN];
+  constexpr int K = FM_MAXN / 64;
+  __shared__ FmBox gb[FM_MAXN], tb[FM_MAXN], db[FM_MAXD];
+  __shared__ double u[FM_MAXN], ov[FM_MAXN];
+  __shared__ int row4col[FM_MAXN], col4row[FM_MAXN], path[FM_MAXN], mg[FM_MAXN], tval[FM_MAXN], tign[FM_MAXN];
   const int tid = threadIdx.x;
   cf.bind(gb, tb);
   const bool tr = G > T;  // rows are the smaller side
@@ -116,86 +95,7 @@ __device__ __forceinline__ void cm_frame_body(F& cf, const CmBox* __restrict__ g
     tval[j] = 0;
   }
   for (int d = tid; d < D; d += 64) db[d] = dsrc[d];
-  for (int r = tid; r < R; r += 64) {
-    u[r] = 0.0;
-    col4row[r] = -1;
-  }
-  for (int j = tid; j < C; j += 64) {
-    row4col[j] = -1;
-    path[j] = -1;
-  }
-  __syncthreads();
-
-  // the search of csrc/assign.hip with one wave and two columns a lane; the gain comes from the cost functor
-  double v[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = 0.0;
-  for (int cur = 0; cur < R; ++cur) {
-    double sp[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) sp[k] = INFINITY;
-    unsigned scanned = 0;
-    double minv = 0.0;
-    int i = cur, sink = -1;
-    for (;;) {
-      const double ui = u[i];
-      const typename F::Row rb = cf.row(tr, i);
-      double bv = INFINITY;
-      int bj = 0x7fffffff;
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const int j = k * 64 + tid;
-        if (j < C && !((scanned >> k) & 1u)) {
-          const double c = cf.cell(rb, tr, j);
-          const double r = minv + cm_cost(c, min_overlap) - ui - v[k];
-          if (r < sp[k]) {
-            sp[k] = r;
-            path[j] = i;
-          }
-          if (sp[k] < bv) {
-            bv = sp[k];
-            bj = j;
-          }
-        }
-      }
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) cm_better(bv, bj, __shfl_xor(bv, o), __shfl_xor(bj, o));
-      if (bj >= C) break;  // cannot happen: every cost is finite and C >= R
-      minv = bv;
-      if ((bj & 63) == tid) scanned |= 1u << (bj >> 6);
-      const int nxt = row4col[bj];
-      if (nxt < 0) {
-        sink = bj;
-        break;
-      }
-      i = nxt;
-    }
-    if (sink >= 0) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const int j = k * 64 + tid;
-        if ((scanned >> k) & 1u) {
-          const double d = minv - sp[k];
-          v[k] -= d;
-          if (j != sink) u[row4col[j]] += d;
-        }
-      }
-      if (tid == 0) u[cur] += minv;
-    }
-    __syncthreads();
-    if (tid == 0 && sink >= 0) {
-      int j = sink;
-      for (;;) {
-        const int r = path[j];
-        row4col[j] = r;
-        const int prev = col4row[r];
-        col4row[r] = j;
-        j = prev;
-        if (r == cur) break;
-      }
-    }
-    __syncthreads();
-  }
+  fm_assign(R, C, tid, u, row4col, col4row, path, CmSearchCost<F>{cf, tr, min_overlap});
 
   // keep the assigned cells that pass the gate (`c < max_cost`, :488)
   for (int r = tid; r < R; r += 64) {
@@ -219,12 +119,12 @@ __device__ __forceinline__ void cm_frame_body(F& cf, const CmBox* __restrict__ g
     const int j = k * 64 + tid;
     bool ign = false;
     if (j < T && !tval[j]) {
-      const CmBox b = tb[j];
+      const FmBox b = tb[j];
       ign = t_attr[2 * (to + cf.col(j)) + 1] == 1 || fabs(b.y1 - b.y2) <= min_height;
-      for (int d = 0; d < D && !ign; ++d) ign = cm_overlap(b, db[d], true) > 0.5;
+      for (int d = 0; d < D && !ign; ++d) ign = fm_overlap(b, db[d], true) > 0.5;
     }
     if (j < T) tign[j] = ign ? 1 : 0;
-    n_itr += cm_count(ign);
+    n_itr += fm_count(ign);
   }
   __syncthreads();
 
@@ -250,10 +150,10 @@ __device__ __forceinline__ void cm_frame_body(F& cf, const CmBox* __restrict__ g
       kept += (val && !is_itp) ? ov[i] : 0.0;
       cf.matched(i, j, val && !is_itp);
     }
-    nvalid += cm_count(val);
-    ifn += cm_count(is_ifn);
-    itp += cm_count(is_itp);
-    npairs += cm_count(pr);
+    nvalid += fm_count(val);
+    ifn += fm_count(is_ifn);
+    itp += fm_count(is_itp);
+    npairs += fm_count(pr);
   }
   cost = wave_sum_d(cost);
   kept = wave_sum_d(kept);

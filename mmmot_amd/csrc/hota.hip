@@ -7,8 +7,8 @@
 //   seq      one workgroup per SEQUENCE: frame sums in frame order, the per-alpha association sums
 //   idf1     one wave per SEQUENCE: maximum-weight matching of the integer pm
 //   total    one workgroup: the sums over the sequences in sequence order
-// Similarities are cm_overlap's fp64 IoU (every product, sum and quotient rounded on its own).  Both per-frame
-// assignments are the shortest-augmenting-path search of csrc/clear_mot.hip over the smaller side with cost = -value:
+// Similarities are fm_overlap's fp64 IoU (every product, sum and quotient rounded on its own).  Both per-frame
+// assignments are the shortest-augmenting-path search of csrc/frame_match.h over the smaller side with cost = -value:
 // every value is >= 0, so assigning all rows of the smaller side loses nothing and the pairs of value 0 are dropped
 // afterwards.  Ties go to the smallest column index.
 //
@@ -16,12 +16,10 @@
 // frame with a barrier in between; within a frame a cell (gt ID, tracker ID) belongs to one thread because IDs are
 // unique per frame (the host refuses tables where they are not).  LocSum is a butterfly over the wave per frame and a
 // serial sum over the frames in order.  mc, pm and the counts are integers.
-#include "common.h"
+#include "frame_match.h"  // the box, the overlap, the limits, the frame-row check and the search
 
 #pragma clang fp contract(off)  // every fp64 operation of this file is rounded on its own
 
-#define HT_MAXN 128            // ground-truth or tracker boxes per frame (CLEAR_MOT_MAX_BOXES)
-#define HT_MAXD 64             // DontCare boxes per frame (CLEAR_MOT_MAX_DONTCARE)
 #define HT_NA 19               // alpha_a = 0.05 (a + 1)
 #define HT_MAX_CELLS (1 << 18) // G * T of one sequence
 #define HT_MAX_IDS 2048        // G or T of one sequence: the potentials and labels of the IDF1 matching sit in LDS
@@ -34,49 +32,9 @@
 
 namespace {
 
-struct HtBox {
-  double x1, y1, x2, y2;
-};
-
-// boxoverlap(a, b, "union") / (a, b, "a") in cm_overlap's operation order
-__device__ __forceinline__ double ht_overlap(const HtBox& a, const HtBox& b, bool over_a) {
-#pragma clang fp contract(off)
-  const double x1 = fmax(a.x1, b.x1), y1 = fmax(a.y1, b.y1), x2 = fmin(a.x2, b.x2), y2 = fmin(a.y2, b.y2);
-  const double w = x2 - x1, h = y2 - y1;
-  if (w <= 0.0 || h <= 0.0) return 0.0;
-  const double inter = w * h;
-  const double aarea = (a.x2 - a.x1) * (a.y2 - a.y1);
-  if (over_a) return inter / aarea;
-  const double barea = (b.x2 - b.x1) * (b.y2 - b.y1);
-  return inter / (aarea + barea - inter);
-}
-
 __device__ __forceinline__ double ht_alpha(int a) {
 #pragma clang fp contract(off)
   return 0.05 * (double)(a + 1);
-}
-
-__device__ __forceinline__ void ht_better(double& bv, int& bj, double ov, int oj) {
-  if (ov < bv || (ov == bv && oj < bj)) {
-    bv = ov;
-    bj = oj;
-  }
-}
-
-__device__ __forceinline__ int ht_count(bool p) { return __popcll(__ballot(p)); }
-
-struct HtFrame {
-  int go, G, to, T, dof, D;
-  bool ok;
-};
-
-__device__ __forceinline__ HtFrame ht_frame(const int* __restrict__ frames, int f, int nG, int nT, int nD) {
-  HtFrame r;
-  r.go = frames[6 * f], r.G = frames[6 * f + 1], r.to = frames[6 * f + 2], r.T = frames[6 * f + 3];
-  r.dof = frames[6 * f + 4], r.D = frames[6 * f + 5];
-  r.ok = !(r.G < 0 || r.T < 0 || r.D < 0 || r.G > HT_MAXN || r.T > HT_MAXN || r.D > HT_MAXD || r.go < 0 || r.to < 0 ||
-           r.dof < 0 || r.go > nG - r.G || r.to > nT - r.T || r.dof > nD - r.D);
-  return r;
 }
 
 struct HtSeq {
@@ -98,88 +56,20 @@ __device__ __forceinline__ HtSeq ht_seq(const int* __restrict__ seq_tab, int s, 
   return r;
 }
 
-// The search of csrc/clear_mot.hip: one wave, two columns a lane, rows 0 .. R-1 all assigned at the smallest sum of
-// cost(row, column); R <= C <= HT_MAXN.  col4row[r] is row r's column.
-template <class F>
-__device__ __forceinline__ void ht_assign(int R, int C, int tid, double* u, int* row4col, int* col4row, int* path,
-                                          F cost) {
-  constexpr int K = HT_MAXN / 64;
-  for (int r = tid; r < R; r += 64) {
-    u[r] = 0.0;
-    col4row[r] = -1;
-  }
-  for (int j = tid; j < C; j += 64) {
-    row4col[j] = -1;
-    path[j] = -1;
-  }
-  __syncthreads();
-  double v[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = 0.0;
-  for (int cur = 0; cur < R; ++cur) {
-    double sp[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) sp[k] = INFINITY;
-    unsigned scanned = 0;
-    double minv = 0.0;
-    int i = cur, sink = -1;
-    for (;;) {
-      const double ui = u[i];
-      double bv = INFINITY;
-      int bj = 0x7fffffff;
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const int j = k * 64 + tid;
-        if (j < C && !((scanned >> k) & 1u)) {
-          const double r = minv + cost(i, j) - ui - v[k];
-          if (r < sp[k]) {
-            sp[k] = r;
-            path[j] = i;
-          }
-          if (sp[k] < bv) {
-            bv = sp[k];
-            bj = j;
-          }
-        }
-      }
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) ht_better(bv, bj, __shfl_xor(bv, o), __shfl_xor(bj, o));
-      if (bj >= C) break;  // cannot happen: every cost is finite and C >= R
-      minv = bv;
-      if ((bj & 63) == tid) scanned |= 1u << (bj >> 6);
-      const int nxt = row4col[bj];
-      if (nxt < 0) {
-        sink = bj;
-        break;
-      }
-      i = nxt;
-    }
-    if (sink >= 0) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const int j = k * 64 + tid;
-        if ((scanned >> k) & 1u) {
-          const double d = minv - sp[k];
-          v[k] -= d;
-          if (j != sink) u[row4col[j]] += d;
-        }
-      }
-      if (tid == 0) u[cur] += minv;
-    }
-    __syncthreads();
-    if (tid == 0 && sink >= 0) {
-      int j = sink;
-      for (;;) {
-        const int r = path[j];
-        row4col[j] = r;
-        const int prev = col4row[r];
-        col4row[r] = j;
-        j = prev;
-        if (r == cur) break;
-      }
-    }
-    __syncthreads();
-  }
+// what fm_assign searches for a value val(ground truth i, tracker j) >= 0: cost = -value, the rows being the smaller
+// side (tr: the tracker side)
+template <class V>
+struct HtCost {
+  const V& val;
+  bool tr;
+  typedef int Row;
+  __device__ __forceinline__ Row row(int i) const { return i; }
+  __device__ __forceinline__ double cell(int r, int c) const { return tr ? -val(c, r) : -val(r, c); }
+};
+
+template <class V>
+__device__ __forceinline__ HtCost<V> ht_cost(const V& val, bool tr) {
+  return HtCost<V>{val, tr};
 }
 
 // preparation: keep flags of every ground-truth and tracker row of the frame, and the value of its assignment
@@ -188,12 +78,12 @@ __global__ __launch_bounds__(64) void ht_prep_kernel(const double* __restrict__ 
                                                      double min_height, double max_truncation, double max_occlusion,
                                                      int prepare, int* __restrict__ gkeep, int* __restrict__ tkeep,
                                                      double* __restrict__ frame_d) {
-  constexpr int K = HT_MAXN / 64;
-  __shared__ HtBox gb[HT_MAXN], tb[HT_MAXN], db[HT_MAXD];
-  __shared__ double u[HT_MAXN];
-  __shared__ int row4col[HT_MAXN], col4row[HT_MAXN], path[HT_MAXN], mt[HT_MAXN];
+  constexpr int K = FM_MAXN / 64;
+  __shared__ FmBox gb[FM_MAXN], tb[FM_MAXN], db[FM_MAXD];
+  __shared__ double u[FM_MAXN];
+  __shared__ int row4col[FM_MAXN], col4row[FM_MAXN], path[FM_MAXN], mt[FM_MAXN];
   const int f = blockIdx.x, tid = threadIdx.x;
-  const HtFrame fr = ht_frame(frames, f, nG, nT, nD);
+  const FmFrame fr = fm_frame(frames + 6 * f, nG, nT, nD);
   if (!fr.ok) return;  // pass 2 marks the frame; its keep flags stay 0
   const int G = fr.G, T = fr.T, D = fr.D, go = fr.go, to = fr.to;
   if (!prepare) {
@@ -202,9 +92,9 @@ __global__ __launch_bounds__(64) void ht_prep_kernel(const double* __restrict__ 
     if (tid == 0) frame_d[HT_FRAME_D * f] = 0.0;
     return;
   }
-  const HtBox* gsrc = (const HtBox*)boxes + go;
-  const HtBox* tsrc = (const HtBox*)boxes + nG + to;
-  const HtBox* dsrc = (const HtBox*)boxes + nG + nT + fr.dof;
+  const FmBox* gsrc = (const FmBox*)boxes + go;
+  const FmBox* tsrc = (const FmBox*)boxes + nG + to;
+  const FmBox* dsrc = (const FmBox*)boxes + nG + nT + fr.dof;
   for (int i = tid; i < G; i += 64) gb[i] = gsrc[i];
   for (int j = tid; j < T; j += 64) {
     tb[j] = tsrc[j];
@@ -216,10 +106,10 @@ __global__ __launch_bounds__(64) void ht_prep_kernel(const double* __restrict__ 
   const int R = tr ? T : G, C = tr ? G : T;
   const double gate = 0.5 - HT_EPS;
   auto val = [&](int i, int j) {  // ground truth i, tracker j
-    const double s = ht_overlap(gb[i], tb[j], false);
+    const double s = fm_overlap(gb[i], tb[j], false);
     return s < gate ? 0.0 : s;
   };
-  ht_assign(R, C, tid, u, row4col, col4row, path, [&](int r, int c) { return tr ? -val(c, r) : -val(r, c); });
+  fm_assign(R, C, tid, u, row4col, col4row, path, ht_cost(val, tr));
   double value = 0.0;
   for (int r = tid; r < R; r += 64) {
     const int c4 = col4row[r];
@@ -245,9 +135,9 @@ __global__ __launch_bounds__(64) void ht_prep_kernel(const double* __restrict__ 
         rm = a[2] == 1 || (double)a[1] > max_occlusion || (double)a[0] > max_truncation;
       } else {
 #pragma clang fp contract(off)
-        const HtBox b = tb[j];
+        const FmBox b = tb[j];
         rm = b.y2 - b.y1 <= min_height + HT_EPS;
-        for (int d = 0; d < D && !rm; ++d) rm = ht_overlap(b, db[d], true) > 0.5 + HT_EPS;
+        for (int d = 0; d < D && !rm; ++d) rm = fm_overlap(b, db[d], true) > 0.5 + HT_EPS;
       }
       tkeep[to + j] = rm ? 0 : 1;
     }
@@ -262,11 +152,11 @@ __global__ __launch_bounds__(64) void ht_prep_kernel(const double* __restrict__ 
 
 // The kept rows of one side of a frame, compacted in order into LDS by ONE wave (lane = threadIdx.x < 64): boxes and
 // dense IDs.  A row whose ID lies outside [0, n_ids) is dropped.  Returns the count (the same in every lane).
-__device__ __forceinline__ int ht_load_kept(const HtBox* __restrict__ src, const int* __restrict__ keep,
+__device__ __forceinline__ int ht_load_kept(const FmBox* __restrict__ src, const int* __restrict__ keep,
                                             const int* __restrict__ id, int id_stride, int n, int n_ids, int lane,
-                                            HtBox* dst, int* dst_id) {
+                                            FmBox* dst, int* dst_id) {
   int base = 0;
-  for (int k = 0; k < HT_MAXN / 64; ++k) {
+  for (int k = 0; k < FM_MAXN / 64; ++k) {
     const int i = k * 64 + lane;
     int my = -1;
     if (i < n && keep[i] != 0) my = id[id_stride * i];
@@ -290,21 +180,21 @@ __global__ __launch_bounds__(256) void ht_pot_kernel(const double* __restrict__ 
                                                      int sumT, const int* __restrict__ gkeep,
                                                      const int* __restrict__ tkeep, double* pot, int* pm,
                                                      int* gcount, int* tcount) {
-  __shared__ HtBox gb[HT_MAXN], tb[HT_MAXN];
-  __shared__ int gid[HT_MAXN], tid_[HT_MAXN], nk[2];
-  __shared__ double rs[HT_MAXN], cs[HT_MAXN];
+  __shared__ FmBox gb[FM_MAXN], tb[FM_MAXN];
+  __shared__ int gid[FM_MAXN], tid_[FM_MAXN], nk[2];
+  __shared__ double rs[FM_MAXN], cs[FM_MAXN];
   const int t = threadIdx.x;
   const HtSeq sq = ht_seq(seq_tab, blockIdx.x, S, NF, cells, sumG, sumT);
   if (!sq.ok) return;
   double* spot = pot + sq.cell0;
   int* spm = pm + sq.cell0;
   for (int f = sq.f0; f < sq.f1; ++f) {
-    const HtFrame fr = ht_frame(frames, f, nG, nT, nD);
+    const FmFrame fr = fm_frame(frames + 6 * f, nG, nT, nD);
     if (!fr.ok) continue;  // uniform
     if (t < 64) {
-      const int a = ht_load_kept((const HtBox*)boxes + fr.go, gkeep + fr.go, g_attr + 4 * fr.go + 3, 4, fr.G, sq.G, t,
+      const int a = ht_load_kept((const FmBox*)boxes + fr.go, gkeep + fr.go, g_attr + 4 * fr.go + 3, 4, fr.G, sq.G, t,
                                  gb, gid);
-      const int b = ht_load_kept((const HtBox*)boxes + nG + fr.to, tkeep + fr.to, t_id + fr.to, 1, fr.T, sq.T, t, tb,
+      const int b = ht_load_kept((const FmBox*)boxes + nG + fr.to, tkeep + fr.to, t_id + fr.to, 1, fr.T, sq.T, t, tb,
                                  tid_);
       if (t == 0) {
         nk[0] = a;
@@ -313,25 +203,25 @@ __global__ __launch_bounds__(256) void ht_pot_kernel(const double* __restrict__ 
     }
     __syncthreads();
     const int Gk = nk[0], Tk = nk[1];
-    if (t < HT_MAXN) {
+    if (t < FM_MAXN) {
       if (t < Gk) {
         gcount[sq.g0 + gid[t]] += 1;
         double a = 0.0;
-        for (int j = 0; j < Tk; ++j) a += ht_overlap(gb[t], tb[j], false);
+        for (int j = 0; j < Tk; ++j) a += fm_overlap(gb[t], tb[j], false);
         rs[t] = a;
       }
-    } else if (t - HT_MAXN < Tk) {
-      const int j = t - HT_MAXN;
+    } else if (t - FM_MAXN < Tk) {
+      const int j = t - FM_MAXN;
       tcount[sq.t0 + tid_[j]] += 1;
       double a = 0.0;
-      for (int i = 0; i < Gk; ++i) a += ht_overlap(gb[i], tb[j], false);
+      for (int i = 0; i < Gk; ++i) a += fm_overlap(gb[i], tb[j], false);
       cs[j] = a;
     }
     __syncthreads();
     for (int p = t; p < Gk * Tk; p += 256) {
 #pragma clang fp contract(off)
       const int i = p / Tk, j = p - i * Tk;
-      const double s = ht_overlap(gb[i], tb[j], false);
+      const double s = fm_overlap(gb[i], tb[j], false);
       if (s > 0.0) {
         const int c = gid[i] * sq.T + tid_[j];
         const double d = cs[j] + rs[i] - s;
@@ -362,15 +252,15 @@ __global__ __launch_bounds__(64) void ht_match_kernel(const double* __restrict__
                                                       const int* __restrict__ tkeep, const double* __restrict__ align,
                                                       int* __restrict__ mc, double* __restrict__ frame_d,
                                                       int* __restrict__ frame_i) {
-  constexpr int K = HT_MAXN / 64;
-  __shared__ HtBox gb[HT_MAXN], tb[HT_MAXN];
-  __shared__ int gid[HT_MAXN], tid_[HT_MAXN];
-  __shared__ double u[HT_MAXN];
-  __shared__ int row4col[HT_MAXN], col4row[HT_MAXN], path[HT_MAXN];
+  constexpr int K = FM_MAXN / 64;
+  __shared__ FmBox gb[FM_MAXN], tb[FM_MAXN];
+  __shared__ int gid[FM_MAXN], tid_[FM_MAXN];
+  __shared__ double u[FM_MAXN];
+  __shared__ int row4col[FM_MAXN], col4row[FM_MAXN], path[FM_MAXN];
   const int f = blockIdx.x, tid = threadIdx.x;
   double* fd = frame_d + HT_FRAME_D * f;
   int* fi = frame_i + HT_FRAME_I * f;
-  const HtFrame fr = ht_frame(frames, f, nG, nT, nD);
+  const FmFrame fr = fm_frame(frames + 6 * f, nG, nT, nD);
   const int s = frame_seq[f];
   HtSeq sq;
   sq.ok = false;
@@ -380,9 +270,9 @@ __global__ __launch_bounds__(64) void ht_match_kernel(const double* __restrict__
     if (tid < HT_FRAME_D) fd[tid] = __builtin_nan("");
     return;
   }
-  const int G = ht_load_kept((const HtBox*)boxes + fr.go, gkeep + fr.go, g_attr + 4 * fr.go + 3, 4, fr.G, sq.G, tid, gb,
+  const int G = ht_load_kept((const FmBox*)boxes + fr.go, gkeep + fr.go, g_attr + 4 * fr.go + 3, 4, fr.G, sq.G, tid, gb,
                              gid);
-  const int T = ht_load_kept((const HtBox*)boxes + nG + fr.to, tkeep + fr.to, t_id + fr.to, 1, fr.T, sq.T, tid, tb,
+  const int T = ht_load_kept((const FmBox*)boxes + nG + fr.to, tkeep + fr.to, t_id + fr.to, 1, fr.T, sq.T, tid, tb,
                              tid_);
   __syncthreads();
   const double* al = align + sq.cell0;
@@ -390,9 +280,9 @@ __global__ __launch_bounds__(64) void ht_match_kernel(const double* __restrict__
   const int R = tr ? T : G, C = tr ? G : T;
   auto val = [&](int i, int j) {
 #pragma clang fp contract(off)
-    return al[gid[i] * sq.T + tid_[j]] * ht_overlap(gb[i], tb[j], false);
+    return al[gid[i] * sq.T + tid_[j]] * fm_overlap(gb[i], tb[j], false);
   };
-  ht_assign(R, C, tid, u, row4col, col4row, path, [&](int r, int c) { return tr ? -val(c, r) : -val(r, c); });
+  fm_assign(R, C, tid, u, row4col, col4row, path, ht_cost(val, tr));
   double sv[K], value = 0.0;
   int cell[K];
 #pragma unroll
@@ -403,7 +293,7 @@ __global__ __launch_bounds__(64) void ht_match_kernel(const double* __restrict__
     if (r < R && col4row[r] >= 0) {
       const int c4 = col4row[r];
       const int i = tr ? c4 : r, j = tr ? r : c4;
-      sv[k] = ht_overlap(gb[i], tb[j], false);
+      sv[k] = fm_overlap(gb[i], tb[j], false);
       cell[k] = gid[i] * sq.T + tid_[j];
       value += val(i, j);
     }
@@ -419,7 +309,7 @@ __global__ __launch_bounds__(64) void ht_match_kernel(const double* __restrict__
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const bool hit = sv[k] >= thr;
-      n += ht_count(hit);
+      n += fm_count(hit);
       if (hit) {
         loc += sv[k];
         atomicAdd(smc + (long long)a * GT + cell[k], 1);
@@ -637,7 +527,7 @@ extern "C" int mmmot_hota(const double* boxes, int nG, int nT, int nD, const int
                           double max_occlusion, int prepare, void* work, long long work_bytes, double* frame_d,
                           int* frame_i, double* seq_d, int* seq_i, void* stream) {
   if (nG < 0 || nT < 0 || nD < 0 || NF < 0 || S < 1 || cells < 0 || sumG < 0 || sumT < 0) return MMMOT_EINVAL;
-  if (max_boxes < 0 || max_boxes > HT_MAXN || max_dontcare < 0 || max_dontcare > HT_MAXD) return MMMOT_EINVAL;
+  if (max_boxes < 0 || max_boxes > FM_MAXN || max_dontcare < 0 || max_dontcare > FM_MAXD) return MMMOT_EINVAL;
   if ((long long)cells > (long long)S * HT_MAX_CELLS || (long long)sumG > (long long)S * HT_MAX_IDS ||
       (long long)sumT > (long long)S * HT_MAX_IDS)
     return MMMOT_EINVAL;

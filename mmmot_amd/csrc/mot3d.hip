@@ -109,9 +109,9 @@ __global__ __launch_bounds__(64) void m3_table_kernel(const double* __restrict__
                                                       double* __restrict__ table) {
   __shared__ double px[2][8][64], pz[2][8][64];
   const int f = blockIdx.x, tid = threadIdx.x;
-  const int* fr = frames + 6 * f;
-  if (!cm_frame_ok(fr, nG, nT, nD)) return;
-  const int go = fr[0], G = fr[1], to = fr[2], T = fr[3];
+  const FmFrame fr = fm_frame(frames + 6 * f, nG, nT, nD);
+  if (!fr.ok) return;
+  const int go = fr.go, G = fr.G, to = fr.to, T = fr.T;
   const int off = cell_off[f];
   if (!m3_cells_ok(off, G, T, cells)) return;
   double* tab = table + off;
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(64) void m3_table_kernel(const double* __restrict__
     const int i = idx / T, j = idx - i * T;
     double c;
     if (mode == 2) {
-      c = cm_c(((const CmBox*)boxes)[go + i], ((const CmBox*)boxes)[nG + to + j]);
+      c = cm_c(((const FmBox*)boxes)[go + i], ((const FmBox*)boxes)[nG + to + j]);
     } else {
       c = m3_c(box3d + (size_t)M3_BOX * (go + i), box3d + (size_t)M3_BOX * (nG + to + j), mode == 1, px, pz, tid);
     }
@@ -136,7 +136,7 @@ struct M3TableCost {
   const double* sigma;  // track score of the frame's tracker objects
   double* msig;         // pass A: matched score per ground-truth object of the frame, or null
   typedef const double* Row;
-  __device__ __forceinline__ void bind(const CmBox*, const CmBox*) const {}  // the 2D boxes are not the cost here
+  __device__ __forceinline__ void bind(const FmBox*, const FmBox*) const {}  // the 2D boxes are not the cost here
   __device__ __forceinline__ Row row(bool tr, int i) const { return tr ? tab + kept[i] : tab + (size_t)i * T0; }
   __device__ __forceinline__ double cell(Row rb, bool tr, int j) const {
     return tr ? rb[(size_t)j * T0] : rb[kept[j]];
@@ -159,20 +159,20 @@ __global__ __launch_bounds__(64) void m3_frame_kernel(const double* __restrict__
                                                       double max_occlusion, double* __restrict__ msig,
                                                       double* __restrict__ frame_d, int* __restrict__ frame_i,
                                                       int* __restrict__ gt_out) {
-  __shared__ int kept[CM_MAXN];
+  __shared__ int kept[FM_MAXN];
   const int f = blockIdx.x, tid = threadIdx.x, level = lev0 + blockIdx.y;
-  const int* fr = frames + 6 * f;
+  const FmFrame fr = fm_frame(frames + 6 * f, nG, nT, nD);
   double* fd = frame_d + 2 * ((size_t)level * NF + f);
   int* fi = frame_i + 6 * ((size_t)level * NF + f);
-  if (!cm_frame_ok(fr, nG, nT, nD) || !m3_cells_ok(cell_off[f], fr[1], fr[3], cells)) {
+  if (!fr.ok || !m3_cells_ok(cell_off[f], fr.G, fr.T, cells)) {
     cm_frame_mark(fd, fi);
     return;
   }
-  const int go = fr[0], G = fr[1], to = fr[2], T0 = fr[3], dof = fr[4], D = fr[5];
+  const int go = fr.go, G = fr.G, to = fr.to, T0 = fr.T, dof = fr.dof, D = fr.D;
   const double th = level == levels ? -INFINITY : thr[level];
   int T = 0;
 #pragma unroll
-  for (int k = 0; k < CM_MAXN / 64; ++k) {
+  for (int k = 0; k < FM_MAXN / 64; ++k) {
     const int j = k * 64 + tid;
     const bool keep = j < T0 && sigma[to + j] >= th;
     const unsigned long long mask = __ballot(keep);
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(64) void m3_frame_kernel(const double* __restrict__
   cf.kept = kept;
   cf.sigma = sigma + to;
   cf.msig = level == levels ? msig + go : nullptr;
-  cm_frame_body(cf, (const CmBox*)boxes + go, (const CmBox*)boxes + nG + to, (const CmBox*)boxes + nG + nT + dof, G, T,
+  cm_frame_body(cf, (const FmBox*)boxes + go, (const FmBox*)boxes + nG + to, (const FmBox*)boxes + nG + nT + dof, G, T,
                 D, go, to, g_attr, t_attr, gate, min_height, max_truncation, max_occlusion, fd, fi,
                 gt_out + (size_t)level * 2 * nG);
 }

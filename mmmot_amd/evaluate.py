@@ -48,6 +48,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .torch_ops import CLEAR_MOT_MAX_BOXES, CLEAR_MOT_MAX_DONTCARE, CLEAR_MOT_SEQ_INTS, clear_mot_layout
+from .torch_ops import FP64_SECTIONS, sections
 from .torch_ops import (HOTA_ALPHAS, HOTA_FRAME_D, HOTA_FRAME_I, HOTA_MAX_CELLS, HOTA_MAX_IDS, HOTA_SEQ_D, HOTA_SEQ_I,
                         hota_layout)
 from .torch_ops import MOT3D_BOX, MOT3D_MAX_LEVELS, MOT3D_MODES, mot3d_layout
@@ -368,6 +369,25 @@ def finish(p, out):
     return m
 
 
+def upload(p, inp, n_in, device):
+    """the tables ``p`` of an evaluator call as its one int32 block on ``device`` (``inp``, ``n_in``: the operator's
+    input layout): one pinned block, the fp64 sections as their bit patterns, one asynchronous copy"""
+    import torch
+    host = torch.empty(n_in, dtype=torch.int32, pin_memory=device != 'meta')
+    h = host.numpy()
+    for name, (o, n) in inp.items():
+        if name in FP64_SECTIONS:
+            h[o:o + n].view(np.float64)[:] = np.asarray(p[name], np.float64).reshape(-1)
+        else:
+            h[o:o + n] = np.asarray(p[name]).reshape(-1)
+    return host.to(device, non_blocking=True)
+
+
+def read_back(res, outl):
+    """an evaluator's result block -> its sections (``outl``: the operator's output layout) as numpy arrays"""
+    return sections(res.cpu().numpy(), outl)
+
+
 def evaluate_sequences(gt, tracker, cls='car', min_overlap=0.5, max_truncation=0, min_height=25, max_occlusion=2,
                        device='cuda'):
     """CLEAR-MOT statistics of tracker Labels against ground-truth Labels (one Labels of S sequences, or a list with
@@ -375,20 +395,10 @@ def evaluate_sequences(gt, tracker, cls='car', min_overlap=0.5, max_truncation=0
     import torch
     p = pack(gt, tracker)
     p['cls'] = cls
-    inp, outl, n_in, n_out = clear_mot_layout(p['sizes'])
-    host = torch.empty(n_in, dtype=torch.int32, pin_memory=True)
-    h = host.numpy()
-    for name, (o, n) in inp.items():
-        if name == 'boxes':
-            h[o:o + n].view(np.float64)[:] = p['boxes'].reshape(-1)
-        else:
-            h[o:o + n] = np.asarray(p[name]).reshape(-1)
-    dev = host.to(device, non_blocking=True)
-    res = torch.ops.mmmot.clear_mot(dev, p['sizes'], [float(min_overlap), float(min_height), float(max_truncation),
-                                                      float(max_occlusion)])
-    r = res.cpu().numpy()
-    out = {name: (r[o:o + n].view(np.float64) if name.endswith('_d') else r[o:o + n]) for name, (o, n) in outl.items()}
-    return finish(p, out)
+    inp, outl, n_in, _ = clear_mot_layout(p['sizes'])
+    res = torch.ops.mmmot.clear_mot(upload(p, inp, n_in, device), p['sizes'],
+                                    [float(min_overlap), float(min_height), float(max_truncation), float(max_occlusion)])
+    return finish(p, read_back(res, outl))
 
 
 def sequences_of(part, gt_path):
@@ -609,17 +619,8 @@ def hota_sequences(gt, tracker, cls='car', prepare='kitti', max_truncation=0, mi
 def run_hota(p, params, device='cuda'):
     """the tables of ``pack_hota`` through torch.ops.mmmot.hota -> the output sections as numpy arrays"""
     import torch
-    inp, outl, n_in, n_out, _ = hota_layout(p['sizes'])
-    host = torch.empty(n_in, dtype=torch.int32, pin_memory=True)
-    h = host.numpy()
-    for name, (o, n) in inp.items():
-        if name == 'boxes':
-            h[o:o + n].view(np.float64)[:] = p['boxes'].reshape(-1)
-        else:
-            h[o:o + n] = np.asarray(p[name]).reshape(-1)
-    dev = host.to(device, non_blocking=True)
-    r = torch.ops.mmmot.hota(dev, p['sizes'], params).cpu().numpy()
-    return {name: (r[o:o + n].view(np.float64) if name.endswith('_d') else r[o:o + n]) for name, (o, n) in outl.items()}
+    inp, outl, n_in, _, _ = hota_layout(p['sizes'])
+    return read_back(torch.ops.mmmot.hota(upload(p, inp, n_in, device), p['sizes'], params), outl)
 
 
 def evaluate_hota(result_sha, root, part='all', gt_path='./data/tracking', cls=None, device='cuda'):
@@ -807,16 +808,8 @@ def finish_3d(p, out, levels, overlap):
 
 def upload_3d(p, sizes, device):
     """the tables of ``pack_3d`` as the one int32 block of mmmot::mot3d on ``device``"""
-    import torch
     inp, _, n_in, _ = mot3d_layout(sizes)
-    host = torch.empty(n_in, dtype=torch.int32, pin_memory=device != 'meta')
-    h = host.numpy()
-    for name, (o, n) in inp.items():
-        if name in ('boxes', 'box3d', 'sigma'):
-            h[o:o + n].view(np.float64)[:] = np.asarray(p[name], np.float64).reshape(-1)
-        else:
-            h[o:o + n] = np.asarray(p[name]).reshape(-1)
-    return host.to(device, non_blocking=True)
+    return upload(p, inp, n_in, device)
 
 
 def overlap_tables(gt, tracker, overlap='3d', device='cuda'):
@@ -849,12 +842,9 @@ def evaluate_3d_sequences(gt, tracker, cls='car', overlap='3d', min_iou=0.25, le
     p['cls'] = cls
     gate = float(min_overlap) if overlap == '2d' else 1.0 - float(min_iou)
     sizes = list(p['sizes']) + [p['cells'], levels, MOT3D_MODES[overlap]]
-    outl = mot3d_layout(sizes)[1]
-    r = torch.ops.mmmot.mot3d(upload_3d(p, sizes, device), sizes, [gate, float(min_height), float(max_truncation),
-                                                                   float(max_occlusion)]).cpu().numpy()
-    out = {name: (r[o:o + n].view(np.float64) if name in ('frame_d', 'seq_d', 'thr') else r[o:o + n])
-           for name, (o, n) in outl.items()}
-    return finish_3d(p, out, levels, overlap)
+    res = torch.ops.mmmot.mot3d(upload_3d(p, sizes, device), sizes,
+                                [gate, float(min_height), float(max_truncation), float(max_occlusion)])
+    return finish_3d(p, read_back(res, mot3d_layout(sizes)[1]), levels, overlap)
 
 
 def evaluate_3d(result_sha, root, part='all', gt_path='./data/tracking', cls=None, overlap='3d', min_iou=0.25,

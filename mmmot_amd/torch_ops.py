@@ -72,6 +72,50 @@ def _lookup(engine, plan):
         raise RuntimeError('mmmot: stale engine / plan handle (the owning TrackingNet or BatchPlan was released)')
 
 
+_OPS = []
+
+
+def _ops():
+    """the launchers of the operators below, made at the first call (importing this module loads no library)"""
+    if not _OPS:
+        from .ops import HipOps
+        _OPS.append(HipOps())
+    return _OPS[0]
+
+
+def _upload(device, *parts):
+    """Host tables (tensors or arrays, each flattened to int32) -> one device slice per part.  ONE pinned block and ONE
+    asynchronous copy (a pageable one would wait for the stream); nothing synchronises.  The first slice starts the
+    block."""
+    flat = [torch.as_tensor(p).reshape(-1) for p in parts]
+    ends = list(itertools.accumulate(int(t.numel()) for t in flat))
+    host = torch.empty(ends[-1], dtype=torch.int32, pin_memory=True)
+    for t, a, b in zip(flat, [0] + ends, ends):
+        host[a:b] = t
+    dev = host.to(device, non_blocking=True)
+    return [dev[a:b] for a, b in zip([0] + ends, ends)]
+
+
+FP64_SECTIONS = frozenset(('boxes', 'box3d', 'sigma', 'frame_d', 'seq_d', 'thr'))  # of the packed evaluator blocks
+
+
+def _sections_layout(op, parts):
+    """({name: (offset, int32 count)}, total ints) of the sections (name, count) laid out one after the other"""
+    out, o = {}, 0
+    for name, n in parts:
+        out[name] = (o, n)
+        o += n
+    if o >= 2 ** 31:
+        raise ValueError('mmmot::%s: block exceeds 32-bit offsets' % op)
+    return out, o
+
+
+def sections(block, lay):
+    """{name: its slice} of an int32 block (a tensor or a numpy array) under a layout; fp64 sections as float64"""
+    f64 = torch.float64 if isinstance(block, torch.Tensor) else np.float64
+    return {name: block[o:o + n].view(f64) if name in FP64_SECTIONS else block[o:o + n] for name, (o, n) in lay.items()}
+
+
 def _forward_batch(crops, points, engine, plan):
     eng, pl = _lookup(engine, plan)
     out = eng.forward(pl, crops, points)
@@ -161,7 +205,6 @@ _LIB.impl('forward_pair_appearance', _forward_pair_appearance_meta, 'Meta')
 #       tensors; pairs: a CPU int32 [B, 4] table (N, M, score offset, link offset) - host data, so that the output sizes
 #       are known without a device read (and the Meta kernel can give them).  Returns [out, objective]: out fp32, pair
 #       p's [det L | new L | end L | link N*M] at offset sum over q < p of 3 (N_q + M_q) + N_q M_q; objective fp64 [B].
-_ASSOC_OPS = []
 MAX_ASSOC = 512
 
 
@@ -193,18 +236,11 @@ def associate_layout(pairs, n_scores=None, n_link=None):
 def _associate(det, new, end, link, pairs):
     n_scores = min(int(det.numel()), int(new.numel()), int(end.numel()))
     total, off, max_nm = associate_layout(pairs, n_scores, int(link.numel()))
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
     B = int(pairs.shape[0])
-    # pair table + output offsets in one pinned block: an asynchronous copy (a pageable one would wait for the stream)
-    host = torch.empty(5 * B, dtype=torch.int32, pin_memory=True)
-    host[:4 * B] = pairs.reshape(-1)
-    host[4 * B:] = off
-    table = host.to(det.device, non_blocking=True)
+    table, off = _upload(det.device, pairs, off)
     out = torch.empty(total, dtype=torch.float32, device=det.device)
     obj = torch.empty(B, dtype=torch.float64, device=det.device)
-    _ASSOC_OPS[0].associate_pairs(det, new, end, link, table[:4 * B], B, max_nm, out, table[4 * B:], obj)
+    _ops().associate_pairs(det, new, end, link, table, B, max_nm, out, off, obj)
     return [out, obj]
 
 
@@ -266,21 +302,13 @@ def chain_layout(chains, n_scores=None, n_link=None, op='associate_chains'):
 def _associate_chains(det, new, end, link, chains):
     n_scores = min(int(det.numel()), int(new.numel()), int(end.numel()))
     total, off, max_n, max_L = chain_layout(chains, n_scores, int(link.numel()))
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
     B = int(chains.shape[0])
     if link.numel() == 0:  # no chain has a link (an empty frame between the others): never read, but not a null pointer
         link = det
-    # chain table + output offsets in one pinned block: an asynchronous copy (a pageable one would wait for the stream)
-    host = torch.empty((CHAIN_ROW + 1) * B, dtype=torch.int32, pin_memory=True)
-    host[:CHAIN_ROW * B] = chains.reshape(-1)
-    host[CHAIN_ROW * B:] = off
-    table = host.to(det.device, non_blocking=True)
+    table, off = _upload(det.device, chains, off)
     out = torch.empty(total, dtype=torch.float32, device=det.device)
     obj = torch.empty(B, dtype=torch.float64, device=det.device)
-    _ASSOC_OPS[0].associate_chains(det, new, end, link, table[:CHAIN_ROW * B], B, max_n, max_L, out,
-                                   table[CHAIN_ROW * B:], obj)
+    _ops().associate_chains(det, new, end, link, table, B, max_n, max_L, out, off, obj)
     return [out, obj]
 
 
@@ -371,31 +399,21 @@ def _launch_sequences(det, new, end, link, seqs, nts, max_gap):
     else:
         lay = sequence_layout(seqs, nts, n_scores, int(link.numel()))
     total, off, woff, units, max_n, max_L, max_T = lay
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
-    B, NT = int(seqs.shape[0]), int(nts.numel())
+    B = int(seqs.shape[0])
     if link.numel() == 0:  # no sequence has a link: never read, but not a null pointer
         link = det
-    # sequence table + the n_t in one pinned block: an asynchronous copy (a pageable one would wait for the stream)
-    host = torch.empty(SEQ_ROW * B + NT, dtype=torch.int32, pin_memory=True)
-    rows = host[:SEQ_ROW * B].view(B, SEQ_ROW)
-    rows[:, :4] = seqs
-    rows[:, 4] = off
-    rows[:, 5] = woff
-    host[SEQ_ROW * B:] = nts
-    table = host.to(det.device, non_blocking=True)
+    # rows of SEQ_ROW ints: the sequence's table row, its output offset, its workspace offset
+    table, nts = _upload(det.device, np.column_stack([seqs.numpy(), off.numpy(), woff.numpy()]), nts)
     out = torch.empty(total, dtype=torch.float32, device=det.device)
     ids = torch.empty(n_scores, dtype=torch.int32, device=det.device)
     obj = torch.empty(B, dtype=torch.float64, device=det.device)
     info = torch.empty((B, 4), dtype=torch.int32, device=det.device)
     ws = torch.empty(units, dtype=torch.float64, device=det.device)
-    args = (det.contiguous(), new.contiguous(), end.contiguous(), link.contiguous(), table[:SEQ_ROW * B],
-            table[SEQ_ROW * B:], B, max_T, max_n, max_L)
+    args = (det.contiguous(), new.contiguous(), end.contiguous(), link.contiguous(), table, nts, B, max_T, max_n, max_L)
     if max_gap:
-        _ASSOC_OPS[0].associate_sequences_gap(*args, int(max_gap), out, ids, obj, info, ws)
+        _ops().associate_sequences_gap(*args, int(max_gap), out, ids, obj, info, ws)
     else:
-        _ASSOC_OPS[0].associate_sequences(*args, out, ids, obj, info, ws)
+        _ops().associate_sequences(*args, out, ids, obj, info, ws)
     return [out, ids, obj, info]
 
 
@@ -526,20 +544,11 @@ def _track_launch(op, layout, blocks, table, frame_idx, state, max_n):
                          % (op, TRACK_STATE_INTS))
     if max_n and (max_n < need or max_n > MAX_ASSOC):
         raise ValueError('mmmot::%s: max_n %d does not cover the table (%d)' % (op, max_n, need))
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
-    B = int(table.shape[0])
-    a, b = table.numel(), table.numel() + B
-    host = torch.empty(b + frame_idx.numel(), dtype=torch.int32, pin_memory=True)
-    host[:a] = table.reshape(-1)
-    host[a:b] = off
-    host[b:] = frame_idx.reshape(-1)
-    dev = host.to(blocks.device, non_blocking=True)
+    tab, off, fidx = _upload(blocks.device, table, off, frame_idx)
     ids = torch.empty(total, dtype=torch.int32, device=blocks.device)
     if blocks.numel() == 0:  # entries without a detection: never read, but not a null pointer
-        blocks = dev.view(torch.float32)
-    getattr(_ASSOC_OPS[0], op)(blocks, dev[:a], dev[a:b], dev[b:], B, max_n or need, state, ids)
+        blocks = tab.view(torch.float32)
+    getattr(_ops(), op)(blocks, tab, off, fidx, int(table.shape[0]), max_n or need, state, ids)
     return ids
 
 
@@ -595,23 +604,12 @@ def _track_launch_multi(op, layout, blocks, table, frame_idx, seq_start, states,
         raise ValueError('mmmot::%s: blocks must be a contiguous fp32 tensor on the states\' device' % op)
     if max_n and (max_n < need or max_n > MAX_ASSOC):
         raise ValueError('mmmot::%s: max_n %d does not cover the table (%d)' % (op, max_n, need))
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
     B, S = int(table.shape[0]), int(states.shape[0])
-    a, b = table.numel(), table.numel() + B
-    c = b + frame_idx.numel()
-    host = torch.empty(c + S + 1, dtype=torch.int32, pin_memory=True)
-    host[:a] = table.reshape(-1)
-    host[a:b] = off
-    host[b:c] = frame_idx.reshape(-1)
-    host[c:] = seq_start
-    dev = host.to(blocks.device, non_blocking=True)
+    tab, off, fidx, start = _upload(blocks.device, table, off, frame_idx, seq_start)
     ids = torch.empty(total, dtype=torch.int32, device=blocks.device)
     if blocks.numel() == 0:  # entries without a detection: never read, but not a null pointer
-        blocks = dev.view(torch.float32)
-    _ASSOC_OPS[0].track_ids_multi(blocks, dev[:a], dev[a:b], dev[b:c], dev[c:], S, B, max_n or need, states, ids,
-                                  chains=chains)
+        blocks = tab.view(torch.float32)
+    _ops().track_ids_multi(blocks, tab, off, fidx, start, S, B, max_n or need, states, ids, chains=chains)
     return ids
 
 
@@ -662,15 +660,7 @@ def clear_mot_layout(sizes):
     if len(sizes) != 6 or min(sizes) < 0 or sizes[5] < 1:
         raise ValueError('mmmot::clear_mot: sizes must be [nG, nT, nD, NF, NTr, S] with S >= 1, got %s' % (list(sizes),))
     nG, nT, nD, NF, NTr, S = (int(v) for v in sizes)
-
-    def lay(parts):
-        out, o = {}, 0
-        for name, n in parts:
-            out[name] = (o, n)
-            o += n
-        if o >= 2 ** 31:
-            raise ValueError('mmmot::clear_mot: block exceeds 32-bit offsets')
-        return out, o
+    lay = lambda parts: _sections_layout('clear_mot', parts)
 
     inp, n_in = lay([('boxes', 8 * (nG + nT + nD)), ('frames', 6 * NF), ('g_attr', 3 * nG), ('t_attr', 2 * nT),
                      ('traj_off', NTr + 1), ('traj_obj', nG), ('seq_off', 2 * (S + 1))])
@@ -685,18 +675,11 @@ def _clear_mot(packed, sizes, params):
         raise ValueError('mmmot::clear_mot: packed must be a contiguous int32 [%d] block for sizes %s' % (n_in, list(sizes)))
     if len(params) != 4:
         raise ValueError('mmmot::clear_mot: params = [min_overlap, min_height, max_truncation, max_occlusion]')
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
     nG, nT, nD, NF, NTr, S = (int(v) for v in sizes)
     res = torch.empty(n_out, dtype=torch.int32, device=packed.device)
-    sec = lambda buf, lay, name: buf[lay[name][0]:lay[name][0] + lay[name][1]]
-    i = lambda name: sec(packed, inp, name)
-    o = lambda name: sec(res, outl, name)
-    _ASSOC_OPS[0].clear_mot(i('boxes').view(torch.float64), nG, nT, nD, i('frames'), NF, i('g_attr'), i('t_attr'),
-                            i('traj_off'), i('traj_obj'), NTr, i('seq_off'), S, params,
-                            o('frame_d').view(torch.float64), o('frame_i'), o('gt_out'), o('traj_i'),
-                            o('seq_d').view(torch.float64), o('seq_i'))
+    i, o = sections(packed, inp), sections(res, outl)
+    _ops().clear_mot(i['boxes'], nG, nT, nD, i['frames'], NF, i['g_attr'], i['t_attr'], i['traj_off'], i['traj_obj'], NTr,
+                     i['seq_off'], S, params, o['frame_d'], o['frame_i'], o['gt_out'], o['traj_i'], o['seq_d'], o['seq_i'])
     return res
 
 
@@ -735,15 +718,7 @@ def hota_layout(sizes):
                          % (CLEAR_MOT_MAX_BOXES, CLEAR_MOT_MAX_DONTCARE))
     if cells > S * HOTA_MAX_CELLS or max(sumG, sumT) > S * HOTA_MAX_IDS:
         raise ValueError('mmmot::hota: the ID tables exceed %d cells or %d IDs per sequence' % (HOTA_MAX_CELLS, HOTA_MAX_IDS))
-
-    def lay(parts):
-        out, o = {}, 0
-        for name, n in parts:
-            out[name] = (o, n)
-            o += n
-        if o >= 2 ** 31:
-            raise ValueError('mmmot::hota: block exceeds 32-bit offsets')
-        return out, o
+    lay = lambda parts: _sections_layout('hota', parts)
 
     inp, n_in = lay([('boxes', 8 * (nG + nT + nD)), ('frames', 6 * NF), ('frame_seq', NF), ('g_attr', 4 * nG),
                      ('t_id', nT), ('seq_tab', HOTA_SEQ_TAB * (S + 1))])
@@ -759,19 +734,13 @@ def _hota(packed, sizes, params):
         raise ValueError('mmmot::hota: packed must be a contiguous int32 [%d] block for sizes %s' % (n_in, list(sizes)))
     if len(params) != 4 or params[3] not in (0., 1.):
         raise ValueError('mmmot::hota: params = [min_height, max_truncation, max_occlusion, prepare (0 or 1)]')
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
     nG, nT, nD, NF, S, cells, sumG, sumT, max_boxes, max_dontcare = (int(v) for v in sizes)
     res = torch.empty(n_out, dtype=torch.int32, device=packed.device)
     work = torch.empty(n_work, dtype=torch.int32, device=packed.device)
-    sec = lambda buf, lay, name: buf[lay[name][0]:lay[name][0] + lay[name][1]]
-    i = lambda name: sec(packed, inp, name)
-    o = lambda name: sec(res, outl, name)
-    _ASSOC_OPS[0].hota(i('boxes').view(torch.float64), nG, nT, nD, i('frames'), NF, i('frame_seq'), i('g_attr'),
-                       i('t_id'), i('seq_tab'), S, cells, sumG, sumT, max_boxes, max_dontcare, params[:3],
-                       int(params[3]), work, o('frame_d').view(torch.float64), o('frame_i'),
-                       o('seq_d').view(torch.float64), o('seq_i'))
+    i, o = sections(packed, inp), sections(res, outl)
+    _ops().hota(i['boxes'], nG, nT, nD, i['frames'], NF, i['frame_seq'], i['g_attr'], i['t_id'], i['seq_tab'], S, cells,
+                sumG, sumT, max_boxes, max_dontcare, params[:3], int(params[3]), work, o['frame_d'], o['frame_i'],
+                o['seq_d'], o['seq_i'])
     return res
 
 
@@ -810,15 +779,7 @@ def mot3d_layout(sizes):
     if cells >= 2 ** 31:
         raise ValueError('mmmot::mot3d: the overlap table exceeds 32-bit offsets')
     Lv = levels + 1
-
-    def lay(parts):
-        out, o = {}, 0
-        for name, n in parts:
-            out[name] = (o, n)
-            o += n
-        if o >= 2 ** 31:
-            raise ValueError('mmmot::mot3d: block exceeds 32-bit offsets')
-        return out, o
+    lay = lambda parts: _sections_layout('mot3d', parts)
 
     inp, n_in = lay([('boxes', 8 * (nG + nT + nD)), ('box3d', 2 * MOT3D_BOX * (nG + nT)), ('sigma', 2 * nT),
                      ('frames', 6 * NF), ('cell_off', NF), ('g_attr', 3 * nG), ('t_attr', 2 * nT),
@@ -837,23 +798,17 @@ def mot3d_run(packed, sizes, params):
         raise ValueError('mmmot::mot3d: packed must be a contiguous int32 [%d] block for sizes %s' % (n_in, list(sizes)))
     if len(params) != 4:
         raise ValueError('mmmot::mot3d: params = [gate, min_height, max_truncation, max_occlusion]')
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
     nG, nT, nD, NF, NTr, S, cells, levels, mode = (int(v) for v in sizes)
     res = torch.empty(n_out, dtype=torch.int32, device=packed.device)
     table = torch.empty(cells, dtype=torch.float64, device=packed.device)
     msig = torch.full((nG,), float('-inf'), dtype=torch.float64, device=packed.device)
-    sec = lambda buf, lay, name: buf[lay[name][0]:lay[name][0] + lay[name][1]]
-    i = lambda name: sec(packed, inp, name)
-    o = lambda name: sec(res, outl, name)
-    d = lambda t: t.view(torch.float64)
+    i, o = sections(packed, inp), sections(res, outl)
 
     def phase(k, m):
-        _ASSOC_OPS[0].mot3d(d(i('boxes')), d(i('box3d')), d(i('sigma')), nG, nT, nD, i('frames'), i('cell_off'), NF,
-                            i('g_attr'), i('t_attr'), i('traj_off'), i('traj_obj'), NTr, i('seq_off'), S, mode, levels,
-                            k, params, table, cells, m, d(o('frame_d')), o('frame_i'), o('gt_out'), o('traj_i'),
-                            d(o('seq_d')), o('seq_i'), d(o('thr')), o('reach'))
+        _ops().mot3d(i['boxes'], i['box3d'], i['sigma'], nG, nT, nD, i['frames'], i['cell_off'], NF, i['g_attr'],
+                     i['t_attr'], i['traj_off'], i['traj_obj'], NTr, i['seq_off'], S, mode, levels, k, params, table,
+                     cells, m, o['frame_d'], o['frame_i'], o['gt_out'], o['traj_i'], o['seq_d'], o['seq_i'], o['thr'],
+                     o['reach'])
 
     phase(0, msig)
     if levels:
@@ -884,18 +839,10 @@ def _generate_gt(ids, cls, chains):
     if ids.dtype != torch.int32 or cls.dtype != torch.int32 or ids.dim() != 1 or cls.dim() != 1:
         raise ValueError('mmmot::generate_gt: ids and cls must be flat int32 tensors')
     total, off, max_n, max_L = chain_layout(chains, min(int(ids.numel()), int(cls.numel())), op='generate_gt')
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
     B = int(chains.shape[0])
-    # chain table + output offsets in one pinned block: an asynchronous copy (a pageable one would wait for the stream)
-    host = torch.empty((CHAIN_ROW + 1) * B, dtype=torch.int32, pin_memory=True)
-    host[:CHAIN_ROW * B] = chains.reshape(-1)
-    host[CHAIN_ROW * B:] = off
-    table = host.to(ids.device, non_blocking=True)
+    table, off = _upload(ids.device, chains, off)
     out = torch.empty(total, dtype=torch.float32, device=ids.device)
-    _ASSOC_OPS[0].generate_gt(ids.contiguous(), cls.contiguous(), table[:CHAIN_ROW * B], B, max_n, max_L, out,
-                              table[CHAIN_ROW * B:])
+    _ops().generate_gt(ids.contiguous(), cls.contiguous(), table, B, max_n, max_L, out, off)
     return out
 
 
@@ -951,17 +898,12 @@ def _match_dets(det_xywh, gt_xywh, gt_id, gt_name, frames, car, dontcare, max_io
     res[1].zero_()
     if n_det == 0:
         return res
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
     NF = int(frames.shape[0])
-    host = torch.empty(4 * NF, dtype=torch.int32, pin_memory=True)
-    host.copy_(frames.reshape(-1))
-    table = host.to(det_xywh.device, non_blocking=True)
+    table, = _upload(det_xywh.device, frames)
     if n_gt == 0:  # never read (every n_gt is 0), but not a null pointer
         gt_xywh, gt_id, gt_name = det_xywh, res[0], res[0]
-    _ASSOC_OPS[0].match_dets(det_xywh.contiguous(), gt_xywh.contiguous(), gt_id.contiguous(), gt_name.contiguous(), table,
-                             NF, car, dontcare, max_iou, max_n, res[0], res[1])
+    _ops().match_dets(det_xywh.contiguous(), gt_xywh.contiguous(), gt_id.contiguous(), gt_name.contiguous(), table, NF,
+                      car, dontcare, max_iou, max_n, res[0], res[1])
     return res
 
 
@@ -1032,10 +974,7 @@ def adam_pack(ptrs, scal, device):
 
 
 def _adam_step(chunks, ptrs, scal, beta1, beta2, eps):
-    if not _ASSOC_OPS:
-        from .ops import HipOps
-        _ASSOC_OPS.append(HipOps())
-    _ASSOC_OPS[0].adam_step(chunks, ptrs, scal, beta1, beta2, eps)  # checks the tables, packs, uploads, launches
+    _ops().adam_step(chunks, ptrs, scal, beta1, beta2, eps)  # checks the tables, packs, uploads, launches
 
 
 def _adam_step_meta(chunks, ptrs, scal, beta1, beta2, eps):

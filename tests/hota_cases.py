@@ -59,6 +59,31 @@ def random_sequence(rng, counts, n_gid, n_stray, kitti=True, cyclic=0):
     return labels(g, F, True), labels(t, F, False)
 
 
+TWIN_COLUMNS, TWIN_IDS = (1, 66), (301, 300)  # the twin in the smaller column carries the larger ID
+
+
+def twin_sequence(rng):
+    """One sequence of three frames for the per-frame search where the drawn frames do not take it: 70 x 3 (the rows are
+    the tracker side, and ground-truth columns in a lane's second slot), 3 x 70 with the SAME box in the tracker columns
+    TWIN_COLUMNS (equal costs in two lanes, one of them in the second slot), and 0 x 2 (no row).  Boxes sit on a grid
+    and overlap their partner only; plain main-class rows, every ID in one frame only, so that apart from which twin
+    is taken nothing depends on the choice among equal matchings."""
+    def spot(k, y0=0.):
+        x, y = 20. + 150 * (k % 10), y0 + 20. + 110 * (k // 10)
+        return np.array([x, y, x + 100, y + 80])
+
+    near = lambda b: b + rng.uniform(-6, 6, 4)
+    g = [[0, 0, k, E.MAIN, 0, 0, *spot(k)] for k in range(70)] + [[0, 1, 200 + k, E.MAIN, 0, 0, *spot(k)] for k in range(3)]
+    t = [[0, 0, 100 + n, E.MAIN, -1, -1, *near(spot(k))] for n, k in enumerate((10, 40, 69))]
+    twin = near(spot(1))
+    partner = {5: near(spot(0)), 69: near(spot(2)), TWIN_COLUMNS[0]: twin, TWIN_COLUMNS[1]: twin}
+    ids = dict(zip(TWIN_COLUMNS, TWIN_IDS))
+    for j in range(70):
+        t.append([0, 1, ids.get(j, 400 + j), E.MAIN, -1, -1, *partner.get(j, spot(j, 3000))])
+    t += [[0, 2, 500 + j, E.MAIN, -1, -1, *spot(j)] for j in range(2)]
+    return labels(g, 3, True), labels(t, 3, False)
+
+
 def distinct_totals(m):
     """totals of all assignments of the smaller side of matrix m, one per set of non-zero cells, descending"""
     m = np.asarray(m, np.float64)
@@ -102,7 +127,8 @@ def conditions_met(gt, tr, prepare, matchings):
     return True
 
 
-# name -> (first seed, prepare, matchings checked, [per sequence: kwargs of random_sequence with the frame counts])
+# name -> (first seed, prepare, matchings checked, [per sequence: kwargs of random_sequence with the frame counts, or
+# make = another generator])
 def _counts(rng, n, choices):
     return [tuple(int(v) for v in rng.choice(choices, 2)) for _ in range(n)]
 
@@ -123,6 +149,8 @@ def specs():
                                                    n_stray=128)]),
         # more IDs than a wave has lanes: G = 70, T = 90, a few boxes a frame
         'wide_ids': (500, None, False, [dict(counts=[(4, 5)] * 40, n_gid=70, n_stray=20, kitti=False, cyclic=3)]),
+        # the tracker side as rows with 70 columns, two equal columns, an empty side
+        'transposed_twins': (600, 'kitti', False, [dict(make=twin_sequence)]),
     }
 
 
@@ -131,8 +159,10 @@ def build(name):
     seed, prepare, matchings, seqs = specs()[name]
     gts, trs, drawn, replaced = [], [], 0, 0
     for kw in seqs:
+        kw = dict(kw)
+        make = kw.pop('make', random_sequence)
         while True:
-            gt, tr = random_sequence(np.random.default_rng(seed), **kw)
+            gt, tr = make(np.random.default_rng(seed), **kw)
             seed += 1
             drawn += 1
             if conditions_met(gt, tr, prepare, matchings):

@@ -20,7 +20,7 @@ ALPHAS = 0.05 * np.arange(1, 20)
 
 
 def iou_matrix(a, b, over_a=False):
-    """IoU (or intersection / area of a) of every box of a [n, 4] with every box of b [m, 4]: cm_overlap's operation
+    """IoU (or intersection / area of a) of every box of a [n, 4] with every box of b [m, 4]: fm_overlap's operation
     order, every operation rounded on its own"""
     a, b = np.asarray(a, np.float64).reshape(-1, 4), np.asarray(b, np.float64).reshape(-1, 4)
     x1 = np.maximum(a[:, None, 0], b[None, :, 0])

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import clear_mot_ref
+import hota_cases
 from test_clear_mot_cpu import CASES, FILES, GOLDEN, ROOT, check_record, golden
 from mmmot_amd import evaluate as E
 
@@ -106,6 +107,19 @@ def test_random_instances_equal_the_serial_restatement(random_cases):
     whole = E.evaluate_sequences([c[0] for c in random_cases], [c[1] for c in random_cases])
     assert whole.tps == [c[2]['tps'][0] for c in random_cases] and whole.fps == [c[2]['fps'][0] for c in random_cases]
     assert whole.id_switches == sum(c[2]['id_switches'] for c in random_cases)
+
+
+def test_transposed_rows_equal_columns_and_an_empty_side():
+    """hota_cases.twin_sequence (70 x 3, 3 x 70 with the same tracker box in two columns, 0 x 2) against the serial
+    restatement; of the two equal columns the device takes the smaller one, the restatement either"""
+    gt, tr = hota_cases.twin_sequence(np.random.default_rng(600))
+    want = {k: np.asarray(v) for k, v in clear_mot_ref.evaluate(gt, tr).items()}
+    twin = np.isin(want['gt_tracker'], hota_cases.TWIN_IDS)
+    assert twin.sum() == 1
+    want['gt_tracker'] = np.where(twin, hota_cases.TWIN_IDS[0], want['gt_tracker'])
+    m = E.evaluate_sequences(gt, tr)
+    check_record(lambda k: getattr(m, k), want, exact_sums=False)
+    assert (m.tp, m.fp, m.fn) == (6, 69, 67)
 
 
 def test_drop_in_returns_the_golden_tuple_and_writes_the_stats_file(tmp_path):

@@ -121,6 +121,14 @@ def test_larger_frames_and_many_ids(cases, name):
     assert h.IDTP > 0 and h.IDFN > 0 and h.IDFP > 0
 
 
+def test_transposed_rows_equal_columns_and_an_empty_side(cases):
+    """hota_cases.twin_sequence: every field - each twin's ID occurs once, so the record is the same whichever is taken"""
+    gts, trs, prepare, _, want = cases['transposed_twins']
+    h = E.hota_sequences(gts, trs, prepare=prepare)
+    check_record(h, want, gts, trs)
+    assert h.TP[0] == 6 and h.IDTP == 6 and h.n_gt == 73 and h.n_tr == 75
+
+
 def test_two_calls_are_bit_equal(cases):
     for name in ('small_kitti', 'full_frame', 'wide_ids'):
         gts, trs, prepare, _, _ = cases[name]

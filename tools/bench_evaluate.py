@@ -12,7 +12,11 @@ read-back, the ratios) and its single operating point (levels = 0) on 3D scenes 
 (tests/mot3d_cases.random_sequence), beside the NumPy restatement tests/mot3d_ref.py, which is run once.  Whether the
 two agree in the thresholds and the per-level counters is reported.  Writes <out>/bench_mot3d.json.
 
+--clear-mot times ``evaluate_sequences`` (packing, one upload, the launches of mmmot_clear_mot, one read-back, the ratios)
+on the workload of --hota.  Writes <out>/bench_clear_mot.json.
+
     python tools/bench_evaluate.py --hota --out <dir> [--repeats 3]
+    python tools/bench_evaluate.py --clear-mot --out <dir> [--repeats 3]
     python tools/bench_evaluate.py --mot3d --out <dir> [--repeats 3]
 """
 import argparse
@@ -77,6 +81,27 @@ def bench_hota(args):
     print(json.dumps(res))
 
 
+def bench_clear_mot(args):
+    gts, trs = workload()
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, r
+
+    m = E.evaluate_sequences(gts, trs)  # untimed
+    times = [timed(lambda: E.evaluate_sequences(gts, trs))[0] for _ in range(args.repeats)]
+    res = {'sequences': len(FRAMES), 'frames': int(sum(FRAMES)), 'repeats': args.repeats, 'MOTA': float(m.MOTA),
+           'tp': int(m.tp), 'fp': int(m.fp), 'fn': int(m.fn), 'id_switches': int(m.id_switches),
+           'seconds': {'evaluate_sequences': {'min': min(times), 'median': float(np.median(times)), 'max': max(times)}}}
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_clear_mot.json'), 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def bench_mot3d(args):
     import mot3d_cases
     import mot3d_ref
@@ -122,13 +147,16 @@ def bench_mot3d(args):
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--hota', action='store_true', help='time hota_sequences beside the NumPy restatement')
+    ap.add_argument('--clear-mot', action='store_true', help='time evaluate_sequences')
     ap.add_argument('--mot3d', action='store_true', help='time evaluate_3d_sequences beside the NumPy restatement')
     ap.add_argument('--out', required=True)
     ap.add_argument('--repeats', type=int, default=3)
     args = ap.parse_args()
-    if not (args.hota or args.mot3d):
-        ap.error('nothing to measure: give --hota or --mot3d')
+    if not (args.hota or args.clear_mot or args.mot3d):
+        ap.error('nothing to measure: give --hota, --clear-mot or --mot3d')
     if args.hota:
         bench_hota(args)
+    if args.clear_mot:
+        bench_clear_mot(args)
     if args.mot3d:
         bench_mot3d(args)
