@@ -523,6 +523,49 @@ int mmmot_align_points(const float* pts, int F, int Q, int NS, const int* seg_ro
                        float* out, long out_row0, int ldo, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Gap filling of tracked sequences (csrc/fill_tracks.hip), additive in ABI 10: one interpolated box
+ * for every LISTED frame that a track skipped between two of its observations, for S sequences in five launches
+ * whatever the number of frames, sequences, tracks and holes.
+ *   det         [L][12] fp32 per detection: 2D box x1 y1 x2 y2, h w l, x y z (camera frame), rotation_y, score
+ *   ids         [L] track ID per detection, -1 = rejected
+ *   frame_start [F+1] detections of listed frame p = [frame_start[p], frame_start[p+1]); 0 first, L last, non-decreasing
+ *   frame_no    [F] frame numbers, strictly increasing inside a sequence
+ *   seq_start   [S+1] listed frames of sequence s = [seq_start[s], seq_start[s+1]); 0 first, F last, non-decreasing
+ *   xf          [F][max_fill+1][MMMOT_FILL_REC] fp64, or NULL for a standing camera.  Record (p, k-1), for the listed
+ *               frames p and p+k of one sequence: [0, 16) C[p<-p+k], a row-vector 4x4 (row-major) that takes camera
+ *               coordinates of frame p+k to those of frame p; [16, 32) its inverse; [32] the yaw step dyaw[p<-p+k].
+ *               Records that reach past the end of a sequence are not read.
+ *   wtab        [MMMOT_FILL_MAX+2][MMMOT_FILL_MAX+2] fp64, wtab[n][k] = k / n (host-made, so that a host restatement
+ *               reads the same bits)
+ *   work        [MMMOT_FILL_WORK(L)] ints of scratch
+ *   fill_start  [F+1] out: the new rows of listed frame p = [fill_start[p], fill_start[p+1])
+ *   out         [capacity][12] fp32, out_id [capacity], out_src [capacity][2] (indices of the two source detections)
+ *   info        [S][4] out: status, rows, links filled, links too long (the last three 0 unless status is 0 or ECAPACITY)
+ * A link joins detection i (listed frame pa) and the next detection j (listed frame pb) of the same ID >= 0 in the same
+ * sequence; with n = frame_no[pb] - frame_no[pa] it is filled iff 2 <= n <= max_fill + 1, by one row per listed frame p
+ * strictly between, ordered per frame by ascending ID.  With w = wtab[n][frame_no[p] - frame_no[pa]], all in fp64, every
+ * product and sum rounded on its own, one rounding to fp32 at the store:
+ *   2D box, h w l, score: (1 - w) a + w b;   location: b' = b C[pa<-pb] (b as (x, y, z, 1), columns 0..2, summed in k
+ *   order), the blend of a and b', then times inv C[pa<-p] (both skipped when xf is NULL);   yaw: d = (ry_b +
+ *   dyaw[pa<-pb]) - ry_a wrapped into [-pi, pi) by at most four steps of 2 pi, then ry_a + w d - dyaw[pa<-p], wrapped.
+ * Status, per sequence, never a fault: EDUP an ID twice in one frame, ECONTRACT frame numbers that do not increase (or,
+ * for every sequence of the call, a frame_start / seq_start that breaks the shape above) - such a sequence gets no rows;
+ * ECAPACITY its rows reach past `capacity` - the rows below it are written, nothing past it, the counts are reported.
+ * Returns MMMOT_EINVAL before any launch for S < 1, a negative L / F / capacity, max_fill outside [1, MMMOT_FILL_MAX]
+ * and, with L > 0 and F > 0, a null pointer (xf may be null; out / out_id / out_src may be with capacity = 0).  L = 0 or
+ * F = 0 is a no-op that returns 0.  No allocation, no synchronisation. */
+#define MMMOT_FILL_MAX 30
+#define MMMOT_FILL_REC 33
+#define MMMOT_FILL_WORK(L) (3 * (long)(L) + 1)
+#define MMMOT_FILL_EDUP 1
+#define MMMOT_FILL_ECAPACITY 2
+#define MMMOT_FILL_ECONTRACT 4
+int mmmot_fill_tracks(const float* det, const int* ids, const int* frame_start, const int* frame_no,
+                      const int* seq_start, const double* xf, const double* wtab, int L, int F, int S, int max_fill,
+                      int capacity, int* work, int* fill_start, float* out, int* out_id, int* out_src, int* info,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------
  * Per-detection image preparation: crop with zero padding -> antialiased bilinear
  * resize to S x S -> to_tensor -> normalize = the model input ``dets`` [N][3][S][S].  Replaces, per
  * detection, PIL img.crop(box).resize((S, S), Image.BILINEAR) + torchvision ToTensor/Normalize

@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('MMMOT_LIB_PATH', os.path.join(_HERE, 'libmmmot_hip.so'))  # override: tools' timing-experiment builds
 SOURCES = ['conv3x3.hip', 'hl16_format.hip', 'conv3x3_hl16_patch.hip', 'gemm_rows.hip', 'gemm_wide.hip',
            'gemm_ares.hip', 'gemm_wres.hip', 'gemm_wreg.hip', 'pn_mlp64.hip', 'gram.hip', 'points_gather.hip', 'crop_resize.hip', 'crop_augment.hip','small_kernels.hip', 'backward.hip', 'train.hip', 'train_vgg.hip', 'gemm_tn_f16.hip',
-           'assign.hip', 'assign_chain.hip', 'assign_sequence.hip','track_ids.hip', 'clear_mot.hip', 'hota.hip', 'mot3d.hip','align_points.hip', 'labels.hip', 'adam_step.hip', 'dropout.hip']
+           'assign.hip', 'assign_chain.hip', 'assign_sequence.hip','track_ids.hip', 'clear_mot.hip', 'hota.hip', 'mot3d.hip','align_points.hip', 'fill_tracks.hip', 'labels.hip', 'adam_step.hip', 'dropout.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 HIPFLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 
@@ -142,6 +142,9 @@ SIGNATURES = {
     'mmmot_points_scatter_batched': [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_f],
     # pts, F, Q, NS, seg_row0, xf, chain, out, out_row0, ldo, stream
     'mmmot_align_points': [c_f, c_i, c_i, c_i, c_f, c_f, c_i, c_f, ctypes.c_long, c_i, c_f],
+    # det, ids, frame_start, frame_no, seq_start, xf, wtab, L, F, S, max_fill, capacity, work, fill_start, out, out_id,
+    # out_src, info, stream
+    'mmmot_fill_tracks': [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f],
     'mmmot_selftest_mfma': [c_f, c_f, c_f, c_i, c_f],
     'mmmot_gn_bwd_partial': [c_f, c_i, c_f, c_i, c_i, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_f],
     'mmmot_gn_bwd_finalize': [c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f],

@@ -104,3 +104,23 @@ def transform_record(R, T, imu2velo):
         rec[25 + 12 * c:28 + 12 * c] = t
     rec[64:80] = np.asarray(to_velo, dtype=np.float64).reshape(-1)
     return rec
+
+
+def box_motion(pose_p, pose_q, calib):
+    """The ego motion of the pair (p, q), p the earlier frame, composed for BOX CENTRES: (C, inv C, dyaw).  C is the
+    row-vector 4x4 float64 matrix that does to a camera-frame location of frame q what ``align_pos([R], [T], ..)`` does
+    with (R, T) = ``pair_motion(pose_p, pose_q)``: camera -> LiDAR (``inv(cam.T)``, cam = R0_rect @ Tr_velo_to_cam) ->
+    IMU (``inv(imu2velo.T)``) -> the step q @ R.T + T -> LiDAR (``imu2velo.T``) -> camera (``cam.T``), multiplied in
+    that order: ``[x, y, z, 1] @ C`` is the location in frame p's coordinates.  ``inv C`` (``np.linalg.inv``) takes it
+    back; ``dyaw`` = (rad_q - rad_p)[2] is what ``align_pos`` adds to ``rotation_y``.  ``calib``: the frame-info dict with
+    ``calib/R0_rect``, ``calib/Tr_velo_to_cam`` and ``calib/Tr_imu_to_velo``.  The records of ``mmmot_fill_tracks``
+    (tracks.pack_fill) are made of these."""
+    R, T = pair_motion(pose_p, pose_q)
+    cam = np.asarray(calib['calib/R0_rect'], dtype=np.float64) @ np.asarray(calib['calib/Tr_velo_to_cam'], dtype=np.float64)
+    to_imu, to_velo = imu_matrices(np.asarray(calib['calib/Tr_imu_to_velo'], dtype=np.float64))
+    step = np.eye(4)
+    step[:3, :3] = R.T
+    step[3, :3] = T
+    C = np.linalg.inv(cam.T) @ to_imu @ step @ to_velo @ cam.T
+    dyaw = float(np.asarray(pose_q[1], dtype=np.float64)[2] - np.asarray(pose_p[1], dtype=np.float64)[2])
+    return C, np.linalg.inv(C), dyaw

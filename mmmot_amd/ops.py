@@ -517,6 +517,17 @@ class HipOps:
                                        _iptr(det_id), _iptr(det_cls), self._stream())
         _lib.check(st, 'mmmot_match_dets')
 
+    def fill_tracks(self, det, ids, frame_start, frame_no, seq_start, xf, wtab, L, F, S, max_fill, capacity, work,
+                    fill_start, out, out_id, out_src, info):
+        """Gap filling of S tracked sequences in five launches; see mmmot_fill_tracks.  det / out: fp32 device tensors,
+        xf (or None: a standing camera) / wtab: fp64, the rest int32.  Returns the entry's status instead of raising, so
+        that a caller can tell a refused call (MMMOT_EINVAL) from its results."""
+        d = torch.float64
+        return self.lib.mmmot_fill_tracks(_ptr(det), _iptr(ids), _iptr(frame_start), _iptr(frame_no), _iptr(seq_start),
+                                          _ptr(xf, d), _ptr(wtab, d), int(L), int(F), int(S), int(max_fill),
+                                          int(capacity), _iptr(work), _iptr(fill_start), _ptr(out), _iptr(out_id),
+                                          _iptr(out_src), _iptr(info), self._stream())
+
     def adam_step(self, chunks, ptrs, scal, beta1, beta2, eps):
         """One Adam step of T tensors in one launch; see mmmot_adam_step and mmmot::adam_step (torch_ops.py).  chunks: the
         device int32 [n, 2] chunk table; ptrs / scal: the step's HOST tables, int64 [T, 6] (p, g, m, v, numel, flags) and

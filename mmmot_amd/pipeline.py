@@ -90,8 +90,8 @@ from . import ego
 from .points import align_points_batched, prep_points_batched
 from .association import _raise_status, gap_sequences_table, select, select_chain, unpack_gaps
 from .tracker_glue import queue_scores, queue_solve, queue_solve_chains
-from .torch_ops import SEQ_MAX_GAP
-from .tracks import TrackState, TrackStates, merge_chain_tracks, merge_tracks, window_starts
+from .torch_ops import FILL_MAX, SEQ_MAX_GAP
+from .tracks import TrackState, TrackStates, fill_gaps, merge_chain_tracks, merge_tracks, window_starts
 
 
 class FrameFeed:
@@ -591,7 +591,7 @@ class SequencePipeline:
         self.stats['gap_pairs'] = self.stats.get('gap_pairs', 0) + len(pairs)
         return links
 
-    def run_global(self, feeds, frames_per_encode=16, pairs_per_forward=8, max_gap=1, gap_penalty=0.0):
+    def run_global(self, feeds, frames_per_encode=16, pairs_per_forward=8, max_gap=1, gap_penalty=0.0, fill=0):
         """The whole sequence decided at once: ``run_offline``'s stage A, alignment, trunk and batched pair forwards, then
         ONE min-cost flow over all frames (association.associate_sequence; DESIGN section 11, "Sequences") in place of a
         solve per pair and the ID walk - a unit of flow is a trajectory, its number the track ID.  Needs ``window == 2``.
@@ -611,7 +611,13 @@ class SequencePipeline:
         of the adjacent pairs.  One association.associate_sequence_gaps launch solves the program, one copy brings it
         back; the result carries the blocks of the gaps 2 .. G in ``.gap_scores`` / ``.gap_assignment``.  With fewer
         than G + 1 kept frames the largest gap that fits is used (``.max_gap``).  ``stats['gap_pairs']`` counts the pairs
-        of the gaps above 1, ``stats['pairs']`` all pairs.  ``max_gap = 1`` is the path above, launch for launch."""
+        of the gaps above 1, ``stats['pairs']`` all pairs.  ``max_gap = 1`` is the path above, launch for launch.
+
+        ``fill = F > 0``: behind the solve the frames a trajectory skipped get an interpolated box,
+        ``tracks.fill_gaps(.., max_fill=F)`` over ALL frames of the sequence (the empty ones included; with the feeds'
+        poses and the first feed's calibration when the camera moves) - one more upload, five small launches, one more
+        copy, no forward.  The ``tracks.FilledTracks`` is stored as ``GlobalResult.filled``; ``self.tracks`` and
+        everything else stay as they are.  ``fill = 0``: nothing of this runs and ``.filled`` is None."""
         if self.window != 2:
             raise ValueError('SequencePipeline.run_global assembles the scores of frame pairs: window must be 2, got %d'
                              % self.window)
@@ -620,8 +626,10 @@ class SequencePipeline:
             raise ValueError('frames_per_encode and pairs_per_forward must be >= 1')
         if not 1 <= int(max_gap) <= SEQ_MAX_GAP:
             raise ValueError('SequencePipeline.run_global: max_gap must lie in 1 .. %d, got %s' % (SEQ_MAX_GAP, max_gap))
+        if not 0 <= int(fill) <= FILL_MAX:
+            raise ValueError('SequencePipeline.run_global: fill must lie in 0 .. %d, got %s' % (FILL_MAX, fill))
         moving = _check_poses(feeds)
-        n_frames = len(feeds)
+        n_frames, all_feeds = len(feeds), feeds
         feeds, idx, _ = _skip_empty(feeds, (None, None, None))
         tracks = [np.full(len(f.dets['bbox']), -1, np.int64) for f in feeds]
         frames = self._offline_frames(feeds, K, moving)
@@ -642,6 +650,11 @@ class SequencePipeline:
             if len(frames) >= 2:
                 self.stats['encoded_frames'] += n_frames - len(idx)
         self.tracks = _spread_tracks(tracks, idx, n_frames)
+        if res is not None and int(fill) > 0:
+            res.filled = fill_gaps([f.dets for f in all_feeds], self.tracks,
+                                   poses=[f.pose for f in all_feeds] if moving else None,
+                                   calib=all_feeds[0].info if moving else None, max_fill=int(fill),
+                                   device=self.dev)
         return res
 
 
@@ -656,6 +669,7 @@ class GlobalResult:
         self.scores, self.assignment, self.ids = scores, assignment, ids
         self.n_tracks, self.objective, self.split = n_tracks, objective, split
         self.gap_scores, self.gap_assignment, self.max_gap = list(gap_scores), list(gap_assignment), max_gap
+        self.filled = None  # run_global(fill=F > 0): the tracks.FilledTracks of the whole sequence
 
 
 def assemble_rows(rows, counts):

@@ -96,7 +96,8 @@ def _upload(device, *parts):
     return [dev[a:b] for a, b in zip([0] + ends, ends)]
 
 
-FP64_SECTIONS = frozenset(('boxes', 'box3d', 'sigma', 'frame_d', 'seq_d', 'thr'))  # of the packed evaluator blocks
+FP64_SECTIONS = frozenset(('boxes', 'box3d', 'sigma', 'frame_d', 'seq_d', 'thr',  # of the packed evaluator blocks
+                           'xf', 'wtab'))                                          # of the gap-filling block
 
 
 def _sections_layout(op, parts):
@@ -916,6 +917,63 @@ _LIB.define('match_dets(Tensor det_xywh, Tensor gt_xywh, Tensor gt_id, Tensor gt
             'int dontcare, float max_iou) -> Tensor')
 _LIB.impl('match_dets', _match_dets, 'CUDA')
 _LIB.impl('match_dets', _match_dets_meta, 'Meta')
+
+
+# ---- gap filling of tracked sequences (mmmot_amd/tracks.py; csrc/fill_tracks.hip) -----------------------------------
+#   mmmot::fill_tracks(Tensor packed, int[] sizes) -> Tensor
+#       One interpolated box per listed frame a track skipped, for S sequences (mmmot_fill_tracks: five launches).
+#       packed: ONE device int32 block holding the call's tables in the order of fill_layout()[0] (the fp64 records and
+#       weights first, as their bit patterns; the fp32 detections as theirs), so that a call is one upload; sizes = [L, F,
+#       S, max_fill, capacity, moving (1: the block holds ego-motion records, 0: a standing camera)].  Returns ONE int32
+#       block in the order of fill_layout()[1] (the fp32 rows as their bit patterns), so that a call is one read-back.
+#       The scratch of the entry is allocated here and never read back.
+FILL_MAX = 30   # MMMOT_FILL_MAX
+FILL_REC = 33   # MMMOT_FILL_REC: doubles per ego-motion record (C 16, inv C 16, dyaw)
+FILL_WT = FILL_MAX + 2
+FILL_EDUP, FILL_ECAPACITY, FILL_ECONTRACT = 1, 2, 4
+
+
+def fill_layout(sizes):
+    """({input section: (offset, int32 count)}, {output section: (offset, int32 count)}, input ints, output ints) of a
+    call with sizes = [L, F, S, max_fill, capacity, moving]; the fp64 sections come first (8-byte aligned)."""
+    if len(sizes) != 6 or min(sizes) < 0 or sizes[2] < 1 or sizes[5] > 1:
+        raise ValueError('mmmot::fill_tracks: sizes must be [L, F, S, max_fill, capacity, moving] with S >= 1, got %s'
+                         % (list(sizes),))
+    L, F, S, max_fill, capacity, moving = (int(v) for v in sizes)
+    if not 1 <= max_fill <= FILL_MAX:
+        raise ValueError('mmmot::fill_tracks: max_fill must be in 1 .. %d, got %d' % (FILL_MAX, max_fill))
+    lay = lambda parts: _sections_layout('fill_tracks', parts)
+    inp, n_in = lay([('xf', 2 * FILL_REC * F * (max_fill + 1) * moving), ('wtab', 2 * FILL_WT * FILL_WT),
+                     ('det', 12 * L), ('ids', L), ('frame_start', F + 1), ('frame_no', F), ('seq_start', S + 1)])
+    out, n_out = lay([('out', 12 * capacity), ('out_id', capacity), ('out_src', 2 * capacity), ('fill_start', F + 1),
+                      ('info', 4 * S)])
+    return inp, out, n_in, n_out
+
+
+def _fill_tracks(packed, sizes):
+    inp, outl, n_in, n_out = fill_layout(sizes)
+    if packed.dtype != torch.int32 or packed.dim() != 1 or packed.numel() != n_in or not packed.is_contiguous():
+        raise ValueError('mmmot::fill_tracks: packed must be a contiguous int32 [%d] block for sizes %s'
+                         % (n_in, list(sizes)))
+    L, F, S, max_fill, capacity, moving = (int(v) for v in sizes)
+    res = torch.zeros(n_out, dtype=torch.int32, device=packed.device)  # L = 0 or F = 0: nothing is launched
+    work = torch.empty(3 * L + 1, dtype=torch.int32, device=packed.device)
+    i, o = sections(packed, inp), sections(res, outl)
+    st = _ops().fill_tracks(i['det'].view(torch.float32), i['ids'], i['frame_start'], i['frame_no'], i['seq_start'],
+                            i['xf'] if moving else None, i['wtab'], L, F, S, max_fill, capacity, work, o['fill_start'],
+                            o['out'].view(torch.float32), o['out_id'], o['out_src'], o['info'])
+    from . import _lib
+    _lib.check(st, 'mmmot_fill_tracks')
+    return res
+
+
+def _fill_tracks_meta(packed, sizes):
+    return packed.new_empty((fill_layout(sizes)[3],), dtype=torch.int32)
+
+
+_LIB.define('fill_tracks(Tensor packed, int[] sizes) -> Tensor')
+_LIB.impl('fill_tracks', _fill_tracks, 'CUDA')
+_LIB.impl('fill_tracks', _fill_tracks_meta, 'Meta')
 
 
 # ---- optimizer step (mmmot_amd/optim.py; csrc/adam_step.hip) --------------------------------------------------------

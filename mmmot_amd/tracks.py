@@ -373,3 +373,203 @@ def write_kitti_tracks(path, frames, ids, frame_idx=None, scores=None):
             lines.append(' '.join(row))
     with open(path, 'w') as f:
         f.write('\n'.join(lines))
+
+
+# ---- gap filling: a box for every listed frame a track skipped (csrc/fill_tracks.hip) -----------
+FILL_KEYS = ('frames', 'ids', 'frame_idx', 'scores', 'poses', 'calib')
+FILL_STATUS = ((torch_ops.FILL_EDUP, 'a track ID occurs twice in one frame'),
+               (torch_ops.FILL_ECAPACITY, 'more rows than the capacity of the call'),
+               (torch_ops.FILL_ECONTRACT, 'frame numbers that do not increase, or a broken frame / sequence table'))
+
+
+class FilledTracks:
+    """What ``fill_gaps`` returns for one sequence: ``frames[t]`` a copy of the frame's detection dict with the new rows
+    appended, ``ids[t]`` / ``scores[t]`` (None when no scores were given) extended likewise, ``filled[t]`` the bool mask
+    of the new rows, ``src[t]`` int64 [new rows, 4] = (frame, detection, frame, detection) of the two observations a row
+    was blended from (positions in this sequence's lists), ``info`` = {'rows', 'links_filled', 'links_too_long'}."""
+
+    def __init__(self, frames, ids, scores, filled, src, info):
+        self.frames, self.ids, self.scores, self.filled, self.src, self.info = frames, ids, scores, filled, src, info
+
+
+def fill_weights():
+    """wtab[n][k] = k / n in fp64, n = 1 .. MMMOT_FILL_MAX + 1 (row 0 stays 0): the kernel and a host restatement read
+    the same bits"""
+    w = np.zeros((torch_ops.FILL_WT, torch_ops.FILL_WT), np.float64)
+    k = np.arange(torch_ops.FILL_WT, dtype=np.float64)
+    for n in range(1, torch_ops.FILL_WT):
+        w[n] = k / np.float64(n)
+    return w
+
+
+def _fill_sequence(seq):
+    if isinstance(seq, dict):
+        unknown = set(seq) - set(FILL_KEYS)
+        if unknown:
+            raise ValueError('fill_gaps: unknown sequence entries %s' % sorted(unknown))
+        return tuple(seq.get(k) for k in FILL_KEYS)
+    seq = tuple(seq)
+    if not 2 <= len(seq) <= len(FILL_KEYS):
+        raise ValueError('fill_gaps: a sequence is a dict or a tuple of %s' % (FILL_KEYS,))
+    return seq + (None,) * (len(FILL_KEYS) - len(seq))
+
+
+def pack_fill(sequences, max_fill=7, capacity=None):
+    """The host side of ``fill_gaps_batch`` before the launches: per sequence (frames, ids, frame_idx, scores, poses,
+    calib) as ``fill_gaps`` takes them (a tuple, or a dict with those keys) -> the tables of mmmot_fill_tracks.  Returns a
+    dict: ``packed`` (the int32 block of torch_ops.fill_layout), ``sizes``, the tables by name (``det`` fp32 [L, 12],
+    ``ids``, ``frame_start``, ``frame_no``, ``seq_start``, ``xf`` fp64 [F, max_fill + 1, 33] or None when no sequence
+    moves, ``wtab``) and ``sequences`` (the normalised inputs, for ``unpack_fill``).  ``capacity``: the rows the output
+    holds; by default the exact count, walked on the host from the IDs.  A sequence with poses gets the records
+    ``ego.box_motion`` of every pair of listed frames a filled link can join; in a call where only some sequences move
+    the others get identity records, which give the standing-camera result."""
+    from . import ego
+    max_fill = int(max_fill)
+    if not 1 <= max_fill <= torch_ops.FILL_MAX:
+        raise ValueError('fill_gaps: max_fill must lie in 1 .. %d, got %d' % (torch_ops.FILL_MAX, max_fill))
+    seqs = [_fill_sequence(s) for s in sequences]
+    if not seqs:
+        raise ValueError('fill_gaps: no sequence')
+    det, ids, counts, frame_no, seq_start, moving, rows = [], [], [], [], [0], [], 0
+    for s, (frames, fids, frame_idx, scores, poses, calib) in enumerate(seqs):
+        n = len(frames)
+        if len(fids) != n or (frame_idx is not None and len(frame_idx) != n) or (scores is not None and len(scores) != n):
+            raise ValueError('fill_gaps: sequence %d has %d frames but ids / frame_idx / scores of another length' % (s, n))
+        if poses is not None and (len(poses) != n or any(p is None for p in poses)):
+            raise ValueError('fill_gaps: sequence %d: poses are given for all frames or none' % s)
+        if poses is not None and calib is None:
+            raise ValueError('fill_gaps: sequence %d: poses need calib (R0_rect, Tr_velo_to_cam, Tr_imu_to_velo)' % s)
+        moving.append(poses is not None and n > 0)
+        no = np.arange(n, dtype=np.int64) if frame_idx is None else np.asarray(frame_idx, dtype=np.int64).reshape(-1)
+        if np.abs(no).max(initial=0) >= 2 ** 31:
+            raise ValueError('fill_gaps: sequence %d: frame numbers must fit 32 bits' % s)
+        last = {}
+        for t, (d, fid) in enumerate(zip(frames, fids)):
+            fid = np.asarray(fid, dtype=np.int64).reshape(-1)
+            m = len(fid)
+            row = np.empty((m, 12), np.float32)
+            row[:, 0:4] = np.asarray(d['bbox'], dtype=np.float64).reshape(m, 4)
+            row[:, 4:7] = np.asarray(d['dimensions'], dtype=np.float64).reshape(m, 3)[:, [1, 2, 0]]
+            row[:, 7:10] = np.asarray(d['location'], dtype=np.float64).reshape(m, 3)
+            row[:, 10] = np.asarray(d['rotation_y'], dtype=np.float64).reshape(m)
+            row[:, 11] = 0.9 if scores is None else np.asarray(scores[t], dtype=np.float64).reshape(m)
+            det.append(row)
+            ids.append(fid)
+            counts.append(m)
+            for i in fid[fid >= 0]:
+                a = last.get(int(i))
+                if a is not None and 2 <= no[t] - no[a] <= max_fill + 1:
+                    rows += t - a - 1
+                last[int(i)] = t
+        frame_no.append(no)
+        seq_start.append(seq_start[-1] + n)
+    F, S = seq_start[-1], len(seqs)
+    tab = {'det': np.concatenate(det + [np.zeros((0, 12), np.float32)]),
+           'ids': np.concatenate(ids + [np.zeros(0, np.int64)]).astype(np.int32),
+           'frame_start': np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32),
+           'frame_no': np.concatenate(frame_no + [np.zeros(0, np.int64)]).astype(np.int32),
+           'seq_start': np.asarray(seq_start, np.int32), 'wtab': fill_weights(), 'xf': None}
+    if any(moving):
+        xf = np.zeros((F, max_fill + 1, torch_ops.FILL_REC), np.float64)
+        xf[:, :, 0:16] = xf[:, :, 16:32] = np.eye(4).reshape(-1)
+        for s, (frames, _, _, _, poses, calib) in enumerate(seqs):
+            if not moving[s]:
+                continue
+            no, f0 = frame_no[s], seq_start[s]
+            for p in range(len(frames)):
+                for q in range(p + 1, min(p + max_fill + 2, len(frames))):
+                    if no[q] - no[p] > max_fill + 1:  # no filled link reaches that far: the record is never read
+                        break
+                    C, Ci, dyaw = ego.box_motion(poses[p], poses[q], calib)
+                    rec = xf[f0 + p, q - p - 1]
+                    rec[0:16], rec[16:32], rec[32] = C.reshape(-1), Ci.reshape(-1), dyaw
+        tab['xf'] = xf
+    L = len(tab['ids'])
+    capacity = rows if capacity is None else int(capacity)
+    sizes = [L, F, S, max_fill, capacity, int(tab['xf'] is not None)]
+    inp, _, n_in, _ = torch_ops.fill_layout(sizes)
+    packed = np.zeros(n_in, np.int32)
+    for name, (o, n) in inp.items():
+        if n:
+            packed[o:o + n] = np.ascontiguousarray(tab[name]).reshape(-1).view(np.int32)
+    return dict(tab, packed=packed, sizes=sizes, sequences=seqs)
+
+
+def _extend(values, new, like_list):
+    if isinstance(values, (list, tuple)) and like_list:
+        return list(values) + list(new)
+    values = np.asarray(values)
+    return np.concatenate([values, np.asarray(new, dtype=values.dtype).reshape((len(new),) + values.shape[1:])])
+
+
+def unpack_fill(p, block):
+    """The host side of ``fill_gaps_batch`` behind the launches: ``p`` from ``pack_fill``, ``block`` the host int32 block
+    of mmmot::fill_tracks (torch_ops.fill_layout()[1]) -> one ``FilledTracks`` per sequence; raises ``TrackingError``
+    naming the sequence on a status word.  The inputs are not modified: the frame dicts are copied, the extended
+    arrays are new."""
+    o = torch_ops.sections(np.asarray(block), torch_ops.fill_layout(p['sizes'])[1])
+    rows = o['out'].view(np.float32).reshape(-1, 12).astype(np.float64)
+    out_id, out_src = o['out_id'].astype(np.int64), o['out_src'].reshape(-1, 2).astype(np.int64)
+    fill_start, info = o['fill_start'].astype(np.int64), o['info'].reshape(-1, 4)
+    for s, st in enumerate(info[:, 0]):
+        for bit, text in FILL_STATUS:
+            if st & bit:
+                raise TrackingError('fill_gaps: sequence %d: %s' % (s, text))
+    frame_start, seq_start = p['frame_start'].astype(np.int64), p['seq_start']
+    frame_of = np.searchsorted(frame_start, out_src, side='right') - 1  # empty frames share their start: the last one holds it
+    res = []
+    for s, (frames, fids, _, scores, _, _) in enumerate(p['sequences']):
+        f0 = int(seq_start[s])
+        nf, ni, ns, nm, nsrc = [], [], [], [], []
+        for t, (d, fid) in enumerate(zip(frames, fids)):
+            a, b = int(fill_start[f0 + t]), int(fill_start[f0 + t + 1])
+            r, m = rows[a:b], len(np.asarray(fid).reshape(-1))
+            src = np.stack([frame_of[a:b, 0] - f0, out_src[a:b, 0] - frame_start[frame_of[a:b, 0]],
+                            frame_of[a:b, 1] - f0, out_src[a:b, 1] - frame_start[frame_of[a:b, 1]]], 1)
+            d = dict(d)
+            d['bbox'] = _extend(np.asarray(d['bbox']).reshape(m, 4), r[:, 0:4], False)
+            d['dimensions'] = _extend(np.asarray(d['dimensions']).reshape(m, 3), r[:, [6, 4, 5]], False)
+            d['location'] = _extend(np.asarray(d['location']).reshape(m, 3), r[:, 7:10], False)
+            d['rotation_y'] = _extend(np.asarray(d['rotation_y']).reshape(m), r[:, 10], False)
+            for key, unknown in (('truncated', -1), ('occluded', -1), ('alpha', -10)):
+                if key in d:
+                    d[key] = _extend(d[key], [unknown] * (b - a), True)
+            if 'name' in d:
+                d['name'] = _extend(d['name'], [frames[ta]['name'][ja] for ta, ja in src[:, 0:2]], True)
+            nf.append(d)
+            ni.append(np.concatenate([np.asarray(fid, dtype=np.int64).reshape(-1), out_id[a:b]]))
+            if scores is not None:
+                ns.append(_extend(np.asarray(scores[t]).reshape(m), r[:, 11], False))
+            nm.append(np.arange(m + b - a) >= m)
+            nsrc.append(src)
+        res.append(FilledTracks(nf, ni, ns if scores is not None else None, nm, nsrc,
+                                {'rows': int(info[s, 1]), 'links_filled': int(info[s, 2]),
+                                 'links_too_long': int(info[s, 3])}))
+    return res
+
+
+def fill_gaps_batch(sequences, max_fill=7, device='cuda'):
+    """``fill_gaps`` for many sequences - all 21 KITTI validation sequences, say - in ONE upload, ONE set of launches
+    (mmmot_fill_tracks: five, whatever the sequences hold) and ONE copy back.  ``sequences``: per sequence the tuple
+    (frames, ids[, frame_idx, scores, poses, calib]) or a dict with those keys.  Returns one ``FilledTracks`` per
+    sequence, bit for bit what ``fill_gaps`` returns for it alone."""
+    p = pack_fill(sequences, max_fill)
+    host = torch.empty(len(p['packed']), dtype=torch.int32, pin_memory=True)
+    host.numpy()[:] = p['packed']
+    block = torch.ops.mmmot.fill_tracks(host.to(device, non_blocking=True), p['sizes'])
+    return unpack_fill(p, block.cpu().numpy())
+
+
+def fill_gaps(frames, ids, frame_idx=None, scores=None, poses=None, calib=None, max_fill=7, device='cuda'):
+    """The last step of an offline tracker: a box for every listed frame a track skipped.  ``frames`` / ``ids`` /
+    ``frame_idx`` / ``scores`` are what ``write_kitti_tracks`` takes (``ids`` with holes, as
+    ``SequencePipeline.run_global(max_gap=G)`` leaves them).  Two observations of one ID with no observation between
+    them, n = 2 .. ``max_fill`` + 1 frame numbers apart, are joined by one interpolated box per listed frame between
+    them: the 2D box, the dimensions and the score blended linearly with w = (frames since the earlier one) / n, the yaw
+    along the shorter arc, the location blended in the earlier frame's coordinates and moved into the hole frame's
+    (DESIGN section 12a).  ``poses``: per frame (pos, rad) as ``FrameFeed(pose=)`` takes them, for all frames or none
+    (a standing camera); with poses ``calib`` is the frame-info dict holding ``calib/R0_rect``, ``calib/Tr_velo_to_cam``
+    and ``calib/Tr_imu_to_velo``.  Returns a ``FilledTracks``; ``write_kitti_tracks(path, ft.frames, ft.ids, frame_idx,
+    ft.scores)`` and ``evaluate.labels_from_tracks(ft.frames, ft.ids, ..)`` take it as it is.  The inputs are not
+    modified.  Raises ``TrackingError`` when an ID occurs twice in a frame or the frame numbers do not increase."""
+    return fill_gaps_batch([(frames, ids, frame_idx, scores, poses, calib)], max_fill, device)[0]

@@ -23,11 +23,19 @@ each gap leaves; and the solver alone on a planted instance (T = 400 frames, 8 h
 with probability 0.1): mmmot_associate_sequences beside mmmot_associate_sequences_gap at G = 1 and at the gaps given, in
 one process, interleaved, HIP-event time of the operator call, median of --solver-calls calls.  Writes
 <out>/bench_sequence_gaps.json.
+--fill measures the gap filling alone (tracks.fill_gaps_batch; no model is built): 21 sequences of
+--fill-frames frames in all (default 8000), 10 - 12 tracks a frame whose detections are missed with probability 0.1,
+max_fill = 7, a standing camera (--ego: a synthetic drive per sequence).  HIP-event time of the operator call for all
+sequences at once and for 21 calls, one per sequence, interleaved, median of --solver-calls after one untimed round; the
+wall time of ``fill_gaps_batch`` (packing, upload, launches, copy, unpacking) and of the NumPy restatement
+tests/fill_ref.py on the same tables, whose rows must equal the device's bit for bit.  Writes
+<out>/bench_sequence_fill.json.
 
     python tools/bench_sequence.py --out <dir> [--repeats 3] [--trunk f16x3] [-K 16] [-B 8] [--associate | --track] [--ego]
     python tools/bench_sequence.py --out <dir> --window 3 5 [--repeats 3] [-K 16] [-B 8] [-W 4] [--ego]
     python tools/bench_sequence.py --out <dir> --streams 1 2 4 8 16 [--frames 40] [--repeats 3]
     python tools/bench_sequence.py --out <dir> --global-gap 1 2 3 4 [--frames 100] [--repeats 3] [--solver-calls 20]
+    python tools/bench_sequence.py --out <dir> --fill [--fill-frames 8000] [--ego] [--solver-calls 20]
 """
 import argparse
 import json
@@ -231,6 +239,87 @@ def bench_gaps(args, model, dev):
     print(json.dumps(rec))
 
 
+def fill_workload(n_seq, n_frames, p_miss, ego, seed=0):
+    """per sequence (frames, ids, None, None, poses, calib): 10 - 12 hidden tracks with linear boxes, every detection
+    missed with probability p_miss"""
+    from mmmot_amd import synth
+    rng = np.random.default_rng(seed)
+    calib = {'calib/R0_rect': synth.KITTI_R0, 'calib/Tr_velo_to_cam': synth.KITTI_TR,
+             'calib/Tr_imu_to_velo': synth.KITTI_IMU2VELO}
+    seqs = []
+    for s in range(n_seq):
+        T = n_frames // n_seq + (s < n_frames % n_seq)
+        n = int(rng.integers(10, 13))
+        x0, v = rng.uniform(-30, 30, (n, 3)), rng.uniform(-0.2, 0.2, (n, 3))
+        frames, ids = [], []
+        for t in range(T):
+            seen = np.flatnonzero(rng.random(n) >= p_miss)
+            loc = x0[seen] + v[seen] * t
+            bbox = np.concatenate([loc[:, :2] * 10 + 500, loc[:, :2] * 10 + 580], 1)
+            frames.append({'bbox': bbox, 'dimensions': np.tile([4.0, 1.5, 1.8], (len(seen), 1)), 'location': loc,
+                           'rotation_y': 0.01 * t + 0.3 * seen})
+            ids.append(seen.astype(np.int64))
+        seqs.append((frames, ids, None, None, synth.ego_poses(T, s) if ego else None, calib if ego else None))
+    return seqs
+
+
+def bench_fill(args):
+    """the operator for all sequences at once beside one call per sequence, and the host routes around them"""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import fill_ref
+    from mmmot_amd import tracks
+    max_fill, n_seq = 7, 21
+    seqs = fill_workload(n_seq, args.fill_frames, 0.1, args.ego)
+    up = lambda p: (torch.from_numpy(p['packed']).cuda(), p['sizes'])
+    t0 = time.perf_counter()
+    p = tracks.pack_fill(seqs, max_fill)
+    pack_ms = 1e3 * (time.perf_counter() - t0)
+    batch, singles = up(p), [up(tracks.pack_fill([s], max_fill)) for s in seqs]
+    calls = {'batch': lambda: [torch.ops.mmmot.fill_tracks(*batch)],
+             'singles': lambda: [torch.ops.mmmot.fill_tracks(*b) for b in singles]}
+    ms, out = {k: [] for k in calls}, {}
+    for i in range(args.solver_calls + 1):  # the first round untimed
+        for name, call in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out[name] = call()
+            e1.record()
+            torch.cuda.synchronize()
+            if i:
+                ms[name].append(e0.elapsed_time(e1))
+    wall = []
+    for _ in range(4):  # the first untimed
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        filled = tracks.fill_gaps_batch(seqs, max_fill)
+        wall.append(1e3 * (time.perf_counter() - t0))
+    t0 = time.perf_counter()
+    ref = fill_ref.fill(p['det'], p['ids'], p['frame_start'], p['frame_no'], p['seq_start'], p['xf'], p['wtab'], max_fill,
+                        p['sizes'][4])
+    ref_ms = 1e3 * (time.perf_counter() - t0)
+    got = out['batch'][0].cpu().numpy()
+    if not np.array_equal(got, fill_ref.block_of(ref, p['sizes'])):
+        raise SystemExit('the device rows differ from the restatement')
+    rows = [int(b.cpu().numpy()[-4 + 1]) for b in out['singles']]
+    if rows != [f.info['rows'] for f in filled] or sum(rows) != len(ref['out']):
+        raise SystemExit('the single calls and the batch count different rows')
+    L, F = p['sizes'][0], p['sizes'][1]
+    rec = {
+        'op_ms': {k: round(float(np.median(v)), 3) for k, v in ms.items()},
+        'op_ms_min_max': {k: [round(min(v), 3), round(max(v), 3)] for k, v in ms.items()},
+        'fill_gaps_batch_wall_ms': round(float(np.median(wall[1:])), 1), 'pack_fill_wall_ms': round(pack_ms, 1),
+        'numpy_restatement_wall_ms': round(ref_ms, 1),
+        'instance': '%d sequences, %d frames, %d detections, p_miss = 0.1, max_fill = %d: %d rows from %d links, %d links '
+                    'too long' % (n_seq, F, L, max_fill, len(ref['out']), int(ref['info'][:, 2].sum()),
+                                  int(ref['info'][:, 3].sum())),
+        'calls': args.solver_calls, 'ego': bool(args.ego), 'device': torch.cuda.get_device_name(0),
+    }
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_sequence_fill.json'), 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', required=True)
@@ -250,7 +339,11 @@ def main():
     ap.add_argument('--global-gap', type=int, nargs='+', default=None,
                     help='time run_global(max_gap=G) for these gaps (1 .. 8) and the sequence solvers alone')
     ap.add_argument('--solver-calls', type=int, default=20)
+    ap.add_argument('--fill', action='store_true', help='time the gap filling alone: all sequences at once, one call each, NumPy')
+    ap.add_argument('--fill-frames', type=int, default=8000)
     args = ap.parse_args()
+    if args.fill:
+        return bench_fill(args)
     assoc = args.associate or args.track
     kw = dict(associate=assoc, track=True) if args.track else dict(associate=assoc)
     if args.repeats < 3 or args.frames < 2:
