@@ -23,18 +23,52 @@ FUSION_MODES = {'A': 0, 'B': 1, 'C': 2}
 LOSS_KINDS = {'bce': 0, 'l2': 1, 'l1': 2}
 
 
-def _ptr(t, dtype=torch.float32):
-    if t is None:
-        return None
-    if not t.is_cuda:
-        raise RuntimeError('mmmot_amd HIP ops need device tensors (got %s); there is no CPU fallback' % t.device)
-    if t.dtype != dtype:
-        raise TypeError('expected %s, got %s' % (dtype, t.dtype))
-    return t.data_ptr()
+def _pointer(dtype):
+    """The converter of a pointer argument to ``dtype`` data: a device tensor of that dtype -> its address; None -> NULL;
+    anything that is no tensor passes as it is (an address the caller has checked itself, a ctypes byref / array)."""
+    def ptr(t):
+        if t is None:
+            return None
+        try:
+            cuda = t.is_cuda
+        except AttributeError:
+            return t
+        if not cuda:
+            raise RuntimeError('mmmot_amd HIP ops need device tensors (got %s); there is no CPU fallback' % t.device)
+        if t.dtype != dtype:
+            raise TypeError('expected %s, got %s' % (dtype, t.dtype))
+        return t.data_ptr()
+    return ptr
 
 
-def _iptr(t):
-    return _ptr(t, torch.int32)
+# element type of a pointer parameter by the header's pointee; the packed Adam rows travel as a uint8 block
+_POINTERS = {c: _pointer(d) for c, d in (
+    ('float', torch.float32), ('int', torch.int32), ('unsigned int', torch.int32), ('long long', torch.int64),
+    ('double', torch.float64), ('unsigned char', torch.uint8), ('mmmot_adam_row', torch.uint8))}
+# `void*` buffers (hl16 / hq8 records, workspaces) have no element type in the header: their call sites say it
+_ptr, _iptr = _POINTERS['float'], _POINTERS['int']
+
+
+def _converter(p):
+    if p.pointee is None:
+        return float if p.ctype in (ctypes.c_float, ctypes.c_double) else int
+    return _POINTERS.get(p.pointee)  # None (passed as it is): void*, char*, the args structs - the caller's to check
+
+
+def _call(name, params):
+    """``f(fn, ops, *args)`` of one entry point: calls ``fn`` with every argument through the converter of its parameter
+    in the header and, where the entry takes one, ``ops._stream()`` behind them (resolved last, as a wrapper that spells
+    the call out would).  One generated lambda per entry, built once at import: the same conversions as a loop over a
+    converter tuple cost about 1 us more per launch, which the host-bound B = 1 forward (~80 launches in 2.5 ms) shows."""
+    stream = name in _lib.TAKES_STREAM
+    conv = {'c%d' % i: _converter(p) for i, p in enumerate(params[:-1] if stream else params)}
+    args = ['a%d' % i for i in range(len(conv))]
+    passed = ['a%d' % i if conv['c%d' % i] is None else 'c%d(a%d)' % (i, i) for i in range(len(conv))]
+    passed += ['ops._stream()'] * stream
+    return eval('lambda fn, ops, %s: fn(%s)' % (', '.join(args), ', '.join(passed)), conv)
+
+
+_CALLS = {name: _call(name, params) for name, params in _lib.PARAMS.items()}
 
 
 def _ld(t):
@@ -92,9 +126,8 @@ class HipOps:
         return v
 
     def _stream(self):
-        if self._pinned_stream is not None:
-            return self._pinned_stream
-        return torch.cuda.current_stream().cuda_stream
+        s = getattr(self._tls, 'stream', None)
+        return torch.cuda.current_stream().cuda_stream if s is None else s
 
     @contextlib.contextmanager
     def on_current_stream(self, stream=None):
@@ -120,54 +153,53 @@ class HipOps:
         finally:
             self._pinned_stream = prev
 
+    def _status(self, name, *args):
+        """One C-ABI call: ``args`` are the header's parameters in order, without the stream (appended where the entry
+        takes one); pointers and scalars are converted as the header types them.  Returns the entry's status."""
+        return _CALLS[name](getattr(self.lib, name), self, *args)
+
+    def _launch(self, name, *args):
+        """``_status`` that raises unless the entry returned 0 (spelled out: one python call less per launch)."""
+        st = _CALLS[name](getattr(self.lib, name), self, *args)
+        if st != 0:
+            _lib.check(st, name)
+
     def conv3x3(self, inp, wp, bias, out, L, H, W, Cin, Cout, first, pool):
-        st = self.lib.mmmot_conv3x3_bn_relu(_ptr(inp), _ptr(wp), _ptr(bias), _ptr(out), L, H, W, Cin, Cout,
-                                            int(first), int(pool), self._stream())
-        _lib.check(st, 'mmmot_conv3x3_bn_relu')
+        self._launch('mmmot_conv3x3_bn_relu', inp, wp, bias, out, L, H, W, Cin, Cout, first, pool)
 
     def conv3x3_hl16_patch(self, inp, wp, bias, out, L, H, W, Cin, Cout, pool, oscale):
         """fp16-split trunk layer (LDS-resident haloed patch kernel): inp/out/wp are fp32-typed buffers holding hl16
         data (same bytes), oscale the [Cout] vector of per-output-channel 2^-shift."""
-        st = self.lib.mmmot_conv3x3_bn_relu_hl16_patch(_ptr(inp), _ptr(wp), _ptr(bias), _ptr(out), L, H, W, Cin,
-                                                       Cout, int(pool), _ptr(self._osv(oscale, Cout, out)), self._stream())
-        _lib.check(st, 'mmmot_conv3x3_bn_relu_hl16_patch')
+        self._launch('mmmot_conv3x3_bn_relu_hl16_patch', _ptr(inp), _ptr(wp), bias, _ptr(out), L, H, W, Cin, Cout, pool,
+                     self._osv(oscale, Cout, out))
 
     def conv1_fused_hl16(self, crops, w1, bias1, oscale1, w2, bias2, oscale2, out, L, H, W):
         """conv1_1 + conv1_2 + max-pool in one launch (the conv1_1 tensor never reaches HBM)."""
-        st = self.lib.mmmot_conv1_fused_hl16(_ptr(crops), _ptr(w1), _ptr(bias1), float(oscale1), _ptr(w2),
-                                             _ptr(bias2), _ptr(self._osv(oscale2, 64, out)), _ptr(out), L, H, W, self._stream())
-        _lib.check(st, 'mmmot_conv1_fused_hl16')
+        self._launch('mmmot_conv1_fused_hl16', crops, _ptr(w1), bias1, oscale1, _ptr(w2), bias2,
+                     self._osv(oscale2, 64, out), _ptr(out), L, H, W)
 
     def conv3x3_hq8(self, inp, wp, bias, out, L, H, W, Cin, Cout, pool, oscale):
         """conv3x3_hl16_patch in hq8 arithmetic: activations / weights are hq8 records (pack.to_hq8_act / to_hq8_w)."""
-        st = self.lib.mmmot_conv3x3_bn_relu_hq8(_ptr(inp), _ptr(wp), _ptr(bias), _ptr(out), L, H, W, Cin, Cout,
-                                                int(pool), _ptr(self._osv(oscale, Cout, out)), self._stream())
-        _lib.check(st, 'mmmot_conv3x3_bn_relu_hq8')
+        self._launch('mmmot_conv3x3_bn_relu_hq8', _ptr(inp), _ptr(wp), bias, _ptr(out), L, H, W, Cin, Cout, pool,
+                     self._osv(oscale, Cout, out))
 
     def conv1_fused_hq8(self, crops, w1, bias1, oscale1, w2, bias2, oscale2, out, L, H, W):
         """conv1_fused_hl16 with conv1_2 in hq8 arithmetic (w1 hl16, w2 hq8, out hq8)."""
-        st = self.lib.mmmot_conv1_fused_hq8(_ptr(crops), _ptr(w1), _ptr(bias1), float(oscale1), _ptr(w2),
-                                            _ptr(bias2), _ptr(self._osv(oscale2, 64, out)), _ptr(out), L, H, W, self._stream())
-        _lib.check(st, 'mmmot_conv1_fused_hq8')
+        self._launch('mmmot_conv1_fused_hq8', crops, _ptr(w1), bias1, oscale1, _ptr(w2), bias2,
+                     self._osv(oscale2, 64, out), _ptr(out), L, H, W)
 
     def conv1_fused_u8(self, crops_u8, mean, std, w1, bias1, oscale1, w2, bias2, oscale2, out, L, H, W, q8=False):
         """conv1_fused_hl16 / _hq8 fed by the 8-bit crops [L][H][W][3]: ToTensor + Normalize in the loader"""
-        st = self.lib.mmmot_conv1_fused_u8(_ptr(crops_u8, torch.uint8), float(mean[0]), float(mean[1]), float(mean[2]),
-                                           float(std[0]), float(std[1]), float(std[2]), _ptr(w1), _ptr(bias1),
-                                           float(oscale1), _ptr(w2), _ptr(bias2), _ptr(self._osv(oscale2, 64, out)),
-                                           _ptr(out), L, H, W, int(bool(q8)), self._stream())
-        _lib.check(st, 'mmmot_conv1_fused_u8')
+        self._launch('mmmot_conv1_fused_u8', crops_u8, mean[0], mean[1], mean[2], std[0], std[1], std[2], _ptr(w1), bias1,
+                     oscale1, _ptr(w2), bias2, self._osv(oscale2, 64, out), _ptr(out), L, H, W, bool(q8))
 
     def u8_normalize(self, crops_u8, mean_std, out, N, S):
-        st = self.lib.mmmot_u8_normalize(_ptr(crops_u8, torch.uint8), N, S, _ptr(mean_std), _ptr(out), self._stream())
-        _lib.check(st, 'mmmot_u8_normalize')
+        self._launch('mmmot_u8_normalize', crops_u8, N, S, mean_std, out)
 
     def crop_augment(self, crops_u8, params, mean_std, out, out_u8, L, S):
         """random-resized-crop + flip + ToTensor / Normalize of the 8-bit crops [L][S][S][3]: params the device int32
         [L][5] table (top, left, h, w, flip); out fp32 [L][3][S][S] and / or out_u8 [L][S][S][3]"""
-        st = self.lib.mmmot_crop_augment(_ptr(crops_u8, torch.uint8), _iptr(params), L, S, _ptr(mean_std), _ptr(out),
-                                         _ptr(out_u8, torch.uint8), self._stream())
-        _lib.check(st, 'mmmot_crop_augment')
+        self._launch('mmmot_crop_augment', crops_u8, params, L, S, mean_std, out, out_u8)
 
     def trunk_range_read(self, device, reset=True):
         """(e4m3-saturated, fp16-clamped, conv1_1 hits, 0) activation-element counters of the trunk epilogues on
@@ -177,61 +209,54 @@ class HipOps:
         buf = (ctypes.c_uint * 4)()
         with torch.cuda.device(device):
             torch.cuda.current_stream().synchronize()
-            _lib.check(self.lib.mmmot_trunk_range_read(buf, int(reset)), 'mmmot_trunk_range_read')
+            self._launch('mmmot_trunk_range_read', buf, reset)
         return tuple(int(v) for v in buf)
 
     def trunk_range_bind(self, counters):
         """Counter block (int32 [4] device tensor, or None = the library's per-device block) the trunk launches issued
         by this thread report to from now on (mmmot_trunk_range_bind)."""
-        _lib.check(self.lib.mmmot_trunk_range_bind(None if counters is None else _ptr(counters, torch.int32)),
-                   'mmmot_trunk_range_bind')
+        self._launch('mmmot_trunk_range_bind', counters)
 
     def set_patch_tile_width(self, bn):
         """Test knob: output channels per tile of the patch kernels (0 = automatic, 64, 128; mmmot_set_patch_tile_width)."""
-        _lib.check(self.lib.mmmot_set_patch_tile_width(int(bn)), 'mmmot_set_patch_tile_width')
+        self._launch('mmmot_set_patch_tile_width', bn)
 
     def patch_choice(self, L, H, W, Cout):
         """(channels per tile, block edge, tiles, workgroups) of the next patch-kernel launch of this shape under the
         current knobs (mmmot_patch_choice); no launch."""
         v = [ctypes.c_int(0) for _ in range(4)]
-        _lib.check(self.lib.mmmot_patch_choice(L, H, W, Cout, *[ctypes.byref(x) for x in v]), 'mmmot_patch_choice')
+        self._launch('mmmot_patch_choice', L, H, W, Cout, *[ctypes.byref(x) for x in v])
         return tuple(x.value for x in v)
 
     def hq8_pack(self, x, y):
-        _lib.check(self.lib.mmmot_hq8_pack(_ptr(x), _ptr(y), x.numel(), self._stream()), 'mmmot_hq8_pack')
+        self._launch('mmmot_hq8_pack', x, _ptr(y), x.numel())
 
     def hq8_unpack(self, x, y):
-        _lib.check(self.lib.mmmot_hq8_unpack(_ptr(x), _ptr(y), y.numel(), self._stream()), 'mmmot_hq8_unpack')
+        self._launch('mmmot_hq8_unpack', _ptr(x), y, y.numel())
 
     def conv3x3_first_hl16(self, inp, wp, bias, out, L, H, W, Cout):
-        st = self.lib.mmmot_conv3x3_first_hl16(_ptr(inp), _ptr(wp), _ptr(bias), _ptr(out), L, H, W, Cout,
-                                               self._stream())
-        _lib.check(st, 'mmmot_conv3x3_first_hl16')
+        self._launch('mmmot_conv3x3_first_hl16', inp, wp, bias, _ptr(out), L, H, W, Cout)
 
     def hl16_pack(self, x, y):
-        _lib.check(self.lib.mmmot_hl16_pack(_ptr(x), _ptr(y), x.numel(), self._stream()), 'mmmot_hl16_pack')
+        self._launch('mmmot_hl16_pack', x, _ptr(y), x.numel())
 
     def hl16_unpack(self, x, y):
-        _lib.check(self.lib.mmmot_hl16_unpack(_ptr(x), _ptr(y), y.numel(), self._stream()), 'mmmot_hl16_unpack')
+        self._launch('mmmot_hl16_unpack', _ptr(x), y, y.numel())
 
     # ---- training step on the fp16 matrix cores: device-side power-of-two scales, raw-output trunk convolution ----
     def absmax(self, X, out):
         """out[0] = max |X| over a contiguous [R][C] tensor (device scalar, no host round trip)"""
         R, C = X.numel() // X.shape[-1], X.shape[-1]
-        _lib.check(self.lib.mmmot_absmax(_ptr(X), C, R, C, _ptr(out), self._stream()), 'mmmot_absmax')
+        self._launch('mmmot_absmax', X, C, R, C, out)
 
     def hl16_pack_pow2(self, x, y, amax, target):
-        _lib.check(self.lib.mmmot_hl16_pack_pow2(_ptr(x), _ptr(y), x.numel(), _ptr(amax), int(target), self._stream()),
-                   'mmmot_hl16_pack_pow2')
+        self._launch('mmmot_hl16_pack_pow2', x, _ptr(y), x.numel(), amax, target)
 
     def pow2_oscale(self, out, amax_a, target_a, amax_b=None, target_b=0):
-        _lib.check(self.lib.mmmot_pow2_oscale(_ptr(out), out.numel(), _ptr(amax_a), int(target_a), _ptr(amax_b), int(target_b),
-                                              self._stream()), 'mmmot_pow2_oscale')
+        self._launch('mmmot_pow2_oscale', out, out.numel(), amax_a, target_a, amax_b, target_b)
 
     def conv3x3_raw_hl16(self, x16, w16, bias, out, L, H, W, Cin, Cout, oscale):
-        st = self.lib.mmmot_conv3x3_raw_hl16(_ptr(x16), _ptr(w16), _ptr(bias), _ptr(out), L, H, W, Cin, Cout, _ptr(oscale),
-                                             self._stream())
-        _lib.check(st, 'mmmot_conv3x3_raw_hl16')
+        self._launch('mmmot_conv3x3_raw_hl16', _ptr(x16), _ptr(w16), bias, out, L, H, W, Cin, Cout, oscale)
 
     def gemm(self, W, tiles, N, K, X=None, bias=None, dbias=None, rowidx=None, Y=None, part=None,
              sc=None, sh=None, FA=None, FB=None, pair=None, amode=A_PLAIN, pairop=0, act=ACT_NONE,
@@ -240,7 +265,7 @@ class HipOps:
         colsum [T][N] (+ osc/osh [G][N]): per-tile column sums of relu(v * osc + osh) (fused next-norm consumer)."""
         a = self._gemm_args(W, tiles, N, K, X, bias, dbias, rowidx, Y, part, sc, sh, FA, FB, pair, amode, pairop, act,
                             w_hl16, oscale, osc, osh, colsum)
-        _lib.check(self.lib.mmmot_gemm_rows(ctypes.byref(a), self._stream()), 'mmmot_gemm_rows')
+        self._launch('mmmot_gemm_rows', ctypes.byref(a))
 
     def gemm_choice(self, W, tiles, N, K, **kw):
         """(wide, nh, items, grid) of the gemm launch of the same arguments under the current variant and grid limit
@@ -252,12 +277,12 @@ class HipOps:
                                                              'FB', 'pair', 'amode', 'pairop', 'act', 'w_hl16', 'oscale',
                                                              'osc', 'osh', 'colsum')])
         v = [ctypes.c_int(0) for _ in range(4)]
-        _lib.check(self.lib.mmmot_gemm_rows_choice(ctypes.byref(a), *[ctypes.byref(x) for x in v]), 'mmmot_gemm_rows_choice')
+        self._launch('mmmot_gemm_rows_choice', ctypes.byref(a), *[ctypes.byref(x) for x in v])
         return tuple(x.value for x in v)
 
     def set_gemm_wide_grid_limit(self, n):
         """Test knob: cap of the wide kernel's persistent grid (0 = automatic; mmmot_set_gemm_wide_grid_limit)."""
-        _lib.check(self.lib.mmmot_set_gemm_wide_grid_limit(int(n)), 'mmmot_set_gemm_wide_grid_limit')
+        self._launch('mmmot_set_gemm_wide_grid_limit', n)
 
     @staticmethod
     def _gemm_args(W, tiles, N, K, X, bias, dbias, rowidx, Y, part, sc, sh, FA, FB, pair, amode, pairop, act, w_hl16,
@@ -297,121 +322,82 @@ class HipOps:
         a.osc, a.osh, a.ldosc = _ptr(osc), _ptr(osh), _ld(osc)
         a.colsum = _ptr(colsum)
         a.T, a.N, a.K, a.oscale = tiles.T, N, K, float(oscale)
-        _lib.check(self.lib.mmmot_gemm_ares(ctypes.byref(a), self._stream()), 'mmmot_gemm_ares')
+        self._launch('mmmot_gemm_ares', ctypes.byref(a))
 
     def pn_mlp64(self, W16, oscale, tiles, N, X, sc, sh, bias, Y, part):
         """PointNet K = 64 layer: Y / part of relu(X*sc+sh) W^T + b from the persistent weight-resident kernel (same
         results contract as gemm(amode=A_NORM_RELU, w_hl16=True, K=64); see mmmot_pn_mlp64)."""
-        st = self.lib.mmmot_pn_mlp64(_ptr(X), _ld(X), _ptr(sc), _ptr(sh), _ld(sc), _ptr(W16), float(oscale),
-                                     _ptr(bias), _ptr(Y), _ld(Y), _ptr(part), _iptr(tiles.row0), _iptr(tiles.nrows),
-                                     _iptr(tiles.group), tiles.T, N, self._stream())
-        _lib.check(st, 'mmmot_pn_mlp64')
+        self._launch('mmmot_pn_mlp64', X, _ld(X), sc, sh, _ld(sc), _ptr(W16), oscale, bias, Y, _ld(Y), part, tiles.row0,
+                     tiles.nrows, tiles.group, tiles.T, N)
 
     def gram_rows(self, X, K, sc, sh, tiles, Gout, Sout):
         """Per super-tile Gram matrix / column sums (float64) of relu(X*sc+sh); see mmmot_gram_rows.  K = 128: only the
         32 x 32 blocks on and above the block diagonal of Gout are written (the lower ones keep what the buffer held);
         gn_finalize_gram(_dbias) reads those blocks only."""
-        st = self.lib.mmmot_gram_rows(_ptr(X), _ld(X), K, _ptr(sc), _ptr(sh), _ld(sc), _iptr(tiles.row0),
-                                      _iptr(tiles.nrows), _iptr(tiles.group), tiles.T,
-                                      _ptr(Gout, torch.float64), _ptr(Sout, torch.float64), self._stream())
-        _lib.check(st, 'mmmot_gram_rows')
+        self._launch('mmmot_gram_rows', X, _ld(X), K, sc, sh, _ld(sc), tiles.row0, tiles.nrows, tiles.group, tiles.T,
+                     Gout, Sout)
 
     def gn_finalize_gram(self, Gp, Sp, tiles, K, W, bias, N, gamma, beta, eps, work, sc, sh):
         """GroupNorm(N, N) scale/shift of v = W a + b from the Gram partials of a; see mmmot_gn_finalize_gram."""
-        st = self.lib.mmmot_gn_finalize_gram(_ptr(Gp, torch.float64), _ptr(Sp, torch.float64), _iptr(tiles.g_tile0),
-                                             _iptr(tiles.g_ntiles), _iptr(tiles.g_count), tiles.G, K, _ptr(W),
-                                             _ptr(bias), N, _ptr(gamma), _ptr(beta), float(eps),
-                                             _ptr(work, torch.float64), _ptr(sc), _ptr(sh), self._stream())
-        _lib.check(st, 'mmmot_gn_finalize_gram')
+        self._launch('mmmot_gn_finalize_gram', Gp, Sp, tiles.g_tile0, tiles.g_ntiles, tiles.g_count, tiles.G, K, W, bias,
+                     N, gamma, beta, eps, work, sc, sh)
 
     def gn_finalize_gram_dbias(self, Gp, Sp, tiles, tile_det, K, W, dbias, N, gamma, beta, eps, work, sc, sh):
         """GroupNorm(N, N) scale/shift of v = W a + dbias[det] from the Gram partials of a over detection-aligned
         super-tiles (tile_det: int32 [T], the dbias row of every super-tile); see mmmot_gn_finalize_gram_dbias."""
-        st = self.lib.mmmot_gn_finalize_gram_dbias(_ptr(Gp, torch.float64), _ptr(Sp, torch.float64), _iptr(tiles.g_tile0),
-                                                   _iptr(tiles.g_ntiles), _iptr(tiles.g_count), tiles.G, _iptr(tiles.nrows),
-                                                   _iptr(tile_det), K, _ptr(W), _ptr(dbias), _ld(dbias), N, _ptr(gamma),
-                                                   _ptr(beta), float(eps), _ptr(work, torch.float64), _ptr(sc), _ptr(sh),
-                                                   self._stream())
-        _lib.check(st, 'mmmot_gn_finalize_gram_dbias')
+        self._launch('mmmot_gn_finalize_gram_dbias', Gp, Sp, tiles.g_tile0, tiles.g_ntiles, tiles.g_count, tiles.G,
+                     tiles.nrows, tile_det, K, W, dbias, _ld(dbias), N, gamma, beta, eps, work, sc, sh)
 
     def gn_finalize(self, part, tiles, C, NG, gamma, beta, eps, sc, sh):
         """part: [T][2][>=C] view (unit inner stride); statistics of its first C channels."""
         if part.dim() != 3 or part.stride(2) != 1 or part.stride(0) != 2 * part.stride(1):
             raise ValueError('part must be a [T][2][C] view of a [T][2][ldp] buffer')
-        st = self.lib.mmmot_gn_finalize(_ptr(part), _iptr(tiles.g_tile0), _iptr(tiles.g_ntiles),
-                                        _iptr(tiles.g_count), _iptr(tiles.nrows) if tiles.ragged else None, tiles.G,
-                                        part.stride(1), C, NG, _ptr(gamma), _ptr(beta),
-                                        float(eps), _ptr(sc), _ptr(sh), self._stream())
-        _lib.check(st, 'mmmot_gn_finalize')
+        self._launch('mmmot_gn_finalize', part, tiles.g_tile0, tiles.g_ntiles, tiles.g_count,
+                     tiles.nrows if tiles.ragged else None, tiles.G, part.stride(1), C, NG, gamma, beta, eps, sc, sh)
 
     def segment_mean(self, X, C, segs, out, sc=None, sh=None, relu=False, use_group=True, hl16=False, take_max=False):
         """segs.div (optional int32 tensor): divisor per segment instead of its row count; take_max: maximum over the
         segment instead of the mean."""
-        st = self.lib.mmmot_segment_mean(_ptr(X), _ld(X), C, _iptr(segs.start), _iptr(segs.count),
-                                         _iptr(segs.stride), _iptr(segs.group) if use_group else None,
-                                         _iptr(getattr(segs, 'div', None)), segs.n,
-                                         _ptr(sc), _ptr(sh), _ld(sc), int(bool(relu)) | (2 if take_max else 0), _ptr(out), _ld(out),
-                                         int(hl16), self._stream())
-        _lib.check(st, 'mmmot_segment_mean')
+        self._launch('mmmot_segment_mean', X, _ld(X), C, segs.start, segs.count, segs.stride,
+                     segs.group if use_group else None, getattr(segs, 'div', None), segs.n, sc, sh, _ld(sc),
+                     bool(relu) | (2 if take_max else 0), out, _ld(out), hl16)
 
     def rowdot(self, X, K, w, b, tiles, out, sc=None, sh=None, act=ACT_NONE, use_thr=False, thr=0.0, omap=None):
-        st = self.lib.mmmot_rowdot(_ptr(X), _ld(X), K, _ptr(w), float(b), _ptr(sc), _ptr(sh), _ld(sc),
-                                   _iptr(tiles.row0), _iptr(tiles.nrows), _iptr(tiles.group), tiles.T, act,
-                                   int(use_thr), float(thr), _ptr(out), _iptr(omap), self._stream())
-        _lib.check(st, 'mmmot_rowdot')
+        self._launch('mmmot_rowdot', X, _ld(X), K, w, b, sc, sh, _ld(sc), tiles.row0, tiles.nrows, tiles.group, tiles.T,
+                     act, use_thr, thr, out, omap)
 
     def row_layernorm(self, X, C, gamma, beta, eps, relu, Y, R):
-        st = self.lib.mmmot_row_layernorm(_ptr(X), _ld(X), C, _ptr(gamma), _ptr(beta), float(eps), int(relu),
-                                          _ptr(Y), _ld(Y), R, self._stream())
-        _lib.check(st, 'mmmot_row_layernorm')
+        self._launch('mmmot_row_layernorm', X, _ld(X), C, gamma, beta, eps, relu, Y, _ld(Y), R)
 
     def skippool_head(self, P, C, hd, eps, out, R):
         """one SkipPool head (appear_net.py:19-32) on the pooled rows P [R][C] -> out [R][128]; hd: packed head dict"""
-        C4 = int(hd['w1'].shape[0])
-        st = self.lib.mmmot_skippool_head(_ptr(P), _ld(P), C, C4, _ptr(hd['g0']), _ptr(hd['b0']), _ptr(hd['w1']),
-                                          _ptr(hd['c1']), _ptr(hd['g2']), _ptr(hd['b2']), _ptr(hd['w4']), _ptr(hd['c4']),
-                                          _ptr(hd['g5']), _ptr(hd['b5']), float(eps), _ptr(out), _ld(out), R, self._stream())
-        _lib.check(st, 'mmmot_skippool_head')
+        self._launch('mmmot_skippool_head', P, _ld(P), C, hd['w1'].shape[0], hd['g0'], hd['b0'], hd['w1'], hd['c1'],
+                     hd['g2'], hd['b2'], hd['w4'], hd['c4'], hd['g5'], hd['b5'], eps, out, _ld(out), R)
 
     def pointnet_layer1(self, X, W, bias, Y, part, tiles):
         """X [P][K] with K = W.shape[1] in (3, 4)."""
-        st = self.lib.mmmot_pointnet_layer1(_ptr(X), int(W.shape[1]), _ptr(W), _ptr(bias), _ptr(Y), _ptr(part),
-                                            _iptr(tiles.row0), _iptr(tiles.nrows), tiles.T, self._stream())
-        _lib.check(st, 'mmmot_pointnet_layer1')
+        self._launch('mmmot_pointnet_layer1', X, W.shape[1], W, bias, Y, part, tiles.row0, tiles.nrows, tiles.T)
 
     def affine_act(self, X, C, sc, sh, tiles, act, Y):
-        st = self.lib.mmmot_affine_act(_ptr(X), _ld(X), C, _ptr(sc), _ptr(sh), _ld(sc), _iptr(tiles.row0),
-                                       _iptr(tiles.nrows), _iptr(tiles.group), tiles.T, act, _ptr(Y), _ld(Y),
-                                       self._stream())
-        _lib.check(st, 'mmmot_affine_act')
+        self._launch('mmmot_affine_act', X, _ld(X), C, sc, sh, _ld(sc), tiles.row0, tiles.nrows, tiles.group, tiles.T, act,
+                     Y, _ld(Y))
 
     def fusion_combine(self, mode, cat, Y0, Y1, sc0, sh0, sc1, sh1, tiles, F, Lt, C):
-        st = self.lib.mmmot_fusion_combine(mode, _ptr(cat), _ptr(Y0), _ld(Y0), _ptr(Y1), _ld(Y1), _ptr(sc0),
-                                           _ptr(sh0), _ptr(sc1), _ptr(sh1), _ld(sc0), _iptr(tiles.row0),
-                                           _iptr(tiles.nrows), _iptr(tiles.group), tiles.T, _ptr(F), Lt, C,
-                                           self._stream())
-        _lib.check(st, 'mmmot_fusion_combine')
+        self._launch('mmmot_fusion_combine', mode, cat, Y0, _ld(Y0), Y1, _ld(Y1), sc0, sh0, sc1, sh1, _ld(sc0),
+                     tiles.row0, tiles.nrows, tiles.group, tiles.T, F, Lt, C)
 
     def softmax_pairs(self, logits, out, row0, gN, gM, G, max_nm, mode):
-        st = self.lib.mmmot_softmax_pairs(_ptr(logits), _ptr(out), _iptr(row0), _iptr(gN), _iptr(gM), G,
-                                          max_nm, mode, self._stream())
-        _lib.check(st, 'mmmot_softmax_pairs')
+        self._launch('mmmot_softmax_pairs', logits, out, row0, gN, gM, G, max_nm, mode)
 
     # ---- frame-pair association (include/mmmot_hip.h, csrc/assign.hip) ------------------------------------------
     def associate_pairs(self, det, new, end, link, pairs, B, max_nm, out, out_off, objective):
         """B frame pairs solved exactly in one launch; see mmmot_associate_pairs.  pairs / out_off: int32 device tensors."""
-        st = self.lib.mmmot_associate_pairs(_ptr(det), _ptr(new), _ptr(end), _ptr(link), _iptr(pairs), int(B),
-                                            int(max_nm), _ptr(out), _iptr(out_off), _ptr(objective, torch.float64),
-                                            self._stream())
-        _lib.check(st, 'mmmot_associate_pairs')
+        self._launch('mmmot_associate_pairs', det, new, end, link, pairs, B, max_nm, out, out_off, objective)
 
     def associate_chains(self, det, new, end, link, chains, B, max_n, max_L, out, out_off, objective):
         """B chains of 2 .. 8 frames solved exactly in one launch; see mmmot_associate_chains.  chains / out_off: int32
         device tensors."""
-        st = self.lib.mmmot_associate_chains(_ptr(det), _ptr(new), _ptr(end), _ptr(link), _iptr(chains), int(B),
-                                             int(max_n), int(max_L), _ptr(out), _iptr(out_off),
-                                             _ptr(objective, torch.float64), self._stream())
-        _lib.check(st, 'mmmot_associate_chains')
+        self._launch('mmmot_associate_chains', det, new, end, link, chains, B, max_n, max_L, out, out_off, objective)
 
     def associate_sequences(self, det, new, end, link, seqs, nts, B, max_T, max_n, max_L, out, ids, objective, info, ws):
         """B whole sequences solved exactly in one launch; see mmmot_associate_sequences.  seqs / nts / ids / info: int32
@@ -423,66 +409,48 @@ class HipOps:
                                 info, ws):
         """B whole sequences with skip links of up to ``max_gap`` frames solved exactly in one launch; see
         mmmot_associate_sequences_gap.  seqs / nts / ids / info: int32 device tensors; ws: the fp64 workspace."""
-        self._associate_sequences('mmmot_associate_sequences_gap', (int(max_gap),), det, new, end, link, seqs, nts, B,
+        self._associate_sequences('mmmot_associate_sequences_gap', (max_gap,), det, new, end, link, seqs, nts, B,
                                   max_T, max_n, max_L, out, ids, objective, info, ws)
 
     def _associate_sequences(self, name, gap, det, new, end, link, seqs, nts, B, max_T, max_n, max_L, out, ids, objective,
                              info, ws):
         """the two entries' one argument list; ``gap``: () or (max_gap,), which the gap entry takes after max_L"""
-        st = getattr(self.lib, name)(_ptr(det), _ptr(new), _ptr(end), _ptr(link), _iptr(seqs), _iptr(nts), int(B),
-                                     int(nts.numel()), int(max_T), int(max_n), int(max_L), *gap,
-                                     int(min(det.numel(), new.numel(), end.numel())), int(link.numel()), _ptr(out),
-                                     int(out.numel()), _iptr(ids), _ptr(objective, torch.float64), _iptr(info),
-                                     _ptr(ws, torch.float64), int(ws.numel()), self._stream())
-        _lib.check(st, name)
+        self._launch(name, det, new, end, link, seqs, nts, B, nts.numel(), max_T, max_n, max_L, *gap,
+                     min(det.numel(), new.numel(), end.numel()), link.numel(), out, out.numel(), ids, objective, info, ws,
+                     ws.numel())
 
     def track_ids(self, blocks, pairs, out_off, frame_idx, B, max_nm, state, ids_out):
         """Track IDs of B consecutive pairs of one sequence from their solver blocks; see mmmot_track_ids.  pairs /
         out_off / frame_idx / state / ids_out: int32 device tensors; state is updated in place."""
-        st = self.lib.mmmot_track_ids(_ptr(blocks), _iptr(pairs), _iptr(out_off), _iptr(frame_idx), int(B), int(max_nm),
-                                      _iptr(state), _iptr(ids_out), self._stream())
-        _lib.check(st, 'mmmot_track_ids')
+        self._launch('mmmot_track_ids', blocks, pairs, out_off, frame_idx, B, max_nm, state, ids_out)
 
     def track_chain_ids(self, blocks, chains, out_off, frame_idx, B, max_n, state, ids_out):
         """Track IDs of B consecutive windows (2 .. 8 frames) of one sequence from their solver blocks; see
         mmmot_track_chain_ids.  chains / out_off / frame_idx / state / ids_out: int32 device tensors; state is updated in
         place."""
-        st = self.lib.mmmot_track_chain_ids(_ptr(blocks), _iptr(chains), _iptr(out_off), _iptr(frame_idx), int(B),
-                                            int(max_n), _iptr(state), _iptr(ids_out), self._stream())
-        _lib.check(st, 'mmmot_track_chain_ids')
+        self._launch('mmmot_track_chain_ids', blocks, chains, out_off, frame_idx, B, max_n, state, ids_out)
 
     def track_ids_multi(self, blocks, table, out_off, frame_idx, seq_start, S, B, max_n, states, ids_out, chains=False):
         """The ID step of S sequences in one launch; see mmmot_track_ids_multi / mmmot_track_chain_ids_multi
         (``chains``).  seq_start [S + 1] and the state table [S, TRACK_STATE_INTS] are int32 device tensors."""
-        name = 'mmmot_track_chain_ids_multi' if chains else 'mmmot_track_ids_multi'
-        st = getattr(self.lib, name)(_ptr(blocks), _iptr(table), _iptr(out_off), _iptr(frame_idx), _iptr(seq_start),
-                                     int(S), int(B), int(max_n), _iptr(states), _iptr(ids_out), self._stream())
-        _lib.check(st, name)
+        self._launch('mmmot_track_chain_ids_multi' if chains else 'mmmot_track_ids_multi', blocks, table, out_off,
+                     frame_idx, seq_start, S, B, max_n, states, ids_out)
 
     def clear_mot(self, boxes, nG, nT, nD, frames, NF, g_attr, t_attr, traj_off, traj_obj, NTr, seq_off, S, params,
                   frame_d, frame_i, gt_out, traj_i, seq_d, seq_i):
         """CLEAR-MOT evaluation of S sequences in four launches; see mmmot_clear_mot.  boxes / frame_d / seq_d: fp64
         device tensors, the rest int32; params: (min_overlap, min_height, max_truncation, max_occlusion)."""
-        d = torch.float64
-        st = self.lib.mmmot_clear_mot(_ptr(boxes, d), int(nG), int(nT), int(nD), _iptr(frames), int(NF), _iptr(g_attr),
-                                      _iptr(t_attr), _iptr(traj_off), _iptr(traj_obj), int(NTr), _iptr(seq_off), int(S),
-                                      float(params[0]), float(params[1]), float(params[2]), float(params[3]),
-                                      _ptr(frame_d, d), _iptr(frame_i), _iptr(gt_out), _iptr(traj_i), _ptr(seq_d, d),
-                                      _iptr(seq_i), self._stream())
-        _lib.check(st, 'mmmot_clear_mot')
+        self._launch('mmmot_clear_mot', boxes, nG, nT, nD, frames, NF, g_attr, t_attr, traj_off, traj_obj, NTr, seq_off, S,
+                     params[0], params[1], params[2], params[3], frame_d, frame_i, gt_out, traj_i, seq_d, seq_i)
 
     def hota(self, boxes, nG, nT, nD, frames, NF, frame_seq, g_attr, t_id, seq_tab, S, cells, sumG, sumT, max_boxes,
              max_dontcare, params, prepare, work, frame_d, frame_i, seq_d, seq_i):
         """HOTA / IDF1 evaluation of S sequences in a fixed number of launches; see mmmot_hota.  boxes / frame_d /
         seq_d: fp64 device tensors, work: an int32 device tensor (8-byte aligned), the rest int32; params: (min_height,
         max_truncation, max_occlusion)."""
-        d = torch.float64
-        st = self.lib.mmmot_hota(_ptr(boxes, d), int(nG), int(nT), int(nD), _iptr(frames), int(NF), _iptr(frame_seq),
-                                 _iptr(g_attr), _iptr(t_id), _iptr(seq_tab), int(S), int(cells), int(sumG), int(sumT),
-                                 int(max_boxes), int(max_dontcare), float(params[0]), float(params[1]),
-                                 float(params[2]), int(prepare), _iptr(work), 4 * int(work.numel()), _ptr(frame_d, d),
-                                 _iptr(frame_i), _ptr(seq_d, d), _iptr(seq_i), self._stream())
-        _lib.check(st, 'mmmot_hota')
+        self._launch('mmmot_hota', boxes, nG, nT, nD, frames, NF, frame_seq, g_attr, t_id, seq_tab, S, cells, sumG, sumT,
+                     max_boxes, max_dontcare, params[0], params[1], params[2], prepare, _iptr(work), 4 * work.numel(),
+                     frame_d, frame_i, seq_d, seq_i)
 
     def mot3d(self, boxes, box3d, sigma, nG, nT, nD, frames, cell_off, NF, g_attr, t_attr, traj_off, traj_obj, NTr,
               seq_off, S, mode, levels, phase, params, table, cells, msig, frame_d, frame_i, gt_out, traj_i, seq_d, seq_i,
@@ -490,43 +458,29 @@ class HipOps:
         """One phase of the 3D MOT evaluation of S sequences; see mmmot_mot3d.  boxes / box3d / sigma / table / msig /
         frame_d / seq_d / thr: fp64 device tensors, the rest int32; params: (gate, min_height, max_truncation,
         max_occlusion)."""
-        d = torch.float64
-        st = self.lib.mmmot_mot3d(_ptr(boxes, d), _ptr(box3d, d), _ptr(sigma, d), int(nG), int(nT), int(nD),
-                                  _iptr(frames), _iptr(cell_off), int(NF), _iptr(g_attr), _iptr(t_attr), _iptr(traj_off),
-                                  _iptr(traj_obj), int(NTr), _iptr(seq_off), int(S), int(mode), int(levels), int(phase),
-                                  float(params[0]), float(params[1]), float(params[2]), float(params[3]),
-                                  _ptr(table, d), int(cells), _ptr(msig, d), _ptr(frame_d, d), _iptr(frame_i),
-                                  _iptr(gt_out), _iptr(traj_i), _ptr(seq_d, d), _iptr(seq_i), _ptr(thr, d), _iptr(reach),
-                                  self._stream())
-        _lib.check(st, 'mmmot_mot3d')
+        self._launch('mmmot_mot3d', boxes, box3d, sigma, nG, nT, nD, frames, cell_off, NF, g_attr, t_attr, traj_off,
+                     traj_obj, NTr, seq_off, S, mode, levels, phase, params[0], params[1], params[2], params[3], table,
+                     cells, msig, frame_d, frame_i, gt_out, traj_i, seq_d, seq_i, thr, reach)
 
     def generate_gt(self, ids, cls, chains, B, max_n, max_L, out, out_off):
         """Training targets of B chains in one launch; see mmmot_generate_gt.  ids / cls / chains / out_off: int32 device
         tensors; out: fp32."""
-        st = self.lib.mmmot_generate_gt(_iptr(ids), _iptr(cls), _iptr(chains), int(B), int(max_n), int(max_L), _ptr(out),
-                                        _iptr(out_off), self._stream())
-        _lib.check(st, 'mmmot_generate_gt')
+        self._launch('mmmot_generate_gt', ids, cls, chains, B, max_n, max_L, out, out_off)
 
     def match_dets(self, det_xywh, gt_xywh, gt_id, gt_name, frames, NF, car_code, dontcare_code, max_iou, max_n, det_id,
                    det_cls):
         """Ground-truth id and class of the detections of NF frames in one launch; see mmmot_match_dets.  det_xywh /
         gt_xywh: fp64 device tensors, the rest int32."""
-        d = torch.float64
-        st = self.lib.mmmot_match_dets(_ptr(det_xywh, d), _ptr(gt_xywh, d), _iptr(gt_id), _iptr(gt_name), _iptr(frames),
-                                       int(NF), int(car_code), int(dontcare_code), float(max_iou), int(max_n),
-                                       _iptr(det_id), _iptr(det_cls), self._stream())
-        _lib.check(st, 'mmmot_match_dets')
+        self._launch('mmmot_match_dets', det_xywh, gt_xywh, gt_id, gt_name, frames, NF, car_code, dontcare_code, max_iou,
+                     max_n, det_id, det_cls)
 
     def fill_tracks(self, det, ids, frame_start, frame_no, seq_start, xf, wtab, L, F, S, max_fill, capacity, work,
                     fill_start, out, out_id, out_src, info):
         """Gap filling of S tracked sequences in five launches; see mmmot_fill_tracks.  det / out: fp32 device tensors,
         xf (or None: a standing camera) / wtab: fp64, the rest int32.  Returns the entry's status instead of raising, so
         that a caller can tell a refused call (MMMOT_EINVAL) from its results."""
-        d = torch.float64
-        return self.lib.mmmot_fill_tracks(_ptr(det), _iptr(ids), _iptr(frame_start), _iptr(frame_no), _iptr(seq_start),
-                                          _ptr(xf, d), _ptr(wtab, d), int(L), int(F), int(S), int(max_fill),
-                                          int(capacity), _iptr(work), _iptr(fill_start), _ptr(out), _iptr(out_id),
-                                          _iptr(out_src), _iptr(info), self._stream())
+        return self._status('mmmot_fill_tracks', det, ids, frame_start, frame_no, seq_start, xf, wtab, L, F, S, max_fill,
+                            capacity, work, fill_start, out, out_id, out_src, info)
 
     def adam_step(self, chunks, ptrs, scal, beta1, beta2, eps):
         """One Adam step of T tensors in one launch; see mmmot_adam_step and mmmot::adam_step (torch_ops.py).  chunks: the
@@ -539,28 +493,19 @@ class HipOps:
 
     def adam_step_table(self, table, T, chunks, n_chunks, beta1, beta2, eps):
         """The launch alone, on a packed table: the device uint8 block of T 64-byte mmmot_adam_row rows."""
-        st = self.lib.mmmot_adam_step(_ptr(table, torch.uint8), int(T), _iptr(chunks), int(n_chunks), float(beta1),
-                                      float(beta2), float(eps), self._stream())
-        _lib.check(st, 'mmmot_adam_step')
+        self._launch('mmmot_adam_step', table, T, chunks, n_chunks, beta1, beta2, eps)
 
     # ---- training backward of the pairwise block (include/mmmot_hip.h, csrc/backward.hip) -------------------
     def gn_bwd_partial(self, dA, Y, C, sc1, sh1, gamma, beta, relu, tiles, P):
-        st = self.lib.mmmot_gn_bwd_partial(_ptr(dA), _ld(dA), _ptr(Y), _ld(Y), C, _ptr(sc1), _ptr(sh1), _ld(sc1),
-                                           _ptr(gamma), _ptr(beta), int(relu), _iptr(tiles.row0), _iptr(tiles.nrows),
-                                           _iptr(tiles.group), tiles.T, _ptr(P), self._stream())
-        _lib.check(st, 'mmmot_gn_bwd_partial')
+        self._launch('mmmot_gn_bwd_partial', dA, _ld(dA), Y, _ld(Y), C, sc1, sh1, _ld(sc1), gamma, beta, relu, tiles.row0,
+                     tiles.nrows, tiles.group, tiles.T, P)
 
     def gn_bwd_finalize(self, S, tiles, C, NG, gamma, M):
-        st = self.lib.mmmot_gn_bwd_finalize(_ptr(S), _iptr(tiles.g_count), tiles.G, C, NG, _ptr(gamma), _ptr(M),
-                                            self._stream())
-        _lib.check(st, 'mmmot_gn_bwd_finalize')
+        self._launch('mmmot_gn_bwd_finalize', S, tiles.g_count, tiles.G, C, NG, gamma, M)
 
     def gn_bwd_apply(self, dA, Y, C, sc1, sh1, gamma, beta, relu, M, tiles, dY):
-        st = self.lib.mmmot_gn_bwd_apply(_ptr(dA), _ld(dA), _ptr(Y), _ld(Y), C, _ptr(sc1), _ptr(sh1), _ld(sc1),
-                                         _ptr(gamma), _ptr(beta), int(relu), _ptr(M), _iptr(tiles.row0),
-                                         _iptr(tiles.nrows), _iptr(tiles.group), tiles.T, _ptr(dY), _ld(dY),
-                                         self._stream())
-        _lib.check(st, 'mmmot_gn_bwd_apply')
+        self._launch('mmmot_gn_bwd_apply', dA, _ld(dA), Y, _ld(Y), C, sc1, sh1, _ld(sc1), gamma, beta, relu, M, tiles.row0,
+                     tiles.nrows, tiles.group, tiles.T, dY, _ld(dY))
 
     def gemm_tn(self, dY, tiles, N, K, dW, db=None, X=None, sc=None, sh=None, FA=None, FB=None, pair=None,
                 amode=A_PLAIN, pairop=0, nsplit=1):
@@ -586,130 +531,94 @@ class HipOps:
             # one scalar per (device, stream): two backward passes issued on different streams through one HipOps
             # must not land their maxima in each other's scale
             amax = self._scratch(('tn_amax', int(self._stream() or 0)), 1, dY.device)
-            _lib.check(self.lib.mmmot_absmax(_ptr(dY), _ld(dY), tiles.R, N, _ptr(amax), self._stream()), 'mmmot_absmax')
-            _lib.check(self.lib.mmmot_gemm_tn_f16(ctypes.byref(a), _ptr(amax), self._stream()), 'mmmot_gemm_tn_f16')
+            self._launch('mmmot_absmax', dY, _ld(dY), tiles.R, N, amax)
+            self._launch('mmmot_gemm_tn_f16', ctypes.byref(a), amax)
             return
-        _lib.check(self.lib.mmmot_gemm_tn(ctypes.byref(a), self._stream()), 'mmmot_gemm_tn')
+        self._launch('mmmot_gemm_tn', ctypes.byref(a))
 
     def pair_bwd(self, dX, F, dF, C, row0, gN, gM, aoff, boff, blk_group, blk_idx, pairop, side):
-        st = self.lib.mmmot_pair_bwd(_ptr(dX), _ld(dX), _ptr(F), _ld(F), _ptr(dF), _ld(dF), C, _iptr(row0), _iptr(gN),
-                                     _iptr(gM), _iptr(aoff), _iptr(boff), _iptr(blk_group), _iptr(blk_idx),
-                                     blk_group.numel(), pairop, side, self._stream())
-        _lib.check(st, 'mmmot_pair_bwd')
+        self._launch('mmmot_pair_bwd', dX, _ld(dX), F, _ld(F), dF, _ld(dF), C, row0, gN, gM, aoff, boff, blk_group,
+                     blk_idx, blk_group.numel(), pairop, side)
 
     def pair_expand_bwd(self, dV, dA, C, tiles, row0, gN, gM, vrow0):
-        st = self.lib.mmmot_pair_expand_bwd(_ptr(dV), _ld(dV), _ptr(dA), _ld(dA), C, _iptr(tiles.row0),
-                                            _iptr(tiles.nrows), _iptr(tiles.group), tiles.T, _iptr(row0), _iptr(gN),
-                                            _iptr(gM), _iptr(vrow0), self._stream())
-        _lib.check(st, 'mmmot_pair_expand_bwd')
+        self._launch('mmmot_pair_expand_bwd', dV, _ld(dV), dA, _ld(dA), C, tiles.row0, tiles.nrows, tiles.group, tiles.T,
+                     row0, gN, gM, vrow0)
 
     def segment_argmax(self, X, C, segs, idx, sc=None, sh=None, relu=False, use_group=True):
         """idx int32 [segs.n][>= C] <- the first row (0 .. count - 1) of every segment that attains the maximum
         segment_mean(take_max=True) writes for the same arguments"""
-        st = self.lib.mmmot_segment_argmax(_ptr(X), _ld(X), C, _iptr(segs.start), _iptr(segs.count), _iptr(segs.stride),
-                                           _iptr(segs.group) if use_group else None, segs.n, _ptr(sc), _ptr(sh),
-                                           _ld(sc), int(bool(relu)), _iptr(idx), _ld(idx), self._stream())
-        _lib.check(st, 'mmmot_segment_argmax')
+        self._launch('mmmot_segment_argmax', X, _ld(X), C, segs.start, segs.count, segs.stride,
+                     segs.group if use_group else None, segs.n, sc, sh, _ld(sc), bool(relu), idx, _ld(idx))
 
     def pair_expand_max_bwd(self, dV, idx, dA, C, tiles, row0, gN, gM, vrow0):
-        st = self.lib.mmmot_pair_expand_max_bwd(_ptr(dV), _ld(dV), _iptr(idx), _ld(idx), _ptr(dA), _ld(dA), C,
-                                                _iptr(tiles.row0), _iptr(tiles.nrows), _iptr(tiles.group), tiles.T,
-                                                _iptr(row0), _iptr(gN), _iptr(gM), _iptr(vrow0), self._stream())
-        _lib.check(st, 'mmmot_pair_expand_max_bwd')
+        self._launch('mmmot_pair_expand_max_bwd', dV, _ld(dV), idx, _ld(idx), dA, _ld(dA), C, tiles.row0, tiles.nrows,
+                     tiles.group, tiles.T, row0, gN, gM, vrow0)
 
     def rowdot_bwd(self, X, K, w, b, sc, sh, tiles, act, gout, gidx, dA, PW):
-        st = self.lib.mmmot_rowdot_bwd(_ptr(X), _ld(X), K, _ptr(w), float(b), _ptr(sc), _ptr(sh), _ld(sc),
-                                       _iptr(tiles.row0), _iptr(tiles.nrows), _iptr(tiles.group), tiles.T, act,
-                                       _ptr(gout), _iptr(gidx), _ptr(dA), _ld(dA), _ptr(PW), _ld(PW), self._stream())
-        _lib.check(st, 'mmmot_rowdot_bwd')
+        self._launch('mmmot_rowdot_bwd', X, _ld(X), K, w, b, sc, sh, _ld(sc), tiles.row0, tiles.nrows, tiles.group,
+                     tiles.T, act, gout, gidx, dA, _ld(dA), PW, _ld(PW))
 
     def softmax_pairs_bwd(self, logits, dout, dlogits, row0, gN, gM, G, max_nm, mode):
-        st = self.lib.mmmot_softmax_pairs_bwd(_ptr(logits), _ptr(dout), _ptr(dlogits), _iptr(row0), _iptr(gN),
-                                              _iptr(gM), G, max_nm, mode, self._stream())
-        _lib.check(st, 'mmmot_softmax_pairs_bwd')
+        self._launch('mmmot_softmax_pairs_bwd', logits, dout, dlogits, row0, gN, gM, G, max_nm, mode)
 
     def fusion_c_bwd(self, dFu, Y0, Y1, sc0, sh0, sc1, sh1, tiles, DY0, DY1, DN0, DN1, C):
-        st = self.lib.mmmot_fusion_c_bwd(_ptr(dFu), _ptr(Y0), _ld(Y0), _ptr(Y1), _ld(Y1), _ptr(sc0), _ptr(sh0),
-                                         _ptr(sc1), _ptr(sh1), _ld(sc0), _iptr(tiles.row0), _iptr(tiles.nrows),
-                                         _iptr(tiles.group), tiles.T, _ptr(DY0), _ptr(DY1), _ld(DY0), _ptr(DN0),
-                                         _ptr(DN1), C, self._stream())
-        _lib.check(st, 'mmmot_fusion_c_bwd')
+        self._launch('mmmot_fusion_c_bwd', dFu, Y0, _ld(Y0), Y1, _ld(Y1), sc0, sh0, sc1, sh1, _ld(sc0), tiles.row0,
+                     tiles.nrows, tiles.group, tiles.T, DY0, DY1, _ld(DY0), DN0, DN1, C)
 
     def add_rows(self, A, B, Y, C):
-        st = self.lib.mmmot_add_rows(_ptr(A), _ld(A), _ptr(B), _ld(B), _ptr(Y), _ld(Y), A.shape[0], C, self._stream())
-        _lib.check(st, 'mmmot_add_rows')
+        self._launch('mmmot_add_rows', A, _ld(A), B, _ld(B), Y, _ld(Y), A.shape[0], C)
 
     # ---- training step, second slice (csrc/train.hip) ----------------------------------------------------------
     def rows_gather_scale(self, S, rowidx, scale, X, C):
         """X[r][:C] = S[rowidx[r]][:C] * scale[rowidx[r]] (scale None: 1): backward of the per-detection average pools"""
-        st = self.lib.mmmot_rows_gather_scale(_ptr(S), _ld(S), _iptr(rowidx), _ptr(scale), _ptr(X), _ld(X), X.shape[0], C,
-                                              self._stream())
-        _lib.check(st, 'mmmot_rows_gather_scale')
+        self._launch('mmmot_rows_gather_scale', S, _ld(S), rowidx, scale, X, _ld(X), X.shape[0], C)
 
     # ---- dropout of the LiDAR encoder (csrc/dropout.hip): keep(r, c) = philox(seed; r, c >> 2)[c & 3] >= threshold ----
     def segment_mean_dropout(self, X, C, segs, out, sc, sh, seed, threshold, scale, use_group=True):
         """segment_mean(relu=True) over the dropped rows: mean_t keep(r, c) * scale * relu(X[r][c] * sc + sh)"""
-        st = self.lib.mmmot_segment_mean_dropout(_ptr(X), _ld(X), C, _iptr(segs.start), _iptr(segs.count),
-                                                 _iptr(segs.group) if use_group else None, segs.n, _ptr(sc), _ptr(sh),
-                                                 _ld(sc), int(seed), int(threshold), float(scale), _ptr(out), _ld(out),
-                                                 self._stream())
-        _lib.check(st, 'mmmot_segment_mean_dropout')
+        self._launch('mmmot_segment_mean_dropout', X, _ld(X), C, segs.start, segs.count,
+                     segs.group if use_group else None, segs.n, sc, sh, _ld(sc), seed, threshold, scale, out, _ld(out))
 
     def rows_gather_scale_dropout(self, S, rowidx, scale, X, C, seed, threshold, dscale):
         """rows_gather_scale times the mask: X[r][:C] = keep(r, c) * dscale * (S[rowidx[r]][:C] * scale[rowidx[r]])"""
-        st = self.lib.mmmot_rows_gather_scale_dropout(_ptr(S), _ld(S), _iptr(rowidx), _ptr(scale), _ptr(X), _ld(X),
-                                                      X.shape[0], C, int(seed), int(threshold), float(dscale),
-                                                      self._stream())
-        _lib.check(st, 'mmmot_rows_gather_scale_dropout')
+        self._launch('mmmot_rows_gather_scale_dropout', S, _ld(S), rowidx, scale, X, _ld(X), X.shape[0], C, seed,
+                     threshold, dscale)
 
     def dropout_mask(self, seed, threshold, out):
         """out uint8 [R][C] contiguous <- keep(r, c): the mask exactly as the two kernels above see it"""
         if out.dim() != 2 or not out.is_contiguous():
             raise ValueError('dropout_mask writes a contiguous [R][C] uint8 tensor')
-        st = self.lib.mmmot_dropout_mask(int(seed), int(threshold), out.shape[0], out.shape[1], _ptr(out, torch.uint8),
-                                         self._stream())
-        _lib.check(st, 'mmmot_dropout_mask')
+        self._launch('mmmot_dropout_mask', seed, threshold, out.shape[0], out.shape[1], out)
 
     def pointnet_layer1_bwd(self, dY, X, tiles, PW):
         """PW [T][64 * (K + 1)] per-tile partials of (dW1 [64][K] | db1 [64]) interleaved per channel; K = X.shape[1]"""
-        st = self.lib.mmmot_pointnet_layer1_bwd(_ptr(dY), _ptr(X), int(X.shape[1]), _iptr(tiles.row0), _iptr(tiles.nrows),
-                                                tiles.T, _ptr(PW), self._stream())
-        _lib.check(st, 'mmmot_pointnet_layer1_bwd')
+        self._launch('mmmot_pointnet_layer1_bwd', dY, X, X.shape[1], tiles.row0, tiles.nrows, tiles.T, PW)
 
     def score_loss(self, x, y, kind, scale, g, PL, mrow=None, mcol=None, M=0, mask_mode=0, ignore=-1.0, accumulate=False):
         """one TrackingLoss term over x [R][C] (see mmmot_score_loss); PL [nblocks] partial sums of the scaled loss
         (accumulate: added to PL's contents)"""
         R, C = x.shape
-        st = self.lib.mmmot_score_loss(_ptr(x), _ld(x), _ptr(y), _ptr(mrow), _ptr(mcol), int(M), int(mask_mode),
-                                       float(ignore), int(kind), float(scale), R, C, _ptr(g), _ld(g), _ptr(PL),
-                                       PL.numel(), int(bool(accumulate)), self._stream())
-        _lib.check(st, 'mmmot_score_loss')
+        self._launch('mmmot_score_loss', x, _ld(x), y, mrow, mcol, M, mask_mode, ignore, kind, scale, R, C, g, _ld(g), PL,
+                     PL.numel(), bool(accumulate))
 
     # ---- training step, third slice: training-mode VGG trunk (csrc/train_vgg.hip, conv3x3.hip RAW) ----
     def ghm_loss(self, x, y, scale, g, PL, acc_sum, bins=30, momentum=0.75, ignore=-1.0, accumulate=False):
         """the 'ghm' DetLoss term (mmmot_ghm_loss): x, g [R][C]; y [C]; acc_sum float64 [bins] = the module's running state"""
         R, C = x.shape
-        st = self.lib.mmmot_ghm_loss(_ptr(x), _ld(x), _ptr(y), float(ignore), float(scale), R, C, int(bins), float(momentum),
-                                     _ptr(acc_sum, torch.float64), _ptr(g), _ld(g), _ptr(PL), int(accumulate), self._stream())
-        _lib.check(st, 'mmmot_ghm_loss')
+        self._launch('mmmot_ghm_loss', x, _ld(x), y, ignore, scale, R, C, bins, momentum, acc_sum, g, _ld(g), PL,
+                     accumulate)
 
     def conv3x3_raw(self, inp, wp, bias, out, L, H, W, Cin, Cout, first):
-        st = self.lib.mmmot_conv3x3_raw(_ptr(inp), _ptr(wp), _ptr(bias), _ptr(out), L, H, W, Cin, Cout, int(first),
-                                        self._stream())
-        _lib.check(st, 'mmmot_conv3x3_raw')
+        self._launch('mmmot_conv3x3_raw', inp, wp, bias, out, L, H, W, Cin, Cout, first)
 
     def rows_stats(self, Y, C, tiles, part):
-        st = self.lib.mmmot_rows_stats(_ptr(Y), _ld(Y), C, _iptr(tiles.row0), _iptr(tiles.nrows), tiles.T, _ptr(part),
-                                       self._stream())
-        _lib.check(st, 'mmmot_rows_stats')
+        self._launch('mmmot_rows_stats', Y, _ld(Y), C, tiles.row0, tiles.nrows, tiles.T, part)
 
     def bn_relu_pool(self, Z, C, sc, sh, L, H, W, pool, A):
-        st = self.lib.mmmot_bn_relu_pool(_ptr(Z), C, _ptr(sc), _ptr(sh), L, H, W, int(bool(pool)), _ptr(A), self._stream())
-        _lib.check(st, 'mmmot_bn_relu_pool')
+        self._launch('mmmot_bn_relu_pool', Z, C, sc, sh, L, H, W, bool(pool), A)
 
     def maxpool_bwd(self, Z, C, sc, sh, dP, L, H, W, dA):
-        st = self.lib.mmmot_maxpool_bwd(_ptr(Z), C, _ptr(sc), _ptr(sh), _ptr(dP), L, H, W, _ptr(dA), self._stream())
-        _lib.check(st, 'mmmot_maxpool_bwd')
+        self._launch('mmmot_maxpool_bwd', Z, C, sc, sh, dP, L, H, W, dA)
 
     def conv3x3_wgrad(self, dZ, A, L, H, W, Cin, Cout, nsplit, dW, amax=None):
         if self.tn_f16:
@@ -717,18 +626,13 @@ class HipOps:
             # (`amax`: that maximum when the caller has it already - the input-gradient convolution uses the same one)
             if amax is None:
                 amax = self._scratch(('tn_amax', int(self._stream() or 0)), 1, dZ.device)
-                _lib.check(self.lib.mmmot_absmax(_ptr(dZ), Cout, L * H * W, Cout, _ptr(amax), self._stream()), 'mmmot_absmax')
-            st = self.lib.mmmot_conv3x3_wgrad_f16(_ptr(dZ), _ptr(A), L, H, W, Cin, Cout, nsplit, _ptr(dW), _ptr(amax),
-                                                  self._stream())
-            _lib.check(st, 'mmmot_conv3x3_wgrad_f16')
+                self._launch('mmmot_absmax', dZ, Cout, L * H * W, Cout, amax)
+            self._launch('mmmot_conv3x3_wgrad_f16', dZ, A, L, H, W, Cin, Cout, nsplit, dW, amax)
             return
-        st = self.lib.mmmot_conv3x3_wgrad(_ptr(dZ), _ptr(A), L, H, W, Cin, Cout, nsplit, _ptr(dW), self._stream())
-        _lib.check(st, 'mmmot_conv3x3_wgrad')
+        self._launch('mmmot_conv3x3_wgrad', dZ, A, L, H, W, Cin, Cout, nsplit, dW)
 
     def conv3x3_first_wgrad(self, dZ, X, L, H, W, PW):
-        st = self.lib.mmmot_conv3x3_first_wgrad(_ptr(dZ), _ptr(X), L, H, W, _ptr(PW), PW.shape[0], self._stream())
-        _lib.check(st, 'mmmot_conv3x3_first_wgrad')
+        self._launch('mmmot_conv3x3_first_wgrad', dZ, X, L, H, W, PW, PW.shape[0])
 
     def selftest_mfma(self, A, B, C, K):
-        _lib.check(self.lib.mmmot_selftest_mfma(_ptr(A), _ptr(B), _ptr(C), K, self._stream()),
-                   'mmmot_selftest_mfma')
+        self._launch('mmmot_selftest_mfma', A, B, C, K)

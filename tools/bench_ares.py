@@ -39,7 +39,7 @@ def main():
         cs = torch.empty(half.T, N).cuda()
         osc, osh = torch.ones(1, N).cuda(), torch.zeros(1, N).cuda()
         for mode, var in [(m, v) for m in a.modes for v in a.variants]:
-            ops.lib.mmmot_set_gemm_ares_variant(var)
+            ops._launch('mmmot_set_gemm_ares_variant', var)  # raises on a rejected variant: it must not be timed under its label
             kw = dict(part=part) if mode == 'stats' else dict(osc=osc, osh=osh, colsum=cs)
             ts = []
             for r in range(6):
@@ -53,7 +53,7 @@ def main():
             ts.sort()
             ms = ts[len(ts) // 2]
             print('K=%d N=%4d %-6s variant %d  %.3f ms  %.0f TFLOP/s-equivalent' % (K, N, mode, var, ms, 2.0 * R * N * K / ms / 1e9))
-        ops.lib.mmmot_set_gemm_ares_variant(0)
+        ops._launch('mmmot_set_gemm_ares_variant', 0)
 
 
 if __name__ == '__main__':

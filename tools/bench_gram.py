@@ -32,7 +32,7 @@ def main():
     ref = None
     for v in (a.variants if K == 128 else [0]):
         if K == 128:
-            ops.lib.mmmot_set_gram128_variant(v)
+            ops._launch('mmmot_set_gram128_variant', v)  # raises on a rejected variant: it must not be timed under its label
         Gp.zero_()
         Sp.zero_()
         ts = []
@@ -54,7 +54,7 @@ def main():
         print('gram_rows K=%d rows=%d super-tiles=%d variant %d: %.3f ms  %.2f TB/s  checksum %.6e%s' % (
             K, sum(counts), tiles.T, v, ms, sum(counts) * K * 4 / ms / 1e9, float(Gp.sum()), same))
     if K == 128:
-        ops.lib.mmmot_set_gram128_variant(0)
+        ops._launch('mmmot_set_gram128_variant', 0)
 
 if __name__ == '__main__':
     main()

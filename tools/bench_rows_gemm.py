@@ -62,7 +62,7 @@ def main():
         # variant was removed again, --ldx / --ldf still set the pitches)
         ref = None
         for v in list(a.variants):
-            ops.lib.mmmot_set_gemm_rows_variant(v)
+            ops._launch('mmmot_set_gemm_rows_variant', v)  # raises on a rejected variant: it must not be timed under its label
             Wv = W16
             ts = []
             for r in range(6):
@@ -90,7 +90,7 @@ def main():
             print('%s K=%d ld=%d N=%4d rows=%d variant %d  %.3f ms  %.0f TFLOP/s-equivalent; %d calls back to back: %.3f ms each%s' % (
                 'PAIR M=%d' % a.pair if a.pair else 'NORM', K, ldx, N, sum(counts), v, ms,
                 2.0 * sum(counts) * N * K / ms / 1e9, a.sustain, sus, same), flush=True)
-        ops.lib.mmmot_set_gemm_rows_variant(0)
+        ops._launch('mmmot_set_gemm_rows_variant', 0)
 
 
 if __name__ == '__main__':

@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes over the wide row GEMM (tools/bench_rows_gemm.py, variant 2): SQ issue/wait split, L1 -> L2 requests, LDS conflicts.
+# PMC passes over the wide row GEMM (tools/bench_rows_gemm.py, variants 3 / 4): SQ issue/wait split, L1 -> L2 requests, LDS conflicts.
 #   tools/gw_pmc.sh <out dir> [kernel substring, default gemm_wide]   (on the GPU box; one counter group per run, no trace domains)
 out=${1:-gpurun_out/gw_pmc}; pat=${2:-gemm_wide}; R=$PWD
 mkdir -p $out
