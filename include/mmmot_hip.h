@@ -566,6 +566,43 @@ int mmmot_fill_tracks(const float* det, const int* ids, const int* frame_start, 
                       void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Motion gate of links (csrc/gate_links.hip; DESIGN section 11, "Sequences: motion gate"), additive in ABI 10: a link
+ * whose two 3D boxes lie further apart than an object travels in the elapsed frames is written as a quiet NaN, which
+ * mmmot_associate, the chain entries and the sequence entries read as an absent edge.  ONE launch whatever NB, F and
+ * the frame sizes; one workgroup per block.
+ *   det         [L][12] fp32, the rows of mmmot_fill_tracks (read: h w l at 4..6, x y z at 7..9)
+ *   frame_start [F+1], frame_no [F]: as for mmmot_fill_tracks; the frames of many sequences may follow each other
+ *   blocks      [NB][4] = (frame a, frame b, link offset, 0): the n_a x n_b links from the detections of frame a to
+ *               those of frame b, row-major at link + offset.  A pair is one block, a window its consecutive pairs, a
+ *               sequence with skip links the gap-by-gap layout of mmmot_associate_sequences_gap
+ *   xf          [F][rec_gaps][MMMOT_FILL_REC] fp64 or NULL (a standing camera); only words 0..15 of record (a, b-a-1)
+ *               are read: C[a<-b], the row-vector 4x4 of mmmot_fill_tracks
+ *   r2, inv_r2  [max_dt+1] fp64, host-made: r2[dt] = (max_speed * dt + slack)^2 and its reciprocal
+ *   link        [n_link] fp32 or NULL (count-only: only kept is written);  out_link [n_link], NULL iff link is NULL; it
+ *               may be link itself
+ *   kept        [NB] out: the links of the block that passed (with link: and whose score is no NaN); -1 = broken block
+ * For detection j of frame a and k of frame b, dt = frame_no[b] - frame_no[a], all in fp64, every product and sum
+ * rounded on its own: p = (x_k, y_k, z_k, 1) C, columns 0..2 summed in order as in mmmot_align_points (skipped when xf
+ * is NULL); d = loc_j - p; d2 = dx dx + dz dz (mode 0, the camera's ground plane), + dy dy last (mode 1).  The link
+ * passes iff dt <= max_dt, d2 <= r2[dt] and - with max_size_ratio > 0 - for each of h, w, l max(a, b) <= max_size_ratio
+ * * min(a, b) (fp64; max / min by a > b); every comparison fails on a NaN operand.  A passing score is copied bit for
+ * bit when weight == 0, else it becomes (float)((double)s - weight * (d2 * inv_r2[dt])); a NaN score is copied as it
+ * is and not counted; a gated link is written as the quiet NaN 0x7fc00000.
+ * A block is broken - kept = -1, nothing else of it read or written - when a >= b, a frame index lies outside [0, F),
+ * frame_no[b] <= frame_no[a], with records b - a > rec_gaps, the offset is negative or the link range reaches past
+ * n_link, or frame_start leaves [0, L] or decreases at a or b.  Returns MMMOT_EINVAL before any launch for a negative
+ * NB / L / F / n_link, max_dt outside [1, MMMOT_GATE_MAX_DT], a mode outside {0, 1}, a max_size_ratio or weight that
+ * is negative or NaN, link NULL and out_link not (or the reverse), xf with rec_gaps < 1 and, with NB > 0, a null table
+ * (det may be null with L = 0).  NB = 0 is a no-op that returns 0.  No allocation, no synchronisation.  The launch
+ * goes to `hip_stream`, a hipStream_t the caller passes itself (the Python binding appends the current stream only to
+ * the 82 entries whose last parameter is named `stream`, a set tests/test_abi_parse_cpu.py pins). */
+#define MMMOT_GATE_MAX_DT 64
+int mmmot_gate_links(const float* det, const int* frame_start, const int* frame_no, const int* blocks,
+                     const double* xf, const double* r2, const double* inv_r2, const float* link, float* out_link,
+                     int* kept, int L, int F, int NB, int rec_gaps, long n_link, int mode, int max_dt,
+                     double max_size_ratio, double weight, void* hip_stream);
+
+/* ---------------------------------------------------------------------------
  * Per-detection image preparation: crop with zero padding -> antialiased bilinear
  * resize to S x S -> to_tensor -> normalize = the model input ``dets`` [N][3][S][S].  Replaces, per
  * detection, PIL img.crop(box).resize((S, S), Image.BILINEAR) + torchvision ToTensor/Normalize

@@ -43,6 +43,13 @@ may miss up to G - 1 frames instead of ending at the first missed detection:
         det, [links_gap1, links_gap2, links_gap3], new, end, det_split, return_ids=True)
 
 ``associate_sequence_gaps_batch`` solves B sequences with the same number of gaps in one launch.
+
+``MotionGate`` with ``gate_links`` / ``gate_sequence_links`` (DESIGN.md, "Sequences: motion gate"; csrc/gate_links.hip, one
+launch for any number of link blocks) turns the links no object could have travelled - by the 3D boxes, the frame
+numbers and, with poses, the ego motion - into NaN scores, which every solver above reads as absent edges:
+
+    from mmmot_amd.association import MotionGate, gate_sequence_links
+    gated, kept = gate_sequence_links([links_gap1, links_gap2, links_gap3], frames, MotionGate(max_speed=4.0, slack=2.0))
 """
 import numpy as np
 import torch
@@ -500,3 +507,180 @@ def associate_sequence_gaps_batch(det_scores, link_scores, new_scores, end_score
         r = unpack_gaps(out[o:o + gap_block_size(s, G)], s, G, d, [[x.size() for x in row] for row in l])
         res.append(r + (split_ids(ids[so:so + sum(s)], s), int(info[i, 1])) if return_ids else r)
     return (res, obj) if return_objective else res
+
+
+# ---- motion gate: links no object could have travelled become absent edges (csrc/gate_links.hip) -------------------------
+GATE_MAX_DT = torch_ops.GATE_MAX_DT
+
+
+class GateError(AssociationError):
+    """The motion gate found a block outside its launch contract (``kept`` = -1): the block's place in the call in
+    ``.index``, its frames in ``.frames``."""
+
+    def __init__(self, index, frames):
+        RuntimeError.__init__(self, 'gate_links: block %d (frames %d -> %d) lies outside the launch contract: frame '
+                                    'indices, increasing frame numbers, the records\' reach or the link range'
+                                    % (index, frames[0], frames[1]))
+        self.index, self.status, self.frames = index, -1, frames
+
+
+class MotionGate:
+    """The parameters of the motion gate ("Sequences: motion gate") and its two fp64 tables: a link
+    between two detections ``dt`` frame numbers apart passes iff ``1 <= dt <= max_dt`` and the squared distance of the
+    two box centres - ``mode`` 'ground': in the camera's x / z plane, '3d': with y - is at most ``r2[dt] = (max_speed *
+    dt + slack) ** 2``; with ``max_size_ratio`` > 0 also each of the three dimensions may differ by at most that factor.
+    ``weight`` > 0 lowers a passing score by ``weight * d2 / r2[dt]``; 0 leaves it bit for bit.  ``max_speed`` is in
+    metres per frame number (4.0: 40 m/s at KITTI's 10 Hz), ``slack`` in metres (the detector's localisation noise)."""
+
+    def __init__(self, max_speed=4.0, slack=2.0, max_dt=8, mode='ground', max_size_ratio=0.0, weight=0.0):
+        fin = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+        if not (fin(max_speed) and fin(slack) and max_speed >= 0 and slack >= 0 and max_speed + slack > 0):
+            raise ValueError('MotionGate: max_speed and slack must be finite and >= 0, and not both 0, got %r, %r'
+                             % (max_speed, slack))
+        if not isinstance(max_dt, (int, np.integer)) or not 1 <= int(max_dt) <= GATE_MAX_DT:
+            raise ValueError('MotionGate: max_dt must be an integer in 1 .. %d, got %r' % (GATE_MAX_DT, max_dt))
+        if mode not in torch_ops.GATE_MODES:
+            raise ValueError('MotionGate: mode must be one of %s, got %r' % (sorted(torch_ops.GATE_MODES), mode))
+        if not (fin(max_size_ratio) and (max_size_ratio == 0 or max_size_ratio >= 1)):
+            raise ValueError('MotionGate: max_size_ratio must be 0 (off) or a finite factor >= 1, got %r' % (max_size_ratio,))
+        if not (fin(weight) and weight >= 0):
+            raise ValueError('MotionGate: weight must be finite and >= 0, got %r' % (weight,))
+        self.max_speed, self.slack, self.max_dt, self.mode = float(max_speed), float(slack), int(max_dt), mode
+        self.max_size_ratio, self.weight = float(max_size_ratio), float(weight)
+        r = np.float64(self.max_speed) * np.arange(self.max_dt + 1, dtype=np.float64) + np.float64(self.slack)
+        self.r2 = r * r
+        self.inv_r2 = np.zeros_like(self.r2)  # entry 0 is never read: dt >= 1
+        self.inv_r2[1:] = np.float64(1.0) / self.r2[1:]
+
+    def block(self, p):
+        """(the int32 block of torch_ops.gate_layout, sizes) of a ``pack_gate`` result under this gate"""
+        sizes = [len(p['det']), len(p['frame_no']), len(p['blocks']), p['rec_gaps'], self.max_dt,
+                 torch_ops.GATE_MODES[self.mode], p['n_link']]
+        lay, n = torch_ops.gate_layout(sizes)
+        tab = dict(p, r2=self.r2, inv_r2=self.inv_r2)
+        packed = np.zeros(n, np.int32)
+        for name, (o, m) in lay.items():
+            if m:
+                packed[o:o + m] = np.ascontiguousarray(tab[name]).reshape(-1).view(np.int32)
+        return packed, sizes
+
+
+def gap_pairs(n_frames, max_gap):
+    """the (t, t + g) of every link block of a sequence in layout order, as ``gap_link_sizes``"""
+    return [(t, t + g) for g in range(1, int(max_gap) + 1) for t in range(int(n_frames) - g)]
+
+
+def pack_gate(frames, frame_idx=None, poses=None, calib=None, pairs=None):
+    """The host side of ``gate_links`` before the launch.  ``frames``: per frame the detection dict (``dimensions``,
+    ``location``, .. as ``tracks.pack_fill`` reads them; the frames of several sequences may follow each other);
+    ``frame_idx``: their frame numbers (default 0, 1, ..); ``pairs``: the (a, b) frame positions of every link block, a <
+    b, in the order of the blocks (default: the consecutive pairs) - ``gap_pairs(T, G)`` for a sequence with skip links.
+    ``poses``: per frame (pos, rad), for all frames or none, with ``calib`` as ``tracks.fill_gaps`` takes them; every
+    listed pair then gets the record ``ego.box_motion`` of its two frames.  Returns a dict of the tables of
+    mmmot_gate_links: ``det`` fp32 [L, 12], ``frame_start``, ``frame_no``, ``blocks`` int32 [NB, 4], ``xf`` fp64 [F,
+    rec_gaps, 33] (or None, ``rec_gaps`` 0), ``sizes`` the (n_a, n_b) per block and ``n_link``."""
+    from . import ego
+    from .tracks import box_rows
+    F = len(frames)
+    pairs = [(t, t + 1) for t in range(F - 1)] if pairs is None else [(int(a), int(b)) for a, b in pairs]
+    no = np.arange(F, dtype=np.int64) if frame_idx is None else np.asarray(frame_idx, dtype=np.int64).reshape(-1)
+    if len(no) != F:
+        raise ValueError('gate_links: %d frames but %d frame numbers' % (F, len(no)))
+    if np.abs(no).max(initial=0) >= 2 ** 31:
+        raise ValueError('gate_links: frame numbers must fit 32 bits')
+    if poses is not None and (len(poses) != F or any(q is None for q in poses)):
+        raise ValueError('gate_links: poses are given for all frames or none')
+    if poses is not None and calib is None:
+        raise ValueError('gate_links: poses need calib (R0_rect, Tr_velo_to_cam, Tr_imu_to_velo)')
+    counts = [len(np.asarray(d['location'], dtype=np.float64).reshape(-1, 3)) for d in frames]
+    det = [box_rows(d, m) for d, m in zip(frames, counts)]
+    blocks, sizes, off = [], [], 0
+    for i, (a, b) in enumerate(pairs):
+        if not 0 <= a < b < F:
+            raise ValueError('gate_links: pair %d joins frames %d -> %d; it needs 0 <= a < b < %d' % (i, a, b, F))
+        if no[b] <= no[a]:
+            raise ValueError('gate_links: pair %d: the frame numbers must increase, got %d -> %d' % (i, no[a], no[b]))
+        blocks.append((a, b, off, 0))
+        sizes.append((counts[a], counts[b]))
+        off += counts[a] * counts[b]
+    if off >= 2 ** 31 - 1:
+        raise ValueError('gate_links: the links of one launch must number fewer than 2^31')
+    xf, rec_gaps = None, 0
+    if poses is not None and pairs:
+        rec_gaps = max(b - a for a, b in pairs)
+        xf = np.zeros((F, rec_gaps, torch_ops.FILL_REC), np.float64)
+        xf[:, :, 0:16] = xf[:, :, 16:32] = np.eye(4).reshape(-1)
+        for a, b in set(pairs):
+            C, Ci, dyaw = ego.box_motion(poses[a], poses[b], calib)
+            rec = xf[a, b - a - 1]
+            rec[0:16], rec[16:32], rec[32] = C.reshape(-1), Ci.reshape(-1), dyaw
+    return {'det': np.concatenate(det + [np.zeros((0, 12), np.float32)]),
+            'frame_start': np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32),
+            'frame_no': no.astype(np.int32), 'blocks': np.asarray(blocks, np.int32).reshape(-1, 4), 'xf': xf,
+            'rec_gaps': rec_gaps, 'sizes': sizes, 'n_link': off}
+
+
+def queue_gate(p, gate, link, device):
+    """ONE upload of the call's tables and ONE launch: ``link`` (flat fp32 on ``device``, or None to count only) is
+    gated in place; returns the device kept counts [NB].  Nothing waits on the host."""
+    packed, sizes = gate.block(p)
+    dev = torch_ops._upload(device, packed)[0]
+    return torch.ops.mmmot.gate_links(dev, link, sizes, gate.max_size_ratio, gate.weight)
+
+
+def check_kept(kept, p):
+    """host kept counts -> int64 array; raises ``GateError`` naming the first block outside the contract"""
+    kept = np.asarray(kept, dtype=np.int64)
+    bad = np.nonzero(kept < 0)[0]
+    if bad.size:
+        raise GateError(int(bad[0]), tuple(int(v) for v in p['blocks'][bad[0], 0:2]))
+    return kept
+
+
+def gate_links(link_blocks, frames, gate, frame_idx=None, poses=None, calib=None, pairs=None):
+    """The motion gate over the link blocks of a pair, a window or any list of frame pairs: ``link_blocks[i]`` scores
+    the links of ``pairs[i]`` = (a, b), n_a x n_b values in any shape (1 x n_a x n_b as the solvers take them), host or
+    device.  Returns (the gated blocks in the shapes, dtype and device given - a gated link is NaN, which ``associate``,
+    ``associate_chain`` and ``associate_sequence[_gaps]`` read as an absent edge; a passing fp32 score is unchanged bit
+    for bit at ``gate.weight`` 0 - and the int64 kept counts per block).  The inputs are not modified.  One upload, one
+    launch, one copy back; raises ``GateError`` for a block outside the contract."""
+    if not isinstance(gate, MotionGate):
+        raise ValueError('gate_links: gate must be a MotionGate, got %r' % (gate,))
+    p = pack_gate(frames, frame_idx, poses, calib, pairs)
+    if len(link_blocks) != len(p['sizes']):
+        raise ValueError('gate_links: %d link blocks for %d pairs' % (len(link_blocks), len(p['sizes'])))
+    for i, (l, (a, b)) in enumerate(zip(link_blocks, p['sizes'])):
+        if l.numel() != a * b:
+            raise ValueError('gate_links: link block %d must hold %d x %d scores, got %s' % (i, a, b, tuple(l.shape)))
+    if not link_blocks:
+        return [], np.zeros(0, np.int64)
+    on_host = not link_blocks[0].is_cuda
+    flat = torch.cat([l.detach().reshape(-1).to(torch.float32) for l in link_blocks] + [link_blocks[0].new_zeros(0, dtype=torch.float32)])
+    if on_host:
+        flat = flat.to('cuda')
+    kept = queue_gate(p, gate, flat, flat.device)
+    if on_host:
+        flat = flat.cpu()
+    kept = check_kept(kept.cpu().numpy(), p)
+    out, o = [], 0
+    for l, (a, b) in zip(link_blocks, p['sizes']):
+        out.append(flat[o:o + a * b].view(l.size()).to(l.dtype))
+        o += a * b
+    return out, kept
+
+
+def gate_sequence_links(link_scores, frames, gate, frame_idx=None, poses=None, calib=None):
+    """``gate_links`` in the nested layout of ``associate_sequence_gaps``: ``link_scores[g - 1][t]`` scores the links
+    from frame t to frame t + g.  Returns (the gated blocks nested alike, the kept counts nested alike)."""
+    G, T = len(link_scores), len(frames)
+    for g, row in enumerate(link_scores, 1):
+        if len(row) != T - g:
+            raise ValueError('gate_sequence_links: gap %d needs %d link blocks, got %d' % (g, T - g, len(row)))
+    out, kept = gate_links([l for row in link_scores for l in row], frames, gate, frame_idx, poses, calib,
+                           gap_pairs(T, G))
+    nested, counts, o = [], [], 0
+    for row in link_scores:
+        nested.append(out[o:o + len(row)])
+        counts.append(kept[o:o + len(row)])
+        o += len(row)
+    return nested, counts

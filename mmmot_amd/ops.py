@@ -482,6 +482,15 @@ class HipOps:
         return self._status('mmmot_fill_tracks', det, ids, frame_start, frame_no, seq_start, xf, wtab, L, F, S, max_fill,
                             capacity, work, fill_start, out, out_id, out_src, info)
 
+    def gate_links(self, det, frame_start, frame_no, blocks, xf, r2, inv_r2, link, out_link, kept, L, F, NB, rec_gaps,
+                   n_link, mode, max_dt, max_size_ratio, weight):
+        """The motion gate over NB link blocks in one launch; see mmmot_gate_links.  det / link / out_link: fp32 device
+        tensors (link = out_link = None: count only; out_link may be link), xf (or None) / r2 / inv_r2: fp64, the rest
+        int32.  Returns the entry's status instead of raising, like ``fill_tracks``.  The entry takes its stream as an
+        ordinary argument (``hip_stream``), so it is passed here."""
+        return self._status('mmmot_gate_links', det, frame_start, frame_no, blocks, xf, r2, inv_r2, link, out_link, kept,
+                            L, F, NB, rec_gaps, n_link, mode, max_dt, max_size_ratio, weight, self._stream())
+
     def adam_step(self, chunks, ptrs, scal, beta1, beta2, eps):
         """One Adam step of T tensors in one launch; see mmmot_adam_step and mmmot::adam_step (torch_ops.py).  chunks: the
         device int32 [n, 2] chunk table; ptrs / scal: the step's HOST tables, int64 [T, 6] (p, g, m, v, numel, flags) and

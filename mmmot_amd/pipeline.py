@@ -88,7 +88,8 @@ import torch
 from .crops import crop_resize_u8, crop_resize_u8_multi
 from . import ego
 from .points import align_points_batched, prep_points_batched
-from .association import _raise_status, gap_sequences_table, select, select_chain, unpack_gaps
+from .association import (MotionGate, _raise_status, check_kept, gap_pairs, gap_sequences_table, pack_gate, queue_gate,
+                          select, select_chain, unpack_gaps)
 from .tracker_glue import queue_scores, queue_solve, queue_solve_chains
 from .torch_ops import FILL_MAX, SEQ_MAX_GAP
 from .tracks import TrackState, TrackStates, fill_gaps, merge_chain_tracks, merge_tracks, window_starts
@@ -562,21 +563,23 @@ class SequencePipeline:
                                                 appearance=torch.cat([f['rows'].rows for _, fr in grp for f in fr]))
             yield grp, outs
 
-    def _gap_links(self, frames, feeds, moving, K, B, G, gap_penalty):
+    def _gap_links(self, frames, feeds, moving, K, B, G, gap_penalty, skip=()):
         """run_global with skip links: the selected link block of every pair (f_t, f_{t+g}), g = 2 .. G, in layout order
         (gap by gap, each in frame order), flat, less ``gap_penalty * (g - 1)``.  The pairs run ``B`` at a time through
         ``forward_batch`` on the cached appearance rows; with poses the second frame of a pair is aligned to the pair's
         first frame, one launch per gap and group of ``K`` frames, and the copy is kept per gap (``points_aligned`` stays
-        the alignment to the frame before)."""
+        the alignment to the frame before).  A pair (t, g) in ``skip`` (the motion gate left it no link) is not
+        forwarded: its block is all NaN."""
         tm, n = self.model.test_mode, len(frames)
-        pairs = [(t, g) for g in range(2, G + 1) for t in range(n - g)]
+        every = [(t, g) for g in range(2, G + 1) for t in range(n - g)]
+        pairs = [p for p in every if p not in skip] if skip else every
         second = {}
         if moving:
             for g in range(2, G + 1):
                 for t0 in range(g, n, K):
                     t1 = min(t0 + K, n)
                     second.update(zip(((t, g) for t in range(t0, t1)), self._aligned_group(frames, feeds, t0, t1, g)))
-        links = []
+        links = {}
         for p0 in range(0, len(pairs), B):
             grp = [(frames[t], frames[t + g], second.get((t + g, g)), g) for t, g in pairs[p0:p0 + B]]
             plan = self.model.make_plan([([a['n'], b['n']], self._window_split([a, b])) for a, b, _, _ in grp], self.size)
@@ -584,14 +587,20 @@ class SequencePipeline:
             with torch.no_grad():
                 outs = self.model.forward_batch(plan, None, torch.cat(points),
                                                 appearance=torch.cat([f['rows'].rows for a, b, _, _ in grp for f in (a, b)]))
-            for o, (_, _, _, g) in zip(outs, grp):
+            for o, (_, _, _, g), key in zip(outs, grp, pairs[p0:p0 + B]):
                 blk = select(o[0], o[1], o[2], o[3], tm)[1][0].reshape(-1)
-                links.append(blk - gap_penalty * (g - 1) if gap_penalty != 0.0 else blk.clone())
+                links[key] = blk - gap_penalty * (g - 1) if gap_penalty != 0.0 else blk.clone()
         self.stats['pairs'] += len(pairs)
         self.stats['gap_pairs'] = self.stats.get('gap_pairs', 0) + len(pairs)
-        return links
+        if skip:
+            self.stats['gated_pairs'] = self.stats.get('gated_pairs', 0) + len(every) - len(pairs)
+            absent = lambda t, g: torch.full((frames[t]['n'] * frames[t + g]['n'],), float('nan'), dtype=torch.float32,
+                                             device=self.dev)
+            return [links[p] if p in links else absent(*p) for p in every]
+        return [links[p] for p in every]
 
-    def run_global(self, feeds, frames_per_encode=16, pairs_per_forward=8, max_gap=1, gap_penalty=0.0, fill=0):
+    def run_global(self, feeds, frames_per_encode=16, pairs_per_forward=8, max_gap=1, gap_penalty=0.0, fill=0,
+                   gate=None):
         """The whole sequence decided at once: ``run_offline``'s stage A, alignment, trunk and batched pair forwards, then
         ONE min-cost flow over all frames (association.associate_sequence; DESIGN section 11, "Sequences") in place of a
         solve per pair and the ID walk - a unit of flow is a trajectory, its number the track ID.  Needs ``window == 2``.
@@ -617,7 +626,18 @@ class SequencePipeline:
         ``tracks.fill_gaps(.., max_fill=F)`` over ALL frames of the sequence (the empty ones included; with the feeds'
         poses and the first feed's calibration when the camera moves) - one more upload, five small launches, one more
         copy, no forward.  The ``tracks.FilledTracks`` is stored as ``GlobalResult.filled``; ``self.tracks`` and
-        everything else stay as they are.  ``fill = 0``: nothing of this runs and ``.filled`` is None."""
+        everything else stay as they are.  ``fill = 0``: nothing of this runs and ``.filled`` is None.
+
+        ``gate`` = an ``association.MotionGate`` ("motion gate"): a link whose two 3D boxes lie
+        further apart than an object travels in the elapsed frames is absent from the program.  The frame numbers are
+        the kept frames' own indices in the sequence; with poses the later box is moved into the earlier frame's
+        coordinates (the feeds' poses and the first feed's calibration, as for ``fill``).  With G > 1, behind stage A one
+        count-only launch (mmmot_gate_links) and one small copy tell which gap pairs (f_t, f_{t+g}) keep no link at
+        all: those are not forwarded and their blocks are NaN; the adjacent pairs are always forwarded, det / new / end
+        come from them.  One more launch gates the assembled link scores in place in front of the solve, and its kept
+        counts ride in the solve's copy (``GlobalResult.gate_kept``, per block in layout order).  ``stats['gap_pairs']``
+        then counts the gap pairs forwarded, ``stats['gated_pairs']`` those left out, ``stats['gated_links']`` the
+        links absent from the program.  ``gate = None``: nothing of this runs."""
         if self.window != 2:
             raise ValueError('SequencePipeline.run_global assembles the scores of frame pairs: window must be 2, got %d'
                              % self.window)
@@ -628,6 +648,8 @@ class SequencePipeline:
             raise ValueError('SequencePipeline.run_global: max_gap must lie in 1 .. %d, got %s' % (SEQ_MAX_GAP, max_gap))
         if not 0 <= int(fill) <= FILL_MAX:
             raise ValueError('SequencePipeline.run_global: fill must lie in 0 .. %d, got %s' % (FILL_MAX, fill))
+        if gate is not None and not isinstance(gate, MotionGate):
+            raise ValueError('SequencePipeline.run_global: gate must be an association.MotionGate or None, got %r' % (gate,))
         moving = _check_poses(feeds)
         n_frames, all_feeds = len(feeds), feeds
         feeds, idx, _ = _skip_empty(feeds, (None, None, None))
@@ -636,14 +658,28 @@ class SequencePipeline:
         res = None
         if len(frames) >= 2:
             tm, rows = self.model.test_mode, []
+            G = min(int(max_gap), len(frames) - 1)  # the largest gap that fits
+            gated, counted = None, None
+            if gate is not None:
+                tables = pack_gate([f.dets for f in feeds], idx, [f.pose for f in feeds] if moving else None,
+                                   all_feeds[0].info if moving else None, gap_pairs(len(frames), G))
+                gated = (tables, gate)
+                if G > 1:  # which gap pairs keep a link at all: queued here, read behind the adjacent forwards
+                    counted = queue_gate(tables, gate, None, self.dev)
             for grp, outs in self._offline_forwards(frames, feeds, moving, B):
                 # the selected rows only: the batch's other rows go back to the allocator
                 rows += [tuple(x.reshape(-1).clone() for x in (d, l[0], n, e))
                          for d, l, n, e in (select(o[0], o[1], o[2], o[3], tm) for o in outs)]
                 self.stats['pairs'] += len(grp)
-            G = min(int(max_gap), len(frames) - 1)  # the largest gap that fits
-            gap_links = self._gap_links(frames, feeds, moving, K, B, G, float(gap_penalty)) if G > 1 else ()
-            res = solve_global(rows, [f['n'] for f in frames], gap_links, G)
+            skip = ()
+            if counted is not None:
+                kept = check_kept(counted.cpu().numpy(), tables)
+                skip = frozenset((a, b - a) for (a, b), k in zip(gap_pairs(len(frames), G), kept) if b - a > 1 and k == 0)
+            gap_links = self._gap_links(frames, feeds, moving, K, B, G, float(gap_penalty), skip) if G > 1 else ()
+            res = solve_global(rows, [f['n'] for f in frames], gap_links, G, gated)
+            if gate is not None:
+                self.stats['gated_links'] = self.stats.get('gated_links', 0) + tables['n_link'] - int(res.gate_kept.sum())
+                self.stats.setdefault('gated_pairs', 0)
             tracks = res.ids
         if len(idx) < n_frames:  # the frames left out: counted, and as encoded too once the trunk has run (``_account_empty``)
             self.stats['empty_frames'] = self.stats.get('empty_frames', 0) + n_frames - len(idx)
@@ -670,6 +706,7 @@ class GlobalResult:
         self.n_tracks, self.objective, self.split = n_tracks, objective, split
         self.gap_scores, self.gap_assignment, self.max_gap = list(gap_scores), list(gap_assignment), max_gap
         self.filled = None  # run_global(fill=F > 0): the tracks.FilledTracks of the whole sequence
+        self.gate_kept = None  # run_global(gate=): int64 [blocks], the links of every block the program holds
 
 
 def assemble_rows(rows, counts):
@@ -683,10 +720,12 @@ def assemble_rows(rows, counts):
     return torch.cat(det + new + end + [r[1] for r in rows])
 
 
-def solve_global(rows, counts, gap_links=(), max_gap=1):
+def solve_global(rows, counts, gap_links=(), max_gap=1, gate=None):
     """assemble, one ``associate_sequences`` launch, one copy; raises association.AssociationError on a status word.
     ``max_gap`` > 1: ``gap_links`` = the flat link blocks of the gaps 2 .. max_gap in layout order, joined behind the
-    adjacent pairs' blocks, and the launch is ``associate_sequences_gap``."""
+    adjacent pairs' blocks, and the launch is ``associate_sequences_gap``.  ``gate`` = (``pack_gate`` tables of the
+    blocks in layout order, MotionGate): one mmmot_gate_links launch gates the assembled link scores in place in front
+    of the solve, and the kept counts come back in the same copy (``GlobalResult.gate_kept``)."""
     split = [int(c) for c in counts]
     L = sum(split)
     flat = assemble_rows(rows, split)
@@ -694,26 +733,35 @@ def solve_global(rows, counts, gap_links=(), max_gap=1):
         flat = torch.cat([flat] + list(gap_links))
     flat = flat.to(torch.float32)
     scores = (flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:])
+    kept = None
+    if gate is not None:
+        if gate[0]['n_link'] != scores[3].numel():
+            raise ValueError('solve_global: the gate tables hold %d links, the scores %d' % (gate[0]['n_link'], scores[3].numel()))
+        kept = queue_gate(gate[0], gate[1], scores[3], flat.device)
     seqs, nts, _, _ = gap_sequences_table([split], max_gap)
     if max_gap == 1:
         out, ids, obj, info = torch.ops.mmmot.associate_sequences(*scores, seqs, nts)
     else:
         out, ids, obj, info = torch.ops.mmmot.associate_sequences_gap(*scores, seqs, nts, max_gap)
     # the fp64 objective first: every part then starts at a multiple of its element size, whatever L and the link count
-    parts = [obj, flat, out, ids, info.reshape(-1)]
+    parts = [obj, flat, out, ids, info.reshape(-1)] + ([kept] if kept is not None else [])
     host = torch.cat([x.view(torch.uint8) for x in parts]).cpu()  # the one copy
     o, got = 0, []
     for x in parts:
         got.append(host[o:o + x.numel() * x.element_size()].view(x.dtype))
         o += x.numel() * x.element_size()
+    if kept is not None:
+        kept = check_kept(got.pop().numpy(), gate[0])
     got = got[1:] + got[:1]  # flat, out, ids, info, objective
     _raise_status(got[3].view(1, 4).numpy())
     like = got[0][0:L]
     tail = ([i.numpy() for i in got[2].to(torch.int64).split(split)], int(got[3][1]), float(got[4][0]), split)
     sizes = [[(1, split[t], split[t + g]) for t in range(len(split) - g)] for g in range(1, max_gap + 1)]
     sc, asg = (unpack_gaps(x, split, max_gap, like, sizes) for x in (got[0], got[1]))
-    return GlobalResult((sc[0], sc[1][0], sc[2], sc[3]), (asg[0], asg[1][0], asg[2], asg[3]), *tail,
-                        gap_scores=sc[1][1:], gap_assignment=asg[1][1:], max_gap=max_gap)
+    res = GlobalResult((sc[0], sc[1][0], sc[2], sc[3]), (asg[0], asg[1][0], asg[2], asg[3]), *tail,
+                       gap_scores=sc[1][1:], gap_assignment=asg[1][1:], max_gap=max_gap)
+    res.gate_kept = kept
+    return res
 
 
 def lockstep_steps(lens):

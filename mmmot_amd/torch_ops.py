@@ -97,7 +97,8 @@ def _upload(device, *parts):
 
 
 FP64_SECTIONS = frozenset(('boxes', 'box3d', 'sigma', 'frame_d', 'seq_d', 'thr',  # of the packed evaluator blocks
-                           'xf', 'wtab'))                                          # of the gap-filling block
+                           'xf', 'wtab',                                           # of the gap-filling block
+                           'r2', 'inv_r2'))                                        # of the motion-gate block
 
 
 def _sections_layout(op, parts):
@@ -975,6 +976,61 @@ _LIB.define('fill_tracks(Tensor packed, int[] sizes) -> Tensor')
 _LIB.impl('fill_tracks', _fill_tracks, 'CUDA')
 _LIB.impl('fill_tracks', _fill_tracks_meta, 'Meta')
 
+
+# ---- motion gate of links (mmmot_amd/association.py; csrc/gate_links.hip) -------------------------------------------
+#   mmmot::gate_links(Tensor packed, Tensor(a!)? link, int[] sizes, float max_size_ratio, float weight) -> Tensor
+#       Links whose two 3D boxes lie too far apart for the elapsed frames become absent edges (NaN), for NB link blocks
+#       in ONE launch (mmmot_gate_links).  packed: ONE device int32 block holding the call's tables in the order of
+#       gate_layout() (the fp64 records and radius tables first, as their bit patterns), so that a call is one upload;
+#       sizes = [L, F, NB, rec_gaps (0: a standing camera, no records), max_dt, mode, n_link].  link: the flat fp32
+#       scores [n_link], gated IN PLACE, or None: count only.  Returns kept int32 [NB] (-1: a block outside the contract).
+GATE_MAX_DT = 64  # MMMOT_GATE_MAX_DT
+GATE_MODES = {'ground': 0, '3d': 1}
+
+
+def gate_layout(sizes):
+    """({section: (offset, int32 count)}, ints) of the packed block of a call with sizes = [L, F, NB, rec_gaps, max_dt,
+    mode, n_link]; the fp64 sections come first (8-byte aligned)."""
+    if len(sizes) != 7 or min(sizes) < 0:
+        raise ValueError('mmmot::gate_links: sizes must be [L, F, NB, rec_gaps, max_dt, mode, n_link], all >= 0, got %s'
+                         % (list(sizes),))
+    L, F, NB, rec_gaps, max_dt, mode, n_link = (int(v) for v in sizes)
+    if not 1 <= max_dt <= GATE_MAX_DT:
+        raise ValueError('mmmot::gate_links: max_dt must be in 1 .. %d, got %d' % (GATE_MAX_DT, max_dt))
+    if mode not in (0, 1):
+        raise ValueError('mmmot::gate_links: mode must be 0 (ground plane) or 1 (3d), got %d' % mode)
+    return _sections_layout('gate_links', [('xf', 2 * FILL_REC * F * rec_gaps), ('r2', 2 * (max_dt + 1)),
+                                           ('inv_r2', 2 * (max_dt + 1)), ('det', 12 * L), ('frame_start', F + 1),
+                                           ('frame_no', F), ('blocks', 4 * NB)])
+
+
+def _gate_links(packed, link, sizes, max_size_ratio, weight):
+    lay, n_in = gate_layout(sizes)
+    if packed.dtype != torch.int32 or packed.dim() != 1 or packed.numel() != n_in or not packed.is_contiguous():
+        raise ValueError('mmmot::gate_links: packed must be a contiguous int32 [%d] block for sizes %s'
+                         % (n_in, list(sizes)))
+    L, F, NB, rec_gaps, max_dt, mode, n_link = (int(v) for v in sizes)
+    if link is not None and (link.dtype != torch.float32 or link.dim() != 1 or link.numel() != n_link
+                             or not link.is_contiguous()):
+        raise ValueError('mmmot::gate_links: link must be a contiguous float32 [%d] tensor' % n_link)
+    kept = torch.zeros(NB, dtype=torch.int32, device=packed.device)
+    i = sections(packed, lay)
+    st = _ops().gate_links(i['det'].view(torch.float32), i['frame_start'], i['frame_no'], i['blocks'],
+                           i['xf'] if rec_gaps else None, i['r2'], i['inv_r2'], link, link, kept, L, F, NB, rec_gaps,
+                           n_link, mode, max_dt, max_size_ratio, weight)
+    from . import _lib
+    _lib.check(st, 'mmmot_gate_links')
+    return kept
+
+
+def _gate_links_meta(packed, link, sizes, max_size_ratio, weight):
+    gate_layout(sizes)
+    return packed.new_empty((int(sizes[2]),), dtype=torch.int32)
+
+
+_LIB.define('gate_links(Tensor packed, Tensor(a!)? link, int[] sizes, float max_size_ratio, float weight) -> Tensor')
+_LIB.impl('gate_links', _gate_links, 'CUDA')
+_LIB.impl('gate_links', _gate_links_meta, 'Meta')
 
 # ---- optimizer step (mmmot_amd/optim.py; csrc/adam_step.hip) --------------------------------------------------------
 #   mmmot::adam_step(Tensor chunks, Tensor ptrs, Tensor scal, float beta1, float beta2, float eps) -> ()

@@ -402,6 +402,19 @@ def fill_weights():
     return w
 
 
+def box_rows(d, m, scores=None):
+    """fp32 [m, 12] rows of a frame's detection dict, the ``det`` layout of mmmot_fill_tracks and mmmot_gate_links: 2D
+    box x1 y1 x2 y2, dimensions lhw -> h w l, location x y z (camera frame), rotation_y, score (0.9 without ``scores``,
+    the constant ``write_kitti_tracks`` writes)"""
+    row = np.empty((m, 12), np.float32)
+    row[:, 0:4] = np.asarray(d['bbox'], dtype=np.float64).reshape(m, 4)
+    row[:, 4:7] = np.asarray(d['dimensions'], dtype=np.float64).reshape(m, 3)[:, [1, 2, 0]]
+    row[:, 7:10] = np.asarray(d['location'], dtype=np.float64).reshape(m, 3)
+    row[:, 10] = np.asarray(d['rotation_y'], dtype=np.float64).reshape(m)
+    row[:, 11] = 0.9 if scores is None else np.asarray(scores, dtype=np.float64).reshape(m)
+    return row
+
+
 def _fill_sequence(seq):
     if isinstance(seq, dict):
         unknown = set(seq) - set(FILL_KEYS)
@@ -447,13 +460,7 @@ def pack_fill(sequences, max_fill=7, capacity=None):
         for t, (d, fid) in enumerate(zip(frames, fids)):
             fid = np.asarray(fid, dtype=np.int64).reshape(-1)
             m = len(fid)
-            row = np.empty((m, 12), np.float32)
-            row[:, 0:4] = np.asarray(d['bbox'], dtype=np.float64).reshape(m, 4)
-            row[:, 4:7] = np.asarray(d['dimensions'], dtype=np.float64).reshape(m, 3)[:, [1, 2, 0]]
-            row[:, 7:10] = np.asarray(d['location'], dtype=np.float64).reshape(m, 3)
-            row[:, 10] = np.asarray(d['rotation_y'], dtype=np.float64).reshape(m)
-            row[:, 11] = 0.9 if scores is None else np.asarray(scores[t], dtype=np.float64).reshape(m)
-            det.append(row)
+            det.append(box_rows(d, m, None if scores is None else scores[t]))
             ids.append(fid)
             counts.append(m)
             for i in fid[fid >= 0]:

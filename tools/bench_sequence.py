@@ -30,12 +30,19 @@ sequences at once and for 21 calls, one per sequence, interleaved, median of --s
 wall time of ``fill_gaps_batch`` (packing, upload, launches, copy, unpacking) and of the NumPy restatement
 tests/fill_ref.py on the same tables, whose rows must equal the device's bit for bit.  Writes
 <out>/bench_sequence_fill.json.
+--gate G measures the motion gate (run_global(max_gap=G, gate=MotionGate(--gate-speed, --gate-slack)), DESIGN section 11
+"motion gate") beside the same call with gate=None on the same feeds, interleaved: wall time of ``run_global``, the gap
+pairs forwarded and left out, the links gated; and the gate's two launches alone on the sequence's own tables (the
+count-only one and the one that gates the flat link scores in place), HIP-event time of the operator call, median of
+--solver-calls calls, with the wall time of the copy that brings the kept counts back.  The synthetic frames hold
+unrelated random boxes, so far more pairs are left out than in a real sequence.  Writes <out>/bench_sequence_gate.json.
 
     python tools/bench_sequence.py --out <dir> [--repeats 3] [--trunk f16x3] [-K 16] [-B 8] [--associate | --track] [--ego]
     python tools/bench_sequence.py --out <dir> --window 3 5 [--repeats 3] [-K 16] [-B 8] [-W 4] [--ego]
     python tools/bench_sequence.py --out <dir> --streams 1 2 4 8 16 [--frames 40] [--repeats 3]
     python tools/bench_sequence.py --out <dir> --global-gap 1 2 3 4 [--frames 100] [--repeats 3] [--solver-calls 20]
     python tools/bench_sequence.py --out <dir> --fill [--fill-frames 8000] [--ego] [--solver-calls 20]
+    python tools/bench_sequence.py --out <dir> --gate 3 [--gate-speed 4.0] [--gate-slack 2.0] [--frames 100] [--ego]
 """
 import argparse
 import json
@@ -239,6 +246,78 @@ def bench_gaps(args, model, dev):
     print(json.dumps(rec))
 
 
+def bench_gate(args, model, dev):
+    """run_global(max_gap=G) with and without a MotionGate, interleaved, and the gate's two launches alone"""
+    from mmmot_amd.association import MotionGate, gap_pairs, pack_gate
+    n, G = args.frames, args.gate
+    if not 2 <= G <= 8 or n <= G:
+        raise SystemExit('--gate takes a gap in 2 .. 8 and needs more frames than that')
+    feeds = sequence_feeds(n, ego=0 if args.ego else None)
+    K, B = args.frames_per_encode, args.pairs_per_forward
+    gate = MotionGate(max_speed=args.gate_speed, slack=args.gate_slack)
+    modes = {'plain': None, 'gated': gate}
+
+    def run(g):
+        pipe = SequencePipeline(model, 224)
+        res = pipe.run_global(feeds, frames_per_encode=K, pairs_per_forward=B, max_gap=G, gate=g)
+        return pipe, res
+
+    stats, tracks = {}, {}
+    for name, g in modes.items():  # untimed
+        pipe, res = run(g)
+        stats[name], tracks[name] = dict(pipe.stats), res.n_tracks
+    wall = {k: [] for k in modes}
+    for _ in range(args.repeats):
+        for name, g in modes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(g)
+            torch.cuda.synchronize()
+            wall[name].append(1e3 * (time.perf_counter() - t0))
+    # the two launches alone, on the tables of this sequence
+    kept_feeds = [f for f in feeds if len(f.dets['bbox'])]
+    p = pack_gate([f.dets for f in kept_feeds], None, [f.pose for f in kept_feeds] if args.ego else None,
+                  feeds[0].info if args.ego else None, gap_pairs(len(kept_feeds), G))
+    packed, sizes = gate.block(p)
+    packed = torch.from_numpy(packed).cuda()
+    link = torch.randn(p['n_link'], device='cuda')
+    calls = {'count_only': lambda: torch.ops.mmmot.gate_links(packed, None, sizes, gate.max_size_ratio, gate.weight),
+             'gate_in_place': lambda: torch.ops.mmmot.gate_links(packed, link, sizes, gate.max_size_ratio, gate.weight)}
+    ms, copy_ms, kept = {k: [] for k in calls}, [], None
+    for i in range(args.solver_calls + 1):  # the first round untimed
+        for name, call in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = call()
+            e1.record()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            kept = out.cpu()
+            if i:
+                ms[name].append(e0.elapsed_time(e1))
+                copy_ms.append(1e3 * (time.perf_counter() - t0))
+    rec = {
+        'run_global_ms': {k: round(float(np.median(v)), 2) for k, v in wall.items()},
+        'run_global_ms_runs': {k: [round(x, 2) for x in v] for k, v in wall.items()},
+        'stats': stats, 'trajectories': tracks,
+        'gap_pairs_forwarded': {k: v.get('gap_pairs', 0) for k, v in stats.items()},
+        'gate_launch_ms': {k: round(float(np.median(v)), 4) for k, v in ms.items()},
+        'gate_launch_ms_min_max': {k: [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()},
+        'kept_copy_wall_ms': round(float(np.median(copy_ms)), 4),
+        'blocks': int(sizes[2]), 'links': int(p['n_link']), 'links_kept': int(kept.sum()),
+        'gate': {'max_speed': gate.max_speed, 'slack': gate.slack, 'max_dt': gate.max_dt, 'mode': gate.mode},
+        'max_gap': G, 'calls': args.solver_calls, 'frames': n, 'repeats': args.repeats, 'frames_per_encode': K,
+        'pairs_per_forward': B, 'ego': bool(args.ego), 'trunk': model.engine().trunk,
+        'device': torch.cuda.get_device_name(dev),
+        'note': 'the synthetic frames hold unrelated random boxes: the share of gap pairs left out is far larger than '
+                'in a sequence whose objects persist',
+    }
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_sequence_gate.json'), 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
 def fill_workload(n_seq, n_frames, p_miss, ego, seed=0):
     """per sequence (frames, ids, None, None, poses, calib): 10 - 12 hidden tracks with linear boxes, every detection
     missed with probability p_miss"""
@@ -341,6 +420,10 @@ def main():
     ap.add_argument('--solver-calls', type=int, default=20)
     ap.add_argument('--fill', action='store_true', help='time the gap filling alone: all sequences at once, one call each, NumPy')
     ap.add_argument('--fill-frames', type=int, default=8000)
+    ap.add_argument('--gate', type=int, default=None,
+                    help='time run_global(max_gap=G) with and without a MotionGate, and the gate launches alone')
+    ap.add_argument('--gate-speed', type=float, default=4.0, help='MotionGate(max_speed=), metres per frame')
+    ap.add_argument('--gate-slack', type=float, default=2.0, help='MotionGate(slack=), metres')
     args = ap.parse_args()
     if args.fill:
         return bench_fill(args)
@@ -359,6 +442,8 @@ def main():
         return bench_streams(args, model, dev)
     if args.global_gap:
         return bench_gaps(args, model, dev)
+    if args.gate:
+        return bench_gate(args, model, dev)
     n = args.frames
     ndet, feeds = detections(n), sequence_feeds(n, ego=0 if args.ego else None)
     K, B = args.frames_per_encode, args.pairs_per_forward
