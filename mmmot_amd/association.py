@@ -44,6 +44,10 @@ may miss up to G - 1 frames instead of ending at the first missed detection:
 
 ``associate_sequence_gaps_batch`` solves B sequences with the same number of gaps in one launch.
 
+The four families share one host path, ``_solve``: the refusals of a batch, the packing table (``_offsets``), one launch
+through ``_launch``, the status check and the walk over every output block (``unpack_gaps``); a single-instance function
+is its own checks and empty-case answer around that path at B = 1.
+
 ``MotionGate`` with ``gate_links`` / ``gate_sequence_links`` (DESIGN.md, "Sequences: motion gate"; csrc/gate_links.hip, one
 launch for any number of link blocks) turns the links no object could have travelled - by the 3D boxes, the frame
 numbers and, with poses, the ego motion - into NaN scores, which every solver above reads as absent edges:
@@ -51,12 +55,157 @@ numbers and, with poses, the ego motion - into NaN scores, which every solver ab
     from mmmot_amd.association import MotionGate, gate_sequence_links
     gated, kept = gate_sequence_links([links_gap1, links_gap2, links_gap3], frames, MotionGate(max_speed=4.0, slack=2.0))
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
 from . import torch_ops  # noqa: F401  (registers mmmot::associate, mmmot::associate_chains, mmmot::associate_sequences[_gap])
 
 
+# ---- what the four families share: the launch seam, the packing offsets, the block walk, the solve path ------------------
+DEVICE = 'cuda'  # where host scores are solved: they go there in one copy and the results come back in one
+
+
+def _launch(op, det, new, end, link, tables, max_gap=None):
+    """Every solver launch of this module: mmmot::``op`` over the four flat fp32 score tensors and the operator's CPU
+    int32 ``tables``, with ``max_gap`` for the operator that takes it."""
+    return getattr(torch.ops.mmmot, op)(det, new, end, link, *tables, *(() if max_gap is None else (max_gap,)))
+
+
+def launch_sequences(scores, tables, max_gap):
+    """The sequence operator for link blocks of the gaps 1 .. ``max_gap``, chosen here and nowhere else:
+    mmmot::associate_sequences for next-frame links alone, else mmmot::associate_sequences_gap.  ``scores``: (det, new,
+    end, link) flat on the device; ``tables``: (seqs, nts) of ``gap_sequences_table``.  -> (out, ids, objective, info)"""
+    if max_gap == 1:
+        return _launch('associate_sequences', *scores, tables)
+    return _launch('associate_sequences_gap', *scores, tables, max_gap)
+
+
+def gap_link_sizes(split, max_gap):
+    """The (n_t, n_{t+g}) of every link block in layout order: all g = 1 blocks in frame order, then all g = 2 blocks,
+    .. up to g = ``max_gap``."""
+    return [(split[t], split[t + g]) for g in range(1, int(max_gap) + 1) for t in range(len(split) - g)]
+
+
+def _offsets(splits, max_gap=1):
+    """The score, link and output offsets of instances packed one after the other, each with the link blocks of the gaps
+    1 .. ``max_gap``: three lists, each closed by its total.  The running sums every table is built on."""
+    sos, los, oos, G = [0], [0], [0], int(max_gap)
+    for split in splits:
+        L, K = sum(split), sum(a * b for g in range(1, G + 1) for a, b in zip(split, split[g:]))
+        sos.append(sos[-1] + L)
+        los.append(los[-1] + K)
+        oos.append(oos[-1] + 3 * L + K)
+    return sos, los, oos
+
+
+def gap_block_size(split, max_gap):
+    return _offsets([split], max_gap)[2][1]
+
+
+def unpack_gaps(block, split, max_gap, like=None, link_sizes=None):
+    """One instance's output block [det L | new L | end L | g = 1 blocks | .. | g = max_gap blocks] -> (det, [[links of
+    gap 1], [links of gap 2], ..], new, end), views of ``block``.  With ``like`` the results take its dtype, det / new /
+    end its size and link (g, t) the size ``link_sizes[g - 1][t]``: one for every block.  The one walk over a block:
+    ``unpack_chain`` and ``unpack`` are its one-gap case."""
+    L, T, ab = sum(split), len(split), gap_link_sizes(split, max_gap)
+    sizes = [L, L, L] + [a * b for a, b in ab]
+    if block.numel() != sum(sizes):
+        block = block[0:sum(sizes)]
+    det, new, end, *flat = block.split_with_sizes(sizes)  # every view in one call
+    if like is None:
+        flat = [l.view(1, a, b) for l, (a, b) in zip(flat, ab)]
+    else:
+        size = like.size()
+        if size != (L,):  # else they have it
+            det, new, end = det.view(size), new.view(size), end.view(size)
+        flat = [l.view(size) for l, size in zip(flat, [size for row in link_sizes for size in row])]
+        if like.dtype != block.dtype:  # the same dtype: .to would hand back the tensor itself
+            det, new, end, *flat = (t.to(like.dtype) for t in (det, new, end, *flat))
+    starts = [0] + [g * T - g * (g + 1) // 2 for g in range(1, int(max_gap) + 1)]  # gap g holds T - g blocks
+    return det, [flat[i:j] for i, j in zip(starts, starts[1:])], new, end
+
+
+def _f32(t):
+    t = t.detach().reshape(-1)
+    return t if t.dtype == torch.float32 else t.to(torch.float32)  # as .to would: the tensor itself
+
+
+# A family of solvers.  ``name`` (of its single-instance function), ``what`` it solves and what every one ``needs`` not
+# to be ``empty`` word the refusals of a batch; ``table(splits, max_gap)`` and ``launch(scores, tables, max_gap)`` are
+# looked up when called; ``ids``: two tables, and IDs and a status word come back too; ``nested``: links nested by gap.
+_Family = namedtuple('_Family', 'name what needs empty table launch ids nested')
+_PAIRS = _Family('associate', 'pair', 'detections in both frames (use associate for empty frames)', lambda s: 0 in s,
+                 lambda splits, G: pairs_table(splits), lambda sc, tb, G: _launch('associate', *sc, tb), False, False)
+_CHAINS = _Family('associate_chain', 'chain', 'a detection (use associate_chain for empty chains)', lambda s: sum(s) == 0,
+                  lambda splits, G: chains_table(splits), lambda sc, tb, G: _launch('associate_chains', *sc, tb), False, False)
+_SEQUENCES = _Family('associate_sequence', 'sequence', 'a detection (use associate_sequence for empty sequences)',
+                     lambda s: sum(s) == 0, lambda splits, G: gap_sequences_table(splits, G), launch_sequences, True, False)
+# associate_sequence_gaps keeps its own convention: the operator with skip links for every G, one gap included
+_GAPS = _SEQUENCES._replace(name='associate_sequence_gaps', needs='a detection (use associate_sequence_gaps for empty sequences)',
+                            launch=lambda sc, tb, G: _launch('associate_sequences_gap', *sc, tb, G), nested=True)
+
+
+def _solve(fam, splits, flats, likes, links, max_gap=1, return_ids=False, single=False):
+    """The one path from checked scores to results: B instances, one launch.  ``flats()``, called behind the refusals of
+    the batch, gives per instance its flat fp32 scores [det | new | end | links], or their four parts in a list; ``likes``
+    / ``links``: per instance the det scores and link blocks whose dtype and sizes the results take; ``single``: the call
+    of a single-instance function, whose scores reach the operator as they are and, if on the host, by way of DEVICE.
+    Returns (per instance (det, links, new, end[, per-frame IDs, track count]), the fp64 optima [B])."""
+    if not splits:
+        raise ValueError('%s_batch: no %ss' % (fam.name, fam.what))
+    if not single and any(fam.empty(s) for s in splits):  # a single-instance function has answered the empty case
+        raise ValueError('%s_batch: every %s needs %s' % (fam.name, fam.what, fam.needs))
+    host = single and not likes[0].is_cuda
+    parts = []
+    for sc, s in zip(flats(), splits):
+        sc = sc.to(DEVICE) if host else sc  # the one host-to-device copy
+        parts.append(sc if isinstance(sc, list) else sc.split_with_sizes([sum(s)] * 3 + [sc.numel() - 3 * sum(s)]))
+    # one sequence, or the instance of a single-instance function, goes as it is; a batch of one pair or chain is joined
+    scores = parts[0] if len(parts) == 1 and (single or fam.ids) else [torch.cat([p[k] for p in parts]) for k in range(4)]
+    if fam.ids:
+        seqs, nts, offs, sos = fam.table(splits, max_gap)
+        out, ids, obj, info = fam.launch(scores, (seqs, nts), max_gap)
+        info = info.cpu().numpy()  # the one status read
+        check_status(info)
+    else:
+        (table, offs), ids = fam.table(splits, max_gap), None
+        out, obj = fam.launch(scores, (table,), max_gap)
+    if host:
+        out, ids = out.cpu(), ids.cpu() if fam.ids else None  # one device-to-host copy each
+    one, res = len(splits) == 1, []
+    blocks = [out] if one else out.split_with_sizes([b - a for a, b in zip(offs, offs[1:] + [out.numel()])])
+    for i, (s, like, l) in enumerate(zip(splits, likes, links)):
+        sizes = [[x.size() for x in row] for row in l] if fam.nested else [[x.size() for x in l]]
+        r = unpack_gaps(blocks[i], s, max_gap, like, sizes)
+        r = r if fam.nested else (r[0], r[1][0], r[2], r[3])
+        if return_ids:
+            r += (split_ids(ids if one else ids[sos[i]:sos[i] + sum(s)], s), int(info[i, 1]))
+        res.append(r)
+    return res, obj
+
+
+def _batch_flats(check, flatten, det_scores, link_scores, new_scores, end_scores, splits, gts):
+    """the ``flats`` of a batch: per instance its scores, checked and flattened when ``_solve`` calls for them"""
+    def flats():
+        out, gt = [], gts if gts is not None else [None] * len(splits)
+        for d, l, n, e, s, g in zip(det_scores, link_scores, new_scores, end_scores, splits, gt):
+            check(d, l, n, e, s)
+            out.append(flatten(d, l, n, e, g))
+        return out
+    return flats
+
+
+def _empty(det_score, link_scores, split=None):
+    """no detection: zeros in the shapes of the scores and, with ``split``, no IDs per frame and no track; no launch"""
+    zeros = lambda l: [zeros(x) for x in l] if isinstance(l, (list, tuple)) else det_score.new_zeros(l.size())
+    z = zeros(det_score)
+    ids = () if split is None else ([torch.zeros(0, dtype=torch.int64, device=det_score.device) for _ in split], 0)
+    return (z, zeros(link_scores), z.clone(), z.clone()) + ids
+
+
+# ---- frame pairs ----------------------------------------------------------------------------------------------------------
 def split_of(det_split):
     """(N, M) of a two-frame ``det_split`` (ints or 1-element tensors, as eval_seq passes them)."""
     if len(det_split) != 2:
@@ -74,14 +223,8 @@ def select(det_score, link_scores, new_score, end_score, test_mode):
 
 def pairs_table(splits):
     """CPU int32 [B, 4] (N, M, score offset, link offset) of pairs packed one after the other, and the output offsets."""
-    rows, so, lo, oo, offs = [], 0, 0, 0, []
-    for N, M in splits:
-        rows.append((N, M, so, lo))
-        offs.append(oo)
-        so += N + M
-        lo += N * M
-        oo += 3 * (N + M) + N * M
-    return torch.tensor(rows, dtype=torch.int32), offs
+    sos, los, oos = _offsets(splits)
+    return torch.tensor([(N, M, so, lo) for (N, M), so, lo in zip(splits, sos, los)], dtype=torch.int32), oos[:-1]
 
 
 def unpack(block, N, M, like=None, link_size=None):
@@ -110,37 +253,18 @@ def associate(det_score, link_score, new_score, end_score, det_split, gt=None):
         raise ValueError('associate: scores do not match det_split [%d, %d]' % (N, M))
     if N == 0 or M == 0:
         return _host_unmatched(det_score, link, new_score, end_score, N, M)
-    parts = [t.detach().reshape(-1).to(torch.float32) for t in (det_score, new_score, end_score, link)]
-    on_host = not det_score.is_cuda
-    if on_host:
-        flat = torch.cat(parts).to('cuda')  # one host-to-device copy
-        parts = [flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:]]
-    else:
-        parts = [p.contiguous() for p in parts]
-    pairs, _ = pairs_table([(N, M)])
-    out, _ = torch.ops.mmmot.associate(parts[0], parts[1], parts[2], parts[3], pairs)
-    if on_host:
-        out = out.cpu()  # one device-to-host copy
-    return unpack(out, N, M, det_score, link.size())
+    parts = [_f32(t) for t in (det_score, new_score, end_score, link)]
+    # device scores go to the operator as they are; host scores travel as one tensor
+    scores = [p.contiguous() for p in parts] if det_score.is_cuda else torch.cat(parts)
+    return _solve(_PAIRS, [(N, M)], lambda: [scores], [det_score], [link_score], single=True)[0][0]
 
 
 def associate_batch(det_scores, link_scores, new_scores, end_scores, det_splits, return_objective=False):
     """B frame pairs in one launch.  Per pair p: det_scores[p] / new_scores[p] / end_scores[p] [L_p],
     link_scores[p] = [link 1 x N_p x M_p] (the ``select`` rows of a ``forward_batch`` result), all on one device.
     Returns the list of ortools_solve tuples (on that device), and the fp64 optima [B] when ``return_objective``."""
-    splits = [split_of(s) for s in det_splits]
-    if not splits:
-        raise ValueError('associate_batch: no pairs')
-    if any(N == 0 or M == 0 for N, M in splits):
-        raise ValueError('associate_batch: every pair needs detections in both frames (use associate for empty frames)')
-    cat = lambda ts: torch.cat([t.detach().reshape(-1).to(torch.float32) for t in ts])
-    det, new, end = cat(det_scores), cat(new_scores), cat(end_scores)
-    link = cat([l[0] for l in link_scores])
-    pairs, offs = pairs_table(splits)
-    out, obj = torch.ops.mmmot.associate(det, new, end, link, pairs)
-    res = []
-    for (N, M), o, d, l in zip(splits, offs, det_scores, link_scores):
-        res.append(unpack(out[o:o + 3 * (N + M) + N * M], N, M, d, l[0].size()))
+    flats = lambda: [[_f32(t) for t in (d, n, e, l[0])] for d, l, n, e in zip(det_scores, link_scores, new_scores, end_scores)]
+    res, obj = _solve(_PAIRS, [split_of(s) for s in det_splits], flats, det_scores, link_scores)
     return (res, obj) if return_objective else res
 
 
@@ -163,35 +287,22 @@ def select_chain(det_score, link_scores, new_score, end_score, test_mode):
 def chains_table(splits):
     """CPU int32 [B, 11] (T, score offset, link offset, n_0 .. n_7) of chains packed one after the other, and the
     output offsets."""
-    rows, so, lo, oo, offs = [], 0, 0, 0, []
     for split in splits:
         if len(split) > torch_ops.CHAIN_MAX_T:
             raise ValueError('associate_chain: at most %d frames, got %d' % (torch_ops.CHAIN_MAX_T, len(split)))
-        K = sum(a * b for a, b in zip(split[:-1], split[1:]))
-        rows.append([len(split), so, lo] + list(split) + [0] * (torch_ops.CHAIN_MAX_T - len(split)))
-        offs.append(oo)
-        so += sum(split)
-        lo += K
-        oo += 3 * sum(split) + K
-    return torch.tensor(rows, dtype=torch.int32), offs
+    sos, los, oos = _offsets(splits)
+    rows = [[len(s), so, lo] + list(s) + [0] * (torch_ops.CHAIN_MAX_T - len(s)) for s, so, lo in zip(splits, sos, los)]
+    return torch.tensor(rows, dtype=torch.int32), oos[:-1]
 
 
 def chain_block_size(split):
-    return 3 * sum(split) + sum(a * b for a, b in zip(split[:-1], split[1:]))
+    return gap_block_size(split, 1)
 
 
 def unpack_chain(block, split, like=None, link_sizes=None):
     """One chain's output block [det L | new L | end L | link_0 | .. | link_{T-2}] -> the ortools_solve tuple (views)."""
-    L = sum(split)
-    det, new, end = block[0:L], block[L:2 * L], block[2 * L:3 * L]
-    links, o = [], 3 * L
-    for a, b in zip(split[:-1], split[1:]):
-        links.append(block[o:o + a * b].view(1, a, b))
-        o += a * b
-    if like is not None:
-        det, new, end = (t.view(like.size()).to(like.dtype) for t in (det, new, end))
-        links = [l.view(sz).to(like.dtype) for l, sz in zip(links, link_sizes)]
-    return det, links, new, end
+    det, links, new, end = unpack_gaps(block, split, 1, like, [link_sizes])
+    return det, links[0], new, end
 
 
 def _check_chain(det_score, link_scores, new_score, end_score, split):
@@ -205,10 +316,10 @@ def _flat_scores(det_score, link_scores, new_score, end_score, gt):
     """[det | new | end | link_0 | ..] fp32 on the scores' device; with ``gt`` the loss-augmented scores of
     solvers.py:50-81: the objective gains gt - y * gt_eff per variable, gt_eff = gt + (gt == 0) * -1, so every score
     drops by gt_eff (the constant sum of gt does not move the arg-max) - one fused expression."""
-    flat = torch.cat([t.detach().reshape(-1).to(torch.float32) for t in (det_score, new_score, end_score, *link_scores)])
+    flat = torch.cat([_f32(t) for t in (det_score, new_score, end_score, *link_scores)])
     if gt is None:
         return flat
-    g = torch.cat([t.detach().reshape(-1).to(torch.float32) for t in (gt[0], gt[1], gt[2], *gt[3])]).to(flat.device)
+    g = torch.cat([_f32(t) for t in (gt[0], gt[1], gt[2], *gt[3])]).to(flat.device)
     if g.numel() != flat.numel():
         raise ValueError('associate_chain: gt does not match the scores')
     return flat - (g + g.eq(0).float().mul(-1))
@@ -221,19 +332,10 @@ def associate_chain(det_score, link_scores, new_score, end_score, det_split, gt=
     assign_end) with the dtype, device and shapes of the scores."""
     split = chain_of(det_split)
     _check_chain(det_score, link_scores, new_score, end_score, split)
-    L = sum(split)
-    if L == 0:
-        z = det_score.new_zeros(det_score.size())
-        return z, [det_score.new_zeros(l.size()) for l in link_scores], z.clone(), z.clone()
+    if sum(split) == 0:
+        return _empty(det_score, link_scores)
     flat = _flat_scores(det_score, link_scores, new_score, end_score, gt)
-    on_host = not det_score.is_cuda
-    if on_host:
-        flat = flat.to('cuda')  # one host-to-device copy
-    chains, _ = chains_table([split])
-    out, _ = torch.ops.mmmot.associate_chains(flat[0:L], flat[L:2 * L], flat[2 * L:3 * L], flat[3 * L:], chains)
-    if on_host:
-        out = out.cpu()  # one device-to-host copy
-    return unpack_chain(out, split, det_score, [l.size() for l in link_scores])
+    return _solve(_CHAINS, [split], lambda: [flat], [det_score], [link_scores], single=True)[0][0]
 
 
 def associate_chain_batch(det_scores, link_scores, new_scores, end_scores, det_splits, gts=None,
@@ -243,22 +345,8 @@ def associate_chain_batch(det_scores, link_scores, new_scores, end_scores, det_s
     None).  Returns the list of ortools_solve tuples (on that device), and the fp64 optima [B] of the solved scores when
     ``return_objective``."""
     splits = [chain_of(s) for s in det_splits]
-    if not splits:
-        raise ValueError('associate_chain_batch: no chains')
-    if any(sum(s) == 0 for s in splits):
-        raise ValueError('associate_chain_batch: every chain needs a detection (use associate_chain for empty chains)')
-    gts = gts if gts is not None else [None] * len(splits)
-    flats = []
-    for d, l, n, e, s, g in zip(det_scores, link_scores, new_scores, end_scores, splits, gts):
-        _check_chain(d, l, n, e, s)
-        flats.append(_flat_scores(d, l, n, e, g))
-    Ls = [sum(s) for s in splits]
-    cat = lambda k: torch.cat([f[k * L:(k + 1) * L] for f, L in zip(flats, Ls)])
-    link = torch.cat([f[3 * L:] for f, L in zip(flats, Ls)])
-    chains, offs = chains_table(splits)
-    out, obj = torch.ops.mmmot.associate_chains(cat(0), cat(1), cat(2), link, chains)
-    res = [unpack_chain(out[o:o + chain_block_size(s)], s, d, [x.size() for x in l])
-           for s, o, d, l in zip(splits, offs, det_scores, link_scores)]
+    flats = _batch_flats(_check_chain, _flat_scores, det_scores, link_scores, new_scores, end_scores, splits, gts)
+    res, obj = _solve(_CHAINS, splits, flats, det_scores, link_scores)
     return (res, obj) if return_objective else res
 
 
@@ -297,34 +385,20 @@ def sequences_table(splits):
     return gap_sequences_table(splits, 1)
 
 
-def _raise_status(info):
+def check_status(info):
     """``info``: host int32 [B, 4]; raises AssociationError for the first sequence whose status word is set"""
     bad = np.nonzero(info[:, 0])[0]
     if bad.size:
         raise AssociationError(int(bad[0]), int(info[bad[0], 0]))
 
 
+_raise_status = check_status
+
+
 def split_ids(ids, split):
     """flat per-detection IDs -> per frame an int64 array (views of one int64 copy)"""
     ids = ids.to(torch.int64)
     return list(ids.split(split))
-
-
-def _solve_sequences(flats, splits, max_gap):
-    """One launch over the sequences' flat device scores ([det | new | end | links] each, ``_flat_scores``): ``max_gap``
-    = 0 is mmmot::associate_sequences (next-frame links), else mmmot::associate_sequences_gap.  Returns (out, ids,
-    objective, host info [B, 4], output offsets, score offsets); raises AssociationError for a status word."""
-    seqs, nts, offs, sos = gap_sequences_table(splits, max(max_gap, 1))
-    cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts)
-    det, new, end = (cat([f[k * sum(s):(k + 1) * sum(s)] for f, s in zip(flats, splits)]) for k in range(3))
-    link = cat([f[3 * sum(s):] for f, s in zip(flats, splits)])
-    if max_gap:
-        out, ids, obj, info = torch.ops.mmmot.associate_sequences_gap(det, new, end, link, seqs, nts, max_gap)
-    else:
-        out, ids, obj, info = torch.ops.mmmot.associate_sequences(det, new, end, link, seqs, nts)
-    info = info.cpu().numpy()
-    _raise_status(info)
-    return out, ids, obj, info, offs, sos
 
 
 def associate_sequence(det_score, link_scores, new_score, end_score, det_split, gt=None, return_ids=False):
@@ -335,21 +409,10 @@ def associate_sequence(det_score, link_scores, new_score, end_score, det_split, 
     AssociationError when the solver reports a status (one host read of four words per call)."""
     split = sequence_of(det_split)
     _check_chain(det_score, link_scores, new_score, end_score, split)
-    L = sum(split)
-    if L == 0:
-        z = det_score.new_zeros(det_score.size())
-        res = (z, [det_score.new_zeros(l.size()) for l in link_scores], z.clone(), z.clone())
-        empty = [torch.zeros(0, dtype=torch.int64, device=det_score.device) for _ in split]
-        return res + (empty, 0) if return_ids else res
+    if sum(split) == 0:
+        return _empty(det_score, link_scores, split if return_ids else None)
     flat = _flat_scores(det_score, link_scores, new_score, end_score, gt)
-    on_host = not det_score.is_cuda
-    if on_host:
-        flat = flat.to('cuda')  # one host-to-device copy
-    out, ids, _, info, _, _ = _solve_sequences([flat], [split], 0)
-    if on_host:
-        out, ids = out.cpu(), ids.cpu()
-    res = unpack_chain(out, split, det_score, [l.size() for l in link_scores])
-    return res + (split_ids(ids, split), int(info[0, 1])) if return_ids else res
+    return _solve(_SEQUENCES, [split], lambda: [flat], [det_score], [link_scores], 1, return_ids, single=True)[0][0]
 
 
 def associate_sequence_batch(det_scores, link_scores, new_scores, end_scores, det_splits, gts=None,
@@ -359,21 +422,8 @@ def associate_sequence_batch(det_scores, link_scores, new_scores, end_scores, de
     (or None).  Returns the list of ortools_solve tuples (on that device) - each followed by its per-frame IDs and its
     trajectory count with ``return_ids`` - and the fp64 optima [B] when ``return_objective``."""
     splits = [sequence_of(s) for s in det_splits]
-    if not splits:
-        raise ValueError('associate_sequence_batch: no sequences')
-    if any(sum(s) == 0 for s in splits):
-        raise ValueError('associate_sequence_batch: every sequence needs a detection (use associate_sequence for empty '
-                         'sequences)')
-    gts = gts if gts is not None else [None] * len(splits)
-    flats = []
-    for d, l, n, e, s, g in zip(det_scores, link_scores, new_scores, end_scores, splits, gts):
-        _check_chain(d, l, n, e, s)
-        flats.append(_flat_scores(d, l, n, e, g))
-    out, ids, obj, info, offs, sos = _solve_sequences(flats, splits, 0)
-    res = []
-    for i, (s, o, so, d, l) in enumerate(zip(splits, offs, sos, det_scores, link_scores)):
-        r = unpack_chain(out[o:o + chain_block_size(s)], s, d, [x.size() for x in l])
-        res.append(r + (split_ids(ids[so:so + sum(s)], s), int(info[i, 1])) if return_ids else r)
+    flats = _batch_flats(_check_chain, _flat_scores, det_scores, link_scores, new_scores, end_scores, splits, gts)
+    res, obj = _solve(_SEQUENCES, splits, flats, det_scores, link_scores, 1, return_ids)
     return (res, obj) if return_objective else res
 
 
@@ -381,51 +431,17 @@ def associate_sequence_batch(det_scores, link_scores, new_scores, end_scores, de
 SEQ_MAX_GAP = torch_ops.SEQ_MAX_GAP
 
 
-def gap_link_sizes(split, max_gap):
-    """The (n_t, n_{t+g}) of every link block in layout order: all g = 1 blocks in frame order, then all g = 2 blocks,
-    .. up to g = ``max_gap``."""
-    return [(split[t], split[t + g]) for g in range(1, int(max_gap) + 1) for t in range(len(split) - g)]
-
-
-def gap_block_size(split, max_gap):
-    return 3 * sum(split) + sum(a * b for a, b in gap_link_sizes(split, max_gap))
-
-
 def gap_sequences_table(splits, max_gap):
     """(seqs CPU int32 [B, 4] = (T, score offset, link offset, offset of n_0 in nts), nts CPU int32 flat, output
     offsets, score offsets) of sequences packed one after the other, with link blocks of every gap 1 .. ``max_gap``."""
-    rows, nts, so, lo, oo, offs, sos = [], [], 0, 0, 0, [], []
-    for split in splits:
-        K = sum(a * b for a, b in gap_link_sizes(split, max_gap))
+    sos, los, oos = _offsets(splits, max_gap)
+    if los[-1] >= 2 ** 31 - 1 or oos[-1] >= 2 ** 31 - 1:
+        raise ValueError('associate_sequence_gaps: the link scores of one launch must number fewer than 2^31')
+    rows, nts = [], []
+    for split, so, lo in zip(splits, sos, los):
         rows.append([len(split), so, lo, len(nts)])
         nts.extend(split)
-        offs.append(oo)
-        sos.append(so)
-        so += sum(split)
-        lo += K
-        oo += 3 * sum(split) + K
-    if lo >= 2 ** 31 - 1 or oo >= 2 ** 31 - 1:
-        raise ValueError('associate_sequence_gaps: the link scores of one launch must number fewer than 2^31')
-    return torch.tensor(rows, dtype=torch.int32), torch.tensor(nts, dtype=torch.int32), offs, sos
-
-
-def unpack_gaps(block, split, max_gap, like=None, link_sizes=None):
-    """One sequence's output block [det L | new L | end L | g = 1 blocks | .. | g = max_gap blocks] -> (det, [[links of
-    gap 1], [links of gap 2], ..], new, end), views of ``block``; ``link_sizes``: the nested sizes the links take."""
-    L, T = sum(split), len(split)
-    det, new, end = block[0:L], block[L:2 * L], block[2 * L:3 * L]
-    links, o = [], 3 * L
-    for g in range(1, int(max_gap) + 1):
-        row = []
-        for t in range(T - g):
-            a, b = split[t], split[t + g]
-            row.append(block[o:o + a * b].view(1, a, b))
-            o += a * b
-        links.append(row)
-    if like is not None:
-        det, new, end = (t.view(like.size()).to(like.dtype) for t in (det, new, end))
-        links = [[l.view(sz).to(like.dtype) for l, sz in zip(row, szs)] for row, szs in zip(links, link_sizes)]
-    return det, links, new, end
+    return torch.tensor(rows, dtype=torch.int32), torch.tensor(nts, dtype=torch.int32), oos[:-1], sos[:-1]
 
 
 def _check_gaps(det_score, link_scores, new_score, end_score, split):
@@ -466,22 +482,10 @@ def associate_sequence_gaps(det_score, link_scores, new_score, end_score, det_sp
     with a ValueError, scores that do not match; raises AssociationError when the solver reports a status."""
     split = sequence_of(det_split)
     G = _check_gaps(det_score, link_scores, new_score, end_score, split)
-    L = sum(split)
-    sizes = [[l.size() for l in row] for row in link_scores]
-    if L == 0:
-        z = det_score.new_zeros(det_score.size())
-        res = (z, [[det_score.new_zeros(sz) for sz in row] for row in sizes], z.clone(), z.clone())
-        empty = [torch.zeros(0, dtype=torch.int64, device=det_score.device) for _ in split]
-        return res + (empty, 0) if return_ids else res
+    if sum(split) == 0:
+        return _empty(det_score, link_scores, split if return_ids else None)
     flat = _flat_gaps(det_score, link_scores, new_score, end_score, gt)
-    on_host = not det_score.is_cuda
-    if on_host:
-        flat = flat.to('cuda')  # one host-to-device copy
-    out, ids, _, info, _, _ = _solve_sequences([flat], [split], G)
-    if on_host:
-        out, ids = out.cpu(), ids.cpu()
-    res = unpack_gaps(out, split, G, det_score, sizes)
-    return res + (split_ids(ids, split), int(info[0, 1])) if return_ids else res
+    return _solve(_GAPS, [split], lambda: [flat], [det_score], [link_scores], G, return_ids, single=True)[0][0]
 
 
 def associate_sequence_gaps_batch(det_scores, link_scores, new_scores, end_scores, det_splits, gts=None,
@@ -490,22 +494,13 @@ def associate_sequence_gaps_batch(det_scores, link_scores, new_scores, end_score
     ``associate_sequence_gaps``, all on one device.  Returns what ``associate_sequence_batch`` returns, the links nested
     by gap."""
     splits = [sequence_of(s) for s in det_splits]
-    if not splits:
-        raise ValueError('associate_sequence_gaps_batch: no sequences')
-    if any(sum(s) == 0 for s in splits):
-        raise ValueError('associate_sequence_gaps_batch: every sequence needs a detection (use associate_sequence_gaps '
-                         'for empty sequences)')
-    gts = gts if gts is not None else [None] * len(splits)
-    flats, G = [], len(link_scores[0])
-    for d, l, n, e, s, g in zip(det_scores, link_scores, new_scores, end_scores, splits, gts):
+    G = len(link_scores[0]) if len(link_scores) else 0  # no link blocks: the refusals of the batch come first
+
+    def check(d, l, n, e, s):
         if _check_gaps(d, l, n, e, s) != G:
             raise ValueError('associate_sequence_gaps_batch: every sequence needs the blocks of the same %d gaps' % G)
-        flats.append(_flat_gaps(d, l, n, e, g))
-    out, ids, obj, info, offs, sos = _solve_sequences(flats, splits, G)
-    res = []
-    for i, (s, o, so, d, l) in enumerate(zip(splits, offs, sos, det_scores, link_scores)):
-        r = unpack_gaps(out[o:o + gap_block_size(s, G)], s, G, d, [[x.size() for x in row] for row in l])
-        res.append(r + (split_ids(ids[so:so + sum(s)], s), int(info[i, 1])) if return_ids else r)
+    flats = _batch_flats(check, _flat_gaps, det_scores, link_scores, new_scores, end_scores, splits, gts)
+    res, obj = _solve(_GAPS, splits, flats, det_scores, link_scores, G, return_ids)
     return (res, obj) if return_objective else res
 
 
@@ -657,7 +652,7 @@ def gate_links(link_blocks, frames, gate, frame_idx=None, poses=None, calib=None
     on_host = not link_blocks[0].is_cuda
     flat = torch.cat([l.detach().reshape(-1).to(torch.float32) for l in link_blocks] + [link_blocks[0].new_zeros(0, dtype=torch.float32)])
     if on_host:
-        flat = flat.to('cuda')
+        flat = flat.to(DEVICE)
     kept = queue_gate(p, gate, flat, flat.device)
     if on_host:
         flat = flat.cpu()

@@ -88,8 +88,8 @@ import torch
 from .crops import crop_resize_u8, crop_resize_u8_multi
 from . import ego
 from .points import align_points_batched, prep_points_batched
-from .association import (MotionGate, _raise_status, check_kept, gap_pairs, gap_sequences_table, pack_gate, queue_gate,
-                          select, select_chain, unpack_gaps)
+from .association import (MotionGate, check_kept, check_status, gap_pairs, gap_sequences_table, launch_sequences,
+                          pack_gate, queue_gate, select, select_chain, unpack_gaps)
 from .tracker_glue import queue_scores, queue_solve, queue_solve_chains
 from .torch_ops import FILL_MAX, SEQ_MAX_GAP
 from .tracks import TrackState, TrackStates, fill_gaps, merge_chain_tracks, merge_tracks, window_starts
@@ -721,9 +721,9 @@ def assemble_rows(rows, counts):
 
 
 def solve_global(rows, counts, gap_links=(), max_gap=1, gate=None):
-    """assemble, one ``associate_sequences`` launch, one copy; raises association.AssociationError on a status word.
-    ``max_gap`` > 1: ``gap_links`` = the flat link blocks of the gaps 2 .. max_gap in layout order, joined behind the
-    adjacent pairs' blocks, and the launch is ``associate_sequences_gap``.  ``gate`` = (``pack_gate`` tables of the
+    """assemble, one ``association.launch_sequences`` launch, one copy; raises association.AssociationError on a status
+    word.  ``max_gap`` > 1: ``gap_links`` = the flat link blocks of the gaps 2 .. max_gap in layout order, joined behind
+    the adjacent pairs' blocks, and the launch is the one with skip links.  ``gate`` = (``pack_gate`` tables of the
     blocks in layout order, MotionGate): one mmmot_gate_links launch gates the assembled link scores in place in front
     of the solve, and the kept counts come back in the same copy (``GlobalResult.gate_kept``)."""
     split = [int(c) for c in counts]
@@ -739,10 +739,7 @@ def solve_global(rows, counts, gap_links=(), max_gap=1, gate=None):
             raise ValueError('solve_global: the gate tables hold %d links, the scores %d' % (gate[0]['n_link'], scores[3].numel()))
         kept = queue_gate(gate[0], gate[1], scores[3], flat.device)
     seqs, nts, _, _ = gap_sequences_table([split], max_gap)
-    if max_gap == 1:
-        out, ids, obj, info = torch.ops.mmmot.associate_sequences(*scores, seqs, nts)
-    else:
-        out, ids, obj, info = torch.ops.mmmot.associate_sequences_gap(*scores, seqs, nts, max_gap)
+    out, ids, obj, info = launch_sequences(scores, (seqs, nts), max_gap)
     # the fp64 objective first: every part then starts at a multiple of its element size, whatever L and the link count
     parts = [obj, flat, out, ids, info.reshape(-1)] + ([kept] if kept is not None else [])
     host = torch.cat([x.view(torch.uint8) for x in parts]).cpu()  # the one copy
@@ -753,7 +750,7 @@ def solve_global(rows, counts, gap_links=(), max_gap=1, gate=None):
     if kept is not None:
         kept = check_kept(got.pop().numpy(), gate[0])
     got = got[1:] + got[:1]  # flat, out, ids, info, objective
-    _raise_status(got[3].view(1, 4).numpy())
+    check_status(got[3].view(1, 4).numpy())
     like = got[0][0:L]
     tail = ([i.numpy() for i in got[2].to(torch.int64).split(split)], int(got[3][1]), float(got[4][0]), split)
     sizes = [[(1, split[t], split[t + g]) for t in range(len(split) - g)] for g in range(1, max_gap + 1)]

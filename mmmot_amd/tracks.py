@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import torch_ops
-from .association import chain_of, chains_table, pairs_table, split_of
+from .association import chain_block_size, chain_of, chains_table, pairs_table, split_of
 from .torch_ops import TRACK_STATE_HEAD, TRACK_STATE_INTS
 
 EINFEASIBLE, ECONTRACT = 1, 2
@@ -287,7 +287,7 @@ def _queue_multi(op, table_of, frames_of, states, blocks, splits, frame_idx, str
         raise ValueError('%s: %d stream names for %d groups' % (op, len(stream_of), len(splits)))
     order, seq_start = stream_major(stream_of, len(states))
     splits = [splits[g] for g in order]
-    sizes = np.asarray([3 * sum(s) + sum(a * b for a, b in zip(s[:-1], s[1:])) for s in splits], dtype=np.int64)
+    sizes = np.asarray([chain_block_size(s) for s in splits], dtype=np.int64)
     inv = np.argsort(order)  # the blocks lie in the order given: block g goes to place inv[g]
     blocks = _reorder_blocks(blocks, sizes[inv], order)
     ids = getattr(torch.ops.mmmot, op)(blocks, table_of(splits)[0], frames_of([frame_idx[g] for g in order], splits),
