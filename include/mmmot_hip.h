@@ -566,6 +566,36 @@ int mmmot_fill_tracks(const float* det, const int* ids, const int* frame_start, 
                       void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Smoothing of tracked sequences (csrc/smooth_tracks.hip; DESIGN section 12b, which states the order of every
+ * operation), additive in ABI 10: a Kalman filter forwards and a Rauch-Tung-Striebel pass backwards along every track,
+ * for S sequences in five launches whatever the number of rows, frames, sequences and tracks.
+ *   det, ids, frame_start, frame_no, seq_start: the tables of mmmot_fill_tracks
+ *   observed    [L] or NULL (every row observed): a row with observed == 0 carries no measurement
+ *   xf0         [F][MMMOT_FILL_REC] fp64, or NULL for a standing camera: the record of listed frame p is C[a<-p] | its
+ *               inverse | dyaw[a<-p] in the layout of mmmot_fill_tracks, a the first listed frame of p's sequence
+ *   q_, r_, v0_ process noise (white acceleration; h w l: a random walk), measurement variance and initial velocity
+ *               variance of the location (x y z), the yaw and the dimensions (h w l), per frame number
+ *   yaw_flip    1: an unwrapped yaw step beyond pi/2 is taken as the detector's front / back confusion (pi is added)
+ *   work        [MMMOT_SMOOTH_WORK(L)] ints of scratch, 8-byte aligned
+ *   out         [L][12] fp32: the rows of det with h w l, x y z and rotation_y smoothed; the 2D box and the score copied
+ *   out_vel     [L][4] fp32 or NULL: vx, vy, vz (the row's own frame's axes) and the yaw rate per frame number
+ *   info        [S][4] out: status, chains smoothed, rows changed, rows copied
+ * A track is the rows of one sequence with the same ID >= 0; its chain starts at its first observed row and holds every
+ * later row (unobserved rows are predictions).  Rows with ID < 0, rows in front of a chain, chains of one row and every
+ * channel group whose r is 0 are copied bit for bit, with velocity 0.  Status, per sequence, never a fault:
+ * MMMOT_FILL_EDUP / MMMOT_FILL_ECONTRACT as for mmmot_fill_tracks - the sequence's rows are copied, info = status, 0, 0,
+ * its rows; a frame_start / seq_start that breaks its shape gives every sequence ECONTRACT, all rows copied, counters 0.
+ * Returns MMMOT_EINVAL before any launch for S < 1, a negative L / F, a negative, NaN or infinite parameter, v0 <= 0 for
+ * a group with r > 0, yaw_flip outside {0, 1} and, with L > 0 and F > 0, a null pointer (observed, xf0 and out_vel may
+ * be null), a work that is not 8-byte aligned or MMMOT_SMOOTH_WORK(L) >= 2^31.  L = 0 or F = 0 is a no-op that returns
+ * 0.  No allocation, no synchronisation.  The launches go to `hip_stream`, as for mmmot_gate_links. */
+#define MMMOT_SMOOTH_WORK(L) (75 * (long)(L) + 2)
+int mmmot_smooth_tracks(const float* det, const int* ids, const int* frame_start, const int* frame_no,
+                        const int* seq_start, const int* observed, const double* xf0, int L, int F, int S, double q_loc,
+                        double r_loc, double v0_loc, double q_yaw, double r_yaw, double v0_yaw, double q_dim,
+                        double r_dim, int yaw_flip, int* work, float* out, float* out_vel, int* info, void* hip_stream);
+
+/* ---------------------------------------------------------------------------
  * Motion gate of links (csrc/gate_links.hip; DESIGN section 11, "Sequences: motion gate"), additive in ABI 10: a link
  * whose two 3D boxes lie further apart than an object travels in the elapsed frames is written as a quiet NaN, which
  * mmmot_associate, the chain entries and the sequence entries read as an absent edge.  ONE launch whatever NB, F and

@@ -13,6 +13,7 @@
 // arithmetic is fp64 with every product and sum rounded on its own and one rounding to fp32 at the store, as in
 // csrc/align_points.hip: plain operators under `#pragma clang fp contract(off)`.
 #include "common.h"
+#include "track_links.h"  // ft_last_le, ft_check_entry, ft_dup_in_frame, ft_successor: shared with smooth_tracks.hip
 
 #define FT_THREADS 256
 #define FT_SCAN_THREADS 1024
@@ -20,36 +21,11 @@
 #define FT_PI 3.141592653589793
 #define FT_TWO_PI 6.283185307179586
 
-// last t in [0, n) with tab[t] <= v (t = 0 when there is none): the frame of a detection, the sequence of a frame.  Empty
-// frames / sequences share their start with the next one and are skipped.  Stays inside [0, n) whatever the table holds.
-__device__ __forceinline__ int ft_last_le(const int* __restrict__ tab, int n, int v) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid] <= v) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(FT_THREADS) void ft_check_kernel(const int* __restrict__ frame_start,
                                                               const int* __restrict__ frame_no,
                                                               const int* __restrict__ seq_start, int L, int F, int S,
                                                               int* __restrict__ work, int* __restrict__ info) {
-  const int i = blockIdx.x * FT_THREADS + threadIdx.x;
-  bool bad = false;
-  if (i < S) {
-    const int a = seq_start[i], b = seq_start[i + 1];
-    bad = a < 0 || a > b || b > F || (i == 0 && a != 0) || (i == S - 1 && b != F);
-  }
-  if (i < F) {
-    const int a = frame_start[i], b = frame_start[i + 1];
-    bad = bad || a < 0 || a > b || b > L || (i == 0 && a != 0) || (i == F - 1 && b != L);
-  }
-  if (bad) atomicOr(work, 1);
-  if (i + 1 < F && frame_no[i] >= frame_no[i + 1]) {
-    const int s = ft_last_le(seq_start, S, i);
-    if (i + 1 < seq_start[s + 1]) atomicOr(&info[4 * s], MMMOT_FILL_ECONTRACT);
-  }
+  ft_check_entry(blockIdx.x * FT_THREADS + threadIdx.x, frame_start, frame_no, seq_start, L, F, S, work, info);
 }
 
 __global__ __launch_bounds__(FT_THREADS) void ft_succ_kernel(const int* __restrict__ ids,
@@ -65,17 +41,9 @@ __global__ __launch_bounds__(FT_THREADS) void ft_succ_kernel(const int* __restri
   const int id = ids[i];
   int sj = -1, sf = -1;
   if (id >= 0) {
-    bool dup = false;
-    for (int c = frame_start[pa]; c < frame_start[pa + 1]; ++c) dup = dup || (c != i && ids[c] == id);
-    if (dup) atomicOr(&info[4 * s], MMMOT_FILL_EDUP);
-    const int e = seq_start[s + 1];
+    if (ft_dup_in_frame(ids, frame_start, pa, i, id)) atomicOr(&info[4 * s], MMMOT_FILL_EDUP);
     int pb = -1;
-    for (int q = pa + 1; q < e && sj < 0; ++q)
-      for (int c = frame_start[q]; c < frame_start[q + 1]; ++c)
-        if (ids[c] == id) {
-          sj = c, pb = q;
-          break;
-        }
+    sj = ft_successor(ids, frame_start, pa, seq_start[s + 1], id, pb);
     if (sj >= 0) {
       const long long n = (long long)frame_no[pb] - (long long)frame_no[pa];
       if (n >= 2 && n <= max_fill + 1) {

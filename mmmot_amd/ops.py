@@ -482,6 +482,15 @@ class HipOps:
         return self._status('mmmot_fill_tracks', det, ids, frame_start, frame_no, seq_start, xf, wtab, L, F, S, max_fill,
                             capacity, work, fill_start, out, out_id, out_src, info)
 
+    def smooth_tracks(self, det, ids, frame_start, frame_no, seq_start, observed, xf0, L, F, S, params, yaw_flip, work,
+                      out, out_vel, info):
+        """Kalman / RTS smoothing of S tracked sequences in five launches; see mmmot_smooth_tracks.  det / out / out_vel
+        (or None): fp32 device tensors, xf0 (or None: a standing camera): fp64, observed (or None) and the rest int32;
+        ``params`` = (q_loc, r_loc, v0_loc, q_yaw, r_yaw, v0_yaw, q_dim, r_dim).  Returns the entry's status instead of
+        raising, like ``fill_tracks``; the stream is passed as for ``gate_links``."""
+        return self._status('mmmot_smooth_tracks', det, ids, frame_start, frame_no, seq_start, observed, xf0, L, F, S,
+                            *params, yaw_flip, work, out, out_vel, info, self._stream())
+
     def gate_links(self, det, frame_start, frame_no, blocks, xf, r2, inv_r2, link, out_link, kept, L, F, NB, rec_gaps,
                    n_link, mode, max_dt, max_size_ratio, weight):
         """The motion gate over NB link blocks in one launch; see mmmot_gate_links.  det / link / out_link: fp32 device

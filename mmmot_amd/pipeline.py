@@ -92,7 +92,8 @@ from .association import (MotionGate, check_kept, check_status, gap_pairs, gap_s
                           pack_gate, queue_gate, select, select_chain, unpack_gaps)
 from .tracker_glue import queue_scores, queue_solve, queue_solve_chains
 from .torch_ops import FILL_MAX, SEQ_MAX_GAP
-from .tracks import TrackState, TrackStates, fill_gaps, merge_chain_tracks, merge_tracks, window_starts
+from .tracks import (TrackSmoother, TrackState, TrackStates, fill_gaps, merge_chain_tracks, merge_tracks, smooth_tracks,
+                     window_starts)
 
 
 class FrameFeed:
@@ -600,7 +601,7 @@ class SequencePipeline:
         return [links[p] for p in every]
 
     def run_global(self, feeds, frames_per_encode=16, pairs_per_forward=8, max_gap=1, gap_penalty=0.0, fill=0,
-                   gate=None):
+                   gate=None, smooth=None):
         """The whole sequence decided at once: ``run_offline``'s stage A, alignment, trunk and batched pair forwards, then
         ONE min-cost flow over all frames (association.associate_sequence; DESIGN section 11, "Sequences") in place of a
         solve per pair and the ID walk - a unit of flow is a trajectory, its number the track ID.  Needs ``window == 2``.
@@ -637,7 +638,14 @@ class SequencePipeline:
         come from them.  One more launch gates the assembled link scores in place in front of the solve, and its kept
         counts ride in the solve's copy (``GlobalResult.gate_kept``, per block in layout order).  ``stats['gap_pairs']``
         then counts the gap pairs forwarded, ``stats['gated_pairs']`` those left out, ``stats['gated_links']`` the
-        links absent from the program.  ``gate = None``: nothing of this runs."""
+        links absent from the program.  ``gate = None``: nothing of this runs.
+
+        ``smooth`` = a ``tracks.TrackSmoother``: behind the solve (and the filling) the filled
+        sequence - with ``fill = 0`` the solved one - goes through ``tracks.smooth_tracks``: a Kalman filter forwards
+        and an RTS pass backwards along every track, the filled rows as unobserved ones, with the feeds' poses and the
+        first feed's calibration when the camera moves - one more upload, five small launches, one more copy, no forward.
+        The ``tracks.SmoothedTracks`` is stored as ``GlobalResult.smoothed``; ``self.tracks``, ``.filled``, the scores
+        and the statistics stay as they are.  ``smooth = None``: nothing of this runs and ``.smoothed`` is None."""
         if self.window != 2:
             raise ValueError('SequencePipeline.run_global assembles the scores of frame pairs: window must be 2, got %d'
                              % self.window)
@@ -650,6 +658,8 @@ class SequencePipeline:
             raise ValueError('SequencePipeline.run_global: fill must lie in 0 .. %d, got %s' % (FILL_MAX, fill))
         if gate is not None and not isinstance(gate, MotionGate):
             raise ValueError('SequencePipeline.run_global: gate must be an association.MotionGate or None, got %r' % (gate,))
+        if smooth is not None and not isinstance(smooth, TrackSmoother):
+            raise ValueError('SequencePipeline.run_global: smooth must be a tracks.TrackSmoother or None, got %r' % (smooth,))
         moving = _check_poses(feeds)
         n_frames, all_feeds = len(feeds), feeds
         feeds, idx, _ = _skip_empty(feeds, (None, None, None))
@@ -691,6 +701,13 @@ class SequencePipeline:
                                    poses=[f.pose for f in all_feeds] if moving else None,
                                    calib=all_feeds[0].info if moving else None, max_fill=int(fill),
                                    device=self.dev)
+        if res is not None and smooth is not None:
+            ft = res.filled
+            res.smoothed = smooth_tracks([f.dets for f in all_feeds] if ft is None else ft.frames,
+                                         self.tracks if ft is None else ft.ids,
+                                         observed=None if ft is None else [~m for m in ft.filled],
+                                         poses=[f.pose for f in all_feeds] if moving else None,
+                                         calib=all_feeds[0].info if moving else None, smoother=smooth, device=self.dev)
         return res
 
 
@@ -706,6 +723,7 @@ class GlobalResult:
         self.n_tracks, self.objective, self.split = n_tracks, objective, split
         self.gap_scores, self.gap_assignment, self.max_gap = list(gap_scores), list(gap_assignment), max_gap
         self.filled = None  # run_global(fill=F > 0): the tracks.FilledTracks of the whole sequence
+        self.smoothed = None  # run_global(smooth=): the tracks.SmoothedTracks of the filled (else the solved) sequence
         self.gate_kept = None  # run_global(gate=): int64 [blocks], the links of every block the program holds
 
 

@@ -98,7 +98,8 @@ def _upload(device, *parts):
 
 FP64_SECTIONS = frozenset(('boxes', 'box3d', 'sigma', 'frame_d', 'seq_d', 'thr',  # of the packed evaluator blocks
                            'xf', 'wtab',                                           # of the gap-filling block
-                           'r2', 'inv_r2'))                                        # of the motion-gate block
+                           'r2', 'inv_r2',                                         # of the motion-gate block
+                           'xf0'))                                                 # of the smoothing block
 
 
 def _sections_layout(op, parts):
@@ -975,6 +976,67 @@ def _fill_tracks_meta(packed, sizes):
 _LIB.define('fill_tracks(Tensor packed, int[] sizes) -> Tensor')
 _LIB.impl('fill_tracks', _fill_tracks, 'CUDA')
 _LIB.impl('fill_tracks', _fill_tracks_meta, 'Meta')
+
+
+# ---- smoothing of tracked sequences (mmmot_amd/tracks.py; csrc/smooth_tracks.hip) -----------------------------------
+#   mmmot::smooth_tracks(Tensor packed, int[] sizes) -> Tensor
+#       A Kalman filter forwards and an RTS pass backwards along every track of S sequences (mmmot_smooth_tracks: five
+#       launches).  packed: ONE device int32 block holding the call's tables in the order of smooth_layout()[0] (the fp64
+#       records first, as their bit patterns); sizes = [L, F, S, moving (1: the block holds the per-frame ego-motion
+#       records xf0), masked (1: the block holds `observed`), yaw_flip] followed by the 8 fp64 parameters q_loc, r_loc,
+#       v0_loc, q_yaw, r_yaw, v0_yaw, q_dim, r_dim as their int64 bit patterns (smooth_param_bits): they are host
+#       arguments of the entry, which refuses bad ones before any launch.  Returns ONE int32 block in the order of
+#       smooth_layout()[1]: out [L, 12] and vel [L, 4] (fp32 as bit patterns), info [S, 4].
+SMOOTH_PARAMS = 8
+
+
+def smooth_param_bits(params):
+    """the 8 fp64 parameters as int64 bit patterns, for the tail of ``sizes``"""
+    return [int(v) for v in np.asarray(list(params), np.float64).view(np.int64)]
+
+
+def smooth_layout(sizes):
+    """({input section: (offset, int32 count)}, {output section: (offset, int32 count)}, input ints, output ints) of a
+    call with sizes = [L, F, S, moving, masked, yaw_flip, ...]; the fp64 section comes first (8-byte aligned)."""
+    head = [int(v) for v in sizes[:6]]
+    if len(sizes) not in (6, 6 + SMOOTH_PARAMS) or min(head) < 0 or head[2] < 1 or max(head[3:]) > 1:
+        raise ValueError('mmmot::smooth_tracks: sizes must be [L, F, S, moving, masked, yaw_flip] (+ %d parameter bit '
+                         'patterns) with S >= 1 and flags 0 / 1, got %s' % (SMOOTH_PARAMS, list(sizes),))
+    L, F, S, moving, masked, _ = head
+    lay = lambda parts: _sections_layout('smooth_tracks', parts)
+    inp, n_in = lay([('xf0', 2 * FILL_REC * F * moving), ('det', 12 * L), ('ids', L), ('observed', L * masked),
+                     ('frame_start', F + 1), ('frame_no', F), ('seq_start', S + 1)])
+    out, n_out = lay([('out', 12 * L), ('vel', 4 * L), ('info', 4 * S)])
+    return inp, out, n_in, n_out
+
+
+def _smooth_tracks(packed, sizes):
+    inp, outl, n_in, n_out = smooth_layout(sizes)
+    if len(sizes) != 6 + SMOOTH_PARAMS:
+        raise ValueError('mmmot::smooth_tracks: sizes must end in the %d parameter bit patterns' % SMOOTH_PARAMS)
+    if packed.dtype != torch.int32 or packed.dim() != 1 or packed.numel() != n_in or not packed.is_contiguous():
+        raise ValueError('mmmot::smooth_tracks: packed must be a contiguous int32 [%d] block for sizes %s'
+                         % (n_in, list(sizes[:6])))
+    L, F, S, moving, masked, yaw_flip = (int(v) for v in sizes[:6])
+    params = [float(v) for v in np.asarray([int(v) for v in sizes[6:]], np.int64).view(np.float64)]
+    res = torch.zeros(n_out, dtype=torch.int32, device=packed.device)  # L = 0 or F = 0: nothing is launched
+    work = torch.empty((75 * L + 2 + 1) // 2, dtype=torch.int64, device=packed.device).view(torch.int32)  # 8-byte aligned
+    i, o = sections(packed, inp), sections(res, outl)
+    st = _ops().smooth_tracks(i['det'].view(torch.float32), i['ids'], i['frame_start'], i['frame_no'], i['seq_start'],
+                              i['observed'] if masked else None, i['xf0'] if moving else None, L, F, S, params, yaw_flip,
+                              work, o['out'].view(torch.float32), o['vel'].view(torch.float32), o['info'])
+    from . import _lib
+    _lib.check(st, 'mmmot_smooth_tracks')
+    return res
+
+
+def _smooth_tracks_meta(packed, sizes):
+    return packed.new_empty((smooth_layout(sizes)[3],), dtype=torch.int32)
+
+
+_LIB.define('smooth_tracks(Tensor packed, int[] sizes) -> Tensor')
+_LIB.impl('smooth_tracks', _smooth_tracks, 'CUDA')
+_LIB.impl('smooth_tracks', _smooth_tracks_meta, 'Meta')
 
 
 # ---- motion gate of links (mmmot_amd/association.py; csrc/gate_links.hip) -------------------------------------------

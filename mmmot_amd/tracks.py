@@ -427,6 +427,40 @@ def _fill_sequence(seq):
     return seq + (None,) * (len(FILL_KEYS) - len(seq))
 
 
+def sequence_tables(seqs, what):
+    """The tables of mmmot_fill_tracks / mmmot_smooth_tracks from normalised sequences (``_fill_sequence``): ({det fp32
+    [L, 12], ids, frame_start, frame_no, seq_start}, per sequence its int64 frame numbers, per sequence whether it
+    carries poses).  ``what`` names the caller in the errors."""
+    if not seqs:
+        raise ValueError('%s: no sequence' % what)
+    det, ids, counts, frame_no, seq_start, moving = [], [], [], [], [0], []
+    for s, (frames, fids, frame_idx, scores, poses, calib) in enumerate(seqs):
+        n = len(frames)
+        if len(fids) != n or (frame_idx is not None and len(frame_idx) != n) or (scores is not None and len(scores) != n):
+            raise ValueError('%s: sequence %d has %d frames but ids / frame_idx / scores of another length' % (what, s, n))
+        if poses is not None and (len(poses) != n or any(p is None for p in poses)):
+            raise ValueError('%s: sequence %d: poses are given for all frames or none' % (what, s))
+        if poses is not None and calib is None:
+            raise ValueError('%s: sequence %d: poses need calib (R0_rect, Tr_velo_to_cam, Tr_imu_to_velo)' % (what, s))
+        moving.append(poses is not None and n > 0)
+        no = np.arange(n, dtype=np.int64) if frame_idx is None else np.asarray(frame_idx, dtype=np.int64).reshape(-1)
+        if np.abs(no).max(initial=0) >= 2 ** 31:
+            raise ValueError('%s: sequence %d: frame numbers must fit 32 bits' % (what, s))
+        for t, (d, fid) in enumerate(zip(frames, fids)):
+            fid = np.asarray(fid, dtype=np.int64).reshape(-1)
+            det.append(box_rows(d, len(fid), None if scores is None else scores[t]))
+            ids.append(fid)
+            counts.append(len(fid))
+        frame_no.append(no)
+        seq_start.append(seq_start[-1] + n)
+    tab = {'det': np.concatenate(det + [np.zeros((0, 12), np.float32)]),
+           'ids': np.concatenate(ids + [np.zeros(0, np.int64)]).astype(np.int32),
+           'frame_start': np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32),
+           'frame_no': np.concatenate(frame_no + [np.zeros(0, np.int64)]).astype(np.int32),
+           'seq_start': np.asarray(seq_start, np.int32)}
+    return tab, frame_no, moving
+
+
 def pack_fill(sequences, max_fill=7, capacity=None):
     """The host side of ``fill_gaps_batch`` before the launches: per sequence (frames, ids, frame_idx, scores, poses,
     calib) as ``fill_gaps`` takes them (a tuple, or a dict with those keys) -> the tables of mmmot_fill_tracks.  Returns a
@@ -441,41 +475,18 @@ def pack_fill(sequences, max_fill=7, capacity=None):
     if not 1 <= max_fill <= torch_ops.FILL_MAX:
         raise ValueError('fill_gaps: max_fill must lie in 1 .. %d, got %d' % (torch_ops.FILL_MAX, max_fill))
     seqs = [_fill_sequence(s) for s in sequences]
-    if not seqs:
-        raise ValueError('fill_gaps: no sequence')
-    det, ids, counts, frame_no, seq_start, moving, rows = [], [], [], [], [0], [], 0
-    for s, (frames, fids, frame_idx, scores, poses, calib) in enumerate(seqs):
-        n = len(frames)
-        if len(fids) != n or (frame_idx is not None and len(frame_idx) != n) or (scores is not None and len(scores) != n):
-            raise ValueError('fill_gaps: sequence %d has %d frames but ids / frame_idx / scores of another length' % (s, n))
-        if poses is not None and (len(poses) != n or any(p is None for p in poses)):
-            raise ValueError('fill_gaps: sequence %d: poses are given for all frames or none' % s)
-        if poses is not None and calib is None:
-            raise ValueError('fill_gaps: sequence %d: poses need calib (R0_rect, Tr_velo_to_cam, Tr_imu_to_velo)' % s)
-        moving.append(poses is not None and n > 0)
-        no = np.arange(n, dtype=np.int64) if frame_idx is None else np.asarray(frame_idx, dtype=np.int64).reshape(-1)
-        if np.abs(no).max(initial=0) >= 2 ** 31:
-            raise ValueError('fill_gaps: sequence %d: frame numbers must fit 32 bits' % s)
+    tab, frame_no, moving = sequence_tables(seqs, 'fill_gaps')
+    tab.update(wtab=fill_weights(), xf=None)
+    seq_start, F, S, rows = tab['seq_start'].tolist(), len(tab['frame_no']), len(seqs), 0
+    for (frames, fids, _, _, _, _), no in zip(seqs, frame_no):
         last = {}
-        for t, (d, fid) in enumerate(zip(frames, fids)):
+        for t, fid in enumerate(fids):
             fid = np.asarray(fid, dtype=np.int64).reshape(-1)
-            m = len(fid)
-            det.append(box_rows(d, m, None if scores is None else scores[t]))
-            ids.append(fid)
-            counts.append(m)
             for i in fid[fid >= 0]:
                 a = last.get(int(i))
                 if a is not None and 2 <= no[t] - no[a] <= max_fill + 1:
                     rows += t - a - 1
                 last[int(i)] = t
-        frame_no.append(no)
-        seq_start.append(seq_start[-1] + n)
-    F, S = seq_start[-1], len(seqs)
-    tab = {'det': np.concatenate(det + [np.zeros((0, 12), np.float32)]),
-           'ids': np.concatenate(ids + [np.zeros(0, np.int64)]).astype(np.int32),
-           'frame_start': np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32),
-           'frame_no': np.concatenate(frame_no + [np.zeros(0, np.int64)]).astype(np.int32),
-           'seq_start': np.asarray(seq_start, np.int32), 'wtab': fill_weights(), 'xf': None}
     if any(moving):
         xf = np.zeros((F, max_fill + 1, torch_ops.FILL_REC), np.float64)
         xf[:, :, 0:16] = xf[:, :, 16:32] = np.eye(4).reshape(-1)
@@ -580,3 +591,173 @@ def fill_gaps(frames, ids, frame_idx=None, scores=None, poses=None, calib=None, 
     ft.scores)`` and ``evaluate.labels_from_tracks(ft.frames, ft.ids, ..)`` take it as it is.  The inputs are not
     modified.  Raises ``TrackingError`` when an ID occurs twice in a frame or the frame numbers do not increase."""
     return fill_gaps_batch([(frames, ids, frame_idx, scores, poses, calib)], max_fill, device)[0]
+
+
+# ---- smoothing: a Kalman filter forwards, an RTS pass backwards along every track (csrc/smooth_tracks.hip; 12b) ------
+SMOOTH_KEYS = ('frames', 'ids', 'frame_idx', 'observed', 'poses', 'calib', 'scores')
+SMOOTH_STATUS = tuple((bit, text) for bit, text in FILL_STATUS if bit != torch_ops.FILL_ECAPACITY)
+
+
+class TrackSmoother:
+    """The parameters of ``smooth_tracks``, per frame number: for the location (metres), the yaw
+    (radians) and the dimensions h w l (metres) a process noise ``q`` (white acceleration; a random walk for the
+    dimensions), a measurement variance ``r`` and - location and yaw - the variance ``v0`` of the velocity a track
+    starts with.  A group with ``r = 0`` is left as it is.  ``q_dim = 0`` makes the size constant over a track: the mean
+    of its observations.  ``yaw_flip``: a yaw step beyond pi/2 between two observations is read as the detector's front
+    / back confusion and pi is added.  The defaults suit KITTI at 10 Hz (a detector noise of 0.2 m and 0.1 rad, objects
+    that change their per-frame velocity by about 0.1 m); none of them was tuned on real data."""
+
+    NAMES = ('q_loc', 'r_loc', 'v0_loc', 'q_yaw', 'r_yaw', 'v0_yaw', 'q_dim', 'r_dim')
+
+    def __init__(self, q_loc=0.01, r_loc=0.04, v0_loc=1.0, q_yaw=0.001, r_yaw=0.01, v0_yaw=0.04, q_dim=0.0, r_dim=0.01,
+                 yaw_flip=False):
+        values = (q_loc, r_loc, v0_loc, q_yaw, r_yaw, v0_yaw, q_dim, r_dim)
+        for name, v in zip(self.NAMES, values):
+            v = float(v)
+            if not (0.0 <= v < float('inf')):
+                raise ValueError('TrackSmoother: %s must be finite and >= 0, got %r' % (name, v))
+            setattr(self, name, v)
+        for grp in ('loc', 'yaw'):
+            if getattr(self, 'r_' + grp) > 0 and not getattr(self, 'v0_' + grp) > 0:
+                raise ValueError('TrackSmoother: v0_%s must be > 0 where r_%s > 0' % (grp, grp))
+        self.yaw_flip = bool(yaw_flip)
+
+    def params(self):
+        return tuple(getattr(self, n) for n in self.NAMES)
+
+    def __repr__(self):
+        return 'TrackSmoother(%s, yaw_flip=%r)' % (', '.join('%s=%r' % (n, getattr(self, n)) for n in self.NAMES),
+                                                   self.yaw_flip)
+
+
+class SmoothedTracks:
+    """What ``smooth_tracks`` returns for one sequence: ``frames[t]`` a copy of the frame's detection dict with
+    ``dimensions`` (lhw), ``location`` and ``rotation_y`` replaced, ``ids[t]`` / ``scores[t]`` (None when no scores were
+    given) copies of what came, ``velocity[t]`` float64 [n, 4] = vx, vy, vz in the frame's camera axes and the yaw rate, per
+    frame number (0 for rows that were copied), ``info`` = {'tracks', 'rows_changed', 'rows_copied'}."""
+
+    def __init__(self, frames, ids, scores, velocity, info):
+        self.frames, self.ids, self.scores, self.velocity, self.info = frames, ids, scores, velocity, info
+
+
+def _smooth_sequence(seq):
+    if isinstance(seq, dict):
+        unknown = set(seq) - set(SMOOTH_KEYS)
+        if unknown:
+            raise ValueError('smooth_tracks: unknown sequence entries %s' % sorted(unknown))
+        return tuple(seq.get(k) for k in SMOOTH_KEYS)
+    seq = tuple(seq)
+    if not 2 <= len(seq) <= len(SMOOTH_KEYS):
+        raise ValueError('smooth_tracks: a sequence is a dict or a tuple of %s' % (SMOOTH_KEYS,))
+    return seq + (None,) * (len(SMOOTH_KEYS) - len(seq))
+
+
+def pack_smooth(sequences, smoother=None):
+    """The host side of ``smooth_tracks_batch`` before the launches: per sequence (frames, ids, frame_idx, observed,
+    poses, calib, scores) as ``smooth_tracks`` takes them (a tuple, or a dict with those keys) -> the tables of
+    mmmot_smooth_tracks.  Returns a dict: ``packed`` (the int32 block of torch_ops.smooth_layout), ``sizes``, the tables
+    by name (``det``, ``ids``, ``frame_start``, ``frame_no``, ``seq_start`` as for ``pack_fill``; ``observed`` int32 [L]
+    or None when no sequence has a mask; ``xf0`` fp64 [F, 33] or None when no sequence moves: per listed frame
+    ``ego.box_motion`` from the first frame of its sequence), ``smoother`` and ``sequences``.  In a call where only some
+    sequences move or carry a mask the others get identity records / an all-ones mask, which give the same bits."""
+    from . import ego
+    smoother = TrackSmoother() if smoother is None else smoother
+    if not isinstance(smoother, TrackSmoother):
+        raise ValueError('smooth_tracks: smoother must be a tracks.TrackSmoother, got %r' % (smoother,))
+    seqs = [_smooth_sequence(s) for s in sequences]
+    tab, _, moving = sequence_tables([(f, i, n, sc, p, c) for f, i, n, _, p, c, sc in seqs], 'smooth_tracks')
+    L, F, S = len(tab['ids']), len(tab['frame_no']), len(seqs)
+    tab.update(observed=None, xf0=None)
+    if any(q[3] is not None for q in seqs):
+        obs = np.ones(L, np.int32)
+        for s, (frames, fids, _, mask, _, _, _) in enumerate(seqs):
+            if mask is None:
+                continue
+            if len(mask) != len(frames):
+                raise ValueError('smooth_tracks: sequence %d has %d frames but a mask of another length' % (s, len(frames)))
+            for t, m in enumerate(mask):
+                a, b = (int(v) for v in tab['frame_start'][tab['seq_start'][s] + t:][:2])
+                m = np.asarray(m).reshape(-1)
+                if len(m) != b - a:
+                    raise ValueError('smooth_tracks: sequence %d, frame %d: the mask has %d entries for %d detections'
+                                     % (s, t, len(m), b - a))
+                obs[a:b] = m != 0
+        tab['observed'] = obs
+    if any(moving):
+        xf0 = np.zeros((F, torch_ops.FILL_REC), np.float64)
+        xf0[:, 0:16] = xf0[:, 16:32] = np.eye(4).reshape(-1)
+        for s, (frames, _, _, _, poses, calib, _) in enumerate(seqs):
+            if not moving[s]:
+                continue
+            f0 = int(tab['seq_start'][s])
+            for p in range(1, len(frames)):  # frame 0 of a sequence keeps the identity
+                C, Ci, dyaw = ego.box_motion(poses[0], poses[p], calib)
+                xf0[f0 + p, 0:16], xf0[f0 + p, 16:32], xf0[f0 + p, 32] = C.reshape(-1), Ci.reshape(-1), dyaw
+        tab['xf0'] = xf0
+    sizes = [L, F, S, int(tab['xf0'] is not None), int(tab['observed'] is not None), int(smoother.yaw_flip)]
+    sizes += torch_ops.smooth_param_bits(smoother.params())
+    inp, _, n_in, _ = torch_ops.smooth_layout(sizes)
+    packed = np.zeros(n_in, np.int32)
+    for name, (o, n) in inp.items():
+        if n:
+            packed[o:o + n] = np.ascontiguousarray(tab[name]).reshape(-1).view(np.int32)
+    return dict(tab, packed=packed, sizes=sizes, sequences=seqs, smoother=smoother)
+
+
+def unpack_smooth(p, block):
+    """The host side of ``smooth_tracks_batch`` behind the launches: ``p`` from ``pack_smooth``, ``block`` the host int32
+    block of mmmot::smooth_tracks -> one ``SmoothedTracks`` per sequence; raises ``TrackingError`` naming the sequence
+    on a status word.  The inputs are not modified: the frame dicts are copied, the replaced arrays are new."""
+    o = torch_ops.sections(np.asarray(block), torch_ops.smooth_layout(p['sizes'])[1])
+    rows = o['out'].view(np.float32).reshape(-1, 12).astype(np.float64)
+    vel, info = o['vel'].view(np.float32).reshape(-1, 4).astype(np.float64), o['info'].reshape(-1, 4)
+    for s, st in enumerate(info[:, 0]):
+        for bit, text in SMOOTH_STATUS:
+            if st & bit:
+                raise TrackingError('smooth_tracks: sequence %d: %s' % (s, text))
+    frame_start, seq_start = p['frame_start'].astype(np.int64), p['seq_start']
+    res = []
+    for s, (frames, fids, _, _, _, _, scores) in enumerate(p['sequences']):
+        f0 = int(seq_start[s])
+        nf, ni, ns, nv = [], [], [], []
+        for t, (d, fid) in enumerate(zip(frames, fids)):
+            a, b = int(frame_start[f0 + t]), int(frame_start[f0 + t + 1])
+            r, d = rows[a:b], dict(d)
+            d['dimensions'], d['location'], d['rotation_y'] = r[:, [6, 4, 5]], r[:, 7:10].copy(), r[:, 10].copy()
+            nf.append(d)
+            ni.append(np.asarray(fid, dtype=np.int64).reshape(-1).copy())
+            if scores is not None:
+                ns.append(np.array(scores[t]).reshape(-1))
+            nv.append(vel[a:b].copy())
+        res.append(SmoothedTracks(nf, ni, ns if scores is not None else None, nv,
+                                  {'tracks': int(info[s, 1]), 'rows_changed': int(info[s, 2]),
+                                   'rows_copied': int(info[s, 3])}))
+    return res
+
+
+def smooth_tracks_batch(sequences, smoother=None, device='cuda'):
+    """``smooth_tracks`` for many sequences in ONE upload, ONE set of launches (mmmot_smooth_tracks: five, whatever the
+    sequences hold) and ONE copy back.  ``sequences``: per sequence the tuple (frames, ids[, frame_idx, observed, poses,
+    calib, scores]) or a dict with those keys.  Returns one ``SmoothedTracks`` per sequence, bit for bit what ``smooth_tracks``
+    returns for it alone."""
+    p = pack_smooth(sequences, smoother)
+    host = torch.empty(len(p['packed']), dtype=torch.int32, pin_memory=True)
+    host.numpy()[:] = p['packed']
+    block = torch.ops.mmmot.smooth_tracks(host.to(device, non_blocking=True), p['sizes'])
+    return unpack_smooth(p, block.cpu().numpy())
+
+
+def smooth_tracks(frames, ids, frame_idx=None, observed=None, poses=None, calib=None, smoother=None, device='cuda',
+                  scores=None):
+    """A trajectory per track in place of the detector's boxes one by one: a fixed-interval smoother (a Kalman filter
+    forwards, a Rauch-Tung-Striebel pass backwards) over every track of the sequence.  ``frames`` /
+    ``ids`` / ``frame_idx`` are what ``write_kitti_tracks`` takes.  The location and the yaw follow a constant-velocity
+    model (the yaw unwrapped along the track), h w l a random walk; rows whose ``observed[t][j]`` is false carry no
+    measurement - ``observed=[~m for m in filled.filled]`` for a ``FilledTracks``, whose straight-line rows are then
+    replaced by the smoother's.  Rows behind a track's last observation are extrapolated, rows in front of its first one,
+    rejected rows (ID -1) and tracks of one row are returned as they are.  ``poses`` / ``calib`` as for ``fill_gaps``: with
+    a moving camera the filter runs in the first frame's coordinates.  ``smoother``: a ``TrackSmoother`` (default: its
+    defaults); ``scores``: per frame the per-detection scores, carried through (``FilledTracks.scores``).  Returns a ``SmoothedTracks``; ``write_kitti_tracks(path, st.frames, st.ids, frame_idx, st.scores)`` and
+    ``evaluate.labels_from_tracks(st.frames, st.ids, .., box3d=True)`` take it as it is.  The 2D box and the score are
+    not changed.  Raises ``TrackingError`` when an ID occurs twice in a frame or the frame numbers do not increase."""
+    return smooth_tracks_batch([(frames, ids, frame_idx, observed, poses, calib, scores)], smoother, device)[0]

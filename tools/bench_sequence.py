@@ -30,6 +30,12 @@ sequences at once and for 21 calls, one per sequence, interleaved, median of --s
 wall time of ``fill_gaps_batch`` (packing, upload, launches, copy, unpacking) and of the NumPy restatement
 tests/fill_ref.py on the same tables, whose rows must equal the device's bit for bit.  Writes
 <out>/bench_sequence_fill.json.
+--smooth measures the track smoothing alone (tracks.smooth_tracks_batch; no model is built) on the
+--fill scene after its gaps were filled on the device, the filled rows as unobserved ones, TrackSmoother() defaults:
+HIP-event time of the operator call on resident blocks for all sequences at once and for 21 calls, interleaved, median
+of --solver-calls after one untimed round; the wall time of ``smooth_tracks_batch`` and of the NumPy restatement
+tests/smooth_ref.py on the same tables, whose block must equal the device's bit for bit.  Writes
+<out>/bench_sequence_smooth.json.
 --gate G measures the motion gate (run_global(max_gap=G, gate=MotionGate(--gate-speed, --gate-slack)), DESIGN section 11
 "motion gate") beside the same call with gate=None on the same feeds, interleaved: wall time of ``run_global``, the gap
 pairs forwarded and left out, the links gated; and the gate's two launches alone on the sequence's own tables (the
@@ -42,6 +48,7 @@ unrelated random boxes, so far more pairs are left out than in a real sequence. 
     python tools/bench_sequence.py --out <dir> --streams 1 2 4 8 16 [--frames 40] [--repeats 3]
     python tools/bench_sequence.py --out <dir> --global-gap 1 2 3 4 [--frames 100] [--repeats 3] [--solver-calls 20]
     python tools/bench_sequence.py --out <dir> --fill [--fill-frames 8000] [--ego] [--solver-calls 20]
+    python tools/bench_sequence.py --out <dir> --smooth [--fill-frames 8000] [--ego] [--solver-calls 20]
     python tools/bench_sequence.py --out <dir> --gate 3 [--gate-speed 4.0] [--gate-slack 2.0] [--frames 100] [--ego]
 """
 import argparse
@@ -399,6 +406,67 @@ def bench_fill(args):
     print(json.dumps(rec))
 
 
+def bench_smooth(args):
+    """the smoothing operator for all sequences at once beside one call per sequence, and the host routes around them"""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import smooth_ref
+    from mmmot_amd import tracks
+    n_seq = 21
+    filled = tracks.fill_gaps_batch(fill_workload(n_seq, args.fill_frames, 0.1, args.ego), 7)
+    base = fill_workload(n_seq, args.fill_frames, 0.1, args.ego)
+    seqs = [(f.frames, f.ids, None, [~m for m in f.filled], b[4], b[5]) for f, b in zip(filled, base)]
+    up = lambda p: (torch.from_numpy(p['packed']).cuda(), p['sizes'])
+    t0 = time.perf_counter()
+    p = tracks.pack_smooth(seqs)
+    pack_ms = 1e3 * (time.perf_counter() - t0)
+    batch, singles = up(p), [up(tracks.pack_smooth([s])) for s in seqs]
+    calls = {'batch': lambda: [torch.ops.mmmot.smooth_tracks(*batch)],
+             'singles': lambda: [torch.ops.mmmot.smooth_tracks(*b) for b in singles]}
+    ms, out = {k: [] for k in calls}, {}
+    for i in range(args.solver_calls + 1):  # the first round untimed
+        for name, call in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out[name] = call()
+            e1.record()
+            torch.cuda.synchronize()
+            if i:
+                ms[name].append(e0.elapsed_time(e1))
+    wall = []
+    for _ in range(4):  # the first untimed
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        smoothed = tracks.smooth_tracks_batch(seqs)
+        wall.append(1e3 * (time.perf_counter() - t0))
+    print('device done, the restatement runs', flush=True)
+    t0 = time.perf_counter()
+    prm = dict(zip(smooth_ref.PARAMS, p['smoother'].params()), yaw_flip=p['smoother'].yaw_flip)
+    ref = smooth_ref.smooth(p['det'], p['ids'], p['frame_start'], p['frame_no'], p['seq_start'], p['observed'], p['xf0'],
+                            **prm)
+    ref_ms = 1e3 * (time.perf_counter() - t0)
+    if not np.array_equal(out['batch'][0].cpu().numpy(), smooth_ref.block_of(ref, p['sizes'])):
+        raise SystemExit('the device block differs from the restatement')
+    info = [b.cpu().numpy()[-4:].tolist() for b in out['singles']]
+    if info != ref['info'].tolist() or [list(s.info.values()) for s in smoothed] != [r[1:] for r in info]:
+        raise SystemExit('the single calls and the batch report different counters')
+    L, F = p['sizes'][0], p['sizes'][1]
+    rec = {
+        'op_ms': {k: round(float(np.median(v)), 3) for k, v in ms.items()},
+        'op_ms_min_max': {k: [round(min(v), 3), round(max(v), 3)] for k, v in ms.items()},
+        'smooth_tracks_batch_wall_ms': round(float(np.median(wall[1:])), 1), 'pack_smooth_wall_ms': round(pack_ms, 1),
+        'numpy_restatement_wall_ms': round(ref_ms, 1),
+        'instance': '%d sequences, %d frames, %d rows (%d of them filled, unobserved): %d tracks smoothed, %d rows '
+                    'changed, %d copied; longest track %d rows'
+                    % (n_seq, F, L, int((p['observed'] == 0).sum()), int(ref['info'][:, 1].sum()),
+                       int(ref['info'][:, 2].sum()), int(ref['info'][:, 3].sum()), max(len(s[0]) for s in seqs)),
+        'calls': args.solver_calls, 'ego': bool(args.ego), 'device': torch.cuda.get_device_name(0),
+    }
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_sequence_smooth.json'), 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', required=True)
@@ -420,6 +488,8 @@ def main():
     ap.add_argument('--solver-calls', type=int, default=20)
     ap.add_argument('--fill', action='store_true', help='time the gap filling alone: all sequences at once, one call each, NumPy')
     ap.add_argument('--fill-frames', type=int, default=8000)
+    ap.add_argument('--smooth', action='store_true',
+                    help='time the track smoothing alone on the filled --fill scene: all sequences at once, one call each, NumPy')
     ap.add_argument('--gate', type=int, default=None,
                     help='time run_global(max_gap=G) with and without a MotionGate, and the gate launches alone')
     ap.add_argument('--gate-speed', type=float, default=4.0, help='MotionGate(max_speed=), metres per frame')
@@ -427,6 +497,8 @@ def main():
     args = ap.parse_args()
     if args.fill:
         return bench_fill(args)
+    if args.smooth:
+        return bench_smooth(args)
     assoc = args.associate or args.track
     kw = dict(associate=assoc, track=True) if args.track else dict(associate=assoc)
     if args.repeats < 3 or args.frames < 2:
