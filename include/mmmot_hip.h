@@ -596,6 +596,60 @@ int mmmot_smooth_tracks(const float* det, const int* ids, const int* frame_start
                         double r_dim, int yaw_flip, int* work, float* out, float* out_vel, int* info, void* hip_stream);
 
 /* ---------------------------------------------------------------------------
+ * Tracklet stitching (csrc/stitch_tracks.hip; DESIGN section 12c, which states the order of every operation), additive
+ * in ABI 10: every track of a sequence is one node; the tail of a track is joined to the head of a later one when a
+ * constant-velocity prediction reaches it, one to one by the exact solver of mmmot_associate_pairs, and the joined
+ * tracks take the ID of the first.  Seven launches and the solver's, whatever the rows, frames, sequences and tracks.
+ *   det, ids, frame_start, frame_no, seq_start: the tables of mmmot_fill_tracks
+ *   vel         [L][4] fp32 or NULL: vx, vy, vz per frame number in the row's own frame's axes (out_vel of
+ *               mmmot_smooth_tracks); word 3 is not read
+ *   xf0         [F][MMMOT_FILL_REC] fp64 or NULL (a standing camera): the records of mmmot_smooth_tracks; only words
+ *               0..15, C[a<-p], are read
+ *   k_start     [S+1]: prefix table of the tracks per sequence, counted on the host; k_start[S] = n_tracks
+ *   pairs       [S][4] = (K_s, K_s, 2 k_start[s], sum of K^2 of the sequences before s): the pair table of
+ *               mmmot_associate_pairs over the link blocks; n_link = the sum over all sequences
+ *   r2, inv_r2  [2][max_dt+1] fp64, host-made: row 0 (drift dt + slack)^2, row 1 (max_speed dt + slack)^2, and the
+ *               reciprocals; entry 0 is never read
+ *   max_k       the largest K_s; the solver is launched for min(max_k, MMMOT_STITCH_MAXK)
+ *   work        [MMMOT_STITCH_WORK(L, F, S, n_tracks, n_link)] ints of scratch, 8-byte aligned
+ *   out_ids     [L]: the ID of the root of the row's chain of tracks; rows with ID < 0 are copied
+ *   next        [L]: for a matched tail row the flat index of the head row it was joined to, else -1
+ *   links       [n_link] fp32: per sequence the [K_s][K_s] scores, tails on rows, heads on columns, at its link offset
+ *   objective   [S] fp64 from the solver: the sum of the kept scores; NaN for K_s = 0 or a status
+ *   info        [S][4] out: status, K_s, stitches, rows whose ID changed
+ * A track is the rows of one sequence with the same ID >= 0 in listed-frame order, its head the first and its tail the
+ * last; tracks are numbered by the ascending flat row index of their heads.  With M = words 0..15 of the row's frame's
+ * record, P_j = ((x M[0][j] + y M[1][j]) + z M[2][j]) + M[3][j] and V_j = (vx M[0][j] + vy M[1][j]) + vz M[2][j] (the
+ * fp32 values as fp64 when xf0 is NULL).  A track has a velocity iff vel is given and it has >= min_rows rows.
+ * Candidate (i, j): dt = frame_no[head_j] - frame_no[tail_i], d = (double)dt; absent unless min_dt <= dt <= max_dt.
+ * Errors e0 e0 + e2 e2 (mode 0), + e1 e1 last (mode 1), of ef: Ph - (Pt + d Vt); eb: Pt - (Ph - d Vh); es: Ph - Pt.
+ * Both have a velocity: passes iff ef <= r2[0][dt] and eb <= r2[0][dt], d2 = eb > ef ? eb : ef; only the tail: d2 = ef
+ * against row 0; only the head: d2 = eb against row 0; neither: d2 = es against row 1; with max_size_ratio > 0 also the
+ * size test of mmmot_gate_links on the tail's and the head's h w l.  Every comparison fails on a NaN operand.  Score
+ * (float)((1.0 - d2 inv_r2[m][dt]) - gap_penalty (d - 1.0)), every operator rounded on its own; an absent link is the
+ * quiet NaN 0x7fc00000.  The solver keeps the maximum-weight matching of the links with a score > 0.
+ * Status, per sequence, never a fault: MMMOT_FILL_EDUP / MMMOT_FILL_ECONTRACT as for mmmot_fill_tracks; ECONTRACT also
+ * when the device counts another number of heads than k_start holds, or more than max_k; MMMOT_STITCH_ETOOMANY for more
+ * than MMMOT_STITCH_MAXK tracks.  With a status out_ids = ids, next = -1, the link block is all NaN, the objective NaN,
+ * info = status, 0, 0, 0.  A frame_start / seq_start that breaks its shape gives every sequence ECONTRACT and nothing
+ * is read through them; so does a k_start / pairs that is not the table above (then all of links is NaN).
+ * Returns MMMOT_EINVAL before any launch for S < 1, a negative L / F / n_tracks / n_link / max_k, min_dt < 1, max_dt <
+ * min_dt or > MMMOT_STITCH_MAX_DT, a mode outside {0, 1}, min_rows < 1, a negative or NaN max_size_ratio or
+ * gap_penalty and, with L > 0 and F > 0, a null pointer (vel and xf0 may be null), a work that is not 8-byte aligned
+ * or MMMOT_STITCH_WORK(..) >= 2^31.  L = 0 or F = 0 is a no-op that returns 0.  No allocation, no synchronisation.
+ * The launches go to `hip_stream`, as for mmmot_gate_links. */
+#define MMMOT_STITCH_MAXK 512
+#define MMMOT_STITCH_MAX_DT 256
+#define MMMOT_STITCH_ETOOMANY 8
+#define MMMOT_STITCH_WORK(L, F, S, T, NL) (4 * (long)(L) + (long)(F) + 5 * (long)(S) + 39 * (long)(T) + (long)(NL) + 2)
+int mmmot_stitch_tracks(const float* det, const int* ids, const int* frame_start, const int* frame_no,
+                        const int* seq_start, const float* vel, const double* xf0, const int* k_start,
+                        const int* pairs, const double* r2, const double* inv_r2, int L, int F, int S, int n_tracks,
+                        long n_link, int max_k, int min_dt, int max_dt, int min_rows, int mode, double max_size_ratio,
+                        double gap_penalty, int* work, int* out_ids, int* next, float* links, double* objective,
+                        int* info, void* hip_stream);
+
+/* ---------------------------------------------------------------------------
  * Motion gate of links (csrc/gate_links.hip; DESIGN section 11, "Sequences: motion gate"), additive in ABI 10: a link
  * whose two 3D boxes lie further apart than an object travels in the elapsed frames is written as a quiet NaN, which
  * mmmot_associate, the chain entries and the sequence entries read as an absent edge.  ONE launch whatever NB, F and

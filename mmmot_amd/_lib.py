@@ -21,7 +21,7 @@ SOURCES = [
     'crop_augment.hip', 'small_kernels.hip', 'backward.hip', 'train.hip', 'train_vgg.hip', 'gemm_tn_f16.hip',
     'assign.hip', 'assign_chain.hip', 'assign_sequence.hip', 'track_ids.hip', 'clear_mot.hip', 'hota.hip',
     'mot3d.hip', 'align_points.hip', 'fill_tracks.hip', 'labels.hip', 'adam_step.hip', 'dropout.hip',
-    'gate_links.hip', 'smooth_tracks.hip',
+    'gate_links.hip', 'smooth_tracks.hip', 'stitch_tracks.hip',
 ]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 HIPFLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']

@@ -491,6 +491,17 @@ class HipOps:
         return self._status('mmmot_smooth_tracks', det, ids, frame_start, frame_no, seq_start, observed, xf0, L, F, S,
                             *params, yaw_flip, work, out, out_vel, info, self._stream())
 
+    def stitch_tracks(self, det, ids, frame_start, frame_no, seq_start, vel, xf0, k_start, pairs, r2, inv_r2, L, F, S,
+                      n_tracks, n_link, max_k, min_dt, max_dt, min_rows, mode, max_size_ratio, gap_penalty, work, out_ids,
+                      nxt, links, objective, info):
+        """Tracklet stitching of S tracked sequences in seven launches and the pair solver's; see mmmot_stitch_tracks.
+        det / vel (or None) / links: fp32 device tensors, xf0 (or None: a standing camera) / r2 / inv_r2 / objective:
+        fp64, the rest int32.  Returns the entry's status instead of raising, like ``fill_tracks``; the stream is passed
+        as for ``gate_links``."""
+        return self._status('mmmot_stitch_tracks', det, ids, frame_start, frame_no, seq_start, vel, xf0, k_start, pairs,
+                            r2, inv_r2, L, F, S, n_tracks, n_link, max_k, min_dt, max_dt, min_rows, mode, max_size_ratio,
+                            gap_penalty, work, out_ids, nxt, links, objective, info, self._stream())
+
     def gate_links(self, det, frame_start, frame_no, blocks, xf, r2, inv_r2, link, out_link, kept, L, F, NB, rec_gaps,
                    n_link, mode, max_dt, max_size_ratio, weight):
         """The motion gate over NB link blocks in one launch; see mmmot_gate_links.  det / link / out_link: fp32 device

@@ -92,8 +92,8 @@ from .association import (MotionGate, check_kept, check_status, gap_pairs, gap_s
                           pack_gate, queue_gate, select, select_chain, unpack_gaps)
 from .tracker_glue import queue_scores, queue_solve, queue_solve_chains
 from .torch_ops import FILL_MAX, SEQ_MAX_GAP
-from .tracks import (TrackSmoother, TrackState, TrackStates, fill_gaps, merge_chain_tracks, merge_tracks, smooth_tracks,
-                     window_starts)
+from .tracks import (TrackSmoother, TrackState, TrackStates, TrackStitcher, fill_gaps, merge_chain_tracks, merge_tracks,
+                     smooth_tracks, stitch_tracks, window_starts)
 
 
 class FrameFeed:
@@ -601,7 +601,7 @@ class SequencePipeline:
         return [links[p] for p in every]
 
     def run_global(self, feeds, frames_per_encode=16, pairs_per_forward=8, max_gap=1, gap_penalty=0.0, fill=0,
-                   gate=None, smooth=None):
+                   gate=None, smooth=None, stitch=None):
         """The whole sequence decided at once: ``run_offline``'s stage A, alignment, trunk and batched pair forwards, then
         ONE min-cost flow over all frames (association.associate_sequence; DESIGN section 11, "Sequences") in place of a
         solve per pair and the ID walk - a unit of flow is a trajectory, its number the track ID.  Needs ``window == 2``.
@@ -645,7 +645,17 @@ class SequencePipeline:
         and an RTS pass backwards along every track, the filled rows as unobserved ones, with the feeds' poses and the
         first feed's calibration when the camera moves - one more upload, five small launches, one more copy, no forward.
         The ``tracks.SmoothedTracks`` is stored as ``GlobalResult.smoothed``; ``self.tracks``, ``.filled``, the scores
-        and the statistics stay as they are.  ``smooth = None``: nothing of this runs and ``.smoothed`` is None."""
+        and the statistics stay as they are.  ``smooth = None``: nothing of this runs and ``.smoothed`` is None.
+
+        ``stitch`` = a ``tracks.TrackStitcher``: behind the solve, the filling and the smoothing the
+        smoothed sequence with its velocities - without ``smooth`` the filled or the solved one, without velocities -
+        goes through ``tracks.stitch_tracks``, which rejoins tracks that an occlusion longer than ``max_gap`` broke -
+        one more upload, eight small launches, one more copy, no forward.  When anything was stitched and ``fill`` > 0,
+        one more ``fill_gaps`` over the relabelled (unsmoothed) sequence fills the new holes and, with ``smooth``, one
+        more ``smooth_tracks`` follows, its mask the first one extended by the new rows.  The ``tracks.StitchedTracks``
+        is stored as ``GlobalResult.stitched``, that second pass in its ``.filled`` / ``.smoothed`` (else None);
+        ``self.tracks``, ``.filled``, ``.smoothed``, the scores and the statistics stay as they are.  ``stitch = None``:
+        nothing of this runs and ``.stitched`` is None."""
         if self.window != 2:
             raise ValueError('SequencePipeline.run_global assembles the scores of frame pairs: window must be 2, got %d'
                              % self.window)
@@ -660,6 +670,8 @@ class SequencePipeline:
             raise ValueError('SequencePipeline.run_global: gate must be an association.MotionGate or None, got %r' % (gate,))
         if smooth is not None and not isinstance(smooth, TrackSmoother):
             raise ValueError('SequencePipeline.run_global: smooth must be a tracks.TrackSmoother or None, got %r' % (smooth,))
+        if stitch is not None and not isinstance(stitch, TrackStitcher):
+            raise ValueError('SequencePipeline.run_global: stitch must be a tracks.TrackStitcher or None, got %r' % (stitch,))
         moving = _check_poses(feeds)
         n_frames, all_feeds = len(feeds), feeds
         feeds, idx, _ = _skip_empty(feeds, (None, None, None))
@@ -708,6 +720,22 @@ class SequencePipeline:
                                          observed=None if ft is None else [~m for m in ft.filled],
                                          poses=[f.pose for f in all_feeds] if moving else None,
                                          calib=all_feeds[0].info if moving else None, smoother=smooth, device=self.dev)
+        if res is not None and stitch is not None:
+            ft, sm = res.filled, res.smoothed
+            ego = dict(poses=[f.pose for f in all_feeds] if moving else None, calib=all_feeds[0].info if moving else None)
+            raw = [f.dets for f in all_feeds] if ft is None else ft.frames  # the rows of ``sm.frames``, unsmoothed
+            sk = stitch_tracks(raw if sm is None else sm.frames, (self.tracks if ft is None else ft.ids) if sm is None
+                               else sm.ids, velocity=None if sm is None else sm.velocity, stitcher=stitch,
+                               device=self.dev, **ego)
+            if sk.info['stitches'] > 0 and int(fill) > 0:
+                sk.filled = fill_gaps(raw, sk.ids, max_fill=int(fill), device=self.dev, **ego)
+                if smooth is not None:
+                    seen = [np.ones(len(i), bool) for i in sk.ids] if ft is None else [~m for m in ft.filled]
+                    sk.smoothed = smooth_tracks(sk.filled.frames, sk.filled.ids,
+                                                observed=[np.concatenate([o, np.zeros(len(m) - len(o), bool)])
+                                                          for o, m in zip(seen, sk.filled.filled)],
+                                                smoother=smooth, device=self.dev, **ego)
+            res.stitched = sk
         return res
 
 
@@ -724,6 +752,7 @@ class GlobalResult:
         self.gap_scores, self.gap_assignment, self.max_gap = list(gap_scores), list(gap_assignment), max_gap
         self.filled = None  # run_global(fill=F > 0): the tracks.FilledTracks of the whole sequence
         self.smoothed = None  # run_global(smooth=): the tracks.SmoothedTracks of the filled (else the solved) sequence
+        self.stitched = None  # run_global(stitch=): the tracks.StitchedTracks of the smoothed (else filled / solved) sequence
         self.gate_kept = None  # run_global(gate=): int64 [blocks], the links of every block the program holds
 
 

@@ -99,7 +99,8 @@ def _upload(device, *parts):
 FP64_SECTIONS = frozenset(('boxes', 'box3d', 'sigma', 'frame_d', 'seq_d', 'thr',  # of the packed evaluator blocks
                            'xf', 'wtab',                                           # of the gap-filling block
                            'r2', 'inv_r2',                                         # of the motion-gate block
-                           'xf0'))                                                 # of the smoothing block
+                           'xf0',                                                  # of the smoothing block
+                           'objective'))                                           # of the stitching block
 
 
 def _sections_layout(op, parts):
@@ -1037,6 +1038,87 @@ def _smooth_tracks_meta(packed, sizes):
 _LIB.define('smooth_tracks(Tensor packed, int[] sizes) -> Tensor')
 _LIB.impl('smooth_tracks', _smooth_tracks, 'CUDA')
 _LIB.impl('smooth_tracks', _smooth_tracks_meta, 'Meta')
+
+
+# ---- tracklet stitching of tracked sequences (mmmot_amd/tracks.py; csrc/stitch_tracks.hip) --------------------------
+#   mmmot::stitch_tracks(Tensor packed, int[] sizes) -> Tensor
+#       Tails of tracks joined to the heads of later ones, one to one, for S sequences (mmmot_stitch_tracks: seven
+#       launches and the pair solver's).  packed: ONE device int32 block holding the call's tables in the order of
+#       stitch_layout()[0] (the fp64 records and radius tables first, as their bit patterns); sizes = [L, F, S, n_tracks,
+#       n_link, max_k, moving (1: the block holds xf0), has_vel (1: the block holds vel), min_dt, max_dt, min_rows, mode]
+#       followed by max_size_ratio and gap_penalty as their int64 bit patterns (stitch_param_bits): host arguments of
+#       the entry, which refuses bad ones before any launch.  Returns ONE int32 block in the order of stitch_layout()[1]:
+#       objective [S] (fp64), out_ids [L], next [L], links [n_link] (fp32 as bit patterns), info [S, 4].
+STITCH_MAXK, STITCH_MAX_DT, STITCH_ETOOMANY = 512, 256, 8  # MMMOT_STITCH_MAXK, MMMOT_STITCH_MAX_DT, MMMOT_STITCH_ETOOMANY
+STITCH_SIZES, STITCH_PARAMS = 12, 2
+STITCH_MODES = {'ground': 0, '3d': 1}
+
+
+def stitch_param_bits(max_size_ratio, gap_penalty):
+    """the 2 fp64 parameters as int64 bit patterns, for the tail of ``sizes``"""
+    return [int(v) for v in np.asarray([max_size_ratio, gap_penalty], np.float64).view(np.int64)]
+
+
+def stitch_work(L, F, S, T, n_link):
+    """MMMOT_STITCH_WORK: the ints of scratch of a call"""
+    return 4 * L + F + 5 * S + 39 * T + n_link + 2
+
+
+def stitch_layout(sizes):
+    """({input section: (offset, int32 count)}, {output section: (offset, int32 count)}, input ints, output ints) of a
+    call with sizes = [L, F, S, n_tracks, n_link, max_k, moving, has_vel, min_dt, max_dt, min_rows, mode, ...]; the
+    fp64 sections come first (8-byte aligned)."""
+    head = [int(v) for v in sizes[:STITCH_SIZES]]
+    if len(sizes) not in (STITCH_SIZES, STITCH_SIZES + STITCH_PARAMS) or min(head) < 0 or head[2] < 1 or \
+            max(head[6:8]) > 1:
+        raise ValueError('mmmot::stitch_tracks: sizes must be [L, F, S, n_tracks, n_link, max_k, moving, has_vel, min_dt, '
+                         'max_dt, min_rows, mode] (+ %d parameter bit patterns) with S >= 1 and flags 0 / 1, got %s'
+                         % (STITCH_PARAMS, list(sizes),))
+    L, F, S, T, n_link, _, moving, has_vel, min_dt, max_dt, _, mode = head
+    if not 1 <= min_dt <= max_dt <= STITCH_MAX_DT:
+        raise ValueError('mmmot::stitch_tracks: 1 <= min_dt <= max_dt <= %d, got %d, %d' % (STITCH_MAX_DT, min_dt, max_dt))
+    if mode not in (0, 1):
+        raise ValueError('mmmot::stitch_tracks: mode must be 0 (ground plane) or 1 (3d), got %d' % mode)
+    lay = lambda parts: _sections_layout('stitch_tracks', parts)
+    inp, n_in = lay([('xf0', 2 * FILL_REC * F * moving), ('r2', 4 * (max_dt + 1)), ('inv_r2', 4 * (max_dt + 1)),
+                     ('det', 12 * L), ('vel', 4 * L * has_vel), ('ids', L), ('frame_start', F + 1), ('frame_no', F),
+                     ('seq_start', S + 1), ('k_start', S + 1), ('pairs', 4 * S)])
+    out, n_out = lay([('objective', 2 * S), ('out_ids', L), ('next', L), ('links', n_link), ('info', 4 * S)])
+    return inp, out, n_in, n_out
+
+
+def _stitch_tracks(packed, sizes):
+    inp, outl, n_in, n_out = stitch_layout(sizes)
+    if len(sizes) != STITCH_SIZES + STITCH_PARAMS:
+        raise ValueError('mmmot::stitch_tracks: sizes must end in the %d parameter bit patterns' % STITCH_PARAMS)
+    if packed.dtype != torch.int32 or packed.dim() != 1 or packed.numel() != n_in or not packed.is_contiguous():
+        raise ValueError('mmmot::stitch_tracks: packed must be a contiguous int32 [%d] block for sizes %s'
+                         % (n_in, list(sizes[:STITCH_SIZES])))
+    L, F, S, T, n_link, max_k, moving, has_vel, min_dt, max_dt, min_rows, mode = (int(v) for v in sizes[:STITCH_SIZES])
+    ratio, penalty = (float(v) for v in np.asarray([int(v) for v in sizes[STITCH_SIZES:]], np.int64).view(np.float64))
+    res = torch.zeros(n_out, dtype=torch.int32, device=packed.device)
+    work = torch.empty((stitch_work(L, F, S, T, n_link) + 1) // 2, dtype=torch.int64,
+                       device=packed.device).view(torch.int32)  # 8-byte aligned
+    i, o = sections(packed, inp), sections(res, outl)
+    if L == 0 or F == 0:  # nothing is launched: no tracks, no links, objectives of sequences without tracks
+        o['objective'].fill_(float('nan'))
+    st = _ops().stitch_tracks(i['det'].view(torch.float32), i['ids'], i['frame_start'], i['frame_no'], i['seq_start'],
+                              i['vel'].view(torch.float32) if has_vel else None, i['xf0'] if moving else None,
+                              i['k_start'], i['pairs'], i['r2'], i['inv_r2'], L, F, S, T, n_link, max_k, min_dt, max_dt,
+                              min_rows, mode, ratio, penalty, work, o['out_ids'], o['next'], o['links'].view(torch.float32),
+                              o['objective'], o['info'])
+    from . import _lib
+    _lib.check(st, 'mmmot_stitch_tracks')
+    return res
+
+
+def _stitch_tracks_meta(packed, sizes):
+    return packed.new_empty((stitch_layout(sizes)[3],), dtype=torch.int32)
+
+
+_LIB.define('stitch_tracks(Tensor packed, int[] sizes) -> Tensor')
+_LIB.impl('stitch_tracks', _stitch_tracks, 'CUDA')
+_LIB.impl('stitch_tracks', _stitch_tracks_meta, 'Meta')
 
 
 # ---- motion gate of links (mmmot_amd/association.py; csrc/gate_links.hip) -------------------------------------------

@@ -761,3 +761,204 @@ def smooth_tracks(frames, ids, frame_idx=None, observed=None, poses=None, calib=
     ``evaluate.labels_from_tracks(st.frames, st.ids, .., box3d=True)`` take it as it is.  The 2D box and the score are
     not changed.  Raises ``TrackingError`` when an ID occurs twice in a frame or the frame numbers do not increase."""
     return smooth_tracks_batch([(frames, ids, frame_idx, observed, poses, calib, scores)], smoother, device)[0]
+
+
+# ---- stitching: the tail of a track joined to the head of a later one (csrc/stitch_tracks.hip; DESIGN section 12c) ---
+STITCH_KEYS = ('frames', 'ids', 'frame_idx', 'velocity', 'poses', 'calib')
+STITCH_STATUS = SMOOTH_STATUS + ((torch_ops.STITCH_ETOOMANY, 'more than %d tracks' % torch_ops.STITCH_MAXK),)
+
+
+class TrackStitcher:
+    """The parameters of ``stitch_tracks`` and its two fp64 tables.  The tail of a track and the
+    head of a later one, ``min_dt <= dt <= max_dt`` frame numbers apart, are a candidate when the constant-velocity
+    prediction of one lies within ``drift * dt + slack`` metres of the other - forwards from the tail, backwards from
+    the head, both where both tracks have a velocity (``min_rows`` rows or more and a ``velocity`` given).  Two tracks
+    without a velocity are compared as they stand, within ``max_speed * dt + slack``.  ``drift`` and ``max_speed`` are
+    in metres per frame number, ``slack`` in metres; ``mode`` 'ground' measures in the camera's x / z plane, '3d' with
+    y; ``max_size_ratio`` > 0 also bounds the factor between the two boxes' h, w and l; ``gap_penalty`` lowers the
+    score of a candidate by that much per frame number beyond the first.  The defaults are stated choices for KITTI at
+    10 Hz (0.5 m per frame of velocity error, 40 m/s, the motion gate's 2 m of slack, three seconds of occlusion); none
+    of them was tuned on real data."""
+
+    def __init__(self, max_dt=30, min_dt=1, drift=0.5, max_speed=4.0, slack=2.0, min_rows=3, mode='ground',
+                 max_size_ratio=0.0, gap_penalty=0.0):
+        fin = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+        whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        if not (whole(min_dt) and whole(max_dt) and 1 <= int(min_dt) <= int(max_dt) <= torch_ops.STITCH_MAX_DT):
+            raise ValueError('TrackStitcher: min_dt and max_dt must be integers with 1 <= min_dt <= max_dt <= %d, got %r, '
+                             '%r' % (torch_ops.STITCH_MAX_DT, min_dt, max_dt))
+        if not (fin(drift) and fin(max_speed) and fin(slack) and min(drift, max_speed, slack) >= 0
+                and drift + slack > 0 and max_speed + slack > 0):
+            raise ValueError('TrackStitcher: drift, max_speed and slack must be finite and >= 0 with every radius > 0, '
+                             'got %r, %r, %r' % (drift, max_speed, slack))
+        if not (whole(min_rows) and int(min_rows) >= 1):
+            raise ValueError('TrackStitcher: min_rows must be an integer >= 1, got %r' % (min_rows,))
+        if mode not in torch_ops.STITCH_MODES:
+            raise ValueError('TrackStitcher: mode must be one of %s, got %r' % (sorted(torch_ops.STITCH_MODES), mode))
+        if not (fin(max_size_ratio) and (max_size_ratio == 0 or max_size_ratio >= 1)):
+            raise ValueError('TrackStitcher: max_size_ratio must be 0 (off) or a finite factor >= 1, got %r'
+                             % (max_size_ratio,))
+        if not (fin(gap_penalty) and gap_penalty >= 0):
+            raise ValueError('TrackStitcher: gap_penalty must be finite and >= 0, got %r' % (gap_penalty,))
+        self.max_dt, self.min_dt, self.min_rows, self.mode = int(max_dt), int(min_dt), int(min_rows), mode
+        self.drift, self.max_speed, self.slack = float(drift), float(max_speed), float(slack)
+        self.max_size_ratio, self.gap_penalty = float(max_size_ratio), float(gap_penalty)
+        dt = np.arange(self.max_dt + 1, dtype=np.float64)
+        r = np.stack([np.float64(self.drift) * dt + np.float64(self.slack),
+                      np.float64(self.max_speed) * dt + np.float64(self.slack)])
+        self.r2 = r * r
+        self.inv_r2 = np.full_like(self.r2, np.nan)  # entry 0 is never read: dt >= 1
+        self.inv_r2[:, 1:] = np.float64(1.0) / self.r2[:, 1:]
+        self.r2[:, 0] = np.nan
+
+    def __repr__(self):
+        return 'TrackStitcher(%s)' % ', '.join('%s=%r' % (n, getattr(self, n)) for n in (
+            'max_dt', 'min_dt', 'drift', 'max_speed', 'slack', 'min_rows', 'mode', 'max_size_ratio', 'gap_penalty'))
+
+
+class StitchedTracks:
+    """What ``stitch_tracks`` returns for one sequence: ``ids[t]`` int64, the frame's IDs with every stitched track
+    under the ID of the first track of its chain; ``pairs`` int64 [stitches, 4] = (frame, detection, frame, detection)
+    of the tail row and the head row of every stitch (positions in the sequence's lists); ``links`` float32 [K, K] the
+    scores, tails on rows and heads on columns, tracks in the order of their first rows (NaN: no candidate);
+    ``objective`` the sum of the kept scores (NaN without tracks); ``info`` = {'tracks', 'stitches', 'rows_changed'}.
+    ``filled`` / ``smoothed``: set by ``SequencePipeline.run_global(stitch=)`` - the second ``fill_gaps`` /
+    ``smooth_tracks`` over the relabelled sequence - else None."""
+
+    def __init__(self, ids, pairs, links, objective, info):
+        self.ids, self.pairs, self.links, self.objective, self.info = ids, pairs, links, objective, info
+        self.filled = self.smoothed = None
+
+
+def _stitch_sequence(seq):
+    if isinstance(seq, dict):
+        unknown = set(seq) - set(STITCH_KEYS)
+        if unknown:
+            raise ValueError('stitch_tracks: unknown sequence entries %s' % sorted(unknown))
+        return tuple(seq.get(k) for k in STITCH_KEYS)
+    seq = tuple(seq)
+    if not 2 <= len(seq) <= len(STITCH_KEYS):
+        raise ValueError('stitch_tracks: a sequence is a dict or a tuple of %s' % (STITCH_KEYS,))
+    return seq + (None,) * (len(STITCH_KEYS) - len(seq))
+
+
+def pack_stitch(sequences, stitcher=None):
+    """The host side of ``stitch_tracks_batch`` before the launches: per sequence (frames, ids, frame_idx, velocity,
+    poses, calib) as ``stitch_tracks`` takes them (a tuple, or a dict with those keys) -> the tables of
+    mmmot_stitch_tracks.  Returns a dict: ``packed`` (the int32 block of torch_ops.stitch_layout), ``sizes``, the tables
+    by name (``det``, ``ids``, ``frame_start``, ``frame_no``, ``seq_start`` as for ``pack_fill``; ``vel`` fp32 [L, 4] or
+    None; ``xf0`` as for ``pack_smooth``; ``k_start`` and ``pairs``, the tracks per sequence counted here from the IDs;
+    ``r2`` / ``inv_r2``), ``stitcher`` and ``sequences``.  The velocities are given for every sequence of a call or for
+    none: a missing one would not be a zero velocity."""
+    from . import ego
+    stitcher = TrackStitcher() if stitcher is None else stitcher
+    if not isinstance(stitcher, TrackStitcher):
+        raise ValueError('stitch_tracks: stitcher must be a tracks.TrackStitcher, got %r' % (stitcher,))
+    seqs = [_stitch_sequence(s) for s in sequences]
+    tab, _, moving = sequence_tables([(f, i, n, None, p, c) for f, i, n, _, p, c in seqs], 'stitch_tracks')
+    L, F, S = len(tab['ids']), len(tab['frame_no']), len(seqs)
+    tab.update(vel=None, xf0=None, r2=stitcher.r2, inv_r2=stitcher.inv_r2)
+    with_vel = [q[3] is not None for q in seqs]
+    if any(with_vel):
+        if not all(with_vel):
+            raise ValueError('stitch_tracks: velocities are given for every sequence of a call or for none')
+        vel = np.zeros((L, 4), np.float32)
+        for s, (frames, _, _, velocity, _, _) in enumerate(seqs):
+            if len(velocity) != len(frames):
+                raise ValueError('stitch_tracks: sequence %d has %d frames but velocities of another length'
+                                 % (s, len(frames)))
+            for t, v in enumerate(velocity):
+                a, b = (int(x) for x in tab['frame_start'][tab['seq_start'][s] + t:][:2])
+                v = np.asarray(v, dtype=np.float64).reshape(b - a, -1) if b > a else np.zeros((0, 3))
+                if v.shape[1] < 3:
+                    raise ValueError('stitch_tracks: sequence %d, frame %d: a velocity is vx, vy, vz[, yaw rate] per '
+                                     'detection' % (s, t))
+                vel[a:b, 0:3] = v[:, 0:3]
+        tab['vel'] = vel
+    if any(moving):
+        xf0 = np.zeros((F, torch_ops.FILL_REC), np.float64)
+        xf0[:, 0:16] = xf0[:, 16:32] = np.eye(4).reshape(-1)
+        for s, (frames, _, _, _, poses, calib) in enumerate(seqs):
+            if not moving[s]:
+                continue
+            f0 = int(tab['seq_start'][s])
+            for p in range(1, len(frames)):  # frame 0 of a sequence keeps the identity
+                C, Ci, dyaw = ego.box_motion(poses[0], poses[p], calib)
+                xf0[f0 + p, 0:16], xf0[f0 + p, 16:32], xf0[f0 + p, 32] = C.reshape(-1), Ci.reshape(-1), dyaw
+        tab['xf0'] = xf0
+    K = []
+    for s in range(S):
+        a, b = (int(tab['frame_start'][f]) for f in tab['seq_start'][s:s + 2])
+        kept = tab['ids'][a:b]
+        K.append(len(np.unique(kept[kept >= 0])))
+    K = np.asarray(K, np.int64)
+    k_start = np.concatenate([[0], np.cumsum(K)])
+    link_off = np.concatenate([[0], np.cumsum(K * K)])
+    if 6 * k_start[-1] + link_off[-1] >= 2 ** 31:
+        raise ValueError('stitch_tracks: the link blocks of the call exceed 32-bit offsets')
+    tab['k_start'] = k_start.astype(np.int32)
+    tab['pairs'] = np.stack([K, K, 2 * k_start[:-1], link_off[:-1]], 1).astype(np.int32)
+    sizes = [L, F, S, int(k_start[-1]), int(link_off[-1]), int(K.max()), int(tab['xf0'] is not None),
+             int(tab['vel'] is not None), stitcher.min_dt, stitcher.max_dt, stitcher.min_rows,
+             torch_ops.STITCH_MODES[stitcher.mode]]
+    sizes += torch_ops.stitch_param_bits(stitcher.max_size_ratio, stitcher.gap_penalty)
+    inp, _, n_in, _ = torch_ops.stitch_layout(sizes)
+    packed = np.zeros(n_in, np.int32)
+    for name, (o, n) in inp.items():
+        if n:
+            packed[o:o + n] = np.ascontiguousarray(tab[name]).reshape(-1).view(np.int32)
+    return dict(tab, packed=packed, sizes=sizes, sequences=seqs, stitcher=stitcher)
+
+
+def unpack_stitch(p, block):
+    """The host side of ``stitch_tracks_batch`` behind the launches: ``p`` from ``pack_stitch``, ``block`` the host int32
+    block of mmmot::stitch_tracks -> one ``StitchedTracks`` per sequence; raises ``TrackingError`` naming the sequence
+    on a status word.  The inputs are not modified."""
+    o = torch_ops.sections(np.asarray(block), torch_ops.stitch_layout(p['sizes'])[1])
+    out_ids, nxt, info = o['out_ids'].astype(np.int64), o['next'].astype(np.int64), o['info'].reshape(-1, 4)
+    links, objective = o['links'].view(np.float32), o['objective']
+    for s, st in enumerate(info[:, 0]):
+        for bit, text in STITCH_STATUS:
+            if st & bit:
+                raise TrackingError('stitch_tracks: sequence %d: %s' % (s, text))
+    frame_start, seq_start = p['frame_start'].astype(np.int64), p['seq_start']
+    res = []
+    for s, (frames, _, _, _, _, _) in enumerate(p['sequences']):
+        f0, K, lo = int(seq_start[s]), int(p['pairs'][s, 0]), int(p['pairs'][s, 3])
+        a, b = int(frame_start[f0]), int(frame_start[int(seq_start[s + 1])])
+        ids = [out_ids[int(frame_start[f0 + t]):int(frame_start[f0 + t + 1])].copy() for t in range(len(frames))]
+        tails = a + np.flatnonzero(nxt[a:b] >= 0)
+        rows = np.stack([tails, nxt[tails]], 1).reshape(-1, 2)
+        frame_of = np.searchsorted(frame_start, rows, side='right') - 1  # empty frames share their start
+        pairs = np.stack([frame_of[:, 0] - f0, rows[:, 0] - frame_start[frame_of[:, 0]],
+                          frame_of[:, 1] - f0, rows[:, 1] - frame_start[frame_of[:, 1]]], 1).astype(np.int64)
+        res.append(StitchedTracks(ids, pairs, links[lo:lo + K * K].reshape(K, K).copy(), float(objective[s]),
+                                  {'tracks': int(info[s, 1]), 'stitches': int(info[s, 2]),
+                                   'rows_changed': int(info[s, 3])}))
+    return res
+
+
+def stitch_tracks_batch(sequences, stitcher=None, device='cuda'):
+    """``stitch_tracks`` for many sequences in ONE upload, ONE set of launches (mmmot_stitch_tracks: seven and the pair
+    solver's, whatever the sequences hold) and ONE copy back.  ``sequences``: per sequence the tuple (frames, ids[,
+    frame_idx, velocity, poses, calib]) or a dict with those keys.  Returns one ``StitchedTracks`` per sequence, bit for
+    bit what ``stitch_tracks`` returns for it alone."""
+    p = pack_stitch(sequences, stitcher)
+    host = torch.empty(len(p['packed']), dtype=torch.int32, pin_memory=True)
+    host.numpy()[:] = p['packed']
+    block = torch.ops.mmmot.stitch_tracks(host.to(device, non_blocking=True), p['sizes'])
+    return unpack_stitch(p, block.cpu().numpy())
+
+
+def stitch_tracks(frames, ids, frame_idx=None, velocity=None, poses=None, calib=None, stitcher=None, device='cuda'):
+    """The second level of an offline tracker: tracks that an occlusion longer than the solve's gap limit broke are
+    rejoined.  Every track of the sequence is one node; the tail of a track is matched to the head
+    of a later one, one to one and with the largest total score, when the constant-velocity prediction of one reaches
+    the other (``TrackStitcher``), and the later track takes the earlier one's ID.  ``frames`` / ``ids`` / ``frame_idx``
+    are what ``write_kitti_tracks`` takes; ``velocity``: ``SmoothedTracks.velocity`` (per frame [n, >= 3]: vx, vy, vz per
+    frame number in the frame's camera axes), or None: tracks are then compared as they stand; ``poses`` / ``calib`` as for
+    ``fill_gaps``: with a moving camera the comparison runs in the first frame's coordinates.  No appearance is
+    compared.  Returns a ``StitchedTracks``, whose ``ids`` go to ``write_kitti_tracks``, ``labels_from_tracks``,
+    ``fill_gaps`` and ``smooth_tracks`` as they are.  The inputs are not modified.  Raises ``TrackingError`` when an ID
+    occurs twice in a frame, the frame numbers do not increase or the sequence holds more than 512 tracks."""
+    return stitch_tracks_batch([(frames, ids, frame_idx, velocity, poses, calib)], stitcher, device)[0]

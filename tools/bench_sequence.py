@@ -36,6 +36,11 @@ HIP-event time of the operator call on resident blocks for all sequences at once
 of --solver-calls after one untimed round; the wall time of ``smooth_tracks_batch`` and of the NumPy restatement
 tests/smooth_ref.py on the same tables, whose block must equal the device's bit for bit.  Writes
 <out>/bench_sequence_smooth.json.
+--stitch measures the tracklet stitching alone (tracks.stitch_tracks_batch; no model is built) on the
+--smooth scene with every track cut into tracklets by holes of 9 .. 20 frames, filled and smoothed first so that the rows
+carry velocities: the operator on resident blocks as for --smooth, the wall time of ``stitch_tracks_batch`` and of the
+NumPy restatement tests/stitch_ref.py on the same tables, whose block must equal the device's bit for bit (the fp64
+objectives to 1e-9 relative).  Writes <out>/bench_sequence_stitch.json.
 --gate G measures the motion gate (run_global(max_gap=G, gate=MotionGate(--gate-speed, --gate-slack)), DESIGN section 11
 "motion gate") beside the same call with gate=None on the same feeds, interleaved: wall time of ``run_global``, the gap
 pairs forwarded and left out, the links gated; and the gate's two launches alone on the sequence's own tables (the
@@ -49,6 +54,7 @@ unrelated random boxes, so far more pairs are left out than in a real sequence. 
     python tools/bench_sequence.py --out <dir> --global-gap 1 2 3 4 [--frames 100] [--repeats 3] [--solver-calls 20]
     python tools/bench_sequence.py --out <dir> --fill [--fill-frames 8000] [--ego] [--solver-calls 20]
     python tools/bench_sequence.py --out <dir> --smooth [--fill-frames 8000] [--ego] [--solver-calls 20]
+    python tools/bench_sequence.py --out <dir> --stitch [--fill-frames 8000] [--ego] [--solver-calls 20]
     python tools/bench_sequence.py --out <dir> --gate 3 [--gate-speed 4.0] [--gate-slack 2.0] [--frames 100] [--ego]
 """
 import argparse
@@ -467,6 +473,103 @@ def bench_smooth(args):
     print(json.dumps(rec))
 
 
+def cut_tracks(seqs, seed=1):
+    """the sequences of ``fill_workload`` with every track cut into tracklets: about every 60 frames an object is hidden
+    for 9 .. 20 frames - longer than the 8 frames the sequence flow bridges - and comes back under a fresh ID"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for frames, ids, no, scores, poses, calib in seqs:
+        T, n = len(frames), 1 + max(int(i.max(initial=-1)) for i in ids)
+        hidden, label, fresh = np.zeros((T, n), bool), np.zeros((T, n), np.int64), n
+        for o in range(n):
+            t, cur = int(rng.integers(20, 60)), o
+            label[:, o] = o
+            while t < T:
+                h = int(rng.integers(9, 21))
+                hidden[t:t + h, o] = True
+                cur, fresh = fresh, fresh + 1
+                label[t + h:, o] = cur
+                t += h + int(rng.integers(40, 80))
+        nf, ni = [], []
+        for t, (d, fid) in enumerate(zip(frames, ids)):
+            keep = ~hidden[t, fid]
+            nf.append({k: np.asarray(v)[keep] for k, v in d.items()})
+            ni.append(label[t, fid[keep]])
+        out.append((nf, ni, no, scores, poses, calib))
+    return out
+
+
+def bench_stitch(args):
+    """the stitching operator for all sequences at once beside one call per sequence, and the host routes around them"""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import stitch_ref
+    from mmmot_amd import tracks
+    n_seq = 21
+    base = cut_tracks(fill_workload(n_seq, args.fill_frames, 0.1, args.ego))
+    filled = tracks.fill_gaps_batch(base, 7)
+    smoothed = tracks.smooth_tracks_batch([(f.frames, f.ids, None, [~m for m in f.filled], b[4], b[5])
+                                           for f, b in zip(filled, base)])
+    seqs = [(s.frames, s.ids, None, s.velocity, b[4], b[5]) for s, b in zip(smoothed, base)]
+    up = lambda p: (torch.from_numpy(p['packed']).cuda(), p['sizes'])
+    t0 = time.perf_counter()
+    p = tracks.pack_stitch(seqs)
+    pack_ms = 1e3 * (time.perf_counter() - t0)
+    batch, singles = up(p), [up(tracks.pack_stitch([s])) for s in seqs]
+    calls = {'batch': lambda: [torch.ops.mmmot.stitch_tracks(*batch)],
+             'singles': lambda: [torch.ops.mmmot.stitch_tracks(*b) for b in singles]}
+    ms, out = {k: [] for k in calls}, {}
+    for i in range(args.solver_calls + 1):  # the first round untimed
+        for name, call in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out[name] = call()
+            e1.record()
+            torch.cuda.synchronize()
+            if i:
+                ms[name].append(e0.elapsed_time(e1))
+    wall = []
+    for _ in range(4):  # the first untimed
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        stitched = tracks.stitch_tracks_batch(seqs)
+        wall.append(1e3 * (time.perf_counter() - t0))
+    print('device done, the restatement runs', flush=True)
+    k = p['stitcher']
+    t0 = time.perf_counter()
+    ref = stitch_ref.stitch(p['det'], p['ids'], p['frame_start'], p['frame_no'], p['seq_start'], p['vel'], p['xf0'],
+                            p['k_start'], p['pairs'], p['r2'], p['inv_r2'], k.min_dt, k.max_dt, k.min_rows,
+                            stitch_ref.MODES[k.mode], k.max_size_ratio, k.gap_penalty, max_k=p['sizes'][5],
+                            n_link=p['sizes'][4])
+    ref_ms = 1e3 * (time.perf_counter() - t0)
+    got, want = out['batch'][0].cpu().numpy(), stitch_ref.block_of(ref, p['sizes'])
+    S = p['sizes'][2]
+    if not np.array_equal(got[2 * S:], want[2 * S:]):  # behind the fp64 objectives, which are compared by value
+        raise SystemExit('the device block differs from the restatement')
+    obj = np.abs(got[:2 * S].view(np.float64) - ref['objective'])
+    if not (obj <= 1e-9 * np.abs(ref['objective'])).all():
+        raise SystemExit('the objectives differ from the restatement by %g' % obj.max())
+    info = [b.cpu().numpy()[-4:].tolist() for b in out['singles']]
+    if info != ref['info'].tolist() or [list(s.info.values()) for s in stitched] != [r[1:] for r in info]:
+        raise SystemExit('the single calls and the batch report different counters')
+    L, F = p['sizes'][0], p['sizes'][1]
+    K = np.diff(p['k_start'])
+    rec = {
+        'op_ms': {k: round(float(np.median(v)), 3) for k, v in ms.items()},
+        'op_ms_min_max': {k: [round(min(v), 3), round(max(v), 3)] for k, v in ms.items()},
+        'stitch_tracks_batch_wall_ms': round(float(np.median(wall[1:])), 1), 'pack_stitch_wall_ms': round(pack_ms, 1),
+        'numpy_restatement_wall_ms': round(ref_ms, 1), 'objective_difference': float(obj.max()),
+        'instance': '%d sequences, %d frames, %d rows: %d tracklets (%d .. %d a sequence), %d links with a score, %d '
+                    'stitches, %d rows relabelled'
+                    % (n_seq, F, L, int(K.sum()), int(K.min()), int(K.max()), int(np.isfinite(ref['links']).sum()),
+                       int(ref['info'][:, 2].sum()), int(ref['info'][:, 3].sum())),
+        'calls': args.solver_calls, 'ego': bool(args.ego), 'device': torch.cuda.get_device_name(0),
+    }
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, 'bench_sequence_stitch.json'), 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', required=True)
@@ -490,6 +593,9 @@ def main():
     ap.add_argument('--fill-frames', type=int, default=8000)
     ap.add_argument('--smooth', action='store_true',
                     help='time the track smoothing alone on the filled --fill scene: all sequences at once, one call each, NumPy')
+    ap.add_argument('--stitch', action='store_true',
+                    help='time the tracklet stitching alone on the --smooth scene with its tracks cut by holes longer than '
+                         '8 frames: all sequences at once, one call each, NumPy')
     ap.add_argument('--gate', type=int, default=None,
                     help='time run_global(max_gap=G) with and without a MotionGate, and the gate launches alone')
     ap.add_argument('--gate-speed', type=float, default=4.0, help='MotionGate(max_speed=), metres per frame')
@@ -499,6 +605,8 @@ def main():
         return bench_fill(args)
     if args.smooth:
         return bench_smooth(args)
+    if args.stitch:
+        return bench_stitch(args)
     assoc = args.associate or args.track
     kw = dict(associate=assoc, track=True) if args.track else dict(associate=assoc)
     if args.repeats < 3 or args.frames < 2:
